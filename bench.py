@@ -9,10 +9,13 @@ bucketed RCCL all-reduce of the clipped gradients.  Workload = BASELINE.json con
 `python bench.py --gpus N` starts the N rank processes itself (children are spawned before the parent touches a GPU;
 nothing is exec'ed); under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the convolution launches (MFMA-bound); `roofline_match`,
-`roofline_loss`, `roofline_detect` (score + decode + NMS) and `roofline_prep` are the HBM-bound stages; `m2` is the
-BASELINE metric's second half (anchor-match + NMS microseconds per image); `cfg5_anchors` runs the anchor-side kernels at
-BASELINE configs[4]'s 24 564 anchors; `cpu_baseline` is the oracle port timed on this host's cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`, the loss scalars of the last step); `--dump-outputs DIR` writes what the last timed step computed as .npy
+files (`dump_outputs`).  Everything else runs with `--full` only: `roofline` is for the convolution launches (MFMA-bound);
+`roofline_match`, `roofline_loss`, `roofline_detect` (score + decode + NMS) and `roofline_prep` are the HBM-bound stages; `m2`
+is the BASELINE metric's second half (anchor-match + NMS microseconds per image); `cfg5_anchors` runs the anchor-side kernels
+at BASELINE configs[4]'s 24 564 anchors; `cpu_baseline` is the oracle port timed on this host's cores;
+`config3_train_plus_eval` is the step with the NMS eval pass; `comm` (N > 1) is the gradient exchange.
 """
 import argparse
 import json
@@ -46,8 +49,11 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch (BASELINE config: 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-stage / roofline sections, the other BASELINE configs, the CPU baseline and (N > 1) comm")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-stage / roofline sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -147,6 +153,34 @@ def nms_inputs(torch, B, A, dtype, seed=7, n_hot=320):
     return conf.to(dtype).contiguous(), loc.to(dtype).contiguous()
 
 
+# --dump-outputs: an array above its cap is written as a fixed, seeded sample of its flattened elements (sorted positions),
+# so that the files stay under 64 MB at any batch (14 Mi float32 elements at most)
+DUMP_CAPS = (("pred_conf", 1 << 21), ("pred_loc", 1 << 22), ("params", 1 << 21), ("target_cls", 1 << 20),
+             ("target_loc", 1 << 22), ("target_mask", 1 << 20))
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(np, torch, outdir, conf, loc, info, param, targets):
+    """What the last timed step handed its caller, as outdir/<name>.npy: the logits (pred_conf, pred_loc), the loss scalars
+    (loss: loc loss, cls loss pos, cls loss neg, status; float64), the parameters after its update (params) and the anchor
+    targets it matched (target_cls, target_loc, target_mask); float32 unless stated.  The same arguments give the same
+    inputs and the same sample positions, so two builds compare file for file."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"loss": np.array([float(info[k]) for k in ("loc loss", "cls loss pos", "cls loss neg", "status")], np.float64)}
+    tensors = {"pred_conf": conf, "pred_loc": loc, "params": param,
+               "target_cls": targets[0], "target_loc": targets[1], "target_mask": targets[2]}
+    for seed, (name, cap) in enumerate(DUMP_CAPS):
+        t = tensors[name]
+        if t.numel() > cap:
+            pos = np.unique(np.random.default_rng(seed).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return arrays
+
+
 def run_rank(args):
     if os.environ.get("SSD_BENCH_WATCHDOG"):             # development: dump every thread's stack and exit after N seconds
         import faulthandler
@@ -235,11 +269,15 @@ def run_rank(args):
             dt = float(t.item())
         return dt
 
+    if step_stream is not None:
+        step_stream.wait_stream(torch.cuda.current_stream())     # weights, batches and xbuf were made on the default stream
     for i in range(args.warmup):
         step(i)
-    if world > 1 and model._reducer is not None:
-        model._reducer.profile = True           # two events per bucket on the communication stream
+    if args.full and world > 1 and model._reducer is not None:
+        model._reducer.profile = True           # two events per bucket on the communication stream (read by comm_report)
     elapsed = timed_steps(args.steps)
+    if rank == 0 and args.dump_outputs:         # before any --full section reuses the step's buffers
+        dump_outputs(np, torch, args.dump_outputs, last["conf"], last["loc"], model.last_info, eng.param, match_out)
     status = float(model.last_info["status"])
     loss_vals = {k: float(model.last_info[k]) for k in ("loc loss", "cls loss pos", "cls loss neg")}
 
@@ -262,17 +300,17 @@ def run_rank(args):
                                      "note": "executed = dense network minus the head gradients' products with all-zero rows"}
     result["frac_of_conv_gemm_roofline"] = round(flops_step / B * value / (world * PEAK_BF16_TFLOPS * 1e12), 4)
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         result["config3_train_plus_eval"] = train_plus_eval(torch, ops, model, pset, B, step, last, timed_steps, args)
 
-    if world > 1:
+    if args.full and world > 1:
         result["comm"] = comm_report(torch, dist, model, backend, world, elapsed / args.steps, timed_steps,
                                      min(args.steps, 10), args.warmup + args.steps)
 
-    if rank == 0 and not args.no_kernel_timing:
+    if args.full and rank == 0 and not args.no_kernel_timing:
         kernel_sections(np, torch, ops, model, eng, pset, batches, match_out, B, result, step)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(np, torch)
 
     if rank == 0:

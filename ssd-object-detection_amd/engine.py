@@ -608,7 +608,15 @@ class SSDEngine:
                         ev2.record(self._red_active)
                     deferred.append((t0, t1, ev, ev2))
                     return
-                on_side(lambda ws: self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"]), [], join=True)
+                # the heads' update rewrites head_w_t, which the large levels' sparse data gradients on the third stream still
+                # read: behind their events as well as behind the main stream
+                readers = list(sparse_head_done.values()) if node is None else []
+
+                def run(ws):
+                    for e in readers:
+                        torch.cuda.current_stream().wait_event(e)
+                    self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
+                on_side(run, [], join=True)
 
         side2 = None
         # (not with a gradient exchange attached: its bucket launch records ONE event on the stream of the bucket's last tensor,

@@ -411,3 +411,38 @@ def test_train_step_at_batch_64():
         assert torch.equal(u, v)
     delta = (a.param - SSDObjectDetectionModel(classes=80, log_dir="gpurun_out/t64", timestamp_dir=False, seed=2).get_engine().param)
     assert 0 < float(delta.abs().max()) < 2e-3                    # Adam's first step: ~lr per touched weight
+
+
+def test_train_steps_are_bitwise_reproducible(tmp_path):
+    """Twenty batch-64 steps as bench.py's loop issues them (targets on the side stream, two batches cycled), but from the
+    default stream, so that every step hands over to the model's step stream and back; run twice from the same seed, the
+    weights and both Adam moments agree bit for bit.  (The heads' per-bucket update once rewrote the heads' transposed weights
+    before the large levels' sparse data gradients on the third stream had read them: runs parted after a dozen steps.)"""
+    from ssd_object_detection_amd import ops, optimizers
+    from ssd_object_detection_amd.data_loaders.synthetic import synth_batch_gt
+    from ssd_object_detection_amd.models import SSDObjectDetectionModel
+    B = 64
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    batches = []
+    for i in range(2):
+        img = torch.rand((B, 300, 300, 3), generator=gen, device="cuda")
+        cls_l, box_l = synth_batch_gt(i * B, B)
+        batches.append((img, ops.pack_gt(box_l, cls_l)))
+
+    def run():
+        model = SSDObjectDetectionModel(classes=80, log_dir=str(tmp_path), timestamp_dir=False, seed=0)
+        opt = optimizers.Adam(optimizers.ExponentialDecay(1e-3, 100, 0.99), beta_1=0.9, beta_2=0.999, epsilon=1e-7)
+        xbuf = torch.empty((B, 300, 300, 8), dtype=torch.bfloat16, device="cuda")
+        tgt = None
+        torch.cuda.synchronize()
+        for i in range(20):
+            img, gt = batches[i % 2]
+            tgt = model.match_async(gt, out=tgt)
+            model._train_step(ops.image_prep(img, normalize=True, out=xbuf), *tgt, opt)
+        torch.cuda.synchronize()
+        eng = model.get_engine()
+        return [t.clone() for t in (eng.param, eng.adam_m, eng.adam_v)]
+
+    a, b = run(), run()
+    for name, x, y in zip(("param", "adam_m", "adam_v"), a, b):
+        assert torch.equal(x, y), name
