@@ -345,6 +345,25 @@ int ssd_maxpool2x2_bwd_argmax(const void* code, const void* dy, void* dx, int B,
 int ssd_quantize_mx_fp8(const void* x_bf16, void* q, void* scale, long long n, void* stream);
 int ssd_conv3x3_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias, void* y, int B,
                           int H, int W, int Cin, int Cout, int relu, void* stream);
+/* The general MX-fp8 forward convolution of the ResNet-50 trunk's fp8 forward (BASELINE configs[4]; resnet_engine.py,
+ * precision="mxfp8"): every trunk layer with Cin % 128 == 0 except the stem, fed directly by the layer before it.
+ *   ssd_conv2d_fwd_mxfp8    relu?(conv of x with w + bias), k x k filters (k = 1 or 3), stride 1 or 2, explicit top / left pads
+ *                           (TF-SAME: ssd_conv2d_fwd's), output [B,Ho,Wo,Cout].  x8 [B,H,W,Cin] / xscale [B,H,W,Cin/32],
+ *                           w8 [Cout][k][k][Cin] / wscale [Cout][k][k][Cin/32] as ssd_quantize_mx_fp8 makes them; fp32 accumulation.
+ *                           Outputs, any non-empty subset (null = not written): y_bf16 bf16 [B,Ho,Wo,Cout] (bias, ReLU, one
+ *                           rounding); y8 u8 [B,Ho,Wo,Cout] + yscale u8 [B,Ho,Wo,Cout/32], given together: ssd_quantize_mx_fp8 of
+ *                           that bf16 result, bit for bit, computed in the epilogue.  At k = 3, stride 1, pads 1 the bf16 output
+ *                           equals ssd_conv3x3_fwd_mxfp8's.  SSD_ERR_VALUE: no output, y8 without yscale (or the reverse), bad
+ *                           dimensions; SSD_ERR_UNSUPPORTED: Cin % 128, k not in {1, 3}, stride not in {1, 2}, Cout % 8, Cout % 32
+ *                           with y8, an operand or output of 2^31 bytes or more.
+ *   ssd_add_relu_fwd_mxfp8  out_bf16 = relu(a + b) (ssd_add_relu_fwd's result) and q u8 [n] / scale u8 [n/32] = its
+ *                           ssd_quantize_mx_fp8, in one pass (a residual add feeding both bf16 and fp8 layers); n % 32 == 0,
+ *                           blocks of 32 consecutive elements (= the per-pixel channel blocks when C % 32 == 0); SSD_ERR_VALUE
+ *                           otherwise or for a null pointer */
+int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias, void* y_bf16,
+                         void* y8, void* yscale, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad_t, int pad_l,
+                         int Ho, int Wo, int relu, void* stream);
+int ssd_add_relu_fwd_mxfp8(const void* a, const void* b, void* out_bf16, void* q, void* scale, long long n, void* stream);
 /* A chain of small convolutions in ONE launch, one workgroup per image, activations in LDS (chain.hip) -- the reference's
  * "extras" behind the 19x19 map (models/ssd_model.py:124-150: six layers on 10x10 ... 1x1 maps), forward or data gradient.
  * Layer l reads the output of layer l-1 (layer 0: in0 [B][Hi*Wi][Kc] bf16) and writes out [B][Ho*Wo][N] bf16:

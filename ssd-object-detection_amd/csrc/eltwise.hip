@@ -4,6 +4,7 @@
 // tape.gradient).  All HBM-bound streams, 16 bytes per lane.
 #include "common.h"
 #include <hip/hip_bf16.h>
+#include "mxfp8.h"
 
 namespace {
 
@@ -31,6 +32,38 @@ __global__ __launch_bounds__(256) void k_add_relu(const uint4* __restrict__ a, c
             r[k] = pack2(lo, hi);
         }
         out[i] = make_uint4(r[0], r[1], r[2], r[3]);
+    }
+}
+
+// out = relu(a + b) as k_add_relu, plus its MX-fp8 form (q, scale) in the same pass, quantised from the bf16-rounded sums by
+// the rule of k_quant_mx_fp8 (mxfp8.h): bitwise k_add_relu followed by the separate quantiser.  16 bytes per lane as k_add_relu;
+// a 32-element block is four neighbouring lanes (nvec % 4 == 0 and 256 threads per block: a group is in or out of the loop
+// together), its amax two xor shuffles.
+__global__ __launch_bounds__(256) void k_add_relu_mxfp8(const uint4* __restrict__ a, const uint4* __restrict__ b, uint4* __restrict__ out,
+                                                        uint2* __restrict__ q, unsigned char* __restrict__ scale, long long nvec) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
+        const uint4 x = a[i], y = b[i];
+        const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
+        unsigned r[4];
+        float v[8];
+        float amax = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float lo = fmaxf(bf2f_(xs[k] & 0xffffu) + bf2f_(ys[k] & 0xffffu), 0.f);
+            const float hi = fmaxf(bf2f_(xs[k] >> 16) + bf2f_(ys[k] >> 16), 0.f);
+            r[k] = pack2(lo, hi);
+            v[2 * k] = __uint_as_float(r[k] << 16);
+            v[2 * k + 1] = __uint_as_float(r[k] & 0xffff0000u);
+        }
+        out[i] = make_uint4(r[0], r[1], r[2], r[3]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+        amax = fmaxf(amax, __shfl_xor(amax, 1));
+        amax = fmaxf(amax, __shfl_xor(amax, 2));
+        const int e = mx_block_exp(amax);
+        const float inv = ldexpf(1.f, -e);
+        q[i] = make_uint2(mx_pack4(v[0], v[1], v[2], v[3], inv), mx_pack4(v[4], v[5], v[6], v[7], inv));
+        if ((i & 3) == 0) scale[i >> 2] = (unsigned char)(e + 127);
     }
 }
 
@@ -142,6 +175,14 @@ int ssd_add_relu_fwd(const void* a, const void* b, void* out, long long n, void*
     if (!a || !b || !out || n <= 0 || (n & 7)) return SSD_ERR_VALUE;
     hipLaunchKernelGGL(k_add_relu, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, static_cast<const uint4*>(a),
                        static_cast<const uint4*>(b), static_cast<uint4*>(out), n / 8);
+    return ssd_launch_status();
+}
+
+int ssd_add_relu_fwd_mxfp8(const void* a, const void* b, void* out_bf16, void* q, void* scale, long long n, void* stream) {
+    if (!a || !b || !out_bf16 || !q || !scale || n <= 0 || (n & 31)) return SSD_ERR_VALUE;
+    hipLaunchKernelGGL(k_add_relu_mxfp8, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, static_cast<const uint4*>(a),
+                       static_cast<const uint4*>(b), static_cast<uint4*>(out_bf16), static_cast<uint2*>(q),
+                       static_cast<unsigned char*>(scale), n / 8);
     return ssd_launch_status();
 }
 

@@ -13,9 +13,14 @@
 // Kernel = the 128 x 128 implicit GEMM of k_conv_igemm_dma (conv.hip) at one byte per element: a k-step is one tap x 128 channels
 // (rows of 128 B, LDS-DMA with the same XOR-swizzled image, two LDS buffers, one barrier per step), the scale bytes of a step
 // travel as 4-byte LDS-DMA pieces next to the tiles, one matrix instruction per 16 x 16 tile and step (bf16: two).
+//
+// k_conv_mxfp8 generalises that kernel to the ResNet-50 trunk's fp8 forward (resnet_engine.py, precision="mxfp8"): 1x1 and 3x3
+// filters, stride 1 and 2 with TF-SAME pads, and an epilogue that writes the bf16 map, its MX-fp8 form (quantised in registers,
+// bitwise ssd_quantize_mx_fp8 of that bf16 map) or both -- so the next fp8 layer is fed without a separate quantisation pass.
 #include "common.h"
 #include <hip/hip_bf16.h>
 #include "conv_common.h"
+#include "mxfp8.h"
 
 namespace {
 
@@ -199,7 +204,212 @@ __global__ __launch_bounds__(256) void k_conv3x3_mxfp8(const unsigned char* __re
     conv_epilogue_rows<EPI_FWD, 4, 4>(acc, g, ep, mrow, n0 + wave_n * 64, lane);
 }
 
+// Outputs of k_conv_mxfp8: any non-empty subset of a bf16 map and its MX-fp8 form.
+struct MxOut {
+    const float* bias;                       // [N] or null
+    int relu;
+    bf16_raw* y;                             // [M][N] bf16 or null
+    unsigned char* q;                        // [M][N] e4m3 or null (then qs is null too); N % 32 == 0
+    unsigned char* qs;                       // [M][N/32] E8M0
+};
+
+// The general MX-fp8 forward convolution: KS x KS filters (1 or 3), stride g.mul (1 or 2), TF-SAME pads g.pad_t / g.pad_l.  The
+// main loop is k_conv3x3_mxfp8's (same staging, same k-step order tap-major, so the 3x3 / stride-1 result is bitwise the same).
+// Epilogue: bias, ReLU, ONE bf16 rounding; then, for the fp8 output, the rule of k_quant_mx_fp8 on the rounded values.  A lane
+// holds channels n + 4 gq .. +3 of one pixel per 16 x 16 tile, so a 32-channel block is tiles 2 cp and 2 cp + 1 of the lanes
+// li, li + 16, li + 32, li + 48: the block amax is the lane's 8 values reduced over the four lane groups (two xor shuffles).
+template <int KS>
+__global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restrict__ x, const unsigned char* __restrict__ xs,
+                                                    const unsigned char* __restrict__ w, const unsigned char* __restrict__ wsc,
+                                                    ConvGeom g, MxOut ep) {
+    // g: x [B,H,W,C] bytes, C % 128 == 0; w [N][KS][KS][C] bytes; xs [B*H*W][C/32], wsc [N][KS][KS][C/32] scale bytes
+    constexpr int KK = KS * KS;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave_m = wave & 1, wave_n = wave >> 1;
+    const int ntn = (g.N + 127) / 128;
+    const int mt = blockIdx.x / ntn, n0 = (blockIdx.x % ntn) * 128, m0 = mt * 128;
+    const int cb = g.C >> 5;
+    const int csteps = g.C >> 7;
+    const int stride = g.mul;
+    const unsigned xbytes = (unsigned)g.B * (unsigned)g.H * (unsigned)g.W * (unsigned)g.C;     // < 2^31 (host check)
+
+    const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wres = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, (unsigned)g.N * (unsigned)KK * (unsigned)g.C, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xsres = __builtin_amdgcn_make_buffer_rsrc((void*)xs, 0, xbytes >> 5, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wsres = __builtin_amdgcn_make_buffer_rsrc((void*)wsc, 0, (unsigned)g.N * (unsigned)KK * (unsigned)cb, 0x00020000);
+    constexpr unsigned OOB = 0xfffffff0u;
+
+    // rows as in k_conv3x3_mxfp8; py / px = top-left input coordinate of the output pixel's window (py < 0 far off: beyond M)
+    int py[4], px[4], pb[4];
+    unsigned wrow[4], cchunk[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = wave + 4 * j;
+        const int r = 8 * i + 2 * (lane >> 4) + ((lane >> 3) & 1);
+        cchunk[j] = (unsigned)((lane & 7) ^ ((4 * i + (lane >> 4)) & 7)) * 16u;
+        const int m = m0 + r;
+        const bool mv = m < g.M;
+        const int mm = mv ? m : 0;
+        const int b = fdiv(mm, g.d_hw);
+        const int rem = mm - b * g.d_hw.d;
+        const int oy = fdiv(rem, g.d_w);
+        py[j] = mv ? oy * stride - g.pad_t : -(1 << 20);
+        px[j] = (rem - oy * g.d_w.d) * stride - g.pad_l;
+        pb[j] = b * g.H * g.W;
+        const int n = n0 + r;
+        wrow[j] = n < g.N ? (unsigned)n * (unsigned)KK * (unsigned)g.C : 0xffffffffu;
+    }
+    const int srow = (wave & 1) * 64 + lane;
+    int sy = 0, sx = 0, sb = 0;
+    unsigned swrow = 0xffffffffu;
+    if (wave < 2) {
+        const int m = m0 + srow;
+        const bool mv = m < g.M;
+        const int mm = mv ? m : 0;
+        const int b = fdiv(mm, g.d_hw);
+        const int rem = mm - b * g.d_hw.d;
+        const int oy = fdiv(rem, g.d_w);
+        sy = mv ? oy * stride - g.pad_t : -(1 << 20);
+        sx = (rem - oy * g.d_w.d) * stride - g.pad_l;
+        sb = b * g.H * g.W;
+    } else {
+        const int n = n0 + srow;
+        swrow = n < g.N ? (unsigned)n * (unsigned)KK * (unsigned)cb : 0xffffffffu;
+    }
+    auto issue = [&](int step, int buf) {
+        const int tap = step / csteps, cs = step - tap * csteps;
+        const int kh = tap / KS, kw = tap % KS;
+        char* base = smem + buf * F8_BUF;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = wave + 4 * j;
+            const int iy = py[j] + kh, ix = px[j] + kw;
+            const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
+            const unsigned off = (unsigned)(pb[j] + iy * g.W + ix) * (unsigned)g.C + (unsigned)cs * 128u + cchunk[j];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_void*)(base + i * 1024), 16, ok ? off : OOB, 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = wave + 4 * j;
+            const unsigned off = wrow[j] + (unsigned)tap * (unsigned)g.C + (unsigned)cs * 128u + cchunk[j];
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wres, (lds_void*)(base + F8_TILE + i * 1024), 16, wrow[j] != 0xffffffffu ? off : OOB, 0, 0, 0);
+        }
+        if (wave < 2) {
+            const int iy = sy + kh, ix = sx + kw;
+            const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
+            const unsigned off = (unsigned)(sb + iy * g.W + ix) * (unsigned)cb + (unsigned)cs * 4u;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xsres, (lds_void*)(base + 2 * F8_TILE + wave * 256), 4, ok ? off : OOB, 0, 0, 0);
+        } else {
+            const unsigned off = swrow + (unsigned)tap * (unsigned)cb + (unsigned)cs * 4u;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wsres, (lds_void*)(base + 2 * F8_TILE + 512 + (wave - 2) * 256), 4, swrow != 0xffffffffu ? off : OOB, 0, 0, 0);
+        }
+    };
+
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) acc[c][p] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const int nsteps = KK * csteps;
+    const int gq = lane >> 4, li = lane & 15;
+    issue(0, 0);
+    for (int st = 0; st < nsteps; ++st) {
+        const int cur = st & 1;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (st + 1 < nsteps) issue(st + 1, cur ^ 1);
+        const char* base = smem + cur * F8_BUF;
+        v8i fx[4], fw[4];
+        int sxv[4], swv[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int row = wave_m * 64 + p * 16 + li;
+            const uint4 lo = lds_ld16_scoped(base + swz(row, gq), smem), hi = lds_ld16_scoped(base + swz(row, 4 + gq), smem);
+            fx[p] = v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+            sxv[p] = (int)(f8_ld4(base + 2 * F8_TILE + row * 4, smem) >> (8 * gq));
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int row = wave_n * 64 + c * 16 + li;
+            const uint4 lo = lds_ld16_scoped(base + F8_TILE + swz(row, gq), smem), hi = lds_ld16_scoped(base + F8_TILE + swz(row, 4 + gq), smem);
+            fw[c] = v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+            swv[c] = (int)(f8_ld4(base + 2 * F8_TILE + 512 + row * 4, smem) >> (8 * gq));
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                acc[c][p] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[c], fx[p], acc[c][p], 0, 0, 0, swv[c], 0, sxv[p]);
+    }
+
+    // epilogue: per pixel tile p and channel block cp (tiles 2 cp, 2 cp + 1); the block test is wave-uniform, so every lane
+    // of the wave takes part in the shuffles (lanes beyond M compute and discard)
+    const int ldq = g.N >> 5;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int m = m0 + wave_m * 64 + p * 16 + li;
+        const bool mv = m < g.M;
+#pragma unroll
+        for (int cp = 0; cp < 2; ++cp) {
+            const int nblk = n0 + wave_n * 64 + cp * 32;
+            if (nblk >= g.N) continue;
+            float v[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int n = nblk + h * 16 + gq * 4;
+                float b4[4] = {0.f, 0.f, 0.f, 0.f};
+                if (ep.bias) {
+                    if (n + 3 < g.N) {
+                        const float4 bv = *reinterpret_cast<const float4*>(ep.bias + n);
+                        b4[0] = bv.x; b4[1] = bv.y; b4[2] = bv.z; b4[3] = bv.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (n + j < g.N) b4[j] = ep.bias[n + j];
+                    }
+                }
+                float t[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    t[j] = acc[2 * cp + h][p][j] + b4[j];
+                    if (ep.relu) t[j] = fmaxf(t[j], 0.f);
+                }
+                const unsigned lo = pack_bf16x2(t[0], t[1]), hi = pack_bf16x2(t[2], t[3]);
+                v[4 * h] = __uint_as_float(lo << 16); v[4 * h + 1] = __uint_as_float(lo & 0xffff0000u);
+                v[4 * h + 2] = __uint_as_float(hi << 16); v[4 * h + 3] = __uint_as_float(hi & 0xffff0000u);
+                if (ep.y && mv && n < g.N) {
+                    bf16_raw* o = ep.y + (long long)m * g.N + n;
+                    if (n + 3 < g.N) {
+                        *reinterpret_cast<uint2*>(o) = make_uint2(lo, hi);
+                    } else {
+                        const bf16_raw e4[4] = {(bf16_raw)(lo & 0xffffu), (bf16_raw)(lo >> 16), (bf16_raw)(hi & 0xffffu), (bf16_raw)(hi >> 16)};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (n + j < g.N) o[j] = e4[j];
+                    }
+                }
+            }
+            if (ep.q) {                                       // N % 32 == 0: the whole block lies inside N
+                float amax = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+                amax = fmaxf(amax, __shfl_xor(amax, 16));
+                amax = fmaxf(amax, __shfl_xor(amax, 32));
+                const int e = mx_block_exp(amax);
+                const float inv = ldexpf(1.f, -e);
+                if (mv) {
+                    unsigned char* o = ep.q + (long long)m * g.N + nblk + gq * 4;
+                    *reinterpret_cast<unsigned*>(o) = mx_pack4(v[0], v[1], v[2], v[3], inv);
+                    *reinterpret_cast<unsigned*>(o + 16) = mx_pack4(v[4], v[5], v[6], v[7], inv);
+                    if (gq == 0) ep.qs[(long long)m * ldq + (nblk >> 5)] = (unsigned char)(e + 127);
+                }
+            }
+        }
+    }
+}
+
 OnceLds g_f8_once;
+OnceLds g_f8g_once[2];
 
 }  // namespace
 
@@ -227,6 +437,35 @@ int ssd_conv3x3_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, co
     hipLaunchKernelGGL(k_conv3x3_mxfp8, dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, static_cast<const unsigned char*>(x8),
                        static_cast<const unsigned char*>(xscale), static_cast<const unsigned char*>(w8),
                        static_cast<const unsigned char*>(wscale), g, ep);
+    return ssd_launch_status();
+}
+
+int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias, void* y_bf16,
+                         void* y8, void* yscale, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad_t, int pad_l,
+                         int Ho, int Wo, int relu, void* stream) {
+    if (!x8 || !xscale || !w8 || !wscale) return SSD_ERR_VALUE;
+    if ((!y_bf16 && !y8) || (!y8 != !yscale)) return SSD_ERR_VALUE;             // no output, or q without its scales
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || pad_t < 0 || pad_l < 0) return SSD_ERR_VALUE;
+    if (Cin % 128 || (k != 1 && k != 3) || (stride != 1 && stride != 2) || Cout % 8 || (y8 && Cout % 32)) return SSD_ERR_UNSUPPORTED;
+    if (pad_t >= k || pad_l >= k || (Ho - 1) * stride - pad_t >= H || (Wo - 1) * stride - pad_l >= W) return SSD_ERR_VALUE;
+    if ((long long)B * H * W * Cin >= (1ll << 31) || (long long)Cout * k * k * Cin >= (1ll << 31) ||
+        (long long)B * Ho * Wo * Cout * 2 >= (1ll << 31))
+        return SSD_ERR_UNSUPPORTED;
+    const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, k, k, stride, 1, pad_t, pad_l);
+    MxOut ep = {};
+    ep.bias = bias; ep.relu = relu; ep.y = static_cast<bf16_raw*>(y_bf16);
+    ep.q = static_cast<unsigned char*>(y8); ep.qs = static_cast<unsigned char*>(yscale);
+    const void* fn = k == 1 ? reinterpret_cast<const void*>(k_conv_mxfp8<1>) : reinterpret_cast<const void*>(k_conv_mxfp8<3>);
+    if (ensure_lds(g_f8g_once[k == 1 ? 0 : 1], fn, F8_LDS) != 0) return SSD_ERR_LAUNCH;
+    const unsigned grid = (unsigned)(((g.M + 127) / 128) * ((Cout + 127) / 128));
+    const auto* xp = static_cast<const unsigned char*>(x8);
+    const auto* xsp = static_cast<const unsigned char*>(xscale);
+    const auto* wp = static_cast<const unsigned char*>(w8);
+    const auto* wsp = static_cast<const unsigned char*>(wscale);
+    if (k == 1)
+        hipLaunchKernelGGL(k_conv_mxfp8<1>, dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
+    else
+        hipLaunchKernelGGL(k_conv_mxfp8<3>, dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
     return ssd_launch_status();
 }
 

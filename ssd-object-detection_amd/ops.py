@@ -755,13 +755,16 @@ def maxpool2x2_bwd(x, y, dy, out=None):
     return out
 
 
-def quantize_mx_fp8(x):
+def quantize_mx_fp8(x, q=None, scale=None):
     """bf16 tensor (last dimension a multiple of 32) -> (q uint8 same shape: OCP e4m3 bytes, scale uint8 [..., C/32]: E8M0)."""
     L = _lib.lib()
     _bf(x)
     assert x.shape[-1] % 32 == 0
-    q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    scale = torch.empty(x.shape[:-1] + (x.shape[-1] // 32,), dtype=torch.uint8, device=x.device)
+    if q is None:
+        q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if scale is None:
+        scale = torch.empty(x.shape[:-1] + (x.shape[-1] // 32,), dtype=torch.uint8, device=x.device)
+    assert q.numel() == x.numel() and scale.numel() == x.numel() // 32
     _lib.check(L.ssd_quantize_mx_fp8(_ptr(x), _ptr(q), _ptr(scale), x.numel(), _stream()))
     return q, scale
 
@@ -789,6 +792,55 @@ def conv3x3_fwd_mxfp8(xq, xs, wq, ws, bias, relu=True, out=None):
         raise NotImplementedError("block-scaled fp8 forward needs Cin % 128 == 0")
     _lib.check(rc)
     return out
+
+
+def conv2d_fwd_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, want_bf16=True, want_fp8=False, out=None,
+                     out_q=None, out_scale=None):
+    """k x k (1 or 3) / stride 1 or 2 forward on block-scaled fp8 operands (quantize_mx_fp8 of x [B,H,W,Cin] and w
+    [Cout,k,k,Cin]), TF-SAME pads as conv2d_fwd.  Returns the outputs asked for: the bf16 map, (q, scale) = its
+    quantize_mx_fp8, or (bf16, q, scale) when both are wanted."""
+    L = _lib.lib()
+    B, H, W, Cin = xq.shape
+    Cout, k = wq.shape[0], wq.shape[1]
+    assert want_bf16 or want_fp8
+    assert wq.shape == (Cout, k, k, Cin) and xs.shape == (B, H, W, Cin // 32) and ws.shape == (Cout, k, k, Cin // 32)
+    for t in (xq, xs, wq, ws):
+        _dev(t, torch.uint8)
+    if want_bf16 and out is None:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=xq.device)
+    if want_fp8:
+        if out_q is None:
+            out_q = torch.empty((B, Ho, Wo, Cout), dtype=torch.uint8, device=xq.device)
+        if out_scale is None:
+            out_scale = torch.empty((B, Ho, Wo, max(Cout // 32, 1)), dtype=torch.uint8, device=xq.device)
+    rc = L.ssd_conv2d_fwd_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
+                                _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout, k,
+                                stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError("block-scaled fp8 forward needs Cin % 128 == 0, k in (1, 3), stride in (1, 2), Cout % 8 == 0 "
+                                  "and Cout % 32 == 0 for an fp8 output")
+    _lib.check(rc)
+    if want_bf16 and want_fp8:
+        return out, out_q, out_scale
+    return out if want_bf16 else (out_q, out_scale)
+
+
+def add_relu_fwd_mxfp8(a, b, out=None, q=None, scale=None):
+    """(out, q, scale): out = relu(a + b) exactly as add_relu_fwd, (q, scale) = quantize_mx_fp8(out), in one pass."""
+    L = _lib.lib()
+    _bf(a); _bf(b)
+    assert a.shape == b.shape and a.shape[-1] % 32 == 0
+    if out is None:
+        out = torch.empty_like(a)
+    if q is None:
+        q = torch.empty(a.shape, dtype=torch.uint8, device=a.device)
+    if scale is None:
+        scale = torch.empty(a.shape[:-1] + (a.shape[-1] // 32,), dtype=torch.uint8, device=a.device)
+    rc = L.ssd_add_relu_fwd_mxfp8(_ptr(a), _ptr(b), _ptr(out), _ptr(q), _ptr(scale), a.numel(), _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError("add_relu_fwd_mxfp8")
+    _lib.check(rc)
+    return out, q, scale
 
 
 def add_relu_fwd(a, b, out=None):
