@@ -364,6 +364,21 @@ int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, con
                          void* y8, void* yscale, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad_t, int pad_l,
                          int Ho, int Wo, int relu, void* stream);
 int ssd_add_relu_fwd_mxfp8(const void* a, const void* b, void* out_bf16, void* q, void* scale, long long n, void* stream);
+/* The stride-1 data gradients of the ResNet-50 trunk after a training-mode fp8 forward (resnet_engine.py, mxfp8_bwd_plan):
+ *   ssd_conv2d_bwd_data_mxfp8  dx[B,H,W,Cin] = ssd_conv2d_bwd_data's result at stride 1 on block-scaled fp8 operands -- dy8
+ *                           [B,Ho,Wo,Cout] / dyscale [B,Ho,Wo,Cout/32] and wt8 [Cin][k][k][Cout] / wtscale [Cin][k][k][Cout/32],
+ *                           ssd_quantize_mx_fp8 of dy and of ssd_weight_transpose's w_t; k = 1 or 3, pad_t / pad_l the FORWARD
+ *                           pads (mirrored inside); fp32 accumulation.  Epilogue in ssd_conv2d_bwd_data's order: accumulate != 0:
+ *                           + the bf16 dx already there; then zero where relu_src <= 0 (relu_src bf16 [B,H,W,Cin] or null); ONE
+ *                           bf16 rounding.  Outputs, any non-empty subset: dx_bf16 bf16 [B,H,W,Cin]; dx8 u8 [B,H,W,Cin] + dxscale
+ *                           u8 [B,H,W,Cin/32], given together: ssd_quantize_mx_fp8 of that bf16 result, bit for bit.
+ *                           SSD_ERR_VALUE: a missing operand, no output, dx8 without dxscale (or the reverse), accumulate
+ *                           without dx_bf16, bad dimensions or pads; SSD_ERR_UNSUPPORTED (nothing launched): Cout % 128,
+ *                           Cin % 32, k not in {1, 3}, an operand or output of 2^31 bytes or more.  Stride-2 data gradients
+ *                           have no fp8 form: ssd_conv2d_bwd_data. */
+int ssd_conv2d_bwd_data_mxfp8(const void* dy8, const void* dyscale, const void* wt8, const void* wtscale, const void* relu_src,
+                              void* dx_bf16, void* dx8, void* dxscale, int B, int H, int W, int Cin, int Cout, int k, int pad_t,
+                              int pad_l, int Ho, int Wo, int accumulate, void* stream);
 /* A chain of small convolutions in ONE launch, one workgroup per image, activations in LDS (chain.hip) -- the reference's
  * "extras" behind the 19x19 map (models/ssd_model.py:124-150: six layers on 10x10 ... 1x1 maps), forward or data gradient.
  * Layer l reads the output of layer l-1 (layer 0: in0 [B][Hi*Wi][Kc] bf16) and writes out [B][Ho*Wo][N] bf16:

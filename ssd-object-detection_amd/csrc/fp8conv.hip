@@ -17,6 +17,8 @@
 // k_conv_mxfp8 generalises that kernel to the ResNet-50 trunk's fp8 forward (resnet_engine.py, precision="mxfp8"): 1x1 and 3x3
 // filters, stride 1 and 2 with TF-SAME pads, and an epilogue that writes the bf16 map, its MX-fp8 form (quantised in registers,
 // bitwise ssd_quantize_mx_fp8 of that bf16 map) or both -- so the next fp8 layer is fed without a separate quantisation pass.
+// Its data-gradient mode (DG) serves the trunk's stride-1 data gradients after a training-mode fp8 forward: the same main loop
+// on dy and the transposed filters, an epilogue with ssd_conv2d_bwd_data's accumulate and ReLU mask.
 #include "common.h"
 #include <hip/hip_bf16.h>
 #include "conv_common.h"
@@ -211,6 +213,8 @@ struct MxOut {
     bf16_raw* y;                             // [M][N] bf16 or null
     unsigned char* q;                        // [M][N] e4m3 or null (then qs is null too); N % 32 == 0
     unsigned char* qs;                       // [M][N/32] E8M0
+    const bf16_raw* mask;                    // DG: zero where mask <= 0 ([M][N] bf16, the forward activation), or null
+    int accumulate;                          // DG: y += result before the mask (y then holds the earlier gradient)
 };
 
 // The general MX-fp8 forward convolution: KS x KS filters (1 or 3), stride g.mul (1 or 2), TF-SAME pads g.pad_t / g.pad_l.  The
@@ -218,7 +222,9 @@ struct MxOut {
 // Epilogue: bias, ReLU, ONE bf16 rounding; then, for the fp8 output, the rule of k_quant_mx_fp8 on the rounded values.  A lane
 // holds channels n + 4 gq .. +3 of one pixel per 16 x 16 tile, so a 32-channel block is tiles 2 cp and 2 cp + 1 of the lanes
 // li, li + 16, li + 32, li + 48: the block amax is the lane's 8 values reduced over the four lane groups (two xor shuffles).
-template <int KS>
+// DG = the stride-1 data gradient (ssd_conv2d_bwd_data_mxfp8): x = dy, w = the transposed filters, pads k - 1 - pad; no bias or
+// ReLU, but y += result (accumulate) and then zero where mask <= 0, in ssd_conv2d_bwd_data's order, before the ONE rounding.
+template <int KS, bool DG>
 __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restrict__ x, const unsigned char* __restrict__ xs,
                                                     const unsigned char* __restrict__ w, const unsigned char* __restrict__ wsc,
                                                     ConvGeom g, MxOut ep) {
@@ -375,6 +381,20 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
                     t[j] = acc[2 * cp + h][p][j] + b4[j];
                     if (ep.relu) t[j] = fmaxf(t[j], 0.f);
                 }
+                if constexpr (DG) {                           // N % 32 == 0: n + 3 < N
+                    if (mv && ep.accumulate) {                // two gradients meet at this map
+                        const uint2 old = *reinterpret_cast<const uint2*>(ep.y + (long long)m * g.N + n);
+                        t[0] += __uint_as_float(old.x << 16); t[1] += __uint_as_float(old.x & 0xffff0000u);
+                        t[2] += __uint_as_float(old.y << 16); t[3] += __uint_as_float(old.y & 0xffff0000u);
+                    }
+                    if (mv && ep.mask) {                      // ReLU backward: zero where the forward activation was <= 0
+                        const uint2 mk = *reinterpret_cast<const uint2*>(ep.mask + (long long)m * g.N + n);
+                        if (!(__uint_as_float(mk.x << 16) > 0.f)) t[0] = 0.f;
+                        if (!(__uint_as_float(mk.x & 0xffff0000u) > 0.f)) t[1] = 0.f;
+                        if (!(__uint_as_float(mk.y << 16) > 0.f)) t[2] = 0.f;
+                        if (!(__uint_as_float(mk.y & 0xffff0000u) > 0.f)) t[3] = 0.f;
+                    }
+                }
                 const unsigned lo = pack_bf16x2(t[0], t[1]), hi = pack_bf16x2(t[2], t[3]);
                 v[4 * h] = __uint_as_float(lo << 16); v[4 * h + 1] = __uint_as_float(lo & 0xffff0000u);
                 v[4 * h + 2] = __uint_as_float(hi << 16); v[4 * h + 3] = __uint_as_float(hi & 0xffff0000u);
@@ -410,6 +430,7 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
 
 OnceLds g_f8_once;
 OnceLds g_f8g_once[2];
+OnceLds g_f8d_once[2];
 
 }  // namespace
 
@@ -455,7 +476,7 @@ int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, con
     MxOut ep = {};
     ep.bias = bias; ep.relu = relu; ep.y = static_cast<bf16_raw*>(y_bf16);
     ep.q = static_cast<unsigned char*>(y8); ep.qs = static_cast<unsigned char*>(yscale);
-    const void* fn = k == 1 ? reinterpret_cast<const void*>(k_conv_mxfp8<1>) : reinterpret_cast<const void*>(k_conv_mxfp8<3>);
+    const void* fn = k == 1 ? reinterpret_cast<const void*>(k_conv_mxfp8<1, false>) : reinterpret_cast<const void*>(k_conv_mxfp8<3, false>);
     if (ensure_lds(g_f8g_once[k == 1 ? 0 : 1], fn, F8_LDS) != 0) return SSD_ERR_LAUNCH;
     const unsigned grid = (unsigned)(((g.M + 127) / 128) * ((Cout + 127) / 128));
     const auto* xp = static_cast<const unsigned char*>(x8);
@@ -463,9 +484,41 @@ int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, con
     const auto* wp = static_cast<const unsigned char*>(w8);
     const auto* wsp = static_cast<const unsigned char*>(wscale);
     if (k == 1)
-        hipLaunchKernelGGL(k_conv_mxfp8<1>, dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
+        hipLaunchKernelGGL((k_conv_mxfp8<1, false>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
     else
-        hipLaunchKernelGGL(k_conv_mxfp8<3>, dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
+        hipLaunchKernelGGL((k_conv_mxfp8<3, false>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
+    return ssd_launch_status();
+}
+
+int ssd_conv2d_bwd_data_mxfp8(const void* dy8, const void* dyscale, const void* wt8, const void* wtscale, const void* relu_src,
+                              void* dx_bf16, void* dx8, void* dxscale, int B, int H, int W, int Cin, int Cout, int k, int pad_t,
+                              int pad_l, int Ho, int Wo, int accumulate, void* stream) {
+    if (!dy8 || !dyscale || !wt8 || !wtscale) return SSD_ERR_VALUE;
+    if ((!dx_bf16 && !dx8) || (!dx8 != !dxscale) || (accumulate && !dx_bf16)) return SSD_ERR_VALUE;
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || pad_t < 0 || pad_l < 0) return SSD_ERR_VALUE;
+    if (Cout % 128 || Cin % 32 || (k != 1 && k != 3)) return SSD_ERR_UNSUPPORTED;
+    // the forward implicit GEMM on dy [B,Ho,Wo,Cout] with the transposed filters and the mirrored pads, output [B,H,W,Cin]
+    const int qt = k - 1 - pad_t, ql = k - 1 - pad_l;
+    if (qt < 0 || ql < 0 || H - 1 - qt >= Ho || W - 1 - ql >= Wo) return SSD_ERR_VALUE;
+    if ((long long)B * Ho * Wo * Cout >= (1ll << 31) || (long long)Cin * k * k * Cout >= (1ll << 31) ||
+        (long long)B * H * W * Cin * 2 >= (1ll << 31))
+        return SSD_ERR_UNSUPPORTED;
+    const ConvGeom g = make_geom(B, Ho, Wo, Cout, H, W, Cin, k, k, 1, 1, qt, ql);
+    MxOut ep = {};
+    ep.y = static_cast<bf16_raw*>(dx_bf16);
+    ep.q = static_cast<unsigned char*>(dx8); ep.qs = static_cast<unsigned char*>(dxscale);
+    ep.mask = static_cast<const bf16_raw*>(relu_src); ep.accumulate = accumulate;
+    const void* fn = k == 1 ? reinterpret_cast<const void*>(k_conv_mxfp8<1, true>) : reinterpret_cast<const void*>(k_conv_mxfp8<3, true>);
+    if (ensure_lds(g_f8d_once[k == 1 ? 0 : 1], fn, F8_LDS) != 0) return SSD_ERR_LAUNCH;
+    const unsigned grid = (unsigned)(((g.M + 127) / 128) * ((Cin + 127) / 128));
+    const auto* xp = static_cast<const unsigned char*>(dy8);
+    const auto* xsp = static_cast<const unsigned char*>(dyscale);
+    const auto* wp = static_cast<const unsigned char*>(wt8);
+    const auto* wsp = static_cast<const unsigned char*>(wtscale);
+    if (k == 1)
+        hipLaunchKernelGGL((k_conv_mxfp8<1, true>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
+    else
+        hipLaunchKernelGGL((k_conv_mxfp8<3, true>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
     return ssd_launch_status();
 }
 

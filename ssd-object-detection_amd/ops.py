@@ -825,6 +825,44 @@ def conv2d_fwd_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, w
     return out if want_bf16 else (out_q, out_scale)
 
 
+def conv2d_bwd_data_mxfp8(dyq, dys, wtq, wts, relu_src, x_shape, stride, pad_t, pad_l, accumulate=False, want_bf16=True,
+                          want_fp8=False, out=None, out_q=None, out_scale=None):
+    """conv2d_bwd_data at stride 1 on block-scaled fp8 operands: quantize_mx_fp8 of dy [B,Ho,Wo,Cout] and of the transposed
+    filters w_t [Cin,k,k,Cout] (k = 1 or 3); pad_t / pad_l are the forward's.  accumulate: out (bf16) += the result before
+    the mask; relu_src (bf16 [B,H,W,Cin] or None): zero where it is <= 0.  Returns the outputs asked for: the bf16 dx,
+    (q, scale) = its quantize_mx_fp8, or (bf16, q, scale) when both are wanted."""
+    L = _lib.lib()
+    B, H, W, Cin = x_shape
+    _, Ho, Wo, Cout = dyq.shape
+    k = wtq.shape[1]
+    assert want_bf16 or want_fp8
+    assert wtq.shape == (Cin, k, k, Cout) and dys.shape == (B, Ho, Wo, Cout // 32) and wts.shape == (Cin, k, k, Cout // 32)
+    for t in (dyq, dys, wtq, wts):
+        _dev(t, torch.uint8)
+    if relu_src is not None:
+        _bf(relu_src)
+        assert relu_src.shape == tuple(x_shape)
+    if stride != 1:
+        raise NotImplementedError("block-scaled fp8 data gradient: stride 1 only (stride-2 layers use conv2d_bwd_data)")
+    if want_bf16 and out is None:
+        assert not accumulate
+        out = torch.empty(x_shape, dtype=torch.bfloat16, device=dyq.device)
+    if want_fp8:
+        if out_q is None:
+            out_q = torch.empty(x_shape, dtype=torch.uint8, device=dyq.device)
+        if out_scale is None:
+            out_scale = torch.empty(tuple(x_shape[:3]) + (max(Cin // 32, 1),), dtype=torch.uint8, device=dyq.device)
+    rc = L.ssd_conv2d_bwd_data_mxfp8(_ptr(dyq), _ptr(dys), _ptr(wtq), _ptr(wts), _ptr(relu_src), _ptr(out) if want_bf16 else None,
+                                     _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
+                                     k, pad_t, pad_l, Ho, Wo, 1 if accumulate else 0, _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError("block-scaled fp8 data gradient needs Cout % 128 == 0, Cin % 32 == 0 and k in (1, 3)")
+    _lib.check(rc)
+    if want_bf16 and want_fp8:
+        return out, out_q, out_scale
+    return out if want_bf16 else (out_q, out_scale)
+
+
 def add_relu_fwd_mxfp8(a, b, out=None, q=None, scale=None):
     """(out, q, scale): out = relu(a + b) exactly as add_relu_fwd, (q, scale) = quantize_mx_fp8(out), in one pass."""
     L = _lib.lib()

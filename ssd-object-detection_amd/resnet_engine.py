@@ -61,13 +61,15 @@ def mxfp8_eligible(nd):
             and nd["k"] in (1, 3) and nd["stride"] in (1, 2))
 
 
-def mxfp8_plan(nodes):
+def mxfp8_plan(nodes, train=False):
     """The fp8 forward of a graph (resnet50_ssd512_graph() or the engine's planned nodes; no device needed).  Returns
     (fp8, writes): the set of nodes that run in fp8, and for every node the outputs it writes, a frozenset of "bf16" / "fp8".
     A producer writes exactly what its consumers read: "fp8" for an fp8 convolution, "bf16" for a bf16 convolution, the
     pooling, an add and the heads (feature maps); adds always write bf16 (ops.add_relu_fwd_mxfp8 adds the fp8 form).  Every
     fp8 map is written by the epilogue of its producer (an fp8 convolution or an add): the plan needs no standalone
-    quantisation of an activation."""
+    quantisation of an activation.  train=True: the training-mode forward, whose producers also write the bf16 map of every
+    node backward() reads -- each convolution's input (its weight gradient; it is also every ReLU mask a data gradient
+    applies) besides the adds (identity-shortcut masks) and the feature maps (heads), which write it anyway."""
     fp8 = {i for i, nd in enumerate(nodes) if mxfp8_eligible(nd)}
     writes = {i: set() for i in range(len(nodes))}
     for i, nd in enumerate(nodes):
@@ -76,12 +78,63 @@ def mxfp8_plan(nodes):
         for s in (nd["src"] if _kind(nd) == "add" else (nd["src"],)):
             if s >= 0:
                 writes[s].add("fp8" if i in fp8 else "bf16")
+                if train and _kind(nd) == "conv":
+                    writes[s].add("bf16")
     for i, w in writes.items():
         assert w, "node %d has no consumer" % i
         if "fp8" in w:
             assert i in fp8 or _kind(nodes[i]) == "add", "node %d would need a standalone activation quantise" % i
     assert all(nodes[i]["src"] >= 0 for i in fp8), "the network input would need a standalone quantise"
     return fp8, {i: frozenset(w) for i, w in writes.items()}
+
+
+def mxfp8_dgrad_eligible(nd):
+    """Whether the data gradient of node `nd` runs in block-scaled fp8 (ops.conv2d_bwd_data_mxfp8): a convolution other than
+    the stem, stride 1, k in (1, 3), whose output channels (the K of this GEMM) are whole MX k-steps (Cout % 128 == 0) and
+    whose input channels are whole MX blocks (Cin % 32 == 0)."""
+    src = nd["src"]
+    return (_kind(nd) == "conv" and isinstance(src, int) and src >= 0 and nd["stride"] == 1 and nd["k"] in (1, 3)
+            and nd["cout"] % 128 == 0 and nd["cin"] % 32 == 0)
+
+
+def mxfp8_bwd_plan(nodes):
+    """The fp8 data gradients after a training-mode fp8 forward (no device needed).  Returns (dgrad, root, maps):
+      dgrad  the set of convolutions whose data gradient runs in fp8 (mxfp8_dgrad_eligible);
+      root   {node: the node whose gradient buffer it shares}: the two linear inputs of an add (the block's 1x1 expand and a
+             projection shortcut) alias the add's gradient, every other node owns its own;
+      maps   {root r: (kind, writer)} for every gradient map an fp8 data gradient reads as dy: the LAST launch of the reverse
+             walk that writes it, which also writes its fp8 form.  kind "fp8" = fp8 data gradient `writer`, whose epilogue
+             quantises; "dgrad" (a bf16 stride-2 data gradient), "pool", "relu_mask" (identity shortcut of add `writer`) or
+             "heads" (writer -1) = a bf16 kernel, behind which ONE standalone ops.quantize_mx_fp8 of the map runs.
+    Writers of a map, in walk order: the heads' data gradient (feature maps), then its consumers from the last to the first."""
+    n = len(nodes)
+    dgrad = {i for i, nd in enumerate(nodes) if mxfp8_dgrad_eligible(nd)}
+    root = list(range(n))
+    for k in range(n - 1, -1, -1):
+        if _kind(nodes[k]) == "add":
+            a, sc = nodes[k]["src"]
+            root[a] = root[k]
+            if _kind(nodes[sc]) == "conv" and not nodes[sc]["relu"]:
+                root[sc] = root[k]
+    writers = {r: ([("heads", -1)] if nodes[r]["feature"] else []) for r in range(n)}
+    for c in range(n - 1, -1, -1):
+        nd = nodes[c]
+        if _kind(nd) == "add":
+            a, sc = nd["src"]
+            assert root[a] != a, "the block output of add %d is not linear" % c
+            if root[sc] == sc:
+                writers[sc].append(("relu_mask", c))
+        elif nd["src"] >= 0:
+            assert root[nd["src"]] == nd["src"], "node %d reads an aliased map" % c
+            kind = "pool" if _kind(nd) == "pool3" else ("fp8" if c in dgrad else "dgrad")
+            writers[nd["src"]].append((kind, c))
+    maps = {}
+    for i in sorted(dgrad):
+        r = root[i]
+        assert writers[r], "gradient map %d has no writer" % r
+        maps[r] = writers[r][-1]
+        assert maps[r][1] == -1 or maps[r][1] > i, "the fp8 form of map %d would come after its reader %d" % (r, i)
+    return dgrad, root, maps
 
 
 class ResNet50SSDEngine(SSDEngine):
@@ -98,8 +151,28 @@ class ResNet50SSDEngine(SSDEngine):
         self.n_trunk = max(bt.block0 + bt.nblocks for _, bt in self.conv_params.values()) * self.block
         self._mx_w = None                      # (q u8 [n_trunk], scale u8 [n_trunk / 32]), allocated at the first fp8 forward
         self._mx_forward = False               # the last forward ran in fp8: the bf16 activations backward() needs are incomplete
+        self.mx_train_writes = mxfp8_plan(self.nodes, train=True)[1]
+        self._mx_train = False                 # ... in training mode: every bf16 map backward() reads was written
+        self._mx_wt = None                     # (q, scale) of the fp8 data gradients' transposed filters, at every fp8 backward
 
     # ---------------------------------------------------------------- static planning
+    def _alloc_params(self):
+        super()._alloc_params()
+        # the transposed filters as slices of ONE buffer, the fp8 data gradients' first: their MX-fp8 form is then one
+        # ssd_quantize_mx_fp8 over its front (every slice starts on a 32-element block: Cout % 32 == 0 for all of them)
+        self.mx_dgrad, self.mx_groot, self.mx_gmaps = mxfp8_bwd_plan(self.nodes)
+        order = sorted(self.w_t, key=lambda i: (i not in self.mx_dgrad, i))
+        sizes = [self.w_t[i].numel() for i in order]
+        assert all(v % 32 == 0 for v in sizes)
+        flat = torch.empty(sum(sizes), dtype=torch.bfloat16, device=self.device)
+        self.wt_off, off = {}, 0
+        for i, v in zip(order, sizes):
+            self.wt_off[i] = off
+            self.w_t[i] = flat[off:off + v].view(self.w_t[i].shape)
+            off += v
+        self.n_wt8 = sum(v for i, v in zip(order, sizes) if i in self.mx_dgrad)
+        self._wt_flat = flat
+
     def _plan_shapes(self):
         self.nodes, self.fm = [], []
         sizes = {-1: self.in_size}
@@ -156,6 +229,35 @@ class ResNet50SSDEngine(SSDEngine):
         return (q[wt.offset:wt.offset + wt.numel].view(shape),
                 sc[wt.offset // 32:(wt.offset + wt.numel) // 32].view(shape[:3] + (nd["cin"] // 32,)))
 
+    def mxfp8_grads(self, B):
+        """{root map: (q u8 [B,H,W,C], scale u8 [B,H,W,C/32])}: the fp8 forms of the gradient maps the fp8 data gradients read
+        (mxfp8_bwd_plan), allocated at the first fp8 backward of batch size B (a bf16-only run allocates none)."""
+        c = self._acts(B)
+        mx = c.get("mxfp8_grad")
+        if mx is None:
+            mx = {}
+            for r in self.mx_gmaps:
+                nd = self.nodes[r]
+                shape = (B, nd["hout"], nd["hout"], nd["cout"])
+                mx[r] = (torch.empty(shape, dtype=torch.uint8, device=self.device),
+                         torch.empty(shape[:3] + (nd["cout"] // 32,), dtype=torch.uint8, device=self.device))
+            c["mxfp8_grad"] = mx
+        return mx
+
+    def mxfp8_wt(self, i):
+        """(q [Cin,k,k,Cout], scale [Cin,k,k,Cout/32]) of the transposed filters of fp8 data gradient i as the last fp8
+        backward quantised them."""
+        nd, o = self.nodes[i], self.wt_off[i]
+        q, sc = self._mx_wt
+        shape = tuple(self.w_t[i].shape)
+        return q[o:o + self.w_t[i].numel()].view(shape), sc[o // 32:(o + self.w_t[i].numel()) // 32].view(shape[:3] + (nd["cout"] // 32,))
+
+    def _quantize_wt(self):
+        if self._mx_wt is None:
+            self._mx_wt = (torch.empty((self.n_wt8,), dtype=torch.uint8, device=self.device),
+                           torch.empty((self.n_wt8 // 32,), dtype=torch.uint8, device=self.device))
+        ops.quantize_mx_fp8(self._wt_flat[:self.n_wt8], q=self._mx_wt[0], scale=self._mx_wt[1])
+
     def _quantize_filters(self):
         if self._mx_w is None:
             self._mx_w = (torch.empty((self.n_trunk,), dtype=torch.uint8, device=self.device),
@@ -166,15 +268,16 @@ class ResNet50SSDEngine(SSDEngine):
         return acts[src + 1]                   # acts[0] = network input, acts[i + 1] = output of node i
 
     # ---------------------------------------------------------------- forward / backward
-    def forward(self, x, precision="bf16"):
+    def forward(self, x, precision="bf16", train=False):
         """(loc, conf) of image batch x.  precision="mxfp8": the trunk's fp8 layers (mxfp8_plan) on block-scaled fp8
-        operands, each fed directly by the layer before it; the rest and the heads in bf16.  Inference only: backward()
-        needs a bf16 forward."""
+        operands, each fed directly by the layer before it; the rest and the heads in bf16.  Inference only unless
+        train=True, which also writes every bf16 map backward() reads (same fp8 launches, same (loc, conf)); backward()
+        then runs the stride-1 data gradients in fp8 (mxfp8_bwd_plan)."""
         if precision == "mxfp8":
-            return self._forward_mxfp8(x)
+            return self._forward_mxfp8(x, train)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
-        self._mx_forward = False
+        self._mx_forward = self._mx_train = False
         B = x.shape[0]
         c = self._acts(B)
         acts = c["acts"]
@@ -196,17 +299,18 @@ class ResNet50SSDEngine(SSDEngine):
                                 self.num_priors[lvl], self.classes, self.level_off[lvl], ws=self._ws)
         return c["loc"], c["conf"]
 
-    def _forward_mxfp8(self, x):
+    def _forward_mxfp8(self, x, train):
         B = x.shape[0]
         c = self._acts(B)
         mx = self.mxfp8_acts(B)
         acts = c["acts"]
         acts[0] = x
         self.bits_valid = set()
-        self._mx_forward = True
+        self._mx_forward, self._mx_train = True, bool(train)
         self._quantize_filters()
+        writes = self.mx_train_writes if train else self.mx_writes
         for i, nd in enumerate(self.nodes):
-            w = self.mx_writes[i]
+            w = writes[i]
             if nd["kind"] == "conv":
                 wt, bt = self.conv_params[i]
                 if i in self.mx_fp8:
@@ -233,16 +337,32 @@ class ResNet50SSDEngine(SSDEngine):
                                 self.num_priors[lvl], self.classes, self.level_off[lvl], ws=self._ws)
         return c["loc"], c["conf"]
 
-    def backward(self, dloc, dconf, on_ready=None, fused_adam=None, heads=None, on_dgrad=None):
-        """Gradients of all parameters into self.grad from d(loss)/d(loc), d(loss)/d(conf) (or the loss's compact rows)."""
+    def backward(self, dloc, dconf, on_ready=None, fused_adam=None, heads=None, on_dgrad=None, dgrad_precision=None):
+        """Gradients of all parameters into self.grad from d(loss)/d(loc), d(loss)/d(conf) (or the loss's compact rows).
+        After forward(x, "mxfp8", train=True) the data gradients of mxfp8_bwd_plan run in block-scaled fp8 (their
+        transposed filters quantised here, once per call); dgrad_precision="bf16" keeps every data gradient in bf16.  Weight
+        gradients, heads, stride-2 data gradients and pooling always run in bf16 on the bf16 maps."""
         assert fused_adam is None and on_dgrad is None, "the per-bucket optimizer schedule belongs to the VGG chain engine"
-        if self._mx_forward:
-            raise RuntimeError("backward() after an mxfp8 forward: the bf16 activations it needs were not all written; run "
-                               "forward(x) in bf16 first (fp8 training is not supported)")
+        if self._mx_forward and not self._mx_train:
+            raise RuntimeError("backward() after an inference mxfp8 forward: the bf16 activations it needs were not all "
+                               "written; run forward(x) in bf16 or forward(x, 'mxfp8', train=True) first")
+        if dgrad_precision not in (None, "bf16", "mxfp8"):
+            raise ValueError("dgrad_precision must be 'bf16' or 'mxfp8', not %r" % (dgrad_precision,))
+        if dgrad_precision == "mxfp8" and not self._mx_train:
+            raise ValueError("fp8 data gradients need a forward(x, 'mxfp8', train=True) first")
+        fp8 = self._mx_train and dgrad_precision != "bf16"
         if heads is None:
             heads = self.heads_from_dense(dloc, dconf)
         c = self._acts(heads.B)
         acts, gacts = c["acts"], list(c["gacts"])
+        if fp8:
+            self._quantize_wt()
+            g8 = self.mxfp8_grads(heads.B)
+
+        def wrote(r, kind, writer):            # a bf16 kernel was the last writer of a map an fp8 data gradient reads
+            if fp8 and self.mx_gmaps.get(r) == (kind, writer):
+                ops.quantize_mx_fp8(c["gacts"][r + 1], q=g8[r][0], scale=g8[r][1])
+
         n = len(self.nodes)
         written = [False] * (n + 1)
         # heads: every feature-map gradient is written (masked by the map's own ReLU), then the trunk accumulates onto it
@@ -252,6 +372,7 @@ class ResNet50SSDEngine(SSDEngine):
         del keep
         for ni, _, _ in self.fm:
             written[ni + 1] = True
+            wrote(ni, "heads", -1)
 
         def relu_of(idx):                      # does activation acts[idx] carry its own ReLU?
             return idx > 0 and self.nodes[idx - 1]["relu"]
@@ -272,12 +393,14 @@ class ResNet50SSDEngine(SSDEngine):
                     gacts[sc + 1] = g
                 else:                           # identity shortcut: masked by the source's own ReLU, summed with its other uses
                     ops.relu_mask_bwd(g, acts[sc + 1], out=gacts[sc + 1], accumulate=written[sc + 1])
+                    wrote(sc, "relu_mask", i)
                 written[sc + 1] = True
                 continue
             src = nd["src"]
             if nd["kind"] == "pool3":
                 assert not written[src + 1]
                 ops.maxpool3x3s2_bwd(c["pool3_code"][i], g, acts[src + 1].shape, out=gacts[src + 1])
+                wrote(src, "pool", i)
                 written[src + 1] = True
                 continue
             wt, bt = self.conv_params[i]
@@ -287,8 +410,18 @@ class ResNet50SSDEngine(SSDEngine):
                 on_ready([wt.index, bt.index])
             if src < 0:
                 continue                        # no gradient w.r.t. the image
-            ops.conv2d_bwd_data(g, self.w_t[i], acts[src + 1] if relu_of(src + 1) else None, acts[src + 1].shape, nd["stride"],
-                                nd["pt"], nd["pl"], accumulate=written[src + 1], out=gacts[src + 1], ws=self._ws)
+            relu_src = acts[src + 1] if relu_of(src + 1) else None
+            if fp8 and i in self.mx_dgrad:
+                dyq, dys = g8[self.mx_groot[i]]
+                wtq, wts = self.mxfp8_wt(i)
+                q, sc = g8[src] if self.mx_gmaps.get(src) == ("fp8", i) else (None, None)
+                ops.conv2d_bwd_data_mxfp8(dyq, dys, wtq, wts, relu_src, acts[src + 1].shape, nd["stride"], nd["pt"], nd["pl"],
+                                          accumulate=written[src + 1], want_fp8=q is not None, out=gacts[src + 1], out_q=q,
+                                          out_scale=sc)
+            else:
+                ops.conv2d_bwd_data(g, self.w_t[i], relu_src, acts[src + 1].shape, nd["stride"], nd["pt"], nd["pl"],
+                                    accumulate=written[src + 1], out=gacts[src + 1], ws=self._ws)
+                wrote(src, "dgrad", i)
             written[src + 1] = True
         if on_ready:
             on_ready([i for wt, bt in self.head_params for t in (wt, bt) for i in t.indices])
