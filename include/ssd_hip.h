@@ -364,6 +364,21 @@ int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, con
                          void* y8, void* yscale, int B, int H, int W, int Cin, int Cout, int k, int stride, int pad_t, int pad_l,
                          int Ho, int Wo, int relu, void* stream);
 int ssd_add_relu_fwd_mxfp8(const void* a, const void* b, void* out_bf16, void* q, void* scale, long long n, void* stream);
+/* The SSD300 VGG trunk's fp8 forward (engine.py, precision="mxfp8"; no reference counterpart: fp32 TensorFlow convolutions and
+ * MaxPool2D, models/ssd_model.py:82-84): block3_conv3 and the SAME 2x2 max pool behind it in one launch, the full-resolution
+ * map never stored -- the seam of ssd_conv2d_fwd_pool's pool_only mode (y == NULL) on block-scaled fp8 operands.
+ *   ssd_conv2d_fwd_pool_mxfp8  ssd_maxpool2x2_fwd(ssd_conv2d_fwd_mxfp8's bf16 y) bit for bit: every conv pixel accumulated in the
+ *                           same order (bias, ReLU, ONE bf16 rounding), then the max over each 2x2 / stride-2 window's pixels
+ *                           inside the [Ho,Wo] map -- Hp = Ho / 2 (VALID) or (Ho + 1) / 2 (TF-SAME, windows clipped at the
+ *                           edge), Wp likewise.  Outputs, any non-empty subset: y_pool_bf16 bf16 [B,Hp,Wp,Cout]; y_pool8 u8
+ *                           [B,Hp,Wp,Cout] + y_pool_scale u8 [B,Hp,Wp,Cout/32], given together: ssd_quantize_mx_fp8 of that pooled
+ *                           map, bit for bit.  Operands and pads as ssd_conv2d_fwd_mxfp8.  SSD_ERR_VALUE (nothing launched): a
+ *                           missing operand, no output, y_pool8 without y_pool_scale (or the reverse), bad dimensions, pads or
+ *                           pooled sizes; SSD_ERR_UNSUPPORTED (nothing launched): k != 3, stride != 1, Cin % 128, Cout % 32, an
+ *                           operand or the unpooled output of 2^31 bytes or more.  Inference only: no winner codes. */
+int ssd_conv2d_fwd_pool_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias,
+                              void* y_pool_bf16, void* y_pool8, void* y_pool_scale, int B, int H, int W, int Cin, int Cout, int k,
+                              int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, int Hp, int Wp, void* stream);
 /* The stride-1 data gradients of the ResNet-50 trunk after a training-mode fp8 forward (resnet_engine.py, mxfp8_bwd_plan):
  *   ssd_conv2d_bwd_data_mxfp8  dx[B,H,W,Cin] = ssd_conv2d_bwd_data's result at stride 1 on block-scaled fp8 operands -- dy8
  *                           [B,Ho,Wo,Cout] / dyscale [B,Ho,Wo,Cout/32] and wt8 [Cin][k][k][Cout] / wtscale [Cin][k][k][Cout/32],

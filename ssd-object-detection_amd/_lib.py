@@ -101,6 +101,7 @@ _SIGNATURES = {
     "ssd_conv2d_fwd_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 12 + [VP]),
     "ssd_add_relu_fwd_mxfp8": (ctypes.c_int, [VP] * 5 + [ctypes.c_longlong, VP]),
     "ssd_conv2d_bwd_data_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 11 + [VP]),
+    "ssd_conv2d_fwd_pool_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 14 + [VP]),
     "ssd_chain_pack_weights": (ctypes.c_int, [ctypes.POINTER(ChainPack), ctypes.c_int, VP]),
     "ssd_chain_prefetch": (ctypes.c_int, [ctypes.POINTER(ChainPack), ctypes.c_int, VP]),
     "ssd_set_wgrad_reduce_stream": (ctypes.c_int, [VP]),

@@ -19,6 +19,8 @@
 // bitwise ssd_quantize_mx_fp8 of that bf16 map) or both -- so the next fp8 layer is fed without a separate quantisation pass.
 // Its data-gradient mode (DG) serves the trunk's stride-1 data gradients after a training-mode fp8 forward: the same main loop
 // on dy and the transposed filters, an epilogue with ssd_conv2d_bwd_data's accumulate and ReLU mask.
+// Its pooled mode (POOL) serves the SSD300 VGG trunk's fp8 forward (engine.py, precision="mxfp8"): block3_conv3 and the 2x2
+// max pool behind it in one launch that stores the pooled map only -- the same main loop on tiles of 32 whole 2x2 windows.
 #include "common.h"
 #include <hip/hip_bf16.h>
 #include "conv_common.h"
@@ -215,6 +217,8 @@ struct MxOut {
     unsigned char* qs;                       // [M][N/32] E8M0
     const bf16_raw* mask;                    // DG: zero where mask <= 0 ([M][N] bf16, the forward activation), or null
     int accumulate;                          // DG: y += result before the mask (y then holds the earlier gradient)
+    int Mp;                                  // POOL: y / q / qs hold the 2x2 max-pooled map [B,Hp,Wp,N], Mp = B*Hp*Wp pixels
+    FastDiv d_phw, d_pw;                     // POOL: divide by Hp*Wp and by Wp
 };
 
 // The general MX-fp8 forward convolution: KS x KS filters (1 or 3), stride g.mul (1 or 2), TF-SAME pads g.pad_t / g.pad_l.  The
@@ -224,7 +228,10 @@ struct MxOut {
 // li, li + 16, li + 32, li + 48: the block amax is the lane's 8 values reduced over the four lane groups (two xor shuffles).
 // DG = the stride-1 data gradient (ssd_conv2d_bwd_data_mxfp8): x = dy, w = the transposed filters, pads k - 1 - pad; no bias or
 // ReLU, but y += result (accumulate) and then zero where mask <= 0, in ssd_conv2d_bwd_data's order, before the ONE rounding.
-template <int KS, bool DG>
+// POOL = the convolution followed by a 2x2 / stride-2 max pool (ssd_conv2d_fwd_pool_mxfp8): a tile is 32 whole pooling windows
+// instead of 128 consecutive pixels, and the epilogue pools the bf16-rounded pixels of each window before its stores.  Every
+// conv pixel still sees the same k-steps in the same order, so it is bitwise the pixel of the plain launch.
+template <int KS, bool DG, bool POOL = false>
 __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restrict__ x, const unsigned char* __restrict__ xs,
                                                     const unsigned char* __restrict__ w, const unsigned char* __restrict__ wsc,
                                                     ConvGeom g, MxOut ep) {
@@ -247,7 +254,35 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
     const __amdgpu_buffer_rsrc_t wsres = __builtin_amdgcn_make_buffer_rsrc((void*)wsc, 0, (unsigned)g.N * (unsigned)KK * (unsigned)cb, 0x00020000);
     constexpr unsigned OOB = 0xfffffff0u;
 
-    // rows as in k_conv3x3_mxfp8; py / px = top-left input coordinate of the output pixel's window (py < 0 far off: beyond M)
+    // tile row r -> top-left input coordinate (y, x) of its output pixel's window (y < 0 far off: no pixel) and the image's
+    // first pixel b0.  Plain: row r is output pixel m0 + r of the flattened [B,Ho,Wo] index.  POOL: the tile holds the pooled
+    // pixels 32 mt .. 32 mt + 31 of the flattened [B,Hp,Wp] index, and row r = 64 wm + 16 p + li is member p (dy = p >> 1,
+    // dx = p & 1) of window 16 wm + li -- the epilogue's lane then holds all four pixels of one window (pixel tiles p = 0..3)
+    auto place = [&](int r, int& y, int& x, int& b0) {
+        if constexpr (POOL) {
+            const int q = mt * 32 + (r >> 6) * 16 + (r & 15), p = (r >> 4) & 3;
+            const bool qv = q < ep.Mp;
+            const int qq = qv ? q : 0;
+            const int b = fdiv(qq, ep.d_phw);
+            const int rem = qq - b * ep.d_phw.d;
+            const int yp = fdiv(rem, ep.d_pw);
+            const int oy = 2 * yp + (p >> 1), ox = 2 * (rem - yp * ep.d_pw.d) + (p & 1);
+            y = (qv && oy < g.Ho && ox < g.Wo) ? oy * stride - g.pad_t : -(1 << 20);
+            x = ox * stride - g.pad_l;
+            b0 = b * g.H * g.W;
+        } else {
+            const int m = m0 + r;
+            const bool mv = m < g.M;
+            const int mm = mv ? m : 0;
+            const int b = fdiv(mm, g.d_hw);
+            const int rem = mm - b * g.d_hw.d;
+            const int oy = fdiv(rem, g.d_w);
+            y = mv ? oy * stride - g.pad_t : -(1 << 20);
+            x = (rem - oy * g.d_w.d) * stride - g.pad_l;
+            b0 = b * g.H * g.W;
+        }
+    };
+    // rows as in k_conv3x3_mxfp8
     int py[4], px[4], pb[4];
     unsigned wrow[4], cchunk[4];
 #pragma unroll
@@ -255,15 +290,7 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
         const int i = wave + 4 * j;
         const int r = 8 * i + 2 * (lane >> 4) + ((lane >> 3) & 1);
         cchunk[j] = (unsigned)((lane & 7) ^ ((4 * i + (lane >> 4)) & 7)) * 16u;
-        const int m = m0 + r;
-        const bool mv = m < g.M;
-        const int mm = mv ? m : 0;
-        const int b = fdiv(mm, g.d_hw);
-        const int rem = mm - b * g.d_hw.d;
-        const int oy = fdiv(rem, g.d_w);
-        py[j] = mv ? oy * stride - g.pad_t : -(1 << 20);
-        px[j] = (rem - oy * g.d_w.d) * stride - g.pad_l;
-        pb[j] = b * g.H * g.W;
+        place(r, py[j], px[j], pb[j]);
         const int n = n0 + r;
         wrow[j] = n < g.N ? (unsigned)n * (unsigned)KK * (unsigned)g.C : 0xffffffffu;
     }
@@ -271,15 +298,7 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
     int sy = 0, sx = 0, sb = 0;
     unsigned swrow = 0xffffffffu;
     if (wave < 2) {
-        const int m = m0 + srow;
-        const bool mv = m < g.M;
-        const int mm = mv ? m : 0;
-        const int b = fdiv(mm, g.d_hw);
-        const int rem = mm - b * g.d_hw.d;
-        const int oy = fdiv(rem, g.d_w);
-        sy = mv ? oy * stride - g.pad_t : -(1 << 20);
-        sx = (rem - oy * g.d_w.d) * stride - g.pad_l;
-        sb = b * g.H * g.W;
+        place(srow, sy, sx, sb);
     } else {
         const int n = n0 + srow;
         swrow = n < g.N ? (unsigned)n * (unsigned)KK * (unsigned)cb : 0xffffffffu;
@@ -350,9 +369,77 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
                 acc[c][p] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[c], fx[p], acc[c][p], 0, 0, 0, swv[c], 0, sxv[p]);
     }
 
+    const int ldq = g.N >> 5;
+    if constexpr (POOL) {
+        // epilogue: bias, ReLU, ONE bf16 rounding per conv pixel; the max over the window's pixels inside the conv map, in
+        // k_maxpool_fwd's order (dy, then dx: tiles p = 0..3); then the pooled pixel's stores and quantisation as below
+        const int q = mt * 32 + wave_m * 16 + li;
+        const bool qv = q < ep.Mp;
+        bool in[4];
+        {
+            const int qq = qv ? q : 0;
+            const int b = fdiv(qq, ep.d_phw);
+            const int rem = qq - b * ep.d_phw.d;
+            const int yp = fdiv(rem, ep.d_pw), xp = rem - yp * ep.d_pw.d;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) in[p] = 2 * yp + (p >> 1) < g.Ho && 2 * xp + (p & 1) < g.Wo;
+        }
+#pragma unroll
+        for (int cp = 0; cp < 2; ++cp) {
+            const int nblk = n0 + wave_n * 64 + cp * 32;
+            if (nblk >= g.N) continue;                        // wave-uniform (N % 32 == 0: the whole block lies inside N)
+            float v[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int n = nblk + h * 16 + gq * 4;
+                float b4[4] = {0.f, 0.f, 0.f, 0.f};
+                if (ep.bias) {
+                    const float4 bv = *reinterpret_cast<const float4*>(ep.bias + n);
+                    b4[0] = bv.x; b4[1] = bv.y; b4[2] = bv.z; b4[3] = bv.w;
+                }
+                float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    float t[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        t[j] = acc[2 * cp + h][p][j] + b4[j];
+                        if (ep.relu) t[j] = fmaxf(t[j], 0.f);
+                    }
+                    const unsigned lo = pack_bf16x2(t[0], t[1]), hi = pack_bf16x2(t[2], t[3]);
+                    const float r[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
+                                        __uint_as_float(hi & 0xffff0000u)};
+                    if (in[p]) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) best[j] = fmaxf(best[j], r[j]);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[4 * h + j] = best[j];
+                if (ep.y && qv)                               // bf16 values already: the packing is exact
+                    *reinterpret_cast<uint2*>(ep.y + (long long)q * g.N + n) = make_uint2(pack_bf16x2(best[0], best[1]),
+                                                                                           pack_bf16x2(best[2], best[3]));
+            }
+            if (ep.q) {
+                float amax = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+                amax = fmaxf(amax, __shfl_xor(amax, 16));
+                amax = fmaxf(amax, __shfl_xor(amax, 32));
+                const int e = mx_block_exp(amax);
+                const float inv = ldexpf(1.f, -e);
+                if (qv) {
+                    unsigned char* o = ep.q + (long long)q * g.N + nblk + gq * 4;
+                    *reinterpret_cast<unsigned*>(o) = mx_pack4(v[0], v[1], v[2], v[3], inv);
+                    *reinterpret_cast<unsigned*>(o + 16) = mx_pack4(v[4], v[5], v[6], v[7], inv);
+                    if (gq == 0) ep.qs[(long long)q * ldq + (nblk >> 5)] = (unsigned char)(e + 127);
+                }
+            }
+        }
+        return;
+    }
     // epilogue: per pixel tile p and channel block cp (tiles 2 cp, 2 cp + 1); the block test is wave-uniform, so every lane
     // of the wave takes part in the shuffles (lanes beyond M compute and discard)
-    const int ldq = g.N >> 5;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const int m = m0 + wave_m * 64 + p * 16 + li;
@@ -431,6 +518,7 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
 OnceLds g_f8_once;
 OnceLds g_f8g_once[2];
 OnceLds g_f8d_once[2];
+OnceLds g_f8p_once;
 
 }  // namespace
 
@@ -487,6 +575,33 @@ int ssd_conv2d_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, con
         hipLaunchKernelGGL((k_conv_mxfp8<1, false>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
     else
         hipLaunchKernelGGL((k_conv_mxfp8<3, false>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream, xp, xsp, wp, wsp, g, ep);
+    return ssd_launch_status();
+}
+
+int ssd_conv2d_fwd_pool_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias,
+                              void* y_pool_bf16, void* y_pool8, void* y_pool_scale, int B, int H, int W, int Cin, int Cout, int k,
+                              int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, int Hp, int Wp, void* stream) {
+    if (!x8 || !xscale || !w8 || !wscale) return SSD_ERR_VALUE;
+    if ((!y_pool_bf16 && !y_pool8) || (!y_pool8 != !y_pool_scale)) return SSD_ERR_VALUE;    // no output, or q without its scales
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || pad_t < 0 || pad_l < 0) return SSD_ERR_VALUE;
+    if ((Hp != Ho / 2 && Hp != (Ho + 1) / 2) || (Wp != Wo / 2 && Wp != (Wo + 1) / 2) || Hp <= 0 || Wp <= 0) return SSD_ERR_VALUE;
+    if (Cin % 128 || k != 3 || stride != 1 || Cout % 32) return SSD_ERR_UNSUPPORTED;
+    if (pad_t >= k || pad_l >= k || (Ho - 1) * stride - pad_t >= H || (Wo - 1) * stride - pad_l >= W) return SSD_ERR_VALUE;
+    if ((long long)B * H * W * Cin >= (1ll << 31) || (long long)Cout * k * k * Cin >= (1ll << 31) ||
+        (long long)B * Ho * Wo * Cout * 2 >= (1ll << 31))
+        return SSD_ERR_UNSUPPORTED;
+    const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, k, k, stride, 1, pad_t, pad_l);
+    MxOut ep = {};
+    ep.bias = bias; ep.relu = relu; ep.y = static_cast<bf16_raw*>(y_pool_bf16);
+    ep.q = static_cast<unsigned char*>(y_pool8); ep.qs = static_cast<unsigned char*>(y_pool_scale);
+    ep.Mp = B * Hp * Wp;
+    ep.d_phw = make_fastdiv(Hp * Wp);
+    ep.d_pw = make_fastdiv(Wp);
+    if (ensure_lds(g_f8p_once, reinterpret_cast<const void*>(k_conv_mxfp8<3, false, true>), F8_LDS) != 0) return SSD_ERR_LAUNCH;
+    const unsigned grid = (unsigned)(((ep.Mp + 31) / 32) * ((Cout + 127) / 128));         // 32 pooling windows per tile
+    hipLaunchKernelGGL((k_conv_mxfp8<3, false, true>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream,
+                       static_cast<const unsigned char*>(x8), static_cast<const unsigned char*>(xscale),
+                       static_cast<const unsigned char*>(w8), static_cast<const unsigned char*>(wscale), g, ep);
     return ssd_launch_status();
 }
 

@@ -65,6 +65,61 @@ SSD512_TRUNK = SSD300_TRUNK[:13] + [
 SSD512_NUM_PRIORS = (4, 6, 6, 6, 6, 4, 4)
 
 
+def _mx_conv(nd):
+    """A convolution the block-scaled fp8 kernels serve (ops.conv2d_fwd_mxfp8): Cin whole MX k-steps, Cout whole MX blocks."""
+    return (nd["kind"] == "conv" and nd["cin"] % 128 == 0 and nd["cout"] % 32 == 0 and nd["k"] in (1, 3)
+            and nd["stride"] in (1, 2))
+
+
+def mxfp8_vgg_plan(nodes, chain_start):
+    """The inference fp8 forward of a VGG trunk (SSDEngine's planned nodes: node i reads node i - 1; no device needed).
+    Returns (fp8, pooled, quant, writes):
+      fp8     the convolutions that run on block-scaled fp8 operands: one run of them up to the chain (which stays bf16),
+              each fed by the epilogue of the layer in front of it;
+      pooled  the pools that run inside the fp8 convolution in front of them (ops.conv2d_fwd_pool_mxfp8: 3x3 / stride 1);
+      quant   the ONE node whose bf16 output gets a standalone ops.quantize_mx_fp8: the input of the run's first layer;
+      writes  {node: frozenset of "bf16" / "fp8"}, the forms of its output the walk stores -- exactly what its consumers read
+              (the heads read bf16), the quantised node's bf16 map besides, nothing for a convolution whose pool runs in
+              its own launch.
+    The run is the longest stretch of such layers that ends in front of the chain.  It starts at its first convolution
+    whose input map is smaller than the map the layer writes: the standalone quantise then costs less than the layer's
+    own store (SSD300: block3_conv1 on the 75x75x128 pooled map, not block2_conv2 on the 150x150x128 one)."""
+    n = len(nodes)
+    end = n if chain_start is None else chain_start
+
+    def pools_itself(i):                 # a 3x3 / stride-1 fp8 convolution with a pool behind it inside the run
+        return (_mx_conv(nodes[i]) and nodes[i]["k"] == 3 and nodes[i]["stride"] == 1 and i + 1 < end
+                and nodes[i + 1]["kind"] == "pool")
+
+    s = end
+    while s > 1 and (_mx_conv(nodes[s - 1]) or (nodes[s - 1]["kind"] == "pool" and pools_itself(s - 2))):
+        s -= 1
+    size = [nd["hout"] ** 2 * nd["cout"] for nd in nodes]
+    start = None
+    for i in range(s, end):
+        out = size[i + 1] if pools_itself(i) else size[i]
+        if nodes[i]["kind"] == "conv" and size[i - 1] < out:
+            start = i
+            break
+    assert start is not None, "no layer of this trunk can run in fp8 behind a quantise cheaper than its own store"
+    fp8 = {i for i in range(start, end) if nodes[i]["kind"] == "conv"}
+    pooled = {i + 1 for i in fp8 if pools_itself(i)}
+    quant = {start - 1}
+    writes = {i: set() for i in range(n)}
+    for i, nd in enumerate(nodes):
+        if nd["feature"]:
+            writes[i].add("bf16")
+        if i > 0 and i not in pooled:
+            writes[i - 1].add("fp8" if i in fp8 else "bf16")
+    writes[start - 1].add("bf16")
+    for i, w in writes.items():
+        assert w or (i in fp8 and i + 1 in pooled), "node %d has no consumer" % i
+        if "fp8" in w:
+            assert i in fp8 or i in pooled or i in quant, "node %d would need a standalone activation quantise" % i
+    assert all(i - 1 in fp8 for i in pooled)
+    return fp8, pooled, quant, {i: frozenset(w) for i, w in writes.items()}
+
+
 class ParamTensor:
     """One trainable variable of the reference (= one tf.clip_by_norm unit, models/ssd_model.py:249): `numel` elements at
     `offset` of the flat buffers, alone in optimizer blocks block0 .. block0 + nblocks - 1 (the rest of them is zero)."""
@@ -155,6 +210,10 @@ class SSDEngine:
         # output has no other consumer and is never stored); False after a refusal
         self.fuse_first = os.environ.get("SSD_FUSE_FIRST", "1") == "1"
         self.wgrad_probe = None                # dict(nodes={...}, events=[]): time those layers' weight-gradient launches in the step
+        # inference in block-scaled fp8 (forward(x, "mxfp8")): the plan (mxfp8_vgg_plan, at the first fp8 forward), the fp8 layers'
+        # quantised filters and whether the last forward ran in fp8 (backward() then refuses)
+        self._vgg_mx, self._vgg_mx_range, self._vgg_mx_w = None, None, None
+        self._vgg_fp8_fwd = False
 
     # ---------------------------------------------------------------- static planning
     def _plan_shapes(self):
@@ -369,8 +428,19 @@ class SSDEngine:
             self._ws_side = ops.MatchWorkspace()
         return self._side
 
-    def forward(self, x):
-        """x: bf16 [B, S, S, 8] (ops.image_prep).  Returns (loc bf16 [B,A,4], conf bf16 [B,A,classes])."""
+    def forward(self, x, precision="bf16"):
+        """x: bf16 [B, S, S, 8] (ops.image_prep).  Returns (loc bf16 [B,A,4], conf bf16 [B,A,classes]).
+        precision="mxfp8": inference only -- the trunk layers of mxfp8_vgg_plan on block-scaled fp8 operands, the rest, the
+        chain and the heads in bf16, on the same streams as the bf16 forward; backward() then raises until a bf16 forward."""
+        if precision == "mxfp8":
+            return self._forward_vgg_mxfp8(x)
+        if precision != "bf16":
+            raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
+        self._vgg_fp8_fwd = False
+        return self._walk(x, self._bf16_node)
+
+    def _walk(self, x, launch_node):
+        """The forward pass: trunk nodes through launch_node(i, c) (the chain excepted), heads, chain and their streams."""
         B = x.shape[0]
         c = self._acts(B)
         acts = c["acts"]
@@ -457,41 +527,7 @@ class SSDEngine:
                     break
                 except NotImplementedError:           # SSD_ERR_UNSUPPORTED: nothing launched
                     self.chain = set()
-            if nd["kind"] == "conv":
-                wt, bt = self.conv_params[i]
-                nxt = self.nodes[i + 1] if i + 1 < len(self.nodes) else None
-                if nxt is not None and nxt["kind"] == "pool":      # conv + the pooling behind it in one call
-                    # nothing but the pooling reads this conv's full-resolution output (the backward pass works from the
-                    # pooled map and the winner codes): ask for the pooled map only, where a fused kernel serves the layer
-                    pool_only = self.pool_only.get(i, self.skip_fullres)
-                    args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"],
-                            nd["pl"], nd["hout"], nd["hout"], True, nxt["hout"] * 2 != nxt["hin"])
-                    kw = dict(out=acts[i + 1], pool_out=acts[i + 2], code=c["pool_code"][i + 1], ws=self._ws)
-                    if pool_only:
-                        try:
-                            ops.conv2d_fwd_pool(*args, pool_only=True, **kw)
-                        except ValueError:            # SSD_ERR_VALUE: no pooling kernel for this shape, nothing launched
-                            pool_only = False
-                    self.pool_only[i] = pool_only
-                    if not pool_only:
-                        ops.conv2d_fwd_pool(*args, **kw)
-                else:
-                    args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"],
-                            nd["hout"], nd["hout"])
-                    done = False
-                    if self.relu_bits is not None and self.relu_bits.get(i + 1, True) and (i + 1) in c["rbits"]:
-                        try:
-                            ops.conv2d_fwd_relubits(*args, c["rbits"][i + 1], out=acts[i + 1], ws=self._ws)
-                            done = True
-                            self.bits_valid.add(i + 1)
-                        except NotImplementedError:   # SSD_ERR_UNSUPPORTED: nothing launched
-                            pass
-                        self.relu_bits[i + 1] = done
-                    if not done:
-                        ops.conv2d_fwd(*args, True, out=acts[i + 1], ws=self._ws)
-            elif i == 0 or self.nodes[i - 1]["kind"] != "conv":
-                ops.maxpool2x2_fwd_argmax(acts[i], out=acts[i + 1], code=c["pool_code"][i],
-                                          same=nd["hout"] * 2 != nd["hin"])
+            launch_node(i, c)
             after_node(i)
         for lvl in range(len(self.fm)):
             if side is None or (lvl not in self.SIDE_HEADS and tail is None):
@@ -501,6 +537,121 @@ class SSDEngine:
             if tail is not None:
                 main.wait_stream(tail)
         return c["loc"], c["conf"]
+
+    def _bf16_node(self, i, c):
+        """Launch trunk node i of the bf16 forward (a pool behind a convolution runs inside that convolution's call)."""
+        nd, acts = self.nodes[i], c["acts"]
+        if nd["kind"] == "conv":
+            wt, bt = self.conv_params[i]
+            nxt = self.nodes[i + 1] if i + 1 < len(self.nodes) else None
+            if nxt is not None and nxt["kind"] == "pool":      # conv + the pooling behind it in one call
+                # nothing but the pooling reads this conv's full-resolution output (the backward pass works from the
+                # pooled map and the winner codes): ask for the pooled map only, where a fused kernel serves the layer
+                pool_only = self.pool_only.get(i, self.skip_fullres)
+                args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"],
+                        nd["pl"], nd["hout"], nd["hout"], True, nxt["hout"] * 2 != nxt["hin"])
+                kw = dict(out=acts[i + 1], pool_out=acts[i + 2], code=c["pool_code"][i + 1], ws=self._ws)
+                if pool_only:
+                    try:
+                        ops.conv2d_fwd_pool(*args, pool_only=True, **kw)
+                    except ValueError:            # SSD_ERR_VALUE: no pooling kernel for this shape, nothing launched
+                        pool_only = False
+                self.pool_only[i] = pool_only
+                if not pool_only:
+                    ops.conv2d_fwd_pool(*args, **kw)
+            else:
+                args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"],
+                        nd["hout"], nd["hout"])
+                done = False
+                if self.relu_bits is not None and self.relu_bits.get(i + 1, True) and (i + 1) in c["rbits"]:
+                    try:
+                        ops.conv2d_fwd_relubits(*args, c["rbits"][i + 1], out=acts[i + 1], ws=self._ws)
+                        done = True
+                        self.bits_valid.add(i + 1)
+                    except NotImplementedError:   # SSD_ERR_UNSUPPORTED: nothing launched
+                        pass
+                    self.relu_bits[i + 1] = done
+                if not done:
+                    ops.conv2d_fwd(*args, True, out=acts[i + 1], ws=self._ws)
+        elif i == 0 or self.nodes[i - 1]["kind"] != "conv":
+            ops.maxpool2x2_fwd_argmax(acts[i], out=acts[i + 1], code=c["pool_code"][i],
+                                      same=nd["hout"] * 2 != nd["hin"])
+
+    # ---------------------------------------------------------------- inference in block-scaled fp8 (MX e4m3)
+    def vgg_mxfp8_plan(self):
+        """mxfp8_vgg_plan of this engine's trunk: (fp8, pooled, quant, writes)."""
+        if self._vgg_mx is None:
+            fp8, pooled, quant, writes = mxfp8_vgg_plan(self.nodes, self.chain_start)
+            # the fp8 layers' filters: ONE ops.quantize_mx_fp8 over their stretch of param_bf16 (conv filters start on
+            # optimizer-block boundaries, so every layer's (q, scale) is a slice of the result)
+            lo = min(self.conv_params[i][0].offset for i in fp8)
+            hi = max(bt.block0 + bt.nblocks for _, bt in (self.conv_params[i] for i in fp8)) * self.block
+            assert all((self.conv_params[i][0].offset - lo) % 32 == 0 for i in fp8) and lo % 32 == 0 and (hi - lo) % 32 == 0
+            self._vgg_mx = (fp8, pooled, quant, writes)
+            self._vgg_mx_range = (lo, hi)
+        return self._vgg_mx
+
+    def vgg_mxfp8_acts(self, B):
+        """{node: (q u8 [B,H,W,C], scale u8 [B,H,W,C/32])} for every node whose fp8 form the fp8 forward stores, beside the bf16
+        activations of batch size B (allocated at the first fp8 forward of that batch size; a bf16-only run allocates none)."""
+        c = self._acts(B)
+        mx = c.get("vgg_mxfp8")
+        if mx is None:
+            mx = {}
+            for i, w in self.vgg_mxfp8_plan()[3].items():
+                if "fp8" in w:
+                    nd = self.nodes[i]
+                    shape = (B, nd["hout"], nd["hout"], nd["cout"])
+                    mx[i] = (torch.empty(shape, dtype=torch.uint8, device=self.device),
+                             torch.empty(shape[:3] + (nd["cout"] // 32,), dtype=torch.uint8, device=self.device))
+            c["vgg_mxfp8"] = mx
+        return mx
+
+    def vgg_mxfp8_weights(self, i):
+        """(q [Cout,k,k,Cin], scale [Cout,k,k,Cin/32]) of fp8 node i as the last fp8 forward quantised them."""
+        nd, (wt, _) = self.nodes[i], self.conv_params[i]
+        q, sc = self._vgg_mx_w
+        o = wt.offset - self._vgg_mx_range[0]
+        shape = (nd["cout"], nd["k"], nd["k"], nd["cin"])
+        return q[o:o + wt.numel].view(shape), sc[o // 32:(o + wt.numel) // 32].view(shape[:3] + (nd["cin"] // 32,))
+
+    def _forward_vgg_mxfp8(self, x):
+        self.vgg_mxfp8_plan()
+        mx = self.vgg_mxfp8_acts(x.shape[0])
+        lo, hi = self._vgg_mx_range
+        if self._vgg_mx_w is None:
+            self._vgg_mx_w = (torch.empty((hi - lo,), dtype=torch.uint8, device=self.device),
+                              torch.empty(((hi - lo) // 32,), dtype=torch.uint8, device=self.device))
+        # quantised at every fp8 forward, nothing cached: no path that writes param_bf16 can leave a stale copy behind
+        ops.quantize_mx_fp8(self.param_bf16[lo:hi], q=self._vgg_mx_w[0], scale=self._vgg_mx_w[1])
+        self._vgg_fp8_fwd = True               # the bf16 maps, ReLU bits and pool codes backward() reads are not all written
+        return self._walk(x, lambda i, c: self._mxfp8_node(i, c, mx))
+
+    def _mxfp8_node(self, i, c, mx):
+        """Launch trunk node i of the fp8 forward: an fp8 convolution (with the pool behind it where the plan fuses one), or
+        node i as the bf16 forward launches it (+ the plan's one standalone quantise of its output)."""
+        fp8, pooled, quant, writes = self._vgg_mx
+        if i in pooled:
+            return                                 # the fp8 convolution in front of it wrote its output
+        if i not in fp8:
+            self._bf16_node(i, c)
+            if i in quant:
+                ops.quantize_mx_fp8(c["acts"][i + 1], q=mx[i][0], scale=mx[i][1])
+            return
+        nd, acts = self.nodes[i], c["acts"]
+        xq, xs = mx[i - 1]
+        wq, ws = self.vgg_mxfp8_weights(i)
+        bias = self.view(self.conv_params[i][1], self.param)
+        args = (xq, xs, wq, ws, bias, nd["stride"], nd["pt"], nd["pl"], nd["hout"], nd["hout"], True)
+        o = i + 1 if i + 1 in pooled else i         # the node whose map this launch writes
+        w = writes[o]
+        q, sc = mx.get(o, (None, None))
+        kw = dict(want_bf16="bf16" in w, want_fp8="fp8" in w, out=acts[o + 1], out_q=q, out_scale=sc)
+        if o != i:
+            pnd = self.nodes[o]
+            ops.conv2d_fwd_pool_mxfp8(*args, pnd["hout"] * 2 != pnd["hin"], **kw)
+        else:
+            ops.conv2d_fwd_mxfp8(*args, **kw)
 
     def head_grad_buffers(self, B):
         """The ops.HeadGradBuffers the loss writes for a batch of B (None when the dense head path is selected)."""
@@ -548,6 +699,9 @@ class SSDEngine:
         return gates
 
     def backward(self, dloc, dconf, on_ready=None, fused_adam=None, heads=None, on_dgrad=None):
+        if self._vgg_fp8_fwd:
+            raise RuntimeError("backward() after an mxfp8 forward: it writes neither the bf16 maps nor the ReLU bits and pool "
+                               "codes backward() reads; run forward(x) in bf16 first")
         try:
             return self._backward(dloc, dconf, on_ready, fused_adam, heads, on_dgrad)
         finally:

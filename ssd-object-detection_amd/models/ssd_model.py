@@ -413,22 +413,28 @@ class SSDObjectDetectionModel:
             raise
 
     # ------------------------------------------------------------------ inference (A9 + A9')
-    def detect(self, image, score_thresh=0.3, iou_thresh=0.45, max_cand=400):
+    def detect(self, image, score_thresh=0.3, iou_thresh=0.45, max_cand=400, precision="bf16"):
         """image f32 [B,300,300,3] in [-1,1] -> (score, cls, box_px, keep) device tensors [B,A(,4)].
-        Scoring/decoding as the reference's visualize(); `keep` adds per-class NMS (no reference counterpart)."""
+        Scoring/decoding as the reference's visualize(); `keep` adds per-class NMS (no reference counterpart).
+        precision="mxfp8": the network forward runs most of its trunk on block-scaled fp8 operands (SSDEngine.forward; no
+        reference counterpart); "bf16" (default) as in training.  Any other value raises ValueError."""
         x = ops.image_prep(image.contiguous(), normalize=False)
-        loc, conf = self._engine.forward(x)
+        loc, conf = self._engine.forward(x, precision)
         score, cls, box, cand = ops.score_decode(conf, loc, self._pset, score_thresh, float(self.cfg.input_shape[0]))
         keep = ops.nms(score, cls, box, cand, iou_thresh, max_cand)
         return score, cls, box, keep
 
-    def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False):
+    def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False,
+                 precision="bf16"):
         """Evaluation pass (the reference fetches its val split at models/ssd_model.py:291 and drops it):
         samples = iterable of (image f32 [S,S,3] in [0,1], cls [n], box [n,4] relative cx,cy,w,h) as the loaders yield
         them.  Network forward, scoring/decoding and per-class NMS run on the device; the kept detections go to
         utils.metrics.coco_map on the host.  Returns its dict (mAP = AP@[.5:.95], AP50, AP75, per_class); with
-        return_detections also the per-image (score, cls, box_px) arrays that were scored."""
+        return_detections also the per-image (score, cls, box_px) arrays that were scored.  precision: detect()'s ("bf16" or
+        "mxfp8")."""
         from ..utils.metrics import coco_map
+        if precision not in ("bf16", "mxfp8"):
+            raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         size = float(self.cfg.input_shape[0])
         dets, gts, buf = [], [], []
 
@@ -436,7 +442,7 @@ class SSDObjectDetectionModel:
             if not buf:
                 return
             img = torch.from_numpy(np.stack([b[0] for b in buf], 0)).to(self.device)
-            score, cls, box, keep = self.detect((img - 0.5) * 2, score_thresh, iou_thresh)
+            score, cls, box, keep = self.detect((img - 0.5) * 2, score_thresh, iou_thresh, precision=precision)
             score, cls, box, keep = score.cpu().numpy(), cls.cpu().numpy(), box.cpu().numpy(), keep.cpu().numpy().astype(bool)
             for i, (_, gcls, gbox) in enumerate(buf):
                 k = keep[i]

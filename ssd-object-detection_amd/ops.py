@@ -825,6 +825,39 @@ def conv2d_fwd_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, w
     return out if want_bf16 else (out_q, out_scale)
 
 
+def conv2d_fwd_pool_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, same, want_bf16=True, want_fp8=False,
+                          out=None, out_q=None, out_scale=None):
+    """conv2d_fwd_mxfp8 (3x3, stride 1) followed by the 2x2 / stride-2 max pool (same: TF-SAME windows clipped at the edge,
+    else VALID) in one launch that never stores the [B,Ho,Wo,Cout] map: maxpool2x2_fwd(conv2d_fwd_mxfp8(...), same) bit for
+    bit.  Returns the pooled outputs asked for: the bf16 map, (q, scale) = its quantize_mx_fp8, or (bf16, q, scale)."""
+    L = _lib.lib()
+    B, H, W, Cin = xq.shape
+    Cout, k = wq.shape[0], wq.shape[1]
+    assert want_bf16 or want_fp8
+    assert wq.shape == (Cout, k, k, Cin) and xs.shape == (B, H, W, Cin // 32) and ws.shape == (Cout, k, k, Cin // 32)
+    for t in (xq, xs, wq, ws):
+        _dev(t, torch.uint8)
+    Hp, Wp = ((Ho + 1) // 2, (Wo + 1) // 2) if same else (Ho // 2, Wo // 2)
+    if want_bf16 and out is None:
+        out = torch.empty((B, Hp, Wp, Cout), dtype=torch.bfloat16, device=xq.device)
+    if want_fp8:
+        if out_q is None:
+            out_q = torch.empty((B, Hp, Wp, Cout), dtype=torch.uint8, device=xq.device)
+        if out_scale is None:
+            out_scale = torch.empty((B, Hp, Wp, max(Cout // 32, 1)), dtype=torch.uint8, device=xq.device)
+    for t in ((out,) if want_bf16 else ()) + ((out_q, out_scale) if want_fp8 else ()):
+        assert t.is_contiguous() and tuple(t.shape[:3]) == (B, Hp, Wp), t.shape
+    rc = L.ssd_conv2d_fwd_pool_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
+                                     _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
+                                     k, stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, Hp, Wp, _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError("pooled block-scaled fp8 forward needs k = 3, stride 1, Cin % 128 == 0 and Cout % 32 == 0")
+    _lib.check(rc)
+    if want_bf16 and want_fp8:
+        return out, out_q, out_scale
+    return out if want_bf16 else (out_q, out_scale)
+
+
 def conv2d_bwd_data_mxfp8(dyq, dys, wtq, wts, relu_src, x_shape, stride, pad_t, pad_l, accumulate=False, want_bf16=True,
                           want_fp8=False, out=None, out_q=None, out_scale=None):
     """conv2d_bwd_data at stride 1 on block-scaled fp8 operands: quantize_mx_fp8 of dy [B,Ho,Wo,Cout] and of the transposed
