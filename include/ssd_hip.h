@@ -324,6 +324,94 @@ int ssd_image_resize_prep(const void* src, const int64_t* src_off, const int32_t
  * divided by the image size (ssd/make_dataset.py:43-44).  gt_off int32 [B+1] as in ssd_match_encode. */
 int ssd_box_prep(const float* box_tlwh, const int32_t* gt_off, const int32_t* src_hw, float* box_out, int B, int total_gt,
                  void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SSD data augmentation for training batches (no reference counterpart: the reference trains without augmentation; this
+ * follows SSD, Liu et al. ECCV 2016 section 3.2, as Caffe-SSD / ssd.pytorch's SSDAugmentation without its channel swap).
+ * Opt-in; tests/augment_oracle.py restates every operation below in numpy, in the same float32 order.
+ *
+ * Recipe, per image, in this order.  All float arithmetic is float32, one rounding per operation, no fused multiply-add;
+ * clamp(x) = min(max(x, 0), 1).
+ *  1. PHOTO, photometric distortion of the source pixels, as values in [0,1] (uint8 / 255 or the f32 source):
+ *       brightness (photo bit 1):  x = clamp(x + delta)
+ *       contrast   (bit 2), before the HSV step when bit 4 is set, after it otherwise:  x = clamp(x * alpha)
+ *       HSV step, only when saturation (bit 8) or hue (bit 16) is on:
+ *         v = max(r,g,b), m = min(r,g,b), d = v - m;  s = v > 0 ? d / v : 0
+ *         h = d == 0 ? 0 : v == r ? 60 * ((g - b) / d) : v == g ? 120 + 60 * ((b - r) / d) : 240 + 60 * ((r - g) / d)
+ *         (ties to r, then g);  h < 0 -> h + 360
+ *         saturation: s = clamp(s * saturation);  hue: h = h + hue, then h >= 360 -> h - 360, h < 0 -> h + 360
+ *         back: q6 = h / 60, i = floor(q6), f = q6 - i, i == 6 -> 0 (h may round to 360);
+ *               p = v * (1 - s), q = v * (1 - s * f), t = v * (1 - s * (1 - f));
+ *               sector 0..5 -> (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q); each channel clamped
+ *  2. EXPAND (zoom out): canvas (canvas_w, canvas_h) = ((int)(ratio * W), (int)(ratio * H)), the image at integer offset
+ *     (off_x, off_y) drawn uniformly in [0, canvas - size]; everything else is the SSD mean (123, 117, 104) / 255 (double
+ *     division rounded to float32), not distorted.  Without expand the canvas is the image.
+ *  3. CROP: mode drawn uniformly from 0..6 = whole image, minimum IoU 0.1 / 0.3 / 0.5 / 0.7 / 0.9, any patch.  For a mode
+ *     other than 0 and an image with at least one box, trials t = 0..49: patch_w = clamp_int((int)(sw * canvas_w), 1,
+ *     canvas_w) with sw = 0.3 + u * 0.7 (patch_h likewise, own draw), rejected unless 2 * patch_h >= patch_w and
+ *     patch_h <= 2 * patch_w, origin drawn uniformly in [0, canvas - patch].  In canvas pixels a box is
+ *         x1 = (cx - w * 0.5) * W + off_x,  x2 = (cx + w * 0.5) * W + off_x,  centre ccx = cx * W + off_x  (y likewise)
+ *     and its IoU with the patch [px, px + pw) x [py, py + ph) is
+ *         iw = max(min(x2, px + pw) - max(x1, px), 0), inter = iw * ih, iou = inter / (((x2 - x1) * (y2 - y1) + pw * ph) - inter)
+ *     A trial is accepted when some box has iou >= the mode's minimum (mode 6: no such condition) and some box centre lies
+ *     strictly inside the patch; the first accepted trial wins, none means no crop (patch = whole canvas).
+ *     Boxes: with a crop, those whose centre lies strictly inside the patch are kept, in input order; without one, all.
+ *     When EXPAND or CROP took effect every kept box is clipped to the patch and made relative to it:
+ *         rx1 = (max(x1, px) - px) / pw,  rx2 = (min(x2, px + pw) - px) / pw,  cx = (rx1 + rx2) * 0.5,  w = rx2 - rx1
+ *     otherwise it passes through unchanged.
+ *  4. FLIP: the output grid is mirrored (output column x reads column S-1-x of the resized patch); cx = 1 - cx.
+ *  5. Resize of the patch to S x S with the INTER_LINEAR rule of ssd_image_resize_prep (scale = patch size / S in double),
+ *     taps clamped inside the patch, horizontal pass first; each tap is the fill or a distorted source pixel.  Then
+ *     (x-0.5)*2 if normalize, bf16 [B,S,S,8] with channels 3..7 zero.
+ * Stage mask bits: SSD_AUG_PHOTO 1, SSD_AUG_EXPAND 2, SSD_AUG_CROP 4, SSD_AUG_FLIP 8.  Mask 0 is the identity:
+ * ssd_image_resize_prep + ssd_box_prep for uint8 sources, (x-0.5)*2 + ssd_image_prep for f32 sources of size S x S.
+ *
+ * Randomness: Philox-4x32-10 (Random123), key = (seed low word, seed high word), counter = (index low word, index high word,
+ * slot, block) with index = first_index + b, the sample's position in the training stream.  u = word >> 8 scaled by 2^-24
+ * is uniform in [0,1); U(lo, hi) = lo + u * (hi - lo); a coin is word >> 31 (1 = apply); an integer in [0, n) is
+ * (word * n) >> 32 in 64 bits.  Slots:
+ *     0  photometric  block 0: brightness coin, delta = (-32 + u * 64) / 255, contrast coin, alpha = 0.5 + u
+ *                     block 1: contrast-first coin, saturation coin, saturation = 0.5 + u, hue coin
+ *                     block 2: hue = -18 + u * 36 (degrees)
+ *     1  expand       coin, ratio = 1 + u * 3, off_x, off_y
+ *     2  mode, flip coin
+ *     3 + t  crop trial t: sw, sh, px, py
+ * A trial's numbers do not depend on earlier rejections: one lane per trial and the lowest accepted lane equal the
+ * sequential loop.  The draws are made whatever the mask; the mask only decides what is applied.
+ *
+ * ssd_augment_plan: two launches of one wave per image (draws and crop search; then offsets and boxes), no host
+ * synchronisation.
+ *   box f32 [total_gt][4] relative (cx, cy, w, h) against src_hw int32 [B][2] (h, w); cls f32 [total_gt]; gt_off int32 [B+1]
+ *   params   [B] ssd_augment_params, what was drawn and applied per image
+ *   box_out / cls_out [total_gt]: the kept boxes compacted in image then input order, off_out int32 [B+1] their offsets;
+ *            rows from off_out[B] up to total_gt are written as zeros.
+ * Bounds contract with ssd_match_encode: it may be called on (box_out, cls_out, off_out) with the un-augmented total_gt and
+ * max_nt, which bound the augmented counts from above: k_match_rows reads every row below total_gt (finite by the above),
+ * the per-image kernels follow off_out, and max_nt only bounds the per-image count (and picks a kernel variant).
+ * ssd_augment_image: one thread per output pixel.  src_kind 0: ragged uint8 as ssd_image_resize_prep (src_off int64 [B]
+ * byte offsets); src_kind 1: f32 images in [0,1], src_off int64 [B] element offsets or NULL for a dense [B,H,W,3]
+ * (image b at b*H*W*3, H and W from src_hw).
+ * Both return SSD_ERR_VALUE before any launch for null pointers, B <= 0, S <= 0, total_gt < 0, unknown stage bits or an
+ * unknown source kind.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum { SSD_AUG_PHOTO = 1, SSD_AUG_EXPAND = 2, SSD_AUG_CROP = 4, SSD_AUG_FLIP = 8, SSD_AUG_ALL = 15 } ssd_augment_stage;
+typedef struct {
+    int32_t stages;            /* stage bits applied: PHOTO as requested; EXPAND, CROP, FLIP where drawn and taken */
+    int32_t mode;              /* crop mode drawn, 0..6 (0 without CROP in the mask) */
+    int32_t trial;             /* accepted crop trial, -1 = none */
+    int32_t photo;             /* photometric bits applied: 1 brightness, 2 contrast, 4 contrast first, 8 saturation, 16 hue */
+    int32_t canvas_w, canvas_h, off_x, off_y;
+    int32_t patch_x, patch_y, patch_w, patch_h;     /* in canvas pixels */
+    int32_t flip;
+    int32_t n_boxes;           /* boxes kept */
+    int32_t reserved[2];
+    float delta, alpha, saturation, hue;            /* drawn values (recorded whether applied or not) */
+} ssd_augment_params;
+int ssd_augment_plan(const float* box, const float* cls, const int32_t* gt_off, const int32_t* src_hw, int B, int total_gt,
+                     int stages, uint64_t seed, int64_t first_index, ssd_augment_params* params, float* box_out,
+                     float* cls_out, int32_t* off_out, void* stream);
+int ssd_augment_image(const void* src, int src_kind, const int64_t* src_off, const int32_t* src_hw,
+                      const ssd_augment_params* params, void* out, int B, int S, int normalize, void* stream);
 /* MaxPool2D 2x2 stride 2 (VGG block pools: VALID; models/ssd_model.py:84: SAME -> Ho = ceil(H/2)) */
 int ssd_maxpool2x2_fwd(const void* x, void* y, int B, int H, int W, int C, int Ho, int Wo, void* stream);
 /* pooling backward fused with the ReLU backward of the layer that produced x */

@@ -32,7 +32,7 @@ _RESTORED = object()                            # _slot_owner marker: Adam momen
 class SSDObjectDetectionModel:
     class TrainConfig:
         def __init__(self, epoch, batch_size, optimizer, warmup=True, warmup_optimizer=None, warmup_step=1000,
-                     visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0):
+                     visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0, augment=None):
             if warmup_optimizer is None:
                 warmup_optimizer = _opt.Adam(_opt.PolynomialDecay(1e-6, 1000, 0.001))
             self.epoch = epoch
@@ -45,6 +45,7 @@ class SSDObjectDetectionModel:
             self.split_batch = split_batch
             self.split_batch_size = split_batch_size
             self.start_epoch = start_epoch                 # > 0: resumed run (no warm-up, epochs start_epoch..epoch-1)
+            self.augment = augment                         # ops.AugmentSpec: SSD data augmentation on the device; None = off
 
     class Config:
         def __init__(self, classes, log_dir):
@@ -98,7 +99,7 @@ class SSDObjectDetectionModel:
             return torch.distributed.get_rank(), torch.distributed.get_world_size()
         return 0, 1
 
-    def get_train_set(self, dataset, batch_size=1, shard=None):
+    def get_train_set(self, dataset, batch_size=1, shard=None, augment=None):
         """Iterable of (image f32[B,300,300,3] in [-1,1], (cls i32[B,A], loc f32[B,A,4], mask u8[B,A])) device
         batches; remainder dropped (reference :209-227: match_bbox -> apply_anchor_box -> (x-0.5)*2 -> batch).
 
@@ -106,7 +107,12 @@ class SSDObjectDetectionModel:
         iterable yields this rank's images of every global batch -- parallel.shard_range, positions
         [rank*b/world, (rank+1)*b/world) -- so all ranks see the same number of batches (the same remainder is dropped)
         and disjoint samples.  Samples of other ranks are skipped without being produced when the dataset offers
-        lazy() (an iterable of zero-argument callables, one per sample, in iteration order)."""
+        lazy() (an iterable of zero-argument callables, one per sample, in iteration order).
+
+        augment (ops.AugmentSpec, no reference counterpart): every batch is augmented on the device and the image comes back as
+        the bf16 network input.  A sample's Philox counter is its position in the stream of samples this iterable produces,
+        counted across batches and passes from augment.first_index, the same on every rank: an image is augmented the same
+        way whatever the world size.  The count restarts with a new iterable (a resumed run does not replay the stream)."""
         model = self
         rank, world = shard if shard is not None else self._rank_world()
         assert batch_size % world == 0, "the global batch must divide evenly over the ranks"
@@ -114,6 +120,8 @@ class SSDObjectDetectionModel:
         raw = bool(getattr(dataset, "raw", False))     # reader-contract samples: /255, resize, box normalisation on the device
 
         class _Batches:
+            produced = 0                               # samples of the global stream yielded so far (all ranks alike)
+
             def __iter__(self_inner):
                 thunks = dataset.lazy() if hasattr(dataset, "lazy") else ((lambda s=s: s) for s in dataset)
                 mine, pos = [], 0
@@ -128,7 +136,13 @@ class SSDObjectDetectionModel:
                             imgs.append(np.asarray(image) if raw else np.asarray(image, np.float32))
                             clss.append(np.asarray(cls, np.float32))
                             boxes.append(np.asarray(box, np.float32))
-                        yield model.make_batch_raw(imgs, clss, boxes) if raw else model.make_batch(imgs, clss, boxes)
+                        make = model.make_batch_raw if raw else model.make_batch
+                        if augment is None:
+                            yield make(imgs, clss, boxes)
+                        else:
+                            first = augment.first_index + self_inner.produced + lo
+                            self_inner.produced += batch_size
+                            yield make(imgs, clss, boxes, augment=augment.at(first))
                         mine, pos = [], 0
 
         return _Batches()
@@ -154,18 +168,37 @@ class SSDObjectDetectionModel:
             self._targets_event.record(side)
         return out
 
-    def make_batch(self, images, cls_list, box_list):
+    def make_batch(self, images, cls_list, box_list, augment=None):
+        """augment (ops.AugmentSpec): SSD data augmentation of the batch on the device (include/ssd_hip.h); the image then
+        comes back as the bf16 network input [B,S,S,8], images f32 [H,W,3] in [0,1] of any one size."""
         img = torch.from_numpy(np.stack(images, 0)).to(self.device, non_blocking=True)
+        if augment is not None:
+            B, H, W = img.shape[0], img.shape[1], img.shape[2]
+            hw = torch.tensor([[H, W]] * B, dtype=torch.int32).to(self.device)
+            return self._augmented(img.contiguous(), 1, None, hw, box_list, cls_list, augment)
         img = (img - 0.5) * 2                          # reference :214 (exact in fp32); get_train_set's contract is f32
         gt = ops.pack_gt(box_list, cls_list, device=self.device)
         cls, loc, mask = ops.match_encode(*gt, self._pset, self.cfg.thresh)
         return img, (cls, loc, mask)
 
-    def make_batch_raw(self, images_u8, cls_list, box_tlwh_list):
+    def _augmented(self, src, kind, src_off, hw_d, box_list, cls_list, augment, tlwh=False):
+        """Augment a batch (boxes relative cx,cy,w,h, or COCO pixels with tlwh) and assign its targets.  match_encode gets
+        the un-augmented total and max_nt: upper bounds of the kept boxes, which is all it needs (include/ssd_hip.h)."""
+        gt_box, gt_cls, gt_off, total, max_nt = ops.pack_gt(box_list, cls_list, device=self.device)
+        if tlwh and total:
+            gt_box = ops.box_prep(gt_box, gt_off, hw_d)
+        params, box, cls_, off = ops.augment_plan(gt_box, gt_cls, gt_off, hw_d, total, augment.stages, augment.seed,
+                                                  augment.first_index)
+        x = ops.augment_image(src, kind, src_off, hw_d, params, int(self.cfg.input_shape[0]), True)
+        cls, loc, mask = ops.match_encode(box, cls_, off, total, max_nt, self._pset, self.cfg.thresh)
+        return x, (cls, loc, mask)
+
+    def make_batch_raw(self, images_u8, cls_list, box_tlwh_list, augment=None):
         """The same from what the COCO reader yields before any preprocessing: decoded uint8 RGB images
         of arbitrary sizes and COCO [x, y, w, h] pixel boxes.  '/255', cv2.resize to the network size, '(x-0.5)*2'
         (reference data_loaders/coco/make_dataset.py:117, data_loaders/ssd/make_dataset.py:40-44, models/ssd_model.py:214)
-        and the box conversion run on the device; returns the prepared bf16 network input instead of the f32 image."""
+        and the box conversion run on the device; returns the prepared bf16 network input instead of the f32 image.
+        augment (ops.AugmentSpec): SSD data augmentation on the device as well (include/ssd_hip.h)."""
         hw = np.array([im.shape[:2] for im in images_u8], np.int32)
         sizes = [int(im.size) for im in images_u8]
         off = np.zeros(len(sizes), np.int64)
@@ -173,6 +206,9 @@ class SSDObjectDetectionModel:
         flat = np.concatenate([np.ascontiguousarray(im, np.uint8).reshape(-1) for im in images_u8])
         dev = self.device
         hw_d = torch.from_numpy(hw).to(dev)
+        if augment is not None:
+            return self._augmented(torch.from_numpy(flat).to(dev), 0, torch.from_numpy(off).to(dev), hw_d, box_tlwh_list,
+                                   cls_list, augment, tlwh=True)
         x = ops.image_resize_prep(torch.from_numpy(flat).to(dev), torch.from_numpy(off).to(dev), hw_d,
                                   int(self.cfg.input_shape[0]), True)
         gt_box, gt_cls, gt_off, total, max_nt = ops.pack_gt(box_tlwh_list, cls_list, device=dev)
@@ -327,7 +363,7 @@ class SSDObjectDetectionModel:
     def _train(self, data_loader, cfg):
         train_set, _val_set = data_loader.get_dataset()
         set_names, set_colors = data_loader.get_names_and_colors()
-        batches = self.get_train_set(train_set, batch_size=cfg.batch_size)
+        batches = self.get_train_set(train_set, batch_size=cfg.batch_size, augment=getattr(cfg, "augment", None))
         self._assert_replicas_identical()
         self._scalars = ScalarLog(self.cfg.log_dir, self.device, distributed=self.distributed,
                                   console_interval=cfg.visualization_log_interval, logger=logger)

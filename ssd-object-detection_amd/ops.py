@@ -709,6 +709,79 @@ def box_prep(box_tlwh, gt_off, src_hw):
     return out
 
 
+AUG_PHOTO, AUG_EXPAND, AUG_CROP, AUG_FLIP = 1, 2, 4, 8
+AUG_ALL = AUG_PHOTO | AUG_EXPAND | AUG_CROP | AUG_FLIP
+# one ssd_augment_params record (include/ssd_hip.h): 16 int32 fields, then 4 float32
+AUG_PARAM_FIELDS = ("stages", "mode", "trial", "photo", "canvas_w", "canvas_h", "off_x", "off_y", "patch_x", "patch_y",
+                    "patch_w", "patch_h", "flip", "n_boxes", "reserved0", "reserved1", "delta", "alpha", "saturation", "hue")
+AUG_PARAM_DTYPE = np.dtype([(n, np.int32) for n in AUG_PARAM_FIELDS[:16]] + [(n, np.float32) for n in AUG_PARAM_FIELDS[16:]])
+
+
+class AugmentSpec:
+    """Training-batch augmentation (include/ssd_hip.h has the recipe): Philox seed, stage mask (AUG_* bits, default all four)
+    and the global stream index of the batch's first sample.  get_train_set fills in first_index per batch."""
+
+    def __init__(self, seed=0, stages=AUG_ALL, first_index=0):
+        if int(stages) & ~AUG_ALL:
+            raise ValueError("unknown augmentation stage bits %#x" % int(stages))
+        self.seed = int(seed)
+        self.stages = int(stages)
+        self.first_index = int(first_index)
+
+    def at(self, first_index):
+        return AugmentSpec(self.seed, self.stages, first_index)
+
+    def __repr__(self):
+        return "AugmentSpec(seed=%d, stages=%d, first_index=%d)" % (self.seed, self.stages, self.first_index)
+
+
+def augment_plan(box, cls, gt_off, src_hw, total_gt, stages, seed, first_index):
+    """ssd_augment_plan: per-image augmentation draws, crop search and box transform on the device, no host sync.
+    box f32 [total_gt,4] relative (cx,cy,w,h), cls f32 [total_gt], gt_off i32 [B+1], src_hw i32 [B,2] (h, w).
+    Returns (params u8 [B, 80] ssd_augment_params records, box_out f32 [total_gt,4], cls_out f32 [total_gt], off_out i32 [B+1]):
+    the kept boxes compacted per image, zero rows after off_out[B]."""
+    L = _lib.lib()
+    _dev(gt_off, torch.int32); _dev(src_hw, torch.int32)
+    B = src_hw.shape[0]
+    dev = src_hw.device
+    if total_gt > 0:
+        _dev(box, torch.float32); _dev(cls, torch.float32)
+    params = torch.empty((B, AUG_PARAM_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    box_out = torch.empty((total_gt, 4), dtype=torch.float32, device=dev)
+    cls_out = torch.empty((total_gt,), dtype=torch.float32, device=dev)
+    off_out = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    _lib.check(L.ssd_augment_plan(_ptr(box if total_gt > 0 else None), _ptr(cls if total_gt > 0 else None), _ptr(gt_off),
+                                  _ptr(src_hw), B, int(total_gt), int(stages), int(seed) & (2 ** 64 - 1), int(first_index),
+                                  _ptr(params), _ptr(box_out if total_gt > 0 else None),
+                                  _ptr(cls_out if total_gt > 0 else None), _ptr(off_out), _stream()))
+    return params, box_out, cls_out, off_out
+
+
+def augment_params_numpy(params):
+    """Device params records (augment_plan) -> numpy structured array of AUG_PARAM_DTYPE."""
+    return params.cpu().numpy().view(AUG_PARAM_DTYPE).reshape(-1)
+
+
+def augment_image(src, src_kind, src_off, src_hw, params, S=300, normalize=True, out=None):
+    """ssd_augment_image: the planned augmentation of every image, resized to S x S -> bf16 [B,S,S,8].
+    src_kind 0: flat uint8 buffer of the ragged batch with src_off i64 [B] byte offsets (as image_resize_prep);
+    src_kind 1: f32 [B,H,W,3] in [0,1] (src_off None)."""
+    L = _lib.lib()
+    _dev(src_hw, torch.int32); _dev(params, torch.uint8)
+    if src_kind == 0:
+        _dev(src, torch.uint8); _dev(src_off, torch.int64)
+    elif src_kind == 1:
+        _dev(src, torch.float32)
+    B = src_hw.shape[0]
+    assert params.shape == (B, AUG_PARAM_DTYPE.itemsize)
+    if out is None:
+        out = torch.empty((B, S, S, 8), dtype=torch.bfloat16, device=src_hw.device)
+    assert out.shape == (B, S, S, 8) and out.dtype == torch.bfloat16 and out.is_contiguous()
+    _lib.check(L.ssd_augment_image(_ptr(src), int(src_kind), _ptr(src_off), _ptr(src_hw), _ptr(params), _ptr(out), B, int(S),
+                                   1 if normalize else 0, _stream()))
+    return out
+
+
 def maxpool2x2_fwd(x, same=False):
     L = _lib.lib()
     _bf(x)

@@ -41,6 +41,16 @@ def cfg_get(config, path):
     return node
 
 
+def augment_from_config(config):
+    """`data: augment: {enable, seed}` (no reference counterpart) -> ops.AugmentSpec with all four stages, or None when the
+    key is absent or enable is false: the default trains without augmentation, as the reference does."""
+    section = (config.get("data") or {}).get("augment")
+    if not section or not section.get("enable", False):
+        return None
+    from ..ops import AugmentSpec
+    return AugmentSpec(seed=int(section.get("seed", 0) or 0))
+
+
 def _make_optimizer(section, schedule):
     from .. import optimizers
     kinds = {"adam": optimizers.Adam, "sgd": optimizers.SGD}
@@ -108,7 +118,8 @@ def train(config):
             f.write(text)
 
     fields = {name: cfg_get(config, path) for name, path in TRAIN_CONFIG_KEYS.items()}
-    fields.update(optimizer=optimizer, warmup_optimizer=warmup_optimizer, start_epoch=start_epoch)
+    fields.update(optimizer=optimizer, warmup_optimizer=warmup_optimizer, start_epoch=start_epoch,
+                  augment=augment_from_config(config))
     model.train(data_loader=data, cfg=SSDObjectDetectionModel.TrainConfig(**fields))
     model.save(os.path.join(model.get_log_dir(), model_cfg["save"]))      # rank 0 writes; the others wait
     return model
