@@ -201,6 +201,42 @@ int ssd_nms(const float* score, const int32_t* cls, const float* box, const uint
             float iou_thresh, int max_cand, uint8_t* keep, int32_t* keep_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation metric on the device (no reference counterpart: the reference fetches its validation split at
+ * models/ssd_model.py:291 and drops it).  Build-defined; the definition and oracle is utils/metrics.py:coco_map -- COCO
+ * AP@[.50:.05:.95] for boxes without crowd regions or area ranges.
+ *
+ * ssd_eval_match: one launch per evaluated batch, consuming what ssd_score_decode + ssd_nms leave in memory.
+ *   score float[B*A], cls int32[B*A], box float[B*A*4] (cx,cy,w,h pixels), keep uint8[B*A]
+ *   gt_cls int32[total_gt], gt_box double[total_gt*4] (cx,cy,w,h pixels), gt_off int32[B+1] (CSR, as ssd_match_encode);
+ *          gt_cls / gt_box may be NULL when gt_off[B] == 0.  Any number of boxes per image.
+ *   iou_thresholds HOST double[10] (np.linspace(0.5, 0.95, 10): passed in, not recomputed)
+ *   max_dets  1 .. ssd_eval_max_dets() (128)
+ * Per image: the kept anchors ordered by (score desc, anchor asc), cut to the first max_dets; then per threshold and class
+ * the detections in that order each claim, among the image's still-unclaimed boxes of their class, the one with the highest
+ * IoU >= threshold, the LAST index winning among equal IoUs.  IoU is utils/metrics.py:iou_matrix in float64, operation for
+ * operation, without fused multiply-adds: flags are bit-exact against the definition.
+ *   n_det int32[B]; det_score float[B*max_dets], det_cls int32[B*max_dets], det_box float[B*max_dets*4],
+ *   det_flags uint16[B*max_dets] (bit t: true positive at threshold t).  All fully written; slots at or beyond n_det hold
+ *   score 0, class -1, box 0, flags 0.
+ *
+ * ssd_eval_ap: after the last batch, from all rows sorted by (class asc, score desc, image asc, rank asc).
+ *   flags_sorted uint16[N] (not NULL, even for N = 0), seg_off int32[C+1] (class c owns rows seg_off[c] .. seg_off[c+1]-1),
+ *   n_gt int32[C] ground truths per class, recall_points HOST double[101] (np.linspace(0, 1, 101))
+ *   ap double[C*10]: 101-point interpolated AP per (class, threshold) -- cumulative TP / FP, recall = ctp / n_gt, precision
+ *   = ctp / max(ctp + cfp, 1) made monotone from the right, sampled at the first index whose recall >= each point (0 where
+ *   none), mean of the samples summed in numpy's pairwise order.  0 for classes with n_gt == 0 (the caller leaves them out
+ *   of its means) and for classes without detections.  Segments of any length.
+ * Both return SSD_ERR_VALUE before any launch for B <= 0, A <= 0, C <= 0, max_dets out of range or a NULL pointer.
+ * ---------------------------------------------------------------------------------------- */
+int ssd_eval_max_dets(void);
+int ssd_eval_match(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
+                   const int32_t* gt_cls, const double* gt_box, const int32_t* gt_off, const double* iou_thresholds,
+                   int max_dets, int32_t* n_det, float* det_score, int32_t* det_cls, float* det_box, uint16_t* det_flags,
+                   void* stream);
+int ssd_eval_ap(const uint16_t* flags_sorted, const int32_t* seg_off, const int32_t* n_gt, int C, const double* recall_points,
+                double* ap, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Convolution stack (NHWC bf16 activations, bf16 weights [Cout][k][k][Cin], fp32 accumulate on MFMA).
  * Replaces the TensorFlow kernels behind SSDObjectDetectionModel._build (models/ssd_model.py:74-171)
  * and behind tape.gradient (:248) for those layers.  TF "SAME" padding is passed explicitly:

@@ -89,6 +89,10 @@ _SIGNATURES = {
                                         ctypes.c_float, ctypes.c_double, VP, VP, VP, VP, VP]),
     "ssd_nms_max_candidates": (ctypes.c_int, []),
     "ssd_nms": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, VP, VP, VP]),
+    "ssd_eval_max_dets": (ctypes.c_int, []),
+    "ssd_eval_match": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP, VP, VP, _c_double_p, ctypes.c_int,
+                                      VP, VP, VP, VP, VP, VP]),
+    "ssd_eval_ap": (ctypes.c_int, [VP, VP, VP, ctypes.c_int, _c_double_p, VP, VP]),
     "ssd_conv2d_fwd": (ctypes.c_int, [VP, VP, VP, VP] + [ctypes.c_int] * 12 + [VP, ctypes.c_size_t, VP]),
     "ssd_conv2d_fwd_pool": (ctypes.c_int, [VP, VP, VP, VP, VP, VP] + [ctypes.c_int] * 14 + [VP, ctypes.c_size_t, VP]),
     "ssd_conv2d_head_fwd": (ctypes.c_int, [VP, VP, VP, VP, VP] + [ctypes.c_int] * 8 + [VP, ctypes.c_size_t, VP]),

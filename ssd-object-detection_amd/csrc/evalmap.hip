@@ -1,0 +1,415 @@
+// Evaluation metric on the device for gfx950 (MI355X): the last stage behind k_score_decode + k_nms (detect.hip).
+//
+//   k_eval_match  per image: the kept anchors ordered by (score desc, anchor asc), cut to the first max_dets -- the order
+//                 utils/metrics.coco_map gets from its stable sort of the anchor-ordered kept list -- then, per class and per
+//                 IoU threshold, coco_map's greedy pass: detections in that order, each claims the still-unclaimed ground truth
+//                 of its class with the highest IoU >= threshold, the LAST index winning among equal IoUs.  One workgroup per
+//                 image: candidate list (LDS atomics), exact radix cut when more than CAP anchors are kept, rank sort of 64-bit
+//                 keys (~score | anchor), rank sort by (class, rank) for the class segments, then one THREAD per (class
+//                 segment, threshold) walks its segment.  With at most GL ground truths in the image (nearly always) every
+//                 class-matched IoU is computed once, by all threads, into an LDS matrix and the claimed set is a register
+//                 mask; with more, the walking thread computes IoUs as it goes and finds claimed boxes in the per-detection
+//                 match list -- slower, no bound on the number of ground truths.
+//   k_eval_ap     per class: 101-point AP at the ten thresholds from the flags sorted by (class, score desc, image, rank).
+//                 The segment is scanned in chunks of one element per thread (ballot prefix counts of the ten flag bits, one
+//                 load serves all thresholds).  Only true positives can raise the right-to-left precision envelope, so each
+//                 contributes precision = ctp / (i + 1) to the LAST recall point <= its recall (LDS 64-bit max on the bits of a
+//                 non-negative double); a suffix maximum over the 101 buckets is the sampled envelope.
+// IoU is utils/metrics.iou_matrix operation for operation in float64.  Compile with -ffp-contract=off.
+#include "common.h"
+#include <limits.h>
+
+namespace {
+
+constexpr int WG = 1024;                     // one key per thread in the rank sort
+constexpr int CAP = 1024;                    // kept anchors that are sorted in LDS without the radix cut (k_nms keeps <= 1024)
+constexpr int MAXD = 128;                    // ssd_eval_max_dets()
+constexpr int GL = 48;                       // ground truths per image whose IoUs are cached in LDS
+constexpr int NT = 10;                       // IoU thresholds
+constexpr int NP = 101;                      // recall points
+
+struct Thresholds { double v[NT]; };
+struct RecallPoints { double v[NP]; };
+
+// float bits -> unsigned, order preserving (-0 ordered as +0: numpy compares them equal)
+__device__ __forceinline__ unsigned ordered_bits(float s) {
+    const unsigned u = __float_as_uint(s + 0.0f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// exclusive prefix of a 0/1 flag over the workgroup (index order), and the total
+__device__ __forceinline__ int wg_prefix(bool flag, int* s_wave, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < WG / 64; ++w) {
+        if (w < wave) base += s_wave[w];
+        total += s_wave[w];
+    }
+    return base + before;
+}
+
+// metrics.iou_matrix for one pair: detection (cx, cy, w, h) float32 widened exactly, ground truth float64
+__device__ __forceinline__ double iou_f64(float4 d, double gx, double gy, double gw, double gh) {
+    const double dx = (double)d.x, dy = (double)d.y, dw = (double)d.z, dh = (double)d.w;
+    const double a0 = dx - dw / 2, a1 = dy - dh / 2, a2 = dx + dw / 2, a3 = dy + dh / 2;
+    const double b0 = gx - gw / 2, b1 = gy - gh / 2, b2 = gx + gw / 2, b3 = gy + gh / 2;
+    const double w = fmax(fmin(a2, b2) - fmax(a0, b0), 0.0);
+    const double h = fmax(fmin(a3, b3) - fmax(a1, b1), 0.0);
+    const double inter = w * h;
+    const double area_a = (a2 - a0) * (a3 - a1);
+    const double area_b = (b2 - b0) * (b3 - b1);
+    const double uni = area_a + area_b - inter;
+    return uni > 0.0 ? inter / fmax(uni, 1e-300) : 0.0;
+}
+
+__global__ __launch_bounds__(WG) void k_eval_match(const float* __restrict__ score, const int* __restrict__ cls,
+                                                   const float4* __restrict__ box, const uint8_t* __restrict__ keep, int A,
+                                                   const int* __restrict__ gt_cls, const double* __restrict__ gt_box,
+                                                   const int* __restrict__ gt_off, Thresholds thr, int max_dets,
+                                                   int* __restrict__ n_det, float* __restrict__ det_score,
+                                                   int* __restrict__ det_cls, float4* __restrict__ det_box,
+                                                   uint16_t* __restrict__ det_flags) {
+    // s_big: the sort keys [CAP] u64 + the candidate list [CAP] int during the selection, the IoU matrix [MAXD][GL] afterwards
+    __shared__ __attribute__((aligned(16))) double s_big[MAXD * GL];
+    __shared__ float4 s_dbox[MAXD];
+    __shared__ int s_dcls[MAXD];
+    __shared__ int s_danchor[MAXD];
+    __shared__ unsigned s_flags[MAXD];
+    __shared__ int s_ord[MAXD];                  // detection ranks ordered by (class, rank)
+    __shared__ int s_seg[MAXD];                  // first position in s_ord of every class segment (any order)
+    __shared__ int s_match[NT][MAXD];            // uncached mode: ground truth claimed by the detection at a position, -1 none
+    __shared__ double s_gbox[GL][4];
+    __shared__ int s_gcls[GL];
+    __shared__ int s_hist[256];
+    __shared__ int s_wave[WG / 64];
+    __shared__ int s_misc[4];
+    static_assert(sizeof(double) * MAXD * GL >= CAP * (sizeof(unsigned long long) + sizeof(int)), "keys + list fit");
+    unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_big);
+    int* s_idx = reinterpret_cast<int*>(s_key + CAP);
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t off = (size_t)b * A;
+    const float* sc = score + off;
+    const uint8_t* kp = keep + off;
+
+    if (tid < 4) s_misc[tid] = 0;
+    if (tid < MAXD) s_flags[tid] = 0u;
+    __syncthreads();
+    // the kept anchors, unordered (the sort orders them completely: the anchor index is part of the key)
+    auto note = [&](int a) {
+        const int slot = atomicAdd(&s_misc[0], 1);
+        if (slot < CAP) s_idx[slot] = a;
+    };
+    if ((A & 3) == 0) {                          // rows of keep are 4-byte aligned: four anchors per load
+        const unsigned* kp4 = reinterpret_cast<const unsigned*>(kp);
+        const int nq = A >> 2;
+        for (int q = tid; q < nq; q += WG) {
+            const unsigned v = kp4[q];
+            if (!v) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if ((v >> (8 * e)) & 0xffu) note(4 * q + e);
+        }
+    } else {
+        for (int a = tid; a < A; a += WG)
+            if (kp[a]) note(a);
+    }
+    __syncthreads();
+    const int total = s_misc[0];
+    int n_in;                                    // keys that enter the sort
+    if (total <= CAP) {
+        n_in = total;
+        if (tid < total) {
+            const int a = s_idx[tid];
+            s_key[tid] = ((unsigned long long)(~ordered_bits(sc[a])) << 32) | (unsigned long long)(unsigned)a;
+        }
+    } else {
+        // more kept anchors than sort slots (not what k_nms produces): exact cut to the max_dets best by radix select on the
+        // ordered score bits, then their ordered compaction -- k_nms's cut
+        unsigned prefix = 0;
+        int k = max_dets;                        // rank (1-based, from the top) still to locate
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) s_hist[tid] = 0;
+            __syncthreads();
+            for (int a = tid; a < A; a += WG)
+                if (kp[a]) {
+                    const unsigned key = ordered_bits(sc[a]);
+                    if (shift == 24 || (key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
+                }
+            __syncthreads();
+            if (tid == 0) {
+                int run = 0, d = 255;
+                for (; d > 0; --d) {
+                    if (run + s_hist[d] >= k) break;
+                    run += s_hist[d];
+                }
+                s_misc[1] = d;
+                s_misc[2] = k - run;
+            }
+            __syncthreads();
+            prefix = (prefix << 8) | (unsigned)s_misc[1];
+            k = s_misc[2];
+            __syncthreads();
+        }
+        const unsigned cut_bits = prefix;        // take score > cut, and the first `k` (anchor order) with score == cut
+        int filled = 0, eq_seen = 0;
+        for (int a0 = 0; a0 < A; a0 += WG) {
+            const int a = a0 + tid;
+            bool is_c = a < A && kp[a];
+            const unsigned key = is_c ? ordered_bits(sc[a]) : 0u;
+            const bool is_eq = is_c && key == cut_bits;
+            is_c = is_c && key >= cut_bits;
+            int tot_eq = 0;
+            const int eq_rank = wg_prefix(is_eq, s_wave, tot_eq);
+            if (is_eq && eq_seen + eq_rank >= k) is_c = false;
+            eq_seen += tot_eq;
+            int tot = 0;
+            const int pos = wg_prefix(is_c, s_wave, tot);
+            if (is_c && filled + pos < CAP)
+                s_key[filled + pos] = ((unsigned long long)(~key) << 32) | (unsigned long long)(unsigned)a;
+            filled += tot;
+        }
+        n_in = min(filled, max_dets);            // == max_dets
+    }
+    __syncthreads();
+    // sort by rank: keys are unique, every thread counts the keys below its own (broadcast LDS reads)
+    const int nd = min(n_in, max_dets);
+    {
+        const unsigned long long mine = tid < n_in ? s_key[tid] : ~0ull;
+        int rank = 0;
+        for (int j = 0; j < n_in; ++j) rank += s_key[j] < mine ? 1 : 0;
+        if (tid < n_in && rank < nd) s_danchor[rank] = (int)(unsigned)(mine & 0xffffffffull);
+    }
+    __syncthreads();                             // s_key / s_idx are dead from here on
+    // the detections: outputs fully written (slots at or beyond nd: score 0, class -1, box 0)
+    if (tid < max_dets) {
+        const size_t o = (size_t)b * max_dets + tid;
+        float s = 0.f;
+        int c = -1;
+        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < nd) {
+            const int a = s_danchor[tid];
+            s = sc[a];
+            c = cls[off + a];
+            bx = box[off + a];
+            s_dcls[tid] = c;
+            s_dbox[tid] = bx;
+        }
+        det_score[o] = s;
+        det_cls[o] = c;
+        det_box[o] = bx;
+    }
+    if (tid == 0) n_det[b] = nd;
+    __syncthreads();
+    // class segments: position of a detection among those ordered by (class, rank)
+    if (tid < nd) {
+        const int c = s_dcls[tid];
+        int pos = 0;
+        for (int r = 0; r < nd; ++r) {
+            const int cr = s_dcls[r];
+            pos += (cr < c || (cr == c && r < tid)) ? 1 : 0;
+        }
+        s_ord[pos] = tid;
+    }
+    __syncthreads();
+    if (tid < nd) {
+        const bool start = tid == 0 || s_dcls[s_ord[tid]] != s_dcls[s_ord[tid - 1]];
+        if (start) s_seg[atomicAdd(&s_misc[3], 1)] = tid;
+    }
+    const int g0 = gt_off[b];
+    const int G = max(gt_off[b + 1] - g0, 0);
+    const bool cached = G <= GL;
+    double* s_iou = s_big;
+    if (cached) {
+        if (tid < G) {
+            s_gcls[tid] = gt_cls[g0 + tid];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s_gbox[tid][e] = gt_box[4 * (size_t)(g0 + tid) + e];
+        }
+        __syncthreads();
+        // every class-matched IoU once
+        for (int p = tid; p < nd * G; p += WG) {
+            const int r = p / G, j = p - r * G;
+            if (s_gcls[j] == s_dcls[r])
+                s_iou[r * GL + j] = iou_f64(s_dbox[r], s_gbox[j][0], s_gbox[j][1], s_gbox[j][2], s_gbox[j][3]);
+        }
+    }
+    __syncthreads();
+    const int nseg = s_misc[3];
+    // the greedy pass: one thread per (class segment, threshold)
+    if (nd > 0 && G > 0) {
+        for (int w = tid; w < nseg * NT; w += WG) {
+            const int sg = w / NT, t = w - sg * NT;
+            const int p0 = s_seg[sg];
+            const int c = s_dcls[s_ord[p0]];
+            const double th = thr.v[t];
+            if (cached) {
+                unsigned long long mine = 0ull;      // ground truths of this class
+                for (int j = 0; j < G; ++j) mine |= (s_gcls[j] == c) ? (1ull << j) : 0ull;
+                if (!mine) continue;
+                unsigned long long taken = 0ull;
+                for (int p = p0; p < nd; ++p) {
+                    const int r = s_ord[p];
+                    if (s_dcls[r] != c) break;
+                    double best = th;
+                    int bj = -1;
+                    unsigned long long open = mine & ~taken;
+                    while (open) {                   // ascending j, >=: the last index wins among equal IoUs
+                        const int j = __ffsll((long long)open) - 1;
+                        open &= open - 1ull;
+                        const double v = s_iou[r * GL + j];
+                        if (v >= best) { best = v; bj = j; }
+                    }
+                    if (bj >= 0) {
+                        taken |= 1ull << bj;
+                        atomicOr(&s_flags[r], 1u << t);
+                    }
+                }
+            } else {
+                for (int p = p0; p < nd; ++p) {
+                    const int r = s_ord[p];
+                    if (s_dcls[r] != c) break;
+                    const float4 d = s_dbox[r];
+                    double best = th;
+                    int bj = -1;
+                    for (int j = 0; j < G; ++j) {
+                        if (gt_cls[g0 + j] != c) continue;
+                        const double* g = gt_box + 4 * (size_t)(g0 + j);
+                        const double v = iou_f64(d, g[0], g[1], g[2], g[3]);
+                        if (!(v >= best)) continue;
+                        bool taken = false;          // claimed by an earlier detection of the segment?
+                        for (int q = p0; q < p && !taken; ++q) taken = s_match[t][q] == j;
+                        if (!taken) { best = v; bj = j; }
+                    }
+                    s_match[t][p] = bj;
+                    if (bj >= 0) atomicOr(&s_flags[r], 1u << t);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < max_dets) det_flags[(size_t)b * max_dets + tid] = tid < nd ? (uint16_t)s_flags[tid] : (uint16_t)0;
+}
+
+// AP of one class at the ten thresholds.  flags: every detection of the data set, sorted; seg_off[c] .. seg_off[c+1] the class's
+// rows.  Any segment length: chunks of one element per thread, running counts carried in registers.
+constexpr int AWG = 256;                    // four waves: ten running counts per thread and the wave totals stay in registers
+__global__ __launch_bounds__(AWG) void k_eval_ap(const uint16_t* __restrict__ flags, const int* __restrict__ seg_off,
+                                                const int* __restrict__ n_gt, RecallPoints pts, double* __restrict__ ap) {
+    __shared__ unsigned long long s_best[NT][NP];    // bits of the best precision whose last recall point <= recall is k
+    __shared__ double s_pts[NP];
+    __shared__ int s_wtot[2][AWG / 64][NT];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ngt = n_gt[c];
+    if (ngt <= 0) {                                  // not part of any mean (the caller excludes it)
+        if (tid < NT) ap[(size_t)c * NT + tid] = 0.0;
+        return;
+    }
+    for (int i = tid; i < NT * NP; i += AWG) (&s_best[0][0])[i] = 0ull;
+    if (tid == 0) {                                  // constant indices: a lane-indexed read would copy the argument to scratch
+#pragma unroll
+        for (int k = 0; k < NP; ++k) s_pts[k] = pts.v[k];
+    }
+    const long long lo = seg_off[c], hi = seg_off[c + 1];
+    const double dngt = (double)ngt;
+    int carry[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) carry[t] = 0;
+    __syncthreads();
+    int par = 0;
+    for (long long i0 = lo; i0 < hi; i0 += AWG, par ^= 1) {
+        const long long i = i0 + tid;
+        const unsigned f = i < hi ? (unsigned)flags[i] : 0u;
+        int incl[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const unsigned long long m = __ballot((f >> t) & 1u);
+            incl[t] = __popcll(m & ((2ull << lane) - 1ull));
+            if (lane == 0) s_wtot[par][wave][t] = __popcll(m);
+        }
+        __syncthreads();                             // (double-buffered totals: one barrier per chunk)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            int base = carry[t], tot = 0;
+#pragma unroll
+            for (int w = 0; w < AWG / 64; ++w) {
+                const int v = s_wtot[par][w][t];
+                if (w < wave) base += v;
+                tot += v;
+            }
+            carry[t] += tot;
+            if ((f >> t) & 1u) {
+                const int ctp = base + incl[t];
+                const double prec = (double)ctp / (double)(i - lo + 1);
+                const double rec = (double)ctp / dngt;
+                int a = 0, z = NP - 1;               // last k with pts[k] <= rec (pts[0] = 0 <= rec)
+                while (a < z) {
+                    const int mid = (a + z + 1) >> 1;
+                    if (s_pts[mid] <= rec) a = mid; else z = mid - 1;
+                }
+                atomicMax(&s_best[t][a], (unsigned long long)__double_as_longlong(prec));
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < NT) {
+        // sampled envelope = suffix maximum over the buckets; mean of the 101 samples summed in numpy's order (pairwise
+        // summation of a block below 128 elements: eight running sums, combined as a tree, then the remainder in order)
+        unsigned long long* row = s_best[tid];
+        unsigned long long run = 0ull;
+        for (int k = NP - 1; k >= 0; --k) {
+            run = row[k] > run ? row[k] : run;
+            row[k] = run;
+        }
+        double r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = __longlong_as_double((long long)row[j]);
+        int k = 8;
+        for (; k + 8 <= NP; k += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] += __longlong_as_double((long long)row[k + j]);
+        }
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; k < NP; ++k) res += __longlong_as_double((long long)row[k]);
+        ap[(size_t)c * NT + tid] = res / (double)NP;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssd_eval_max_dets(void) { return MAXD; }
+
+int ssd_eval_match(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
+                   const int32_t* gt_cls, const double* gt_box, const int32_t* gt_off, const double* iou_thresholds,
+                   int max_dets, int32_t* n_det, float* det_score, int32_t* det_cls, float* det_box, uint16_t* det_flags,
+                   void* stream) {
+    if (B <= 0 || A <= 0 || max_dets <= 0 || max_dets > MAXD) return SSD_ERR_VALUE;
+    if (!score || !cls || !box || !keep || !gt_off || !iou_thresholds) return SSD_ERR_VALUE;
+    if (!n_det || !det_score || !det_cls || !det_box || !det_flags) return SSD_ERR_VALUE;
+    Thresholds thr;
+    for (int t = 0; t < NT; ++t) thr.v[t] = iou_thresholds[t];
+    hipLaunchKernelGGL(k_eval_match, dim3(B), dim3(WG), 0, (hipStream_t)stream, score, cls, reinterpret_cast<const float4*>(box),
+                       keep, A, gt_cls, gt_box, gt_off, thr, max_dets, n_det, det_score, det_cls,
+                       reinterpret_cast<float4*>(det_box), det_flags);
+    return ssd_launch_status();
+}
+
+int ssd_eval_ap(const uint16_t* flags_sorted, const int32_t* seg_off, const int32_t* n_gt, int C, const double* recall_points,
+                double* ap, void* stream) {
+    if (C <= 0 || !flags_sorted || !seg_off || !n_gt || !recall_points || !ap) return SSD_ERR_VALUE;
+    RecallPoints pts;
+    for (int k = 0; k < NP; ++k) pts.v[k] = recall_points[k];
+    hipLaunchKernelGGL(k_eval_ap, dim3(C), dim3(AWG), 0, (hipStream_t)stream, flags_sorted, seg_off, n_gt, pts, ap);
+    return ssd_launch_status();
+}
+
+}  // extern "C"

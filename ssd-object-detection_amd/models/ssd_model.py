@@ -29,10 +29,16 @@ logger = logging.getLogger(__name__)
 _RESTORED = object()                            # _slot_owner marker: Adam moments were loaded from a checkpoint
 
 
+class _RawList(list):
+    """The first samples of a reader-contract split (data_loaders RawSplit), still marked for device preprocessing."""
+    raw = True
+
+
 class SSDObjectDetectionModel:
     class TrainConfig:
         def __init__(self, epoch, batch_size, optimizer, warmup=True, warmup_optimizer=None, warmup_step=1000,
-                     visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0, augment=None):
+                     visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0, augment=None,
+                     val=None):
             if warmup_optimizer is None:
                 warmup_optimizer = _opt.Adam(_opt.PolynomialDecay(1e-6, 1000, 0.001))
             self.epoch = epoch
@@ -46,6 +52,11 @@ class SSDObjectDetectionModel:
             self.split_batch_size = split_batch_size
             self.start_epoch = start_epoch                 # > 0: resumed run (no warm-up, epochs start_epoch..epoch-1)
             self.augment = augment                         # ops.AugmentSpec: SSD data augmentation on the device; None = off
+            # validation during the run (None = off): dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
+            # max_dets=100, num_data=0, precision="bf16"); missing keys take these defaults.  After every `every`-th epoch
+            # the validation split (its first num_data samples if > 0) is evaluated with metric="device"
+            self.val = None if val is None else dict(dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
+                                                          max_dets=100, num_data=0, precision="bf16"), **val)
 
     class Config:
         def __init__(self, classes, log_dir):
@@ -361,7 +372,8 @@ class SSDObjectDetectionModel:
 
     # ------------------------------------------------------------------ trainer shell
     def _train(self, data_loader, cfg):
-        train_set, _val_set = data_loader.get_dataset()
+        train_set, val_set = data_loader.get_dataset()     # (the reference drops the validation split, :291)
+        self._val_set = val_set if getattr(cfg, "val", None) else None
         set_names, set_colors = data_loader.get_names_and_colors()
         batches = self.get_train_set(train_set, batch_size=cfg.batch_size, augment=getattr(cfg, "augment", None))
         self._assert_replicas_identical()
@@ -428,9 +440,30 @@ class SSDObjectDetectionModel:
                                               set_colors, step, cfg)
                 self._log(step, info, cfg, "train")
             self._scalars.flush()                      # one device->host read per epoch (or per full ring)
+            val = getattr(cfg, "val", None)
+            if val and (epoch + 1) % val["every"] == 0:
+                self._validate(val, cfg.optimizer.iterations)
             self.save(os.path.join(self.cfg.log_dir, "model_weight", "model_weight_epoch_%d.pt" % epoch),
                       extra=dict(epoch=epoch + 1, iterations=cfg.optimizer.iterations,
                                  warmup_iterations=cfg.warmup_optimizer.iterations if cfg.warmup_optimizer else 0))
+
+    def _validate(self, val, step):
+        """Validation inside a run: the kept validation split through evaluate(metric="device") on the step's stream, then
+        val/mAP, val/AP50, val/AP75 in scalars.jsonl at the optimizer's step count, behind the epoch's train lines.  Data
+        parallel: the replicas are identical, so every rank evaluates the whole split (no collective inside the pass) and
+        rank 0 writes."""
+        samples = self._val_set
+        if val["num_data"] > 0:
+            import itertools
+            raw = bool(getattr(samples, "raw", False))
+            samples = list(itertools.islice(iter(samples), val["num_data"]))
+            if raw:
+                samples = _RawList(samples)
+        r = self.evaluate(samples, batch_size=val["batch_size"], score_thresh=val["score_thresh"], iou_thresh=val["iou_thresh"],
+                          max_dets=val["max_dets"], precision=val["precision"], metric="device")
+        self._scalars.write_values("val", step, {k: r[k] for k in ("mAP", "AP50", "AP75")})
+        logger.info("validation at step %d: mAP %.4f AP50 %.4f AP75 %.4f", step, r["mAP"], r["AP50"], r["AP75"])
+        return r
 
     def _log(self, step, info, cfg, stage):
         """Reference :281-285 writes five scalars per step, each a host read; here a step enqueues one 32-byte device
@@ -454,36 +487,121 @@ class SSDObjectDetectionModel:
         Scoring/decoding as the reference's visualize(); `keep` adds per-class NMS (no reference counterpart).
         precision="mxfp8": the network forward runs most of its trunk on block-scaled fp8 operands (SSDEngine.forward; no
         reference counterpart); "bf16" (default) as in training.  Any other value raises ValueError."""
-        x = ops.image_prep(image.contiguous(), normalize=False)
+        return self._detect_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh, max_cand,
+                                     precision)
+
+    def _detect_prepared(self, x, score_thresh, iou_thresh, max_cand=400, precision="bf16"):
+        """detect() from the prepared network input bf16 [B,S,S,8]."""
         loc, conf = self._engine.forward(x, precision)
         score, cls, box, cand = ops.score_decode(conf, loc, self._pset, score_thresh, float(self.cfg.input_shape[0]))
         keep = ops.nms(score, cls, box, cand, iou_thresh, max_cand)
         return score, cls, box, keep
 
-    def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False,
-                 precision="bf16"):
-        """Evaluation pass (SURVEY.md 8f, N2; the reference fetches its val split at models/ssd_model.py:291 and drops it):
-        samples = iterable of (image f32 [S,S,3] in [0,1], cls [n], box [n,4] relative cx,cy,w,h) as the loaders yield
-        them.  Network forward, scoring/decoding and per-class NMS run on the device; the kept detections go to
-        utils.metrics.coco_map on the host.  Returns its dict (mAP = AP@[.5:.95], AP50, AP75, per_class); with
-        return_detections also the per-image (score, cls, box_px) arrays that were scored.  precision: detect()'s ("bf16" or
-        "mxfp8")."""
-        from ..utils.metrics import coco_map
+    def _to_device(self, array):
+        """Host array -> device through pinned memory, stream-ordered: no host synchronisation."""
+        t = torch.from_numpy(np.ascontiguousarray(array))
+        if t.numel() == 0:
+            return torch.empty(t.shape, dtype=t.dtype, device=self.device)
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+    def _eval_batch_raw(self, buf):
+        """Reader-contract samples (decoded uint8 images of any size, COCO top-left pixel boxes: RawSplit) -> the prepared
+        network input and the relative centre-form boxes, by the device preprocessing of make_batch_raw (no augmentation).
+        Returns (x bf16 [B,S,S,8], box f32 [total,4] device, counts)."""
+        imgs = [np.ascontiguousarray(b[0], np.uint8) for b in buf]
+        hw = np.array([im.shape[:2] for im in imgs], np.int32)
+        sizes = [int(im.size) for im in imgs]
+        off = np.zeros(len(sizes), np.int64)
+        off[1:] = np.cumsum(sizes[:-1])
+        hw_d = self._to_device(hw)
+        x = ops.image_resize_prep(self._to_device(np.concatenate([im.reshape(-1) for im in imgs])), self._to_device(off), hw_d,
+                                  int(self.cfg.input_shape[0]), True)
+        counts = [int(np.shape(b[2])[0]) for b in buf]
+        gt_off = np.zeros(len(buf) + 1, np.int32)
+        gt_off[1:] = np.cumsum(counts)
+        box = np.concatenate([np.asarray(b[2], np.float32).reshape(-1, 4) for b in buf], 0)
+        box_d = self._to_device(box)
+        if box.shape[0]:
+            box_d = ops.box_prep(box_d, self._to_device(gt_off), hw_d)
+        return x, box_d, counts
+
+    def evaluate_into(self, acc, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, precision="bf16"):
+        """The batch loop of evaluate(metric="device"): every batch of `samples` through the network, scoring/decoding, NMS
+        and acc.add (utils.device_map.DeviceMapAccumulator) on the current stream.  Host arrays reach the device through
+        pinned memory; nothing in the loop reads the device or waits for it."""
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         size = float(self.cfg.input_shape[0])
+        raw = bool(getattr(samples, "raw", False))
+        buf = []
+
+        def flush():
+            if not buf:
+                return
+            gt_off = np.zeros(len(buf) + 1, np.int32)
+            gt_off[1:] = np.cumsum([int(np.shape(b[1])[0]) for b in buf])
+            gt_cls = np.concatenate([np.asarray(b[1]).reshape(-1) for b in buf]).astype(np.int32)
+            if raw:
+                x, box_d, _ = self._eval_batch_raw(buf)
+            else:
+                img = self._to_device(np.stack([np.asarray(b[0], np.float32) for b in buf], 0))
+                x = ops.image_prep(((img - 0.5) * 2).contiguous(), normalize=False)
+                box_d = self._to_device(np.concatenate([np.asarray(b[2], np.float32).reshape(-1, 4) for b in buf], 0))
+            score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
+            acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off))
+            buf.clear()
+
+        for sample in samples:
+            buf.append(sample)
+            if len(buf) == batch_size:
+                flush()
+        flush()
+
+    def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False,
+                 precision="bf16", metric="host"):
+        """Evaluation pass (SURVEY.md 8f, N2; the reference fetches its val split at models/ssd_model.py:291 and drops it):
+        samples = iterable of (image f32 [S,S,3] in [0,1], cls [n], box [n,4] relative cx,cy,w,h) as the loaders yield
+        them, or a split of reader-contract samples (getattr(samples, "raw"): decoded uint8 images of any size, COCO top-left
+        pixel boxes -- data_loaders RawSplit), which go through the device preprocessing of make_batch_raw.  Network forward,
+        scoring/decoding and per-class NMS run on the device.
+        metric="host": the kept detections go to utils.metrics.coco_map on the host.
+        metric="device": top-max_dets selection, matching and AP run on the device as well (utils.device_map); no dense map
+        is copied to the host and nothing synchronises before the result is read.  max_dets <= ops.eval_max_dets().
+        Ground-truth boxes are float64(float32 relative box) * input size in both modes.
+        Returns coco_map's dict (mAP = AP@[.5:.95], AP50, AP75, per_class); with return_detections also the per-image
+        (score, cls, box_px) arrays: all kept detections with "host", the top-max_dets that were scored with "device".
+        precision: detect()'s ("bf16" or "mxfp8")."""
+        from ..utils.metrics import coco_map
+        if precision not in ("bf16", "mxfp8"):
+            raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
+        if metric == "device":
+            from ..utils.device_map import DeviceMapAccumulator
+            acc = DeviceMapAccumulator(self.cfg.classes - 1, max_dets, self.device)
+            self.evaluate_into(acc, samples, batch_size, score_thresh, iou_thresh, precision)
+            result = acc.result()
+            return (result, acc.detections()) if return_detections else result
+        if metric != "host":
+            raise ValueError("metric must be 'host' or 'device', not %r" % (metric,))
+        size = float(self.cfg.input_shape[0])
+        raw = bool(getattr(samples, "raw", False))
         dets, gts, buf = [], [], []
 
         def flush():
             if not buf:
                 return
-            img = torch.from_numpy(np.stack([b[0] for b in buf], 0)).to(self.device)
-            score, cls, box, keep = self.detect((img - 0.5) * 2, score_thresh, iou_thresh, precision=precision)
+            if raw:
+                x, box_d, counts = self._eval_batch_raw(buf)
+                score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
+                gboxes = np.split(box_d.cpu().numpy(), np.cumsum(counts)[:-1])
+            else:
+                img = torch.from_numpy(np.stack([b[0] for b in buf], 0)).to(self.device)
+                score, cls, box, keep = self.detect((img - 0.5) * 2, score_thresh, iou_thresh, precision=precision)
+                gboxes = [b[2] for b in buf]
             score, cls, box, keep = score.cpu().numpy(), cls.cpu().numpy(), box.cpu().numpy(), keep.cpu().numpy().astype(bool)
-            for i, (_, gcls, gbox) in enumerate(buf):
+            for i, (_, gcls, _) in enumerate(buf):
                 k = keep[i]
                 dets.append((score[i][k], cls[i][k], box[i][k]))
-                gts.append((np.asarray(gcls), np.asarray(gbox, np.float64) * size))     # pixels, like the decoded boxes
+                gts.append((np.asarray(gcls), np.asarray(gboxes[i], np.float64) * size))     # pixels, like the decoded boxes
             buf.clear()
 
         for sample in samples:

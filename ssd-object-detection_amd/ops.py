@@ -354,6 +354,54 @@ def nms(score, cls, box, cand, iou_thresh=0.45, max_cand=400, want_count=False):
     return (keep, count) if want_count else keep
 
 
+def eval_max_dets():
+    return int(_lib.lib().ssd_eval_max_dets())
+
+
+_EVAL_THRESHOLDS = np.linspace(0.5, 0.95, 10)          # utils.metrics.IOU_THRESHOLDS / RECALL_POINTS: passed in, not recomputed
+_EVAL_RECALL_POINTS = np.linspace(0.0, 1.0, 101)
+
+
+def eval_match(score, cls, box, keep, gt_cls, gt_box, gt_off, max_dets=100):
+    """ssd_eval_match: top-max_dets kept detections per image + greedy COCO matching at the ten thresholds, behind
+    score_decode + nms.  gt_cls i32 [total], gt_box f64 [total,4] pixels, gt_off i32 [B+1].  Returns (n_det i32 [B],
+    det_score f32 [B,max_dets], det_cls i32 [B,max_dets], det_box f32 [B,max_dets,4], det_flags int16 [B,max_dets] holding the
+    uint16 flag words: bit t = true positive at threshold t)."""
+    L = _lib.lib()
+    B, A = score.shape
+    _dev(score, torch.float32); _dev(cls, torch.int32); _dev(box, torch.float32); _dev(keep, torch.uint8)
+    _dev(gt_cls, torch.int32); _dev(gt_box, torch.float64); _dev(gt_off, torch.int32)
+    assert gt_off.numel() == B + 1 and gt_box.shape[0] == gt_cls.shape[0]
+    max_dets = int(max_dets)
+    dev = score.device
+    md = max(max_dets, 1)
+    n_det = torch.empty((B,), dtype=torch.int32, device=dev)
+    det_score = torch.empty((B, md), dtype=torch.float32, device=dev)
+    det_cls = torch.empty((B, md), dtype=torch.int32, device=dev)
+    det_box = torch.empty((B, md, 4), dtype=torch.float32, device=dev)
+    det_flags = torch.empty((B, md), dtype=torch.int16, device=dev)
+    thr = _EVAL_THRESHOLDS.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    _lib.check(L.ssd_eval_match(_ptr(score), _ptr(cls), _ptr(box), _ptr(keep), B, A, _ptr(gt_cls), _ptr(gt_box), _ptr(gt_off),
+                                thr, max_dets, _ptr(n_det), _ptr(det_score), _ptr(det_cls), _ptr(det_box), _ptr(det_flags),
+                                _stream()))
+    return n_det, det_score, det_cls, det_box, det_flags
+
+
+def eval_ap(flags_sorted, seg_off, n_gt):
+    """ssd_eval_ap: flags int16 [N] (uint16 words) sorted by (class, score desc, image, rank), seg_off i32 [C+1], n_gt i32 [C]
+    -> AP f64 [C,10] (101-point, per class and threshold; 0 for classes without ground truth)."""
+    L = _lib.lib()
+    _dev(flags_sorted, torch.int16); _dev(seg_off, torch.int32); _dev(n_gt, torch.int32)
+    C = n_gt.numel()
+    assert seg_off.numel() == C + 1
+    if flags_sorted.numel() == 0:                      # the entry point wants a pointer even when there is nothing to read
+        flags_sorted = torch.zeros((1,), dtype=torch.int16, device=n_gt.device)
+    ap = torch.empty((C, 10), dtype=torch.float64, device=n_gt.device)
+    pts = _EVAL_RECALL_POINTS.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    _lib.check(L.ssd_eval_ap(_ptr(flags_sorted), _ptr(seg_off), _ptr(n_gt), C, pts, _ptr(ap), _stream()))
+    return ap
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution stack (NHWC bf16)
 # ------------------------------------------------------------------------------------------------

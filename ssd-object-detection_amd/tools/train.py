@@ -51,6 +51,27 @@ def augment_from_config(config):
     return AugmentSpec(seed=int(section.get("seed", 0) or 0))
 
 
+VAL_DEFAULTS = dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, num_data=0, precision="bf16")
+
+
+def val_from_config(config):
+    """`model: eval: {enable, every, batch_size, score_thresh, iou_thresh, max_dets, num_data, precision}` (no reference
+    counterpart: the reference drops its validation split) -> the `val` dict of TrainConfig, or None when the key is absent or
+    enable is false: the default run does not validate, as the reference does not."""
+    section = (config.get("model") or {}).get("eval")
+    if not section or not section.get("enable", False):
+        return None
+    unknown = set(section) - set(VAL_DEFAULTS) - {"enable"}
+    if unknown:
+        raise ValueError("unknown model.eval keys: %s" % sorted(unknown))
+    val = {k: type(d)(section.get(k, d)) for k, d in VAL_DEFAULTS.items()}
+    if val["precision"] not in ("bf16", "mxfp8"):
+        raise ValueError("model.eval.precision must be 'bf16' or 'mxfp8', not %r" % (val["precision"],))
+    if val["every"] < 1:
+        raise ValueError("model.eval.every must be >= 1")
+    return val
+
+
 def _make_optimizer(section, schedule):
     from .. import optimizers
     kinds = {"adam": optimizers.Adam, "sgd": optimizers.SGD}
@@ -119,7 +140,7 @@ def train(config):
 
     fields = {name: cfg_get(config, path) for name, path in TRAIN_CONFIG_KEYS.items()}
     fields.update(optimizer=optimizer, warmup_optimizer=warmup_optimizer, start_epoch=start_epoch,
-                  augment=augment_from_config(config))
+                  augment=augment_from_config(config), val=val_from_config(config))
     model.train(data_loader=data, cfg=SSDObjectDetectionModel.TrainConfig(**fields))
     model.save(os.path.join(model.get_log_dir(), model_cfg["save"]))      # rank 0 writes; the others wait
     return model

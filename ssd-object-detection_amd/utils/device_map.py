@@ -1,0 +1,62 @@
+"""COCO-style mAP accumulated on the device: utils.metrics.coco_map without the dense maps on
+the host and without its Python loops.
+
+Per evaluated batch `add` enqueues one ssd_eval_match launch (top-max_dets detections per image + greedy matching at the ten
+IoU thresholds) behind ssd_score_decode + ssd_nms and keeps its small record tensors; nothing synchronises.  `result` sorts
+all rows by (class, score desc, image, rank) -- a stable device sort of a 64-bit key over rows that are already in (image,
+rank) order --, runs ssd_eval_ap and reads one [C, 11] table back.  The definition, and the oracle of both kernels, is
+utils.metrics.coco_map."""
+import numpy as np
+import torch
+
+from .. import ops
+from .metrics import map_from_ap_table
+
+
+class DeviceMapAccumulator:
+    def __init__(self, classes, max_dets=100, device="cuda"):
+        """classes: number of object classes (ids 0 .. classes-1); max_dets: detections scored per image."""
+        if not 1 <= int(max_dets) <= ops.eval_max_dets():
+            raise ValueError("max_dets must be in 1 .. %d, not %r" % (ops.eval_max_dets(), max_dets))
+        self.classes, self.max_dets, self.device = int(classes), int(max_dets), torch.device(device)
+        self._records, self._gt_cls = [], []
+
+    def add(self, score, cls, box, keep, gt_cls, gt_box, gt_off):
+        """One batch: score f32 [B,A], cls i32 [B,A], box f32 [B,A,4] pixels, keep u8 [B,A] (ops.score_decode + ops.nms);
+        ground truth as CSR: gt_cls i32 [total], gt_box f64 [total,4] (cx,cy,w,h pixels), gt_off i32 [B+1].  Enqueue only."""
+        self._records.append(ops.eval_match(score, cls, box, keep, gt_cls, gt_box, gt_off, self.max_dets))
+        self._gt_cls.append(gt_cls)
+
+    def _cat(self, i):
+        return torch.cat([r[i] for r in self._records], 0)
+
+    def detections(self):
+        """Per image (score [k], cls [k], box [k,4]) numpy arrays: the top-max_dets kept detections that were scored."""
+        if not self._records:
+            return []
+        n = self._cat(0).cpu().numpy()
+        score, cls, box = self._cat(1).cpu().numpy(), self._cat(2).cpu().numpy(), self._cat(3).cpu().numpy()
+        return [(score[i, :k].copy(), cls[i, :k].copy(), box[i, :k].copy()) for i, k in enumerate(n)]
+
+    def result(self):
+        """The dict utils.metrics.coco_map returns for the same detections and ground truths."""
+        C, dev = self.classes, self.device
+        if not self._records:
+            return map_from_ap_table({})
+        score, cls, flags = self._cat(1).reshape(-1), self._cat(2).reshape(-1), self._cat(4).reshape(-1)
+        # empty slots (class -1) sort behind every class; (score + 0.0) orders -0 as +0, as the comparison of floats does
+        bits = (score + 0.0).view(torch.int32).to(torch.int64)
+        ordered = torch.where(bits < 0, bits ^ 0x7fffffff, bits)               # signed order of the int32 = order of the floats
+        cls_key = torch.where(cls < 0, torch.full_like(cls, C), cls).to(torch.int64)
+        key = (cls_key << 32) | (0x7fffffff - ordered)                         # descending score inside a class
+        order = torch.sort(key, stable=True).indices                           # rows are in (image, rank) order already
+        flags_sorted = flags[order].contiguous()
+        per_class = torch.bincount(cls_key, minlength=C + 1)[:C + 1]
+        seg_off = torch.zeros((C + 1,), dtype=torch.int32, device=dev)
+        seg_off[1:] = torch.cumsum(per_class[:C], 0).to(torch.int32)
+        gt = torch.cat(self._gt_cls, 0).to(torch.int64)
+        gt = gt[(gt >= 0) & (gt < C)]
+        n_gt = torch.bincount(gt, minlength=C)[:C].to(torch.int32)
+        ap = ops.eval_ap(flags_sorted, seg_off, n_gt)
+        host = torch.cat([ap, n_gt.to(torch.float64).reshape(C, 1)], 1).cpu().numpy()      # the one device-to-host read
+        return map_from_ap_table({c: host[c, :10].tolist() for c in np.nonzero(host[:, 10] > 0)[0].tolist()})

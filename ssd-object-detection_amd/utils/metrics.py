@@ -47,6 +47,40 @@ def average_precision(scores, matched, n_gt):
     return float(sampled.mean())
 
 
+def ap_table_from_flags(rows, n_gt):
+    """AP per (class, threshold) from matched rows -- the second stage of the device metric (ssd_eval_ap) on the host.
+    rows = (cls [N], score [N], flags [N]): every detection that was scored, in (image, rank within image) order -- the
+    order coco_map appends in -- with bit t of flags = true positive at IOU_THRESHOLDS[t] (ssd_eval_match's det_flags).
+    n_gt: ground truths per class, a {class: count} mapping or a 1-D array indexed by class.
+    Returns {class: [AP at each threshold]} for the classes with ground truth."""
+    cls = np.asarray(rows[0]).astype(int).reshape(-1)
+    score = np.asarray(rows[1], np.float64).reshape(-1)
+    flags = np.asarray(rows[2]).astype(np.int64).reshape(-1) & 0xffff
+    counts = dict(n_gt) if hasattr(n_gt, "items") else {c: int(n) for c, n in enumerate(np.asarray(n_gt).reshape(-1))}
+    table = {}
+    for c in sorted(int(c) for c, n in counts.items() if n > 0):
+        sel = cls == c
+        sc, fl = score[sel], flags[sel]                       # average_precision's stable sort keeps (image, rank) order
+        table[c] = [average_precision(sc, (fl >> ti) & 1, counts[c]) for ti in range(len(IOU_THRESHOLDS))]
+    return table
+
+
+def map_from_ap_table(table):
+    """coco_map's result dict from {class: [AP per threshold]} (classes with ground truth only)."""
+    if not table:
+        return dict(mAP=0.0, AP50=0.0, AP75=0.0, per_class={})
+    classes = sorted(table)
+    per_class = {c: float(np.mean(table[c])) for c in classes}
+    return dict(mAP=float(np.mean(list(per_class.values()))), AP50=float(np.mean([table[c][0] for c in classes])),
+                AP75=float(np.mean([table[c][5] for c in classes])), per_class=per_class)
+
+
+def map_from_flags(rows, n_gt):
+    """coco_map's result from rows that are already matched (see ap_table_from_flags): equal to coco_map on the same
+    detections when the flags are its greedy matches."""
+    return map_from_ap_table(ap_table_from_flags(rows, n_gt))
+
+
 def coco_map(detections, ground_truths, max_dets=100):
     """detections: per image (score [k], cls [k], box [k,4]); ground_truths: per image (cls [n], box [n,4]).
     Returns dict(mAP=..., AP50=..., AP75=..., per_class={cls: AP@[.5:.95]})."""

@@ -100,6 +100,19 @@ class ScalarLog:
                                    "raises there (models/ssd_model.py:359,368)" % (stage, step))
         return rows
 
+    def write_values(self, stage, step, values):
+        """Host-side scalars (validation metrics: `val/mAP` ...) appended as `<stage>/<tag>` lines at `step`, behind everything
+        flushed so far.  Data parallel: rank 0 writes.  Flush first: rows still in the ring would land behind these lines."""
+        write = (not self.distributed) or (not torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
+        if not write:
+            return
+        if self._file is None:
+            os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
+            self._file = open(self.path, "a")
+        for tag, v in values.items():
+            self._file.write(json.dumps({"tag": stage + "/" + tag, "step": int(step), "value": float(v)}) + "\n")
+        self._file.flush()
+
     def close(self, collective=True):
         """collective=False while unwinding from an exception: a rank that failed alone must not enter an all-reduce the
         others never reach (its rows are written from local values)."""
