@@ -667,6 +667,16 @@ int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksi
 int ssd_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int ldy, int ksize, int stride, int pad_t, int pad_l,
                                int Ho, int Wo);
 const char* ssd_conv_plan_name(int plan);
+/* Launch size (the same dispatch code, launching switched off): the number of ACTIVE workgroups of the launch the call
+ * resolves to -- the grid minus the workgroups that return at once (grids are rounded up to whole groups of 8, one per
+ * XCD); for a split-K call the GEMM launch, not the finalize.  Set against the CU count (x workgroups per CU of the
+ * kernel) it tells how full the launch's last round is.  Arguments as ssd_conv2d_fwd_plan / ssd_conv2d_bwd_data_plan.
+ * Return: a count > 0, a negative ssd_status for a shape the call would reject, SSD_ERR_UNSUPPORTED where the launch site
+ * reports none (the persistent pointwise GEMM). */
+int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
+                              int Wo, int pool, size_t ws_bytes);
+int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
+                                   int Ho, int Wo, int accumulate, size_t ws_bytes);
 
 /* Development only (no reference counterpart): override one of the library's kernel-selection defaults (names in DESIGN.md
  * section 4, e.g. "SSD_CONV_TILE") for A/B timing of kernel variants or to force a dispatch path in a test, inside one

@@ -149,6 +149,8 @@ _SIGNATURES = {
     "ssd_conv2d_fwd_plan": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
     "ssd_conv2d_head_fwd_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_size_t]),
     "ssd_conv2d_bwd_data_plan": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
+    "ssd_conv2d_fwd_workgroups": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
+    "ssd_conv2d_bwd_data_workgroups": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
     "ssd_conv2d_bwd_weight_plan": (ctypes.c_int, [ctypes.c_int] * 12),
     "ssd_conv_plan_name": (ctypes.c_char_p, [ctypes.c_int]),
     "ssd_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -572,10 +572,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave & 3, wave_n = wave >> 2;
     // two block shapes.  flat == 0: a 16x16 block of one image, halo patch 18x18 (tap pitch Q = 18).
-    // flat != 0 (narrow maps): the batch is one long strip of positions, image rows padded to Q = W + 2 (a zero column
-    // on either side) and images separated by ONE zero row; a block is 256 consecutive positions, its patch those plus
-    // Q + 1 on either side, tap (kh,kw) is position + kh*Q + kw.  Pad positions are computed and dropped: 7 % of the
-    // work at 38x38 and 14 % at 19x19, where 16x16 blocks would waste 37 % and 65 %.
+    // flat != 0 (narrow maps): the batch is one long strip of positions, image rows at pitch Q = W + 1 (ONE zero column
+    // in front of every row: it is the right padding of the row before it as well, the way the ONE zero row between
+    // images is the bottom padding of one and the top padding of the next); a block is 256 consecutive positions, its
+    // patch those plus Q + 1 on either side, tap (kh,kw) is position + kh*Q + kw.  Pad positions are computed and
+    // dropped: 5 % of the work at 38x38 and 10 % at 19x19, where 16x16 blocks would waste 37 % and 65 %.
     // XCD-aware order (workgroup L runs on XCD L % 8): the channel tiles of one pixel block are consecutive on ONE
     // XCD, so the block's patch is fetched into that L2 once
     const int ntn = (g.N + BN - 1) / BN;
@@ -584,7 +585,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if (pblock >= nblocks) return;
     const int n0 = (kx % ntn) * BN;
     constexpr bool flat = FLAT;
-    const int Q = FLAT ? g.W + 2 : PATCH_W;
+    const int Q = FLAT ? g.W + 1 : PATCH_W;
     const int img = (g.H + 1) * Q;                          // flat positions per image
     int b = 0, y0 = 0, x0 = 0, f0 = 0;
     if constexpr (FLAT) {
@@ -599,12 +600,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // rowflat (wide maps whose height is not a multiple of 16): the rows of all images form one strip, images separated
     // by ONE zero row, and a block is 16 consecutive strip rows x 16 columns -- it may straddle two images, the shared
     // zero row is the bottom padding of one and the top padding of the other.  75 rows per image cost 76 instead of 80.
+    // The image pitch in strip rows is g.d_h1.d: H + 1, or the next EVEN number when the epilogue pools (H + 2 for an
+    // even H, two zero rows), so that no 2x2 window straddles two images or two blocks (blocks start at even strip rows).
     // block row r (-1 .. 16 for the halo) -> row index into [B * H], -1 = padding / outside
     auto image_row = [&](int r) {
         if (!rowflat) { const int y = y0 + r; return (unsigned)y < (unsigned)g.H ? b * g.H + y : -1; }
         const int R = y0 + r;
         if (R < 0) return -1;
-        const int bb = fdiv(R, g.d_h1), yy = R - bb * (g.H + 1);
+        const int bb = fdiv(R, g.d_h1), yy = R - bb * g.d_h1.d;
         return (bb < g.B && yy < g.H) ? bb * g.H + yy : -1;
     };
     // flat position -> source pixel (element offset / C) or -1
@@ -786,9 +789,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             return (ir >= 0 && xx < g.Wo) ? ir * g.Wo + xx : -1;
         };
         auto pool_index = [&](int py, int px) -> long long {
-            if (flat || rowflat) return -1;
-            const int gy = (y0 >> 1) + py, gx = (x0 >> 1) + px;
-            return (gy < ep.pool_h && gx < ep.pool_w) ? ((long long)b * ep.pool_h + gy) * ep.pool_w + gx : -1;
+            if (flat) return -1;
+            int bb = b, gy = (y0 >> 1) + py;
+            const int gx = (x0 >> 1) + px;
+            if (rowflat) {                                  // even image pitch: the window's two rows lie in ONE image's span
+                const int R = y0 + 2 * py;
+                bb = fdiv(R, g.d_h1);
+                gy = (R - bb * g.d_h1.d) >> 1;
+                if (bb >= g.B) return -1;
+            }
+            return (gy < ep.pool_h && gx < ep.pool_w) ? ((long long)bb * ep.pool_h + gy) * ep.pool_w + gx : -1;
         };
         staged_epilogue<EPI, 256, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 64, wave_n * (16 * CT), tid, row_to_m, pool_index);
         return;
@@ -844,7 +854,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict
     const int pblock = (kx / ntn) * 8 + (blockIdx.x & 7);   // channel tiles of one pixel block consecutive on ONE XCD
     if (pblock >= nblocks) return;
     const int n0 = (kx % ntn) * BN;
-    const int Q = FLAT ? g.W + 2 : PATCH_W;
+    const int Q = FLAT ? g.W + 1 : PATCH_W;
     const int img = (g.H + 1) * Q;
     int b = 0, y0 = 0, x0 = 0, f0 = 0;
     if constexpr (FLAT) {
@@ -860,7 +870,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict
         if (!rowflat) { const int y = y0 + r; return (unsigned)y < (unsigned)g.H ? b * g.H + y : -1; }
         const int R = y0 + r;
         if (R < 0) return -1;
-        const int bb = fdiv(R, g.d_h1), yy = R - bb * (g.H + 1);
+        const int bb = fdiv(R, g.d_h1), yy = R - bb * g.d_h1.d;
         return (bb < g.B && yy < g.H) ? bb * g.H + yy : -1;
     };
     auto flat_pixel = [&](int f) {
@@ -1006,10 +1016,17 @@ __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict
             const int ir = image_row(row >> 4), xx = x0 + (row & 15);
             return (ir >= 0 && xx < g.Wo) ? ir * g.Wo + xx : -1;
         };
-        auto pool_index = [&](int py, int px) -> long long {
-            if (FLAT || rowflat) return -1;
-            const int gy = (y0 >> 1) + py, gx = (x0 >> 1) + px;
-            return (gy < ep.pool_h && gx < ep.pool_w) ? ((long long)b * ep.pool_h + gy) * ep.pool_w + gx : -1;
+        auto pool_index = [&](int py, int px) -> long long {    // as in k_conv3x3_patch32
+            if (FLAT) return -1;
+            int bb = b, gy = (y0 >> 1) + py;
+            const int gx = (x0 >> 1) + px;
+            if (rowflat) {
+                const int R = y0 + 2 * py;
+                bb = fdiv(R, g.d_h1);
+                gy = (R - bb * g.d_h1.d) >> 1;
+                if (bb >= g.B) return -1;
+            }
+            return (gy < ep.pool_h && gx < ep.pool_w) ? ((long long)bb * ep.pool_h + gy) * ep.pool_w + gx : -1;
         };
         staged_epilogue<EPI, 512, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 128, wave_n * 64, tid, row_to_m, pool_index);
         return;
@@ -2787,7 +2804,11 @@ int knob(const char* name, int dflt) {
 
 // Which kernel a call resolves to (ssd_conv2d_*_plan): the dispatch code below runs as usual and, with `plan` set, records
 // the id at the launch site and returns instead of launching -- the query cannot drift from the dispatch.
-#define SSD_PLAN(ID_) do { if (plan) { *plan = (ID_); return SSD_OK; } } while (0)
+// ssd_conv2d_*_workgroups: the caller presets *plan to PLAN_WANT_WGS and the launch sites that know their count record
+// the number of ACTIVE workgroups (the grid minus the workgroups that return at once) instead of the id.
+constexpr int PLAN_WANT_WGS = -1;
+#define SSD_PLAN(ID_) do { if (plan) { if (*plan == PLAN_WANT_WGS) return SSD_ERR_UNSUPPORTED; *plan = (ID_); return SSD_OK; } } while (0)
+#define SSD_PLAN_WGS(ID_, WGS_) do { if (plan) { *plan = *plan == PLAN_WANT_WGS ? (int)(WGS_) : (ID_); return SSD_OK; } } while (0)
 
 template <int EPI>
 bool staged_ok_host(const ConvGeom& g, const Epilogue& ep) {
@@ -2813,9 +2834,9 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
             const int tiles_x = (g.Wo + 15) / 16, tiles_y = (g.Ho + C64B_ROWS - 1) / C64B_ROWS;
             const int nblocks = g.B * tiles_x * tiles_y;
             auto kern = k_conv3x3_c64b<EPI, false>;
-            SSD_PLAN(SSD_PLAN_C64B | ((pooled && ep.pool_out) ? SSD_PLAN_F_POOL_FUSED : 0));
-            static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(C64B_LDS)) != 0) return SSD_ERR_LAUNCH;
             const int maxwg = knob("SSD_C64B_WGS", 512);
+            SSD_PLAN_WGS(SSD_PLAN_C64B | ((pooled && ep.pool_out) ? SSD_PLAN_F_POOL_FUSED : 0), nblocks < maxwg ? nblocks : maxwg);
+            static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(C64B_LDS)) != 0) return SSD_ERR_LAUNCH;
             hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < maxwg ? nblocks : maxwg)), dim3(256), C64B_LDS, s, xp, wp, g, ep, tiles_x, tiles_y, C64W0{});
             if (pooled && ep.pool_out) *pooled = true;
             return ssd_launch_status();
@@ -2825,7 +2846,9 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
     // the 16x16 blocks waste little of the map (75x75 and larger: <= 14 %; 38x38 would waste 37 %)
     const int use_patch = knob("SSD_CONV_PATCH", 256);
     const bool patch_fits = g.N <= 128 || (long long)((g.Wo + 15) / 16) * ((g.Ho + 15) / 16) * 256 * 4 <= (long long)g.Wo * g.Ho * 5;
-    // narrow maps (patch of 256 + 2 (W + 3) positions fits 32 KB): strip blocks, any channel count
+    // narrow maps: strip blocks, any channel count.  The patch of 256 + 2 (W + 2) positions has to fit the 341 pixel rows of
+    // a 32 KB buffer; the bound on W dates from the strip's first form (row pitch W + 2, 256 + 2 (W + 3) positions) and stays:
+    // which layers take the strip form is part of the tested dispatch
     const int flat_knob = knob("SSD_CONV_PATCH_FLAT", 1);
     const bool use_flat = flat_knob && g.W <= 39 && g.W >= 16 && g.H >= 16 && (flat_knob >= 2 || !patch_fits || g.N > use_patch);
     if (g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 && g.pad_l == 1 &&
@@ -2835,22 +2858,25 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
         const unsigned gx = (unsigned)(tiles_x * tiles_y * g.B);
         {
             const bool flat = use_flat;
-            // wide maps: one strip of rows over all images (k_conv3x3_patch32, "rowflat") when that needs fewer blocks and
-            // the epilogue does not pool (2x2 windows would straddle blocks)
-            const unsigned strip_rows = (unsigned)(((long long)g.B * (g.H + 1) + 15) / 16);
-            const int rowflat = (!flat && !ep.pool_out && knob("SSD_CONV_PATCH_ROWFLAT", 1) &&
-                                 strip_rows < (unsigned)(tiles_y * g.B)) ? 1 : 0;
-            const unsigned gxx = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 2) + 255) / 256)
+            ConvGeom gk = g;                                     // what the kernel gets: g with the row strip's image pitch
+            // wide maps: one strip of rows over all images (k_conv3x3_patch32, "rowflat") when that needs fewer blocks.
+            // Image pitch in strip rows: H + 1 (one shared zero row); under fused pooling the next even number, so that a
+            // 2x2 window never straddles two images -- nor two blocks, which start at multiples of 16 / 32 strip rows
+            const int pitch = (EPI == EPI_FWD && ep.pool_out && (g.H & 1) == 0) ? g.H + 2 : g.H + 1;
+            gk.d_h1 = make_fastdiv(pitch);
+            const unsigned strip_rows = (unsigned)(((long long)g.B * pitch + 15) / 16);
+            const int rowflat = (!flat && knob("SSD_CONV_PATCH_ROWFLAT", 1) && strip_rows < (unsigned)(tiles_y * g.B)) ? 1 : 0;
+            const unsigned gxx = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + 255) / 256)
                                       : (rowflat ? strip_rows * (unsigned)tiles_x : gx);
 #define SSD_LAUNCH_P32(BN_, FLAT_)                                                                                  \
             do {                                                                                                    \
                 constexpr int lds_ = 2 * P32_PATCH + 2 * (BN_ == 64 ? 128 : BN_) * 64;   /* BN = 64 stages two taps per step */ \
                 auto kern_ = k_conv3x3_patch32<BN_, EPI, FLAT_>;                                                    \
-                SSD_PLAN((BN_ == 64 ? SSD_PLAN_P32_64 : SSD_PLAN_P32_128) | (FLAT_ ? SSD_PLAN_F_FLAT : 0) |            \
-                         (rowflat ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0));                \
-                static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)(lds_)) != 0) return SSD_ERR_LAUNCH; \
                 const unsigned ntn_ = (unsigned)((g.N + BN_ - 1) / BN_);                                            \
-                hipLaunchKernelGGL(kern_, dim3(8 * ntn_ * ((gxx + 7) / 8)), dim3(512), lds_, s, xp, wp, g, ep, tiles_x, tiles_y, (int)gxx, rowflat); \
+                SSD_PLAN_WGS((BN_ == 64 ? SSD_PLAN_P32_64 : SSD_PLAN_P32_128) | (FLAT_ ? SSD_PLAN_F_FLAT : 0) |        \
+                             (rowflat ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0), gxx * ntn_);  \
+                static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)(lds_)) != 0) return SSD_ERR_LAUNCH; \
+                hipLaunchKernelGGL(kern_, dim3(8 * ntn_ * ((gxx + 7) / 8)), dim3(512), lds_, s, xp, wp, gk, ep, tiles_x, tiles_y, (int)gxx, rowflat); \
             } while (0)
             const bool can_pool = pooled && ep.pool_out && !flat && (g.N & 7) == 0 && (ep.ldo & 7) == 0 && !(g.ablate & 8);
             if (EPI == EPI_FWD && !ep.out && !can_pool) return SSD_ERR_VALUE;
@@ -2866,20 +2892,21 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
             //  loss 130 us later.  With the 78 KB workgroups of the patch kernel the two overlap: -0.07 ms per step.)
             if (p512 && g.C % 64 == 0 && g.N > 64 && (p512 >= 2 || (EPI != EPI_HEAD && g.C >= 256))) {
                 const int ty32 = (g.Ho + 31) / 32;
-                const unsigned strips32 = (unsigned)(((long long)g.B * (g.H + 1) + 31) / 32);
-                const int rf = (!flat && !ep.pool_out && knob("SSD_CONV_PATCH_ROWFLAT", 1) && strips32 < (unsigned)(ty32 * g.B)) ? 1 : 0;
-                const unsigned nb = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 2) + 511) / 512)
+                const unsigned strips32 = (unsigned)(((long long)g.B * pitch + 31) / 32);
+                const int rf = (!flat && knob("SSD_CONV_PATCH_ROWFLAT", 1) && strips32 < (unsigned)(ty32 * g.B)) ? 1 : 0;
+                const unsigned nb = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + 511) / 512)
                                          : (rf ? strips32 * (unsigned)tiles_x : (unsigned)(tiles_x * ty32 * g.B));
                 const unsigned ntn5 = (unsigned)((g.N + 127) / 128);
-                SSD_PLAN(SSD_PLAN_P512 | (flat ? SSD_PLAN_F_FLAT : 0) | (rf ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0));
+                SSD_PLAN_WGS(SSD_PLAN_P512 | (flat ? SSD_PLAN_F_FLAT : 0) | (rf ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0),
+                             nb * ntn5);
                 if (flat) {
                     auto kern5 = k_conv3x3_p512<EPI, true>;
                     static OnceLds set5; if (ensure_lds(set5, reinterpret_cast<const void*>(kern5), P5_LDS) != 0) return SSD_ERR_LAUNCH;
-                    hipLaunchKernelGGL(kern5, dim3(8 * ntn5 * ((nb + 7) / 8)), dim3(512), P5_LDS, s, xp, wp, g, ep, tiles_x, ty32, (int)nb, rf);
+                    hipLaunchKernelGGL(kern5, dim3(8 * ntn5 * ((nb + 7) / 8)), dim3(512), P5_LDS, s, xp, wp, gk, ep, tiles_x, ty32, (int)nb, rf);
                 } else {
                     auto kern5 = k_conv3x3_p512<EPI, false>;
                     static OnceLds set5; if (ensure_lds(set5, reinterpret_cast<const void*>(kern5), P5_LDS) != 0) return SSD_ERR_LAUNCH;
-                    hipLaunchKernelGGL(kern5, dim3(8 * ntn5 * ((nb + 7) / 8)), dim3(512), P5_LDS, s, xp, wp, g, ep, tiles_x, ty32, (int)nb, rf);
+                    hipLaunchKernelGGL(kern5, dim3(8 * ntn5 * ((nb + 7) / 8)), dim3(512), P5_LDS, s, xp, wp, gk, ep, tiles_x, ty32, (int)nb, rf);
                 }
                 if (can_pool) *pooled = true;
                 return ssd_launch_status();
@@ -2941,15 +2968,15 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
             constexpr int NT_ = (BM_ / (16 * PT_)) * (BN_ >= 128 ? BN_ / 64 : 2) * 64;                              \
             const size_t lds_ = 2 * (BM_ + BN_) * 128;                                                             \
             auto kern_ = k_conv_igemm_dma<BM_, BN_, EPI, PT_>;                                                     \
-            SSD_PLAN((BM_ == 256 ? (BN_ == 256 ? SSD_PLAN_DMA_256_256 : (BN_ == 128 ? SSD_PLAN_DMA_256_128 : SSD_PLAN_DMA_256_64)) \
-                                 : (BN_ == 64 ? SSD_PLAN_DMA_128_64 : SSD_PLAN_DMA_128_128)) |                       \
-                     (ksplit > 1 ? SSD_PLAN_F_SPLITK : 0) | (g.s2 ? SSD_PLAN_F_S2 : 0));                              \
-            if (lds_ > 65536) {                                                                                    \
-                static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)((int)lds_)) != 0) return SSD_ERR_LAUNCH; \
-            }                                                                                                      \
             unsigned ntm_ = (unsigned)((g.M + BM_ - 1) / BM_);                                                      \
             const unsigned ntn_ = (unsigned)((g.N + BN_ - 1) / BN_);                                               \
             if (g.s2) { ntm_ = 0; for (int c_ = 0; c_ < 4; ++c_) ntm_ += (unsigned)((g.cls_n[c_] + BM_ - 1) / BM_); } \
+            SSD_PLAN_WGS((BM_ == 256 ? (BN_ == 256 ? SSD_PLAN_DMA_256_256 : (BN_ == 128 ? SSD_PLAN_DMA_256_128 : SSD_PLAN_DMA_256_64)) \
+                                     : (BN_ == 64 ? SSD_PLAN_DMA_128_64 : SSD_PLAN_DMA_128_128)) |                   \
+                         (ksplit > 1 ? SSD_PLAN_F_SPLITK : 0) | (g.s2 ? SSD_PLAN_F_S2 : 0), ntm_ * ntn_ * ksplit);    \
+            if (lds_ > 65536) {                                                                                    \
+                static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)((int)lds_)) != 0) return SSD_ERR_LAUNCH; \
+            }                                                                                                      \
             hipLaunchKernelGGL(kern_, dim3(8 * ntn_ * ((ntm_ + 7) / 8), ksplit), dim3(NT_), lds_, s, xp, wp, g, ep); \
         } while (0)
         if (bm == 256 && bn == 256 && force != 4 && !g.s2 && ksplit == 1 && g.cpt >= 8 &&
@@ -2958,7 +2985,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
 #define SSD_LAUNCH_8PH(ABL_)                                                                                        \
             do {                                                                                                    \
                 auto kern = k_conv_igemm_8ph<EPI, ABL_>;                                                            \
-                SSD_PLAN(SSD_PLAN_8PH);                                                                             \
+                SSD_PLAN_WGS(SSD_PLAN_8PH, ntm * ntn);                                                              \
                 static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(131072)) != 0) return SSD_ERR_LAUNCH; \
                 hipLaunchKernelGGL(kern, dim3(8 * ntn * ((ntm + 7) / 8)), dim3(512), 131072, s, xp, wp, g, ep);      \
             } while (0)
@@ -3055,8 +3082,8 @@ static int conv2d_fwd_impl(const void* x, const void* w, const float* bias, void
     const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, ksize, ksize, stride, 1, pad_t, pad_l);
     if (knob("SSD_CONV_FIRST", 1) && Cin == 8 && Cout == 64 && ksize == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && H == Ho &&
         W == Wo && H >= 16 && W >= 16) {                     // the image layer
-        SSD_PLAN(SSD_PLAN_CONV0_FWD);
         const int tx = (Wo + 15) / 16, ty = (Ho + 15) / 16;
+        SSD_PLAN_WGS(SSD_PLAN_CONV0_FWD, B * tx * ty < 768 ? B * tx * ty : 768);
         hipLaunchKernelGGL(k_conv0_fwd, dim3((unsigned)(B * tx * ty < 768 ? B * tx * ty : 768)), dim3(512), 0, (hipStream_t)stream,
                            static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(w), bias, static_cast<bf16_raw*>(y), g, relu,
                            tx, ty, static_cast<unsigned char*>(relu_bits));
@@ -3540,6 +3567,31 @@ int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int cla
 int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                              int Wo, int accumulate, size_t ws_bytes) {
     int plan = 0;
+    const int rc = conv2d_bwd_data_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l,
+                                        Ho, Wo, accumulate, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
+    return rc != SSD_OK ? rc : plan;
+}
+
+// ---- launch size: ACTIVE workgroups of the (first) launch the call resolves to; SSD_ERR_UNSUPPORTED where the launch site
+// does not report one (the persistent pointwise GEMM) ----
+int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                              int pool, size_t ws_bytes) {
+    int plan = PLAN_WANT_WGS, rc;
+    void* ws = ws_bytes ? PLAN_PTR : nullptr;
+    if (pool) {
+        const int Hp = (Ho + 1) / 2, Wp = (Wo + 1) / 2;
+        rc = conv2d_fwd_pool_impl(PLAN_PTR, PLAN_PTR, nullptr, pool == 2 ? nullptr : PLAN_PTR, PLAN_PTR, PLAN_PTR, B, H, W, Cin, Cout,
+                                  ksize, stride, pad_t, pad_l, Ho, Wo, 1, Hp, Wp, ws, ws_bytes, nullptr, &plan);
+    } else {
+        rc = conv2d_fwd_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 1, ws,
+                             ws_bytes, nullptr, &plan);
+    }
+    return rc != SSD_OK ? rc : plan;
+}
+
+int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
+                                   int Wo, int accumulate, size_t ws_bytes) {
+    int plan = PLAN_WANT_WGS;
     const int rc = conv2d_bwd_data_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l,
                                         Ho, Wo, accumulate, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
     return rc != SSD_OK ? rc : plan;

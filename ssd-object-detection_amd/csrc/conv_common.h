@@ -46,7 +46,8 @@ struct ConvGeom {
     int ldw;                                 // weight row stride (elements) = KH*KW*C
     int cpt;                                 // chunks per tap = C/8
     FastDiv d_hw, d_w;                       // divide by Ho*Wo and by Wo
-    FastDiv d_h1;                            // divide by H + 1 (row strip of k_conv3x3_patch32)
+    FastDiv d_h1;                            // divide by the image pitch of the row strip (k_conv3x3_patch32 / p512): H + 1, or
+                                             // the next even number when the launch pools in its epilogue (set by the dispatch)
     // stride-2 data gradient: destination pixels are enumerated parity class by parity class (py,px), each class
     // padded to whole tiles, so that a tile has ONE parity and the taps that cannot hit it are skipped outright
     int s2;                                  // 1: parity-class enumeration active (div == 2, cpt % 8 == 0)
