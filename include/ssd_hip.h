@@ -336,12 +336,6 @@ typedef struct {
 } ssd_wgrad_item;
 size_t ssd_conv2d_bwd_weight_batched_workspace_bytes(const ssd_wgrad_item* items, int count);
 int ssd_conv2d_bwd_weight_batched(const ssd_wgrad_item* items, int count, void* ws, size_t ws_bytes, void* stream);
-/* The weight-gradient entry points finish with a fixed-order sum of per-split fp32 slabs (a small HBM-bound launch).  With a
- * non-null stream set here (per calling thread; null = off, the default) that launch goes to `stream`, ordered behind the
- * slab kernel by an event: the caller's stream is free for the next layer's kernel while the sum runs.  The caller then owns
- * two obligations: dw / dbias are complete on `stream`, not on the call's own stream; and the workspace of a call must not be
- * reused before that call's sum has run (alternate two workspaces, wait for the sum two calls back). */
-int ssd_set_wgrad_reduce_stream(void* stream);
 /* w bf16 [Cout][k][k][Cin] -> w_t bf16 [Cin][k][k][Cout_pad], spatially flipped (data-gradient operand) */
 int ssd_weight_transpose(const void* w, void* w_t, int Cout, int ksize, int Cin, int Cout_pad, void* stream);
 /* the same for `ntensors` weight tensors in one launch: desc = device array of int64 rows {w, w_t, Cout, ksize, Cin,
@@ -600,10 +594,8 @@ int ssd_heads_bwd_data_sparse(const ssd_head_grads* hg, const ssd_head_layers* h
 /* The same for a subset of the levels (bit l of level_mask): the small maps' gradients head the extras' data-gradient
  * chain, the 38x38 / 19x19 maps' are not read until that chain reaches them, so a caller may issue the two groups on two
  * streams.  Every level keeps its own slice of `ws`: calls with disjoint masks may share one workspace concurrently.
- * prezeroed != 0: the caller has cleared dx of the selected levels (anywhere earlier in the step, off the critical path) and
- * pixels that no gradient row reaches -- ~95 % of a large map, 140 MB of zero stores at batch 64 -- are not written again.
  * SSD_ERR_VALUE for an empty mask. */
-int ssd_heads_bwd_data_sparse_levels(const ssd_head_grads* hg, const ssd_head_layers* hl, int B, unsigned level_mask, int prezeroed,
+int ssd_heads_bwd_data_sparse_levels(const ssd_head_grads* hg, const ssd_head_layers* hl, int B, unsigned level_mask,
                                      void* ws, size_t ws_bytes, void* stream);
 size_t ssd_heads_bwd_weight_sparse_workspace_bytes(int B, const ssd_head_grads* hg, const ssd_head_layers* hl);
 int ssd_heads_bwd_weight_sparse(const ssd_head_grads* hg, const ssd_head_layers* hl, int B, void* ws, size_t ws_bytes,

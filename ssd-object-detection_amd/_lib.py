@@ -108,7 +108,6 @@ _SIGNATURES = {
     "ssd_conv2d_fwd_pool_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 14 + [VP]),
     "ssd_chain_pack_weights": (ctypes.c_int, [ctypes.POINTER(ChainPack), ctypes.c_int, VP]),
     "ssd_chain_prefetch": (ctypes.c_int, [ctypes.POINTER(ChainPack), ctypes.c_int, VP]),
-    "ssd_set_wgrad_reduce_stream": (ctypes.c_int, [VP]),
     "ssd_conv2d_bwd_weight_batched_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(WgradItem), ctypes.c_int]),
     "ssd_conv2d_bwd_weight_batched": (ctypes.c_int, [ctypes.POINTER(WgradItem), ctypes.c_int, VP, ctypes.c_size_t, VP]),
     "ssd_conv_chain": (ctypes.c_int, [VP, ctypes.POINTER(ChainLayer), ctypes.c_int, ctypes.c_int, VP]),
@@ -159,7 +158,7 @@ _SIGNATURES = {
                                               ctypes.c_float, VP, _HG, VP, ctypes.c_size_t, ctypes.c_int, VP]),
     "ssd_heads_bwd_data_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, _HL]),
     "ssd_heads_bwd_data_sparse": (ctypes.c_int, [_HG, _HL, ctypes.c_int, VP, ctypes.c_size_t, VP]),
-    "ssd_heads_bwd_data_sparse_levels": (ctypes.c_int, [_HG, _HL, ctypes.c_int, ctypes.c_uint, ctypes.c_int, VP, ctypes.c_size_t, VP]),
+    "ssd_heads_bwd_data_sparse_levels": (ctypes.c_int, [_HG, _HL, ctypes.c_int, ctypes.c_uint, VP, ctypes.c_size_t, VP]),
     "ssd_heads_bwd_weight_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, _HG, _HL]),
     "ssd_heads_bwd_weight_sparse": (ctypes.c_int, [_HG, _HL, ctypes.c_int, VP, ctypes.c_size_t, VP]),
     "ssd_loss_fwd_bwd": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -5,24 +5,11 @@
 // and weight gradient, and 2x2 max-pooling forward/backward.  TF "SAME" padding is asymmetric for
 // stride 2 (pad_before = pad_total/2, the remainder after) and is passed explicitly as (pad_t, pad_l).
 //
-//   k_conv_igemm   forward AND data-gradient: out[m][n] = sum_k A[m][k] * Wm[n][k].
-//                  A is gathered on the fly from an NHWC tensor: GEMM row m = output pixel (b,oy,ox),
-//                  k = (tap, channel); the source pixel of a tap is (o*mul + k - pad) / div, taken only
-//                  when divisible and in range (zero otherwise).  Forward: mul = stride, div = 1.
-//                  Data gradient: the same kernel run on dY with the spatially flipped, transposed
-//                  weights ([Cin][kh][kw][Cout], made by k_weight_transpose), mul = 1, div = stride,
-//                  pad = k-1-pad: one code path for stride 1 and 2.
-//                  Tile 128 pixels x BN channels x 64 (k); 4 waves (2x2), each 64 x BN/2 as 16x16x32
-//                  bf16 MFMAs with weights as the A operand, so a lane ends up with 4 consecutive output
-//                  channels of one pixel (8-byte NHWC stores).  Global->register->LDS staging, one tile
-//                  ahead (loads issued before the MFMAs of the current tile, LDS written after them, one
-//                  barrier per k-step), XOR-swizzled 16-byte slots so ds_read_b128 is conflict-free.
-//   k_conv_wgrad   dW[co][(tap,ci)] = sum_pixels dY[pix][co] * X[src(pix,tap)][ci]: both operands are
-//                  "k-major" in memory, so tiles are staged as [pixel][channel] and the fragments are
-//                  fetched with the transposing LDS read ds_read_b64_tr_b16.  Split over pixel ranges
-//                  (grid.z); fp32 partial slabs are summed in fixed order (deterministic) by
-//                  k_wgrad_reduce.  The bias gradient rides along as an extra MFMA against a B fragment
-//                  of ones.
+// Kernels (DESIGN.md section 4 has the table): forward and data gradient on k_conv3x3_patch32 / k_conv3x3_p512 (3x3 with the
+// halo patch in LDS), k_conv3x3_c64b (64 -> 64), k_conv0_fwd (image layer), k_conv_igemm_8ph / k_conv_igemm_dma (implicit GEMM,
+// split-K through k_igemm_finalize); weight gradient on k_conv3x3_wgrad_patch, k_conv_wgrad_tile, k_conv0_wgrad and k_conv_wgrad
+// (+ _batched), fp32 slabs per pixel split summed in fixed order by k_wgrad_reduce2 / k_wgrad_reduce_wide; pooling, weight
+// transposes, casts and the head-gradient packing.  The dispatch and the C entries are at the end of the file.
 #include <atomic>
 #include <climits>
 #include <cstdint>
@@ -32,9 +19,6 @@
 #include <hip/hip_bf16.h>
 #include <stdlib.h>
 
-namespace {
-
-}  // namespace
 #include "conv_common.h"
 namespace {
 
@@ -1839,10 +1823,8 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce2_batched(ReduceBatchArgs a
 // (lds_read_tr16_scoped: defined in front of k_conv3x3_c64b)
 
 constexpr int WT_TILE = 64 * 512;                          // one [64 px][256 ch] image
-// STAGES = 2: two 64-pixel buffers, one step ahead, vmcnt(0) + barrier per step.  STAGES = 4 (round 4): four 32-pixel stages
-// (one MFMA k-sub-step each), three stages of DMA in flight behind a COUNTED vmcnt -- the step no longer waits for the DMA it
-// has just issued, and a stage's latency hides under three sub-steps of MFMAs instead of two.
-template <int STAGES>
+// Four 32-pixel stages (one MFMA k-sub-step each), three stages of DMA in flight behind a COUNTED vmcnt -- the step does not
+// wait for the DMA it has just issued, and a stage's latency hides under three sub-steps of MFMAs.
 __global__ __launch_bounds__(512) void k_conv_wgrad_tile(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy,
                                                          float* __restrict__ slab_w, float* __restrict__ slab_b, ConvGeom g,
                                                          int m_per_split, int nsplit, int cout) {
@@ -1896,8 +1878,8 @@ __global__ __launch_bounds__(512) void k_conv_wgrad_tile(const bf16_raw* __restr
         }
     }
     const bool pointwise = g.KH == 1 && g.KW == 1 && g.mul == 1 && g.pad_t == 0 && g.pad_l == 0;   // source pixel = output pixel
-    constexpr int NJ = STAGES == 4 ? 2 : 4;                      // DMA instructions per wave, operand and stage
-    constexpr int XOFF = STAGES == 4 ? WT_TILE / 2 : WT_TILE;     // the x image of a stage starts here
+    constexpr int NJ = 2;                                        // DMA instructions per wave, operand and stage
+    constexpr int XOFF = WT_TILE / 2;                            // the x image of a stage starts here
     auto issue_dma = [&](int mstep, int buf) {
         char* base = smem + buf * (2 * XOFF);
 #pragma unroll
@@ -1958,77 +1940,39 @@ __global__ __launch_bounds__(512) void k_conv_wgrad_tile(const bf16_raw* __restr
     }
     auto rd = [&](int addr) { return lds_read_tr16_scoped(smem + addr, smem); };
 
-    const int nsteps = STAGES == 4 ? (m_end - m_begin + 31) / 32 : (m_end - m_begin + 63) / 64;
-    if constexpr (STAGES == 4) {
+    const int nsteps = (m_end - m_begin + 31) / 32;
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
-            if (p < nsteps) issue_dma(m_begin + p * 32, p);
-    } else {
-        if (nsteps > 0) issue_dma(m_begin, 0);
-    }
+    for (int p = 0; p < 3; ++p)
+        if (p < nsteps) issue_dma(m_begin + p * 32, p);
     auto run = [&](auto bias_tag) {
         constexpr bool BIAS = decltype(bias_tag)::value;
         for (int st = 0; st < nsteps; ++st) {
-            if constexpr (STAGES == 4) {
-                // stage st has landed when at most the two younger stages' 2 * NJ instructions each are still in flight
-                const int younger = min(2, nsteps - 1 - st);
-                if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();                    // ... for every wave; and stage st - 1's buffer is free (raw barrier:
-                asm volatile("" ::: "memory");                   //  __syncthreads() would wait for vmcnt(0) first)
-                if (st + 3 < nsteps) issue_dma(m_begin + (st + 3) * 32, (st + 3) & 3);
-                const int boff = (st & 3) * (2 * XOFF);
-                bf16x8_t fb[4], fa[8];
+            // stage st has landed when at most the two younger stages' 2 * NJ instructions each are still in flight
+            const int younger = min(2, nsteps - 1 - st);
+            if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                    // ... for every wave; and stage st - 1's buffer is free (raw barrier:
+            asm volatile("" ::: "memory");                   //  __syncthreads() would wait for vmcnt(0) first)
+            if (st + 3 < nsteps) issue_dma(m_begin + (st + 3) * 32, (st + 3) & 3);
+            const int boff = (st & 3) * (2 * XOFF);
+            bf16x8_t fb[4], fa[8];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int half = 0; half < 2; ++half)
+                    reinterpret_cast<s16x4_t*>(&fb[c])[half] = rd(bbase[c] + boff + half * 4096);
+#pragma unroll
+            for (int a = 0; a < 8; ++a)
+#pragma unroll
+                for (int half = 0; half < 2; ++half)
+                    reinterpret_cast<s16x4_t*>(&fa[a])[half] = rd(abase[a] + boff + half * 4096);
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int half = 0; half < 2; ++half)
-                        reinterpret_cast<s16x4_t*>(&fb[c])[half] = rd(bbase[c] + boff + half * 4096);
-#pragma unroll
-                for (int a = 0; a < 8; ++a)
-#pragma unroll
-                    for (int half = 0; half < 2; ++half)
-                        reinterpret_cast<s16x4_t*>(&fa[a])[half] = rd(abase[a] + boff + half * 4096);
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[c], acc[a][c], 0, 0, 0);
-                    if constexpr (BIAS) accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], ones, accb[a], 0, 0, 0);
-                }
-                continue;
-            }
-            const int cur = st & 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (st + 1 < nsteps) issue_dma(m_begin + (st + 1) * 64, cur ^ 1);
-            const int boff = cur * (2 * WT_TILE);
-            int ab[8], bb[4];
-#pragma unroll
-            for (int a = 0; a < 8; ++a) ab[a] = abase[a] + boff;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) bb[c] = bbase[c] + boff;
-#pragma unroll
-            for (int ksub = 0; ksub < 2; ++ksub) {
-                bf16x8_t fb[4], fa[8];
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int half = 0; half < 2; ++half)
-                        reinterpret_cast<s16x4_t*>(&fb[c])[half] = rd(bb[c] + ksub * 16384 + half * 4096);
-#pragma unroll
-                for (int a = 0; a < 8; ++a)
-#pragma unroll
-                    for (int half = 0; half < 2; ++half)
-                        reinterpret_cast<s16x4_t*>(&fa[a])[half] = rd(ab[a] + ksub * 16384 + half * 4096);
-#pragma unroll
-                for (int a = 0; a < 8; ++a) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[c], acc[a][c], 0, 0, 0);
-                    if constexpr (BIAS) accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], ones, accb[a], 0, 0, 0);
-                }
+                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[c], acc[a][c], 0, 0, 0);
+                if constexpr (BIAS) accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], ones, accb[a], 0, 0, 0);
             }
         }
     };
@@ -2785,12 +2729,13 @@ struct Knob { const char* name; std::atomic<int> value; };
 constexpr int KNOB_UNSET = INT_MIN;
 Knob g_knobs[] = {{"SSD_ABLATE", {KNOB_UNSET}}, {"SSD_DGRAD_S2", {KNOB_UNSET}}, 
                   {"SSD_CONV_PATCH", {KNOB_UNSET}}, {"SSD_CONV_TILE", {KNOB_UNSET}}, {"SSD_SPLITK", {KNOB_UNSET}},
-                  {"SSD_WGRAD_PATCH", {KNOB_UNSET}}, {"SSD_WGRAD_PATCH_SINGLE", {KNOB_UNSET}},
+                  {"SSD_WGRAD_PATCH", {KNOB_UNSET}},
                   {"SSD_WGRAD_PATCH_SHAPE", {KNOB_UNSET}}, {"SSD_WGRAD_TILE", {KNOB_UNSET}},
                   {"SSD_CONV_PATCH_FLAT", {KNOB_UNSET}}, {"SSD_WGRAD_FIRST", {KNOB_UNSET}}, {"SSD_CONV_FIRST", {KNOB_UNSET}},
                   {"SSD_WGRAD_PATCH_XCD", {KNOB_UNSET}}, {"SSD_CONV_C64", {KNOB_UNSET}}, {"SSD_CONV_POOL_FUSE", {KNOB_UNSET}},
                   {"SSD_CONV_PATCH_ROWFLAT", {KNOB_UNSET}}, {"SSD_MATCH_FUSED", {KNOB_UNSET}}, {"SSD_CONV_P512", {KNOB_UNSET}},
-                  {"SSD_C64B_WGS", {KNOB_UNSET}}, {"SSD_CONV_PW", {KNOB_UNSET}}, {"SSD_PW_WGS", {KNOB_UNSET}}, {"SSD_PW_DYNAMIC", {KNOB_UNSET}}, {"SSD_SP_ABLATE", {KNOB_UNSET}}, {"SSD_WGTILE_STAGES", {KNOB_UNSET}}, {"SSD_CHAIN_WAVES", {KNOB_UNSET}}, {"SSD_WGTILE_MIN_TILES", {KNOB_UNSET}}, {"SSD_CHAIN_TOUCH", {KNOB_UNSET}}, {"SSD_WGTILE_SLAB_X", {KNOB_UNSET}}, {"SSD_WGRAD_PATCH_WGS", {KNOB_UNSET}}};
+                  {"SSD_C64B_WGS", {KNOB_UNSET}}, {"SSD_CONV_PW", {KNOB_UNSET}}, {"SSD_PW_WGS", {KNOB_UNSET}},
+                  {"SSD_SP_ABLATE", {KNOB_UNSET}}};
 Knob* find_knob(const char* name) {
     for (Knob& k : g_knobs) if (!strcmp(k.name, name)) return &k;
     return nullptr;
@@ -2925,14 +2870,13 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
         // (SSD_CONV_PW: bit 0 forward, bit 1 data gradient)
         if ((knob("SSD_CONV_PW", 3) & (EPI == EPI_FWD ? 1 : 2)) && !(g.ablate & 8) && ssd_pw_gemm_serves(EPI, &g, &ep)) {
             SSD_PLAN(SSD_PLAN_PW);
-            return ssd_pw_gemm_launch(EPI, x, w, &g, &ep, ws, ws_bytes, s);
+            return ssd_pw_gemm_launch(EPI, x, w, &g, &ep, s);
         }
     }
     {
         // tile choice: the CU ingests ~28 B/clk from L2, so MACs per staged byte decide the ceiling: prefer the
         // largest tile that still gives every CU work (>= ~2 workgroups per CU), SSD_CONV_TILE overrides (testing)
         const int force = knob("SSD_CONV_TILE", 0);
-        const long long wg_128 = (long long)((g.M + 127) / 128);
         const long long wg_256 = (long long)((g.M + 255) / 256);
         int bm = 128, bn = g.N <= 64 ? 64 : 128;
         const long long pad256 = (long long)((g.N + 255) / 256) * 256, pad128 = (long long)((g.N + 127) / 128) * 128;
@@ -2945,7 +2889,6 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
         if (force == 1) { bm = 128; bn = g.N <= 64 ? 64 : 128; }
         if ((force == 2 || force == 4) && g.N > 128) { bm = 256; bn = 256; }   // (4: the LDS-DMA kernel instead of the 8-phase one)
         if (force == 3 && g.N > 64) { bm = 256; bn = 128; }
-        (void)wg_128;
         // split-K for skinny problems (few tiles, long k loop): partial sums to the caller's workspace
         unsigned ksplit = 1;
         {
@@ -3032,25 +2975,9 @@ bool geom_ok(int B, int H, int W, int C, int Ho, int Wo, int N, int K) {
 
 int ssd_knob(const char* name, int dflt) { return knob(name, dflt); }
 
-// Optional second stream for the slab reductions (ssd_set_wgrad_reduce_stream): per calling thread.  The reduction is ordered
-// behind the slab kernel by an event from a small ring (events are reused: a recorded-and-waited event can be re-recorded).
-static thread_local hipStream_t t_reduce_stream = nullptr;
-static thread_local hipEvent_t t_reduce_events[64];
-static thread_local int t_reduce_event_next = 0, t_reduce_events_made = 0;
-
+// dW / dbias = sum over splits of the slabs, fixed order
 void ssd_launch_wgrad_reduce(hipStream_t s, const float* slab_w, long long sw, long long nw, float* dw, const float* slab_b,
                              long long sb, int nb, float* db, int ns) {
-    if (t_reduce_stream && t_reduce_stream != s) {
-        if (t_reduce_events_made < 64) {
-            for (; t_reduce_events_made < 64; ++t_reduce_events_made)
-                if (hipEventCreateWithFlags(&t_reduce_events[t_reduce_events_made], hipEventDisableTiming) != hipSuccess) break;
-        }
-        if (t_reduce_events_made == 64) {
-            hipEvent_t ev = t_reduce_events[t_reduce_event_next];
-            t_reduce_event_next = (t_reduce_event_next + 1) & 63;
-            if (hipEventRecord(ev, s) == hipSuccess && hipStreamWaitEvent(t_reduce_stream, ev, 0) == hipSuccess) s = t_reduce_stream;
-        }
-    }
     if (ns >= 32) {
         const unsigned nbw = (unsigned)((nw / 4 + 15) / 16), nbb = db ? (unsigned)((nb + 15) / 16) : 0u;
         hipLaunchKernelGGL(k_wgrad_reduce_wide, dim3(nbw + nbb), dim3(256), 0, s, slab_w, sw, nw, dw, slab_b, sb, nb, db, ns, nbw);
@@ -3061,11 +2988,6 @@ void ssd_launch_wgrad_reduce(hipStream_t s, const float* slab_w, long long sw, l
 }
 
 extern "C" {
-
-int ssd_set_wgrad_reduce_stream(void* stream) {
-    t_reduce_stream = (hipStream_t)stream;
-    return SSD_OK;
-}
 
 int ssd_dev_knob(const char* name, int value) {
     if (!name) return SSD_ERR_VALUE;
@@ -3209,12 +3131,6 @@ static int wgrad_patch_min_hw() {           // SSD_WGRAD_PATCH = smallest featur
     return knob("SSD_WGRAD_PATCH", 16);
 }
 
-// dW / dbias = sum over splits of the slabs, fixed order
-static void launch_wgrad_reduce(hipStream_t s, const float* slab_w, long long sw, long long nw, float* dw, const float* slab_b,
-                                long long sb, int nb, float* db, int ns) {
-    ssd_launch_wgrad_reduce(s, slab_w, sw, nw, dw, slab_b, sb, nb, db, ns);
-}
-
 // Data gradient of the second layer (64 -> 64, 3x3 / stride 1 / pad 1) fused with the weight gradient of the first
 // (8 padded image channels -> 64): k_conv3x3_c64b<EPI_DGRAD, true>.  The gradient w.r.t. the first layer's output never
 // reaches memory.  dy [B,H,W,64]; w_t [64][3][3][64] (ssd_weight_transpose of the second layer); relu_bits [B*H*W][8] (sign
@@ -3245,7 +3161,7 @@ int ssd_conv2d_bwd_data_wgrad_first(const void* dy, const void* w_t, const void*
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), C64B_W0_LDS, s, static_cast<const bf16_raw*>(dy), static_cast<const bf16_raw*>(w_t),
                        g, ep, tiles_x, tiles_y, C64W0{static_cast<const bf16_raw*>(image), slab_w, dbias0 ? slab_b : nullptr});
     if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-    launch_wgrad_reduce(s, slab_w, 64ll * 72, 64ll * 72, dw0, slab_b, 64ll, 64, dbias0, (int)grid);
+    ssd_launch_wgrad_reduce(s, slab_w, 64ll * 72, 64ll * 72, dw0, slab_b, 64ll, 64, dbias0, (int)grid);
     return ssd_launch_status();
 }
 
@@ -3283,18 +3199,14 @@ static void wgrad_patch_plan(int B, int Ho, int Wo, int Cin, int Cout, int* tile
     *tiles_x = (Wo + bw - 1) / bw; *tiles_y = (Ho + bh - 1) / bh;
     const int ntiles = B * *tiles_x * *tiles_y;
     const int groups = (Cin / 64) * ((Cout + 63) / 64);
-    const int wp_mult = knob("SSD_WGRAD_PATCH_SINGLE", 0) ? 2 : 1;
-    int want = knob("SSD_WGRAD_PATCH_WGS", 256) * wp_mult / groups;   // one (two when single-buffered) workgroup per CU
+    int want = 256 / groups;                                 // one workgroup per CU
     if (want < 1) want = 1;
     if (want > ntiles) want = ntiles;
     *tps = (ntiles + want - 1) / want;
     *ns = (ntiles + *tps - 1) / *tps;
 }
 
-static void wgrad_tiles(int Cout, long long ktot, int* bmo, int* bnc) {
-    (void)Cout; (void)ktot;
-    *bmo = 128; *bnc = 128;
-}
+constexpr int WG_BMO = 128, WG_BNC = 128;                    // k_conv_wgrad's tile: output channels x (tap, ci) columns
 
 static int wgrad_splits(long long M, int tiles) {
     long long want = 768 / tiles;                            // whole rounds: <= 3 workgroups per CU in total
@@ -3307,11 +3219,8 @@ static int wgrad_splits(long long M, int tiles) {
 
 // 256x256 GEMM weight-gradient kernel: used for wide layers the patch kernel does not serve
 static bool wgrad_use_tile(long long M, int Cout, int ldy, long long ktot, long long x_elems) {
-    // (SSD_WGTILE_MIN_TILES, development: layers with fewer 256 x 256 output tiles go to the 128 x 128 kernel -- a quarter of
-    //  the slab bytes per split at the same workgroup count)
-    const long long tiles = ((ktot + 255) / 256) * ((Cout + 255) / 256);
     return knob("SSD_WGRAD_TILE", 1) && Cout > 128 && ktot >= 256 && M >= 2048 && M * ldy < (1ll << 31) - 16 &&
-           x_elems < (1ll << 31) - 16 && tiles >= knob("SSD_WGTILE_MIN_TILES", 0);
+           x_elems < (1ll << 31) - 16;
 }
 
 // pixel splits for that kernel (one workgroup per CU): estimated time = rounds x steps per split + slab traffic
@@ -3322,9 +3231,7 @@ static int wgrad_tile_splits(long long M, int tiles, long long slab_elems) {
     for (int ns = 1; ns <= 64 && ns <= maxs; ++ns) {
         const long long rounds = ((long long)tiles * ns + 255) / 256;
         const long long steps = ((M + ns - 1) / ns + 63) / 64;
-        // (SSD_WGTILE_SLAB_X: weight of the slab term in tenths, development -- in the step the slab sums run beside another
-        //  stream's kernels at a third of their speed alone, and CUs this kernel leaves idle are not wasted there)
-        const double cost = (double)rounds * steps * 2.2 + (double)ns * slab_elems * 8.0 / 4.0e6 * (knob("SSD_WGTILE_SLAB_X", 10) / 10.0);   // microseconds
+        const double cost = (double)rounds * steps * 2.2 + (double)ns * slab_elems * 8.0 / 4.0e6;   // microseconds
         if (ns == 1 || cost < best_cost) { best = ns; best_cost = cost; }
     }
     return best;
@@ -3339,9 +3246,7 @@ size_t ssd_conv2d_bwd_weight_workspace_bytes(int B, int Ho, int Wo, int Cin, int
         wgrad_patch_plan(B, Ho, Wo, Cin, Cout, &tx, &ty, &tps, &ns);
         patch_bytes = (size_t)ns * ((size_t)ldy * ktot + ldy) * sizeof(float);
     }
-    int bmo, bnc;
-    wgrad_tiles(Cout, ktot, &bmo, &bnc);
-    const int tiles = (int)(((ktot + bnc - 1) / bnc) * ((Cout + bmo - 1) / bmo));
+    const int tiles = (int)(((ktot + WG_BNC - 1) / WG_BNC) * ((Cout + WG_BMO - 1) / WG_BMO));
     const int ns = wgrad_splits((long long)B * Ho * Wo, tiles);
     size_t gen = (size_t)ns * ((size_t)ldy * ktot + ldy) * sizeof(float);
     if (Cin == 8 && Cout <= 64 && ldy <= 64 && ksize == 3) {  // first-layer kernel: up to 512 splits
@@ -3379,7 +3284,7 @@ static int conv2d_bwd_weight_impl(const void* x, const void* dy, float* dw, floa
                            tx, ty, tps, Cout);
         if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
         const int nsr = (ntiles + tps - 1) / tps;
-        launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, nsr);
+        ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, nsr);
         return ssd_launch_status();
     }
     if (wgrad_use_patch(H, W, Ho, Wo, Cin, ksize, stride, pad_t, pad_l) &&
@@ -3389,7 +3294,6 @@ static int conv2d_bwd_weight_impl(const void* x, const void* dy, float* dw, floa
         float* slab_w = static_cast<float*>(ws);
         float* slab_b = slab_w + (size_t)ns * ldy * ktot;
         hipStream_t s = (hipStream_t)stream;
-        const int single = 0;                                   // (single-buffer mode was dropped with the loader-wave kernel)
         const int groups = (Cin / 64) * ((Cout + 63) / 64), nunits = groups * ns;
         // units per XCD group: the largest divisor of the channel-group count whose round-robin placement (group i on
         // XCD i % 8) keeps every XCD within ~7 % of its fair share of workgroups
@@ -3411,16 +3315,16 @@ static int conv2d_bwd_weight_impl(const void* x, const void* dy, float* dw, floa
             using G_ = WpGeom<BH_, BW8_>;                                                                           \
             auto kern_ = k_conv3x3_wgrad_patch<BH_, BW8_>;                                                          \
             static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)(2 * G_::BUF)) != 0) return SSD_ERR_LAUNCH; \
-            hipLaunchKernelGGL(kern_, dim3(grid), dim3(512), (size_t)(single ? 1 : 2) * G_::BUF, s,                  \
+            hipLaunchKernelGGL(kern_, dim3(grid), dim3(512), (size_t)2 * G_::BUF, s,                                 \
                                static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(dy), slab_w,          \
-                               dbias ? slab_b : nullptr, g, tx, ty, tps, ns, Cout, single, xg);                     \
+                               dbias ? slab_b : nullptr, g, tx, ty, tps, ns, Cout, 0, xg);                          \
         } while (0)
         if (shape == 1) SSD_LAUNCH_WP(6, 5);
         else if (shape == 2) SSD_LAUNCH_WP(10, 3);
         else SSD_LAUNCH_WP(16, 2);
 #undef SSD_LAUNCH_WP
         if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-        launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
+        ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
         return ssd_launch_status();
     }
     if (wgrad_use_tile(g.M, Cout, ldy, ktot, (long long)B * H * W * Cin)) {
@@ -3432,24 +3336,15 @@ static int conv2d_bwd_weight_impl(const void* x, const void* dy, float* dw, floa
         float* slab_w = static_cast<float*>(ws);
         float* slab_b = slab_w + (size_t)ns * ldy * ktot;
         hipStream_t s = (hipStream_t)stream;
-if (knob("SSD_WGTILE_STAGES", 4) == 4) {
-            static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(k_conv_wgrad_tile<4>), (int)(4 * WT_TILE)) != 0) return SSD_ERR_LAUNCH;
-            hipLaunchKernelGGL(k_conv_wgrad_tile<4>, dim3(ctiles * mtiles * ns), dim3(512), 4 * WT_TILE, s,
+        static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(k_conv_wgrad_tile), (int)(4 * WT_TILE)) != 0) return SSD_ERR_LAUNCH;
+        hipLaunchKernelGGL(k_conv_wgrad_tile, dim3(ctiles * mtiles * ns), dim3(512), 4 * WT_TILE, s,
                            static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(dy), slab_w, dbias ? slab_b : nullptr, g,
                            mps, ns, Cout);
-        } else {
-            static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(k_conv_wgrad_tile<2>), (int)(4 * WT_TILE)) != 0) return SSD_ERR_LAUNCH;
-            hipLaunchKernelGGL(k_conv_wgrad_tile<2>, dim3(ctiles * mtiles * ns), dim3(512), 4 * WT_TILE, s,
-                           static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(dy), slab_w, dbias ? slab_b : nullptr, g,
-                           mps, ns, Cout);
-        }
         if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-        launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
+        ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
         return ssd_launch_status();
     }
-    int bmo, bnc;
-    wgrad_tiles(Cout, ktot, &bmo, &bnc);
-    const int ctiles = (int)((ktot + bnc - 1) / bnc), mtiles = (Cout + bmo - 1) / bmo;
+    const int ctiles = (int)((ktot + WG_BNC - 1) / WG_BNC), mtiles = (Cout + WG_BMO - 1) / WG_BMO;
     const int ns = wgrad_splits(g.M, ctiles * mtiles);
     int mps = (int)(((long long)g.M + ns - 1) / ns);
     mps = (mps + 63) / 64 * 64;
@@ -3466,7 +3361,7 @@ if (knob("SSD_WGTILE_STAGES", 4) == 4) {
         hipLaunchKernelGGL(k_conv_wgrad, dim3(ctiles, mtiles, ns), dim3(WG), lds, s, xp, dyp, slab_w, sb, g, mps);
     }
     if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-    launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
+    ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
     return ssd_launch_status();
 }
 
@@ -3504,9 +3399,7 @@ int ssd_conv2d_bwd_weight_batched(const ssd_wgrad_item* items, int count, void* 
             wgrad_use_patch(it.H, it.W, it.Ho, it.Wo, it.Cin, it.ksize, it.stride, it.pad_t, it.pad_l) ||
             wgrad_use_tile(g.M, it.Cout, it.ldy, ktot, (long long)it.B * it.H * it.W * it.Cin))
             return SSD_ERR_UNSUPPORTED;
-        int bmo, bnc;
-        wgrad_tiles(it.Cout, ktot, &bmo, &bnc);
-        const int ctiles = (int)((ktot + bnc - 1) / bnc), mtiles = (it.Cout + bmo - 1) / bmo;
+        const int ctiles = (int)((ktot + WG_BNC - 1) / WG_BNC), mtiles = (it.Cout + WG_BMO - 1) / WG_BMO;
         const int ns = wgrad_splits(g.M, ctiles * mtiles);
         if (ns >= 32) return SSD_ERR_UNSUPPORTED;              // (the wide reduction's case)
         int mps = (int)(((long long)g.M + ns - 1) / ns);

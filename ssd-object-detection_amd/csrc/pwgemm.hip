@@ -72,7 +72,7 @@ __device__ __forceinline__ void pw_mma_quadrant(f32x4_t (&acc)[4][8], const bf16
 // which fetches the activation tile into its L2 once).  Tickets 0 .. G/8 - 1 of a class are the first tiles of its G/8
 // workgroups; the following ones are CLAIMED from a per-class counter (one returning atomic per tile), so that a workgroup
 // that reaches its CU late -- the kernel shares the chip with another stream's launches -- simply takes fewer tiles; with
-// counters == nullptr every workgroup has a fixed share (ticket += G/8).  See the launch function for which is the default.
+// counters == nullptr every workgroup has a fixed share (ticket += G/8): the only form the launch function selects.
 struct PwCursor {
     int k;                                   // ticket in the class, >= kmax: exhausted
     int kt;                                  // k-tile inside the tile
@@ -385,8 +385,7 @@ bool ssd_pw_gemm_serves(int epi, const void* geom, const void* epilogue) {
     return true;
 }
 
-int ssd_pw_gemm_launch(int epi, const void* x, const void* w, const void* geom, const void* epilogue, void* ws, size_t ws_bytes,
-                       void* stream) {
+int ssd_pw_gemm_launch(int epi, const void* x, const void* w, const void* geom, const void* epilogue, void* stream) {
     if (!ssd_pw_gemm_serves(epi, geom, epilogue)) return SSD_ERR_UNSUPPORTED;
     const ConvGeom& g = *static_cast<const ConvGeom*>(geom);
     const Epilogue& ep = *static_cast<const Epilogue*>(epilogue);
@@ -400,15 +399,12 @@ int ssd_pw_gemm_launch(int epi, const void* x, const void* w, const void* geom, 
     if (G > tiles) G = tiles;
     G = (G + 7) / 8 * 8;
     sc.G8 = G / 8;
-    // claimed tiles need eight zeroed counters: the head of the caller's split-K workspace (stream-ordered with everything
-    // else that uses it), cleared by a memset node in front of the launch; without a workspace every workgroup takes a fixed share
-    // Default: fixed shares.  Measured on the batch-64 train step (same box, interleaved, tools_dev/ab_train_step.py and
-    // tools_dev/ab_knobs.sh): fixed shares 9.43-9.51 ms, claimed tiles + the memset node 9.50-9.51 ms, the one-tile-per-workgroup
-    // kernels this replaces 9.45-9.56 ms -- the memset is a fill KERNEL that needs a CU slot (5 us alone, 66 us once behind
-    // another stream's resident workgroups), which eats what claiming gains.  SSD_PW_DYNAMIC=1 selects claiming.
-    sc.counters = (ws && ws_bytes >= 64 && ssd_knob("SSD_PW_DYNAMIC", 0)) ? static_cast<unsigned*>(ws) : nullptr;
+    // Every workgroup takes a fixed share.  Claimed tiles + the memset node of their counters measured 9.50-9.51 ms on the
+    // batch-64 train step against 9.43-9.51 ms -- the memset is a fill KERNEL that needs a CU slot (5 us alone, 66 us once behind
+    // another stream's resident workgroups), which ate what claiming gained: the host side of it is removed.  The kernel keeps
+    // its `counters` argument (always null): without it the compiler lays the main loop out differently.
+    sc.counters = nullptr;
     hipStream_t s = (hipStream_t)stream;
-    if (sc.counters && hipMemsetAsync(sc.counters, 0, 32, s) != hipSuccess) return SSD_ERR_LAUNCH;
 #define PW_LAUNCH(KERN_, SLOT_)                                                                                      \
     do {                                                                                                            \
         auto kern = KERN_;                                                                                          \

@@ -153,7 +153,7 @@ struct CLevel {
 };
 struct CArgs {
     int levels, B;
-    int prezeroed;                           // the caller cleared the maps: pixels no row reaches are left alone
+    int prezeroed;                           // always 0 (the host-side switch is removed): pixels no row reaches are zero-filled
     CLevel lv[SSD_MAX_LEVELS];
 };
 
@@ -534,7 +534,7 @@ size_t ssd_heads_bwd_data_sparse_workspace_bytes(int B, const ssd_head_layers* h
     return tot;
 }
 
-int ssd_heads_bwd_data_sparse_levels(const ssd_head_grads* hg, const ssd_head_layers* hl, int B, unsigned level_mask, int prezeroed,
+int ssd_heads_bwd_data_sparse_levels(const ssd_head_grads* hg, const ssd_head_layers* hl, int B, unsigned level_mask,
                                      void* ws, size_t ws_bytes, void* stream) {
     const int rc = check_heads(hg, hl, B);
     if (rc != SSD_OK) return rc;
@@ -547,8 +547,7 @@ int ssd_heads_bwd_data_sparse_levels(const ssd_head_grads* hg, const ssd_head_la
     za.levels = ca.levels = hg->levels;
     za.mask = level_mask;
     za.count = hg->count;
-    ca.B = B;
-    ca.prezeroed = prezeroed ? 1 : 0;
+    ca.B = B; ca.prezeroed = 0;
     char* p = static_cast<char*>(ws);
     int blk = 0, cap_tiles = 0;
     for (int l = 0; l < SSD_MAX_LEVELS; ++l) {
@@ -576,7 +575,7 @@ int ssd_heads_bwd_data_sparse_levels(const ssd_head_grads* hg, const ssd_head_la
 
 int ssd_heads_bwd_data_sparse(const ssd_head_grads* hg, const ssd_head_layers* hl, int B, void* ws, size_t ws_bytes,
                               void* stream) {
-    return ssd_heads_bwd_data_sparse_levels(hg, hl, B, ~0u, 0, ws, ws_bytes, stream);
+    return ssd_heads_bwd_data_sparse_levels(hg, hl, B, ~0u, ws, ws_bytes, stream);
 }
 
 size_t ssd_heads_bwd_weight_sparse_workspace_bytes(int B, const ssd_head_grads* hg, const ssd_head_layers* hl) {

@@ -320,10 +320,15 @@ int ssd_conv2d_bwd_weight_unpooled(const void* x, const void* dpool, const void*
     float* slab_w = static_cast<float*>(ws);
     float* slab_b = slab_w + (size_t)p.ns * Cout * ktot;
     hipStream_t s = (hipStream_t)stream;
+#ifdef SSD_DEV_ABLATE                        // timing-only ablations (they change results): development builds only
+    const int ablate = ssd_knob("SSD_SP_ABLATE", 0);
+#else
+    const int ablate = 0;
+#endif
     if (ensure_lds(g_sp_once, reinterpret_cast<const void*>(k_conv3x3_wgrad_unpool), SP_LDS) != 0) return SSD_ERR_LAUNCH;
     hipLaunchKernelGGL(k_conv3x3_wgrad_unpool, dim3(p.grid), dim3(256), SP_LDS, s, static_cast<const bf16_raw*>(x),
                        static_cast<const bf16_raw*>(dpool), static_cast<const unsigned*>(pool_code), slab_w, dbias ? slab_b : nullptr, g,
-                       Hp, Wp, p.tx, p.ty, p.tps, p.ns, p.xg, ssd_knob("SSD_SP_ABLATE", 0));
+                       Hp, Wp, p.tx, p.ty, p.tps, p.ns, p.xg, ablate);
     if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
     ssd_launch_wgrad_reduce(s, slab_w, (long long)Cout * ktot, (long long)Cout * ktot, dw, slab_b, (long long)Cout, Cout, dbias, p.ns);
     return ssd_launch_status();

@@ -7,7 +7,6 @@ block3_conv3, a SAME max-pool, three 38x38 convolutions, five extra stages, and 
 Activations are NHWC bf16, weights [Cout][k][k][Cin] bf16 (fp32 masters), accumulation fp32 on MFMA.
 The 3-channel image is carried in 8 zero-padded channels (first-layer weights of channels 3..7 are and stay 0).
 """
-import ctypes
 import math
 import os
 
@@ -173,33 +172,16 @@ class SSDEngine:
         self.tail_stream = os.environ.get("SSD_TAIL_STREAM", "1") == "1"
         self.big_heads_side = os.environ.get("SSD_BIG_HEADS_SIDE", "1") == "1"
         self.pack_side = os.environ.get("SSD_PACK_SIDE", "1") == "1"
-        # 2 = weight gradients alternate between two side streams: measured 8.99 -> 9.36 ms (three MFMA kernels share the CUs'
-        # LDS and registers badly); 1 = one side stream
-        self.side_streams = int(os.environ.get("SSD_SIDE_STREAMS", "1"))
-        # the split reductions behind the weight-gradient kernels (0.55 ms of small HBM-bound launches per step, each in front
-        # of the next layer's kernel on the side stream) on a stream of their own (ssd_set_wgrad_reduce_stream): measured
-        # 9.02 -> 9.34 ms -- beside TWO MFMA kernels the small launches starve, and the next-but-one layer waits for them: off
-        self.reduce_stream = os.environ.get("SSD_REDUCE_STREAM", "0") == "1"
         self.batch_chain_wgrads = os.environ.get("SSD_BATCH_CHAIN_WGRADS", "1") == "1"
-        self.batch_chain_front = os.environ.get("SSD_BATCH_CHAIN_FRONT", "0") == "1"   # measured 9.015 -> 9.037 ms: off
-        self.wgrad_group = int(os.environ.get("SSD_WGRAD_GROUP", "3"))
-        self.wgrad_on_main = set(int(v) for v in os.environ.get("SSD_WGRAD_ON_MAIN", "").split(",") if v.strip())   # trunk nodes      # weight-gradient launches per cross-stream wait
+        self.wgrad_group = int(os.environ.get("SSD_WGRAD_GROUP", "3"))      # weight-gradient launches per cross-stream wait
         self.split_heads_dgrad = int(os.environ.get("SSD_SPLIT_HEADS_DGRAD", "2"))   # 0 one call, 1 small | large levels, 2 ... and one call per large level
         # the heads of the maps the forward chain produces (all available at once, behind one launch): every other one on the
         # main stream instead of queueing all of them on the third
         self.chain_heads_split = os.environ.get("SSD_CHAIN_HEADS_SPLIT", "1") == "1"
         self.chain_prefetch = os.environ.get("SSD_CHAIN_PREFETCH", "1") == "1"
-        # the large levels' gradient maps (38x38, 19x19: 140 MB at batch 64) are cleared during the FORWARD pass, on the third
-        # stream under a compute-bound layer, and the heads' data gradient then writes only the ~5 % of pixels a gradient row
-        # reaches: the 140 MB of zero stores leave the window behind the loss, where nothing large can run yet
-        self.prezero_maps = os.environ.get("SSD_PREZERO_MAPS", "0") == "1"   # measured neutral (9.046 vs 9.060 ms): off
-        self._prezeroed = set()
         # fused-optimizer buckets that run at the END of the main stream instead of in the side stream's queue: the side stream (weight
         # gradients) is the longer chain, the main stream finishes ~0.5 ms earlier (round 4, same-box A/B: 1 -> 4 buckets -0.06 ms)
         self.opt_defer = int(os.environ.get("SSD_OPT_DEFER", "4"))
-        # the heads' bucket (45 % of the parameters) is complete right after the loss, where the side stream would run its
-        # HBM-bound update next to the extras' latency-bound data-gradient chain: 1 = run it at the main stream's tail instead
-        self.opt_defer_heads = int(os.environ.get("SSD_OPT_DEFER_HEADS", "0"))
         self.pool_only = {}                    # node -> whether a pool-only kernel serves it (learned at the first call)
         self.fuse_unpool = {} if os.environ.get("SSD_FUSE_UNPOOL", "1") == "1" else None    # node -> data gradient un-pools itself
         # activation index -> its sign bits are written by the forward kernel (learned at the first call); data-gradient
@@ -481,19 +463,7 @@ class SSDEngine:
                     head(lvl, self._ws_tail)
 
         self.bits_valid = set()
-        self._prezeroed = set()
-        big_maps = [ni + 1 for lvl, (ni, h, ch) in enumerate(self.fm) if B * h * h >= 16384]
-        clear_at = min(9, len(self.nodes) - 1)            # under block 4 (compute-bound 3x3 layers on 38x38 maps)
         for i, nd in enumerate(self.nodes):
-            if (i == clear_at and tail is not None and self.prezero_maps and self.sparse_heads and self.split_heads_dgrad
-                    and big_maps and len(big_maps) < len(self.fm)):
-                ev = torch.cuda.Event()
-                ev.record(main)
-                with torch.cuda.stream(tail):
-                    tail.wait_event(ev)
-                    for a in big_maps:
-                        c["gacts"][a].zero_()
-                self._prezeroed = set(big_maps)
             if (self.chain_start is not None and i == self.chain_start - 1 and "fwd" in self.chain and tail is not None
                     and self.chain_prefetch):
                 ev = torch.cuda.Event()                   # the chain's packed filters into L2 while the layer in front of it runs
@@ -699,17 +669,6 @@ class SSDEngine:
         return gates
 
     def backward(self, dloc, dconf, on_ready=None, fused_adam=None, heads=None, on_dgrad=None):
-        if self._vgg_fp8_fwd:
-            raise RuntimeError("backward() after an mxfp8 forward: it writes neither the bf16 maps nor the ReLU bits and pool "
-                               "codes backward() reads; run forward(x) in bf16 first")
-        try:
-            return self._backward(dloc, dconf, on_ready, fused_adam, heads, on_dgrad)
-        finally:
-            if getattr(self, "_red_active", None) is not None:   # (an exception between set and reset: do not leave the
-                self.L.ssd_set_wgrad_reduce_stream(None)          #  library sending other callers' reductions to our stream)
-                self._red_active = None
-
-    def _backward(self, dloc, dconf, on_ready=None, fused_adam=None, heads=None, on_dgrad=None):
         """Gradients of all parameters into self.grad (flat fp32) from d(loss)/d(loc), d(loss)/d(conf).
         on_ready([tensor indices]) is called right after the launches that complete those tensors' gradients (on the
         stream that runs them: an event recorded there covers them).
@@ -720,6 +679,9 @@ class SSDEngine:
         The data-gradient chain (the critical path) runs on the current stream, every weight gradient on the side
         stream as soon as its input gradient exists: the split reductions and round tails of one overlap the MFMA
         work of the other.  Each launch still sums in a fixed order, so results do not depend on the overlap."""
+        if self._vgg_fp8_fwd:
+            raise RuntimeError("backward() after an mxfp8 forward: it writes neither the bf16 maps nor the ReLU bits and pool "
+                               "codes backward() reads; run forward(x) in bf16 first")
         if heads is None and self.sparse_heads:
             heads = self.heads_from_dense(dloc, dconf)
         B = heads.B if heads is not None else dloc.shape[0]
@@ -749,18 +711,11 @@ class SSDEngine:
                 on_dgrad(node)
             if node in opt_at:
                 t0, t1 = opt_at.pop(node)
-                if side is not None and ((node is not None and node in defer_nodes) or (node is None and self.opt_defer_heads)):
+                if side is not None and node in defer_nodes:
                     flush_side()
                     ev = torch.cuda.Event()
                     ev.record(side)                    # the bucket's weight gradients are all enqueued there by now
-                    ev2 = None
-                    if getattr(self, "_side2", None) is not None and self.side_streams == 2 and on_ready is None and on_dgrad is None:
-                        ev2 = torch.cuda.Event()
-                        ev2.record(self._side2)
-                    if getattr(self, "_red_active", None) is not None:
-                        ev2 = torch.cuda.Event()
-                        ev2.record(self._red_active)
-                    deferred.append((t0, t1, ev, ev2))
+                    deferred.append((t0, t1, ev))
                     return
                 # the heads' update rewrites head_w_t, which the large levels' sparse data gradients on the third stream still
                 # read: behind their events as well as behind the main stream
@@ -772,41 +727,17 @@ class SSDEngine:
                     self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
                 on_side(run, [], join=True)
 
-        side2 = None
-        # (not with a gradient exchange attached: its bucket launch records ONE event on the stream of the bucket's last tensor,
-        #  which covers the bucket only if all of its weight gradients ran on that stream)
-        if side is not None and self.side_streams == 2 and on_ready is None and on_dgrad is None:
-            if getattr(self, "_side2", None) is None:
-                self._side2 = torch.cuda.Stream(device=self.device)
-                self._ws_side2 = ops.MatchWorkspace()
-            side2 = self._side2
-        turn = [0]
-        red, red_events = None, []
-        if side is not None and self.reduce_stream and side2 is None and on_ready is None and on_dgrad is None:
-            if getattr(self, "_red", None) is None:
-                self._red = torch.cuda.Stream(device=self.device)
-                self._ws_side_b = ops.MatchWorkspace()
-            red = self._red
-            ev0 = torch.cuda.Event()
-            ev0.record(main)
-            red.wait_event(ev0)                                # (joins the launch sequence / a graph capture here)
-            _lib.check(self.L.ssd_set_wgrad_reduce_stream(ctypes.c_void_p(red.cuda_stream)))
-        self._red_active = red
-
         def on_side(fn, tensors, join=False, now=False):
-            """Run fn (a weight-gradient launch) after everything enqueued so far on the main stream.
-            Reduction stream: the slab sums of the calls go to `red` (the library orders each behind its slab kernel); calls
-            alternate between two slab workspaces and call k waits for the sum of call k - 2, whose workspace it reuses.
-            join: fn reads gradients (the optimizer): behind every sum enqueued so far.
-            Two side streams (SSD_SIDE_STREAMS=2): the launches alternate between them instead."""
+            """Run fn (a weight-gradient launch, or with join=True the optimizer, which reads gradients) on the side stream,
+            after everything enqueued so far on the main stream."""
             if side is None:
                 fn(self._ws)
                 if on_ready:
                     on_ready(tensors)
                 return
-            if join or now or self.wgrad_group <= 1 or side2 is not None or red is not None:
+            if join or now or self.wgrad_group <= 1:
                 flush_side()
-                run_on_side(fn, tensors, join, None)
+                run_on_side(fn, tensors, None)
                 return
             # grouped: the side stream is hundreds of microseconds behind the main stream for most of the backward pass, yet every
             # cross-stream wait costs it ~6 us of idle time (30 of them per step).  `wgrad_group` launches share ONE wait -- on the
@@ -824,42 +755,19 @@ class SSDEngine:
             ev.record(main)
             first = True
             for fn_, tensors_ in pending:
-                run_on_side(fn_, tensors_, False, ev if first else False)
+                run_on_side(fn_, tensors_, ev if first else False)
                 first = False
             pending.clear()
 
-        def run_on_side(fn, tensors, join, ev):
+        def run_on_side(fn, tensors, ev):
             """ev: None = wait for the main stream as it is now; an event = wait for it; False = no wait (grouped behind one)."""
             if ev is None:
                 ev = torch.cuda.Event()
                 ev.record(main)
-            s_, ws_ = side, self._ws_side
-            if side2 is not None and not join:
-                turn[0] ^= 1
-                if turn[0] == 0:
-                    s_, ws_ = side2, self._ws_side2
-            with torch.cuda.stream(s_):
+            with torch.cuda.stream(side):
                 if ev is not False:
-                    s_.wait_event(ev)
-                if join and side2 is not None:
-                    e2 = torch.cuda.Event()
-                    e2.record(side2)
-                    s_.wait_event(e2)
-                if red is not None:
-                    if join:
-                        if red_events:
-                            s_.wait_event(red_events[-1])
-                    else:
-                        k = len(red_events)
-                        if k & 1:
-                            ws_ = self._ws_side_b
-                        if k >= 2:
-                            s_.wait_event(red_events[k - 2])
-                fn(ws_)
-                if red is not None and not join:
-                    e = torch.cuda.Event()
-                    e.record(red)
-                    red_events.append(e)
+                    side.wait_event(ev)
+                fn(self._ws_side)
                 if on_ready:
                     on_ready(tensors)
 
@@ -901,18 +809,16 @@ class SSDEngine:
                 ev.record(main)
                 with torch.cuda.stream(self._tail):
                     self._tail.wait_event(ev)
-                    pz = all(self.fm[lvl][0] + 1 in self._prezeroed for lvl in big_lv)
-                    self._prezeroed = set()                # (consumed: the trunk chain accumulates into the maps from here on)
                     if self.split_heads_dgrad == 2:
                         # one call per level, the level the chain reaches first (19x19) first: its event does not wait for
                         # the 38x38 level's 94 MB of stores
                         for lvl in reversed(big_lv):
-                            ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=[lvl], prezeroed=pz)
+                            ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=[lvl])
                             done = torch.cuda.Event()
                             done.record(self._tail)
                             sparse_head_done[self.fm[lvl][0] + 1] = done
                     else:
-                        ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=big_lv, prezeroed=pz)
+                        ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=big_lv)
                         done = torch.cuda.Event()
                         done.record(self._tail)
                         for lvl in big_lv:
@@ -1011,29 +917,21 @@ class SSDEngine:
             except NotImplementedError:               # SSD_ERR_UNSUPPORTED: nothing launched
                 self.chain = self.chain - {"bwd"}
         batched_w = set()
-        if chained and side is not None and self.batch_chain_wgrads and side2 is None and red is None and self.wgrad_probe is None:
+        if chained and side is not None and self.batch_chain_wgrads and self.wgrad_probe is None:
             # ... and their weight gradients in two launches (slab kernel + slab sums) instead of twelve
-            # (the layer in FRONT of the chain too, where the small-layer kernel serves it: its output gradient is the chain's
-            #  last result, so its weight gradient is ready at the same moment)
-            extra = [self.chain_start - 1] if (self.batch_chain_front and self.nodes[self.chain_start - 1]["kind"] == "conv") else []
-            for front in (extra, []):
-                order = sorted(chained, reverse=True) + front
-                layers, tens = [], []
-                for j in order:
-                    ndj = self.nodes[j]
-                    wt, bt = self.conv_params[j]
-                    layers.append((acts[j], gacts[j + 1], ndj["cout"], ndj["k"], ndj["stride"], ndj["pt"], ndj["pl"],
-                                   self.view(wt, self.grad), self.view(bt, self.grad)))
-                    tens += [wt.index, bt.index]
-                try:
-                    on_side(lambda ws: ops.conv2d_bwd_weight_batched(layers, ws=ws), tens, now=True)
-                    batched_w = set(order)
-                    break
-                except NotImplementedError:           # SSD_ERR_UNSUPPORTED: nothing launched
-                    if front:
-                        self.batch_chain_front = False
-                    else:
-                        self.batch_chain_wgrads = False
+            order = sorted(chained, reverse=True)
+            layers, tens = [], []
+            for j in order:
+                ndj = self.nodes[j]
+                wt, bt = self.conv_params[j]
+                layers.append((acts[j], gacts[j + 1], ndj["cout"], ndj["k"], ndj["stride"], ndj["pt"], ndj["pl"],
+                               self.view(wt, self.grad), self.view(bt, self.grad)))
+                tens += [wt.index, bt.index]
+            try:
+                on_side(lambda ws: ops.conv2d_bwd_weight_batched(layers, ws=ws), tens, now=True)
+                batched_w = set(order)
+            except NotImplementedError:               # SSD_ERR_UNSUPPORTED: nothing launched
+                self.batch_chain_wgrads = False
         for i in range(len(self.nodes) - 1, -1, -1):
             nd = self.nodes[i]
             g_out = gacts[i + 1]
@@ -1062,12 +960,6 @@ class SSDEngine:
                     probe["events"].append((i, e0, e1))
             if i in batched_w:
                 pass                                  # (its weight gradient left with the batched launch above)
-            elif side is not None and i in self.wgrad_on_main:
-                # the side stream (every weight gradient + the optimizer) ends ~0.45 ms after the main stream: this layer's weight
-                # gradient runs on the MAIN stream, in front of its data gradient, and both chains end closer together
-                wgrad(self._ws)
-                if on_ready:
-                    on_ready([wt.index, bt.index])
             else:
                 on_side(wgrad, [wt.index, bt.index])
             if i == 0 or i in chained:            # no gradient w.r.t. the image / its data gradient came out of the chain launch
@@ -1119,19 +1011,11 @@ class SSDEngine:
             main.wait_event(prefetch_done)                # (joins the third stream even where nothing else ran on it)
         for ev in sparse_head_done.values():      # (a large level whose map no trunk node accumulated into)
             main.wait_event(ev)
-        for t0, t1, ev, ev2 in deferred:
+        for t0, t1, ev in deferred:
             main.wait_event(ev)
-            if ev2 is not None:
-                main.wait_event(ev2)
             self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
         if side is not None:
             main.wait_stream(side)
-            if side2 is not None:
-                main.wait_stream(side2)
-            if red is not None:
-                main.wait_stream(red)
-                _lib.check(self.L.ssd_set_wgrad_reduce_stream(None))
-                self._red_active = None
 
     # ---------------------------------------------------------------- optimizer
     def clip_scales(self, clip=0.01):

@@ -80,8 +80,7 @@ def test_round4_entries_refuse_on_the_host():
     need = L.ssd_conv2d_bwd_weight_batched_workspace_bytes(items, 1)
     assert need > 0
     assert L.ssd_conv2d_bwd_weight_batched(items, 1, dummy, need, None) == _lib.SSD_ERR_UNSUPPORTED       # the 256-wide tile kernel's layer
-    assert L.ssd_heads_bwd_data_sparse_levels(None, None, 4, 3, 0, None, 0, None) != _lib.SSD_OK
-    assert L.ssd_set_wgrad_reduce_stream(None) == _lib.SSD_OK
+    assert L.ssd_heads_bwd_data_sparse_levels(None, None, 4, 3, None, 0, None) != _lib.SSD_OK
 
 
 def test_synthetic_generator_matches_fixture_inputs():

@@ -309,7 +309,7 @@ def test_chain_launch_matches_the_per_layer_schedule():
 
 
 def test_schedule_switches_are_bitwise_neutral():
-    """Every schedule switch the engine keeps (round 4: most of them measured slower and left off) only moves the SAME launches
+    """Every schedule switch the engine keeps (the ones that measured slower were removed) only moves the SAME launches
     between streams, groups them or batches them into launches that run the same blocks: predictions and every gradient must
     equal the default schedule bit for bit.  Batch 48: both large head levels (38x38, 19x19) take the split path."""
     import ssd_object_detection_amd.ops as ops
@@ -330,9 +330,8 @@ def test_schedule_switches_are_bitwise_neutral():
 
     ref = run()
     assert eng.chain == {"fwd", "bwd"} and eng.batch_chain_wgrads          # the default really is the chained / batched schedule
-    switches = [("wgrad_group", 1), ("batch_chain_wgrads", False), ("batch_chain_front", True), ("split_heads_dgrad", 0),
-                ("split_heads_dgrad", 1), ("prezero_maps", True), ("reduce_stream", True), ("side_streams", 2),
-                ("wgrad_on_main", {14}), ("chain_heads_split", False), ("chain_prefetch", False), ("pack_side", False)]
+    switches = [("wgrad_group", 1), ("batch_chain_wgrads", False), ("split_heads_dgrad", 0), ("split_heads_dgrad", 1),
+                ("chain_heads_split", False), ("chain_prefetch", False), ("pack_side", False)]
     for name, value in switches:
         saved = getattr(eng, name)
         setattr(eng, name, value)

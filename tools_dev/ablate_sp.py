@@ -1,4 +1,5 @@
-"""Dev: timing-only ablations of k_conv3x3_wgrad_unpool (SSD_SP_ABLATE bits: 1 no DMA after the first block, 2 no smfmac, 4 no B reads, 8 no producer)."""
+"""Dev: timing-only ablations of k_conv3x3_wgrad_unpool (SSD_SP_ABLATE bits: 1 no DMA after the first block, 2 no smfmac, 4 no B reads, 8 no producer).
+Needs a library built with -DSSD_DEV_ABLATE (SSD_EXTRA_HIPCC_FLAGS=-DSSD_DEV_ABLATE python ssd-object-detection_amd/build.py --force)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
