@@ -829,12 +829,13 @@ def augment_image(src, src_kind, src_off, src_hw, params, S=300, normalize=True,
     return out
 
 
-def maxpool2x2_fwd(x, same=False):
+def maxpool2x2_fwd(x, same=False, out=None):
     L = _lib.lib()
     _bf(x)
     B, H, W, C = x.shape
     Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if same else (H // 2, W // 2)
-    y = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
+    y = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device) if out is None else out
+    assert y.shape == (B, Ho, Wo, C) and y.dtype == torch.bfloat16 and y.is_contiguous()
     _lib.check(L.ssd_maxpool2x2_fwd(_ptr(x), _ptr(y), B, H, W, C, Ho, Wo, _stream()))
     return y
 

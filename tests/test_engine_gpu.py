@@ -174,8 +174,7 @@ def test_optimizer_vs_oracle(engine):
             m[sl], v[sl] = m_, v_
         got = engine.param.cpu().numpy()
         assert np.abs(got - p).max() <= 2e-6, step
-    bf = engine.param_bf16.float().cpu().numpy()
-    assert np.abs(bf - got).max() <= 2 ** -8 * np.abs(got).max()
+    assert torch.equal(engine.param_bf16, engine.param.bfloat16())          # the bf16 copy the convolutions read: one rounding
     engine.init_params(seed=3)
 
 
