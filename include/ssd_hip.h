@@ -200,6 +200,35 @@ int ssd_nms_max_candidates(void);
 int ssd_nms(const float* score, const int32_t* cls, const float* box, const uint8_t* cand, int B, int A,
             float iou_thresh, int max_cand, uint8_t* keep, int32_t* keep_count, void* stream);
 
+/* Multi-label detection output (build-defined; the SSD detection-output protocol: every (anchor, class) pair is scored, an
+ * anchor may be reported under several classes).  Per image, F = C-1 foreground classes, background = class C-1:
+ *   1. p[a][c], c < F: float32 softmax probability (row maximum subtracted, __expf, fixed summation order).  One device
+ *      function computes it for both entry points: the score bits ssd_detect_pairs reports equal what ssd_class_scores
+ *      writes for the same pair.  (Not necessarily bit-equal to ssd_score_decode's score.)
+ *   2. pair (a, c) is a candidate iff p[a][c] > score_thresh.  There is NO background test: the reference's
+ *      `p_background <= thresh` rule belongs to the single-label path (ssd_score_decode) only.
+ *   3. candidates are ordered by (score desc, anchor asc, class asc); only the first max_cand take part
+ *      (1 <= max_cand <= ssd_detect_max_candidates()).  The cut is exact for every input, score ties included.
+ *   4. a participating anchor is decoded as ssd_score_decode does it (float64, stored as float32 cx, cy, w, h).
+ *   5. in that order a pair is kept iff its IoU (ssd_nms's float32 IoU) with every already kept pair OF ITS CLASS is
+ *      <= iou_thresh.
+ *   6. the kept pairs, in the same order, cut to the first keep_top_k (1 <= keep_top_k <= ssd_detect_max_keep()) = K rows.
+ *   n_cand int32[B]  pairs above the threshold before the cut (exact); n_det int32[B] rows that hold a detection;
+ *   det_score float[B*K], det_cls int32[B*K], det_anchor int32[B*K], det_box float[B*K*4], det_valid uint8[B*K]:
+ *   rows at or beyond n_det hold score 0, class -1, anchor -1, box 0, valid 0 (ssd_eval_match's convention).  Every output
+ *   element is written on every call.  ws: ssd_detect_pairs_workspace_bytes(B, A, C) bytes, no initial contents needed.
+ * ssd_class_scores: step 1 alone, prob float[B*A*(C-1)] dense.
+ * dtype SSD_F32 / SSD_BF16; 1 <= A <= 65536, 2 <= C <= 65536, A*(C-1) < 2^31.  Before any launch: SSD_ERR_VALUE for a NULL
+ * pointer, B / A / C, max_cand or keep_top_k out of range; SSD_ERR_WORKSPACE for a short ws. */
+int ssd_detect_max_candidates(void);
+int ssd_detect_max_keep(void);
+int ssd_class_scores(const void* conf, int dtype, int B, int A, int C, float* prob, void* stream);
+size_t ssd_detect_pairs_workspace_bytes(int B, int A, int C);
+int ssd_detect_pairs(const void* conf, const void* loc, int dtype, const double* priors, int B, int A, int C,
+                     float score_thresh, double in_size, float iou_thresh, int max_cand, int keep_top_k, int32_t* n_cand,
+                     int32_t* n_det, float* det_score, int32_t* det_cls, int32_t* det_anchor, float* det_box,
+                     uint8_t* det_valid, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation metric on the device (no reference counterpart: the reference fetches its validation split at
  * models/ssd_model.py:291 and drops it).  Build-defined; the definition and oracle is utils/metrics.py:coco_map -- COCO

@@ -89,6 +89,13 @@ _SIGNATURES = {
                                         ctypes.c_float, ctypes.c_double, VP, VP, VP, VP, VP]),
     "ssd_nms_max_candidates": (ctypes.c_int, []),
     "ssd_nms": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, VP, VP, VP]),
+    "ssd_detect_max_candidates": (ctypes.c_int, []),
+    "ssd_detect_max_keep": (ctypes.c_int, []),
+    "ssd_class_scores": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP, VP]),
+    "ssd_detect_pairs_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "ssd_detect_pairs": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                        ctypes.c_double, ctypes.c_float, ctypes.c_int, ctypes.c_int, VP, VP, VP, VP, VP, VP, VP,
+                                        VP, ctypes.c_size_t, VP]),
     "ssd_eval_max_dets": (ctypes.c_int, []),
     "ssd_eval_match": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP, VP, VP, _c_double_p, ctypes.c_int,
                                       VP, VP, VP, VP, VP, VP]),

@@ -54,7 +54,10 @@ class SSDObjectDetectionModel:
             self.augment = augment                         # ops.AugmentSpec: SSD data augmentation on the device; None = off
             # validation during the run (None = off): dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
             # max_dets=100, num_data=0, precision="bf16"); missing keys take these defaults.  After every `every`-th epoch
-            # the validation split (its first num_data samples if > 0) is evaluated with metric="device"
+            # the validation split (its first num_data samples if > 0) is evaluated with metric="device".  An optional key
+            # scoring="best" | "all" (evaluate()'s; absent = "best") is kept only when given
+            if val is not None and val.get("scoring", "best") not in ("best", "all"):
+                raise ValueError("val['scoring'] must be 'best' or 'all', not %r" % (val["scoring"],))
             self.val = None if val is None else dict(dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
                                                           max_dets=100, num_data=0, precision="bf16"), **val)
 
@@ -460,7 +463,8 @@ class SSDObjectDetectionModel:
             if raw:
                 samples = _RawList(samples)
         r = self.evaluate(samples, batch_size=val["batch_size"], score_thresh=val["score_thresh"], iou_thresh=val["iou_thresh"],
-                          max_dets=val["max_dets"], precision=val["precision"], metric="device")
+                          max_dets=val["max_dets"], precision=val["precision"], metric="device",
+                          scoring=val.get("scoring", "best"))
         self._scalars.write_values("val", step, {k: r[k] for k in ("mAP", "AP50", "AP75")})
         logger.info("validation at step %d: mAP %.4f AP50 %.4f AP75 %.4f", step, r["mAP"], r["AP50"], r["AP75"])
         return r
@@ -497,6 +501,20 @@ class SSDObjectDetectionModel:
         keep = ops.nms(score, cls, box, cand, iou_thresh, max_cand)
         return score, cls, box, keep
 
+    def detections(self, image, score_thresh=0.01, iou_thresh=0.45, max_cand=None, keep_top_k=200, precision="bf16"):
+        """image f32 [B,300,300,3] in [-1,1] -> ops.DetectPairs(n_det, score, cls, anchor, box, valid, n_cand): the compact
+        multi-label detection output (ops.detect_pairs; no reference counterpart).  Every (anchor, class) pair above
+        score_thresh is a candidate, so an anchor may be reported under several classes; per-class NMS over the best max_cand
+        pairs (None: the library maximum), then the best keep_top_k rows per image.  precision as detect()."""
+        return self._detections_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh, max_cand,
+                                         keep_top_k, precision)
+
+    def _detections_prepared(self, x, score_thresh, iou_thresh, max_cand=None, keep_top_k=200, precision="bf16"):
+        """detections() from the prepared network input bf16 [B,S,S,8]."""
+        loc, conf = self._engine.forward(x, precision)
+        return ops.detect_pairs(conf, loc, self._pset, score_thresh, iou_thresh, max_cand, keep_top_k,
+                                float(self.cfg.input_shape[0]))
+
     def _to_device(self, array):
         """Host array -> device through pinned memory, stream-ordered: no host synchronisation."""
         t = torch.from_numpy(np.ascontiguousarray(array))
@@ -525,12 +543,16 @@ class SSDObjectDetectionModel:
             box_d = ops.box_prep(box_d, self._to_device(gt_off), hw_d)
         return x, box_d, counts
 
-    def evaluate_into(self, acc, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, precision="bf16"):
+    def evaluate_into(self, acc, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, precision="bf16", scoring="best"):
         """The batch loop of evaluate(metric="device"): every batch of `samples` through the network, scoring/decoding, NMS
         and acc.add (utils.device_map.DeviceMapAccumulator) on the current stream.  Host arrays reach the device through
-        pinned memory; nothing in the loop reads the device or waits for it."""
+        pinned memory; nothing in the loop reads the device or waits for it.  scoring="all": the compact rows of
+        ops.detect_pairs (keep_top_k = acc.max_dets) go to acc.add as they are -- ssd_eval_match takes any row count, and its
+        (score desc, index asc) order is the rows' own."""
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
+        if scoring not in ("best", "all"):
+            raise ValueError("scoring must be 'best' or 'all', not %r" % (scoring,))
         size = float(self.cfg.input_shape[0])
         raw = bool(getattr(samples, "raw", False))
         buf = []
@@ -547,7 +569,11 @@ class SSDObjectDetectionModel:
                 img = self._to_device(np.stack([np.asarray(b[0], np.float32) for b in buf], 0))
                 x = ops.image_prep(((img - 0.5) * 2).contiguous(), normalize=False)
                 box_d = self._to_device(np.concatenate([np.asarray(b[2], np.float32).reshape(-1, 4) for b in buf], 0))
-            score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
+            if scoring == "all":
+                d = self._detections_prepared(x, score_thresh, iou_thresh, keep_top_k=acc.max_dets, precision=precision)
+                score, cls, box, keep = d.score, d.cls, d.box, d.valid
+            else:
+                score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
             acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off))
             buf.clear()
 
@@ -558,7 +584,7 @@ class SSDObjectDetectionModel:
         flush()
 
     def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False,
-                 precision="bf16", metric="host"):
+                 precision="bf16", metric="host", scoring="best"):
         """Evaluation pass (the reference fetches its val split at models/ssd_model.py:291 and drops it):
         samples = iterable of (image f32 [S,S,3] in [0,1], cls [n], box [n,4] relative cx,cy,w,h) as the loaders yield
         them, or a split of reader-contract samples (getattr(samples, "raw"): decoded uint8 images of any size, COCO top-left
@@ -570,14 +596,20 @@ class SSDObjectDetectionModel:
         Ground-truth boxes are float64(float32 relative box) * input size in both modes.
         Returns coco_map's dict (mAP = AP@[.5:.95], AP50, AP75, per_class); with return_detections also the per-image
         (score, cls, box_px) arrays: all kept detections with "host", the top-max_dets that were scored with "device".
-        precision: detect()'s ("bf16" or "mxfp8")."""
+        precision: detect()'s ("bf16" or "mxfp8").
+        scoring="best" (default): one label per anchor, as detect().  scoring="all": the SSD detection-output protocol, as
+        detections() -- every (anchor, class) pair above score_thresh, per-class NMS, the best max_dets rows per image
+        (keep_top_k = max_dets <= ops.detect_max_keep(); the top max_dets rows of a longer list are the same rows); "host"
+        then copies the compact rows once per batch.  Any other value raises ValueError."""
         from ..utils.metrics import coco_map
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
+        if scoring not in ("best", "all"):
+            raise ValueError("scoring must be 'best' or 'all', not %r" % (scoring,))
         if metric == "device":
             from ..utils.device_map import DeviceMapAccumulator
             acc = DeviceMapAccumulator(self.cfg.classes - 1, max_dets, self.device)
-            self.evaluate_into(acc, samples, batch_size, score_thresh, iou_thresh, precision)
+            self.evaluate_into(acc, samples, batch_size, score_thresh, iou_thresh, precision, scoring)
             result = acc.result()
             return (result, acc.detections()) if return_detections else result
         if metric != "host":
@@ -591,12 +623,25 @@ class SSDObjectDetectionModel:
                 return
             if raw:
                 x, box_d, counts = self._eval_batch_raw(buf)
-                score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
                 gboxes = np.split(box_d.cpu().numpy(), np.cumsum(counts)[:-1])
+            else:
+                gboxes = [b[2] for b in buf]
+            if scoring == "all":
+                if not raw:
+                    img = torch.from_numpy(np.stack([b[0] for b in buf], 0)).to(self.device)
+                    x = ops.image_prep(((img - 0.5) * 2).contiguous(), normalize=False)
+                d = self._detections_prepared(x, score_thresh, iou_thresh, keep_top_k=max_dets, precision=precision)
+                n, score, cls, box = d.n_det.cpu().numpy(), d.score.cpu().numpy(), d.cls.cpu().numpy(), d.box.cpu().numpy()
+                for i, (_, gcls, _) in enumerate(buf):
+                    dets.append((score[i, :n[i]].copy(), cls[i, :n[i]].copy(), box[i, :n[i]].copy()))
+                    gts.append((np.asarray(gcls), np.asarray(gboxes[i], np.float64) * size))
+                buf.clear()
+                return
+            if raw:
+                score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
             else:
                 img = torch.from_numpy(np.stack([b[0] for b in buf], 0)).to(self.device)
                 score, cls, box, keep = self.detect((img - 0.5) * 2, score_thresh, iou_thresh, precision=precision)
-                gboxes = [b[2] for b in buf]
             score, cls, box, keep = score.cpu().numpy(), cls.cpu().numpy(), box.cpu().numpy(), keep.cpu().numpy().astype(bool)
             for i, (_, gcls, _) in enumerate(buf):
                 k = keep[i]

@@ -1,5 +1,6 @@
 """Device-tensor wrappers over the C ABI (include/ssd_hip.h).  torch supplies device memory and the
 current HIP stream only; every computation runs in libssd_hip.so."""
+import collections
 import ctypes
 
 import numpy as np
@@ -351,6 +352,60 @@ def nms(score, cls, box, cand, iou_thresh=0.45, max_cand=400, want_count=False):
     _lib.check(L.ssd_nms(_ptr(score), _ptr(cls), _ptr(box), _ptr(cand), B, A, float(iou_thresh), int(max_cand),
                          _ptr(keep), _ptr(count), _stream()))
     return (keep, count) if want_count else keep
+
+
+def class_scores(conf):
+    """ssd_class_scores: the float32 softmax probability of every foreground class, prob f32 [B,A,C-1] -- bit for bit the
+    scores detect_pairs reports for the same (anchor, class)."""
+    L = _lib.lib()
+    B, A, C = conf.shape
+    assert conf.dtype in (torch.float32, torch.bfloat16) and conf.is_cuda and conf.is_contiguous()
+    prob = torch.empty((B, A, max(C - 1, 0)), dtype=torch.float32, device=conf.device)
+    _lib.check(L.ssd_class_scores(_ptr(conf), 0 if conf.dtype == torch.float32 else 1, B, A, C, _ptr(prob), _stream()))
+    return prob
+
+
+def detect_max_candidates():
+    return int(_lib.lib().ssd_detect_max_candidates())
+
+
+def detect_max_keep():
+    return int(_lib.lib().ssd_detect_max_keep())
+
+
+DetectPairs = collections.namedtuple("DetectPairs", "n_det score cls anchor box valid n_cand")
+_detect_ws = MatchWorkspace()
+
+
+def detect_pairs(conf, loc, pset, score_thresh=0.01, iou_thresh=0.45, max_cand=None, keep_top_k=200, in_size=300.0, ws=None):
+    """ssd_detect_pairs: the multi-label detection output (build-defined; the reference has none).  Every (anchor, class) pair
+    with softmax probability > score_thresh is a candidate (no background test); the first max_cand (None: the library
+    maximum) by (score desc, anchor asc, class asc) go through per-class greedy NMS; the kept pairs come out in that order,
+    cut to keep_top_k = K rows per image.  Returns DetectPairs(n_det i32 [B], score f32 [B,K], cls i32 [B,K], anchor i32 [B,K],
+    box f32 [B,K,4] pixels, valid u8 [B,K], n_cand i32 [B]); rows at or beyond n_det hold score 0, class -1, anchor -1,
+    box 0, valid 0.  Raises ValueError for max_cand / keep_top_k out of range."""
+    L = _lib.lib()
+    B, A, C = conf.shape
+    assert conf.dtype == loc.dtype and conf.dtype in (torch.float32, torch.bfloat16)
+    assert conf.is_cuda and conf.is_contiguous() and loc.is_contiguous() and A == pset.A
+    dev = conf.device
+    max_cand = detect_max_candidates() if max_cand is None else int(max_cand)
+    K = int(keep_top_k)
+    rows = max(K, 1)
+    n_cand = torch.empty((B,), dtype=torch.int32, device=dev)
+    n_det = torch.empty((B,), dtype=torch.int32, device=dev)
+    score = torch.empty((B, rows), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, rows), dtype=torch.int32, device=dev)
+    anchor = torch.empty((B, rows), dtype=torch.int32, device=dev)
+    box = torch.empty((B, rows, 4), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, rows), dtype=torch.uint8, device=dev)
+    nbytes = L.ssd_detect_pairs_workspace_bytes(B, A, C)
+    wbuf = (ws or _detect_ws).get(nbytes, dev)
+    _lib.check(L.ssd_detect_pairs(_ptr(conf), _ptr(loc), 0 if conf.dtype == torch.float32 else 1, _ptr(pset.priors), B, A, C,
+                                  float(score_thresh), float(in_size), float(iou_thresh), max_cand, K, _ptr(n_cand),
+                                  _ptr(n_det), _ptr(score), _ptr(cls), _ptr(anchor), _ptr(box), _ptr(valid), _ptr(wbuf),
+                                  wbuf.numel(), _stream()))
+    return DetectPairs(n_det, score, cls, anchor, box, valid, n_cand)
 
 
 def eval_max_dets():

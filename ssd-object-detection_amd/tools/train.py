@@ -57,11 +57,13 @@ VAL_DEFAULTS = dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45, 
 def val_from_config(config):
     """`model: eval: {enable, every, batch_size, score_thresh, iou_thresh, max_dets, num_data, precision}` (no reference
     counterpart: the reference drops its validation split) -> the `val` dict of TrainConfig, or None when the key is absent or
-    enable is false: the default run does not validate, as the reference does not."""
+    enable is false: the default run does not validate, as the reference does not.  The optional key `scoring` ("best": one
+    label per anchor, the default when absent; "all": the multi-label detection output, evaluate(scoring="all")) is in the
+    dict only when the config gives it."""
     section = (config.get("model") or {}).get("eval")
     if not section or not section.get("enable", False):
         return None
-    unknown = set(section) - set(VAL_DEFAULTS) - {"enable"}
+    unknown = set(section) - set(VAL_DEFAULTS) - {"enable", "scoring"}
     if unknown:
         raise ValueError("unknown model.eval keys: %s" % sorted(unknown))
     val = {k: type(d)(section.get(k, d)) for k, d in VAL_DEFAULTS.items()}
@@ -69,6 +71,10 @@ def val_from_config(config):
         raise ValueError("model.eval.precision must be 'bf16' or 'mxfp8', not %r" % (val["precision"],))
     if val["every"] < 1:
         raise ValueError("model.eval.every must be >= 1")
+    if "scoring" in section:
+        if section["scoring"] not in ("best", "all"):
+            raise ValueError("model.eval.scoring must be 'best' or 'all', not %r" % (section["scoring"],))
+        val["scoring"] = str(section["scoring"])
     return val
 
 

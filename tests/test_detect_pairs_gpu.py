@@ -1,0 +1,396 @@
+"""GPU: the multi-label detection output.  ssd_class_scores within float tolerance of the float64 softmax; every discrete
+result of ssd_detect_pairs bit for bit against tests/detect_pairs_oracle.pairs_reference run on the device's OWN scores
+(ops.class_scores) and decoded boxes; the model's detections() / evaluate(scoring="all") and validation with it in a run."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from oracle import ssd_oracle as O                                   # noqa: E402
+from tests import detect_pairs_oracle as R                           # noqa: E402
+from tests import strict                                             # noqa: E402
+
+A300, C81 = 8732, 81
+
+
+@pytest.fixture(scope="module")
+def ops():
+    import ssd_object_detection_amd.ops as ops_
+    return ops_
+
+
+@pytest.fixture(scope="module")
+def pset(ops):
+    return ops.build_priors()
+
+
+@pytest.fixture(scope="module")
+def small_pset(ops):
+    ps = ops.build_priors(**R.SMALL_GEOMETRY)
+    assert ps.A == 190
+    return ps
+
+
+class Case:
+    """One input on the device, with what every check of it shares computed once: the device's scores, the float64 decode,
+    the single-label call's boxes."""
+
+    def __init__(self, ops, pset, conf_np, loc_np, dtype=torch.float32):
+        self.ops, self.pset = ops, pset
+        self.conf = torch.from_numpy(conf_np).cuda().to(dtype)
+        self.loc = torch.from_numpy(loc_np).cuda().to(dtype)
+        self.B, self.A, self.C = self.conf.shape
+        self.prob = ops.class_scores(self.conf).cpu().numpy()
+        self.box64 = O.decode(self.loc.float().cpu().numpy(), pset.priors.cpu().numpy()[None], 300)
+
+    def check(self, thresh, iou=0.45, max_cand=None, K=200):
+        """detect_pairs against the reference; returns (device rows, reference rows) per image"""
+        ops = self.ops
+        mc = ops.detect_max_candidates() if max_cand is None else max_cand
+        d = ops.detect_pairs(self.conf, self.loc, self.pset, thresh, iou, max_cand, K)
+        assert d._fields == ("n_det", "score", "cls", "anchor", "box", "valid", "n_cand")
+        n_det, score, cls, anchor, box, valid, n_cand = [t.cpu().numpy() for t in d]
+        assert score.shape == (self.B, K) and box.shape == (self.B, K, 4) and valid.dtype == np.uint8
+        _, _, sbox, scand = [t.cpu().numpy() for t in ops.score_decode(self.conf, self.loc, self.pset, thresh)]
+        refs = []
+        for b in range(self.B):
+            n = int(n_det[b])
+            assert 0 <= n <= K
+            an, cl = anchor[b, :n], cls[b, :n]
+            assert (an >= 0).all() and (an < self.A).all() and (cl >= 0).all() and (cl < self.C - 1).all()
+            # the score bits are ssd_class_scores' for the same pair
+            assert np.array_equal(score[b, :n].view(np.uint32), self.prob[b, an, cl].view(np.uint32)), b
+            # the box: the float64 decode within its tolerance, the single-label call's bits where that call decoded the anchor
+            np.testing.assert_allclose(box[b, :n], self.box64[b, an], rtol=3e-7, atol=0)
+            both = scand[b, an].astype(bool)
+            assert np.array_equal(box[b, :n][both].view(np.uint32), sbox[b, an][both].view(np.uint32)), b
+            # the reference suppresses with the device's own boxes: the float64 decode rounded to float32 (the arithmetic the
+            # kernel restates), with the device's bits wherever the device reported the anchor
+            ref_box = self.box64[b].copy()
+            ref_box[scand[b].astype(bool)] = sbox[b][scand[b].astype(bool)]
+            ref_box[an] = box[b, :n]
+            r = R.pairs_reference(self.prob[b], ref_box, thresh, iou, mc, K)
+            print("thresh", thresh, "max_cand", mc, "K", K, "image", b, "n_cand", int(n_cand[b]), r["n_cand"], "n_det", n, r["n_det"])
+            assert int(n_cand[b]) == r["n_cand"], b
+            assert n == r["n_det"], b
+            assert np.array_equal(cls[b], r["cls"]) and np.array_equal(anchor[b], r["anchor"]), b
+            assert np.array_equal(valid[b], r["valid"]), b
+            assert np.array_equal(score[b].view(np.uint32), r["score"].view(np.uint32)), b
+            assert np.array_equal(box[b].view(np.uint32), r["box"].view(np.uint32)), b
+            refs.append(r)
+        return d, refs
+
+
+@pytest.fixture(scope="module")
+def typical(ops, pset):
+    conf, loc = R.synth_logits2(2, A300, C81, 320, 5)
+    return Case(ops, pset, conf, loc)
+
+
+@pytest.mark.parametrize("geometry", ["ssd300", "small"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_class_scores_vs_float64(ops, dtype, geometry):
+    B, A, C = (3, A300, C81) if geometry == "ssd300" else (3, 190, 6)
+    conf_np, _ = R.synth_logits2(B, A, C, 300 if A > 200 else 64, 1)
+    conf = torch.from_numpy(conf_np).cuda().to(dtype)
+    prob = ops.class_scores(conf)
+    assert prob.shape == (B, A, C - 1) and prob.dtype == torch.float32
+    want = np.exp(O._log_softmax(conf.float().cpu().numpy()))[..., :-1]
+    np.testing.assert_allclose(prob.cpu().numpy(), want, rtol=2e-6, atol=1e-9)
+
+
+@pytest.mark.parametrize("thresh", [0.3, 0.05, 0.01])
+def test_pipeline_bit_exact(ops, typical, thresh):
+    """0.3 stays under every cap, 0.05 crosses max_cand (exact cut from the list), 0.01 crosses the list (rescan)."""
+    mc, mk = ops.detect_max_candidates(), ops.detect_max_keep()
+    d, refs = typical.check(thresh, K=200)
+    n_cand = d.n_cand.cpu().numpy()
+    assert (d.n_det.cpu().numpy() == 200).all()                       # the keep_top_k cut is at work
+    if thresh == 0.3:
+        assert (n_cand > 150).all() and (n_cand < mc).all()
+        d, refs = typical.check(thresh, K=mk)
+        n_det = d.n_det.cpu().numpy()
+        assert (n_det < mk).all() and (n_det < n_cand).all()          # padding rows exist; something was suppressed
+        twice = [r["n_det"] - len(set(r["anchor"][:r["n_det"]].tolist())) for r in refs]
+        print("rows that repeat an anchor under another class:", twice)
+        assert max(twice) >= 1
+        typical.check(thresh, iou=0.1, K=mk)
+        typical.check(thresh, iou=0.9, K=mk)
+    elif thresh == 0.05:
+        assert (n_cand > mc).all() and (n_cand < 16384).all()
+    else:
+        assert (n_cand > 65536).all()
+
+
+@pytest.fixture(scope="module")
+def tied(ops, pset):
+    conf, loc = R.synth_logits2(2, A300, C81, 2400, 3)
+    return Case(ops, pset, R.add_score_ties(conf), loc)
+
+
+@pytest.mark.parametrize("max_cand", [50, 333, None])
+def test_cuts_with_ties(ops, tied, max_cand):
+    """More candidates than max_cand with exactly tied scores straddling the cut: the lowest (anchor, class) win; and the
+    keep_top_k cut at 1, 37 and the maximum."""
+    case = tied
+    for K in (1, 37, ops.detect_max_keep()):
+        d, _ = case.check(0.3, max_cand=max_cand, K=K)
+    n_cand = d.n_cand.cpu().numpy()
+    assert (n_cand > 1100).all()
+    p = case.prob[0][case.prob[0] > np.float32(0.3)]
+    assert np.unique(p).size < p.size - 100                            # the ties are there
+
+
+def test_overflow_rescan_beside_an_ordinary_image(ops, pset):
+    """score_thresh = 0: all 698 560 pairs of an image are candidates, far more than the list holds -- the cut comes from a
+    rescan of the image's logits.  Image 0 random, image 1 with a stronger background (few pairs above 0.012), image 2
+    all-zero logits: every score equal (1/81), the order is (anchor, class) alone."""
+    conf, loc = R.synth_logits2(3, A300, C81, 320, 8)
+    conf[1, :, C81 - 1] += 4.0
+    conf[2] = 0.0
+    case = Case(ops, pset, conf, loc)
+    F = C81 - 1
+    d, refs = case.check(0.0, K=200)
+    assert d.n_cand.cpu().numpy().tolist() == [A300 * F] * 3
+    d, refs = case.check(0.0, K=ops.detect_max_keep())
+    mc = ops.detect_max_candidates()
+    assert refs[2]["anchor"][:refs[2]["n_det"]].max() < -(-mc // F) and refs[2]["n_det"] > 0
+    # one launch, both paths: at 0.012 images 0 and 2 overflow the list (every probability of image 2 is 1/81), image 1 stays
+    # far below its 16384 entries
+    d, refs = case.check(0.012, K=200)
+    n_cand = d.n_cand.cpu().numpy()
+    assert n_cand[2] == A300 * F and n_cand[0] > 65536 and 0 < n_cand[1] < 8192
+
+
+def test_empty_image_and_guarded_outputs(ops, pset):
+    """An image without any candidate gives n_det = 0 and padding rows only; and with the outputs, the workspace and the guard
+    bands around every tensor poisoned twice, every output element is written, nothing else is, no input changes."""
+    from ssd_object_detection_amd import _lib
+    conf, loc = R.synth_logits2(3, A300, C81, 600, 4, per_anchor=1)
+    conf[2] = 0.0
+    conf[2, :, C81 - 1] = 6.0
+    case = Case(ops, pset, conf, loc)
+    K = 64
+    d, refs = case.check(0.3, K=K)
+    assert int(d.n_det[2]) == 0 and int(d.n_cand[2]) == 0 and int(d.valid[2].sum()) == 0
+    assert int(d.n_det[0]) > 0
+    B, A, C = 3, A300, C81
+    need = _lib.lib().ssd_detect_pairs_workspace_bytes(B, A, C)
+    shapes = [((B,), torch.int32), ((B,), torch.int32), ((B, K), torch.float32), ((B, K), torch.int32), ((B, K), torch.int32),
+              ((B, K, 4), torch.float32), ((B, K), torch.uint8)]
+    arena = strict.Arena("cuda", strict.Arena.bytes_for(case.conf.numel() * 4, case.loc.numel() * 4, A * 32, need,
+                                                        *[int(np.prod(s)) * 4 for s, _ in shapes]))
+    a_conf, a_loc, a_pri = arena.put(case.conf, "conf"), arena.put(case.loc, "loc"), arena.put(pset.priors, "priors")
+    outs = [arena.out(s, t, n) for (s, t), n in zip(shapes, ("n_cand", "n_det", "score", "cls", "anchor", "box", "valid"))]
+    ws = arena.workspace().get(need, a_conf.device)
+    want = [d.n_cand, d.n_det, d.score, d.cls, d.anchor, d.box, d.valid]
+    L = _lib.lib()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())                          # noqa: E731
+
+    def call():
+        _lib.check(L.ssd_detect_pairs(P(a_conf), P(a_loc), 0, P(a_pri), B, A, C, 0.3, 300.0, 0.45, ops.detect_max_candidates(),
+                                      K, *[P(t) for t in outs], P(ws), need,
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+    arena.run(call, list(zip(outs, want)))
+
+
+@pytest.mark.parametrize("thresh", [0.3, 0.05, 0.01])
+def test_candidate_set_vs_float64(typical, thresh):
+    """Away from the threshold the candidate set is the float64 softmax's: pairs within 1e-6 of the threshold are left out, and
+    they are at most 0.1 % of the pairs."""
+    p64 = np.exp(O._log_softmax(typical.conf.cpu().numpy()))[..., :-1]
+    border = np.abs(p64 - thresh) < 1e-6
+    print("thresh", thresh, "border fraction", border.mean())
+    assert border.mean() <= 1e-3
+    assert np.array_equal((typical.prob > np.float32(thresh))[~border], (p64 > thresh)[~border])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_small_geometry_runtime_class_count(ops, small_pset, dtype):
+    """A = 190 (one full block of rows and tails), C = 6 (the run-time class count), B = 3: the pipeline and the cuts."""
+    conf, loc = R.synth_logits2(3, 190, 6, 64, 7)
+    case = Case(ops, small_pset, R.add_score_ties(conf, 2, 60, 2), loc, dtype)
+    mk = ops.detect_max_keep()
+    n_dup = 0
+    for thresh in (0.3, 0.05, 0.01):
+        d, refs = case.check(thresh, K=200)
+        n_dup += sum(r["n_det"] - len(set(r["anchor"][:r["n_det"]].tolist())) for r in refs)
+    assert n_dup > 0
+    assert (d.n_cand.cpu().numpy() > 333).all()
+    for max_cand in (50, 333, None):
+        for K in (1, 37, mk):
+            case.check(0.01, max_cand=max_cand, K=K)
+    case.check(0.0, K=mk)                                             # all 950 pairs of an image
+
+
+def test_argument_checks(ops, pset):
+    conf = torch.zeros((1, A300, C81), device="cuda")
+    loc = torch.zeros((1, A300, 4), device="cuda")
+    for kw in (dict(max_cand=0), dict(max_cand=ops.detect_max_candidates() + 1), dict(keep_top_k=0),
+               dict(keep_top_k=ops.detect_max_keep() + 1)):
+        with pytest.raises(ValueError):
+            ops.detect_pairs(conf, loc, pset, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- model level
+def twin_best_class(model):
+    """The spread biases alone put whole (prior shape, class) planes at the top of an image's list, each anchor under ONE class
+    (measured: no anchor twice among the best 1024 rows at any threshold, since only the best detect_max_candidates() pairs
+    take part).  So that the multi-label output is multi-label here, every prior shape's best class gets a twin: the next
+    class index, 0.25 below it in bias."""
+    eng = model.get_engine()
+    for lvl, (wt, bt) in enumerate(eng.head_params):
+        n = eng.num_priors[lvl]
+        cb = eng.param[bt.offset + n * 4:bt.offset + bt.numel].reshape(n, 81).clone()
+        rows = torch.arange(n, device=cb.device)
+        top = cb[:, :80].argmax(1)
+        cb[rows, (top + 1) % 80] = cb[rows, top] - 0.25
+        eng.param[bt.offset + n * 4:bt.offset + bt.numel] = cb.reshape(-1)
+
+
+def test_model_evaluate_scoring_all(tmp_path, ops):
+    from tests.test_eval_device_gpu import assert_same_result, spread_model
+    from ssd_object_detection_amd.data_loaders import SSDDataLoader
+    from ssd_object_detection_amd.utils.device_map import DeviceMapAccumulator
+    from ssd_object_detection_amd.utils.metrics import coco_map
+    _, val = SSDDataLoader("unused", dataset="synthetic", shuffle=False, mini_batch=70).get_dataset()
+    samples = list(val)
+    assert len(samples) == 7
+    model = spread_model(tmp_path)
+    twin_best_class(model)
+    T = 0.05
+
+    # default arguments: scoring="best" is what omitting the argument gives, in both metric modes
+    base, bdets = model.evaluate(samples, batch_size=4, score_thresh=0.2, return_detections=True)
+    best, sdets = model.evaluate(samples, batch_size=4, score_thresh=0.2, return_detections=True, scoring="best")
+    assert best == base
+    for x, y in zip(bdets, sdets):
+        assert all(np.array_equal(p, q) for p, q in zip(x, y))
+    assert model.evaluate(samples, batch_size=4, score_thresh=0.2, metric="device", scoring="best") == \
+        model.evaluate(samples, batch_size=4, score_thresh=0.2, metric="device")
+
+    for max_dets in (100, 20):
+        host, hdets = model.evaluate(samples, batch_size=4, score_thresh=T, max_dets=max_dets, return_detections=True,
+                                     scoring="all")
+        dev, ddets = model.evaluate(samples, batch_size=4, score_thresh=T, max_dets=max_dets, return_detections=True,
+                                    metric="device", scoring="all")
+        assert_same_result(dev, host)
+        assert len(hdets) == len(ddets) == 7
+        for x, y in zip(hdets, ddets):
+            assert all(np.array_equal(p, q) for p, q in zip(x, y))
+        assert max(len(x[0]) for x in hdets) == max_dets
+
+    # the reference on the model's own logits (the batches evaluate() forms: 4 + 3 images)
+    size = 300.0
+    pri = model._pset.priors.cpu().numpy()
+    ref_dets, gts, dup = [], [], 0
+    for lo in (0, 4):
+        chunk = samples[lo:lo + 4]
+        img = torch.from_numpy(np.stack([s[0] for s in chunk], 0)).to(model.device)
+        x = ops.image_prep(((img - 0.5) * 2).contiguous(), normalize=False)
+        loc, conf = model._engine.forward(x, "bf16")
+        prob = ops.class_scores(conf).cpu().numpy()
+        box = O.decode(loc.float().cpu().numpy(), pri[None], 300)
+        d = ops.detect_pairs(conf, loc, model._pset, T, 0.45, None, 100)
+        for i, s in enumerate(chunk):
+            n = int(d.n_det[i])
+            an = d.anchor[i, :n].cpu().numpy()
+            ref_box = box[i].copy()
+            ref_box[an] = d.box[i, :n].cpu().numpy()
+            r = R.pairs_reference(prob[i], ref_box, T, 0.45, ops.detect_max_candidates(), 100)
+            k = r["n_det"]
+            dup += k - len(set(r["anchor"][:k].tolist()))
+            ref_dets.append((r["score"][:k], r["cls"][:k], r["box"][:k]))
+            gts.append((np.asarray(s[1]), np.asarray(s[2], np.float64) * size))
+    host, hdets = model.evaluate(samples, batch_size=4, score_thresh=T, return_detections=True, scoring="all")
+    for x, y in zip(hdets, ref_dets):
+        assert all(np.array_equal(p, q) for p, q in zip(x, y))
+    assert_same_result(coco_map(ref_dets, gts, max_dets=100), host)
+    # the multi-label output is multi-label here: some anchor is reported under two classes
+    img = torch.from_numpy(np.stack([s[0] for s in samples[:4]], 0)).to(model.device)
+    d = model.detections((img - 0.5) * 2, score_thresh=T, keep_top_k=ops.detect_max_keep())
+    wide = 0
+    for i in range(4):
+        an = d.anchor[i, :int(d.n_det[i])].cpu().numpy().tolist()
+        wide += len(an) - len(set(an))
+    print("rows that repeat an anchor under another class: top 100", dup, "top", ops.detect_max_keep(), wide)
+    assert wide >= 1
+
+    # ground truth that the detections hit: five of every image's own detections
+    hit = []
+    for (img, _, _), (s, c, b) in zip(samples, hdets):
+        pick = np.arange(0, len(s), max(1, len(s) // 5))[:5]
+        hit.append((img, c[pick].astype(np.float32), (b[pick] / np.float32(300.0)).astype(np.float32)))
+    host = model.evaluate(hit, batch_size=4, score_thresh=T, scoring="all")
+    dev = model.evaluate(hit, batch_size=4, score_thresh=T, metric="device", scoring="all")
+    print("host", host["mAP"], host["AP50"], "device", dev["mAP"], dev["AP50"])
+    assert host["AP50"] > 0.0
+    assert_same_result(dev, host)
+
+    # nothing in the device loop synchronises
+    acc = DeviceMapAccumulator(80, 100, model.device)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        model.evaluate_into(acc, hit, batch_size=4, score_thresh=T, scoring="all")
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert_same_result(acc.result(), host)
+
+    # detections(): the public compact output
+    first = torch.from_numpy(np.stack([s[0] for s in samples[:4]], 0)).to(model.device)
+    d = model.detections((first - 0.5) * 2, score_thresh=T, keep_top_k=100)
+    for i in range(4):
+        n = int(d.n_det[i])
+        assert np.array_equal(d.score[i, :n].cpu().numpy(), hdets[i][0]) and np.array_equal(d.cls[i, :n].cpu().numpy(), hdets[i][1])
+    with pytest.raises(ValueError):
+        model.evaluate(samples, scoring="every")
+    with pytest.raises(ValueError):
+        model.evaluate(samples, scoring="all", max_dets=ops.detect_max_keep() + 1)
+
+
+def test_validation_with_scoring_all_inside_a_training_run(tmp_path, monkeypatch):
+    from tests.test_eval_device_gpu import real_model, spread_biases
+    from ssd_object_detection_amd.data_loaders import SSDDataLoader
+    from ssd_object_detection_amd.models import SSDObjectDetectionModel
+    from ssd_object_detection_amd.tools import train as T
+    from ssd_object_detection_amd.utils.scalar_log import read_scalars
+
+    real_init = SSDObjectDetectionModel.__init__
+
+    def init(self, *a, **k):
+        real_init(self, *a, **k)
+        spread_biases(self)
+
+    monkeypatch.setattr(SSDObjectDetectionModel, "__init__", init)
+    cfg = T.load_config(os.path.join(os.path.dirname(T.__file__), "..", "config", "default.yml"))
+    cfg["data"]["mini_batch"]["num_data"] = 40
+    cfg["data"]["shuffle"] = False
+    cfg["model"]["log_dir"] = str(tmp_path / "val")
+    cfg["model"]["train"]["batch_size"] = 4
+    cfg["model"]["train"]["epoch"] = 1
+    cfg["model"]["train"]["lr"]["initial"] = 1e-5
+    cfg["model"]["split_train"]["enable"] = False
+    cfg["model"]["warmup"]["enable"] = False
+    cfg["model"]["log_interval"] = 100
+    cfg["model"]["eval"] = dict(enable=True, batch_size=4, score_thresh=0.05, num_data=8, scoring="all")
+    assert T.val_from_config(cfg)["scoring"] == "all"
+    run = T.train(cfg)
+    got = read_scalars(os.path.join(run.get_log_dir(), "scalars.jsonl"))
+    assert {"val/mAP", "val/AP50", "val/AP75"} <= set(got)
+    _, val = SSDDataLoader("unused", dataset="synthetic", shuffle=False, mini_batch=40).get_dataset()
+    samples = list(val)[:8]
+    m = real_model(real_init, tmp_path / "ck")
+    m.load(os.path.join(run.get_log_dir(), "model_weight", "model_weight_epoch_0.pt"))
+    want = m.evaluate(samples, batch_size=4, score_thresh=0.05, scoring="all")
+    other = m.evaluate(samples, batch_size=4, score_thresh=0.05)
+    for tag, key in (("val/mAP", "mAP"), ("val/AP50", "AP50"), ("val/AP75", "AP75")):
+        assert len(got[tag]) == 1
+        step, value = got[tag][0]
+        assert step == 10
+        assert abs(value - want[key]) <= 1e-12, (tag, value, want[key], other[key])

@@ -2,7 +2,8 @@
 
 512 samples, batch 64, score threshold 0.05, head biases spread as in tests/test_eval_device_gpu.py (conf: background +2,
 classes N(0, 1.5)) so that scoring and NMS have work; one warm-up pass, then the median of `--passes` passes per metric mode,
-the modes alternated.  A tree without the device metric (no `metric` argument) is timed in its only mode.
+the modes alternated.  A tree without the device metric (no `metric` argument) is timed in its only mode; one with the
+multi-label detection output (a `scoring` argument) also in "host+all" and "device+all" (evaluate(scoring="all")).
 Kernel times: a run of its own under `rocprofv3 --kernel-trace --stats -- python tools_dev/time_eval.py --passes 1`.
 Usage: python tools_dev/time_eval.py [--samples 512] [--batch 64] [--passes 5] [--out FILE.json]"""
 import argparse
@@ -43,9 +44,13 @@ def main():
         eng.param[bt.offset:bt.offset + bt.numel] = b.cuda()
     samples = [(synth_image((1 << 20) + i),) + synth_gt((1 << 20) + i) for i in range(args.samples)]
     modes = ["host", "device"] if "metric" in inspect.signature(model.evaluate).parameters else [None]
+    if "scoring" in inspect.signature(model.evaluate).parameters:
+        modes += ["host+all", "device+all"]
 
     def run(mode):
-        kw = {} if mode is None else {"metric": mode}
+        kw = {} if mode is None else {"metric": mode.split("+")[0]}
+        if mode is not None and mode.endswith("+all"):
+            kw["scoring"] = "all"
         t0 = time.perf_counter()
         r = model.evaluate(samples, batch_size=args.batch, score_thresh=0.05, **kw)     # ends in a device-to-host read
         torch.cuda.synchronize()
