@@ -139,10 +139,14 @@ int ssd_iou_n(const float* b1, const double* b2, int n, double* out, void* strea
  *             their sum, P, N (= number of mined negatives, ties included :372), tau, status
  *             (0 ok; 1 = P==0 or 3P > B*A, where TF would raise; 2 = tau==0, where the assert at :375 fires;
  *             3 = a logit row or a positive's offsets were NaN / Inf: a diverged run, reported first)
- *   dconf     [B*A*C], dloc [B*A*4]: gradients, same dtype as conf/loc
+ *   dconf     [B*A*C], dloc [B*A*4]: gradients, same dtype as conf/loc; every element is written.  With status 1 both are
+ *             exact zeros (and the compact form below has no rows: every count is 0, every row_of_pixel is -1)
+ *   C         2 <= C <= SSD_LOSS_MAX_CLASSES: a block of 128 logit rows (512 * C bytes as f32) and the 8 KB level-1 histogram
+ *             of the mining threshold share the 160 KB of LDS of a workgroup; SSD_ERR_UNSUPPORTED (nothing launched) beyond
  * Hard-negative mining is global over the B images handed in (one micro-batch), as in the reference.
  * fp32 losses agree with a float64 evaluation to <= 1e-4 relative.
  * ---------------------------------------------------------------------------------------- */
+#define SSD_LOSS_MAX_CLASSES 303
 size_t ssd_loss_workspace_bytes(int B, int A, int C);
 int ssd_loss_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls,
                      const float* gt_loc, const uint8_t* gt_mask, int B, int A, int C, float grad_scale,

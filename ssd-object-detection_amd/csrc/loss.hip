@@ -18,11 +18,12 @@
 // fixed-order partial sums only).
 #include "common.h"
 #include <hip/hip_bf16.h>
+#include "conv_common.h"
 #include "rowblock.h"
 
 namespace {
 
-constexpr int WG = 256;
+static_assert(WG == 256, "two threads per anchor row (WG: conv_common.h)");
 constexpr int ROWS = 128;                    // anchor rows per workgroup (2 threads per row)
 constexpr int HB1 = 2048, HB2 = 2048, HB3 = 1024;   // radix digits: 11 + 11 + 10 bits
 // Level-1 keys of a real batch sit in one or two bins, and every workgroup's flush would hit the
@@ -33,6 +34,14 @@ constexpr int NREP = 4;                      // (16 until round 4: k_loss_hist<2
                                              //  put <= 192 same-address flushes on a bin over the ~30 us of k_loss_rows)
 constexpr int H1STRIDE = HB1 + 16;           // [HB1] bins, then [HB1] = P, padded
 constexpr int MAX_PERSIST = 768;             // 3 workgroups per CU
+// LDS of a workgroup: the logit / gradient block [ROWS][C] f32 (dynamic) next to k_loss_rows' static level-1 histogram, its
+// reduction slots and its positive counter.  Both must fit the 160 KB of a gfx950 workgroup: C <= SSD_LOSS_MAX_CLASSES.
+constexpr size_t LDS_LIMIT = 160 * 1024;
+constexpr size_t ROWS_STATIC_LDS = HB1 * sizeof(int) + 64;       // s_hist + s_red[4] + s_np, padded
+constexpr size_t MAX_DYN_LDS = (LDS_LIMIT - ROWS_STATIC_LDS) / 16 * 16;
+constexpr size_t loss_lds_bytes(int C) { return ((size_t)ROWS * C * sizeof(float) + 15) / 16 * 16; }
+constexpr bool loss_lds_fits(int C) { return loss_lds_bytes(C) <= MAX_DYN_LDS; }
+static_assert(loss_lds_fits(SSD_LOSS_MAX_CLASSES) && !loss_lds_fits(SSD_LOSS_MAX_CLASSES + 1), "ssd_hip.h states the bound");
 
 struct LossWs {                              // layout of the caller's workspace
     float* ce_bg;                            // [n] masked background CE (0 at positives)
@@ -635,12 +644,20 @@ __global__ __launch_bounds__(WG) void k_loss_grad_rows(const __hip_bfloat16* __r
     }
 }
 
+// More than 64 KB of dynamic LDS (C > 128) is registered once per device and kernel, for the largest block the bound admits.
+template <typename K>
+int register_lds(OnceLds& once, K kern, size_t lds) {
+    return lds <= 64 * 1024 ? 0 : ensure_lds(once, reinterpret_cast<const void*>(kern), (int)MAX_DYN_LDS);
+}
+
 // the launches both forms share: conf read once, exact radix select of tau
 template <typename T>
-void launch_loss_select(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
-                        size_t n, int C, LossWs w, hipStream_t s, size_t lds, bool select_launch = true) {
+int launch_loss_select(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
+                       size_t n, int C, LossWs w, hipStream_t s, size_t lds, bool select_launch = true) {
     const size_t nblk = (n + ROWS - 1) / ROWS;
     const unsigned pgrid = (unsigned)min((size_t)MAX_PERSIST, nblk);
+    static OnceLds once81, once0;
+    if (C == 81 ? register_lds(once81, k_loss_rows<T, 81>, lds) : register_lds(once0, k_loss_rows<T, 0>, lds)) return SSD_ERR_LAUNCH;
     if (C == 81)
         hipLaunchKernelGGL((k_loss_rows<T, 81>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc, mask, n, C, w);
     else
@@ -649,15 +666,18 @@ void launch_loss_select(const void* conf, const void* loc, const int32_t* cls, c
     hipLaunchKernelGGL(k_loss_hist<2>, dim3(hgrid), dim3(WG), 0, s, n, w);
     hipLaunchKernelGGL(k_loss_hist<3>, dim3(hgrid), dim3(WG), 0, s, n, w);
     if (select_launch) hipLaunchKernelGGL(k_loss_select, dim3(1), dim3(WG), 0, s, w);
+    return 0;
 }
 
 template <typename T>
 int launch_loss(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
                 size_t n, int C, float* out, void* dconf, void* dloc, float grad_scale, LossWs w, hipStream_t s) {
     const size_t nblk = (n + ROWS - 1) / ROWS;
-    const size_t lds = ((size_t)ROWS * C * sizeof(float) + 15) / 16 * 16;
+    const size_t lds = loss_lds_bytes(C);
+    static OnceLds once_grad;
+    if (register_lds(once_grad, k_loss_grad<T>, lds)) return SSD_ERR_LAUNCH;
     if (hipMemsetAsync(w.hist1, 0, w.zero_bytes, s) != hipSuccess) return SSD_ERR_LAUNCH;
-    launch_loss_select<T>(conf, loc, cls, gloc, mask, n, C, w, s, lds);
+    if (launch_loss_select<T>(conf, loc, cls, gloc, mask, n, C, w, s, lds)) return SSD_ERR_LAUNCH;
     hipLaunchKernelGGL(k_loss_grad<T>, dim3((unsigned)nblk), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc,
                        mask, n, C, grad_scale, (T*)dconf, (T*)dloc, w);
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(WG), 0, s, nblk, w, out);
@@ -685,7 +705,7 @@ int ssd_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const i
     if (B <= 0 || A <= 0 || C < 2 || !hg) return SSD_ERR_VALUE;
     if (!conf || !loc || !gt_cls || !gt_loc || !gt_mask || !out8 || !hg->count) return SSD_ERR_VALUE;
     if (dtype != SSD_BF16) return SSD_ERR_UNSUPPORTED;
-    if ((size_t)ROWS * C * sizeof(float) > 144 * 1024) return SSD_ERR_UNSUPPORTED;
+    if (!loss_lds_fits(C)) return SSD_ERR_UNSUPPORTED;
     if (hg->levels <= 0 || hg->levels > SSD_MAX_LEVELS) return SSD_ERR_VALUE;
     HeadGradsDev h;
     h.levels = hg->levels; h.A = A; h.B = B;
@@ -712,11 +732,11 @@ int ssd_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const i
     hipStream_t s = (hipStream_t)stream;
     typedef __hip_bfloat16 T;
     const size_t nblk = (n + ROWS - 1) / ROWS;
-    const size_t lds = ((size_t)ROWS * C * sizeof(float) + 15) / 16 * 16;
+    const size_t lds = loss_lds_bytes(C);
     // ws_clean: the caller states that the histogram words of THIS workspace layout are zero -- true after a completed call of
     // this function with the same B, A (its last launch re-zeroes them) -- and the memset node is skipped
     if (!ws_clean && hipMemsetAsync(w.hist1, 0, w.zero_bytes, s) != hipSuccess) return SSD_ERR_LAUNCH;
-    launch_loss_select<T>(conf, loc, gt_cls, gt_loc, gt_mask, n, C, w, s, lds, false);
+    if (launch_loss_select<T>(conf, loc, gt_cls, gt_loc, gt_mask, n, C, w, s, lds, false)) return SSD_ERR_LAUNCH;
     hipLaunchKernelGGL(k_hg_count, dim3(B, hg->levels), dim3(WG), 0, s, gt_mask, w, h, part_neg_il, nblk);
     hipLaunchKernelGGL(k_hg_assign, dim3(B, hg->levels), dim3(WG), 0, s, gt_mask, w, h, nblk, (const double*)part_neg_il, out8);
     hipLaunchKernelGGL(k_loss_grad_rows, dim3((unsigned)nblk), dim3(WG), 0, s, (const T*)conf, (const T*)loc, gt_cls, gt_loc,
@@ -730,7 +750,7 @@ int ssd_loss_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t
     if (B <= 0 || A <= 0 || C < 2) return SSD_ERR_VALUE;
     if (!conf || !loc || !gt_cls || !gt_loc || !gt_mask || !out8 || !dconf || !dloc) return SSD_ERR_VALUE;
     if (dtype != SSD_F32 && dtype != SSD_BF16) return SSD_ERR_VALUE;
-    if ((size_t)ROWS * C * sizeof(float) > 144 * 1024) return SSD_ERR_UNSUPPORTED;
+    if (!loss_lds_fits(C)) return SSD_ERR_UNSUPPORTED;
     const size_t n = (size_t)B * A;
     if (!ws || ws_bytes < loss_ws_layout(n, nullptr, nullptr)) return SSD_ERR_WORKSPACE;
     LossWs w;

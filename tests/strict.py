@@ -681,3 +681,491 @@ EXTRAS = {
     "mxfp8 fwd_pool (1,7,7,128,128) same": lambda: mx_conv_case((1, 7, 7, 128, 128, 3, 1, "same")),
     "mxfp8 bwd_data (2,19,19,64,256,1)": lambda: mx_conv_case((2, 19, 19, 64, 256, 1, 1, "same")),
 }
+
+
+# ---- the SSD loss: exact logits ------------------------------------------------------------------------------------------------
+# Every row has one maximum m (a small integer) and every other logit is at most m - 1024, so exp(z - m) is exactly 0 in fp32 and
+# in float64, the row sum is exactly 1, its log exactly 0 and lse = m.  The background key m - z[C-1] and a positive's label CE
+# m - z[label] are then exact fp32 numbers that the case CHOOSES, the softmax is exactly one-hot, and every gradient entry is 0 or
+# +-grad_scale / P or +-grad_scale / N: oracle.ssd_oracle.ssd_loss (float64) returns values that convert to the output dtype
+# without rounding, and the mining threshold can be put on any bit pattern at or above 1024.
+FILL = (-2048.0, -4096.0, -8192.0, -1048576.0)                 # the logits that are neither the maximum nor chosen: <= m - 1024
+
+
+def f32_bits(bits):
+    return np.asarray(bits, dtype=np.uint32).view(np.float32)
+
+
+def _low_bit_exponent(v):
+    """exponent e of the lowest set bit 2^e of every (positive, normal) fp32 value"""
+    b = np.asarray(v, dtype=np.float32).view(np.uint32).astype(np.int64)
+    mant = (b & 0x7FFFFF) | 0x800000
+    tz = np.log2((mant & -mant).astype(np.float64)).astype(np.int64)
+    return ((b >> 23) & 0xFF) - 127 - 23 + tz
+
+
+def sums_exactly(values):
+    """a float64 sum of these non-negative fp32 values is exact in any order: all are multiples of a quantum q = 2^e and the total
+    is below 2^53 q, so no partial sum of any grouping rounds"""
+    v = np.asarray(values, dtype=np.float32).astype(np.float64)
+    v = v[v != 0]
+    if v.size == 0:
+        return True
+    assert (v > 0).all()
+    q = 2.0 ** int(_low_bit_exponent(v.astype(np.float32)).min())
+    import math
+    return math.fsum(v / q) < 2.0 ** 53
+
+
+def _holds(v32, dtype):
+    """the fp32 values survive the cast to `dtype`"""
+    if dtype == torch.float32:
+        return np.ones(v32.shape, dtype=bool)
+    return (np.ascontiguousarray(v32, dtype=np.float32).view(np.uint32) & 0xFFFF) == 0
+
+
+def scatter_keys(n, P, keys, seed):
+    """(mask bool[n], key f32[n]): P positives at seeded random places, `keys` (n - P of them) on the other rows in a seeded
+    random order, so that the selected rows fall into many blocks"""
+    keys = np.asarray(keys, dtype=np.float32)
+    assert keys.shape == (n - P,), (keys.shape, n, P)
+    rng = np.random.default_rng(seed)
+    mask = np.zeros(n, dtype=bool)
+    mask[rng.choice(n, P, replace=False)] = True
+    key = np.zeros(n, dtype=np.float32)
+    key[~mask] = rng.permutation(keys)
+    return mask, key
+
+
+def loss_case(B, A, C, mask, key, pos_ce=None, dtype=torch.float32, grad_scale=1.0, seed=0, design=None):
+    """An exact case of ssd_loss_fwd_bwd.  mask bool[B*A]: the positives; key f32[B*A]: the background CE of every other row, 0
+    (the background is the row's maximum) or >= 1024; pos_ce f32[B*A]: a positive's label CE, 0 (the label is the maximum: an
+    all-zero gradient row that is still selected) or >= 1024 (default: a seeded mix of 0, 1024, 1536 and 2048).
+    Returns the inputs (torch, CPU) and the expected out8 / dconf / dloc: oracle.ssd_oracle.ssd_loss on the same inputs, the
+    scalars cast to fp32 (out8[3] their fp32 sum in k_loss_final's order), the gradient's entries -- the oracle's signs -- scaled
+    by the fp32 quotients grad_scale / P and grad_scale / N and cast to `dtype`.  P == 0 or 3P > B*A: status 1, zero gradients."""
+    from oracle import ssd_oracle as O
+    n = B * A
+    rng = np.random.default_rng(1000 + seed)
+    mask = np.asarray(mask, dtype=bool).reshape(n)
+    key = np.where(mask, 0, np.asarray(key, dtype=np.float32).reshape(n)).astype(np.float32)
+    if pos_ce is None:
+        pos_ce = rng.choice(np.array([0.0, 1024.0, 1536.0, 2048.0], dtype=np.float32), n)
+    pos_ce = np.where(mask, np.asarray(pos_ce, dtype=np.float32).reshape(n), 0).astype(np.float32)
+    chosen = np.where(mask, pos_ce, key)                        # the one logit below the maximum that the case chooses: m - chosen
+    assert ((chosen == 0) | (chosen >= 1024)).all()
+    label = rng.integers(0, C - 1, n)                           # foreground classes 0 .. C-2
+    other = (label + 1 + rng.integers(0, C - 1, n)) % C         # any class but the label
+    fg = rng.integers(0, C - 1, n)
+    # the class that holds the maximum / the class that holds m - chosen
+    top = np.where(mask, np.where(pos_ce == 0, label, other), np.where(key == 0, C - 1, fg))
+    low = np.where(mask, label, C - 1)
+    m_pref = rng.choice(np.array([0.0, 4.0, -4.0, 0.0, 256.0] if dtype == torch.bfloat16 else [0.0, 4.0, -4.0]), n)
+    z64 = m_pref - chosen.astype(np.float64)
+    z32 = z64.astype(np.float32)
+    ok = (z32.astype(np.float64) == z64) & _holds(z32, dtype) & (m_pref - z32.astype(np.float64) == chosen)
+    m = np.where(ok | (chosen == 0), m_pref, 0.0)
+    conf = rng.choice(np.array(FILL, dtype=np.float32), (n, C))
+    rows = np.arange(n)
+    has_low = chosen != 0
+    conf[rows[has_low], low[has_low]] = (m - chosen.astype(np.float64))[has_low].astype(np.float32)
+    conf[rows, top] = m.astype(np.float32)
+    loc = rng.integers(-8, 9, (n, 4)).astype(np.float32) / 4
+    gt_loc = rng.integers(-8, 9, (n, 4)).astype(np.float32) / 4
+    gt_loc[~mask] = 12345.0                                     # never read
+    gt_loc[rows[mask][::3], 1] = loc[rows[mask][::3], 1]        # exact zeros of the difference: sign 0
+    gt_cls = np.where(mask, label, rng.integers(0, C, n)).astype(np.int32)
+    r = dict(B=B, A=A, C=C, dtype=dtype, grad_scale=float(grad_scale), design=design or {}, m=m, key=key, pos_ce=pos_ce,
+             conf=torch.from_numpy(conf).view(B, A, C).to(dtype), loc=torch.from_numpy(loc).view(B, A, 4).to(dtype),
+             gt_cls=torch.from_numpy(gt_cls).view(B, A), gt_loc=torch.from_numpy(gt_loc).view(B, A, 4),
+             gt_mask=torch.from_numpy(mask.astype(np.uint8)).view(B, A))
+    assert torch.equal(r["conf"].float(), torch.from_numpy(conf).view(B, A, C)), "a logit does not survive the cast"
+    P = int(mask.sum())
+    out8 = np.zeros(8, dtype=np.float32)
+    out8[4] = P
+    if P == 0 or 3 * P > n:
+        out8[7] = 1.0
+        r.update(status=1, P=P, N=0, selected=np.zeros(n, dtype=bool), ref=None,
+                 dconf=torch.zeros((B, A, C), dtype=dtype), dloc=torch.zeros((B, A, 4), dtype=dtype))
+    else:
+        ref = O.ssd_loss(gt_cls.reshape(B, A), gt_loc.reshape(B, A, 4), mask.reshape(B, A), loc.reshape(B, A, 4),
+                         conf.reshape(B, A, C), want_grad=True)
+        N = ref["num_neg"]
+        gs = np.float32(grad_scale)
+        inv_p, inv_n = gs / np.float32(P), gs / np.float32(N)
+        scale = np.where(mask, inv_p, inv_n).astype(np.float32).reshape(B, A, 1)
+        dconf = (np.sign(ref["dcls"]).astype(np.float32) * scale + np.float32(0)).astype(np.float32)
+        dloc = (np.sign(ref["dbox"]).astype(np.float32) * inv_p + np.float32(0)).astype(np.float32)
+        out8[0], out8[1], out8[2] = np.float32(ref["loc"]), np.float32(ref["pos"]), np.float32(ref["neg"])
+        out8[3] = (out8[0] + out8[1]) + out8[2]
+        out8[5], out8[6] = N, np.float32(ref["tau"])
+        r.update(status=0, P=P, N=N, ref=ref, selected=mask | ref["neg_mask"].reshape(n), inv_p=inv_p, inv_n=inv_n,
+                 dconf=torch.from_numpy(dconf).to(dtype), dloc=torch.from_numpy(dloc).to(dtype))
+    r["out8"] = torch.from_numpy(out8)
+    return r
+
+
+def check_loss_regime(r):
+    """The conditions under which the expected outputs of loss_case are exact, on the inputs and the float64 reference."""
+    B, A, C, dtype = r["B"], r["A"], r["C"], r["dtype"]
+    n = B * A
+    z = r["conf"].float().numpy().reshape(n, C)
+    mask = r["gt_mask"].numpy().reshape(n).astype(bool)
+    m = z.max(-1)
+    assert np.array_equal(m, r["m"].astype(np.float32)) and ((z == m[:, None]).sum(-1) == 1).all(), "one maximum per row"
+    assert (np.exp((z - m[:, None]).astype(np.float32)).astype(np.float32).sum(-1, dtype=np.float32) == 1).all()
+    assert (np.exp(z.astype(np.float64) - m[:, None]).sum(-1) == 1).all()
+    # the kernel's fp32 formulas restated: the keys and the label CEs are the chosen numbers, bit for bit
+    key32 = np.where(mask, np.float32(0), (m - z[:, C - 1]) + np.log(np.float32(1)))
+    assert np.array_equal(key32.view(np.uint32), r["key"].view(np.uint32))
+    lab = r["gt_cls"].numpy().reshape(n)
+    ce32 = (m - z[np.arange(n), lab])[mask]
+    assert np.array_equal(ce32, r["pos_ce"][mask])
+    assert len(set(np.unique(m[~mask]))) > 1 or n < 8 or dtype == torch.bfloat16, "the maximum varies between rows"
+    loc, gl = r["loc"].float().numpy().reshape(n, 4), r["gt_loc"].numpy().reshape(n, 4)
+    assert np.array_equal(loc * 4, np.round(loc * 4)) and np.array_equal(gl[mask] * 4, np.round(gl[mask] * 4))
+    if r["status"] != 0:
+        return
+    ref, P, N, gs = r["ref"], r["P"], r["N"], r["grad_scale"]
+    neg = ref["neg_mask"].reshape(n)
+    assert not (neg & mask).any() and ref["tau"] >= 1024 and int(neg.sum()) == N
+    tau32 = np.float32(ref["tau"])
+    assert float(tau32) == ref["tau"]
+    # rank and ties as designed; no key lies within the tie by accident
+    keys = r["key"][~mask]
+    above, tie = int((keys > tau32).sum()), int((keys == tau32).sum())
+    assert above < 3 * P <= above + tie and N == above + tie
+    d = r["design"]
+    for name, got in (("N", N), ("tie", tie), ("rank_in_tie", 3 * P - above), ("tau_bits", int(tau32.view(np.uint32)))):
+        if name in d:
+            assert d[name] == got, (name, d[name], got)
+    # the three sums are exact in float64 whatever their order
+    assert sums_exactly(keys[keys >= tau32]) and sums_exactly(r["pos_ce"][mask]) and sums_exactly(np.abs(loc - gl)[mask].sum(-1))
+    # the gradient: the oracle's entries are 0 or +-1/P or +-1/N; where P, N and grad_scale are powers of two the scaled float64
+    # reference converts to the output dtype without rounding and equals the expected tensor
+    pow2 = all(v > 0 and float(np.log2(v)).is_integer() for v in (P, N, gs))
+    r["pow2"] = pow2
+    vals = np.unique(np.abs(ref["dcls"]))
+    assert set(vals) <= {0.0, 1.0 / P, 1.0 / N}
+    if pow2:
+        for name, key in (("dconf", "dcls"), ("dloc", "dbox")):
+            want = torch.from_numpy(ref[key] * gs)
+            assert torch.equal(want.to(dtype).double(), want), name
+            assert torch.equal(r[name].double(), want), name
+    for i, name in enumerate(("loc", "pos", "neg")):
+        assert np.isfinite(r["out8"][i].item())
+    assert np.isfinite(r["out8"][3].item())
+
+
+# (H, W, per_cell) per level
+GEOM8 = ((19, 19, 4), (7, 5, 6), (5, 7, 6), (3, 3, 6), (2, 3, 4), (2, 2, 4), (1, 2, 4), (1, 1, 4))
+GEOM7 = ((8, 8, 4), (4, 4, 6), (3, 4, 6), (2, 2, 6), (2, 1, 6), (1, 1, 4), (1, 1, 4))
+GEOM1 = ((6, 7, 4),)
+
+
+def anchors_of(geom):
+    return sum(h * w * n for h, w, n in geom)
+
+
+def heads_expected(r, geom, npad):
+    """The compact-row form of a loss_case by the header's contract, from the oracle's selection: per level count, pixel_of_row
+    (ascending flat pixel b*hw + pix), row_of_pixel (-1 where unselected) and the rows [per_cell*4 loc | per_cell*C conf | 0]"""
+    B, A, C = r["B"], r["A"], r["C"]
+    assert anchors_of(geom) == A and r["dtype"] == torch.bfloat16
+    sel = torch.from_numpy(r["selected"]).view(B, A)
+    out, off = [], 0
+    for (h, w, n), p in zip(geom, npad):
+        hw = h * w
+        assert p % 8 == 0 and p >= n * (4 + C)
+        pix = sel[:, off:off + hw * n].reshape(B * hw, n).any(-1)
+        por = pix.nonzero()[:, 0].to(torch.int32)
+        rop = torch.full((B * hw,), -1, dtype=torch.int32)
+        rop[por.long()] = torch.arange(por.numel(), dtype=torch.int32)
+        full = torch.zeros((B * hw, p), dtype=torch.bfloat16)
+        full[:, :n * 4] = r["dloc"][:, off:off + hw * n].reshape(B * hw, n * 4)
+        full[:, n * 4:n * (4 + C)] = r["dconf"][:, off:off + hw * n].reshape(B * hw, n * C)
+        rows = torch.zeros((B * hw, p), dtype=torch.bfloat16)
+        rows[:por.numel()] = full[por.long()]
+        assert not bool((full[~pix] != 0).any())                    # an unselected pixel carries no gradient
+        out.append(dict(hw=hw, H=h, W=w, n=n, npad=p, off=off, count=int(por.numel()), pixel_of_row=por, row_of_pixel=rop,
+                        rows=rows, dense=full.view(B, h, w, p)))
+        off += hw * n
+    return out
+
+
+# ---- the catalogue of exact loss cases ------------------------------------------------------------------------------------------
+def _fill_keys(count, seed, dtype=torch.float32):
+    """`count` keys that stay below every threshold of the catalogue (all thresholds are >= 1536): exact zeros (the background is
+    the maximum) and values of [1024, 1536) that differ in their low bits"""
+    rng = np.random.default_rng(77 + seed)
+    step = 8 if dtype == torch.bfloat16 else 1
+    lo = f32_bits(0x44800000 + step * 0x10000 * rng.integers(0, 0x400000 // (step * 0x10000), count)) if dtype == torch.bfloat16 \
+        else f32_bits(0x44800000 + rng.integers(0, 0x400000, count))
+    assert ((lo >= 1024) & (lo < 1536)).all()
+    return np.where(rng.random(count) < 0.3, np.float32(0), lo).astype(np.float32)
+
+
+def tie_case(B, A, C, P, top, tie_value, tie, rank_in_tie, dtype=torch.float32, grad_scale=1.0, seed=0, below=()):
+    """3P - rank_in_tie keys of `top` (all above tie_value, the smallest of them) above a tie group of `tie` keys at tie_value; the
+    threshold is member rank_in_tie of the group, N = 3P - rank_in_tie + tie.  `below`: keys under tie_value that share its
+    radix prefix; the remaining rows hold keys below 1536."""
+    n = B * A
+    above = 3 * P - rank_in_tie
+    top = np.sort(np.asarray(top, dtype=np.float32))[:above]
+    below = np.asarray(below, dtype=np.float32)
+    assert top.size == above and (top > tie_value).all() and tie_value >= 1536 and 1 <= rank_in_tie <= tie
+    assert (below < tie_value).all()
+    rest = n - P - above - tie - below.size
+    keys = np.concatenate([top, np.full(tie, tie_value, dtype=np.float32), below, _fill_keys(rest, seed, dtype)])
+    mask, key = scatter_keys(n, P, keys, seed)
+    design = dict(N=above + tie, tie=tie, rank_in_tie=rank_in_tie, tau_bits=int(np.float32(tie_value).view(np.uint32)))
+    return loss_case(B, A, C, mask, key, dtype=dtype, grad_scale=grad_scale, seed=seed, design=design)
+
+
+def level3_keys():
+    """1024 consecutive floats that share their top 22 bits (one level-2 bin of the radix select): only the low digit differs"""
+    return f32_bits(0x45000400 + np.arange(1024))
+
+
+def level2_keys(seed=0):
+    """one key in each of 1500 level-2 bins of one level-1 bin (top 11 bits shared), random low digits"""
+    rng = np.random.default_rng(5 + seed)
+    bins = rng.choice(2048, 1500, replace=False)
+    return np.sort(f32_bits(0x45000000 + (bins << 10) + rng.integers(0, 1024, 1500)))
+
+
+def level1_keys():
+    """four keys per binade from 2^10 to 2^127 -- one per level-1 bin, 472 bins, owned by 59 threads of find_bin -- and FLT_MAX"""
+    e = np.repeat(np.arange(10, 128), 4)
+    q = np.tile(np.arange(4), 118)
+    return np.concatenate([((1 + q / 4.0) * 2.0 ** e).astype(np.float32), f32_bits([0x7F7FFFFF])])        # ascending
+
+
+def bf16_keys(count):
+    """the `count` smallest bf16 values above 1536"""
+    return f32_bits((0x44C00000 + 0x10000 * (1 + np.arange(count))).astype(np.uint32))
+
+
+def _dense_catalogue():
+    f32, bf = torch.float32, torch.bfloat16
+    c = {}
+    # radix level 3 decides: the threshold's key is the first / a middle / the last member of its level-3 bin (one fp32 value)
+    k3, k2, k1 = level3_keys(), level2_keys(), level1_keys()
+    for name, rank in (("first", 1), ("middle", 3), ("last", 5)):
+        c["level3 %s (2,300,21) f32" % name] = lambda rank=rank: tie_case(2, 300, 21, 16, k3[500:], k3[499], 5, rank, seed=rank, below=k3[:499])
+    c["level3 all 1024 low digits (4,500,21) f32"] = lambda: tie_case(4, 500, 21, 300, k3[125:], k3[124], 2, 1, seed=4, below=k3[:124])
+    c["level2 (4,500,5) f32"] = lambda: tie_case(4, 500, 5, 200, k2[901:], k2[900], 3, 2, seed=6, below=k2[:900])
+    # (the selected keys start at 1.5 * 2^104: their float64 sum is exact, see sums_exactly)
+    c["level1 (3,301,21) f32"] = lambda: tie_case(3, 301, 21, 32, k1[379:], k1[378], 2, 2, seed=7, below=k1[:378])
+    for dt, tag in ((f32, "f32"), (bf, "bf16")):
+        c["tie straddles 3P (2,300,21) %s" % tag] = lambda dt=dt: tie_case(2, 300, 21, 16, bf16_keys(64)[1:], bf16_keys(64)[0], 21, 5, dtype=dt, seed=8)
+        c["tie ends at 3P (2,300,21) %s" % tag] = lambda dt=dt: tie_case(2, 300, 21, 16, bf16_keys(64)[1:], bf16_keys(64)[0], 6, 6, dtype=dt, seed=9)
+        # every negative selected: 3P = n - P, the threshold is the smallest key
+        c["every negative (2,128,21) %s" % tag] = lambda dt=dt: tie_case(2, 128, 21, 64, bf16_keys(200)[1:], bf16_keys(200)[0], 1, 1, dtype=dt, seed=10)
+        c["n=4 P=1 (1,4,21) %s" % tag] = lambda dt=dt: tie_case(1, 4, 21, 1, bf16_keys(3)[1:], bf16_keys(3)[0], 1, 1, dtype=dt, seed=11)
+        c["odd tail (3,301,21) %s" % tag] = lambda dt=dt: tie_case(3, 301, 21, 32, bf16_keys(128)[1:], bf16_keys(128)[0], 40, 7, dtype=dt, seed=12)
+        for C in (2, 5, 81, 112, 288, 303):
+            c["C=%d (3,301,%d) %s" % (C, C, tag)] = lambda dt=dt, C=C: tie_case(3, 301, C, 32, bf16_keys(128)[1:], bf16_keys(128)[0], 40, 7, dtype=dt, seed=13 + C)
+        c["status 1: P=0 (2,150,21) %s" % tag] = lambda dt=dt: loss_case(2, 150, 21, np.zeros(300, dtype=bool), _fill_keys(300, 1, dt), dtype=dt, seed=14)
+        c["status 1: 3P>n (2,150,21) %s" % tag] = lambda dt=dt: loss_case(2, 150, 21, np.arange(300) % 3 != 1, bf16_keys(300), dtype=dt, seed=15)
+    # more rows than persistent workgroups of k_loss_rows (768 x 128) and than one stride of k_loss_hist (256 x 256 keys)
+    c["persistent (5,19661,81) bf16"] = lambda: tie_case(5, 19661, 81, 512, bf16_keys(1700)[1:], bf16_keys(1700)[0], 600, 88, dtype=bf, seed=16)
+    c["persistent (5,19661,4) f32"] = lambda: tie_case(5, 19661, 4, 512, level3_keys()[100:].repeat(2), level3_keys()[99], 3, 2, seed=17, below=level3_keys()[:99])
+    return c
+
+
+LOSS_CASES = _dense_catalogue()
+_LOSS_CACHE = {}
+
+
+def loss_cached(name, table=None):
+    """a case of the catalogue, built once per process and never modified"""
+    table = LOSS_CASES if table is None else table
+    if name not in _LOSS_CACHE:
+        _LOSS_CACHE[name] = table[name]()
+    return _LOSS_CACHE[name]
+
+
+# ---- exact loss cases for the compact-row form: P, N = 4P and grad_scale are powers of two ------------------------------------
+def heads_loss_case(B, geom, C, P, full=(), empty=(), empty_img=(), grad_scale=1.0, seed=0, rank_in_tie=1):
+    """5P selected anchors at chosen places: one per pixel of every level in `full` (every pixel gets a row), none in the levels
+    of `empty`, none in (image, level) of `empty_img`, the rest at seeded random places.  P of them are positives, 3P -
+    rank_in_tie hold distinct keys above a tie group of P + rank_in_tie at 1544: N = 4P.  bf16."""
+    A = anchors_of(geom)
+    n = B * A
+    rng = np.random.default_rng(300 + seed)
+    allowed = np.ones((B, A), dtype=bool)
+    chosen = np.zeros((B, A), dtype=bool)
+    off = 0
+    for l, (h, w, k) in enumerate(geom):
+        sl = slice(off, off + h * w * k)
+        if l in empty:
+            allowed[:, sl] = False
+        for b, le in empty_img:
+            if le == l:
+                allowed[b, sl] = False
+        if l in full:
+            pick = off + np.arange(h * w) * k + rng.integers(0, k, (B, h * w))
+            chosen[np.arange(B)[:, None], pick] = True
+        for b in range(B):                                      # at least one selected anchor wherever any is allowed
+            if allowed[b, off]:
+                chosen[b, off + rng.integers(0, h * w * k)] = True
+        off += h * w * k
+    need = 5 * P - int(chosen.sum())
+    free = np.flatnonzero((allowed & ~chosen).reshape(n))
+    assert 0 <= need <= free.size, (need, free.size)
+    chosen.reshape(n)[rng.choice(free, need, replace=False)] = True
+    sel = rng.permutation(np.flatnonzero(chosen.reshape(n)))
+    mask = np.zeros(n, dtype=bool)
+    mask[sel[:P]] = True
+    above, tie = 3 * P - rank_in_tie, P + rank_in_tie
+    keys = bf16_keys(above + 1)
+    key = np.zeros(n, dtype=np.float32)
+    key[sel[P:P + above]] = keys[1:]
+    key[sel[P + above:]] = keys[0]
+    rest = np.flatnonzero(~chosen.reshape(n))
+    key[rest] = _fill_keys(rest.size, seed, torch.bfloat16)
+    design = dict(N=4 * P, tie=tie, rank_in_tie=rank_in_tie)
+    r = loss_case(B, A, C, mask, key, dtype=torch.bfloat16, grad_scale=grad_scale, seed=seed, design=design)
+    assert np.array_equal(r["selected"], chosen.reshape(n))
+    r["geom"] = geom
+    r["npad"] = tuple((k * (4 + C) + 7) // 8 * 8 + (8 if C == 5 else 0) + (16 if C == 5 and k == 6 else 0) for _, _, k in geom)
+    r["levels"] = heads_expected(r, geom, r["npad"])
+    return r
+
+
+HEADS_LOSS_CASES = {
+    # a level with every pixel selected (19 x 19: two chunks of k_hg_assign), one without any, an image without any in a level
+    "8 levels B=3 C=81": lambda: heads_loss_case(3, GEOM8, 81, 256, full=(0,), empty=(5,), empty_img=((1, 2), (0, 7)), grad_scale=4.0, seed=1),
+    "8 levels B=1 C=5": lambda: heads_loss_case(1, GEOM8, 5, 64, empty=(7,), seed=2),
+    "7 levels B=3 C=81": lambda: heads_loss_case(3, GEOM7, 81, 64, full=(0, 3), empty_img=((1, 1),), seed=3, rank_in_tie=5),
+    "1 level B=1 C=5": lambda: heads_loss_case(1, GEOM1, 5, 8, grad_scale=0.5, seed=4),
+    "1 level B=3 C=81": lambda: heads_loss_case(3, GEOM1, 81, 32, full=(0,), seed=5),
+    # a second batch of the first geometry: the inputs Y of the ws_clean cases
+    "8 levels B=3 C=81 second": lambda: heads_loss_case(3, GEOM8, 81, 128, empty=(1,), seed=6),
+}
+
+
+def heads_cached(name):
+    return loss_cached(name, HEADS_LOSS_CASES)
+
+
+# ---- the sparse head backward kernels: hand-made compact rows ---------------------------------------------------------------------
+UNREAD = 2.0 ** 100                                            # (finite: the arena compares inputs with torch.equal)
+
+
+def hand_rows(g, B, H, W, n, C, npad, count):
+    """ssd_head_grads contents of one level with `count` rows, as the loss writes them: ascending pixel_of_row that holds the
+    four corners and an edge pixel of image 0 first (as far as count allows), the inverse map, and rows with the entries of one
+    or two selected anchors -- a positive's +-2^-6 on its offsets, its label and the row maximum, a mined negative's +-2^-8 on
+    the row maximum and the background.  Rows and indices past `count` hold what must never be read (2^100; pixel 0)."""
+    hw, total = H * W, B * H * W
+    assert 0 <= count <= total
+    must = [0, W - 1, (H - 1) * W, hw - 1, (H // 2) * W, W // 2, (H // 2) * W + W - 1, (H - 1) * W + W // 2]
+    must = list(dict.fromkeys(must))[:count]
+    rest = [p for p in torch.randperm(total, generator=g).tolist() if p not in must][:count - len(must)]
+    por = torch.tensor(sorted(must + rest), dtype=torch.int32)
+    rop = torch.full((total,), -1, dtype=torch.int32)
+    rop[por.long()] = torch.arange(count, dtype=torch.int32)
+    rows = torch.zeros((total, npad), dtype=torch.float32)
+    for r in range(count):
+        for a in set(torch.randint(0, n, (2,), generator=g).tolist()):
+            c0, c1 = torch.randperm(C - 1, generator=g)[:2].tolist() if C > 2 else (0, 0)
+            if int(torch.randint(0, 2, (1,), generator=g)):                       # a positive: offsets, label and maximum
+                for j in torch.randperm(4, generator=g)[:2].tolist():
+                    rows[r, a * 4 + j] = 2.0 ** -6 * (1 if int(torch.randint(0, 2, (1,), generator=g)) else -1)
+                rows[r, n * 4 + a * C + c0] = -2.0 ** -6
+                rows[r, n * 4 + a * C + (c1 if c1 != c0 else C - 1)] = 2.0 ** -6
+            else:                                                                  # a mined negative: maximum and background
+                rows[r, n * 4 + a * C + c0] = 2.0 ** -8
+                rows[r, n * 4 + a * C + C - 1] = -2.0 ** -8
+    dense = torch.zeros((total, npad), dtype=torch.float32)
+    dense[por.long()] = rows[:count]
+    rows[count:] = UNREAD
+    por_full = torch.zeros((total,), dtype=torch.int32)
+    por_full[:count] = por
+    return dict(rows=rows.to(torch.bfloat16), pixel_of_row=por_full, row_of_pixel=rop, count=count, dense=dense.view(B, H, W, npad))
+
+
+def head_bwd_reference(x, w, dy):
+    """fp32 gradients of y = conv3x3_same(x, w) + b for dL/dy = dy on the CPU (torch autograd), NHWC / [cout,3,3,Cin]"""
+    xr = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    wr = w.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    br = torch.zeros(w.shape[0], dtype=w.dtype, requires_grad=True)
+    F.conv2d(xr, wr, br, padding=1).backward(dy.permute(0, 3, 1, 2))
+    return xr.grad.permute(0, 2, 3, 1).contiguous(), wr.grad.permute(0, 2, 3, 1).contiguous(), br.grad
+
+
+def sparse_level(g, B, H, W, Cin, cout, npad, dense, relu):
+    """operands and references of one head level for dL/dy = dense[..., :cout]: x in {-2..2} (clamped at 0 where a ReLU mask is
+    derived from it), filters in {-1, 0, 1} thinned until the fp32 data gradient is bf16-exact"""
+    x = ints(g, (B, H, W, Cin), (-2, -1, 0, 1, 2))
+    if relu != "none":
+        x = x.clamp_min(0)
+    dy = dense[..., :cout].contiguous()
+    density = 0.5
+    while True:
+        w = ints(g, (cout, 3, 3, Cin), (-1, 1), density)
+        dx, dw, db = head_bwd_reference(x.float(), w.float(), dy)
+        if in_bf16_regime(dx):
+            break
+        density /= 2
+        assert density > 1e-3
+    if relu != "none":
+        dx = masked(dx, x.float() > 0)
+    w_tap = torch.zeros((3, 3, Cin, npad), dtype=torch.bfloat16)
+    w_tap[..., :cout] = w.permute(1, 2, 3, 0)
+    units = dy.abs()[dy != 0].min() if bool((dy != 0).any()) else torch.tensor(1.0)
+    return dict(H=H, W=W, Cin=Cin, cout=cout, npad=npad, x=x, w=w, w_tap=w_tap, bits=pack_bits(x.float() > 0), dx=dx, dw=dw, dbias=db,
+                density=density, fp32=((B * H * W, x, dy / units),))
+
+
+# name -> (B, relu, [(H, W, Cin, per_cell, classes, npad, rows)]); cout = per_cell * (4 + classes) = 36, 340, 510
+SPARSE_CASES = {
+    # B * hw = 361, 35, 35, 9, 1: no multiple of k_hz_col2im's four pixels; one row more than k_hz_gemm's tile; every pixel of a
+    # non-square map; one row; none
+    "B=1 bits": (1, "bits", [(19, 19, 128, 4, 81, 344, 129), (7, 5, 256, 6, 81, 512, 35), (5, 7, 128, 4, 5, 48, 1),
+                             (3, 3, 256, 4, 5, 40, 0), (1, 1, 128, 4, 81, 344, 1)]),
+    "B=1 src": (1, "src", [(19, 19, 128, 4, 81, 344, 129), (7, 5, 256, 6, 81, 512, 35), (5, 7, 128, 4, 5, 48, 1),
+                           (3, 3, 256, 4, 5, 40, 0), (1, 1, 128, 4, 81, 344, 1)]),
+    # exactly one tile of rows, one row fewer, and a map with every pixel selected
+    "B=3 none": (3, "none", [(16, 8, 128, 4, 81, 344, 128), (8, 16, 256, 4, 5, 40, 127), (3, 3, 128, 6, 81, 512, 27)]),
+    # 1444 rows: two active pixel splits of the weight gradient; 768 rows on the same shape: one
+    "B=4 splits": (4, "bits", [(19, 19, 128, 4, 81, 344, 1444), (19, 19, 128, 4, 81, 344, 768)]),
+}
+
+
+def sparse_case(name):
+    B, relu, levels = SPARSE_CASES[name]
+    g = _gen(B, len(levels), len(relu))
+    out = []
+    for H, W, Cin, n, C, npad, count in levels:
+        hg = hand_rows(g, B, H, W, n, C, npad, count)
+        lv = sparse_level(g, B, H, W, Cin, n * (4 + C), npad, hg["dense"], relu)
+        lv.update(hw=H * W, n=n, **{k: hg[k] for k in ("rows", "pixel_of_row", "row_of_pixel", "count")})
+        out.append(lv)
+    return dict(B=B, relu=relu, levels=out)
+
+
+def sparse_cached(name):
+    if ("sparse", name) not in _LOSS_CACHE:
+        _LOSS_CACHE[("sparse", name)] = sparse_case(name)
+    return _LOSS_CACHE[("sparse", name)]
+
+
+def chained_case(name="7 levels B=3 C=81", Cin=128):
+    """an exact loss case in the compact-row form and, per level, the operands and references of the head convolutions' backward
+    pass for the gradient that loss produces"""
+    if ("chained", name) not in _LOSS_CACHE:
+        r = heads_cached(name)
+        g = _gen(r["B"], r["A"], 9)
+        lv = [sparse_level(g, r["B"], l["H"], l["W"], Cin, l["n"] * (4 + r["C"]), l["npad"], l["dense"].float(), "bits") for l in r["levels"]]
+        _LOSS_CACHE[("chained", name)] = dict(loss=r, levels=lv)
+    return _LOSS_CACHE[("chained", name)]
+
+
+def check_sparse_regime(levels):
+    for lv in levels:
+        assert in_bf16_regime(lv["dx"]), "dx"
+        for k_total, a, b in lv["fp32"]:
+            assert in_fp32_regime(k_total, a, b)

@@ -153,3 +153,26 @@ def test_loss_full_config_properties(ops):
     # determinism: bitwise identical on a second run
     out2, dconf2, _ = ops.ssd_loss(conf, loc, cls, gloc, mask)
     assert torch.equal(out, out2) and torch.equal(dconf, dconf2)
+
+
+def hand_targets(B, A, C, P, seed):
+    """targets without the 81-class prior set: a random mask with exactly P positives, random foreground classes, random offsets"""
+    g = torch.Generator().manual_seed(seed)
+    mask = torch.zeros((B * A,), dtype=torch.uint8)
+    mask[torch.randperm(B * A, generator=g)[:P]] = 1
+    cls = torch.randint(0, C - 1, (B, A), generator=g, dtype=torch.int32)
+    gloc = torch.randn((B, A, 4), generator=g)
+    return cls.cuda(), gloc.cuda(), mask.view(B, A).cuda()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("C", [2, 21, 112, 288])
+def test_loss_random_logits_any_class_count(ops, C, dtype):
+    """k_loss_rows<T, 0> (any class count but 81) and the ragged last block on ordinary logits: __expf / __logf away from the
+    exact regime of tests/test_loss_strict_gpu.py.  A = 301, B = 3: seven rows in the last block, a scalar tail for every C."""
+    B, A = 3, 301
+    cls, gloc, mask = hand_targets(B, A, C, 40, 5 + C)
+    g = torch.Generator(device="cuda").manual_seed(C)
+    conf = (2.0 * torch.randn((B, A, C), generator=g, device="cuda")).to(dtype)
+    loc = (0.5 * torch.randn((B, A, 4), generator=g, device="cuda")).to(dtype)
+    run_case(ops, conf, loc, cls, gloc, mask)

@@ -203,3 +203,215 @@ def test_arena_reports_an_output_the_call_does_not_list():
         y.copy_(x * 2)
         z[0] = 1.0
     check_reported(a, bad, [(y, x.clone() * 2)], "z was written although the call does not list it")
+
+
+# ---------------------------------------------------------------- the exact loss cases
+import numpy as np                                                                    # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(strict.LOSS_CASES), ids=str)
+def test_loss_case_regime(name):
+    strict.check_loss_regime(strict.loss_cached(name))
+
+
+@pytest.mark.parametrize("name", sorted(strict.HEADS_LOSS_CASES), ids=str)
+def test_heads_loss_case_regime(name):
+    r = strict.heads_cached(name)
+    strict.check_loss_regime(r)
+    assert r["pow2"] and r["N"] == 4 * r["P"], "P, N and grad_scale are powers of two in every case that feeds the head kernels"
+    for l in r["levels"]:
+        k = l["count"]
+        assert bool((l["pixel_of_row"][1:] > l["pixel_of_row"][:-1]).all()) and int((l["row_of_pixel"] >= 0).sum()) == k
+        assert not bool((l["rows"][:, l["n"] * (4 + r["C"]):] != 0).any())
+    mask = r["gt_mask"].numpy().reshape(-1).astype(bool)
+    assert int(((r["pos_ce"] == 0) & mask).sum()) > 0, "a selected positive with an all-zero row"
+
+
+def test_loss_catalogue_covers_what_it_names():
+    """the radix digits that decide, the tie shapes, the block shapes: properties of the inputs"""
+    def keys(name):
+        r = strict.loss_cached(name)
+        return r, r["key"][~r["gt_mask"].numpy().reshape(-1).astype(bool)].view(np.uint32), int(r["out8"][6:7].view(torch.int32))
+    for name in ("level3 first (2,300,21) f32", "level3 middle (2,300,21) f32", "level3 last (2,300,21) f32"):
+        r, k, tau = keys(name)
+        near = k[(k >> 21) == (tau >> 21)]
+        assert len(set(near >> 10)) == 1 and len(set(near & 1023)) > 500            # one level-2 bin, the low digit decides
+        assert sorted(set(np.diff(np.unique(near)))) == [1]                       # consecutive floats
+    assert [strict.loss_cached("level3 %s (2,300,21) f32" % n)["design"]["rank_in_tie"] for n in ("first", "middle", "last")] == [1, 3, 5]
+    r, k, tau = keys("level3 all 1024 low digits (4,500,21) f32")
+    assert len(set(k[(k >> 10) == (tau >> 10)] & 1023)) == 1024
+    r, k, tau = keys("level2 (4,500,5) f32")
+    near = k[(k >> 21) == (tau >> 21)]
+    assert len(set(near >> 10)) >= 1499 and len(set((near >> 10) & 2047) & set(range(0, 2048, 8))) > 100    # every owner thread
+    r, k, tau = keys("level1 (3,301,21) f32")
+    assert len(set(k >> 21)) >= 473 and k.max() == 0x7F7FFFFF and (k >> 21).min() <= 0x224
+    for tag in ("f32", "bf16"):
+        r = strict.loss_cached("tie straddles 3P (2,300,21) %s" % tag)
+        assert r["N"] > 3 * r["P"] and (r["key"] == 0).sum() > r["P"]               # background-is-maximum rows below tau
+        r = strict.loss_cached("tie ends at 3P (2,300,21) %s" % tag)
+        assert r["N"] == 3 * r["P"] and r["design"]["tie"] > 1
+        r = strict.loss_cached("every negative (2,128,21) %s" % tag)
+        assert r["N"] == 3 * r["P"] == r["B"] * r["A"] - r["P"]
+        r = strict.loss_cached("odd tail (3,301,21) %s" % tag)
+        assert (r["B"] * r["A"]) % 128 % 2 == 1 and ((r["B"] * r["A"]) % 128 * r["C"]) % 4 != 0
+    for name in ("persistent (5,19661,81) bf16", "persistent (5,19661,4) f32"):
+        r = strict.loss_cached(name)
+        assert r["B"] * r["A"] >= 98305 and r["conf"].numel() * r["conf"].element_size() <= 16 << 20
+
+
+def fake_loss(r, ge=True, rank_shift=0):
+    """The loss restated for the exact regime in plain fp32 numpy (the softmax is the one-hot of the row maximum), with the two
+    classic mistakes of a selection as switches.  Returns out8, dconf, dloc, selected."""
+    B, A, C, gs = r["B"], r["A"], r["C"], np.float32(r["grad_scale"])
+    n = B * A
+    z = r["conf"].float().numpy().reshape(n, C)
+    mask = r["gt_mask"].numpy().reshape(n).astype(bool)
+    cls = r["gt_cls"].numpy().reshape(n)
+    m = z.max(-1)
+    key = np.where(mask, np.float32(0), m - z[:, C - 1])
+    P = int(mask.sum())
+    tau = np.sort(key)[::-1][3 * P + rank_shift - 1]
+    neg = ~mask & ((key >= tau) if ge else (key > tau))
+    N = int(neg.sum())
+    label = np.where(mask, cls, C - 1)
+    onehot = (np.arange(C)[None, :] == label[:, None]).astype(np.float32)
+    sc = np.where(mask, gs / np.float32(P), gs / np.float32(N)) * (mask | neg)
+    dconf = ((z == m[:, None]).astype(np.float32) - onehot) * sc[:, None].astype(np.float32) + np.float32(0)
+    d = r["loc"].float().numpy().reshape(n, 4) - r["gt_loc"].numpy().reshape(n, 4)
+    dloc = np.sign(d) * (mask[:, None] * (gs / np.float32(P))) + np.float32(0)
+    ce = (m - z[np.arange(n), cls])[mask].astype(np.float64).sum() / P
+    out = np.array([np.abs(d)[mask].astype(np.float64).sum() / P, ce, key[neg].astype(np.float64).sum() / N, 0, P, N, tau, 0], dtype=np.float32)
+    out[3] = (out[0] + out[1]) + out[2]
+    dt = r["dtype"]
+    return (torch.from_numpy(out), torch.from_numpy(dconf.astype(np.float32)).view(B, A, C).to(dt),
+            torch.from_numpy(dloc.astype(np.float32)).view(B, A, 4).to(dt), mask | neg)
+
+
+def loss_arena(r):
+    a = strict.Arena("cpu", 64 << 20)
+    return a, a.out((8,), torch.float32, "out8"), a.out(tuple(r["dconf"].shape), r["dtype"], "dconf"), a.out(tuple(r["dloc"].shape), r["dtype"], "dloc")
+
+
+def run_fake(r, **kw):
+    a, out8, dconf, dloc = loss_arena(r)
+
+    def fn():
+        o, dc, dl, _ = fake_loss(r, **kw)
+        out8.copy_(o); dconf.copy_(dc); dloc.copy_(dl)
+    return a.run(fn, [(out8, r["out8"]), (dconf, r["dconf"]), (dloc, r["dloc"])])
+
+
+@pytest.mark.parametrize("name", ["tie straddles 3P (2,300,21) f32", "tie straddles 3P (2,300,21) bf16", "level3 middle (2,300,21) f32",
+                                  "level1 (3,301,21) f32", "odd tail (3,301,21) bf16", "C=2 (3,301,2) f32"])
+def test_arena_passes_a_correct_fake_loss(name):
+    """an fp32 restatement of the kernel's formulas gives the expected outputs bit for bit: the expectation does not lean on
+    float64"""
+    run_fake(strict.loss_cached(name))
+
+
+def test_arena_reports_a_loss_that_selects_with_greater_than():
+    r = strict.loss_cached("tie straddles 3P (2,300,21) f32")
+    with pytest.raises(strict.StrictError) as e:
+        run_fake(r, ge=False)
+    assert "out8 differs from the reference" in str(e.value) and "dconf differs from the reference" in str(e.value)
+
+
+@pytest.mark.parametrize("shift", [-1, 1])
+def test_arena_reports_a_loss_that_is_off_by_one_rank(shift):
+    """consecutive floats around the threshold: one rank is one ulp of tau and one row of dconf"""
+    r = strict.loss_cached("level3 last (2,300,21) f32" if shift == 1 else "level3 first (2,300,21) f32")
+    with pytest.raises(strict.StrictError) as e:
+        run_fake(r, rank_shift=shift)
+    assert "out8 differs from the reference" in str(e.value) and "dconf differs from the reference" in str(e.value)
+
+
+def heads_fake_arena(r):
+    a = strict.Arena("cpu", 64 << 20)
+    B = r["B"]
+    t = dict(rows=[a.out((B * l["hw"], l["npad"]), torch.bfloat16, "rows[%d]" % i) for i, l in enumerate(r["levels"])],
+             por=[a.out((B * l["hw"],), torch.int32, "pixel_of_row[%d]" % i) for i, l in enumerate(r["levels"])],
+             count=a.out((8,), torch.int32, "count"))
+    expect = []
+    nl = len(r["levels"])
+    counts = torch.zeros((8,), dtype=torch.int32)
+    counts[:nl] = torch.tensor([l["count"] for l in r["levels"]], dtype=torch.int32)
+    expect.append((t["count"], counts, torch.arange(8) < nl))
+    for i, l in enumerate(r["levels"]):
+        first = torch.arange(B * l["hw"]) < l["count"]
+        por = torch.zeros((B * l["hw"],), dtype=torch.int32)
+        por[:l["count"]] = l["pixel_of_row"]
+        expect += [(t["por"][i], por, first), (t["rows"][i], l["rows"], first[:, None].expand(-1, l["npad"]).clone())]
+
+    def good():
+        t["count"][:nl] = counts[:nl]
+        for i, l in enumerate(r["levels"]):
+            k = l["count"]
+            t["por"][i][:k] = l["pixel_of_row"]
+            t["rows"][i][:k] = l["rows"][:k]
+    return a, t, expect, good, nl
+
+
+def test_arena_reports_a_stale_row_behind_count_and_a_write_of_count_levels():
+    r = strict.heads_cached("1 level B=1 C=5")
+    a, t, expect, good, nl = heads_fake_arena(r)
+    a.run(good, expect)
+    k = r["levels"][0]["count"]
+
+    def stale_row():
+        good()
+        t["rows"][0][k] = 0                                                          # a zero-filled row nobody asked for
+    check_reported(a, stale_row, expect, r"rows\[0\] was written outside its documented extent")
+
+    def stale_index():
+        good()
+        t["por"][0][k] = 0
+    check_reported(a, stale_index, expect, r"pixel_of_row\[0\] was written outside its documented extent")
+
+    def count_levels():
+        good()
+        t["count"][nl] = 0
+    check_reported(a, count_levels, expect, "count was written outside its documented extent")
+
+
+# ---------------------------------------------------------------- the sparse head backward cases
+@pytest.mark.parametrize("name", sorted(strict.SPARSE_CASES), ids=str)
+def test_sparse_case_regime(name):
+    case = strict.sparse_cached(name)
+    strict.check_sparse_regime(case["levels"])
+    for l in case["levels"]:
+        k, por, rop = l["count"], l["pixel_of_row"], l["row_of_pixel"]
+        assert bool((por[:k][1:] > por[:k][:-1]).all()) and int((rop >= 0).sum()) == k
+        assert torch.equal(rop[por[:k].long()], torch.arange(k, dtype=torch.int32))
+        assert bool((l["rows"][k:].float() == strict.UNREAD).all())
+        vals = set(l["rows"][:k].float().abs().unique().tolist())
+        assert vals <= {0.0, 2.0 ** -6, 2.0 ** -8}
+        assert not bool((l["rows"][:k, l["cout"]:] != 0).any())
+        if case["relu"] != "none":
+            assert bool((l["x"] >= 0).all()) and bool((l["x"] == 0).any())
+        # the reference of the weight gradient in float64 is the same number
+        dy = torch.zeros((case["B"] * l["hw"], l["npad"]))
+        dy[por[:k].long()] = l["rows"][:k].float()
+        dy = dy.view(case["B"], l["H"], l["W"], l["npad"])[..., :l["cout"]].contiguous()
+        _, dw64, db64 = strict.head_bwd_reference(l["x"].double(), l["w"].double(), dy.double())
+        assert torch.equal(dw64, l["dw"].double()) and torch.equal(db64.double(), l["dbias"].double())
+
+
+def test_sparse_catalogue_covers_what_it_names():
+    counts = sorted(l["count"] for n in strict.SPARSE_CASES for l in strict.sparse_cached(n)["levels"])
+    assert {0, 1, 127, 128, 129, 768, 1444} <= set(counts)
+    b1 = strict.sparse_cached("B=1 bits")
+    assert all((b1["B"] * l["hw"]) % 4 for l in b1["levels"]) and any(l["H"] != l["W"] for l in b1["levels"])
+    full = b1["levels"][1]
+    assert full["count"] == full["hw"]                                                  # every corner and edge of a 7 x 5 map
+    assert {l["cout"] for n in strict.SPARSE_CASES for l in strict.sparse_cached(n)["levels"]} == {36, 340, 510}
+    assert {l["Cin"] for n in strict.SPARSE_CASES for l in strict.sparse_cached(n)["levels"]} == {128, 256}
+    for l in strict.sparse_cached("B=1 bits")["levels"][:1] + strict.sparse_cached("B=4 splits")["levels"]:
+        k, por = l["count"], l["pixel_of_row"]
+        assert {0, l["W"] - 1, (l["H"] - 1) * l["W"], l["hw"] - 1} <= set(por[:k].tolist())
+
+
+def test_chained_case_regime():
+    c = strict.chained_case()
+    strict.check_sparse_regime(c["levels"])
+    strict.check_loss_regime(c["loss"])
+    assert len(c["levels"]) == 7 and c["loss"]["pow2"]
