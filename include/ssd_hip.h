@@ -182,6 +182,47 @@ int ssd_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const i
                            const ssd_head_grads* hg, void* ws, size_t ws_bytes, int ws_clean, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The SSD paper's MultiBox loss (Liu et al. 2016, eq. 1-3), forward + backward.  Opt-in, no reference counterpart: the
+ * loss above stays the default.  Inputs as ssd_loss_fwd_bwd.  With CE(a, c) = logsumexp(conf[a]) - conf[a, c] and
+ * key(a) = CE(a, C-1):
+ *   per image b: P_b positives (gt_mask); the candidates are the other anchors; k_b = min(neg_pos_ratio * P_b, A - P_b);
+ *             k_b == 0 mines nothing, else tau_b = the k_b-th largest candidate key and neg_b = {candidates with
+ *             key >= tau_b} (ties at tau_b kept; positives are excluded explicitly, so tau_b == 0 is legal)
+ *   P = sum P_b, N = sum |neg_b|, smoothL1(d) = 0.5 d^2 if |d| < 1 else |d| - 0.5
+ *   L_pos = sum_pos CE(a, gt_cls) / P;  L_neg = sum_neg key(a) / P;  L_loc = loc_weight * sum_pos sum_4 smoothL1(loc - gt_loc) / P
+ *   dconf = grad_scale / P * [pos * (softmax - onehot(gt_cls)) + neg * (softmax - onehot(C-1))]
+ *   dloc  = grad_scale * loc_weight / P * pos * clamp(loc - gt_loc, -1, 1);  every element of both is written
+ *   out8      float[8]: L_loc, L_pos, L_neg, (L_loc + L_pos) + L_neg, P, N, tau_min (the smallest tau_b of the images that
+ *             mined, 0 if none did), status (0 ok; 1 = P == 0: scalars 0, gradients exact zeros, the rows form has every
+ *             count 0 and every row_of_pixel -1; 3 = a logit row or a positive's offsets were NaN / Inf, reported first)
+ *   neg_pos_ratio >= 1, loc_weight finite and >= 0, grad_scale finite: SSD_ERR_VALUE otherwise, as for a NULL pointer, a
+ *             dtype that is neither SSD_F32 nor SSD_BF16, B <= 0, A <= 0 or C < 2
+ *   C         <= SSD_LOSS_MAX_CLASSES; A <= SSD_MULTIBOX_MAX_ANCHORS (= ssd_multibox_loss_max_anchors()): the select keeps one
+ *             image's A keys (4 bytes each) next to its 8 KB digit histogram in the 160 KB of LDS of a workgroup;
+ *             SSD_ERR_UNSUPPORTED beyond either bound
+ *   ws        >= ssd_multibox_loss_workspace_bytes(B, A, C) bytes (SSD_ERR_WORKSPACE otherwise); needs NO initial contents:
+ *             every word is written before it is read, no global atomics
+ * Every refusal happens on the host before anything is launched.  The normaliser P is per call (one micro-batch or one
+ * rank's shard), as the counts of the loss above are.  Deterministic: integer counts and fixed-order f64 sums only.
+ * The _heads form hands the gradient over as the compact rows of ssd_loss_fwd_bwd_heads (same struct, same layout, same
+ * refusals for `hg`; SSD_ERR_ASSERT when the levels do not sum to A): dtype SSD_BF16 only (SSD_F32: SSD_ERR_UNSUPPORTED);
+ * ws >= ssd_multibox_loss_heads_workspace_bytes(B, A, C) bytes, no ws_clean (nothing is carried from call to call);
+ * scattered back, the rows are bit-identical to the dense form's dconf / dloc.
+ * ---------------------------------------------------------------------------------------- */
+#define SSD_MULTIBOX_MAX_ANCHORS 36864
+int ssd_multibox_loss_max_anchors(void);
+size_t ssd_multibox_loss_workspace_bytes(int B, int A, int C);
+int ssd_multibox_loss_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                              const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
+                              float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
+                              void* stream);
+size_t ssd_multibox_loss_heads_workspace_bytes(int B, int A, int C);
+int ssd_multibox_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                    const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
+                                    float grad_scale, float* out8, const ssd_head_grads* hg, void* ws, size_t ws_bytes,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inference scoring + decode -- replaces the scoring half of SSDObjectDetectionModel.visualize
  * (models/ssd_model.py:479-488, mask=None branch) and the box decode of visualize_dataset (:466-467).
  *   conf [B*A*C], loc [B*A*4] (SSD_F32 / SSD_BF16), priors double[A*4]

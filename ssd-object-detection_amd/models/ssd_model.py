@@ -38,7 +38,7 @@ class SSDObjectDetectionModel:
     class TrainConfig:
         def __init__(self, epoch, batch_size, optimizer, warmup=True, warmup_optimizer=None, warmup_step=1000,
                      visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0, augment=None,
-                     val=None):
+                     val=None, loss=None):
             if warmup_optimizer is None:
                 warmup_optimizer = _opt.Adam(_opt.PolynomialDecay(1e-6, 1000, 0.001))
             self.epoch = epoch
@@ -52,6 +52,9 @@ class SSDObjectDetectionModel:
             self.split_batch_size = split_batch_size
             self.start_epoch = start_epoch                 # > 0: resumed run (no warm-up, epochs start_epoch..epoch-1)
             self.augment = augment                         # ops.AugmentSpec: SSD data augmentation on the device; None = off
+            # the training loss: None / "reference" = the reference's _ssd_loss; "multibox" or an ops.LossSpec = the SSD
+            # paper's loss (per-image mining, smooth L1, every term over P).  ValueError for anything else
+            self.loss = ops.LossSpec.of(loss)
             # validation during the run (None = off): dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
             # max_dets=100, num_data=0, precision="bf16"); missing keys take these defaults.  After every `every`-th epoch
             # the validation split (its first num_data samples if > 0) is evaluated with metric="device".  An optional key
@@ -232,14 +235,24 @@ class SSDObjectDetectionModel:
 
     # ------------------------------------------------------------------ loss (A6)
     @staticmethod
-    def _ssd_loss(y_true, y_pred, heads=None):
+    def _ssd_loss(y_true, y_pred, heads=None, loss=None):
         """Returns (total loss tensor, info) where info maps the reference's three names to device scalars and
         carries the gradients w.r.t. (pred_box, pred_cls) under 'dloc' / 'dconf' -- or, with `heads` (the engine's
-        ops.HeadGradBuffers), as the compact per-level rows the heads' backward pass consumes ('heads')."""
+        ops.HeadGradBuffers), as the compact per-level rows the heads' backward pass consumes ('heads').  `loss`: None,
+        a kind name or an ops.LossSpec (None / "reference": the reference's loss)."""
         gt_cls, gt_box, gt_mask = y_true
         pred_box, pred_cls = y_pred
         assert gt_cls.shape[0] == gt_box.shape[0] == gt_mask.shape[0] == pred_box.shape[0] == pred_cls.shape[0]
-        if heads is not None:
+        spec = None if loss is None else ops.LossSpec.of(loss)
+        if spec is not None and spec.kind == "multibox":
+            if heads is not None:
+                out = ops.multibox_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads, spec.neg_pos_ratio,
+                                              spec.loc_weight)
+                dconf = dloc = None
+            else:
+                out, dconf, dloc = ops.multibox_loss(pred_cls, pred_box, gt_cls, gt_box, gt_mask, spec.neg_pos_ratio,
+                                                     spec.loc_weight)
+        elif heads is not None:
             out = ops.ssd_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads)
             dconf = dloc = None
         else:
@@ -309,7 +322,7 @@ class SSDObjectDetectionModel:
                 self._targets_event = None
             heads = eng.head_grad_buffers(pred_loc.shape[0]) if pred_conf.dtype == torch.bfloat16 else None
             _, info = self._ssd_loss((gt_cls[i:i + batch_step], gt_bbox[i:i + batch_step], gt_mask[i:i + batch_step]),
-                                     (pred_loc, pred_conf), heads)
+                                     (pred_loc, pred_conf), heads, getattr(cfg, "loss", None))
             if overlap:
                 post = gates = None
                 if fused_dp:

@@ -261,6 +261,89 @@ def ssd_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, grad_scale=1.0, ws=N
     return out
 
 
+class LossSpec:
+    """Which training loss a step uses.  kind "reference": the reference's _ssd_loss (ssd_loss / ssd_loss_heads; the other
+    two fields are not used).  kind "multibox": the SSD paper's loss (multibox_loss / multibox_loss_heads) with
+    `neg_pos_ratio` mined negatives per positive, per image, and the box term weighted by `loc_weight`."""
+    KINDS = ("reference", "multibox")
+
+    def __init__(self, kind="reference", neg_pos_ratio=3, loc_weight=1.0):
+        if kind not in self.KINDS:
+            raise ValueError("loss kind must be one of %s, not %r" % (", ".join(self.KINDS), kind))
+        if isinstance(neg_pos_ratio, bool) or not isinstance(neg_pos_ratio, (int, np.integer)) or neg_pos_ratio < 1:
+            raise ValueError("neg_pos_ratio must be an integer >= 1, not %r" % (neg_pos_ratio,))
+        if isinstance(loc_weight, bool) or not isinstance(loc_weight, (int, float, np.integer, np.floating)):
+            raise ValueError("loc_weight must be a number, not %r" % (loc_weight,))
+        if not (np.isfinite(loc_weight) and loc_weight >= 0):
+            raise ValueError("loc_weight must be finite and >= 0, not %r" % (loc_weight,))
+        self.kind = kind
+        self.neg_pos_ratio = int(neg_pos_ratio)
+        self.loc_weight = float(loc_weight)
+
+    @classmethod
+    def of(cls, loss):
+        """None / a kind name / a LossSpec -> LossSpec."""
+        if loss is None:
+            return cls()
+        if isinstance(loss, cls):
+            return loss
+        if isinstance(loss, str):
+            return cls(kind=loss)
+        raise ValueError("loss must be None, a kind name or an ops.LossSpec, not %r" % (loss,))
+
+    def __repr__(self):
+        return "LossSpec(kind=%r, neg_pos_ratio=%d, loc_weight=%r)" % (self.kind, self.neg_pos_ratio, self.loc_weight)
+
+
+_multibox_ws = MatchWorkspace()
+
+
+def _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight):
+    B, A, C = conf.shape
+    assert conf.is_cuda and conf.is_contiguous() and loc.is_contiguous()
+    assert loc.shape == (B, A, 4) and gt_loc.shape == (B, A, 4)
+    assert gt_cls.shape == (B, A) and gt_mask.shape == (B, A)
+    _dev(gt_cls, torch.int32); _dev(gt_loc, torch.float32); _dev(gt_mask, torch.uint8)
+    spec = LossSpec("multibox", neg_pos_ratio, loc_weight)         # ValueError for bad values, before anything is allocated
+    return B, A, C, spec
+
+
+def multibox_loss(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio=3, loc_weight=1.0, grad_scale=1.0, ws=None):
+    """ssd_multibox_loss_fwd_bwd: the SSD paper's loss (per-image hard-negative mining, smooth L1, every term over P) and its
+    gradient.  Arguments as ssd_loss.  Returns (out8 f32[8] device tensor, dconf, dloc); out8 = loc, pos, neg, total, P, N,
+    tau_min, status."""
+    L = _lib.lib()
+    B, A, C, spec = _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight)
+    assert conf.dtype == loc.dtype and conf.dtype in (torch.float32, torch.bfloat16)
+    dtype = 0 if conf.dtype == torch.float32 else 1
+    out = torch.empty((8,), dtype=torch.float32, device=conf.device)
+    dconf = torch.empty_like(conf)
+    dloc = torch.empty_like(loc)
+    wsobj = ws or _multibox_ws
+    wbuf = wsobj.get(L.ssd_multibox_loss_workspace_bytes(B, A, C), conf.device)
+    wsobj.clean_key = None                         # (a buffer shared with ssd_loss_heads no longer holds its zeroed words)
+    _lib.check(L.ssd_multibox_loss_fwd_bwd(_ptr(conf), _ptr(loc), dtype, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A, C,
+                                           spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out), _ptr(dconf),
+                                           _ptr(dloc), _ptr(wbuf), wbuf.numel(), _stream()))
+    return out, dconf, dloc
+
+
+def multibox_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, neg_pos_ratio=3, loc_weight=1.0, grad_scale=1.0, ws=None):
+    """ssd_multibox_loss_fwd_bwd_heads: the loss of multibox_loss with its gradient as compact per-level pixel rows in `hgb`
+    (HeadGradBuffers; bf16 only).  Returns out8 (device f32[8])."""
+    L = _lib.lib()
+    B, A, C, spec = _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight)
+    assert conf.dtype == loc.dtype == torch.bfloat16 and hgb.B == B
+    out = torch.empty((8,), dtype=torch.float32, device=conf.device)
+    wsobj = ws or _multibox_ws
+    wbuf = wsobj.get(L.ssd_multibox_loss_heads_workspace_bytes(B, A, C), conf.device)
+    wsobj.clean_key = None
+    _lib.check(L.ssd_multibox_loss_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A, C,
+                                                 spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out),
+                                                 ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream()))
+    return out
+
+
 def head_layers(x, w_tap, dx, dw, dbias, cout, relu_bits=None, relu_src=None):
     """ssd_head_layers from per-level lists of tensors (x bf16 [B,H,W,Cin]; w_tap bf16 [3,3,Cin,npad]; dx like x; dw f32
     [cout,3,3,Cin]; dbias f32 [cout] or None).  Returns (struct, keep-alive list)."""

@@ -78,6 +78,23 @@ def val_from_config(config):
     return val
 
 
+def loss_from_config(config):
+    """`model: train: loss: {kind, neg_pos_ratio, loc_weight}` (no reference counterpart) -> ops.LossSpec, or None when the
+    section is absent: the default run trains with the reference's loss.  kind "multibox" is the SSD paper's loss;
+    ValueError for an unknown key, an unknown kind or bad values."""
+    section = ((config.get("model") or {}).get("train") or {}).get("loss")
+    if section is None:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError("model.train.loss must be a mapping, not %r" % (section,))
+    unknown = set(section) - {"kind", "neg_pos_ratio", "loc_weight"}
+    if unknown:
+        raise ValueError("unknown model.train.loss keys: %s" % sorted(unknown))
+    from ..ops import LossSpec
+    return LossSpec(kind=section.get("kind", "reference"), neg_pos_ratio=section.get("neg_pos_ratio", 3),
+                    loc_weight=section.get("loc_weight", 1.0))
+
+
 def _make_optimizer(section, schedule):
     from .. import optimizers
     kinds = {"adam": optimizers.Adam, "sgd": optimizers.SGD}
@@ -146,7 +163,7 @@ def train(config):
 
     fields = {name: cfg_get(config, path) for name, path in TRAIN_CONFIG_KEYS.items()}
     fields.update(optimizer=optimizer, warmup_optimizer=warmup_optimizer, start_epoch=start_epoch,
-                  augment=augment_from_config(config), val=val_from_config(config))
+                  augment=augment_from_config(config), val=val_from_config(config), loss=loss_from_config(config))
     model.train(data_loader=data, cfg=SSDObjectDetectionModel.TrainConfig(**fields))
     model.save(os.path.join(model.get_log_dir(), model_cfg["save"]))      # rank 0 writes; the others wait
     return model
