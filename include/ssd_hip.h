@@ -703,6 +703,19 @@ int ssd_adam_step(float* param, const float* grad, float* m, float* v, void* par
                   float beta2, float eps, void* stream);
 int ssd_sgd_step(float* param, const float* grad, void* param_bf16, long long n, const int32_t* block_tensor,
                  const float* scale, float grad_scale, float lr, void* stream);
+/* Momentum SGD with an optional per-tensor L2 term (no reference counterpart beyond tools/train.py:44-45's name == "sgd":
+ * Keras SGD(momentum, nesterov), which is also Caffe SSD's solver form -- the learning rate is folded into the velocity).
+ * Per element, in fp32, in this order, t = block_tensor[block]:
+ *   sc = grad_scale * (scale ? scale[t] : 1)
+ *   ge = g * sc;   if (decay) ge = ge + decay[t] * p          decay fp32[ntensors]: L2 coefficient per tensor, NULL = none
+ *   v' = momentum * v - lr * ge
+ *   p' = nesterov ? p + (momentum * v' - lr * ge) : p + v'
+ * velocity is read and written; param_bf16 (may be NULL) receives the bf16 copy of p'.  One pass, no reductions; nothing
+ * outside [0, n) is touched.  SSD_ERR_VALUE (nothing launched): param, grad or velocity NULL; n <= 0 or not a multiple of
+ * ssd_opt_block_elems(); scale or decay without block_tensor; momentum outside [0, 1); nesterov not 0 or 1. */
+int ssd_sgd_momentum_step(float* param, const float* grad, float* velocity, void* param_bf16, long long n,
+                          const int32_t* block_tensor, const float* scale, const float* decay, float grad_scale, float lr,
+                          float momentum, int nesterov, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dispatch queries (no reference counterpart; testing / reports): which kernel a convolution call with this shape

@@ -148,6 +148,8 @@ _SIGNATURES = {
     "ssd_grad_accumulate": (ctypes.c_int, [VP, VP, ctypes.c_longlong, VP, VP, ctypes.c_int, VP]),
     "ssd_adam_step": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_longlong, VP, VP] + [ctypes.c_float] * 5 + [VP]),
     "ssd_sgd_step": (ctypes.c_int, [VP, VP, VP, ctypes.c_longlong, VP, VP, ctypes.c_float, ctypes.c_float, VP]),
+    "ssd_sgd_momentum_step": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_longlong, VP, VP, VP] + [ctypes.c_float] * 3
+                              + [ctypes.c_int, VP]),
     "ssd_dev_knob": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "ssd_dev_mfma_calibration_workgroups": (ctypes.c_int, []),
     "ssd_dev_mfma_calibration_flops": (ctypes.c_double, [ctypes.c_int]),

@@ -4,6 +4,8 @@
 //   tf.clip_by_norm(g, 0.01)            models/ssd_model.py:249   g * clip / max(||g||_2, clip)
 //   mean over micro-batches / ranks     :251-256                  (grad_scale = 1/count)
 //   Adam.apply_gradients                :258-260; hyper-parameters tools/train.py:42-51, config/default.yml:20-24
+//   SGD (name == "sgd")                  tools/train.py:44-45: k_sgd; with momentum / an L2 term (the SSD paper's recipe, no
+//                                        reference counterpart): k_sgd_momentum, velocity in one more flat fp32 buffer
 // Parameters, gradients and both Adam moments live in flat fp32 buffers; every tensor starts on a
 // multiple of OPT_BLOCK elements, so each block of OPT_BLOCK elements belongs to exactly one tensor
 // (block -> tensor id table).  All reductions are fixed-order (deterministic).
@@ -136,6 +138,40 @@ __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float*
                                                            (unsigned)f2bf_bits(pv.z) | ((unsigned)f2bf_bits(pv.w) << 16));
 }
 
+// Momentum SGD, Keras SGD(momentum, nesterov) = Caffe's form (the learning rate is folded into the velocity), with an
+// optional per-tensor L2 term:  ge = g * sc (+ decay[t] * p);  v' = mom * v - lr * ge;
+// p' = nesterov ? p + (mom * v' - lr * ge) : p + v'.  One pass, 22 bytes per element; also refreshes the bf16 copy.
+__global__ __launch_bounds__(256) void k_sgd_momentum(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
+                                                      unsigned short* __restrict__ p_bf16, long long n,
+                                                      const int* __restrict__ block_tensor, const float* __restrict__ scale,
+                                                      const float* __restrict__ decay, float grad_scale, float lr, float mom,
+                                                      int nesterov) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const int t = block_tensor ? block_tensor[blockIdx.x] : 0;
+    const float sc = grad_scale * (scale ? scale[t] : 1.f);
+    const float wd = decay ? decay[t] : 0.f;
+    const float4 gv = *reinterpret_cast<const float4*>(g + i);
+    float4 pv = *reinterpret_cast<float4*>(p + i);
+    float4 vv = *reinterpret_cast<float4*>(v + i);
+    const float gs[4] = {gv.x * sc, gv.y * sc, gv.z * sc, gv.w * sc};
+    float* pp = reinterpret_cast<float*>(&pv);
+    float* vq = reinterpret_cast<float*>(&vv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float ge = gs[k];
+        if (decay) ge = ge + wd * pp[k];
+        const float step = lr * ge;
+        vq[k] = mom * vq[k] - step;
+        pp[k] = nesterov ? pp[k] + (mom * vq[k] - step) : pp[k] + vq[k];
+    }
+    *reinterpret_cast<float4*>(p + i) = pv;
+    *reinterpret_cast<float4*>(v + i) = vv;
+    if (p_bf16)
+        *reinterpret_cast<uint2*>(p_bf16 + i) = make_uint2((unsigned)f2bf_bits(pp[0]) | ((unsigned)f2bf_bits(pp[1]) << 16),
+                                                           (unsigned)f2bf_bits(pp[2]) | ((unsigned)f2bf_bits(pp[3]) << 16));
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,6 +218,17 @@ int ssd_sgd_step(float* param, const float* grad, void* param_bf16, long long n,
     if (!param || !grad || n <= 0 || n % OPT_BLOCK || (scale && !block_tensor)) return SSD_ERR_VALUE;
     hipLaunchKernelGGL(k_sgd, dim3((unsigned)(n / OPT_BLOCK)), dim3(256), 0, (hipStream_t)stream, param, grad,
                        static_cast<unsigned short*>(param_bf16), n, block_tensor, scale, grad_scale, lr);
+    return ssd_launch_status();
+}
+
+int ssd_sgd_momentum_step(float* param, const float* grad, float* velocity, void* param_bf16, long long n,
+                          const int32_t* block_tensor, const float* scale, const float* decay, float grad_scale, float lr,
+                          float momentum, int nesterov, void* stream) {
+    if (!param || !grad || !velocity || n <= 0 || n % OPT_BLOCK || ((scale || decay) && !block_tensor)) return SSD_ERR_VALUE;
+    if (!(momentum >= 0.f && momentum < 1.f) || (nesterov != 0 && nesterov != 1)) return SSD_ERR_VALUE;
+    hipLaunchKernelGGL(k_sgd_momentum, dim3((unsigned)(n / OPT_BLOCK)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                       velocity, static_cast<unsigned short*>(param_bf16), n, block_tensor, scale, decay, grad_scale, lr,
+                       momentum, nesterov);
     return ssd_launch_status();
 }
 

@@ -166,6 +166,7 @@ class SSDEngine:
         self._side = None
         self.overlap_heads = os.environ.get("SSD_OVERLAP_HEADS", "1") != "0" and self.device.type == "cuda"
         self.step_count = 0
+        self.slots = "adam"                    # what adam_m holds: Adam's first moment, or "sgd_momentum": the velocity
         self.skip_fullres = os.environ.get("SSD_SKIP_FULLRES", "1") == "1"   # pooled convs store the pooled map only
         # schedule switches of the host program (read once, here): third stream for the small heads of the forward pass; dense
         # head path only: the two large heads' backward on the side stream, their gradient packing there too
@@ -675,6 +676,8 @@ class SSDEngine:
         fused_adam = dict(lr, beta1, beta2, eps, clip): clip_by_norm + Adam + weight copies run per bucket of tensors
         (opt_buckets) on the side stream as soon as the bucket's gradients exist and the last data gradient that reads
         its transposed weights has been enqueued -- the optimizer disappears under the rest of the backward pass.
+        With kind="sgd_momentum" the dict is dict(kind, lr, momentum, nesterov, decay, clip) and the bucket's update is
+        sgd_range() in the same places; without the key (or kind="adam") it is Adam's, as above.
 
         The data-gradient chain (the critical path) runs on the current stream, every weight gradient on the side
         stream as soon as its input gradient exists: the split reductions and round tails of one overlap the MFMA
@@ -702,7 +705,15 @@ class SSDEngine:
             self.step_count += 1
             t = self.step_count
             hp = fused_adam
-            lr_t = hp["lr"] * math.sqrt(1.0 - hp["beta2"] ** t) / (1.0 - hp["beta1"] ** t)
+            kind = hp.get("kind", "adam")
+            if kind == "adam":
+                lr_t = hp["lr"] * math.sqrt(1.0 - hp["beta2"] ** t) / (1.0 - hp["beta1"] ** t)
+                opt_range = lambda t0, t1: self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
+            elif kind == "sgd_momentum":
+                opt_range = lambda t0, t1: self.sgd_range(t0, t1, hp["lr"], hp["momentum"], hp["nesterov"], hp["decay"],
+                                                          hp["clip"])
+            else:
+                raise ValueError("unknown fused optimizer kind %r" % (kind,))
             opt_at = {node: (t0, t1) for t0, t1, node in self.opt_buckets()}
 
         def opt_bucket(node):
@@ -724,7 +735,7 @@ class SSDEngine:
                 def run(ws):
                     for e in readers:
                         torch.cuda.current_stream().wait_event(e)
-                    self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
+                    opt_range(t0, t1)
                 on_side(run, [], join=True)
 
         def on_side(fn, tensors, join=False, now=False):
@@ -1013,7 +1024,7 @@ class SSDEngine:
             main.wait_event(ev)
         for t0, t1, ev in deferred:
             main.wait_event(ev)
-            self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
+            opt_range(t0, t1)
         if side is not None:
             main.wait_stream(side)
 
@@ -1075,6 +1086,41 @@ class SSDEngine:
                                         ops._ptr(self.adam_v[sl]), ops._ptr(self.param_bf16[sl]), n, ops._ptr(bt),
                                         ops._ptr(self.clip_scale[t0:]) if clip is not None else None, float(grad_scale),
                                         float(lr_t), float(beta1), float(beta2), float(eps), ops._stream()))
+        self.slots = "adam"
+        self.refresh_weights(tensors=(t0, t1))
+
+    def decay_table(self, weight_decay, decay_bias=False):
+        """Device fp32 [len(tensors)]: the L2 coefficient of every tensor for ssd_sgd_momentum_step -- weight_decay on the
+        filters (names ending in "kernel"), on the biases only with decay_bias (Caffe SSD: decay_mult 0), else 0.
+        Cached per (weight_decay, decay_bias)."""
+        key = (float(weight_decay), bool(decay_bias))
+        if not hasattr(self, "_decay_tables"):
+            self._decay_tables = {}
+        tab = self._decay_tables.get(key)
+        if tab is None:
+            host = [key[0] if (t.name.endswith("kernel") or key[1]) else 0.0 for t in self.tensors]
+            tab = torch.tensor(host, dtype=torch.float32).to(self.device)
+            self._decay_tables[key] = tab
+        return tab
+
+    def sgd_range(self, t0, t1, lr, momentum, nesterov, decay, clip, grad_scale=1.0):
+        """clip_by_norm + momentum SGD + bf16 / transposed copies for parameter tensors t0..t1-1 on the current stream; the
+        velocity lives in adam_m.  decay: decay_table() or None.  Per tensor the arithmetic is that of clip_scales() +
+        sgd_momentum() over the whole flat buffer, bit for bit.
+        clip=None: the gradient is already clipped (and summed over ranks): only grad_scale (1 / world) applies."""
+        b0, tbo, bt = self._range_table(t0, t1)
+        start, n = b0 * self.block, bt.numel() * self.block
+        sl = slice(start, start + n)
+        if clip is not None:
+            _lib.check(self.L.ssd_grad_clip_scales(ops._ptr(self.grad[sl]), n, ops._ptr(tbo), t1 - t0, float(clip),
+                                                   ops._ptr(self.sq_partial[b0:]), ops._ptr(self.clip_scale[t0:]),
+                                                   ops._ptr(self.grad_norms[t0:]), ops._stream()))
+        _lib.check(self.L.ssd_sgd_momentum_step(ops._ptr(self.param[sl]), ops._ptr(self.grad[sl]), ops._ptr(self.adam_m[sl]),
+                                                ops._ptr(self.param_bf16[sl]), n, ops._ptr(bt),
+                                                ops._ptr(self.clip_scale[t0:]) if clip is not None else None,
+                                                ops._ptr(decay[t0:]) if decay is not None else None, float(grad_scale),
+                                                float(lr), float(momentum), 1 if nesterov else 0, ops._stream()))
+        self.slots = "sgd_momentum"
         self.refresh_weights(tensors=(t0, t1))
 
     def clip_range_in_place(self, t0, t1, clip=0.01):
@@ -1103,6 +1149,19 @@ class SSDEngine:
                                         ops._ptr(self.param_bf16), self.n_flat, ops._ptr(self.block_tensor),
                                         ops._ptr(self.clip_scale) if use_clip_scale else None, float(grad_scale),
                                         float(lr_t), float(beta1), float(beta2), float(eps), ops._stream()))
+        self.slots = "adam"
+        self.refresh_weights()
+
+    def sgd_momentum(self, lr, grad, grad_scale=1.0, use_clip_scale=False, momentum=0.9, nesterov=False, decay=None):
+        """Momentum SGD over the whole flat buffer (ssd_sgd_momentum_step); the velocity lives in adam_m, adam_v is untouched.
+        decay: decay_table() or None."""
+        self.step_count += 1
+        _lib.check(self.L.ssd_sgd_momentum_step(ops._ptr(self.param), ops._ptr(grad), ops._ptr(self.adam_m),
+                                                ops._ptr(self.param_bf16), self.n_flat, ops._ptr(self.block_tensor),
+                                                ops._ptr(self.clip_scale) if use_clip_scale else None,
+                                                ops._ptr(decay) if decay is not None else None, float(grad_scale), float(lr),
+                                                float(momentum), 1 if nesterov else 0, ops._stream()))
+        self.slots = "sgd_momentum"
         self.refresh_weights()
 
     def sgd(self, lr, grad, grad_scale=1.0, use_clip_scale=False):
@@ -1118,7 +1177,7 @@ class SSDEngine:
     def state_dict(self):
         return dict(param=self.param.cpu(), adam_m=self.adam_m.cpu(), adam_v=self.adam_v.cpu(), step=self.step_count,
                     names=[t.name for t in self.tensors], shapes=[t.shape for t in self.tensors],
-                    offsets=[t.offset for t in self.tensors], layout_version=self.LAYOUT_VERSION)
+                    offsets=[t.offset for t in self.tensors], layout_version=self.LAYOUT_VERSION, slots=self.slots)
 
     def load_state_dict(self, sd):
         """The flat buffers are only meaningful together with the layout they were saved under: names, shapes and offsets of
@@ -1132,8 +1191,12 @@ class SSDEngine:
                              "(version %d, %d variables, %d elements)%s" % (
                                  sd.get("layout_version", 1), len(theirs[0]), sd["param"].numel(), self.LAYOUT_VERSION,
                                  len(mine[0]), self.n_flat, "; e.g. " + ", ".join(bad) if bad else ""))
+        slots = sd.get("slots", "adam")                # what adam_m holds; checkpoints from before the key: Adam's moments
+        if slots not in ("adam", "sgd_momentum"):
+            raise ValueError("checkpoint optimizer slots %r: expected 'adam' or 'sgd_momentum'" % (slots,))
         self.param.copy_(sd["param"])
         self.adam_m.copy_(sd["adam_m"])
         self.adam_v.copy_(sd["adam_v"])
         self.step_count = int(sd["step"])
+        self.slots = slots
         self.refresh_weights(cast=True)

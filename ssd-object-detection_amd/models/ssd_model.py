@@ -26,7 +26,7 @@ from .. import optimizers as _opt
 from ..utils.scalar_log import ScalarLog
 
 logger = logging.getLogger(__name__)
-_RESTORED = object()                            # _slot_owner marker: Adam moments were loaded from a checkpoint
+_RESTORED = object()                            # _slot_owner marker: the optimizer slots were loaded from a checkpoint
 
 
 class _RawList(list):
@@ -38,7 +38,7 @@ class SSDObjectDetectionModel:
     class TrainConfig:
         def __init__(self, epoch, batch_size, optimizer, warmup=True, warmup_optimizer=None, warmup_step=1000,
                      visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0, augment=None,
-                     val=None, loss=None):
+                     val=None, loss=None, clip=0.01):
             if warmup_optimizer is None:
                 warmup_optimizer = _opt.Adam(_opt.PolynomialDecay(1e-6, 1000, 0.001))
             self.epoch = epoch
@@ -55,6 +55,11 @@ class SSDObjectDetectionModel:
             # the training loss: None / "reference" = the reference's _ssd_loss; "multibox" or an ops.LossSpec = the SSD
             # paper's loss (per-image mining, smooth L1, every term over P).  ValueError for anything else
             self.loss = ops.LossSpec.of(loss)
+            # per-tensor clip norm of the gradients (tf.clip_by_norm(g, clip), reference :249); None or 0: no clipping (the
+            # clip kernels run with clip = 0: every scale is 1, the norms are still written)
+            if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip >= 0):
+                raise ValueError("clip must be a number >= 0 or None, not %r" % (clip,))
+            self.clip = float(clip) if clip else 0.0
             # validation during the run (None = off): dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
             # max_dets=100, num_data=0, precision="bf16"); missing keys take these defaults.  After every `every`-th epoch
             # the validation split (its first num_data samples if > 0) is evaluated with metric="device".  An optional key
@@ -297,20 +302,31 @@ class SSDObjectDetectionModel:
         world = torch.distributed.get_world_size() if self.distributed else 1
         single = world == 1 and batch_step >= batch_size
         overlap = world > 1 and batch_step >= batch_size           # one micro-batch per rank: bucketed, overlapped reduce
+        clip = float(getattr(cfg, "clip", 0.01))       # tf.clip_by_norm(x, 0.01), reference :249; 0.0 = off
+        self._clip = clip
         if overlap and self._reducer is None:
             blocks = [t.nblocks for t in eng.tensors]
             self._reducer = GradReducer(eng.grad, [t.block0 * eng.block for t in eng.tensors], blocks, eng.block,
-                                        eng.clip_range_in_place)
-        fused = single and isinstance(ssd_optimizer, _opt.Adam) and self.fused_optimizer
-        fused_dp = overlap and isinstance(ssd_optimizer, _opt.Adam) and self.fused_optimizer
+                                        lambda t0, t1: eng.clip_range_in_place(t0, t1, self._clip))
+        momentum = isinstance(ssd_optimizer, _opt.SGD) and ssd_optimizer.uses_slots     # the momentum / decay kernel
+        decay = None
+        if momentum and ssd_optimizer.weight_decay > 0.0:
+            decay = eng.decay_table(ssd_optimizer.weight_decay, ssd_optimizer.decay_bias)
+        per_bucket = (isinstance(ssd_optimizer, _opt.Adam) or momentum) and self.fused_optimizer
+        fused = single and per_bucket
+        fused_dp = overlap and per_bucket
         if fused_dp:
             self._adopt_slots(ssd_optimizer)
         if fused:                                      # the optimizer runs per bucket inside the backward pass
             self._adopt_slots(ssd_optimizer)
             eng.step_count = ssd_optimizer.iterations
             lr = ssd_optimizer.lr()
-            fused_adam = dict(lr=lr, beta1=ssd_optimizer.beta_1, beta2=ssd_optimizer.beta_2,
-                              eps=ssd_optimizer.epsilon, clip=0.01)          # tf.clip_by_norm(x, 0.01), reference :249
+            if momentum:
+                fused_adam = dict(kind="sgd_momentum", lr=lr, momentum=ssd_optimizer.momentum,
+                                  nesterov=ssd_optimizer.nesterov, decay=decay, clip=clip)
+            else:
+                fused_adam = dict(lr=lr, beta1=ssd_optimizer.beta_1, beta2=ssd_optimizer.beta_2,
+                                  eps=ssd_optimizer.epsilon, clip=clip)
         for i in range(0, batch_size, batch_step):
             if image.dtype == torch.bfloat16:          # already prepared on the device (make_batch_raw)
                 x = image[i:i + batch_step]
@@ -332,9 +348,13 @@ class SSDObjectDetectionModel:
                     eng.step_count = ssd_optimizer.iterations + 1
                     t = eng.step_count
                     lr = ssd_optimizer.lr()
-                    b1, b2 = ssd_optimizer.beta_1, ssd_optimizer.beta_2
-                    lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
-                    post = lambda t0, t1: eng.adam_range(t0, t1, lr_t, b1, b2, ssd_optimizer.epsilon, None, 1.0 / world)
+                    if momentum:
+                        post = lambda t0, t1: eng.sgd_range(t0, t1, lr, ssd_optimizer.momentum, ssd_optimizer.nesterov,
+                                                            decay, None, 1.0 / world)
+                    else:
+                        b1, b2 = ssd_optimizer.beta_1, ssd_optimizer.beta_2
+                        lr_t = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+                        post = lambda t0, t1: eng.adam_range(t0, t1, lr_t, b1, b2, ssd_optimizer.epsilon, None, 1.0 / world)
                     gates = eng.bucket_gates(self._reducer.buckets)
                 self._reducer.begin(post, gates)
                 eng.backward(info["dloc"], info["dconf"], on_ready=self._reducer.tensor_ready, heads=info["heads"],
@@ -344,7 +364,7 @@ class SSDObjectDetectionModel:
                 eng.backward(info["dloc"], info["dconf"], fused_adam=fused_adam, heads=info["heads"])
             else:
                 eng.backward(info["dloc"], info["dconf"], heads=info["heads"])
-                eng.clip_scales(0.01)                  # tf.clip_by_norm(x, 0.01) per tensor, reference :249
+                eng.clip_scales(clip)                  # tf.clip_by_norm(x, 0.01) per tensor, reference :249
                 if not single:
                     eng.accumulate_clipped(first=(n_micro == 0))
             n_micro += 1
@@ -362,7 +382,10 @@ class SSDObjectDetectionModel:
             if world > 1:
                 torch.distributed.all_reduce(grad)     # RCCL over xGMI: sum of the ranks' clipped gradients
             gscale = 1.0 / (n_micro * world)           # reference :256
-        if isinstance(ssd_optimizer, _opt.SGD):
+        if momentum:
+            eng.step_count = ssd_optimizer.iterations
+            eng.sgd_momentum(lr, grad, gscale, use_clip, ssd_optimizer.momentum, ssd_optimizer.nesterov, decay)
+        elif isinstance(ssd_optimizer, _opt.SGD):
             eng.sgd(lr, grad, gscale, use_clip)
         else:
             eng.step_count = ssd_optimizer.iterations
@@ -372,8 +395,16 @@ class SSDObjectDetectionModel:
 
     def _adopt_slots(self, ssd_optimizer):
         eng = self._engine
-        if self._slot_owner is _RESTORED:             # moments came from a checkpoint: the first optimizer adopts them
+        if self._slot_owner is _RESTORED:             # slots came from a checkpoint: the first optimizer adopts them ...
             self._slot_owner = ssd_optimizer
+            plain = isinstance(ssd_optimizer, _opt.SGD) and not ssd_optimizer.uses_slots       # reads no slot
+            kind = "sgd_momentum" if isinstance(ssd_optimizer, _opt.SGD) else "adam"
+            # ... unless they are another optimizer's: Adam moments are not a velocity.  (All-zero slots -- a model that was
+            # never trained, or only by plain SGD -- are nobody's: no warning.  One host read, at the first step after load)
+            if not plain and eng.slots != kind and bool(eng.adam_m.any() or eng.adam_v.any()):
+                logger.warning("checkpoint holds %s slots, the optimizer is %s: starting from zero slots", eng.slots, kind)
+                eng.adam_m.zero_()
+                eng.adam_v.zero_()
         elif self._slot_owner is not ssd_optimizer:   # Keras keeps separate slots per optimizer (warm-up vs train)
             eng.adam_m.zero_()
             eng.adam_v.zero_()

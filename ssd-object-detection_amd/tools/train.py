@@ -95,12 +95,54 @@ def loss_from_config(config):
                     loc_weight=section.get("loc_weight", 1.0))
 
 
+def schedule_from_config(section):
+    """`model: train: lr:` -> a learning-rate schedule.  `kind: exponential` (the default when the key is absent: the
+    reference's schema) reads `initial`, `decay_step`, `decay_rate`; `kind: piecewise` (no reference counterpart: the SSD
+    paper's step schedule) reads `boundaries` and `values`, Keras PiecewiseConstantDecay.  ValueError for an unknown kind or
+    missing keys."""
+    from .. import optimizers
+    if not isinstance(section, dict):
+        raise ValueError("model.train.lr must be a mapping, not %r" % (section,))
+    kind = section.get("kind", "exponential")
+    need = {"exponential": ("initial", "decay_step", "decay_rate"), "piecewise": ("boundaries", "values")}.get(kind)
+    if need is None:
+        raise ValueError("model.train.lr.kind must be 'exponential' or 'piecewise', not %r" % (kind,))
+    missing = [k for k in need if k not in section]
+    if missing:
+        raise ValueError("model.train.lr (kind %s) lacks %s" % (kind, missing))
+    if kind == "piecewise":
+        return optimizers.PiecewiseConstantDecay(section["boundaries"], section["values"])
+    return optimizers.ExponentialDecay(section["initial"], section["decay_step"], section["decay_rate"])
+
+
+def clip_from_config(config):
+    """`model: train: clip_norm` (no reference counterpart) -> TrainConfig's clip: the per-tensor clip norm, `null` or 0 for no
+    clipping; absent = the reference's 0.01.  ValueError for anything but a non-negative number or null."""
+    section = (config.get("model") or {}).get("train") or {}
+    if "clip_norm" not in section:
+        return 0.01
+    clip = section["clip_norm"]
+    if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip >= 0):
+        raise ValueError("model.train.clip_norm must be a number >= 0 or null, not %r" % (clip,))
+    return clip
+
+
+OPTIMIZER_KEYS = {"Adam": {"name", "beta_1", "beta_2", "epsilon"},
+                  "SGD": {"name", "momentum", "nesterov", "weight_decay", "decay_bias"}}
+
+
 def _make_optimizer(section, schedule):
+    """`optimizer: {name, ...}`: Adam reads beta_1, beta_2, epsilon; SGD reads momentum, nesterov, weight_decay, decay_bias
+    (optimizers.SGD raises ValueError for bad values)."""
     from .. import optimizers
     kinds = {"adam": optimizers.Adam, "sgd": optimizers.SGD}
     kind = kinds.get(section["name"].lower())
     if kind is None:
         raise ValueError                     # reference tools/train.py:47,53
+    # the optimizers take **_ as Keras' do: a key they do not read (a misspelt `momentun`) would vanish without a word
+    unread = sorted(set(section) - OPTIMIZER_KEYS[kind.__name__])
+    if unread:
+        logger.warning("optimizer %s does not read the config keys %s: ignored", kind.__name__, unread)
     return kind(schedule, **section)
 
 
@@ -139,8 +181,7 @@ def train(config):
     model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1)
 
     lr, wlr = model_cfg["train"]["lr"], model_cfg["warmup"]["lr"]
-    optimizer = _make_optimizer(model_cfg["train"]["optimizer"],
-                                optimizers.ExponentialDecay(lr["initial"], lr["decay_step"], lr["decay_rate"]))
+    optimizer = _make_optimizer(model_cfg["train"]["optimizer"], schedule_from_config(lr))
     warmup_optimizer = _make_optimizer(model_cfg["warmup"]["optimizer"],
                                        optimizers.PolynomialDecay(wlr["start"], model_cfg["warmup"]["step"], wlr["end"]))
 
@@ -163,7 +204,8 @@ def train(config):
 
     fields = {name: cfg_get(config, path) for name, path in TRAIN_CONFIG_KEYS.items()}
     fields.update(optimizer=optimizer, warmup_optimizer=warmup_optimizer, start_epoch=start_epoch,
-                  augment=augment_from_config(config), val=val_from_config(config), loss=loss_from_config(config))
+                  augment=augment_from_config(config), val=val_from_config(config), loss=loss_from_config(config),
+                  clip=clip_from_config(config))
     model.train(data_loader=data, cfg=SSDObjectDetectionModel.TrainConfig(**fields))
     model.save(os.path.join(model.get_log_dir(), model_cfg["save"]))      # rank 0 writes; the others wait
     return model
