@@ -718,6 +718,25 @@ int ssd_sgd_momentum_step(float* param, const float* grad, float* velocity, void
                           float momentum, int nesterov, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * L2 normalisation over the channels with a learned per-channel scale (no reference counterpart: the SSD paper's layer on
+ * the 38x38 map, section 3.1 / Caffe SSD's Normalize).  x, y, dy, dx: bf16 [P][C]; scale, dscale: fp32 [C]; rnorm: fp32 [P].
+ * All arithmetic in fp32, per pixel p:
+ *   r_p = 1 / sqrt(sum_k x_pk^2 + eps)      xh_pc = x_pc r_p      y_pc = bf16(scale_c xh_pc)
+ *   t_pc = scale_c dy_pc      D_p = sum_k t_pk xh_pk      dx_pc = bf16(r_p (t_pc - xh_pc D_p) [+ dx_pc if accumulate])
+ *   dscale_c = sum_p dy_pc xh_pc            (written, not accumulated; fixed summation order: bitwise reproducible)
+ * ssd_l2norm_fwd writes r_p to rnorm where it is not NULL.  ssd_l2norm_bwd reads r_p from rnorm, or recomputes it from x
+ * where rnorm is NULL (the same bits); xh is always rebuilt from x, never taken from y.  ws: ssd_l2norm_ws_bytes(P, C) bytes
+ * of scratch without initial-content requirements.  y may not alias x; dx may alias neither x nor dy.
+ * Shapes: C % 128 == 0, 128 <= C <= 1024, P >= 1; any other C: SSD_ERR_UNSUPPORTED (ssd_l2norm_ws_bytes: 0).  SSD_ERR_VALUE: a
+ * NULL required pointer (everything but rnorm), an aliased output, P < 1, eps < 0 or a workspace that is too small.  Nothing is
+ * launched on either error.
+ * ---------------------------------------------------------------------------------------- */
+size_t ssd_l2norm_ws_bytes(long long P, int C);
+int ssd_l2norm_fwd(const void* x, const float* scale, void* y, float* rnorm, long long P, int C, float eps, void* stream);
+int ssd_l2norm_bwd(const void* dy, const void* x, const float* scale, const float* rnorm, void* dx, int accumulate,
+                   float* dscale, void* ws, size_t ws_bytes, long long P, int C, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dispatch queries (no reference counterpart; testing / reports): which kernel a convolution call with this shape
  * resolves to.  They run the library's own dispatch code with launching switched off, so the answer cannot drift from
  * what the call does.  Return: a plan word >= 0 (kernel id in SSD_PLAN_KERNEL_MASK, path flags above it) or a negative

@@ -150,6 +150,10 @@ _SIGNATURES = {
     "ssd_sgd_step": (ctypes.c_int, [VP, VP, VP, ctypes.c_longlong, VP, VP, ctypes.c_float, ctypes.c_float, VP]),
     "ssd_sgd_momentum_step": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_longlong, VP, VP, VP] + [ctypes.c_float] * 3
                               + [ctypes.c_int, VP]),
+    "ssd_l2norm_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
+    "ssd_l2norm_fwd": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_longlong, ctypes.c_int, ctypes.c_float, VP]),
+    "ssd_l2norm_bwd": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int, VP, VP, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int,
+                                      ctypes.c_float, VP]),
     "ssd_dev_knob": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "ssd_dev_mfma_calibration_workgroups": (ctypes.c_int, []),
     "ssd_dev_mfma_calibration_flops": (ctypes.c_double, [ctypes.c_int]),

@@ -144,8 +144,12 @@ class FusedView:
 
 class SSDEngine:
     def __init__(self, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, device="cuda",
-                 seed=0, sparse_heads=None):
+                 seed=0, sparse_heads=None, l2norm=None):
+        """l2norm: the SSD paper's L2 normalisation of feature map 0 in front of its head (ops.L2NormSpec.of: None / False = off,
+        True, an initial scale, a dict or a spec).  Off, the engine plans the same tensors and launches what it did without
+        the option; on, one more variable "l2norm0/scale" follows every other one."""
         self.L = _lib.lib()
+        self.l2norm = ops.L2NormSpec.of(l2norm)
         self.classes, self.in_size, self.device = classes, in_size, torch.device(device)
         self.trunk, self.num_priors = list(trunk), tuple(num_priors)
         self.block = self.L.ssd_opt_block_elems()
@@ -163,6 +167,7 @@ class SSDEngine:
         self._ws = ops.MatchWorkspace()
         self._ws_hz = ops.MatchWorkspace()     # Z of the sparse head data gradient
         self._ws_hw = ops.MatchWorkspace()     # slabs of the sparse head weight gradient
+        self._ws_l2n = ops.MatchWorkspace()    # partial sums of the l2norm scale's gradient
         self._side = None
         self.overlap_heads = os.environ.get("SSD_OVERLAP_HEADS", "1") != "0" and self.device.type == "cuda"
         self.step_count = 0
@@ -263,6 +268,14 @@ class SSDEngine:
             lb, cb = add("head%d/loc_bias" % lvl, (nl,), True), add("head%d/conf_bias" % lvl, (nc,))
             self.head_params.append((FusedView("head%d/kernel" % lvl, (nl + nc, 3, 3, c), (lk, ck)),
                                      FusedView("head%d/bias" % lvl, (nl + nc,), (lb, cb))))
+        # the scale of the L2 normalisation in front of head 0: behind every other tensor, so those keep index, offset and
+        # block; opt_buckets() then has it in the heads' bucket (which ends at len(self.tensors))
+        self.l2norm_scale = None
+        if self.l2norm is not None:
+            c0 = self.fm[0][2]
+            if c0 % 128 or not 128 <= c0 <= 1024:
+                raise ValueError("l2norm: feature map 0 has %d channels; the kernels serve multiples of 128 in 128 .. 1024" % c0)
+            self.l2norm_scale = add("l2norm0/scale", (c0,))
         self.n_flat = off
         self.n_params = sum(t.numel for t in self.tensors)
 
@@ -310,7 +323,7 @@ class SSDEngine:
 
     def init_params(self, seed=0):
         """Keras defaults: glorot_uniform kernels, zero biases (the reference's VGG part loads ImageNet weights
-        from the network, which is unavailable offline -- SURVEY.md F9)."""
+        from the network, which is unavailable offline -- SURVEY.md F9); the l2norm scale, where planned, at its spec's init."""
         rng = np.random.default_rng(seed)
         host = np.zeros(self.n_flat, np.float32)
         for t in self.tensors:
@@ -327,6 +340,9 @@ class SSDEngine:
                 if real_cin != cin:
                     w[..., real_cin:] = 0.0
             host[t.offset:t.offset + t.numel] = w.astype(np.float32).reshape(-1)
+        if self.l2norm_scale is not None:
+            t = self.l2norm_scale
+            host[t.offset:t.offset + t.numel] = self.l2norm.init
         self.param.copy_(torch.from_numpy(host))
         self.adam_m.zero_()
         self.adam_v.zero_()
@@ -395,6 +411,12 @@ class SSDEngine:
             if self.sparse_heads:
                 hgb = ops.HeadGradBuffers(B, [h * h for _, h, _ in self.fm], self.num_priors, self.head_npad, device=dev)
             c = dict(acts=acts, gacts=gacts, loc=loc, conf=conf, packed=packed, pool_code=pool_code, rbits=rbits, hgb=hgb)
+            if self.l2norm is not None:
+                # the normalised feature map 0 (what head 0 reads; the trunk keeps the map itself), 1 / norm per pixel as the
+                # forward pass computed it, and the gradient w.r.t. the normalised map (head 0's data gradient)
+                a0 = acts[self.fm[0][0] + 1]
+                c["l2n_y"], c["l2n_gy"] = torch.empty_like(a0), torch.empty_like(a0)
+                c["l2n_r"] = torch.empty((a0.numel() // a0.shape[-1],), dtype=torch.float32, device=dev)
             self._act_cache = {B: c}              # keep one batch size resident
         return c
 
@@ -441,7 +463,11 @@ class SSDEngine:
         def head(lvl, ws):
             ni = self.fm[lvl][0]
             wt, bt = self.head_params[lvl]
-            ops.conv2d_head_fwd(acts[ni + 1], self.view(wt, self.param_bf16), self.view(bt, self.param), c["loc"],
+            src = acts[ni + 1]
+            if lvl == 0 and self.l2norm is not None:
+                src = ops.l2norm_fwd(src, self.view(self.l2norm_scale, self.param), out=c["l2n_y"], rnorm=c["l2n_r"],
+                                     eps=self.l2norm.eps)
+            ops.conv2d_head_fwd(src, self.view(wt, self.param_bf16), self.view(bt, self.param), c["loc"],
                                 c["conf"], self.num_priors[lvl], self.classes, self.level_off[lvl], ws=ws)
 
         def after_node(i):
@@ -652,8 +678,13 @@ class SSDEngine:
         acts, gacts = c["acts"], c["gacts"]
         idx = [ni + 1 for ni, _, _ in self.fm]
         use_bits = [self.relu_bits is not None and a in self.bits_valid for a in idx]
+        xs, dxs = [acts[a] for a in idx], [gacts[a] for a in idx]
+        if self.l2norm is not None:
+            # head 0 reads the normalised map and its data gradient goes to that map's own buffer (l2norm_bwd turns it into
+            # gacts); the ReLU mask stays the un-normalised map's: the normalised one is zero exactly where that one is
+            xs[0], dxs[0] = c["l2n_y"], c["l2n_gy"]
         hl, keep = ops.head_layers(
-            [acts[a] for a in idx], self.head_w_t, [gacts[a] for a in idx],
+            xs, self.head_w_t, dxs,
             [self.view(wt, self.grad) for wt, _ in self.head_params], [self.view(bt, self.grad) for _, bt in self.head_params],
             [n * (4 + self.classes) for n in self.num_priors],
             relu_bits=[c["rbits"][a] if ub else None for a, ub in zip(idx, use_bits)],
@@ -800,6 +831,18 @@ class SSDEngine:
         else:
             prefetch_done = None
         sparse_head_done = {}                              # activation index -> event after a large level's sparse data gradient
+        l2n_done = []                                      # the event behind l2norm_bwd (kept only for on_ready's report)
+
+        def l2norm_bwd():
+            """Right behind head 0's data gradient, on its stream: that gradient (w.r.t. the normalised map) becomes gacts of
+            feature map 0 -- written, the trunk accumulates into it afterwards as before -- and the scale's gradient."""
+            a0, sc = self.fm[0][0] + 1, self.l2norm_scale
+            ops.l2norm_bwd(c["l2n_gy"], acts[a0], self.view(sc, self.param), rnorm=c["l2n_r"], out=gacts[a0],
+                           dscale=self.view(sc, self.grad), ws=self._ws_l2n, eps=self.l2norm.eps)
+            if on_ready:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream())
+                l2n_done.append(ev)
         if heads is not None:
             # all levels at once from the compact rows: data gradient on the main stream (every feature-map gradient is
             # written before the trunk chain accumulates into it), weight gradient next to it on the side stream
@@ -813,6 +856,8 @@ class SSDEngine:
                 # dense maps are ~140 MB of stores) are not read until the chain reaches those maps -- third stream, the
                 # chain's accumulation waits for its event (sparse_head_done)
                 ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=small_lv)
+                if self.l2norm is not None and 0 in small_lv:
+                    l2norm_bwd()
                 if getattr(self, "_tail", None) is None:
                     self._tail = torch.cuda.Stream(device=self.device)
                     self._ws_tail = ops.MatchWorkspace()
@@ -825,17 +870,23 @@ class SSDEngine:
                         # the 38x38 level's 94 MB of stores
                         for lvl in reversed(big_lv):
                             ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=[lvl])
+                            if self.l2norm is not None and lvl == 0:
+                                l2norm_bwd()           # in front of the level's event: the trunk and the heads' optimizer wait for it
                             done = torch.cuda.Event()
                             done.record(self._tail)
                             sparse_head_done[self.fm[lvl][0] + 1] = done
                     else:
                         ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=big_lv)
+                        if self.l2norm is not None and 0 in big_lv:
+                            l2norm_bwd()
                         done = torch.cuda.Event()
                         done.record(self._tail)
                         for lvl in big_lv:
                             sparse_head_done[self.fm[lvl][0] + 1] = done
             else:
                 ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz)
+                if self.l2norm is not None:
+                    l2norm_bwd()
             for ni, _, _ in self.fm:
                 written[ni + 1] = True
             del keep
@@ -854,28 +905,35 @@ class SSDEngine:
             if lvl not in big or not pack_side:
                 pack(lvl)
 
-        def masked_dgrad(key, dy, w_t, a, stride, pt, pl, accumulate, ws):
+        def masked_dgrad(key, dy, w_t, a, stride, pt, pl, accumulate, ws, out=None):
             """Data gradient w.r.t. activation a (index), masked by its ReLU sign: from the sign bits where this step's forward
-            pass wrote them and the kernel reads them (learned per call site), else from the bf16 activation."""
+            pass wrote them and the kernel reads them (learned per call site), else from the bf16 activation.  out: where it
+            goes instead of gacts[a]."""
+            out = gacts[a] if out is None else out
             if self.relu_bits is not None and a in self.bits_valid and self.relu_bits.get(key, True):
                 try:
                     ops.conv2d_bwd_data_bits(dy, w_t, c["rbits"][a], acts[a].shape, stride, pt, pl, accumulate=accumulate,
-                                             out=gacts[a], ws=ws)
+                                             out=out, ws=ws)
                     self.relu_bits[key] = True
                     return
                 except NotImplementedError:
                     self.relu_bits[key] = False
-            ops.conv2d_bwd_data(dy, w_t, acts[a], acts[a].shape, stride, pt, pl, accumulate=accumulate, out=gacts[a], ws=ws)
+            ops.conv2d_bwd_data(dy, w_t, acts[a], acts[a].shape, stride, pt, pl, accumulate=accumulate, out=out, ws=ws)
 
         def head_dgrad(lvl, ws):
             ni = self.fm[lvl][0]
-            masked_dgrad("head%d" % lvl, packed[lvl], self.head_w_t[lvl], ni + 1, 1, 1, 1, False, ws)
+            normed = lvl == 0 and self.l2norm is not None
+            masked_dgrad("head%d" % lvl, packed[lvl], self.head_w_t[lvl], ni + 1, 1, 1, 1, False, ws,
+                         out=c["l2n_gy"] if normed else None)
+            if normed:
+                l2norm_bwd()
             written[ni + 1] = True
 
         def head_wgrad(lvl, ws):
             ni = self.fm[lvl][0]
             wt, bt = self.head_params[lvl]
-            ops.conv2d_bwd_weight(acts[ni + 1], packed[lvl], wt.shape[0], 3, 1, 1, 1, dw=self.view(wt, self.grad),
+            src = c["l2n_y"] if lvl == 0 and self.l2norm is not None else acts[ni + 1]
+            ops.conv2d_bwd_weight(src, packed[lvl], wt.shape[0], 3, 1, 1, 1, dw=self.view(wt, self.grad),
                                   dbias=self.view(bt, self.grad), ws=ws)
 
         if big:
@@ -899,6 +957,10 @@ class SSDEngine:
                 continue
             on_side(lambda ws, lvl=lvl: head_wgrad(lvl, ws), [i for t in self.head_params[lvl] for i in t.indices], now=True)
             head_dgrad(lvl, self._ws)
+        if l2n_done:
+            # the scale's gradient is reported from the side stream like every weight gradient, behind the event of the stream
+            # that ran l2norm_bwd: the reducer records ONE event, on the current stream, when a bucket completes
+            on_side(lambda ws: torch.cuda.current_stream().wait_event(l2n_done[0]), [self.l2norm_scale.index], now=True)
         opt_bucket(None)
         # trunk, last layer first
         unpooled = set()                          # pooling nodes whose backward pass ran inside the next convolution's data gradient
@@ -1091,7 +1153,8 @@ class SSDEngine:
 
     def decay_table(self, weight_decay, decay_bias=False):
         """Device fp32 [len(tensors)]: the L2 coefficient of every tensor for ssd_sgd_momentum_step -- weight_decay on the
-        filters (names ending in "kernel"), on the biases only with decay_bias (Caffe SSD: decay_mult 0), else 0.
+        filters (names ending in "kernel"), on the biases only with decay_bias (Caffe SSD: decay_mult 0), else 0.  The l2norm
+        scale ("l2norm0/scale") counts as a bias: an L2 term only with decay_bias.
         Cached per (weight_decay, decay_bias)."""
         key = (float(weight_decay), bool(decay_bias))
         if not hasattr(self, "_decay_tables"):

@@ -76,7 +76,10 @@ class SSDObjectDetectionModel:
             self.classes = classes + 1               # background is the LAST class index
             self.thresh = 0.5
 
-    def __init__(self, classes, log_dir, device="cuda", seed=0, distributed=False, timestamp_dir=True):
+    def __init__(self, classes, log_dir, device="cuda", seed=0, distributed=False, timestamp_dir=True, l2norm=None):
+        """l2norm: the SSD paper's L2 normalisation of the 38x38 feature map in front of its head, with a learned per-channel
+        scale (ops.L2NormSpec.of: None / False = off as in the reference, True = the paper's initial scale 20, a number, a dict
+        or a spec).  The scale is one more variable of the engine: trained, clipped, saved and loaded like the others."""
         self.distributed = bool(distributed)
         if timestamp_dir:
             stamp = [time.strftime("%Y-%m-%d-%H%M%S", time.localtime())]
@@ -85,7 +88,8 @@ class SSDObjectDetectionModel:
             log_dir = os.path.join(log_dir, stamp[0])
         self.cfg = SSDObjectDetectionModel.Config(classes, log_dir)
         self.device = torch.device(device)
-        self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed)
+        self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed,
+                                 l2norm=l2norm)
         self._pset = ops.build_priors(grids=self._engine.grids, device=device)
         assert self._pset.A == self._engine.A
         self._prior_box = None

@@ -295,6 +295,102 @@ class LossSpec:
         return "LossSpec(kind=%r, neg_pos_ratio=%d, loc_weight=%r)" % (self.kind, self.neg_pos_ratio, self.loc_weight)
 
 
+class L2NormSpec:
+    """The SSD paper's L2 normalisation of the first feature map (l2norm_fwd / l2norm_bwd): the learned per-channel scale
+    starts at `init` (the paper's 20), `eps` is added to the sum of squares under the root (Caffe SSD's Normalize: 1e-10)."""
+
+    def __init__(self, init=20.0, eps=1e-10):
+        for name, v in (("init", init), ("eps", eps)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("l2norm %s must be a number, not %r" % (name, v))
+            if not (np.isfinite(v) and v > 0):
+                raise ValueError("l2norm %s must be finite and > 0, not %r" % (name, v))
+        self.init = float(init)
+        self.eps = float(eps)
+
+    @classmethod
+    def of(cls, v):
+        """None / False -> None (the layer is off); True -> the defaults; a positive number -> that init; an L2NormSpec ->
+        itself; a dict with the keys init / eps -> a spec.  ValueError for anything else."""
+        if v is None or v is False:
+            return None
+        if v is True:
+            return cls()
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, dict):
+            unknown = sorted(set(v) - {"init", "eps"}, key=str)
+            if unknown:
+                raise ValueError("l2norm: unknown key(s) %s (known: init, eps)" % ", ".join(repr(k) for k in unknown))
+            return cls(**v)
+        if isinstance(v, (int, float, np.integer, np.floating)):
+            return cls(init=v)
+        raise ValueError("l2norm must be None, a bool, a positive number, a dict(init, eps) or an ops.L2NormSpec, not %r" % (v,))
+
+    def __repr__(self):
+        return "L2NormSpec(init=%r, eps=%r)" % (self.init, self.eps)
+
+
+_l2norm_ws = MatchWorkspace()
+
+
+def l2norm_fwd(x, scale, out=None, rnorm=None, eps=1e-10):
+    """ssd_l2norm_fwd: y = bf16(scale_c x_pc / sqrt(sum_k x_pk^2 + eps)) over the last axis of x (bf16 [..., C]); scale fp32
+    [C].  rnorm: None, an fp32 tensor of one element per pixel that receives 1 / sqrt(...), or True to allocate one -- then
+    (y, rnorm) is returned instead of y.  NotImplementedError (SSD_ERR_UNSUPPORTED, nothing launched) unless C % 128 == 0 and
+    128 <= C <= 1024."""
+    L = _lib.lib()
+    _bf(x)
+    C = x.shape[-1]
+    P = x.numel() // C
+    if scale is not None:
+        _dev(scale, torch.float32)
+        assert scale.numel() == C
+    if out is None:
+        out = torch.empty_like(x)
+    assert _bf(out).shape == x.shape
+    want = rnorm is True
+    if want:
+        rnorm = torch.empty((P,), dtype=torch.float32, device=x.device)
+    if rnorm is not None:
+        assert _dev(rnorm, torch.float32).numel() == P
+    rc = L.ssd_l2norm_fwd(_ptr(x), _ptr(scale), _ptr(out), _ptr(rnorm), P, C, float(eps), _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError("l2norm serves multiples of 128 channels in 128 .. 1024, not C = %d" % C)
+    _lib.check(rc)
+    return (out, rnorm) if want else out
+
+
+def l2norm_bwd(dy, x, scale, rnorm=None, out=None, accumulate=False, dscale=None, ws=None, eps=1e-10):
+    """ssd_l2norm_bwd: the gradients of l2norm_fwd w.r.t. x (bf16 like x, into `out`; accumulate: added to its contents in fp32
+    before the rounding) and w.r.t. scale (fp32 [C], written; bitwise reproducible).  rnorm: what l2norm_fwd saved, or None to
+    recompute it from x (the same bits).  Returns (dx, dscale)."""
+    L = _lib.lib()
+    _bf(dy); _bf(x)
+    assert dy.shape == x.shape
+    C = x.shape[-1]
+    P = x.numel() // C
+    if scale is not None:
+        _dev(scale, torch.float32)
+        assert scale.numel() == C
+    if rnorm is not None:
+        assert _dev(rnorm, torch.float32).numel() == P
+    if out is None:
+        assert not accumulate
+        out = torch.empty_like(x)
+    assert _bf(out).shape == x.shape
+    if dscale is None:
+        dscale = torch.empty((C,), dtype=torch.float32, device=x.device)
+    assert _dev(dscale, torch.float32).numel() == C
+    wbuf = (ws or _l2norm_ws).get(L.ssd_l2norm_ws_bytes(P, C), x.device)
+    rc = L.ssd_l2norm_bwd(_ptr(dy), _ptr(x), _ptr(scale), _ptr(rnorm), _ptr(out), 1 if accumulate else 0, _ptr(dscale),
+                          _ptr(wbuf), wbuf.numel(), P, C, float(eps), _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError("l2norm serves multiples of 128 channels in 128 .. 1024, not C = %d" % C)
+    _lib.check(rc)
+    return out, dscale
+
+
 _multibox_ws = MatchWorkspace()
 
 

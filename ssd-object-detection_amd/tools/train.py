@@ -95,6 +95,26 @@ def loss_from_config(config):
                     loc_weight=section.get("loc_weight", 1.0))
 
 
+def l2norm_from_config(config):
+    """`model: l2norm: {enable, init, eps}` (no reference counterpart: the SSD paper's L2 normalisation of the 38x38 map) ->
+    ops.L2NormSpec, or None when the key is absent or enable is false: the default network has no such layer, as the
+    reference has none.  ValueError for an unknown key or bad values."""
+    section = (config.get("model") or {}).get("l2norm")
+    if section is None:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError("model.l2norm must be a mapping, not %r" % (section,))
+    unknown = set(section) - {"enable", "init", "eps"}
+    if unknown:
+        raise ValueError("unknown model.l2norm keys: %s" % sorted(unknown))
+    from ..ops import L2NormSpec
+    spec = L2NormSpec(**{k: section[k] for k in ("init", "eps") if k in section})      # (bad values raise when disabled too)
+    enable = section.get("enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError("model.l2norm.enable must be true or false, not %r" % (enable,))
+    return spec if enable else None
+
+
 def schedule_from_config(section):
     """`model: train: lr:` -> a learning-rate schedule.  `kind: exponential` (the default when the key is absent: the
     reference's schema) reads `initial`, `decay_step`, `decay_rate`; `kind: piecewise` (no reference counterpart: the SSD
@@ -178,7 +198,8 @@ def train(config):
     subset = data_cfg["mini_batch"]
     data = SSDDataLoader(dataset_root=data_cfg["dataset_root"], dataset=data_cfg["dataset"], shuffle=data_cfg["shuffle"],
                          mini_batch=subset["num_data"] if subset["enable"] else 0)
-    model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1)
+    model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1,
+                                    l2norm=l2norm_from_config(config))
 
     lr, wlr = model_cfg["train"]["lr"], model_cfg["warmup"]["lr"]
     optimizer = _make_optimizer(model_cfg["train"]["optimizer"], schedule_from_config(lr))
