@@ -531,6 +531,9 @@ int ssd_maxpool2x2_bwd_argmax(const void* code, const void* dy, void* dx, int B,
  * convolutions are fp32 TensorFlow ops, models/ssd_model.py:86-93 for the >= 256-channel 3x3 layers this serves).  MX format: OCP
  * e4m3 elements, one E8M0 scale byte (2^(s-127)) per 32 consecutive channels, multiplied on v_mfma_scale_f32_16x16x128_f8f6f4.
  *   ssd_quantize_mx_fp8     x bf16 [n] (n % 32 == 0) -> q u8 [n], scale u8 [n/32]: scale = smallest power of two with |x|/scale <= 448
+ *                           (exponent clamped to -127 .. 127; an all-zero block: byte 127).  A block that holds a NaN or an infinity:
+ *                           32 bytes 0x7F (e4m3 NaN) under the scale byte 127 -- it dequantises to NaN, no scale byte is ever 255.
+ *                           The fused quantisers below follow the same rule (csrc/mxfp8.h).
  *   ssd_conv3x3_fwd_mxfp8   y bf16 [B,H,W,Cout] = relu?(conv3x3 SAME stride 1 of x with w + bias); x8 [B,H,W,Cin] / xscale [B,H,W,Cin/32],
  *                           w8 [Cout][3][3][Cin] / wscale [Cout][3][3][Cin/32] as ssd_quantize_mx_fp8 makes them; Cin % 128 == 0,
  *                           Cout % 8 == 0 (SSD_ERR_UNSUPPORTED otherwise); fp32 accumulation */

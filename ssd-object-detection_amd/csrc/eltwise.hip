@@ -46,7 +46,6 @@ __global__ __launch_bounds__(256) void k_add_relu_mxfp8(const uint4* __restrict_
         const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
         unsigned r[4];
         float v[8];
-        float amax = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float lo = fmaxf(bf2f_(xs[k] & 0xffffu) + bf2f_(ys[k] & 0xffffu), 0.f);
@@ -56,13 +55,15 @@ __global__ __launch_bounds__(256) void k_add_relu_mxfp8(const uint4* __restrict_
             v[2 * k + 1] = __uint_as_float(r[k] & 0xffff0000u);
         }
         out[i] = make_uint4(r[0], r[1], r[2], r[3]);
+        float amax = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
-        amax = fmaxf(amax, __shfl_xor(amax, 1));
-        amax = fmaxf(amax, __shfl_xor(amax, 2));
+        for (int j = 0; j < 8; ++j) amax = mx_amax(amax, v[j]);
+        amax = mx_amax(amax, __shfl_xor(amax, 1));
+        amax = mx_amax(amax, __shfl_xor(amax, 2));
         const int e = mx_block_exp(amax);
+        const bool bad = mx_nonfinite(amax);
         const float inv = ldexpf(1.f, -e);
-        q[i] = make_uint2(mx_pack4(v[0], v[1], v[2], v[3], inv), mx_pack4(v[4], v[5], v[6], v[7], inv));
+        q[i] = make_uint2(mx_pack4(v[0], v[1], v[2], v[3], inv, bad), mx_pack4(v[4], v[5], v[6], v[7], inv, bad));
         if ((i & 3) == 0) scale[i >> 2] = (unsigned char)(e + 127);
     }
 }

@@ -42,7 +42,6 @@ __global__ __launch_bounds__(256) void k_quant_mx_fp8(const bf16_raw* __restrict
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nblocks; i += (long long)gridDim.x * 256) {
         const uint4* src = reinterpret_cast<const uint4*>(x + i * 32);
         float v[32];
-        float amax = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint4 w = src[j];
@@ -53,24 +52,15 @@ __global__ __launch_bounds__(256) void k_quant_mx_fp8(const bf16_raw* __restrict
                 v[j * 8 + 2 * k + 1] = __uint_as_float(ws[k] & 0xffff0000u);
             }
         }
+        float amax = 0.f;                                     // the rule and its non-finite case: mxfp8.h
 #pragma unroll
-        for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j]));
-        int e = 0;                                            // smallest e with amax * 2^-e <= 448 (e4m3's largest finite value)
-        if (amax > 0.f) {
-            int ex;
-            const float m = frexpf(amax / 448.f, &ex);       // amax / 448 = m * 2^ex, m in [0.5, 1)
-            e = (m == 0.5f) ? ex - 1 : ex;
-            e = e < -127 ? -127 : (e > 127 ? 127 : e);
-        }
+        for (int j = 0; j < 32; ++j) amax = mx_amax(amax, v[j]);
+        const int e = mx_block_exp(amax);                     // smallest e with amax * 2^-e <= 448 (e4m3's largest finite value)
+        const bool bad = mx_nonfinite(amax);
         const float inv = ldexpf(1.f, -e);
         unsigned out[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            int w = 0;
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * inv, v[4 * j + 1] * inv, w, false);
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * inv, v[4 * j + 3] * inv, w, true);
-            out[j] = (unsigned)w;
-        }
+        for (int j = 0; j < 8; ++j) out[j] = mx_pack4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3], inv, bad);
         uint4* dst = reinterpret_cast<uint4*>(q + i * 32);
         dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
         dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
@@ -423,15 +413,16 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
             if (ep.q) {
                 float amax = 0.f;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
-                amax = fmaxf(amax, __shfl_xor(amax, 16));
-                amax = fmaxf(amax, __shfl_xor(amax, 32));
+                for (int j = 0; j < 8; ++j) amax = mx_amax(amax, v[j]);
+                amax = mx_amax(amax, __shfl_xor(amax, 16));
+                amax = mx_amax(amax, __shfl_xor(amax, 32));
                 const int e = mx_block_exp(amax);
+                const bool bad = mx_nonfinite(amax);
                 const float inv = ldexpf(1.f, -e);
                 if (qv) {
                     unsigned char* o = ep.q + (long long)q * g.N + nblk + gq * 4;
-                    *reinterpret_cast<unsigned*>(o) = mx_pack4(v[0], v[1], v[2], v[3], inv);
-                    *reinterpret_cast<unsigned*>(o + 16) = mx_pack4(v[4], v[5], v[6], v[7], inv);
+                    *reinterpret_cast<unsigned*>(o) = mx_pack4(v[0], v[1], v[2], v[3], inv, bad);
+                    *reinterpret_cast<unsigned*>(o + 16) = mx_pack4(v[4], v[5], v[6], v[7], inv, bad);
                     if (gq == 0) ep.qs[(long long)q * ldq + (nblk >> 5)] = (unsigned char)(e + 127);
                 }
             }
@@ -499,15 +490,16 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
             if (ep.q) {                                       // N % 32 == 0: the whole block lies inside N
                 float amax = 0.f;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
-                amax = fmaxf(amax, __shfl_xor(amax, 16));
-                amax = fmaxf(amax, __shfl_xor(amax, 32));
+                for (int j = 0; j < 8; ++j) amax = mx_amax(amax, v[j]);
+                amax = mx_amax(amax, __shfl_xor(amax, 16));
+                amax = mx_amax(amax, __shfl_xor(amax, 32));
                 const int e = mx_block_exp(amax);
+                const bool bad = mx_nonfinite(amax);
                 const float inv = ldexpf(1.f, -e);
                 if (mv) {
                     unsigned char* o = ep.q + (long long)m * g.N + nblk + gq * 4;
-                    *reinterpret_cast<unsigned*>(o) = mx_pack4(v[0], v[1], v[2], v[3], inv);
-                    *reinterpret_cast<unsigned*>(o + 16) = mx_pack4(v[4], v[5], v[6], v[7], inv);
+                    *reinterpret_cast<unsigned*>(o) = mx_pack4(v[0], v[1], v[2], v[3], inv, bad);
+                    *reinterpret_cast<unsigned*>(o + 16) = mx_pack4(v[4], v[5], v[6], v[7], inv, bad);
                     if (gq == 0) ep.qs[(long long)m * ldq + (nblk >> 5)] = (unsigned char)(e + 127);
                 }
             }

@@ -1111,7 +1111,8 @@ def maxpool2x2_bwd(x, y, dy, out=None):
 
 
 def quantize_mx_fp8(x, q=None, scale=None):
-    """bf16 tensor (last dimension a multiple of 32) -> (q uint8 same shape: OCP e4m3 bytes, scale uint8 [..., C/32]: E8M0)."""
+    """bf16 tensor (last dimension a multiple of 32) -> (q uint8 same shape: OCP e4m3 bytes, scale uint8 [..., C/32]: E8M0).
+    A block that holds a NaN or an infinity comes out as 32 NaN bytes (0x7F) under the scale byte 127."""
     L = _lib.lib()
     _bf(x)
     assert x.shape[-1] % 32 == 0

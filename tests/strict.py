@@ -52,6 +52,10 @@ def first_diff(got, want):
     return "%d of %d elements differ, first at %s: got %r, want %r" % (n, g.numel(), idx, g[idx].item(), w[idx].item())
 
 
+def _bits(t):
+    return t.contiguous().view(-1).view(_INT[t.element_size()])
+
+
 class _Slot:
     def __init__(self, name, start, nbytes, size, tensor, kind):
         self.name, self.start, self.nbytes, self.size, self.tensor, self.kind = name, start, nbytes, size, tensor, kind
@@ -181,7 +185,7 @@ class Arena:
         out = []
         for s in self.slots:
             out += self._guard_findings(s)
-            if s.kind == "in" and not torch.equal(s.tensor, s.keep):
+            if s.kind == "in" and not torch.equal(_bits(s.tensor), _bits(s.keep)):      # bit for bit: an input may hold a NaN
                 out.append("input %s was modified: %s" % (s.name, first_diff(s.tensor, s.keep)))
             if s.kind in ("out", "inout") and s.want is not None:
                 want = s.want
@@ -410,12 +414,16 @@ def ref_unpool(code, dy, x_shape, ksize, stride, pad_t, pad_l):
 # ---- MX-fp8, by the stated rule -----------------------------------------------------------------------------------------
 def ref_quantize_mx(t):
     """bf16 [..., C] (C % 32 == 0) -> (q uint8 [..., C] OCP e4m3 bytes, scale uint8 [..., C/32] E8M0): per block of 32 the scale
-    2^e with e the smallest integer such that amax / 2^e <= 448 (0 for an all-zero block), elements v / 2^e rounded to nearest"""
+    2^e with e the smallest integer such that amax / 2^e <= 448, clamped to -127 .. 127 (0 for an all-zero block), elements
+    v / 2^e rounded to nearest.  A block that holds a NaN or an infinity: 32 bytes 0x7F (NaN) under the scale byte 127."""
     v = t.float().reshape(*t.shape[:-1], t.shape[-1] // 32, 32)
+    bad = ~torch.isfinite(v).all(-1)
+    v = torch.where(bad.unsqueeze(-1), torch.zeros(()), v)
     amax = v.abs().amax(-1)
     m, ex = torch.frexp(amax / 448.0)
     e = torch.where(amax > 0, torch.where(m == 0.5, ex - 1, ex), torch.zeros_like(ex)).clamp(-127, 127)
-    q = (v * torch.exp2(-e.float()).unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8).reshape(t.shape)
+    q = (v * torch.exp2(-e.float()).unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    q = torch.where(bad.unsqueeze(-1), torch.tensor(0x7F, dtype=torch.uint8), q).reshape(t.shape)
     return q, (e + 127).to(torch.uint8)
 
 
@@ -647,6 +655,227 @@ def mx_conv_case(case):
         assert torch.equal(ref_dequantize_mx(q, s), (r[name] if name != "w_t" else r["w_t"][..., :case[4]]).float()), name
         r[name + "_q"], r[name + "_s"] = q, s
     return r
+
+
+# ---- MX-fp8 operands whose block scales differ ------------------------------------------------------------------------------------
+# mx_conv_case's operands have ONE activation scale byte (120) and one filter scale byte (119), so a kernel that takes the scale of
+# a neighbouring block, k-step, tap, pixel or filter passes it.  The two designs below give neighbouring blocks different scales
+# and still have ONE exact expected result, whatever the matrix instruction does inside one issue:
+#
+# A, "cancelling":  x' = x 2^(u(j) + alpha(p)),  w' = w 2^(-u(j) + beta(n) + gamma(t))  for the integer operands x, w of
+#    conv_operands, block j, pixel p, filter n, tap t.  Every product of one instruction (one pixel, filter, tap, 128 channels) is
+#    x w 2^(alpha + beta + gamma): one power-of-two grid, so any order of accumulation inside the instruction is exact.  Catches
+#    a scale taken from another pixel, tap, filter or k-step, and any mis-routing of the blocks of ONE operand -- but not the same
+#    block permutation applied to both operands (the u cancel).
+# B, "block-isolated":  w is non-zero in one block of each 128-channel k-step only, block (n + tap + kstep) mod 4; every block of
+#    x and of w has an independent exponent in -3 .. 3; the all-zero blocks of w carry decoy scale bytes.  An instruction sums
+#    products of a single scale pair.  Catches a block permutation common to both operands.
+# Across instructions the fp32 accumulator adds multiples of `grid` whose absolute sum stays below 2^24 grid (asserted), so the
+# sum is exact in any order and the kernel's ONE bf16 rounding gives the float64 reference rounded once to nearest-even.
+U_TABLE = (-3, 2, -1, 3, 1, -2, 3, 0, -2, 0, 2, -3, 3, -1, -3, 1)   # neighbours differ; blocks i, i + 4, i + 8, i + 12 differ
+GAMMA = (0, 2, 1, 0, 1, 2, 1, 0, 2)                                  # per tap: consecutive taps differ, rows and columns differ
+WIDE = 13                                                            # the wide variant: u spans +-39
+# Scale bytes of w's all-zero blocks under design B.  Any byte but 255 is legal there (0 * 2^any = 0); they stay at or below 126 so
+# that a zero product's exponent (activation scale <= 123, a zero element 14 binades under a live one) never rises above the live
+# products' (scales >= 116 + 117): the expected bits then do not depend on whether the instruction's alignment looks at zeros.
+DECOY = (100, 126)
+
+
+def _pow2_blocks(t, e):
+    """integer-valued t [..., C] times 2^e per 32-channel block (e [..., C/32]), in bf16 -- exactly"""
+    v = t.float() * torch.exp2(e.float()).repeat_interleave(32, -1)
+    out = v.to(torch.bfloat16)
+    assert torch.equal(out.float(), v) and bool(torch.isfinite(v).all())
+    return out
+
+
+def isolated_filters(g, shape, reduce_k):
+    """filters [N,k,k,C] in {-1,0,1}, non-zero in block (n + tap + kstep) mod 4 of each 128-channel k-step only, there at the
+    density of conv_operands times 4"""
+    N, k, _, C = shape
+    w = ints(g, shape, (-1, 1), min(1.0, 4 * 256.0 / reduce_k))
+    j = torch.arange(C) // 32
+    n, tap = torch.arange(N).view(N, 1, 1), torch.arange(k * k).view(1, k * k, 1)
+    keep = (j % 4).view(1, 1, C) == (n + tap + (j // 4).view(1, 1, C)) % 4
+    return (w.float() * keep.view(N, k, k, C)).to(torch.bfloat16)
+
+
+def mx_design_operands(act, filt, design, wide, g):
+    """act [B,h,w,K] and filt [N,k,k,K] (integers, bf16) -> the designed pair with their reference bytes and scales.  Returns
+    a dict: a, f (bf16), a_q, a_s, f_q, f_s (ref_quantize_mx), f_s_op (f_s with design B's decoys), grid."""
+    B, h, w_, K = act.shape
+    N, k = filt.shape[:2]
+    nb = K // 32
+    if design == "A":
+        u = torch.tensor([U_TABLE[j % 16] for j in range(nb)]) * (WIDE if wide else 1)
+        alpha = torch.randint(0, 3, (B, h, w_, 1), generator=g)
+        beta = torch.randint(0, 3, (N, 1, 1, 1), generator=g)
+        gamma = torch.tensor(GAMMA[:k * k]).view(1, k, k, 1)
+        ea, ef, grid = u + alpha, -u + beta + gamma, 1.0
+    else:
+        assert design == "B" and not wide
+        ea = torch.randint(-3, 4, (B, h, w_, nb), generator=g)
+        ef = torch.randint(-3, 4, (N, k, k, nb), generator=g)
+        grid = 2.0 ** -6
+    d = dict(a=_pow2_blocks(act, ea), f=_pow2_blocks(filt, ef), grid=grid)
+    for name in ("a", "f"):
+        q, s = ref_quantize_mx(d[name])
+        assert torch.equal(ref_dequantize_mx(q, s), d[name].float()), name        # MX e4m3 holds the operand exactly
+        d[name + "_q"], d[name + "_s"] = q, s
+    d["f_s_op"] = d["f_s"]
+    if design == "B":                                      # decoys: the kernel gets bytes and scales directly, 0 * 2^any = 0
+        zero = d["f"].float().view(N, k, k, nb, 32).abs().amax(-1) == 0
+        decoy = torch.randint(DECOY[0], DECOY[1] + 1, zero.shape, generator=g).to(torch.uint8)
+        d["f_s_op"] = torch.where(zero, decoy, d["f_s"])
+        assert torch.equal(ref_dequantize_mx(d["f_q"], d["f_s_op"]), d["f"].float()) and int(zero.sum()) >= 3 * zero.numel() // 4
+    return d
+
+
+def _to_bf16_once(t64):
+    """the float64 reference rounded ONCE to bf16: it is exactly an fp32 number (asserted), so float64 -> fp32 does not round"""
+    assert torch.equal(t64.float().double(), t64)
+    return t64.float().to(torch.bfloat16)
+
+
+def _dgrad64(dy, w_t, x_shape, k, pt, pl):
+    """data gradient (stride 1) of dy [B,Ho,Wo,Cout] through the filters given TRANSPOSED, w_t [Cin,k,k,Cout]; float64"""
+    xr = torch.zeros(x_shape, dtype=torch.float64, requires_grad=True)
+    w = w_t.permute(3, 1, 2, 0).flip(1, 2).contiguous().double()
+    ref_conv(xr, w, None, k, 1, pt, pl, dy.shape[1], dy.shape[2], False).backward(dy.double())
+    return xr.grad
+
+
+def mx_fwd_from_scales(r, xs, ws):
+    """the forward of r's BYTES under the scale arrays xs, ws (no ReLU), rounded to bf16: r["y"] for r's own scales"""
+    B, H, W, Cin, Cout, k, stride, mode = r["case"]
+    Ho, Wo, pt, pl = r["geom"]
+    y = ref_conv(ref_dequantize_mx(r["x_q"], xs).double(), ref_dequantize_mx(r["w_q"], ws).double(), r["bias"].double(), k, stride,
+                 pt, pl, Ho, Wo, False)
+    return y.float().to(torch.bfloat16)
+
+
+def mx_dgrad_from_scales(r, dys, wts):
+    B, H, W, Cin, Cout, k, stride, mode = r["case"]
+    Ho, Wo, pt, pl = r["geom"]
+    dx = _dgrad64(ref_dequantize_mx(r["dy_q"], dys), ref_dequantize_mx(r["w_t_q"], wts), (B, H, W, Cin), k, pt, pl)
+    return dx.float().to(torch.bfloat16)
+
+
+def _design_gen(case, design, wide, salt):
+    return torch.Generator().manual_seed((case_seed(case) * 31 + {"A": 1, "B": 2}[design] + (4 if wide else 0) + salt) % 100003)
+
+
+_MX_CACHE = {}
+
+
+def mx_fwd_design(case, design, wide=False):
+    """Forward operands of design A or B for a (B,H,W,Cin,Cout,k,stride,mode) case (cached: treat as read-only): x, w (bf16),
+    x_q, x_s, w_q, w_s = ref_quantize_mx of them, w_s_op = the scale bytes the kernel gets (design B: with decoys), bias, the
+    float64 reference y64 and the expected bf16 maps y, y_relu, and `bound` = max sum |terms| / grid."""
+    key = ("fwd", tuple(case[:8]), design, wide)
+    if key in _MX_CACHE:
+        return _MX_CACHE[key]
+    B, H, W, Cin, Cout, k, stride, mode = case[:8]
+    o = conv_operands(case)
+    Ho, Wo, pt, pl = o["geom"]
+    g = _design_gen(case, design, wide, 0)
+    w_int = o["w"] if design == "A" else isolated_filters(g, (Cout, k, k, Cin), k * k * Cin)
+    d = mx_design_operands(o["x"], w_int, design, wide, g)
+    r = dict(case=tuple(case[:8]), design=design, wide=wide, geom=o["geom"], bias=o["bias"], grid=d["grid"], x=d["a"], w=d["f"],
+             x_q=d["a_q"], x_s=d["a_s"], w_q=d["f_q"], w_s=d["f_s"], w_s_op=d["f_s_op"])
+    x64, w64, b64 = r["x"].double(), r["w"].double(), r["bias"].double()
+    r["y64"] = ref_conv(x64, w64, b64, k, stride, pt, pl, Ho, Wo, False)
+    r["bound"] = float(ref_conv(x64.abs(), w64.abs(), b64.abs(), k, stride, pt, pl, Ho, Wo, False).max()) / r["grid"]
+    r["y"], r["y_relu"] = _to_bf16_once(r["y64"]), _to_bf16_once(r["y64"].relu())
+    check_mx_regime(r)
+    _MX_CACHE[key] = r
+    return r
+
+
+def mx_dgrad_design(case, design, wide=False):
+    """Data-gradient operands of design A or B (stride 1; the blocks run over Cout): dy, w_t [Cin,k,k,Cout] (bf16), dy_q, dy_s,
+    w_t_q, w_t_s, w_t_s_op, the accumulate base and ReLU mask source of conv_operands, the float64 reference dx64 and the expected
+    bf16 maps dx, dx_masked = dx where mask_src > 0, dx_acc = (dx + base) where mask_src > 0, as conv_reference."""
+    key = ("dgrad", tuple(case[:8]), design, wide)
+    if key in _MX_CACHE:
+        return _MX_CACHE[key]
+    B, H, W, Cin, Cout, k, stride, mode = case[:8]
+    assert stride == 1 and Cout % 128 == 0
+    o = conv_operands(case)
+    Ho, Wo, pt, pl = o["geom"]
+    g = _design_gen(case, design, wide, 8)
+    wt_int = o["w"].flip(1, 2).permute(3, 1, 2, 0).contiguous() if design == "A" else isolated_filters(g, (Cin, k, k, Cout), k * k * Cin)
+    d = mx_design_operands(o["dy"], wt_int, design, wide, g)
+    r = dict(case=tuple(case[:8]), design=design, wide=wide, geom=o["geom"], grid=d["grid"], dy=d["a"], w_t=d["f"], dy_q=d["a_q"],
+             dy_s=d["a_s"], w_t_q=d["f_q"], w_t_s=d["f_s"], w_t_s_op=d["f_s_op"], mask_src=o["mask_src"], base=o["base"])
+    keep = r["mask_src"].float() > 0
+    r["dx64"] = _dgrad64(r["dy"], r["w_t"], (B, H, W, Cin), k, pt, pl)
+    r["bound"] = float((_dgrad64(r["dy"].abs(), r["w_t"].abs(), (B, H, W, Cin), k, pt, pl) + r["base"].double().abs()).max()) / r["grid"]
+    r["dx"], r["dx_masked"] = _to_bf16_once(r["dx64"]), _to_bf16_once(masked(r["dx64"], keep))
+    r["dx_acc"] = _to_bf16_once(masked(r["dx64"] + r["base"].double(), keep))
+    check_mx_regime(r)
+    _MX_CACHE[key] = r
+    return r
+
+
+def check_mx_regime(r):
+    """the accumulator adds exactly: every term is a multiple of grid and the absolute sum stays below 2^24 grid"""
+    assert r["bound"] < 2 ** 24, (r["case"], r["design"], r["bound"])
+    ref = r["y64"] if "y64" in r else r["dx64"]
+    assert torch.equal((ref / r["grid"]).round(), ref / r["grid"]) and torch.equal(ref.float().double(), ref)
+
+
+def mx_eltwise_case(shape):
+    """eltwise_case's integers times a power of two per 32-channel block (both addends the same one): sums exact in bf16, block
+    maxima over 2^-20 .. 2^22"""
+    r = eltwise_case(shape)
+    e = torch.randint(-20, 21, tuple(shape[:-1]) + (shape[-1] // 32,), generator=_gen(*shape, 5))
+    a, b = _pow2_blocks(r["a"], e), _pow2_blocks(r["b"], e)
+    out = (a.float() + b.float()).relu()
+    assert in_bf16_regime(out)
+    return dict(a=a, b=b, out=out, bf16=("out",))
+
+
+def mx_scale_mutations(r, a_s, f_s, k, design):
+    """[(name, mutated a_s, mutated f_s)]: the wrong scale routings the designs must expose.  a_s [B,h,w,nb] activation scales,
+    f_s [N,k,k,nb] filter scales (the operand ones).  Swaps of blocks inside every k-step on ONE operand under design A, on
+    both under design B; two k-steps swapped; the scale of the pixel to the right / below, of the next tap, of the next filter."""
+    nb = a_s.shape[-1]
+
+    def perm(t, p):
+        return t[..., torch.tensor(p)]
+    out = []
+    for i in range(3):
+        p = list(range(nb))
+        for s in range(0, nb, 4):
+            p[s + i], p[s + i + 1] = p[s + i + 1], p[s + i]
+        if design == "A":
+            out += [("x blocks %d<->%d" % (i, i + 1), perm(a_s, p), f_s), ("w blocks %d<->%d" % (i, i + 1), a_s, perm(f_s, p))]
+        else:
+            out.append(("both blocks %d<->%d" % (i, i + 1), perm(a_s, p), perm(f_s, p)))
+    if nb >= 8:
+        p = list(range(4, 8)) + list(range(0, 4)) + list(range(8, nb))
+        out.append(("k-steps 0<->1", perm(a_s, p), f_s if design == "A" else perm(f_s, p)))
+    out.append(("pixel to the right", a_s.roll(-1, 2), f_s))
+    out.append(("pixel below", a_s.roll(-1, 1), f_s))
+    if k == 3:
+        out.append(("next tap", a_s, f_s.reshape(f_s.shape[0], 9, nb).roll(-1, 1).reshape(f_s.shape)))
+    out.append(("next filter", a_s, f_s.roll(-1, 0)))
+    return out
+
+
+def _same(*cases):
+    return [tuple(c) + ("same",) for c in cases]
+
+
+# the cases of tests/test_mxfp8_strict_gpu.py (B, H, W, Cin, Cout, k, stride, mode): the smallest shapes that reach each path
+MX_CONV3X3_CASES = _same((2, 19, 19, 256, 256, 3, 1), (1, 5, 5, 512, 96, 3, 1))      # a tail tile of pixels; 4 k-steps, a Cout tail
+MX_CONV2D_CASES = _same((2, 7, 7, 512, 64, 1, 1), (2, 9, 11, 256, 160, 1, 2), (3, 17, 13, 128, 160, 3, 1), (1, 9, 11, 128, 96, 3, 2),
+                        (2, 8, 8, 256, 128, 3, 2))                                       # the last: TF-SAME pad 0 at top and left
+MX_POOL_CASES = _same((1, 7, 7, 128, 128, 3, 1), (3, 8, 8, 256, 160, 3, 1))           # 48 windows: a tail tile, images share a tile
+MX_DGRAD_CASES = _same((2, 15, 15, 96, 256, 3, 1), (2, 19, 19, 64, 256, 1, 1), (1, 9, 11, 256, 512, 3, 1))
+MX_WIDE_FWD_CASE, MX_WIDE_DGRAD_CASE = MX_CONV2D_CASES[0], MX_DGRAD_CASES[1]
+MX_FWD_CASES = MX_CONV3X3_CASES + MX_CONV2D_CASES + MX_POOL_CASES
 
 
 EXTRAS = {
