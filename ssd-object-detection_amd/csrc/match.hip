@@ -232,7 +232,8 @@ __global__ __launch_bounds__(WG) void k_match_pairs(
 
     RowF32 nxt[4];                             // uniform -> scalar loads, four in flight, one batch ahead
 #pragma unroll
-    for (int i = 0; i < 4; ++i) nxt[i] = slots[g0 + min(i, max(nt - 1, 0))].recf;
+    for (int i = 0; i < 4; ++i) nxt[i] = slots[nt > 0 ? g0 + min(i, nt - 1) : 0].recf;   // (no row: slot 0, which always exists --
+                                                                                         // slot g0 of a trailing empty image does not)
     for (int r0 = 0; r0 < nt; r0 += 4) {
         RowF32 f[4];
 #pragma unroll
@@ -510,7 +511,9 @@ __global__ __launch_bounds__(WG) void k_match_phase1(
 //               inter <= (ow + 1e-10)(min(hP, hG) + 1e-10) with ow the overlap of the x extents: so ow >= m_w := T /
 //               (min(hP, hG) + 2e-10) - 2e-10, i.e. the prior's centre lies in [g.lx + m_w - wP/2, g.hx - m_w + wP/2]; likewise
 //               in y.  Per (row, anchor type) that is a rectangle of cells (typically 0-9 cells, ~25 per row in all),
-//               queued in LDS one cell per entry.
+//               queued in LDS one cell per entry.  (The bound on inter holds for overlapping extents; it covers disjoint ones
+//               too only while m_w, m_h > 1e-10.  A zero-area row, whose IoUs are products of the 1e-10 clamps on and off
+//               the window alike, is scanned exactly instead.)
 //   4. evaluate every queued cell EXACTLY, one per thread and pass (the prior comes from the model: the same bits as the array; iou_n's arithmetic, division only past the
 //               division-free filter); pairs with q >= 0.8 L' go to the row's candidate chain in LDS.  The chain holds
 //               every column of the row with IoU >= 0.8 L' -- what the lists of the three-launch path hold.
@@ -682,6 +685,10 @@ __global__ __launch_bounds__(WG) void k_match_local(
             if (fmin(wP * hP, g.a) + 4e-10 < T) continue;                  // inter <= min(aP, aG) + 3e-10: this type cannot reach the bound
             const double m_w = T / (fmin(hP, fmax(g.hy - g.ly, 0.0)) + 2e-10) - 2e-10;
             const double m_h = T / (fmin(wP, fmax(g.hx - g.lx, 0.0)) + 2e-10) - 2e-10;
+            // inter <= (ow + 1e-10)(..) needs ow >= 0: a prior whose x extent is disjoint from the row's still has inter =
+            // 1e-10 max(1e-10, oh) <= 1e-10 (min(hP, hG) + 1e-10), below T only if m_w > 1e-10 (likewise in y).  A degenerate
+            // row (zero area: every IoU is a product of the clamps, the same on and off the window) fails this: exact scan.
+            if (!(m_w > 1e-10) || !(m_h > 1e-10)) { S.nolist[r] = 1; continue; }
             const double gw = (double)tgw, gh = (double)tgh;
             // cell x has its centre at (x + .5) / gw: x in [xlo, xhi]; 1e-6 of a cell against the roundings of this block
             const double xlo = (g.lx + m_w - 0.5 * wP) * gw - 0.5 - 1e-6, xhi = (g.hx - m_w + 0.5 * wP) * gw - 0.5 + 1e-6;

@@ -18,10 +18,11 @@ N_CLS = 12                                                   # classes with grou
 REGIMES = {"continuous": (None, 0, 60), "quantised": (20, 0, 60), "cut_in_ties": (10, 80, 160), "sparse": (None, 0, 3)}
 
 
-def gen(rng, n_img, kept_lo, kept_hi, quant=None, size=300.0, n_gt_hi=8):
+def gen(rng, n_img, kept_lo, kept_hi, quant=None, size=300.0, n_gt_hi=8, n_anchors=A):
     """Per image: detections (score f32 [k], cls i32 [k], box f32 [k,4]) in anchor order, their anchors (sorted), and ground
     truth (cls [n], box f64 [n,4] pixels).  0 .. n_gt_hi boxes per image; about 70 % of the detections are jittered copies of
-    a ground-truth box, some exact; half the images carry two identical detections, 30 % two identical ground truths."""
+    a ground-truth box, some exact; half the images carry two identical detections, 30 % two identical ground truths.
+    n_anchors: the anchor count the kept anchors are drawn from (the module's A unless given)."""
     dets, gts, anchors = [], [], []
     for _ in range(n_img):
         n = int(rng.integers(0, n_gt_hi + 1))
@@ -30,7 +31,7 @@ def gen(rng, n_img, kept_lo, kept_hi, quant=None, size=300.0, n_gt_hi=8):
         wh = rng.uniform(0.05, 0.3, (n, 2))
         gbox = np.concatenate([cxy, wh], 1)
         k = int(rng.integers(kept_lo, kept_hi + 1))
-        anc = np.sort(rng.choice(A, k, replace=False))
+        anc = np.sort(rng.choice(n_anchors, k, replace=False))
         score = rng.uniform(0.05, 1.0, k).astype(np.float32)
         if quant:
             score = (np.round(score * quant) / quant).astype(np.float32)
