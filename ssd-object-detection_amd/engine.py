@@ -142,6 +142,393 @@ class FusedView:
         self.indices = [p.index for p in parts]
 
 
+def _launched(fn, *args, refused=NotImplementedError, **kw):
+    """Try a fused launch: whether it ran.  The library refuses a shape it has no kernel for before it launches anything
+    (SSD_ERR_UNSUPPORTED -> NotImplementedError, SSD_ERR_VALUE -> ValueError): the caller takes the fallback and writes the
+    answer where it keeps what it learned, so that it does not ask again."""
+    try:
+        fn(*args, **kw)
+        return True
+    except refused:
+        return False
+
+
+class _Streams:
+    """The streams of the schedule beside the caller's, each created at its first use with the MatchWorkspace of the launches
+    that go to it, and the two operations the schedule is made of."""
+
+    def __init__(self, device):
+        self.device = device
+        self.side = self.ws_side = self.tail = self.ws_tail = None
+
+    def side_stream(self):
+        if self.side is None:
+            self.side = torch.cuda.Stream(device=self.device, priority=int(os.environ.get("SSD_SIDE_PRIO", "0")))
+            self.ws_side = ops.MatchWorkspace()
+        return self.side
+
+    def tail_stream(self):
+        if self.tail is None:
+            self.tail = torch.cuda.Stream(device=self.device)
+            self.ws_tail = ops.MatchWorkspace()
+        return self.tail
+
+    @staticmethod
+    def behind(s, m):
+        """`with behind(s, m):` runs the block on stream s, behind everything enqueued so far on stream m (one new event)."""
+        ev = torch.cuda.Event()
+        ev.record(m)
+        s.wait_event(ev)
+        return torch.cuda.stream(s)
+
+    @staticmethod
+    def after(s):
+        """An event behind what stream s has enqueued."""
+        ev = torch.cuda.Event()
+        ev.record(s)
+        return ev
+
+
+class _BackwardPass:
+    """One call of SSDEngine.backward: the state its phases share, and the phases (backward() is the order they run in)."""
+
+    def __init__(self, eng, c, heads, dloc, dconf, on_ready, fused_adam, on_dgrad):
+        self.eng, self.c, self.heads, self.dloc, self.dconf = eng, c, heads, dloc, dconf
+        self.on_ready, self.hp, self.on_dgrad = on_ready, fused_adam, on_dgrad
+        self.B = c["loc"].shape[0]
+        self.big_levels = [lvl for lvl, (_, h, _) in enumerate(eng.fm) if self.B * h * h >= eng.BIG_LEVEL_PIXELS]
+        self.acts, self.gacts = c["acts"], c["gacts"]
+        self.written = [False] * len(self.acts)            # activation index -> its gradient holds a value to accumulate into
+        self.main = torch.cuda.current_stream()
+        self.side = eng._side_stream() if eng.overlap_heads else None
+        self.pending = []                                  # (fn, tensors) waiting for the side stream's next wait
+        self.opt_range, self.opt_at = None, {}             # the bucket update; node -> (t0, t1) of the bucket behind its data gradient
+        self.deferred, self.defer_nodes = [], set()        # (t0, t1, event) of the buckets that run at the end of the main stream
+        self.prefetch_done = None
+        self.sparse_head_done = {}                         # activation index -> event after a large level's sparse data gradient
+        self.head_done = {}                                # activation index -> event after a large level's dense data gradient
+        self.l2n_done = []                                 # the event behind l2norm_bwd (kept only for on_ready's report)
+        self.packed = [None] * len(eng.fm)                 # dense heads: loc + conf gradients per level
+        self.unpooled = set()                              # pooling nodes whose backward pass ran inside the next convolution's data gradient
+        self.chained, self.batched_w, self.first_fused = set(), set(), False
+
+    # ---- phases, in order
+    def plan_optimizer(self):
+        e, hp = self.eng, self.hp
+        if hp is None:
+            return
+        trunk_nodes = [node for _, _, node in e.opt_buckets() if node is not None]
+        # the last bucket (lowest node) follows its own weight gradients on the side stream; the `opt_defer` before it go to the
+        # END of the main stream, which finishes its chain ~0.3 ms before the side stream does
+        if e.opt_defer > 0:
+            self.defer_nodes = set(trunk_nodes[max(0, len(trunk_nodes) - 1 - e.opt_defer):len(trunk_nodes) - 1])
+        e.step_count += 1
+        t = e.step_count
+        kind = hp.get("kind", "adam")
+        if kind == "adam":
+            lr_t = hp["lr"] * math.sqrt(1.0 - hp["beta2"] ** t) / (1.0 - hp["beta1"] ** t)
+            self.opt_range = lambda t0, t1: e.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
+        elif kind == "sgd_momentum":
+            self.opt_range = lambda t0, t1: e.sgd_range(t0, t1, hp["lr"], hp["momentum"], hp["nesterov"], hp["decay"], hp["clip"])
+        else:
+            raise ValueError("unknown fused optimizer kind %r" % (kind,))
+        self.opt_at = {node: (t0, t1) for t0, t1, node in e.opt_buckets()}
+
+    def prefetch_chain(self):
+        e = self.eng
+        if self.side is not None and e.chain_start is not None and "bwd" in e.chain and e.chain_prefetch:
+            tail = e._streams.tail_stream()                # (whether or not `tail_stream` is set: that governs the forward heads)
+            with _Streams.behind(tail, self.main):         # the data-gradient chain's packed filters into L2, ~50 us ahead of it
+                ops.chain_prefetch([e.chain_pk_bwd[j] for j in range(e.chain_start, len(e.nodes))])
+            self.prefetch_done = _Streams.after(tail)
+
+    def heads_sparse(self):
+        """All levels from the compact rows: data gradient on the main stream (every feature-map gradient is written before
+        the trunk chain accumulates into it), weight gradient next to it on the side stream."""
+        e, heads = self.eng, self.heads
+        hl, keep = e._head_layers(self.c)                  # (keep: what the descriptors point to, alive until the calls are enqueued)
+        self.on_side(lambda ws: ops.heads_bwd_weight_sparse(heads, hl, ws=e._ws_hw),
+                     [i for wt, bt in e.head_params for t in (wt, bt) for i in t.indices])
+        big_lv = self.big_levels
+        small_lv = [lvl for lvl in range(len(e.fm)) if lvl not in big_lv]
+        if self.side is not None and e.split_heads_dgrad and big_lv and small_lv:
+            # the small maps' gradients head the extras' chain; the 38x38 / 19x19 maps' (most of the launch's time: their
+            # dense maps are ~140 MB of stores) are not read until the chain reaches those maps -- third stream, the
+            # chain's accumulation waits for its event (sparse_head_done)
+            self.heads_dgrad_sparse(hl, small_lv)
+            # split_heads_dgrad 2: one call per level, the level the chain reaches first (19x19) first: its event does not wait
+            # for the 38x38 level's 94 MB of stores
+            calls = [[lvl] for lvl in reversed(big_lv)] if e.split_heads_dgrad == 2 else [big_lv]
+            tail = e._streams.tail_stream()
+            with _Streams.behind(tail, self.main):
+                for levels in calls:
+                    self.heads_dgrad_sparse(hl, levels)    # (l2norm_bwd in front of the level's event: the trunk and the heads' optimizer wait for it)
+                    done = _Streams.after(tail)
+                    for lvl in levels:
+                        self.sparse_head_done[e.fm[lvl][0] + 1] = done
+        else:
+            self.heads_dgrad_sparse(hl)
+        for ni, _, _ in e.fm:
+            self.written[ni + 1] = True
+
+    def heads_dense(self):
+        """From the dense (dloc, dconf): per level a packed gradient, a data gradient and a weight gradient on the dense kernels."""
+        e = self.eng
+        big = self.big_levels if self.side is not None and e.big_heads_side else []
+        for lvl in range(len(e.fm)):                       # the large levels are packed where they are consumed (side stream)
+            if lvl not in big or not e.pack_side:
+                self.pack(lvl)
+        if big:
+            with _Streams.behind(self.side, self.main):
+                for lvl in reversed(big):                  # 19x19 first: the trunk chain reaches it first
+                    if e.pack_side:
+                        self.pack(lvl)
+                    self.head_dgrad(lvl, e._ws_side)
+                    self.head_done[e.fm[lvl][0] + 1] = _Streams.after(self.side)
+                for lvl in reversed(big):
+                    self.head_wgrad(lvl, e._ws_side)
+                    if self.on_ready:
+                        self.on_ready([i for t in e.head_params[lvl] for i in t.indices])
+        for lvl in range(len(e.fm)):
+            if lvl not in big:
+                self.on_side(lambda ws, lvl=lvl: self.head_wgrad(lvl, ws), [i for t in e.head_params[lvl] for i in t.indices])
+                self.head_dgrad(lvl, e._ws)
+
+    def report_l2norm(self):
+        if self.l2n_done:
+            # the scale's gradient is reported from the side stream like every weight gradient, behind the event of the stream
+            # that ran l2norm_bwd: the reducer records ONE event, on the current stream, when a bucket completes
+            self.on_side(lambda ws: torch.cuda.current_stream().wait_event(self.l2n_done[0]), [self.eng.l2norm_scale.index])
+
+    def opt_bucket(self, node):
+        """Called once the data gradient of `node` (None: of every head) is enqueued on the main stream."""
+        if self.on_dgrad is not None:
+            self.on_dgrad(node)
+        if node not in self.opt_at:
+            return
+        t0, t1 = self.opt_at.pop(node)
+        if self.side is not None and node in self.defer_nodes:
+            self.flush_side()                             # the bucket's weight gradients are all enqueued there by now
+            self.deferred.append((t0, t1, _Streams.after(self.side)))
+            return
+        # the heads' update rewrites head_w_t, which the large levels' sparse data gradients on the third stream still
+        # read: behind their events as well as behind the main stream
+        readers = list(self.sparse_head_done.values()) if node is None else []
+
+        def run(ws):
+            for ev in readers:
+                torch.cuda.current_stream().wait_event(ev)
+            self.opt_range(t0, t1)
+        self.on_side(run, [])
+
+    def chain_dgrads(self):
+        """Data gradients of nodes end .. chain_start in one launch (ops.conv_chain): the head of the backward pass's critical
+        path -- nothing large can start before this chain reaches the 19x19 map."""
+        e, c, written = self.eng, self.c, self.written
+        if e.chain_start is None or "bwd" not in e.chain:
+            return
+        last = len(e.nodes) - 1
+        assert written[last + 1]
+        layers = []
+        for j in range(last, e.chain_start - 1, -1):
+            ndj = e.nodes[j]
+            use_bits = e.relu_bits is not None and j in e.bits_valid
+            layers.append(ops.chain_layer_dgrad(e.w_t[j], e.chain_pk_bwd[j], self.gacts[j], ndj["stride"], ndj["pt"], ndj["pl"],
+                                                accumulate=written[j], mask_bits=c["rbits"][j] if use_bits else None,
+                                                mask_src=None if use_bits else self.acts[j]))
+        for j in range(last, e.chain_start - 1, -1):
+            self.wait_for_head(j)
+        if _launched(ops.conv_chain, self.gacts[last + 1], layers):
+            self.chained = set(range(e.chain_start, last + 1))
+            for j in self.chained:
+                written[j] = True
+        else:
+            e.chain = e.chain - {"bwd"}
+
+    def chain_wgrads(self):
+        """... and their weight gradients in two launches (slab kernel + slab sums) instead of twelve."""
+        e = self.eng
+        if not (self.chained and self.side is not None and e.batch_chain_wgrads and e.wgrad_probe is None):
+            return
+        order = sorted(self.chained, reverse=True)
+        layers, tens = [], []
+        for j in order:
+            ndj = e.nodes[j]
+            wt, bt = e.conv_params[j]
+            layers.append((self.acts[j], self.gacts[j + 1], ndj["cout"], ndj["k"], ndj["stride"], ndj["pt"], ndj["pl"],
+                           e.view(wt, e.grad), e.view(bt, e.grad)))
+            tens += [wt.index, bt.index]
+        if _launched(self.on_side, lambda ws: ops.conv2d_bwd_weight_batched(layers, ws=ws), tens):
+            self.batched_w = set(order)
+        else:
+            e.batch_chain_wgrads = False
+
+    def node(self, i):
+        """Trunk node i: its weight gradient to the side stream, its data gradient (a pooling's backward pass) on the
+        main stream, then the optimizer bucket that waited for that data gradient."""
+        e, nd, written = self.eng, self.eng.nodes[i], self.written
+        assert written[i + 1]
+        if nd["kind"] == "pool":
+            assert not written[i], "a pooled activation cannot also feed a head (the pool gradient overwrites)"
+            if i not in self.unpooled:                     # (else the convolution behind the pooling already wrote gacts[i])
+                ops.maxpool2x2_bwd_argmax(self.c["pool_code"][i], self.gacts[i + 1], self.acts[i].shape, out=self.gacts[i])
+            written[i] = True
+            return
+        wt, bt = e.conv_params[i]
+        if i == 0 and self.first_fused:                    # its weight gradient came out of the second layer's data-gradient kernel
+            self.on_side(lambda ws: None, [wt.index, bt.index], grouped=True)
+        elif i not in self.batched_w:                      # (else its weight gradient left with the batched launch)
+            self.on_side(lambda ws: self.wgrad(i, ws), [wt.index, bt.index], grouped=True)
+        if i > 0 and i not in self.chained:                # (no gradient w.r.t. the image / its data gradient came out of the chain launch)
+            self.dgrad(i)
+        self.opt_bucket(i)
+
+    def finish(self):
+        assert not self.opt_at
+        self.flush_side()
+        if self.prefetch_done is not None:
+            self.main.wait_event(self.prefetch_done)       # (joins the third stream even where nothing else ran on it)
+        for ev in self.sparse_head_done.values():          # (a large level whose map no trunk node accumulated into)
+            self.main.wait_event(ev)
+        for t0, t1, ev in self.deferred:
+            self.main.wait_event(ev)
+            self.opt_range(t0, t1)
+        if self.side is not None:
+            self.main.wait_stream(self.side)
+
+    # ---- the side stream's queue: weight-gradient launches, the report behind each (on_ready) and the optimizer
+    def on_side(self, fn, tensors, grouped=False):
+        """Run fn(ws) on the side stream, after everything enqueued so far on the main stream, and report `tensors` from there
+        (in place where there is no side stream).  grouped: it may wait for the next flush_side()."""
+        if self.side is None:
+            self._run(fn, tensors, self.eng._ws)
+        elif grouped and self.eng.wgrad_group > 1:
+            # the side stream is hundreds of microseconds behind the main stream for most of the backward pass, yet every
+            # cross-stream wait costs it ~6 us of idle time (30 of them per step).  `wgrad_group` launches share ONE wait -- on the
+            # event of the LAST of them, which a stream that is behind anyway has long passed
+            self.pending.append((fn, tensors))
+            if len(self.pending) >= self.eng.wgrad_group:
+                self.flush_side()
+        else:
+            self.flush_side()
+            with _Streams.behind(self.side, self.main):
+                self._run(fn, tensors, self.eng._ws_side)
+
+    def flush_side(self):
+        """Precedes every direct run on the side stream and every event recorded there."""
+        if self.pending:
+            with _Streams.behind(self.side, self.main):
+                for fn, tensors in self.pending:
+                    self._run(fn, tensors, self.eng._ws_side)
+            self.pending.clear()
+
+    def _run(self, fn, tensors, ws):
+        fn(ws)
+        if self.on_ready:
+            self.on_ready(tensors)                         # inside the stream context of the launch: the reducer records its event there
+
+    # ---- launches the phases share
+    def wait_for_head(self, a):
+        """A large head wrote the gradient of activation a on another stream: the main stream accumulates after it."""
+        for done in (self.head_done, self.sparse_head_done):
+            if a in done:
+                self.main.wait_event(done.pop(a))
+
+    def l2norm_bwd(self):
+        """Right behind head 0's data gradient, on its stream: that gradient (w.r.t. the normalised map) becomes gacts of
+        feature map 0 -- written, the trunk accumulates into it afterwards as before -- and the scale's gradient."""
+        e, c = self.eng, self.c
+        a0, sc = e.fm[0][0] + 1, e.l2norm_scale
+        ops.l2norm_bwd(c["l2n_gy"], self.acts[a0], e.view(sc, e.param), rnorm=c["l2n_r"], out=self.gacts[a0],
+                       dscale=e.view(sc, e.grad), ws=e._ws_l2n, eps=e.l2norm.eps)
+        if self.on_ready:
+            self.l2n_done.append(_Streams.after(torch.cuda.current_stream()))
+
+    def heads_dgrad_sparse(self, hl, levels=None):
+        e = self.eng
+        ops.heads_bwd_data_sparse(self.heads, hl, ws=e._ws_hz, levels=levels)
+        if e.l2norm is not None and (levels is None or 0 in levels):
+            self.l2norm_bwd()
+
+    def pack(self, lvl):                                   # loc + conf gradients of one level in the head's channel order
+        e, h = self.eng, self.eng.fm[lvl][1]
+        self.packed[lvl] = ops.head_grad_pack(self.dloc, self.dconf, h * h, e.num_priors[lvl], e.classes, e.head_npad[lvl],
+                                              e.level_off[lvl], out=self.c["packed"][lvl]).view(self.B, h, h, e.head_npad[lvl])
+
+    def head_dgrad(self, lvl, ws):
+        e = self.eng
+        ni = e.fm[lvl][0]
+        normed = lvl == 0 and e.l2norm is not None
+        self.masked_dgrad("head%d" % lvl, self.packed[lvl], e.head_w_t[lvl], ni + 1, 1, 1, 1, False, ws,
+                          out=self.c["l2n_gy"] if normed else None)
+        if normed:
+            self.l2norm_bwd()
+        self.written[ni + 1] = True
+
+    def head_wgrad(self, lvl, ws):
+        e = self.eng
+        wt, bt = e.head_params[lvl]
+        src = self.c["l2n_y"] if lvl == 0 and e.l2norm is not None else self.acts[e.fm[lvl][0] + 1]
+        ops.conv2d_bwd_weight(src, self.packed[lvl], wt.shape[0], 3, 1, 1, 1, dw=e.view(wt, e.grad), dbias=e.view(bt, e.grad), ws=ws)
+
+    def masked_dgrad(self, key, dy, w_t, a, stride, pt, pl, accumulate, ws, out=None):
+        """Data gradient w.r.t. activation a (index), masked by its ReLU sign: from the sign bits where this step's forward
+        pass wrote them and the kernel reads them (learned per call site), else from the bf16 activation.  out: where it
+        goes instead of gacts[a]."""
+        e, x = self.eng, self.acts[a]
+        out = self.gacts[a] if out is None else out
+        if e.relu_bits is not None and a in e.bits_valid and e.relu_bits.get(key, True):
+            e.relu_bits[key] = _launched(ops.conv2d_bwd_data_bits, dy, w_t, self.c["rbits"][a], x.shape, stride, pt, pl,
+                                         accumulate=accumulate, out=out, ws=ws)
+            if e.relu_bits[key]:
+                return
+        ops.conv2d_bwd_data(dy, w_t, x, x.shape, stride, pt, pl, accumulate=accumulate, out=out, ws=ws)
+
+    def wgrad(self, i, ws):
+        e, nd = self.eng, self.eng.nodes[i]
+        wt, bt = e.conv_params[i]
+        probe = e.wgrad_probe                              # measurement only (bench.py): HIP events around the launches of chosen layers
+        timed = probe is not None and i in probe["nodes"]
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        ops.conv2d_bwd_weight(self.acts[i], self.gacts[i + 1], nd["cout"], nd["k"], nd["stride"], nd["pt"], nd["pl"],
+                              dw=e.view(wt, e.grad), dbias=e.view(bt, e.grad), ws=ws)
+        if timed:
+            e1.record()
+            probe["events"].append((i, e0, e1))
+
+    def dgrad(self, i):
+        """Data gradient of convolution i (> 0, not in the chain) on the main stream."""
+        e, c, nd, written = self.eng, self.c, self.eng.nodes[i], self.written
+        g_out = self.gacts[i + 1]
+        if i == 1 and e.fuse_first and e.first_pair and not written[1] and e.relu_bits is not None and 1 in e.bits_valid:
+            # ... and the first layer's weight gradient in one kernel (gacts[1] is consumed there, not written)
+            wt0, bt0 = e.conv_params[0]
+            self.first_fused = e.fuse_first = _launched(ops.conv2d_bwd_data_wgrad_first, g_out, e.w_t[1], c["rbits"][1], self.acts[0],
+                                                        dw=e.view(wt0, e.grad), dbias=e.view(bt0, e.grad), ws=e._ws)
+            if self.first_fused:
+                written[1] = True
+                return
+        self.wait_for_head(i)
+        # a 3x3 / stride-1 convolution right behind a pooling: its data gradient is carried through the pooling in the
+        # convolution's own store stage (no pooled gradient in HBM, no pooling-backward launch) where an LDS-patch kernel
+        # serves the layer; learned at the first call, like pool_only
+        fused = False
+        if (e.fuse_unpool is not None and e.fuse_unpool.get(i, True) and e.nodes[i - 1]["kind"] == "pool" and not written[i]
+                and not written[i - 1] and nd["k"] == 3 and nd["stride"] == 1 and nd["pt"] == 1 and nd["pl"] == 1):
+            fused = e.fuse_unpool[i] = _launched(ops.conv2d_bwd_data_unpool, g_out, e.w_t[i], None, c["pool_code"][i - 1],
+                                                 tuple(self.gacts[i - 1].shape), out=self.gacts[i - 1], ws=e._ws)
+            if fused:
+                self.unpooled.add(i - 1)
+        if not fused and e.nodes[i - 1]["kind"] == "conv": # (its ReLU masks the gradient)
+            self.masked_dgrad("conv%d" % i, g_out, e.w_t[i], i, nd["stride"], nd["pt"], nd["pl"], written[i], e._ws)
+        elif not fused:
+            ops.conv2d_bwd_data(g_out, e.w_t[i], None, self.acts[i].shape, nd["stride"], nd["pt"], nd["pl"],
+                                accumulate=written[i], out=self.gacts[i], ws=e._ws)
+        written[i] = True
+
+
 class SSDEngine:
     def __init__(self, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, device="cuda",
                  seed=0, sparse_heads=None, l2norm=None):
@@ -168,7 +555,7 @@ class SSDEngine:
         self._ws_hz = ops.MatchWorkspace()     # Z of the sparse head data gradient
         self._ws_hw = ops.MatchWorkspace()     # slabs of the sparse head weight gradient
         self._ws_l2n = ops.MatchWorkspace()    # partial sums of the l2norm scale's gradient
-        self._side = None
+        self._streams = _Streams(self.device)
         self.overlap_heads = os.environ.get("SSD_OVERLAP_HEADS", "1") != "0" and self.device.type == "cuda"
         self.step_count = 0
         self.slots = "adam"                    # what adam_m holds: Adam's first moment, or "sgd_momentum": the velocity
@@ -234,6 +621,10 @@ class SSDEngine:
             self.level_off.append(self.level_off[-1] + h * h * n)
         self.A = self.level_off[-1]            # 8732 for SSD300 (models/ssd_model.py:221)
         self.grids = tuple((h, h) for _, h, _ in self.fm)
+        # the first two layers are the pair ops.conv2d_bwd_data_wgrad_first serves: 3x3 / stride 1, 8 -> 64 -> 64 channels
+        pair = [(nd["kind"], nd["cin"], nd["cout"], nd["k"], nd["stride"]) for nd in self.nodes[:2]]
+        self.first_pair = (pair == [("conv", 8, 64, 3, 1), ("conv", 64, 64, 3, 1)]
+                           and self.nodes[1]["pt"] == self.nodes[1]["pl"] == 1)
 
     def _plan_params(self):
         self.tensors = []
@@ -426,12 +817,14 @@ class SSDEngine:
     # stream next to it, forward and backward; results do not depend on this (disjoint outputs, the one shared
     # accumulation target is ordered by an event).
     SIDE_HEADS = (0, 1)
+    BIG_LEVEL_PIXELS = 16384                   # backward: a level with at least B * h * h of them is a "large" one (SSD300: 38x38 from B = 12, 19x19 from 46)
+
+    _side = property(lambda self: self._streams.side)
+    _ws_side = property(lambda self: self._streams.ws_side)
+    _ws_tail = property(lambda self: self._streams.ws_tail)
 
     def _side_stream(self):
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.device, priority=int(os.environ.get("SSD_SIDE_PRIO", "0")))
-            self._ws_side = ops.MatchWorkspace()
-        return self._side
+        return self._streams.side_stream()
 
     def forward(self, x, precision="bf16"):
         """x: bf16 [B, S, S, 8] (ops.image_prep).  Returns (loc bf16 [B,A,4], conf bf16 [B,A,classes]).
@@ -452,12 +845,7 @@ class SSDEngine:
         acts[0] = x
         main = torch.cuda.current_stream()
         side = self._side_stream() if self.overlap_heads else None
-        tail = None
-        if side is not None and self.tail_stream:
-            if getattr(self, "_tail", None) is None:
-                self._tail = torch.cuda.Stream(device=self.device)
-                self._ws_tail = ops.MatchWorkspace()
-            tail = self._tail
+        tail = self._streams.tail_stream() if side is not None and self.tail_stream else None
         fm_level = {ni: lvl for lvl, (ni, _, _) in enumerate(self.fm)}
 
         def head(lvl, ws):
@@ -474,29 +862,22 @@ class SSDEngine:
             """Launch the head of the feature map node i produced, where it runs next to the trunk."""
             lvl = fm_level.get(i)
             if side is not None and lvl in self.SIDE_HEADS:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                with torch.cuda.stream(side):
-                    side.wait_event(ev)
-                    head(lvl, self._ws_side)
+                s, ws = side, self._ws_side
             elif tail is not None and lvl is not None:
                 # the small levels' heads (10x10 and below: a few workgroups each) on a third stream, as soon as their map
                 # exists: next to the extras' chain on the main stream and the 19x19 head on the side stream they cost
                 # nothing, behind them they were 190 us of a nearly idle GPU
-                ev = torch.cuda.Event()
-                ev.record(main)
-                with torch.cuda.stream(tail):
-                    tail.wait_event(ev)
-                    head(lvl, self._ws_tail)
+                s, ws = tail, self._ws_tail
+            else:
+                return
+            with _Streams.behind(s, main):
+                head(lvl, ws)
 
         self.bits_valid = set()
         for i, nd in enumerate(self.nodes):
             if (self.chain_start is not None and i == self.chain_start - 1 and "fwd" in self.chain and tail is not None
                     and self.chain_prefetch):
-                ev = torch.cuda.Event()                   # the chain's packed filters into L2 while the layer in front of it runs
-                ev.record(main)
-                with torch.cuda.stream(tail):
-                    tail.wait_event(ev)
+                with _Streams.behind(tail, main):                  # the chain's packed filters into L2 while the layer in front of it runs
                     ops.chain_prefetch([self.chain_pk_fwd[j] for j in range(self.chain_start, len(self.nodes))])
             if i == self.chain_start and "fwd" in self.chain:
                 # nodes i .. end in one launch, one workgroup per image (ops.conv_chain)
@@ -508,8 +889,7 @@ class SSDEngine:
                     rb = c["rbits"].get(j + 1) if want_bits else None
                     layers.append(ops.chain_layer_fwd(self.view(wt, self.param_bf16), self.chain_pk_fwd[j], self.view(bt, self.param), acts[j + 1],
                                                       ndj["stride"], ndj["pt"], ndj["pl"], relu=True, relu_bits=rb))
-                try:
-                    ops.conv_chain(acts[i], layers)
+                if _launched(ops.conv_chain, acts[i], layers):
                     nth = 0
                     for j in range(i, len(self.nodes)):
                         if layers[j - i]["relu_bits"] is not None:
@@ -522,8 +902,7 @@ class SSDEngine:
                                 continue
                         after_node(j)
                     break
-                except NotImplementedError:           # SSD_ERR_UNSUPPORTED: nothing launched
-                    self.chain = set()
+                self.chain = set()
             launch_node(i, c)
             after_node(i)
         for lvl in range(len(self.fm)):
@@ -540,34 +919,27 @@ class SSDEngine:
         nd, acts = self.nodes[i], c["acts"]
         if nd["kind"] == "conv":
             wt, bt = self.conv_params[i]
+            args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"],
+                    nd["hout"], nd["hout"])
             nxt = self.nodes[i + 1] if i + 1 < len(self.nodes) else None
             if nxt is not None and nxt["kind"] == "pool":      # conv + the pooling behind it in one call
                 # nothing but the pooling reads this conv's full-resolution output (the backward pass works from the
                 # pooled map and the winner codes): ask for the pooled map only, where a fused kernel serves the layer
                 pool_only = self.pool_only.get(i, self.skip_fullres)
-                args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"],
-                        nd["pl"], nd["hout"], nd["hout"], True, nxt["hout"] * 2 != nxt["hin"])
+                args += (True, nxt["hout"] * 2 != nxt["hin"])
                 kw = dict(out=acts[i + 1], pool_out=acts[i + 2], code=c["pool_code"][i + 1], ws=self._ws)
-                if pool_only:
-                    try:
-                        ops.conv2d_fwd_pool(*args, pool_only=True, **kw)
-                    except ValueError:            # SSD_ERR_VALUE: no pooling kernel for this shape, nothing launched
-                        pool_only = False
+                if pool_only:                     # (refused with SSD_ERR_VALUE: no pooling kernel for this shape)
+                    pool_only = _launched(ops.conv2d_fwd_pool, *args, pool_only=True, refused=ValueError, **kw)
                 self.pool_only[i] = pool_only
                 if not pool_only:
                     ops.conv2d_fwd_pool(*args, **kw)
             else:
-                args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"],
-                        nd["hout"], nd["hout"])
                 done = False
                 if self.relu_bits is not None and self.relu_bits.get(i + 1, True) and (i + 1) in c["rbits"]:
-                    try:
-                        ops.conv2d_fwd_relubits(*args, c["rbits"][i + 1], out=acts[i + 1], ws=self._ws)
-                        done = True
+                    done = self.relu_bits[i + 1] = _launched(ops.conv2d_fwd_relubits, *args, c["rbits"][i + 1], out=acts[i + 1],
+                                                             ws=self._ws)
+                    if done:
                         self.bits_valid.add(i + 1)
-                    except NotImplementedError:   # SSD_ERR_UNSUPPORTED: nothing launched
-                        pass
-                    self.relu_bits[i + 1] = done
                 if not done:
                     ops.conv2d_fwd(*args, True, out=acts[i + 1], ws=self._ws)
         elif i == 0 or self.nodes[i - 1]["kind"] != "conv":
@@ -683,13 +1055,12 @@ class SSDEngine:
             # head 0 reads the normalised map and its data gradient goes to that map's own buffer (l2norm_bwd turns it into
             # gacts); the ReLU mask stays the un-normalised map's: the normalised one is zero exactly where that one is
             xs[0], dxs[0] = c["l2n_y"], c["l2n_gy"]
-        hl, keep = ops.head_layers(
+        return ops.head_layers(
             xs, self.head_w_t, dxs,
             [self.view(wt, self.grad) for wt, _ in self.head_params], [self.view(bt, self.grad) for _, bt in self.head_params],
             [n * (4 + self.classes) for n in self.num_priors],
             relu_bits=[c["rbits"][a] if ub else None for a, ub in zip(idx, use_bits)],
             relu_src=[None if ub else acts[a] for a, ub in zip(idx, use_bits)])
-        return hl, keep
 
     def bucket_gates(self, buckets):
         """For tensor ranges [(t0, t1)] (the gradient exchange's buckets): the trunk node whose data gradient is the last
@@ -719,376 +1090,24 @@ class SSDEngine:
         if heads is None and self.sparse_heads:
             heads = self.heads_from_dense(dloc, dconf)
         B = heads.B if heads is not None else dloc.shape[0]
-        c = self._acts(B)
-        acts, gacts = c["acts"], c["gacts"]
-        written = [False] * len(acts)
-        main = torch.cuda.current_stream()
-        side = self._side_stream() if self.overlap_heads else None
-        opt_at = {}
-        deferred, defer_nodes = [], set()
-        if fused_adam is not None:
-            ndefer = self.opt_defer
-            trunk_nodes = [node for _, _, node in self.opt_buckets() if node is not None]
-            # the last bucket (lowest node) follows its own weight gradients on the side stream; the `ndefer` before it go to the
-            # END of the main stream, which finishes its chain ~0.3 ms before the side stream does
-            defer_nodes = set(trunk_nodes[max(0, len(trunk_nodes) - 1 - ndefer):len(trunk_nodes) - 1]) if ndefer > 0 else set()
-        if fused_adam is not None:
-            self.step_count += 1
-            t = self.step_count
-            hp = fused_adam
-            kind = hp.get("kind", "adam")
-            if kind == "adam":
-                lr_t = hp["lr"] * math.sqrt(1.0 - hp["beta2"] ** t) / (1.0 - hp["beta1"] ** t)
-                opt_range = lambda t0, t1: self.adam_range(t0, t1, lr_t, hp["beta1"], hp["beta2"], hp["eps"], hp["clip"])
-            elif kind == "sgd_momentum":
-                opt_range = lambda t0, t1: self.sgd_range(t0, t1, hp["lr"], hp["momentum"], hp["nesterov"], hp["decay"],
-                                                          hp["clip"])
-            else:
-                raise ValueError("unknown fused optimizer kind %r" % (kind,))
-            opt_at = {node: (t0, t1) for t0, t1, node in self.opt_buckets()}
-
-        def opt_bucket(node):
-            """Called once the data gradient of `node` (None: of every head) is enqueued on the main stream."""
-            if on_dgrad is not None:
-                on_dgrad(node)
-            if node in opt_at:
-                t0, t1 = opt_at.pop(node)
-                if side is not None and node in defer_nodes:
-                    flush_side()
-                    ev = torch.cuda.Event()
-                    ev.record(side)                    # the bucket's weight gradients are all enqueued there by now
-                    deferred.append((t0, t1, ev))
-                    return
-                # the heads' update rewrites head_w_t, which the large levels' sparse data gradients on the third stream still
-                # read: behind their events as well as behind the main stream
-                readers = list(sparse_head_done.values()) if node is None else []
-
-                def run(ws):
-                    for e in readers:
-                        torch.cuda.current_stream().wait_event(e)
-                    opt_range(t0, t1)
-                on_side(run, [], join=True)
-
-        def on_side(fn, tensors, join=False, now=False):
-            """Run fn (a weight-gradient launch, or with join=True the optimizer, which reads gradients) on the side stream,
-            after everything enqueued so far on the main stream."""
-            if side is None:
-                fn(self._ws)
-                if on_ready:
-                    on_ready(tensors)
-                return
-            if join or now or self.wgrad_group <= 1:
-                flush_side()
-                run_on_side(fn, tensors, None)
-                return
-            # grouped: the side stream is hundreds of microseconds behind the main stream for most of the backward pass, yet every
-            # cross-stream wait costs it ~6 us of idle time (30 of them per step).  `wgrad_group` launches share ONE wait -- on the
-            # event of the LAST of them, which a stream that is behind anyway has long passed
-            pending.append((fn, tensors))
-            if len(pending) >= self.wgrad_group:
-                flush_side()
-
-        pending = []
-
-        def flush_side():
-            if not pending:
-                return
-            ev = torch.cuda.Event()
-            ev.record(main)
-            first = True
-            for fn_, tensors_ in pending:
-                run_on_side(fn_, tensors_, ev if first else False)
-                first = False
-            pending.clear()
-
-        def run_on_side(fn, tensors, ev):
-            """ev: None = wait for the main stream as it is now; an event = wait for it; False = no wait (grouped behind one)."""
-            if ev is None:
-                ev = torch.cuda.Event()
-                ev.record(main)
-            with torch.cuda.stream(side):
-                if ev is not False:
-                    side.wait_event(ev)
-                fn(self._ws_side)
-                if on_ready:
-                    on_ready(tensors)
-
-        # heads.  The two large levels (38x38, 19x19: ~1.1 ms of work) go to the side stream whole, data gradient first, so
-        # that the main stream can walk the small levels and the extras' data-gradient chain (a dozen launches that
-        # each fill a fraction of the chip) underneath them.  The accumulation order into a feature-map gradient is
-        # still "head first, trunk second": the trunk launch waits for the head's event.
-        if side is not None and self.chain_start is not None and "bwd" in self.chain and self.chain_prefetch:
-            if getattr(self, "_tail", None) is None:
-                self._tail = torch.cuda.Stream(device=self.device)
-                self._ws_tail = ops.MatchWorkspace()
-            ev = torch.cuda.Event()                       # the data-gradient chain's packed filters into L2, ~50 us ahead of it
-            ev.record(main)
-            with torch.cuda.stream(self._tail):
-                self._tail.wait_event(ev)
-                ops.chain_prefetch([self.chain_pk_bwd[j] for j in range(self.chain_start, len(self.nodes))])
-            prefetch_done = torch.cuda.Event()
-            prefetch_done.record(self._tail)
-        else:
-            prefetch_done = None
-        sparse_head_done = {}                              # activation index -> event after a large level's sparse data gradient
-        l2n_done = []                                      # the event behind l2norm_bwd (kept only for on_ready's report)
-
-        def l2norm_bwd():
-            """Right behind head 0's data gradient, on its stream: that gradient (w.r.t. the normalised map) becomes gacts of
-            feature map 0 -- written, the trunk accumulates into it afterwards as before -- and the scale's gradient."""
-            a0, sc = self.fm[0][0] + 1, self.l2norm_scale
-            ops.l2norm_bwd(c["l2n_gy"], acts[a0], self.view(sc, self.param), rnorm=c["l2n_r"], out=gacts[a0],
-                           dscale=self.view(sc, self.grad), ws=self._ws_l2n, eps=self.l2norm.eps)
-            if on_ready:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream())
-                l2n_done.append(ev)
+        p = _BackwardPass(self, self._acts(B), heads, dloc, dconf, on_ready, fused_adam, on_dgrad)
+        p.plan_optimizer()                         # host only: which bucket's update follows which node's data gradient
+        p.prefetch_chain()                         # third stream: the data-gradient chain's filters into L2
+        # heads.  The two large levels (38x38, 19x19: ~1.1 ms of work) leave the main stream, data gradient first, so that the
+        # main stream can walk the small levels and the extras' data-gradient chain (a dozen launches that each fill a
+        # fraction of the chip) underneath them.  The accumulation order into a feature-map gradient is still "head
+        # first, trunk second": the trunk launch waits for the head's event.
         if heads is not None:
-            # all levels at once from the compact rows: data gradient on the main stream (every feature-map gradient is
-            # written before the trunk chain accumulates into it), weight gradient next to it on the side stream
-            hl, keep = self._head_layers(c)
-            on_side(lambda ws: ops.heads_bwd_weight_sparse(heads, hl, ws=self._ws_hw),
-                    [i for wt, bt in self.head_params for t in (wt, bt) for i in t.indices], now=True)
-            big_lv = [lvl for lvl, (ni, h, ch) in enumerate(self.fm) if B * h * h >= 16384]
-            small_lv = [lvl for lvl in range(len(self.fm)) if lvl not in big_lv]
-            if side is not None and self.split_heads_dgrad and big_lv and small_lv:
-                # the small maps' gradients head the extras' chain; the 38x38 / 19x19 maps' (most of the launch's time: their
-                # dense maps are ~140 MB of stores) are not read until the chain reaches those maps -- third stream, the
-                # chain's accumulation waits for its event (sparse_head_done)
-                ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=small_lv)
-                if self.l2norm is not None and 0 in small_lv:
-                    l2norm_bwd()
-                if getattr(self, "_tail", None) is None:
-                    self._tail = torch.cuda.Stream(device=self.device)
-                    self._ws_tail = ops.MatchWorkspace()
-                ev = torch.cuda.Event()
-                ev.record(main)
-                with torch.cuda.stream(self._tail):
-                    self._tail.wait_event(ev)
-                    if self.split_heads_dgrad == 2:
-                        # one call per level, the level the chain reaches first (19x19) first: its event does not wait for
-                        # the 38x38 level's 94 MB of stores
-                        for lvl in reversed(big_lv):
-                            ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=[lvl])
-                            if self.l2norm is not None and lvl == 0:
-                                l2norm_bwd()           # in front of the level's event: the trunk and the heads' optimizer wait for it
-                            done = torch.cuda.Event()
-                            done.record(self._tail)
-                            sparse_head_done[self.fm[lvl][0] + 1] = done
-                    else:
-                        ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz, levels=big_lv)
-                        if self.l2norm is not None and 0 in big_lv:
-                            l2norm_bwd()
-                        done = torch.cuda.Event()
-                        done.record(self._tail)
-                        for lvl in big_lv:
-                            sparse_head_done[self.fm[lvl][0] + 1] = done
-            else:
-                ops.heads_bwd_data_sparse(heads, hl, ws=self._ws_hz)
-                if self.l2norm is not None:
-                    l2norm_bwd()
-            for ni, _, _ in self.fm:
-                written[ni + 1] = True
-            del keep
-        big = [lvl for lvl, (ni, h, ch) in enumerate(self.fm) if heads is None and side is not None and B * h * h >= 16384
-               and self.big_heads_side]
-        head_done = {}                                     # activation index -> event after the head's data gradient
-        packed = [None] * len(self.fm)
-
-        def pack(lvl):                                     # loc + conf gradients of one level in the head's channel order
-            h = self.fm[lvl][1]
-            packed[lvl] = ops.head_grad_pack(dloc, dconf, h * h, self.num_priors[lvl], self.classes, self.head_npad[lvl],
-                                             self.level_off[lvl], out=c["packed"][lvl]).view(B, h, h, self.head_npad[lvl])
-
-        pack_side = self.pack_side
-        for lvl in range(len(self.fm) if heads is None else 0):   # the large levels are packed where they are consumed (side stream)
-            if lvl not in big or not pack_side:
-                pack(lvl)
-
-        def masked_dgrad(key, dy, w_t, a, stride, pt, pl, accumulate, ws, out=None):
-            """Data gradient w.r.t. activation a (index), masked by its ReLU sign: from the sign bits where this step's forward
-            pass wrote them and the kernel reads them (learned per call site), else from the bf16 activation.  out: where it
-            goes instead of gacts[a]."""
-            out = gacts[a] if out is None else out
-            if self.relu_bits is not None and a in self.bits_valid and self.relu_bits.get(key, True):
-                try:
-                    ops.conv2d_bwd_data_bits(dy, w_t, c["rbits"][a], acts[a].shape, stride, pt, pl, accumulate=accumulate,
-                                             out=out, ws=ws)
-                    self.relu_bits[key] = True
-                    return
-                except NotImplementedError:
-                    self.relu_bits[key] = False
-            ops.conv2d_bwd_data(dy, w_t, acts[a], acts[a].shape, stride, pt, pl, accumulate=accumulate, out=out, ws=ws)
-
-        def head_dgrad(lvl, ws):
-            ni = self.fm[lvl][0]
-            normed = lvl == 0 and self.l2norm is not None
-            masked_dgrad("head%d" % lvl, packed[lvl], self.head_w_t[lvl], ni + 1, 1, 1, 1, False, ws,
-                         out=c["l2n_gy"] if normed else None)
-            if normed:
-                l2norm_bwd()
-            written[ni + 1] = True
-
-        def head_wgrad(lvl, ws):
-            ni = self.fm[lvl][0]
-            wt, bt = self.head_params[lvl]
-            src = c["l2n_y"] if lvl == 0 and self.l2norm is not None else acts[ni + 1]
-            ops.conv2d_bwd_weight(src, packed[lvl], wt.shape[0], 3, 1, 1, 1, dw=self.view(wt, self.grad),
-                                  dbias=self.view(bt, self.grad), ws=ws)
-
-        if big:
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                for lvl in reversed(big):                  # 19x19 first: the trunk chain reaches it first
-                    if pack_side:
-                        pack(lvl)
-                    head_dgrad(lvl, self._ws_side)
-                    done = torch.cuda.Event()
-                    done.record(side)
-                    head_done[self.fm[lvl][0] + 1] = done
-                for lvl in reversed(big):
-                    head_wgrad(lvl, self._ws_side)
-                    if on_ready:
-                        on_ready([i for t in self.head_params[lvl] for i in t.indices])
-        for lvl in range(len(self.fm) if heads is None else 0):
-            if lvl in big:
-                continue
-            on_side(lambda ws, lvl=lvl: head_wgrad(lvl, ws), [i for t in self.head_params[lvl] for i in t.indices], now=True)
-            head_dgrad(lvl, self._ws)
-        if l2n_done:
-            # the scale's gradient is reported from the side stream like every weight gradient, behind the event of the stream
-            # that ran l2norm_bwd: the reducer records ONE event, on the current stream, when a bucket completes
-            on_side(lambda ws: torch.cuda.current_stream().wait_event(l2n_done[0]), [self.l2norm_scale.index], now=True)
-        opt_bucket(None)
-        # trunk, last layer first
-        unpooled = set()                          # pooling nodes whose backward pass ran inside the next convolution's data gradient
-        first_fused = False
-        chained = set()
-        if self.chain_start is not None and "bwd" in self.chain:
-            # data gradients of nodes end .. chain_start in one launch (ops.conv_chain): the head of the backward pass's
-            # critical path -- nothing large can start before this chain reaches the 19x19 map
-            last = len(self.nodes) - 1
-            assert written[last + 1]
-            layers = []
-            for j in range(last, self.chain_start - 1, -1):
-                ndj = self.nodes[j]
-                use_bits = self.relu_bits is not None and j in self.bits_valid
-                layers.append(ops.chain_layer_dgrad(self.w_t[j], self.chain_pk_bwd[j], gacts[j], ndj["stride"], ndj["pt"], ndj["pl"], accumulate=written[j],
-                                                    mask_bits=c["rbits"][j] if use_bits else None,
-                                                    mask_src=None if use_bits else acts[j]))
-            try:
-                for j in range(last, self.chain_start - 1, -1):
-                    for done in (head_done, sparse_head_done):
-                        if j in done:
-                            main.wait_event(done.pop(j))
-                ops.conv_chain(gacts[last + 1], layers)
-                chained = set(range(self.chain_start, last + 1))
-                for j in chained:
-                    written[j] = True
-            except NotImplementedError:               # SSD_ERR_UNSUPPORTED: nothing launched
-                self.chain = self.chain - {"bwd"}
-        batched_w = set()
-        if chained and side is not None and self.batch_chain_wgrads and self.wgrad_probe is None:
-            # ... and their weight gradients in two launches (slab kernel + slab sums) instead of twelve
-            order = sorted(chained, reverse=True)
-            layers, tens = [], []
-            for j in order:
-                ndj = self.nodes[j]
-                wt, bt = self.conv_params[j]
-                layers.append((acts[j], gacts[j + 1], ndj["cout"], ndj["k"], ndj["stride"], ndj["pt"], ndj["pl"],
-                               self.view(wt, self.grad), self.view(bt, self.grad)))
-                tens += [wt.index, bt.index]
-            try:
-                on_side(lambda ws: ops.conv2d_bwd_weight_batched(layers, ws=ws), tens, now=True)
-                batched_w = set(order)
-            except NotImplementedError:               # SSD_ERR_UNSUPPORTED: nothing launched
-                self.batch_chain_wgrads = False
-        for i in range(len(self.nodes) - 1, -1, -1):
-            nd = self.nodes[i]
-            g_out = gacts[i + 1]
-            assert written[i + 1]
-            if nd["kind"] == "pool":
-                assert not written[i], "a pooled activation cannot also feed a head (the pool gradient overwrites)"
-                if i not in unpooled:                 # (else the convolution behind the pooling already wrote gacts[i])
-                    ops.maxpool2x2_bwd_argmax(c["pool_code"][i], g_out, acts[i].shape, out=gacts[i])
-                written[i] = True
-                continue
-            wt, bt = self.conv_params[i]
-            if i == 0 and first_fused:            # its weight gradient came out of the second layer's data-gradient kernel
-                on_side(lambda ws: None, [wt.index, bt.index])
-                opt_bucket(i)
-                continue
-            def wgrad(ws, i=i, a=acts[i], go=g_out, nd=nd, wt=wt, bt=bt):
-                probe = self.wgrad_probe          # measurement only (bench.py): HIP events around the launches of chosen layers
-                timed = probe is not None and i in probe["nodes"]
-                if timed:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                ops.conv2d_bwd_weight(a, go, nd["cout"], nd["k"], nd["stride"], nd["pt"], nd["pl"], dw=self.view(wt, self.grad),
-                                      dbias=self.view(bt, self.grad), ws=ws)
-                if timed:
-                    e1.record()
-                    probe["events"].append((i, e0, e1))
-            if i in batched_w:
-                pass                                  # (its weight gradient left with the batched launch above)
-            else:
-                on_side(wgrad, [wt.index, bt.index])
-            if i == 0 or i in chained:            # no gradient w.r.t. the image / its data gradient came out of the chain launch
-                opt_bucket(i)
-                continue
-            if (i == 1 and self.fuse_first and not written[1] and self.nodes[0]["kind"] == "conv" and self.nodes[0]["cin"] == 8
-                    and self.nodes[0]["cout"] == 64 and nd["cin"] == 64 and nd["cout"] == 64 and nd["k"] == 3 and nd["stride"] == 1
-                    and nd["pt"] == 1 and nd["pl"] == 1 and self.nodes[0]["k"] == 3 and self.nodes[0]["stride"] == 1
-                    and self.relu_bits is not None and 1 in self.bits_valid):
-                wt0, bt0 = self.conv_params[0]
-                try:
-                    ops.conv2d_bwd_data_wgrad_first(g_out, self.w_t[1], c["rbits"][1], acts[0], dw=self.view(wt0, self.grad),
-                                                    dbias=self.view(bt0, self.grad), ws=self._ws)
-                    first_fused = True
-                    written[1] = True             # (consumed in the kernel: gacts[1] is not written)
-                    opt_bucket(i)
-                    continue
-                except NotImplementedError:       # SSD_ERR_UNSUPPORTED: nothing was launched
-                    self.fuse_first = False
-            prev_is_relu_conv = self.nodes[i - 1]["kind"] == "conv"
-            if i in head_done:                    # a large head wrote gacts[i] on the side stream: accumulate after it
-                main.wait_event(head_done.pop(i))
-            if i in sparse_head_done:
-                main.wait_event(sparse_head_done.pop(i))
-            # a 3x3 / stride-1 convolution right behind a pooling: its data gradient is carried through the pooling in the
-            # convolution's own store stage (no pooled gradient in HBM, no pooling-backward launch) where an LDS-patch kernel
-            # serves the layer; learned at the first call, like pool_only
-            fused = False
-            if (self.fuse_unpool is not None and self.fuse_unpool.get(i, True) and self.nodes[i - 1]["kind"] == "pool" and not written[i] and not written[i - 1]
-                    and nd["k"] == 3 and nd["stride"] == 1 and nd["pt"] == 1 and nd["pl"] == 1):
-                try:
-                    ops.conv2d_bwd_data_unpool(g_out, self.w_t[i], None, c["pool_code"][i - 1], tuple(gacts[i - 1].shape),
-                                               out=gacts[i - 1], ws=self._ws)
-                    fused = True
-                    unpooled.add(i - 1)
-                except NotImplementedError:       # SSD_ERR_UNSUPPORTED: nothing was launched
-                    pass
-                self.fuse_unpool[i] = fused
-            if not fused and prev_is_relu_conv:
-                masked_dgrad("conv%d" % i, g_out, self.w_t[i], i, nd["stride"], nd["pt"], nd["pl"], written[i], self._ws)
-            elif not fused:
-                ops.conv2d_bwd_data(g_out, self.w_t[i], None, acts[i].shape, nd["stride"], nd["pt"], nd["pl"],
-                                    accumulate=written[i], out=gacts[i], ws=self._ws)
-            written[i] = True
-            opt_bucket(i)
-        assert not opt_at
-        flush_side()
-        if prefetch_done is not None:
-            main.wait_event(prefetch_done)                # (joins the third stream even where nothing else ran on it)
-        for ev in sparse_head_done.values():      # (a large level whose map no trunk node accumulated into)
-            main.wait_event(ev)
-        for t0, t1, ev in deferred:
-            main.wait_event(ev)
-            opt_range(t0, t1)
-        if side is not None:
-            main.wait_stream(side)
+            p.heads_sparse()                       # data gradients: main stream, large levels third stream; weight gradients: side
+        else:
+            p.heads_dense()                        # large levels whole on the side stream; the others' weight gradients too
+        p.report_l2norm()
+        p.opt_bucket(None)                         # the heads' optimizer bucket: side stream
+        p.chain_dgrads()                           # main stream, one launch
+        p.chain_wgrads()                           # side stream, one batched launch
+        for i in range(len(self.nodes) - 1, -1, -1):   # trunk, last layer first
+            p.node(i)                              # data gradient: main stream; weight gradient and optimizer bucket: side
+        p.finish()                                 # joins the streams; the deferred optimizer buckets at the end of the main stream
 
     # ---------------------------------------------------------------- optimizer
     def clip_scales(self, clip=0.01):
@@ -1133,10 +1152,9 @@ class SSDEngine:
             self._opt_buckets = out
         return self._opt_buckets
 
-    def adam_range(self, t0, t1, lr_t, beta1, beta2, eps, clip, grad_scale=1.0):
-        """clip_by_norm + Adam + bf16 / transposed copies for parameter tensors t0..t1-1 on the current stream.
-        Per tensor the arithmetic is that of clip_scales() + adam() over the whole flat buffer, bit for bit.
-        clip=None: the gradient is already clipped (and summed over ranks): only grad_scale (1 / world) applies."""
+    def _clip_scales_range(self, t0, t1, clip):
+        """Tensors t0..t1-1 as (slice of the flat buffers, its elements, block -> tensor map relative to t0); unless clip is
+        None, their clip_by_norm scales are computed first, on the current stream."""
         b0, tbo, bt = self._range_table(t0, t1)
         start, n = b0 * self.block, bt.numel() * self.block
         sl = slice(start, start + n)
@@ -1144,6 +1162,13 @@ class SSDEngine:
             _lib.check(self.L.ssd_grad_clip_scales(ops._ptr(self.grad[sl]), n, ops._ptr(tbo), t1 - t0, float(clip),
                                                    ops._ptr(self.sq_partial[b0:]), ops._ptr(self.clip_scale[t0:]),
                                                    ops._ptr(self.grad_norms[t0:]), ops._stream()))
+        return sl, n, bt
+
+    def adam_range(self, t0, t1, lr_t, beta1, beta2, eps, clip, grad_scale=1.0):
+        """clip_by_norm + Adam + bf16 / transposed copies for parameter tensors t0..t1-1 on the current stream.
+        Per tensor the arithmetic is that of clip_scales() + adam() over the whole flat buffer, bit for bit.
+        clip=None: the gradient is already clipped (and summed over ranks): only grad_scale (1 / world) applies."""
+        sl, n, bt = self._clip_scales_range(t0, t1, clip)
         _lib.check(self.L.ssd_adam_step(ops._ptr(self.param[sl]), ops._ptr(self.grad[sl]), ops._ptr(self.adam_m[sl]),
                                         ops._ptr(self.adam_v[sl]), ops._ptr(self.param_bf16[sl]), n, ops._ptr(bt),
                                         ops._ptr(self.clip_scale[t0:]) if clip is not None else None, float(grad_scale),
@@ -1171,13 +1196,7 @@ class SSDEngine:
         velocity lives in adam_m.  decay: decay_table() or None.  Per tensor the arithmetic is that of clip_scales() +
         sgd_momentum() over the whole flat buffer, bit for bit.
         clip=None: the gradient is already clipped (and summed over ranks): only grad_scale (1 / world) applies."""
-        b0, tbo, bt = self._range_table(t0, t1)
-        start, n = b0 * self.block, bt.numel() * self.block
-        sl = slice(start, start + n)
-        if clip is not None:
-            _lib.check(self.L.ssd_grad_clip_scales(ops._ptr(self.grad[sl]), n, ops._ptr(tbo), t1 - t0, float(clip),
-                                                   ops._ptr(self.sq_partial[b0:]), ops._ptr(self.clip_scale[t0:]),
-                                                   ops._ptr(self.grad_norms[t0:]), ops._stream()))
+        sl, n, bt = self._clip_scales_range(t0, t1, clip)
         _lib.check(self.L.ssd_sgd_momentum_step(ops._ptr(self.param[sl]), ops._ptr(self.grad[sl]), ops._ptr(self.adam_m[sl]),
                                                 ops._ptr(self.param_bf16[sl]), n, ops._ptr(bt),
                                                 ops._ptr(self.clip_scale[t0:]) if clip is not None else None,
@@ -1188,14 +1207,9 @@ class SSDEngine:
 
     def clip_range_in_place(self, t0, t1, clip=0.01):
         """clip_by_norm of tensors t0..t1-1 (a contiguous range of the flat gradient) in place, on the current stream."""
-        b0, tbo, bt = self._range_table(t0, t1)
-        start = b0 * self.block
-        n = bt.numel() * self.block
-        g = self.grad[start:start + n]
-        _lib.check(self.L.ssd_grad_clip_scales(ops._ptr(g), n, ops._ptr(tbo), t1 - t0, float(clip),
-                                               ops._ptr(self.sq_partial[b0:]), ops._ptr(self.clip_scale[t0:]),
-                                               ops._ptr(self.grad_norms[t0:]), ops._stream()))
-        _lib.check(self.L.ssd_grad_apply_scale(ops._ptr(g), n, ops._ptr(bt), ops._ptr(self.clip_scale[t0:]), ops._stream()))
+        sl, n, bt = self._clip_scales_range(t0, t1, clip)
+        _lib.check(self.L.ssd_grad_apply_scale(ops._ptr(self.grad[sl]), n, ops._ptr(bt), ops._ptr(self.clip_scale[t0:]),
+                                               ops._stream()))
 
     def accumulate_clipped(self, first):
         if self.grad_acc is None:

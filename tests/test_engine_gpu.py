@@ -330,7 +330,7 @@ def test_schedule_switches_are_bitwise_neutral():
     ref = run()
     assert eng.chain == {"fwd", "bwd"} and eng.batch_chain_wgrads          # the default really is the chained / batched schedule
     switches = [("wgrad_group", 1), ("batch_chain_wgrads", False), ("split_heads_dgrad", 0), ("split_heads_dgrad", 1),
-                ("chain_heads_split", False), ("chain_prefetch", False), ("pack_side", False)]
+                ("chain_heads_split", False), ("chain_prefetch", False), ("pack_side", False), ("tail_stream", False)]
     for name, value in switches:
         saved = getattr(eng, name)
         setattr(eng, name, value)
@@ -341,6 +341,45 @@ def test_schedule_switches_are_bitwise_neutral():
         assert torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2]), name
         assert torch.equal(got[0], ref[0]), name
     assert torch.equal(run()[0], ref[0])
+
+
+def test_dense_head_backward_side_schedule_is_bitwise_neutral():
+    """The dense head branch's side-stream part (sparse_heads=False: the two large levels' gradient packing, data and weight
+    gradients on the side stream, the trunk's accumulation behind their events) against the same launches on the main stream:
+    every switch that governs it leaves predictions and every gradient equal bit for bit.  Batch 46 is the smallest at which
+    both large levels (38x38, 19x19) take the side path: 19 * 19 * 46 = 16606 pixels, 45 gives 16245."""
+    import ssd_object_detection_amd.ops as ops
+    from ssd_object_detection_amd.engine import SSDEngine
+    B = 46
+    eng = SSDEngine(classes=81, seed=13, sparse_heads=False)
+    assert not eng.sparse_heads
+    assert [lvl for lvl, (_, h, _) in enumerate(eng.fm) if B * h * h >= SSDEngine.BIG_LEVEL_PIXELS] == [0, 1]
+    assert (B - 1) * eng.fm[1][1] ** 2 < SSDEngine.BIG_LEVEL_PIXELS
+    g = torch.Generator().manual_seed(43)
+    x = ops.image_prep(torch.rand((B, 300, 300, 3), generator=g).cuda())
+    dloc = (torch.randn((B, 8732, 4), generator=g) * 1e-3).bfloat16().cuda()
+    dconf = (torch.randn((B, 8732, 81), generator=g) * 1e-3).bfloat16().cuda()
+
+    def run():
+        eng.grad.zero_()
+        loc, conf = eng.forward(x)
+        eng.backward(dloc, dconf)
+        torch.cuda.synchronize()
+        return eng.grad.clone(), loc.clone(), conf.clone()
+
+    ref = run()
+    assert eng.overlap_heads and eng.big_heads_side and eng.pack_side      # the default really is the side-stream schedule
+    for name, value in [("big_heads_side", False), ("pack_side", False), ("overlap_heads", False)]:
+        saved = getattr(eng, name)
+        setattr(eng, name, value)
+        try:
+            got = run()
+        finally:
+            setattr(eng, name, saved)
+        assert torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2]), name
+        assert torch.equal(got[0], ref[0]), name
+    got = run()
+    assert torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2]) and torch.equal(got[0], ref[0])
 
 
 def test_train_step_at_batch_64():
