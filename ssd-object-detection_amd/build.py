@@ -31,6 +31,9 @@ PER_FILE = {
     # ReLU is fmaxf(x, 0): with NaNs honoured every one of them is preceded by the sNaN-quieting v_max(x, x) -- 1 800 vector
     # instructions over the convolution epilogues, all on finite data
     "conv.hip": ["-fno-honor-nans"],
+    # conv.hip's flags for the files split off it (k_maxpool_* are fmaxf too)
+    "conv_wgrad.hip": ["-fno-honor-nans"],
+    "conv_aux.hip": ["-fno-honor-nans"],
 }
 
 

@@ -1,19 +1,16 @@
-// Convolution stack for gfx950 (MI355X): NHWC bf16 implicit-GEMM convolutions on MFMA.
+// Convolution stack for gfx950 (MI355X): NHWC bf16 implicit-GEMM convolutions on MFMA, forward and data gradient.
 //
 // Replaces the TensorFlow kernels behind SSDObjectDetectionModel._build (models/ssd_model.py:74-171)
-// and their autodiff (tape.gradient, :248): Conv2D 3x3/1x1 (+bias, +ReLU) forward, data gradient
-// and weight gradient, and 2x2 max-pooling forward/backward.  TF "SAME" padding is asymmetric for
-// stride 2 (pad_before = pad_total/2, the remainder after) and is passed explicitly as (pad_t, pad_l).
+// and their autodiff (tape.gradient, :248): Conv2D 3x3/1x1 (+bias, +ReLU) forward and data gradient.  TF "SAME" padding is
+// asymmetric for stride 2 (pad_before = pad_total/2, the remainder after) and is passed explicitly as (pad_t, pad_l).
 //
-// Kernels (DESIGN.md section 4 has the table): forward and data gradient on k_conv3x3_patch32 / k_conv3x3_p512 (3x3 with the
-// halo patch in LDS), k_conv3x3_c64b (64 -> 64), k_conv0_fwd (image layer), k_conv_igemm_8ph / k_conv_igemm_dma (implicit GEMM,
-// split-K through k_igemm_finalize); weight gradient on k_conv3x3_wgrad_patch, k_conv_wgrad_tile, k_conv0_wgrad and k_conv_wgrad
-// (+ _batched), fp32 slabs per pixel split summed in fixed order by k_wgrad_reduce2 / k_wgrad_reduce_wide; pooling, weight
-// transposes, casts and the head-gradient packing.  The dispatch and the C entries are at the end of the file.
+// Kernels (DESIGN.md section 4 has the table): k_conv3x3_patch32 / k_conv3x3_p512 (3x3 with the halo patch in LDS),
+// k_conv3x3_c64b (64 -> 64; its W0 form also produces the first layer's weight gradient), k_conv0_fwd (image layer),
+// k_conv_igemm_8ph / k_conv_igemm_dma (implicit GEMM, split-K through k_igemm_finalize).  The dispatch (launch_igemm) and the C
+// entries are at the end of the file.  The weight gradient is conv_wgrad.hip; pooling, weight transposes, casts and the
+// head-gradient packing are conv_aux.hip; the development knobs are knobs.hip.
 #include <atomic>
-#include <climits>
 #include <cstdint>
-#include <cstring>
 #include <type_traits>
 #include "common.h"
 #include <hip/hip_bf16.h>
@@ -57,21 +54,10 @@ __global__ void k_igemm_finalize(ConvGeom g, Epilogue ep) {
 // gather address, wave-uniform 1 KiB LDS destination, no VGPR staging, no ds_write).  The swizzled LDS
 // image is produced by choosing which chunk each lane fetches: wave-instruction i fills bank rows
 // 4i..4i+3 = tile rows 8i..8i+7; lane L owns slot L of that KiB.  Padding / out-of-range chunks are
-// fetched from a 16-byte zero block.  Schedule per k-step (two LDS buffers, ONE barrier):
+// fetched from a 16-byte zero block (g_zero16, conv_common.h).  Schedule per k-step (two LDS buffers, ONE barrier):
 //   wait vmcnt(0) + barrier  -> tile ks has landed everywhere and everybody is done reading tile ks-1
 //   issue the DMA of tile ks+1 into the other buffer (in flight during this step's MFMAs)
 //   read fragments of tile ks, 64 MFMAs.
-__device__ __attribute__((aligned(16))) const unsigned g_zero16[4] = {0u, 0u, 0u, 0u};
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-// (a device function, not a call inside the kernel's lambda: with the builtin written there clang's HOST pass silently emitted
-//  no stub for any instantiation of k_conv_igemm_dma -- an undefined symbol at load time, no diagnostic)
-__device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t r, char* lds, unsigned off) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds, 16, off, 0, 0, 0);
-}
-
 template <int BM, int BN, int EPI, int PT>
 __global__ __launch_bounds__((BM / (16 * PT)) * (BN >= 128 ? BN / 64 : 2) * 64) void k_conv_igemm_dma(
     const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ w, ConvGeom g, Epilogue ep) {
@@ -516,11 +502,6 @@ __global__ __launch_bounds__(512) void k_conv_igemm_8ph(const bf16_raw* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// Halo patch of a 16x16 block of output pixels (3x3 / stride 1 / pad 1 kernels below)
-constexpr int PATCH_W = 18;
-constexpr int PATCH_PIX = PATCH_W * PATCH_W;               // 324
-
-// ------------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1 convolution with an LDS-resident input patch (forward, and data gradient with the transposed
 // weights): the halo patch of a block is brought into LDS once per channel chunk and all nine taps read their MFMA
 // fragments from it at shifted addresses; only the weight slice of a tap streams.  32-channel chunks, linear padded images, two workgroups per CU.
@@ -533,12 +514,6 @@ constexpr int PATCH_PIX = PATCH_W * PATCH_W;               // 324
 //   * 80 KB of LDS (two patch buffers, two weight buffers) and <= 128 VGPRs: two workgroups per CU cover each other's
 //     prologue, barriers and store tail; the next chunk's patch is prefetched at the first tap of the current one and
 //     left in flight across the barrier (counted vmcnt).
-// LDS fragment read that carries an alias scope (see lds_read_tr16_scoped): keeps the compiler's waitcnt pass from ordering
-// it behind LDS-DMA requests that are in flight for OTHER buffers.
-__device__ __forceinline__ bf16x8_t lds_read_b128_scoped(const char* __restrict__ p, const char* __restrict__ other) {
-    (void)other;
-    return *reinterpret_cast<const bf16x8_t*>(p);
-}
 constexpr int P32_PITCH = 96;
 constexpr int P32_PATCH = 32 * 1024;                       // 324 px x 96 B = 31104 B, rounded to 32 DMA instructions
 
@@ -1076,12 +1051,6 @@ constexpr int C64B_W0_IMG = 2 * C64B_PATCH;                 // (the staging tile
 constexpr int C64B_W0_SUMS = C64B_W0_IMG + 2 * C64B_IMG;
 constexpr int C64B_W0_LDS = C64B_W0_SUMS + 4 * 3 * 64 * 16; // [wave][column tile][lane] f32x4
 
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-__device__ __forceinline__ s16x4_t lds_read_tr16_scoped(const char* __restrict__ p, const char* __restrict__ other) {
-    (void)other;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-}
-
 template <int EPI, bool W0 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_conv3x3_c64b(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ w, ConvGeom g, Epilogue ep, int tiles_x, int tiles_y,
@@ -1591,1170 +1560,7 @@ __global__ __launch_bounds__(512) void k_conv0_fwd(const bf16_raw* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Weight gradient.  grid (col tiles, co tiles, splits).  Per step 64 pixels.
-constexpr int WG_LD = 288;                   // LDS row stride (bytes) of a [pixel][128 ch] tile: 256 + 32 pad
-
-__device__ __forceinline__ void conv_wgrad_block(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy,
-                                                 float* __restrict__ slab_w, float* __restrict__ slab_b, const ConvGeom& g,
-                                                 int m_per_split, char* smem, const int bidx, const int bidy, const int bidz) {
-    // g: source = x dims (B,H,W,C), destination = dy dims (Ho,Wo,N); mul = stride, div = 1
-    constexpr int TILE = 64 * WG_LD;
-    auto s_dy = [&](int buf) { return smem + buf * (2 * TILE); };
-    auto s_x = [&](int buf) { return smem + buf * (2 * TILE) + TILE; };
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_m = wave & 1, wave_n = wave >> 1;       // m: co, n: (tap,ci) columns
-    const int col0 = bidx * 128, co0 = bidy * 128;
-    const int ktot = g.ldw;                                 // KH*KW*C columns
-    const int m_begin = bidz * m_per_split;
-    const int m_end = min(g.M, m_begin + m_per_split);
-
-    const int cslot = tid & 15, prow = tid >> 4;           // 16-byte column chunk, pixel row (+16j)
-    // this thread's X column chunk -> (tap, channel)
-    const int qx = (col0 >> 3) + cslot;
-    const bool xcol_ok = qx < g.nchunks;
-    const int tapx = xcol_ok ? qx / g.cpt : 0;
-    const int ccx = qx - tapx * g.cpt;
-    const int khx = tapx / g.KW, kwx = tapx - khx * g.KW;
-    const int co_chunk = co0 + cslot * 8;
-    const bool dycol_ok = co_chunk < g.N;
-
-    uint4 rdy[4], rxx[4];
-    auto load_tiles = [&](int mstep) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = mstep + prow + 16 * j;
-            const bool mok = m < m_end;
-            rdy[j] = make_uint4(0, 0, 0, 0);
-            rxx[j] = make_uint4(0, 0, 0, 0);
-            if (mok && dycol_ok) rdy[j] = *reinterpret_cast<const uint4*>(dy + ((long long)m * g.N + co_chunk));
-            if (mok && xcol_ok) {
-                const int b = fdiv(m, g.d_hw);
-                const int rem = m - b * g.d_hw.d;
-                const int oy = fdiv(rem, g.d_w);
-                const int ox = rem - oy * g.d_w.d;
-                const int iy = oy * g.mul - g.pad_t + khx, ix = ox * g.mul - g.pad_l + kwx;
-                if (iy >= 0 && iy < g.H && ix >= 0 && ix < g.W)
-                    rxx[j] = *reinterpret_cast<const uint4*>(x + ((((long long)b * g.H + iy) * g.W + ix) * g.C + ccx * 8));
-            }
-        }
-    };
-    auto store_tiles = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            *reinterpret_cast<uint4*>(s_dy(buf) + (prow + 16 * j) * WG_LD + cslot * 16) = rdy[j];
-            *reinterpret_cast<uint4*>(s_x(buf) + (prow + 16 * j) * WG_LD + cslot * 16) = rxx[j];
-        }
-    };
-
-    f32x4_t acc[4][4];
-    f32x4_t accb[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        accb[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[a][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    const bool do_bias = slab_b != nullptr && bidx == 0 && wave_n == 0;
-    bf16x8_t ones;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-
-    const int nsteps = (m_end - m_begin + 63) / 64;
-    if (nsteps > 0) {
-        load_tiles(m_begin);
-        store_tiles(0);
-    }
-    __syncthreads();
-    // transposing read: lane (16-group gq, index i) supplies the address of k-row (i>>2), columns 4*(i&3)..+3
-    const int gq = lane >> 4, li = lane & 15;
-    const int tr_row = li >> 2, tr_col = (li & 3) * 4;
-    for (int st = 0; st < nsteps; ++st) {
-        const int cur = st & 1;
-        const bool more = st + 1 < nsteps;
-        if (more) load_tiles(m_begin + (st + 1) * 64);
-#pragma unroll
-        for (int ksub = 0; ksub < 2; ++ksub) {
-            bf16x8_t fa[4], fb[4];
-            const int krow = ksub * 32 + gq * 8 + tr_row;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const char* base = s_dy(cur) + krow * WG_LD + (wave_m * 64 + a * 16 + tr_col) * 2;
-                const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(base));
-                const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(base + 4 * WG_LD));
-                union { s16x4_t h[2]; bf16x8_t v; } u;
-                u.h[0] = lo; u.h[1] = hi;
-                fa[a] = u.v;
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const char* base = s_x(cur) + krow * WG_LD + (wave_n * 64 + c * 16 + tr_col) * 2;
-                const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(base));
-                const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(base + 4 * WG_LD));
-                union { s16x4_t h[2]; bf16x8_t v; } u;
-                u.h[0] = lo; u.h[1] = hi;
-                fb[c] = u.v;
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[c], acc[a][c], 0, 0, 0);
-            if (do_bias) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], ones, accb[a], 0, 0, 0);
-            }
-        }
-        if (more) store_tiles(cur ^ 1);
-        __syncthreads();
-    }
-    // partial tile -> slab[z][co][col]  (D[row = co (lane>>4)*4+j][col = lane&15])
-    float* out = slab_w + (long long)bidz * g.N * ktot;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int col = col0 + wave_n * 64 + c * 16 + (lane & 15);
-            if (col >= ktot) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + wave_m * 64 + a * 16 + (lane >> 4) * 4 + j;
-                if (co < g.N) out[(long long)co * ktot + col] = acc[a][c][j];
-            }
-        }
-    if (do_bias && (lane & 15) == 0) {
-        float* ob = slab_b + (long long)bidz * g.N;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + wave_m * 64 + a * 16 + (lane >> 4) * 4 + j;
-                if (co < g.N) ob[co] = accb[a][j];
-            }
-    }
-}
-
-__global__ __launch_bounds__(WG) void k_conv_wgrad(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy,
-                                                   float* __restrict__ slab_w, float* __restrict__ slab_b, ConvGeom g,
-                                                   int m_per_split) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    conv_wgrad_block(x, dy, slab_w, slab_b, g, m_per_split, smem, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// Several small layers' weight gradients in ONE launch (ssd_conv2d_bwd_weight_batched): block b belongs to the layer whose block
-// range holds it and runs exactly the block of k_conv_wgrad it would have been there -- same slabs, same sums, bit for bit.
-constexpr int WGB_MAX = 8;
-struct WgradBatchItem {
-    const bf16_raw* x;
-    const bf16_raw* dy;
-    float* slab_w;
-    float* slab_b;
-    ConvGeom g;
-    int mps, ctiles, mtiles, blk0;
-};
-struct WgradBatchArgs {
-    int count;
-    WgradBatchItem it[WGB_MAX];
-};
-__global__ __launch_bounds__(WG) void k_conv_wgrad_batched(WgradBatchArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < WGB_MAX; ++k) l += (k < a.count && (int)blockIdx.x >= a.it[k].blk0) ? 1 : 0;
-    const WgradBatchItem& it = a.it[l];
-    const int local = (int)blockIdx.x - it.blk0;
-    const int per_split = it.ctiles * it.mtiles;
-    const int bz = local / per_split, r = local - bz * per_split;
-    const int by = r / it.ctiles, bx = r - by * it.ctiles;
-    conv_wgrad_block(it.x, it.dy, it.slab_w, it.slab_b, it.g, it.mps, smem, bx, by, bz);
-}
-
-// ... and their slab sums in one launch: k_wgrad_reduce2's arithmetic per layer
-struct ReduceBatchItem {
-    const float* slab_w;
-    const float* slab_b;
-    float* dw;
-    float* db;
-    long long sw, nw, sb;
-    int nb, ns, blk0;
-    unsigned nbw;
-};
-struct ReduceBatchArgs {
-    int count;
-    ReduceBatchItem it[WGB_MAX];
-};
-__global__ __launch_bounds__(256) void k_wgrad_reduce2_batched(ReduceBatchArgs a) {
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < WGB_MAX; ++k) l += (k < a.count && (int)blockIdx.x >= a.it[k].blk0) ? 1 : 0;
-    const ReduceBatchItem& it = a.it[l];
-    const unsigned local = blockIdx.x - (unsigned)it.blk0;
-    if (local < it.nbw) {
-        const long long i = ((long long)local * 256 + threadIdx.x) * 4;
-        if (i >= it.nw) return;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int z = 0; z < it.ns; ++z) {
-            const float4 v = *reinterpret_cast<const float4*>(it.slab_w + (long long)z * it.sw + i);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        *reinterpret_cast<float4*>(it.dw + i) = s;
-    } else {
-        const int i = (int)(local - it.nbw) * 256 + threadIdx.x;
-        if (i >= it.nb) return;
-        float s = 0.f;
-        for (int z = 0; z < it.ns; ++z) s += it.slab_b[(long long)z * it.sb + i];
-        it.db[i] = s;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient as a plain GEMM over pixels, 256 output channels x 256 (tap, ci) columns per workgroup, 64 pixels
-// per step (the 1x1 and the strided layers with >= 256 channels; the 3x3 / stride-1 layers use the patch kernel below).
-//   dW[co][col] += sum_m dY[m][co] * Xcol[m][col]
-// Both tiles are [pixel][256 channels] images (512-byte rows) filled by buffer LDS-DMA (a lane whose pixel / column is
-// padding gets an out-of-range offset = zeros) and read with transposing LDS reads.  The 32-byte column groups of a
-// row are XORed with (row & 7): the eight consecutive rows of a half-wave read then hit eight bank groups, and since
-// the key has period 8 every read address is a per-lane base + immediate.  Eight waves (2 x 4), each 128 co x 64 cols
-// = 32 accumulator tiles, 64 MFMAs per step; two LDS buffers (128 KB), one barrier per step.
-// Transposing LDS read whose access carries an alias scope (the __restrict__ pair, inlined).  The compiler's waitcnt pass
-// orders an LDS read behind every in-flight LDS-DMA (s_waitcnt vmcnt(0)) unless the read has scope information; without it
-// the first fragment read of a step waited for the NEXT tile's DMA issued just before, i.e. the double buffer never
-// overlapped a transfer with the MFMAs.  The kernels order DMA and reads themselves (s_waitcnt vmcnt + barrier per step).
-// (lds_read_tr16_scoped: defined in front of k_conv3x3_c64b)
-
-constexpr int WT_TILE = 64 * 512;                          // one [64 px][256 ch] image
-// Four 32-pixel stages (one MFMA k-sub-step each), three stages of DMA in flight behind a COUNTED vmcnt -- the step does not
-// wait for the DMA it has just issued, and a stage's latency hides under three sub-steps of MFMAs.
-__global__ __launch_bounds__(512) void k_conv_wgrad_tile(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy,
-                                                         float* __restrict__ slab_w, float* __restrict__ slab_b, ConvGeom g,
-                                                         int m_per_split, int nsplit, int cout) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wave_m = wave & 1, wave_n = wave >> 1;           // 128 channels x 64 columns per wave
-    // XCD-aware order when the splits are a multiple of 8: all tiles of one pixel split run consecutively on ONE XCD
-    // (workgroup L -> XCD L % 8) and share its rows through that L2; otherwise plain order, which keeps every XCD busy
-    const int ktot = g.ldw;
-    const int ctiles = (ktot + 255) >> 8, mtiles = (cout + 255) >> 8, tiles = ctiles * mtiles;
-    int split, tile;
-    if ((nsplit & 7) == 0) {
-        const int kx = blockIdx.x >> 3;
-        split = (kx / tiles) * 8 + (blockIdx.x & 7);
-        tile = kx % tiles;
-    } else {
-        split = blockIdx.x / tiles;
-        tile = blockIdx.x - split * tiles;
-    }
-    if (split >= nsplit) return;
-    const int bx = tile % ctiles, by = tile / ctiles;
-    const int col0 = bx * 256, co0 = by * 256;
-    const int m_begin = split * m_per_split;
-    const int m_end = min(g.M, m_begin + m_per_split);
-
-    // DMA: instruction i (= wave + 8j, j < 4) fills tile rows 2i, 2i+1; lane L -> row 2i + (L>>5), physical chunk L & 31
-    const __amdgpu_buffer_rsrc_t dyres = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, (unsigned)g.M * (unsigned)g.N * 2u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (unsigned)g.B * g.H * g.W * g.C * 2u, 0x00020000);
-    constexpr unsigned OOB = 0xfffffff0u;
-    const int drow = lane >> 5;
-    int rowj[4];
-    unsigned dycol[4], xcol[4];                                // byte offset of the lane's chunk inside a pixel row, OOB if padding
-    int xkh[4], xkw[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = 2 * (wave + 8 * j) + drow;
-        rowj[j] = row;
-        const int pc = lane & 31;                              // physical 16-byte chunk
-        const int lg = ((pc >> 1) & 8) | (((pc >> 1) ^ row) & 7);   // logical 32-byte group
-        const int ch = (lg * 2 + (pc & 1)) * 8;                // channel / column of the tile
-        dycol[j] = co0 + ch < g.N ? (unsigned)(co0 + ch) * 2u : OOB;
-        const int q = (col0 + ch) >> 3;
-        if (q < g.nchunks) {
-            const int tap = q / g.cpt;
-            xcol[j] = (unsigned)(q - tap * g.cpt) * 16u;
-            xkh[j] = tap / g.KW;
-            xkw[j] = tap - xkh[j] * g.KW;
-        } else {
-            xcol[j] = OOB; xkh[j] = 0; xkw[j] = 0;
-        }
-    }
-    const bool pointwise = g.KH == 1 && g.KW == 1 && g.mul == 1 && g.pad_t == 0 && g.pad_l == 0;   // source pixel = output pixel
-    constexpr int NJ = 2;                                        // DMA instructions per wave, operand and stage
-    constexpr int XOFF = WT_TILE / 2;                            // the x image of a stage starts here
-    auto issue_dma = [&](int mstep, int buf) {
-        char* base = smem + buf * (2 * XOFF);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int m = mstep + rowj[j];
-            const bool mok = m < m_end;
-            const unsigned od = (unsigned)m * (unsigned)g.N * 2u + dycol[j];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(dyres, (lds_void*)(base + (wave + 8 * j) * 1024), 16,
-                                                     (mok && dycol[j] != OOB) ? od : OOB, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int m = mstep + rowj[j];
-            bool ok = m < m_end && xcol[j] != OOB;
-            unsigned pix;
-            if (pointwise) {
-                pix = (unsigned)m;
-            } else {
-                const int mm = ok ? m : 0;
-                const int b = fdiv(mm, g.d_hw);
-                const int rem = mm - b * g.d_hw.d;
-                const int oy = fdiv(rem, g.d_w);
-                const int ox = rem - oy * g.d_w.d;
-                const int iy = oy * g.mul - g.pad_t + xkh[j], ix = ox * g.mul - g.pad_l + xkw[j];
-                ok = ok && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-                pix = (unsigned)((b * g.H + iy) * g.W + ix);
-            }
-            const unsigned ox_ = pix * (unsigned)g.C * 2u + xcol[j];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_void*)(base + XOFF + (wave + 8 * j) * 1024), 16,
-                                                     ok ? ox_ : OOB, 0, 0, 0);
-        }
-    };
-
-    f32x4_t acc[8][4];
-    f32x4_t accb[8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        accb[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[a][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    const bool do_bias = slab_b != nullptr && bx == 0 && wave_n == 0;
-    bf16x8_t ones;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-
-    // MFMA k index <-> tile row: sub-step ksub, lane group gq, `half`: row = 32 ksub + 16 (gq>>1) + 8 half + 4 (gq&1) + (li>>2)
-    const int gq = lane >> 4, li = lane & 15;
-    const int kk0 = (gq >> 1) * 16 + (gq & 1) * 4 + (li >> 2);
-    const int key = kk0 & 7;
-    int abase[8], bbase[4];
-#pragma unroll
-    for (int a = 0; a < 8; ++a) abase[a] = kk0 * 512 + ((wave_m * 8 + (a ^ key)) << 5) + (li & 3) * 8;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int gl = wave_n * 4 + c;
-        bbase[c] = XOFF + kk0 * 512 + (((gl & 8) | ((gl & 7) ^ key)) << 5) + (li & 3) * 8;
-    }
-    auto rd = [&](int addr) { return lds_read_tr16_scoped(smem + addr, smem); };
-
-    const int nsteps = (m_end - m_begin + 31) / 32;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-        if (p < nsteps) issue_dma(m_begin + p * 32, p);
-    auto run = [&](auto bias_tag) {
-        constexpr bool BIAS = decltype(bias_tag)::value;
-        for (int st = 0; st < nsteps; ++st) {
-            // stage st has landed when at most the two younger stages' 2 * NJ instructions each are still in flight
-            const int younger = min(2, nsteps - 1 - st);
-            if (younger == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                    // ... for every wave; and stage st - 1's buffer is free (raw barrier:
-            asm volatile("" ::: "memory");                   //  __syncthreads() would wait for vmcnt(0) first)
-            if (st + 3 < nsteps) issue_dma(m_begin + (st + 3) * 32, (st + 3) & 3);
-            const int boff = (st & 3) * (2 * XOFF);
-            bf16x8_t fb[4], fa[8];
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int half = 0; half < 2; ++half)
-                    reinterpret_cast<s16x4_t*>(&fb[c])[half] = rd(bbase[c] + boff + half * 4096);
-#pragma unroll
-            for (int a = 0; a < 8; ++a)
-#pragma unroll
-                for (int half = 0; half < 2; ++half)
-                    reinterpret_cast<s16x4_t*>(&fa[a])[half] = rd(abase[a] + boff + half * 4096);
-#pragma unroll
-            for (int a = 0; a < 8; ++a) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[c], acc[a][c], 0, 0, 0);
-                if constexpr (BIAS) accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], ones, accb[a], 0, 0, 0);
-            }
-        }
-    };
-    if (do_bias) run(std::true_type{}); else run(std::false_type{});
-
-    float* out = slab_w + (long long)split * g.N * ktot;
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int col = col0 + wave_n * 64 + c * 16 + (lane & 15);
-            if (col >= ktot) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + wave_m * 128 + a * 16 + (lane >> 4) * 4 + j;
-                if (co < g.N) out[(long long)co * ktot + col] = acc[a][c][j];
-            }
-        }
-    if (do_bias && (lane & 15) == 0) {
-        float* ob = slab_b + (long long)split * g.N;
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + wave_m * 128 + a * 16 + (lane >> 4) * 4 + j;
-                if (co < g.N) ob[co] = accb[a][j];
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient of a 3x3 / stride 1 / pad 1 convolution with LDS-resident tiles ("patch" form).
-// A workgroup owns 64 output channels x 64 input channels (one channel chunk) x all nine taps, and walks a range
-// of 16x16 output-pixel blocks.  Per block it brings in the dY tile [256 px][64 co] and the 18x18 halo patch of X
-// [324 px][64 ci] ONCE (LDS-DMA, double-buffered) and accumulates
-//     dW[co][t][ci] += sum_px dY[px][co] * X[px + shift(t)][ci]          for the nine taps t
-// with both operands fetched by transposing LDS reads (the patch at tap-shifted addresses).  The 144 accumulator
-// tiles (4 co-tiles x 9 taps x 4 ci-tiles) are dealt to eight waves, 18 each (2 co-tiles x 9 taps x 1 ci-tile), so
-// that all four SIMDs carry the same MFMA load (one wave per tap left one SIMD with 3 waves and the others with 2).
-// ~128 MACs per byte brought into the CU, versus 32 for the generic 128x128 tile that re-stages X for every tap.
-// Block geometry (template): BH output rows x 8*BW8 output columns.  The block's pixels are consumed as "pair groups"
-// of 16 (two rows x eight columns); a k-step (32 pixels) takes two of them; an odd count is padded with an all-zero
-// dY group.  Three shapes cover the SSD300 maps: 16x16 (300, 150, 75), 6x40 (38) and 10x24 (19).
-template <int BH, int BW8>
-struct WpGeom {
-    static constexpr int BW = BW8 * 8;
-    static constexpr int PW = BW + 2, PH = BH + 2;             // halo patch
-    static constexpr int PPIX = PW * PH;
-    static constexpr int P_INSTR = (PPIX * 8 + 63) / 64;       // one-KiB DMA instructions (8 pixels each)
-    static constexpr int P_BYTES = P_INSTR * 1024;
-    static constexpr int NPG = (BH / 2) * BW8;                 // pair groups
-    static constexpr int KS = (NPG + 1) / 2;                   // k-steps per block
-    static constexpr int DY_PIX = KS * 32;
-    static constexpr int DY_BYTES = DY_PIX * 128;
-    static constexpr int DY_INSTR = DY_PIX / 8;
-    static constexpr int BUF = DY_BYTES + P_BYTES;             // one buffer: dY tile + X patch
-    static_assert(BH % 2 == 0 && DY_INSTR % 8 == 0, "block shape");
-};
-
-// 32-byte column group permutation of a 128-byte pixel row.  A half-wave of a transposing read touches 8 CONSECUTIVE
-// pixel rows (any alignment: taps shift them); (p & 1, (p >> 1) & 3) then takes all eight values, i.e. the eight
-// 32-byte pieces fall into eight different bank groups.  The key has period 8 in p, which is what lets the reader
-// keep eight per-lane base addresses and reach every (k-step, tap, half) with an immediate offset.
-__device__ __forceinline__ int wp_key(int px) { return (px >> 1) & 3; }
-
-template <int BH, int BW8>
-__global__ __launch_bounds__(512) void k_conv3x3_wgrad_patch(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy,
-                                                             float* __restrict__ slab_w, float* __restrict__ slab_b,
-                                                             ConvGeom g, int tiles_x, int tiles_y, int tiles_per_split,
-                                                             int nsplit, int cout, int single_buf, int xg) {
-    // g: source = x (B,H,W,C), destination = dy (Ho=H, Wo=W, N = ldy)
-    using G = WpGeom<BH, BW8>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    // eight waves, two per SIMD (waves w and w + 4 share one), with UNEQUAL roles: the "loader" waves 0-3 issue all of
-    // the next block's LDS-DMA (an LDS-DMA instruction holds its wave for 100-200 cycles, ~2700 cycles per block) and own
-    // LTAPS = 4 taps x four co-tiles = 16 accumulator tiles of input-channel tile ct = w; their partners 4-7 issue no
-    // DMA and own the other five taps = 20 tiles.  While a loader is stuck in its DMA issue the partner keeps the SIMD's MFMA
-    // pipe busy; with equal shares and everybody issuing DMA both waves of a SIMD stalled together (measured: 459 us
-    // with, 340 us without the DMA, same clock, the difference all in barrier waits).
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ct = wave & 3, role = wave >> 2;              // role 0: loader, first taps; role 1: the rest
-    // work units (split, co tile, ci chunk), chunk fastest.  XCD-aware order (workgroup L runs on XCD L % 8): `xg`
-    // consecutive units -- the channel groups that walk the SAME pixel blocks -- sit on one XCD, so that a dY tile /
-    // X patch is fetched into that L2 once instead of once per group (xg from the host: a divisor of the unit count
-    // per split, or a multiple of it, that still leaves every XCD with work)
-    const int nchunk = g.C >> 6, cotiles = (cout + 63) >> 6;
-    const int nunits = nchunk * cotiles * nsplit;
-    const int j = blockIdx.x >> 3;
-    int id = ((j / xg) * 8 + (blockIdx.x & 7)) * xg + j % xg;
-    if (id >= nunits) return;
-    const int chunk = id % nchunk; id /= nchunk;
-    const int cot = id % cotiles;
-    const int split = id / cotiles;
-    const int co0 = cot * 64, ci0 = chunk * 64;
-    const int ntiles = g.B * tiles_x * tiles_y;
-    const int t_begin = split * tiles_per_split, t_end = min(ntiles, t_begin + tiles_per_split);
-
-    // (buffer-descriptor DMA: 32-bit byte offsets, a lane outside the map / the tile gets an out-of-range offset and the
-    //  hardware writes zeros -- no 64-bit address arithmetic and no zero block)
-    const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (unsigned)g.B * g.H * g.W * g.C * 2u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dyres = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, (unsigned)g.B * g.Ho * g.Wo * g.N * 2u, 0x00020000);
-    constexpr unsigned WP_OOB = 0xfffffff0u;
-    // DMA ownership: instruction i of the dY tile / of the patch goes to loader wave i % 4
-    auto issue_dma = [&](int t, int buf) {
-        int r = t;
-        const int tx = r % tiles_x; r /= tiles_x;
-        const int ty = r % tiles_y;
-        const int b = r / tiles_y;
-        const int y0 = ty * BH, x0 = tx * G::BW;
-        char* base = smem + buf * G::BUF;
-#pragma unroll
-        for (int j = 0; j < G::DY_INSTR / 4; ++j) {
-            const int i = ct + 4 * j;                       // 8 pixel slots x 128 B per instruction
-            const int kk = 8 * i + (lane >> 3), sl = lane & 7;
-            const int c16 = (((sl >> 1) ^ wp_key(kk)) << 1) | (sl & 1);
-            const int pg = kk >> 4;                         // pair group -> (row pair, column group)
-            const int rp = pg / BW8, xg = pg - rp * BW8;
-            const int y = y0 + 2 * rp + ((kk >> 3) & 1), xx = x0 + xg * 8 + (kk & 7);
-            const int co = co0 + c16 * 8;
-            const bool ok = pg < G::NPG && y < g.Ho && xx < g.Wo && co < g.N;
-            const unsigned off = ((unsigned)((b * g.Ho + y) * g.Wo + xx) * (unsigned)g.N + (unsigned)co) * 2u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(dyres, (lds_void*)(base + i * 1024), 16, ok ? off : WP_OOB, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < (G::P_INSTR + 3) / 4; ++j) {
-            const int i = ct + 4 * j;
-            if (i < G::P_INSTR) {
-                const int pp = 8 * i + (lane >> 3), sl = lane & 7;
-                const int c16 = (((sl >> 1) ^ wp_key(pp)) << 1) | (sl & 1);
-                const int py = pp / G::PW, px = pp - py * G::PW;
-                const int iy = y0 - 1 + py, ix = x0 - 1 + px;
-                const bool ok = pp < G::PPIX && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-                const unsigned off = ((unsigned)((b * g.H + iy) * g.W + ix) * (unsigned)g.C + (unsigned)(ci0 + c16 * 8)) * 2u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_void*)(base + G::DY_BYTES + i * 1024), 16, ok ? off : WP_OOB, 0, 0, 0);
-            }
-        }
-    };
-
-    constexpr int LTAPS = 4;                                // taps of a loader wave; its partner takes the other 9 - LTAPS (3 | 6 measured the same)
-    f32x4_t acc[4][9 - LTAPS];                              // [co tile][tap of this role]
-    f32x4_t accb[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        accb[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t5 = 0; t5 < 9 - LTAPS; ++t5) acc[a][t5] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    const bool do_bias = slab_b != nullptr && chunk == 0 && ct == 0 && role == 1;
-    bf16x8_t ones;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-
-    // two LDS buffers: the next block's DMA is in flight during this block's MFMAs
-    if (t_begin < t_end && role == 0) issue_dma(t_begin, 0);
-    // MFMA k index <-> block pixel: k-step ks, `half` select pair group pg = 2ks + half = (row pair rp, column group xg);
-    // within it lane group gq and the lane select row 2rp + (gq>>1), column 8xg + 4*(gq&1) + (li>>2), so that the 8 rows
-    // of a half-wave instruction are consecutive pixels.  All address arithmetic is hoisted: the dY row of a lane is
-    // base + immediate, and a patch row is one of eight per-lane bases (pixel offset mod 8) + immediate.
-    const int gq = lane >> 4, li = lane & 15;
-    int abase[4];
-    {
-        const int kk0 = (gq >> 1) * 8 + (gq & 1) * 4 + (li >> 2);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) abase[a] = kk0 * 128 + ((a ^ wp_key(kk0)) << 5) + (li & 3) * 8;
-    }
-    int gbase[8];
-    {
-        const int p0 = (gq >> 1) * G::PW + (gq & 1) * 4 + (li >> 2);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) gbase[r] = G::DY_BYTES + (p0 + r) * 128 + ((ct ^ wp_key(p0 + r)) << 5) + (li & 3) * 8;
-    }
-    typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-    // fragments of one k-step: 8 dY reads + 2 patch reads per tap (all with immediate offsets)
-    struct Frag { bf16x8_t fa[4]; bf16x8_t fb[9 - LTAPS]; };
-    // the block loop exists per role (and with / without the bias MFMAs) so that its body has no branch: the k-steps of
-    // a block are one basic block, software-pipelined by hand (fragments of k-step ks+1 are read during the MFMAs of ks)
-    auto run = [&](auto role_tag, auto bias_tag) {
-        constexpr int ROLE = decltype(role_tag)::value;
-        constexpr bool BIAS = decltype(bias_tag)::value;
-        constexpr int TAP0 = ROLE == 0 ? 0 : LTAPS, NTAP = ROLE == 0 ? LTAPS : 9 - LTAPS;
-        auto load_frag = [&](Frag& f, const int (&ab)[4], const int (&gb)[8], auto ks_tag) {
-            constexpr int ks = decltype(ks_tag)::value;
-#pragma unroll
-            for (int half = 0; half < 2; ++half)
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-                    reinterpret_cast<s16x4_t*>(&f.fa[a])[half] =
-                        lds_read_tr16_scoped(smem + ab[a] + (ks * 2 + half) * 2048, smem);
-#pragma unroll
-            for (int t5 = 0; t5 < NTAP; ++t5)
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    const int tap = TAP0 + t5;
-                    const int pg = (ks * 2 + half) < G::NPG ? (ks * 2 + half) : 0;   // padding group: any finite data (dY is zero there)
-                    const int rp = pg / BW8, xg = pg - rp * BW8;
-                    const int ctap = (2 * rp + tap / 3) * G::PW + xg * 8 + (tap % 3);   // compile-time pixel offset
-                    reinterpret_cast<s16x4_t*>(&f.fb[t5])[half] =
-                        lds_read_tr16_scoped(smem + gb[ctap & 7] + (ctap >> 3) * 1024, smem);
-                }
-        };
-        for (int t = t_begin; t < t_end; ++t) {
-            const int cur = (t - t_begin) & 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if constexpr (ROLE == 0) { if (t + 1 < t_end) issue_dma(t + 1, cur ^ 1); }
-            const int boff = cur * G::BUF;
-            int ab[4], gb[8];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) ab[a] = abase[a] + boff;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) gb[r] = gbase[r] + boff;
-            Frag f0, f1;
-            auto mma = [&](const Frag& f) {
-#pragma unroll
-                for (int t5 = 0; t5 < NTAP; ++t5)
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-                        acc[a][t5] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.fa[a], f.fb[t5], acc[a][t5], 0, 0, 0);
-                if constexpr (BIAS) {
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.fa[a], ones, accb[a], 0, 0, 0);
-                }
-            };
-            // interleave: one MFMA, then one LDS read of the next k-step
-            auto weave = [&]() {
-                constexpr int NR = 8 + 2 * NTAP, NM = 4 * NTAP;          // reads of the next k-step, MFMAs of this one
-                constexpr int PAIRS = NR < NM ? NR : NM;
-                if constexpr (NR > PAIRS) {                             // more reads than MFMAs: the surplus goes first
-                    __builtin_amdgcn_sched_group_barrier(0x100, NR - PAIRS, 0);
-                }
-#pragma unroll
-                for (int i = 0; i < PAIRS; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                constexpr int REST = NM - PAIRS + (BIAS ? 4 : 0);
-                if constexpr (REST > 0) __builtin_amdgcn_sched_group_barrier(0x008, REST, 0);
-            };
-            static_assert(G::KS == 8, "the hand-unrolled pipeline below assumes eight k-steps per block");
-            load_frag(f0, ab, gb, std::integral_constant<int, 0>{});
-            // the woven fragment-read / MFMA stream of a block runs at LOW priority, the top of the block (wait, barrier, the
-            // loaders' DMA issue, address set-up, first fragments) at high: the two waves of a SIMD are in different phases for
-            // most of a block (loader / partner), and the one in its MFMAs no longer holds the other one up: +3-5 % per layer
-            __builtin_amdgcn_s_setprio(0);
-            load_frag(f1, ab, gb, std::integral_constant<int, 1>{}); mma(f0); weave();
-            load_frag(f0, ab, gb, std::integral_constant<int, 2>{}); mma(f1); weave();
-            load_frag(f1, ab, gb, std::integral_constant<int, 3>{}); mma(f0); weave();
-            load_frag(f0, ab, gb, std::integral_constant<int, 4>{}); mma(f1); weave();
-            load_frag(f1, ab, gb, std::integral_constant<int, 5>{}); mma(f0); weave();
-            load_frag(f0, ab, gb, std::integral_constant<int, 6>{}); mma(f1); weave();
-            load_frag(f1, ab, gb, std::integral_constant<int, 7>{}); mma(f0); weave();
-            mma(f1);
-            __builtin_amdgcn_s_setprio(3);
-        }
-    };
-    if (role == 0) run(std::integral_constant<int, 0>{}, std::false_type{});
-    else if (do_bias) run(std::integral_constant<int, 1>{}, std::true_type{});
-    else run(std::integral_constant<int, 1>{}, std::false_type{});
-    // slab[split][co][tap][ci]  (dW layout [Cout][kh][kw][Cin], rows = ldy channels)
-    const int ktot = g.ldw;
-    float* out = slab_w + (long long)split * g.N * ktot;
-    const int tap0 = role == 0 ? 0 : LTAPS, ntap = role == 0 ? LTAPS : 9 - LTAPS;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int t5 = 0; t5 < 9 - LTAPS; ++t5) {
-            if (t5 >= ntap) continue;
-            const int col = (tap0 + t5) * g.C + ci0 + ct * 16 + (lane & 15);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + a * 16 + (lane >> 4) * 4 + j;
-                if (co < g.N) out[(long long)co * ktot + col] = acc[a][t5][j];
-            }
-        }
-    if (do_bias && (lane & 15) == 0) {
-        float* ob = slab_b + (long long)split * g.N;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + a * 16 + (lane >> 4) * 4 + j;
-                if (co < g.N) ob[co] = accb[a][j];
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient of the first layer (3x3 / stride 1 / pad 1, 8 input channels = 3 image channels + padding, <= 64
-// output channels): dW[co][tap][ch] = sum_px dY[px][co] * X[px + shift(tap)][ch], 72 columns.  The work is reading dY
-// once (HBM-bound); a workgroup walks 16x16-pixel blocks (dY tile 32 KB + an 18x18 x 16-byte halo patch, LDS-DMA,
-// double-buffered), wave w multiplies k-step w (32 pixels) of every block: 4 channel tiles x 5 column tiles (a column
-// tile = two taps x 8 channels) = 20 MFMAs; the eight partial sums are added in wave order at the end.
-constexpr int W0_DY = 256 * 128;                           // dY tile bytes
-constexpr int W0_PATCH = 6 * 1024;                         // 324 px x 16 B = 5184 B -> 6 DMA instructions
-constexpr int W0_BUF = W0_DY + W0_PATCH;
-
-__global__ __launch_bounds__(512) void k_conv0_wgrad(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy,
-                                                     float* __restrict__ slab_w, float* __restrict__ slab_b, ConvGeom g,
-                                                     int tiles_x, int tiles_y, int tiles_per_split, int cout) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int split = blockIdx.x;
-    const int ntiles = g.B * tiles_x * tiles_y;
-    const int t_begin = split * tiles_per_split, t_end = min(ntiles, t_begin + tiles_per_split);
-
-    auto issue_dma = [&](int t, int buf) {
-        int r = t;
-        const int tx = r % tiles_x; r /= tiles_x;
-        const int ty = r % tiles_y;
-        const int b = r / tiles_y;
-        const int y0 = ty * 16, x0 = tx * 16;
-        char* base = smem + buf * W0_BUF;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                       // dY: slot layout of k_conv3x3_wgrad_patch<16, 2>
-            const int i = wave + 8 * j;
-            const int kk = 8 * i + (lane >> 3), sl = lane & 7;
-            const int c16 = (((sl >> 1) ^ wp_key(kk)) << 1) | (sl & 1);
-            const int pg = kk >> 4;
-            const int y = y0 + 2 * (pg >> 1) + ((kk >> 3) & 1), xx = x0 + (pg & 1) * 8 + (kk & 7);
-            const int co = c16 * 8;
-            const bool ok = y < g.Ho && xx < g.Wo && co < g.N;
-            const bf16_raw* src = ok ? dy + ((unsigned)((b * g.Ho + y) * g.Wo + xx) * (unsigned)g.N + (unsigned)co)
-                                     : reinterpret_cast<const bf16_raw*>(g_zero16);
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(base + i * 1024), 16, 0, 0);
-        }
-        if (wave < 6) {                                     // patch: one 16-byte pixel per lane, row-major 18x18
-            const int pp = wave * 64 + lane;
-            const int py = pp / PATCH_W, px = pp - py * PATCH_W;
-            const int iy = y0 - 1 + py, ix = x0 - 1 + px;
-            const bool ok = pp < PATCH_PIX && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-            const bf16_raw* src = ok ? x + (unsigned)((b * g.H + iy) * g.W + ix) * 8u : reinterpret_cast<const bf16_raw*>(g_zero16);
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(base + W0_DY + wave * 1024), 16, 0, 0);
-        }
-    };
-
-    f32x4_t acc[4][5];
-    f32x4_t accb[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        accb[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 5; ++c) acc[a][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    bf16x8_t ones;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-
-    // this wave's k-step: block rows 2w, 2w+1.  MFMA k index <-> pixel as in k_conv3x3_wgrad_patch
-    const int gq = lane >> 4, li = lane & 15;
-    const int kk0 = (gq >> 1) * 8 + (gq & 1) * 4 + (li >> 2);
-    int abase[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) abase[a] = wave * 4096 + kk0 * 128 + ((a ^ wp_key(kk0)) << 5) + (li & 3) * 8;
-    // patch pixel of tap (0,0) for half 0: row 2w + (gq>>1), column 4 (gq&1) + (li>>2); column tile t: lanes with
-    // (li & 2) == 0 read tap 2t, the others tap 2t+1 (tap 9 does not exist: its columns are never stored)
-    const int p0 = (2 * wave + (gq >> 1)) * PATCH_W + (gq & 1) * 4 + (li >> 2);
-    int bbase[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        int tap = 2 * t + ((li >> 1) & 1);
-        if (tap > 8) tap = 8;
-        bbase[t] = W0_DY + (p0 + (tap / 3) * PATCH_W + tap % 3) * 16 + (li & 1) * 8;
-    }
-    typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-    auto rd = [&](int addr) { return lds_read_tr16_scoped(smem + addr, smem); };
-
-    if (t_begin < t_end) issue_dma(t_begin, 0);
-    for (int t = t_begin; t < t_end; ++t) {
-        const int cur = (t - t_begin) & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (t + 1 < t_end) issue_dma(t + 1, cur ^ 1);
-        const int boff = cur * W0_BUF;
-        bf16x8_t fa[4], fb[5];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) reinterpret_cast<s16x4_t*>(&fa[a])[half] = rd(boff + abase[a] + half * 2048);
-#pragma unroll
-            for (int c = 0; c < 5; ++c) reinterpret_cast<s16x4_t*>(&fb[c])[half] = rd(boff + bbase[c] + half * 8 * 16);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-#pragma unroll
-            for (int c = 0; c < 5; ++c) acc[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[c], acc[a][c], 0, 0, 0);
-            accb[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], ones, accb[a], 0, 0, 0);
-        }
-    }
-    // sum the eight waves' partial tiles in wave order (fixed order: reproducible), through LDS
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);            // [24 tiles][64 lanes][4]
-    for (int w = 0; w < 8; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    f32x4_t v;
-                    if (c < 5) v = acc[a][c < 5 ? c : 0]; else v = accb[a];
-                    f32x4_t* slot = reinterpret_cast<f32x4_t*>(red + ((a * 6 + c) * 64 + lane) * 4);
-                    if (w > 0) { const f32x4_t o = *slot; v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
-                    *slot = v;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // slab[split][co][72]; tile (a, c): D row = co a*16 + (lane>>4)*4 + j, column c*16 + (lane&15)
-    const int ktot = g.ldw;                                 // 72
-    for (int idx = tid; idx < 24 * 64; idx += 512) {
-        const int tile = idx >> 6, l = idx & 63;
-        const int a = tile / 6, c = tile - a * 6;
-        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(red + idx * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int co = a * 16 + (l >> 4) * 4 + j;
-            if (co >= g.N) continue;
-            if (c < 5) {
-                const int col = c * 16 + (l & 15);
-                if (col < ktot) slab_w[((long long)split * g.N + co) * ktot + col] = v[j];
-            } else if (slab_b != nullptr && (l & 15) == 0) {
-                slab_b[(long long)split * g.N + co] = v[j];
-            }
-        }
-    }
-}
-
-// weights and bias in one launch: blocks [0, nbw) reduce the first nw elements of the weight slab (stride sw per split)
-// four at a time, the remaining blocks the nb bias elements (stride sb)
-__global__ __launch_bounds__(256) void k_wgrad_reduce2(const float* __restrict__ slab_w, long long sw, long long nw,
-                                                       float* __restrict__ dw, const float* __restrict__ slab_b, long long sb,
-                                                       int nb, float* __restrict__ db, int nsplit, unsigned nbw) {
-    if (blockIdx.x < nbw) {
-        const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-        if (i >= nw) return;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int z = 0; z < nsplit; ++z) {
-            const float4 v = *reinterpret_cast<const float4*>(slab_w + (long long)z * sw + i);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        *reinterpret_cast<float4*>(dw + i) = s;
-    } else {
-        const int i = (int)(blockIdx.x - nbw) * 256 + threadIdx.x;
-        if (i >= nb) return;
-        float s = 0.f;
-        for (int z = 0; z < nsplit; ++z) s += slab_b[(long long)z * sb + i];
-        db[i] = s;
-    }
-}
-
-// many splits, few outputs (first layer: 512 splits of 4.6 K values): 16 threads per float4 of the output, thread g adds
-// splits g, g+16, ... in order, then the 16 partial sums are added in order: fixed summation order, 16x the parallelism
-__global__ __launch_bounds__(256) void k_wgrad_reduce_wide(const float* __restrict__ slab_w, long long sw, long long nw,
-                                                          float* __restrict__ dw, const float* __restrict__ slab_b, long long sb,
-                                                          int nb, float* __restrict__ db, int nsplit, unsigned nbw) {
-    __shared__ float4 part[256];
-    const int o = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (blockIdx.x < nbw) {
-        const long long i = ((long long)blockIdx.x * 16 + o) * 4;
-        if (i < nw)
-            for (int z = grp; z < nsplit; z += 16) {
-                const float4 v = *reinterpret_cast<const float4*>(slab_w + (long long)z * sw + i);
-                s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w;
-            }
-        part[threadIdx.x] = s4;
-        __syncthreads();
-        if (grp == 0 && i < nw) {
-            float4 t = part[o];
-            for (int k = 1; k < 16; ++k) { const float4 v = part[k * 16 + o]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-            *reinterpret_cast<float4*>(dw + i) = t;
-        }
-    } else {
-        const int i = (int)(blockIdx.x - nbw) * 16 + o;
-        float sacc = 0.f;
-        if (i < nb)
-            for (int z = grp; z < nsplit; z += 16) sacc += slab_b[(long long)z * sb + i];
-        part[threadIdx.x].x = sacc;
-        __syncthreads();
-        if (grp == 0 && i < nb) {
-            float t = part[o].x;
-            for (int k = 1; k < 16; ++k) t += part[k * 16 + o].x;
-            db[i] = t;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// W[co][kh][kw][ci] (bf16) -> Wt[ci][KH-1-kh][KW-1-kw][co] for the data gradient
-__global__ void k_weight_transpose(const bf16_raw* __restrict__ w, bf16_raw* __restrict__ wt, int Cout, int KH, int KW,
-                                   int Cin, int Cout_pad) {
-    // wt has row length KH*KW*Cout_pad (Cout padded to a multiple of 8 with zeros)
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)Cin * KH * KW * Cout_pad;
-    if (i >= total) return;
-    const int co = (int)(i % Cout_pad);
-    long long r = i / Cout_pad;
-    const int kw = (int)(r % KW); r /= KW;
-    const int kh = (int)(r % KH); r /= KH;
-    const int ci = (int)r;
-    bf16_raw v = 0;
-    if (co < Cout) v = w[(((long long)co * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)) * Cin + ci];
-    wt[i] = v;
-}
-
-// All transposed copies of a network in ONE launch: blockIdx.y = tensor, descriptor rows {src, dst, Cout, K, Cin, Cout_pad}
-// (device array of int64), blockIdx.x = 32x32 (co, ci) tile x tap; the tile goes through LDS so that both the read (ci
-// contiguous) and the write (co contiguous) are 64-byte runs.  33 launches of the per-tensor kernel cost 0.26 ms per step.
-__global__ __launch_bounds__(256) void k_weight_transpose_batched(const long long* __restrict__ desc) {
-    __shared__ bf16_raw tile[32][33];
-    const long long* d = desc + (long long)blockIdx.y * 6;
-    const bf16_raw* w = reinterpret_cast<const bf16_raw*>(d[0]);
-    bf16_raw* wt = reinterpret_cast<bf16_raw*>(d[1]);
-    // K field: kernel size in the low byte; bit 8 set = tap-major layout for the sparse head data gradient (sparse.hip):
-    // wt[kh][kw][ci][co] = w[co][kh][kw][ci], not flipped
-    const int Cout = (int)d[2], K = (int)d[3] & 0xff, tapmajor = ((int)d[3] >> 8) & 1, Cin = (int)d[4], Cout_pad = (int)d[5];
-    const int tco = (Cout_pad + 31) >> 5, tci = (Cin + 31) >> 5;
-    int t = blockIdx.x;
-    if (t >= tco * tci * K * K) return;
-    const int tap = t % (K * K); t /= K * K;
-    const int ci0 = (t % tci) * 32, co0 = (t / tci) * 32;
-    const int kh = tap / K, kw = tap - kh * K;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                 // 32 x 8
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int co = co0 + ty + 8 * j, ci = ci0 + tx;
-        bf16_raw v = 0;
-        const int skh = tapmajor ? kh : K - 1 - kh, skw = tapmajor ? kw : K - 1 - kw;
-        if (co < Cout && ci < Cin) v = w[(((long long)co * K + skh) * K + skw) * Cin + ci];
-        tile[ty + 8 * j][tx] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ci = ci0 + ty + 8 * j, co = co0 + tx;
-        if (ci >= Cin || co >= Cout_pad) continue;
-        if (tapmajor) wt[(((long long)kh * K + kw) * Cin + ci) * Cout_pad + co] = tile[tx][ty + 8 * j];
-        else wt[(((long long)ci * K + kh) * K + kw) * Cout_pad + co] = tile[tx][ty + 8 * j];
-    }
-}
-
-// f32 -> bf16 cast (weights after an optimizer step)
-__global__ void k_cast_bf16(const float* __restrict__ src, bf16_raw* __restrict__ dst, long long n) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = f2bf(src[i]);
-}
-
-// image f32 [B,H,W,3] in [0,1] -> bf16 [B,H,W,8], (x-0.5)*2 (models/ssd_model.py:214), channels 3..7 zero
-__global__ void k_image_prep(const float* __restrict__ img, bf16_raw* __restrict__ out, long long npix, int normalize) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    float r = img[3 * i], gch = img[3 * i + 1], b = img[3 * i + 2];
-    if (normalize) { r = (r - 0.5f) * 2.f; gch = (gch - 0.5f) * 2.f; b = (b - 0.5f) * 2.f; }
-    *reinterpret_cast<uint4*>(out + 8 * i) =
-        make_uint4(pack_bf16x2(r, gch), (unsigned)f2bf(b), 0u, 0u);
-}
-
-// 2x2 stride-2 max pooling, NHWC bf16, 8 channels per thread.  pad_b/pad_r = 1 for TF "SAME" on odd sizes.
-__global__ void k_maxpool_fwd(const bf16_raw* __restrict__ x, bf16_raw* __restrict__ y, int B, int H, int W, int C,
-                              int Ho, int Wo) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c8 = C >> 3;
-    const long long total = (long long)B * Ho * Wo * c8;
-    if (i >= total) return;
-    const int c = (int)(i % c8);
-    long long r = i / c8;
-    const int ox = (int)(r % Wo); r /= Wo;
-    const int oy = (int)(r % Ho);
-    const int b = (int)(r / Ho);
-    float best[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) best[k] = -INFINITY;
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-            const int iy = 2 * oy + dy, ix = 2 * ox + dx;
-            if (iy >= H || ix >= W) continue;
-            const uint4 v = *reinterpret_cast<const uint4*>(x + ((((long long)b * H + iy) * W + ix) * C + c * 8));
-            const unsigned wds[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                best[2 * k] = fmaxf(best[2 * k], __uint_as_float(wds[k] << 16));
-                best[2 * k + 1] = fmaxf(best[2 * k + 1], __uint_as_float(wds[k] & 0xffff0000u));
-            }
-        }
-    unsigned o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (__float_as_uint(best[2 * k]) >> 16) | (__float_as_uint(best[2 * k + 1]) & 0xffff0000u);
-    *reinterpret_cast<uint4*>(y + ((((long long)b * Ho + oy) * Wo + ox) * C + c * 8)) = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-// Backward of the pooling + the ReLU in front of it: dx = dy at the first maximum of each window (TF
-// MaxPoolGrad), zero elsewhere and wherever x <= 0 (x is a post-ReLU activation).
-__global__ void k_maxpool_bwd(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ y, const bf16_raw* __restrict__ dy,
-                              bf16_raw* __restrict__ dx, int B, int H, int W, int C, int Ho, int Wo) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c8 = C >> 3;
-    const long long total = (long long)B * Ho * Wo * c8;
-    if (i >= total) return;
-    const int c = (int)(i % c8);
-    long long r = i / c8;
-    const int ox = (int)(r % Wo); r /= Wo;
-    const int oy = (int)(r % Ho);
-    const int b = (int)(r / Ho);
-    const long long oidx = (((long long)b * Ho + oy) * Wo + ox) * C + c * 8;
-    const uint4 yv = *reinterpret_cast<const uint4*>(y + oidx);
-    const uint4 gv = *reinterpret_cast<const uint4*>(dy + oidx);
-    const bf16_raw* yy = reinterpret_cast<const bf16_raw*>(&yv);
-    const bf16_raw* gg = reinterpret_cast<const bf16_raw*>(&gv);
-    bool done[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) done[k] = false;
-#pragma unroll
-    for (int dyy = 0; dyy < 2; ++dyy)
-#pragma unroll
-        for (int dxx = 0; dxx < 2; ++dxx) {
-            const int iy = 2 * oy + dyy, ix = 2 * ox + dxx;
-            if (iy >= H || ix >= W) continue;
-            const long long iidx = (((long long)b * H + iy) * W + ix) * C + c * 8;
-            const uint4 xv = *reinterpret_cast<const uint4*>(x + iidx);
-            const bf16_raw* xx = reinterpret_cast<const bf16_raw*>(&xv);
-            bf16_raw o[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const bool hit = !done[k] && xx[k] == yy[k];
-                o[k] = (hit && bf2f(xx[k]) > 0.f) ? gg[k] : (bf16_raw)0;
-                done[k] = done[k] || hit;
-            }
-            *reinterpret_cast<uint4*>(dx + iidx) = *reinterpret_cast<const uint4*>(o);
-        }
-}
-
-// Pooling with a recorded winner: the forward pass also writes, per pooled element, a 4-bit code = position (2 dy + dx) of
-// the first maximum of its window, or 4 if that maximum is <= 0 (post-ReLU input: no gradient flows).  The backward pass
-// then needs only dy and the codes (1/4 byte per input element) instead of re-reading x and y: 0.97 GB instead of
-// 1.84 GB for the first pool at batch 64.  Same routing rule as k_maxpool_bwd (TF MaxPoolGrad + ReLU mask).
-__global__ void k_maxpool_fwd_argmax(const bf16_raw* __restrict__ x, bf16_raw* __restrict__ y, unsigned* __restrict__ code,
-                                     int B, int H, int W, int C, int Ho, int Wo) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c8 = C >> 3;
-    if (i >= (long long)B * Ho * Wo * c8) return;
-    const int c = (int)(i % c8);
-    long long r = i / c8;
-    const int ox = (int)(r % Wo); r /= Wo;
-    const int oy = (int)(r % Ho);
-    const int b = (int)(r / Ho);
-    float best[8];
-    unsigned pos[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { best[k] = -INFINITY; pos[k] = 4u; }
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-            const int iy = 2 * oy + dy, ix = 2 * ox + dx;
-            if (iy >= H || ix >= W) continue;
-            const uint4 v = *reinterpret_cast<const uint4*>(x + ((((long long)b * H + iy) * W + ix) * C + c * 8));
-            const unsigned wds[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float f = (k & 1) ? __uint_as_float(wds[k >> 1] & 0xffff0000u) : __uint_as_float(wds[k >> 1] << 16);
-                if (f > best[k]) { best[k] = f; pos[k] = (unsigned)(2 * dy + dx); }   // strict: the first maximum wins
-            }
-        }
-    unsigned o[4], cw = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (__float_as_uint(best[2 * k]) >> 16) | (__float_as_uint(best[2 * k + 1]) & 0xffff0000u);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) cw |= (best[k] > 0.f ? pos[k] : 4u) << (4 * k);
-    *reinterpret_cast<uint4*>(y + ((((long long)b * Ho + oy) * Wo + ox) * C + c * 8)) = make_uint4(o[0], o[1], o[2], o[3]);
-    code[i] = cw;
-}
-
-__global__ void k_maxpool_bwd_argmax(const unsigned* __restrict__ code, const bf16_raw* __restrict__ dy, bf16_raw* __restrict__ dx,
-                                     int B, int H, int W, int C, int Ho, int Wo) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c8 = C >> 3;
-    if (i >= (long long)B * Ho * Wo * c8) return;
-    const int c = (int)(i % c8);
-    long long r = i / c8;
-    const int ox = (int)(r % Wo); r /= Wo;
-    const int oy = (int)(r % Ho);
-    const int b = (int)(r / Ho);
-    const uint4 gv = *reinterpret_cast<const uint4*>(dy + ((((long long)b * Ho + oy) * Wo + ox) * C + c * 8));
-    const unsigned g[4] = {gv.x, gv.y, gv.z, gv.w};
-    const unsigned cw = code[i];
-#pragma unroll
-    for (int dyy = 0; dyy < 2; ++dyy)
-#pragma unroll
-        for (int dxx = 0; dxx < 2; ++dxx) {
-            const int iy = 2 * oy + dyy, ix = 2 * ox + dxx;
-            if (iy >= H || ix >= W) continue;
-            const unsigned p = (unsigned)(2 * dyy + dxx);
-            unsigned o[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned lo = ((cw >> (8 * k)) & 15u) == p ? 0x0000ffffu : 0u;
-                const unsigned hi = ((cw >> (8 * k + 4)) & 15u) == p ? 0xffff0000u : 0u;
-                o[k] = g[k] & (lo | hi);
-            }
-            *reinterpret_cast<uint4*>(dx + ((((long long)b * H + iy) * W + ix) * C + c * 8)) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-}
-
-// dloc [B][A][4], dconf [B][A][classes] (bf16) -> one level's padded NHWC gradient [B][H*W][npad].  A pixel's row is the
-// concatenation of its per_cell*4 loc values, its per_cell*classes conf values (both contiguous in the sources) and
-// zero padding.  One thread per 16-byte chunk of the output (8 channels): the sources are only 2-byte aligned
-// (classes = 81 is odd), so they are read element-wise (consecutive lanes -> consecutive addresses) and stored once.
-__global__ void k_head_grad_pack(const bf16_raw* __restrict__ dloc, const bf16_raw* __restrict__ dconf,
-                                 bf16_raw* __restrict__ out, int B, int hw, int per_cell, int classes, int npad,
-                                 int anchors_total, int level_off) {
-    const int cpr = npad >> 3;                                // chunks per row
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)B * hw * cpr) return;
-    const int ch = (int)(i % cpr);
-    const long long r = i / cpr;
-    const int pix = (int)(r % hw);
-    const int b = (int)(r / hw);
-    const int n_loc = per_cell * 4, n_conf = per_cell * classes;
-    const long long anchor0 = (long long)b * anchors_total + level_off + (long long)pix * per_cell;
-    const bf16_raw* pl = dloc + anchor0 * 4;
-    const bf16_raw* pc = dconf + anchor0 * classes - n_loc;
-    if (!((per_cell | level_off | anchors_total) & 1)) {      // even anchor counts: every run 4-byte aligned, two channels per load
-        unsigned w4[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = ch * 8 + 2 * j;
-            w4[j] = n < n_loc ? *reinterpret_cast<const unsigned*>(pl + n)
-                              : (n < n_loc + n_conf ? *reinterpret_cast<const unsigned*>(pc + n) : 0u);
-        }
-        *reinterpret_cast<uint4*>(out + r * npad + ch * 8) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-        return;
-    }
-    bf16_raw v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int n = ch * 8 + j;
-        v[j] = n < n_loc ? pl[n] : (n < n_loc + n_conf ? pc[n] : (bf16_raw)0);
-    }
-    *reinterpret_cast<uint4*>(out + r * npad + ch * 8) =
-        make_uint4((unsigned)v[0] | ((unsigned)v[1] << 16), (unsigned)v[2] | ((unsigned)v[3] << 16),
-                   (unsigned)v[4] | ((unsigned)v[5] << 16), (unsigned)v[6] | ((unsigned)v[7] << 16));
-}
-
-// Development overrides (ssd_dev_knob): A/B timing of kernel variants and forcing a dispatch path in tests, inside one
-// process.  NOT configuration: the product never sets them, nothing is read from the environment, and results never
-// depend on them (every variant computes the same convolution).  Values are relaxed atomics (-1 in the table = unset:
-// the caller's default applies), so concurrent calls are safe.
-struct Knob { const char* name; std::atomic<int> value; };
-constexpr int KNOB_UNSET = INT_MIN;
-Knob g_knobs[] = {{"SSD_ABLATE", {KNOB_UNSET}}, {"SSD_DGRAD_S2", {KNOB_UNSET}}, 
-                  {"SSD_CONV_PATCH", {KNOB_UNSET}}, {"SSD_CONV_TILE", {KNOB_UNSET}}, {"SSD_SPLITK", {KNOB_UNSET}},
-                  {"SSD_WGRAD_PATCH", {KNOB_UNSET}},
-                  {"SSD_WGRAD_PATCH_SHAPE", {KNOB_UNSET}}, {"SSD_WGRAD_TILE", {KNOB_UNSET}},
-                  {"SSD_CONV_PATCH_FLAT", {KNOB_UNSET}}, {"SSD_WGRAD_FIRST", {KNOB_UNSET}}, {"SSD_CONV_FIRST", {KNOB_UNSET}},
-                  {"SSD_WGRAD_PATCH_XCD", {KNOB_UNSET}}, {"SSD_CONV_C64", {KNOB_UNSET}}, {"SSD_CONV_POOL_FUSE", {KNOB_UNSET}},
-                  {"SSD_CONV_PATCH_ROWFLAT", {KNOB_UNSET}}, {"SSD_MATCH_FUSED", {KNOB_UNSET}}, {"SSD_CONV_P512", {KNOB_UNSET}},
-                  {"SSD_C64B_WGS", {KNOB_UNSET}}, {"SSD_CONV_PW", {KNOB_UNSET}}, {"SSD_PW_WGS", {KNOB_UNSET}},
-                  {"SSD_SP_ABLATE", {KNOB_UNSET}}};
-Knob* find_knob(const char* name) {
-    for (Knob& k : g_knobs) if (!strcmp(k.name, name)) return &k;
-    return nullptr;
-}
-int knob(const char* name, int dflt) {
-    Knob* k = find_knob(name);
-    if (!k) return dflt;
-    const int v = k->value.load(std::memory_order_relaxed);
-    return v == KNOB_UNSET ? dflt : v;
-}
-
-// Which kernel a call resolves to (ssd_conv2d_*_plan): the dispatch code below runs as usual and, with `plan` set, records
-// the id at the launch site and returns instead of launching -- the query cannot drift from the dispatch.
-// ssd_conv2d_*_workgroups: the caller presets *plan to PLAN_WANT_WGS and the launch sites that know their count record
-// the number of ACTIVE workgroups (the grid minus the workgroups that return at once) instead of the id.
-constexpr int PLAN_WANT_WGS = -1;
-#define SSD_PLAN(ID_) do { if (plan) { if (*plan == PLAN_WANT_WGS) return SSD_ERR_UNSUPPORTED; *plan = (ID_); return SSD_OK; } } while (0)
-#define SSD_PLAN_WGS(ID_, WGS_) do { if (plan) { *plan = *plan == PLAN_WANT_WGS ? (int)(WGS_) : (ID_); return SSD_OK; } } while (0)
-
+// Dispatch.  SSD_PLAN / SSD_PLAN_WGS (conv_common.h) record the kernel id or the workgroup count at the launch site.
 template <int EPI>
 bool staged_ok_host(const ConvGeom& g, const Epilogue& ep) {
     if (ep.slab) return false;
@@ -2771,7 +1577,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
     ep.slab = nullptr;
     ep.ksplit = 1;
     if constexpr (EPI != EPI_HEAD) {
-        if (knob("SSD_CONV_C64", 1) && g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 &&
+        if (ssd_knob("SSD_CONV_C64", 1) && g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 &&
             g.pad_l == 1 && g.C == 64 && g.N == 64 && g.ldw == 576 && g.H == g.Ho && g.W == g.Wo && g.H >= 16 && g.W >= 16 &&
             !ep.accumulate && !ep.up_out && (ep.ldo & 7) == 0 && (long long)g.B * g.H * g.W * 64 < (1ll << 31) - 16) {
             if (EPI == EPI_FWD && !ep.out && !(pooled && ep.pool_out)) return SSD_ERR_VALUE;
@@ -2779,7 +1585,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
             const int tiles_x = (g.Wo + 15) / 16, tiles_y = (g.Ho + C64B_ROWS - 1) / C64B_ROWS;
             const int nblocks = g.B * tiles_x * tiles_y;
             auto kern = k_conv3x3_c64b<EPI, false>;
-            const int maxwg = knob("SSD_C64B_WGS", 512);
+            const int maxwg = ssd_knob("SSD_C64B_WGS", 512);
             SSD_PLAN_WGS(SSD_PLAN_C64B | ((pooled && ep.pool_out) ? SSD_PLAN_F_POOL_FUSED : 0), nblocks < maxwg ? nblocks : maxwg);
             static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(C64B_LDS)) != 0) return SSD_ERR_LAUNCH;
             hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < maxwg ? nblocks : maxwg)), dim3(256), C64B_LDS, s, xp, wp, g, ep, tiles_x, tiles_y, C64W0{});
@@ -2789,12 +1595,12 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
     }
     // LDS-patch kernel: 3x3 / stride 1 / pad 1 with N <= SSD_CONV_PATCH (default 256); beyond 128 channels only when
     // the 16x16 blocks waste little of the map (75x75 and larger: <= 14 %; 38x38 would waste 37 %)
-    const int use_patch = knob("SSD_CONV_PATCH", 256);
+    const int use_patch = ssd_knob("SSD_CONV_PATCH", 256);
     const bool patch_fits = g.N <= 128 || (long long)((g.Wo + 15) / 16) * ((g.Ho + 15) / 16) * 256 * 4 <= (long long)g.Wo * g.Ho * 5;
     // narrow maps: strip blocks, any channel count.  The patch of 256 + 2 (W + 2) positions has to fit the 341 pixel rows of
     // a 32 KB buffer; the bound on W dates from the strip's first form (row pitch W + 2, 256 + 2 (W + 3) positions) and stays:
     // which layers take the strip form is part of the tested dispatch
-    const int flat_knob = knob("SSD_CONV_PATCH_FLAT", 1);
+    const int flat_knob = ssd_knob("SSD_CONV_PATCH_FLAT", 1);
     const bool use_flat = flat_knob && g.W <= 39 && g.W >= 16 && g.H >= 16 && (flat_knob >= 2 || !patch_fits || g.N > use_patch);
     if (g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 && g.pad_l == 1 &&
         g.C % 64 == 0 && g.H == g.Ho && g.W == g.Wo && ((g.N <= use_patch && patch_fits) || use_flat) && g.H >= 16 && g.W >= 16 &&
@@ -2810,7 +1616,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
             const int pitch = (EPI == EPI_FWD && ep.pool_out && (g.H & 1) == 0) ? g.H + 2 : g.H + 1;
             gk.d_h1 = make_fastdiv(pitch);
             const unsigned strip_rows = (unsigned)(((long long)g.B * pitch + 15) / 16);
-            const int rowflat = (!flat && knob("SSD_CONV_PATCH_ROWFLAT", 1) && strip_rows < (unsigned)(tiles_y * g.B)) ? 1 : 0;
+            const int rowflat = (!flat && ssd_knob("SSD_CONV_PATCH_ROWFLAT", 1) && strip_rows < (unsigned)(tiles_y * g.B)) ? 1 : 0;
             const unsigned gxx = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + 255) / 256)
                                       : (rowflat ? strip_rows * (unsigned)tiles_x : gx);
 #define SSD_LAUNCH_P32(BN_, FLAT_)                                                                                  \
@@ -2829,7 +1635,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
                 return SSD_ERR_UNSUPPORTED;                      // un-pooling and the sign bits live in the staged store
             // 512 px x 128 channels, one workgroup per CU: from 256 input channels on (eight 32-channel chunks amortise its longer
             // prologue / epilogue; measured per layer in DESIGN.md section 9).  SSD_CONV_P512: 0 never, 1 (default) that rule, 2 always
-            const int p512 = knob("SSD_CONV_P512", 1);
+            const int p512 = ssd_knob("SSD_CONV_P512", 1);
             // (the heads never take it.  Head 0, 38x38 x 512 channels: its element-wise scatter epilogue has nothing to hide
             //  behind with one workgroup per CU, 385 vs 334 us.  Head 1, 19x19 x 1024 channels, is 208 vs 222 us ALONE -- but it
             //  runs beside the extras' chain of small launches, and a 512-pixel workgroup holds 152 of the CU's 160 KB of LDS:
@@ -2838,7 +1644,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
             if (p512 && g.C % 64 == 0 && g.N > 64 && (p512 >= 2 || (EPI != EPI_HEAD && g.C >= 256))) {
                 const int ty32 = (g.Ho + 31) / 32;
                 const unsigned strips32 = (unsigned)(((long long)g.B * pitch + 31) / 32);
-                const int rf = (!flat && knob("SSD_CONV_PATCH_ROWFLAT", 1) && strips32 < (unsigned)(ty32 * g.B)) ? 1 : 0;
+                const int rf = (!flat && ssd_knob("SSD_CONV_PATCH_ROWFLAT", 1) && strips32 < (unsigned)(ty32 * g.B)) ? 1 : 0;
                 const unsigned nb = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + 511) / 512)
                                          : (rf ? strips32 * (unsigned)tiles_x : (unsigned)(tiles_x * ty32 * g.B));
                 const unsigned ntn5 = (unsigned)((g.N + 127) / 128);
@@ -2868,7 +1674,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
     if constexpr (EPI != EPI_HEAD) {
         // 1x1 / stride 1 on a large map: the persistent GEMM (pwgemm.hip) -- the DMA stream runs on across tile boundaries
         // (SSD_CONV_PW: bit 0 forward, bit 1 data gradient)
-        if ((knob("SSD_CONV_PW", 3) & (EPI == EPI_FWD ? 1 : 2)) && !(g.ablate & 8) && ssd_pw_gemm_serves(EPI, &g, &ep)) {
+        if ((ssd_knob("SSD_CONV_PW", 3) & (EPI == EPI_FWD ? 1 : 2)) && !(g.ablate & 8) && ssd_pw_gemm_serves(EPI, &g, &ep)) {
             SSD_PLAN(SSD_PLAN_PW);
             return ssd_pw_gemm_launch(EPI, x, w, &g, &ep, s);
         }
@@ -2876,7 +1682,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
     {
         // tile choice: the CU ingests ~28 B/clk from L2, so MACs per staged byte decide the ceiling: prefer the
         // largest tile that still gives every CU work (>= ~2 workgroups per CU), SSD_CONV_TILE overrides (testing)
-        const int force = knob("SSD_CONV_TILE", 0);
+        const int force = ssd_knob("SSD_CONV_TILE", 0);
         const long long wg_256 = (long long)((g.M + 255) / 256);
         int bm = 128, bn = g.N <= 64 ? 64 : 128;
         const long long pad256 = (long long)((g.N + 255) / 256) * 256, pad128 = (long long)((g.N + 127) / 128) * 128;
@@ -2892,7 +1698,7 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
         // split-K for skinny problems (few tiles, long k loop): partial sums to the caller's workspace
         unsigned ksplit = 1;
         {
-            const int sk_on = knob("SSD_SPLITK", 1);
+            const int sk_on = ssd_knob("SSD_SPLITK", 1);
             const long long tiles = (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
             const int nks_all = g.s2 ? 0 : (g.nchunks + 7) / 8;
             if (sk_on && ws && tiles < 160 && nks_all >= 8) {
@@ -2963,46 +1769,16 @@ int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue
     }
 }
 
-bool geom_ok(int B, int H, int W, int C, int Ho, int Wo, int N, int K) {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || N <= 0 || K <= 0) return false;
-    if (C % 8) return false;
-    if ((long long)B * Ho * Wo >= (1ll << 31) || (long long)B * H * W >= (1ll << 31)) return false;
-    if ((long long)B * H * W * C >= (1ll << 32) || (long long)B * Ho * Wo * N >= (1ll << 32)) return false;   // 32-bit element offsets
-    return true;
-}
-
 }  // namespace
 
-int ssd_knob(const char* name, int dflt) { return knob(name, dflt); }
-
-// dW / dbias = sum over splits of the slabs, fixed order
-void ssd_launch_wgrad_reduce(hipStream_t s, const float* slab_w, long long sw, long long nw, float* dw, const float* slab_b,
-                             long long sb, int nb, float* db, int ns) {
-    if (ns >= 32) {
-        const unsigned nbw = (unsigned)((nw / 4 + 15) / 16), nbb = db ? (unsigned)((nb + 15) / 16) : 0u;
-        hipLaunchKernelGGL(k_wgrad_reduce_wide, dim3(nbw + nbb), dim3(256), 0, s, slab_w, sw, nw, dw, slab_b, sb, nb, db, ns, nbw);
-    } else {
-        const unsigned nbw = (unsigned)((nw / 4 + 255) / 256), nbb = db ? (unsigned)((nb + 255) / 256) : 0u;
-        hipLaunchKernelGGL(k_wgrad_reduce2, dim3(nbw + nbb), dim3(256), 0, s, slab_w, sw, nw, dw, slab_b, sb, nb, db, ns, nbw);
-    }
-}
-
 extern "C" {
-
-int ssd_dev_knob(const char* name, int value) {
-    if (!name) return SSD_ERR_VALUE;
-    Knob* k = find_knob(name);
-    if (!k) return SSD_ERR_VALUE;
-    k->value.store(value, std::memory_order_relaxed);
-    return SSD_OK;
-}
 
 static int conv2d_fwd_impl(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
                            int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, void* ws, size_t ws_bytes,
                            void* stream, int* plan, void* relu_bits = nullptr) {
     if (!x || !w || !y || !geom_ok(B, H, W, Cin, Ho, Wo, Cout, ksize) || stride <= 0) return SSD_ERR_VALUE;
     const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, ksize, ksize, stride, 1, pad_t, pad_l);
-    if (knob("SSD_CONV_FIRST", 1) && Cin == 8 && Cout == 64 && ksize == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && H == Ho &&
+    if (ssd_knob("SSD_CONV_FIRST", 1) && Cin == 8 && Cout == 64 && ksize == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && H == Ho &&
         W == Wo && H >= 16 && W >= 16) {                     // the image layer
         const int tx = (Wo + 15) / 16, ty = (Ho + 15) / 16;
         SSD_PLAN_WGS(SSD_PLAN_CONV0_FWD, B * tx * ty < 768 ? B * tx * ty : 768);
@@ -3035,8 +1811,8 @@ static int conv2d_fwd_pool_impl(const void* x, const void* w, const float* bias,
     const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, ksize, ksize, stride, 1, pad_t, pad_l);
     Epilogue ep = {};
     ep.bias = bias; ep.relu = relu; ep.out = static_cast<bf16_raw*>(y); ep.ldo = Cout;
-    if (!y && !knob("SSD_CONV_POOL_FUSE", 1)) return SSD_ERR_VALUE;
-    if (knob("SSD_CONV_POOL_FUSE", 1)) {
+    if (!y && !ssd_knob("SSD_CONV_POOL_FUSE", 1)) return SSD_ERR_VALUE;
+    if (ssd_knob("SSD_CONV_POOL_FUSE", 1)) {
         ep.pool_out = static_cast<bf16_raw*>(y_pool); ep.pool_code = static_cast<unsigned*>(pool_code); ep.pool_h = Hp; ep.pool_w = Wp;
     }
     bool pooled = false;
@@ -3127,10 +1903,6 @@ int ssd_conv2d_bwd_data(const void* dy, const void* w_t, const void* relu_src, v
                                 ws, ws_bytes, stream, nullptr);
 }
 
-static int wgrad_patch_min_hw() {           // SSD_WGRAD_PATCH = smallest feature-map side served by the patch kernel (0: off)
-    return knob("SSD_WGRAD_PATCH", 16);
-}
-
 // Data gradient of the second layer (64 -> 64, 3x3 / stride 1 / pad 1) fused with the weight gradient of the first
 // (8 padded image channels -> 64): k_conv3x3_c64b<EPI_DGRAD, true>.  The gradient w.r.t. the first layer's output never
 // reaches memory.  dy [B,H,W,64]; w_t [64][3][3][64] (ssd_weight_transpose of the second layer); relu_bits [B*H*W][8] (sign
@@ -3165,279 +1937,12 @@ int ssd_conv2d_bwd_data_wgrad_first(const void* dy, const void* w_t, const void*
     return ssd_launch_status();
 }
 
-// first layer (8 padded image channels): dedicated kernel, 512 pixel-block splits at most
-static bool wgrad_first_layer(int H, int W, int Ho, int Wo, int Cin, int Cout, int ldy, int ksize, int stride, int pad_t, int pad_l) {
-    return knob("SSD_WGRAD_FIRST", 1) && Cin == 8 && Cout <= 64 && ldy <= 64 && ksize == 3 && stride == 1 && pad_t == 1 && pad_l == 1 &&
-           H == Ho && W == Wo && H >= 16 && W >= 16;
-}
-
-static bool wgrad_use_patch(int H, int W, int Ho, int Wo, int Cin, int ksize, int stride, int pad_t, int pad_l) {
-    const int mn = wgrad_patch_min_hw();
-    return mn > 0 && ksize == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && H == Ho && W == Wo && Cin % 64 == 0 &&
-           H >= mn && W >= mn;
-}
-
-// block shape of the patch kernel for a map: the candidate with the least padded work (0: 16x16, 1: 6x40, 2: 10x24)
-static int wgrad_patch_shape(int Ho, int Wo, int* bh, int* bw) {
-    static const int shapes[3][3] = {{16, 16, 16}, {6, 40, 15}, {10, 24, 15}};   // rows, columns, pair groups (of 16 slots)
-    int best = 0;
-    double best_cost = 0;
-    for (int i = 0; i < 3; ++i) {
-        // every block costs eight k-steps whatever its shape: fewest blocks wins
-        const double cost = (double)((Ho + shapes[i][0] - 1) / shapes[i][0]) * ((Wo + shapes[i][1] - 1) / shapes[i][1]);
-        if (i == 0 || cost < best_cost) { best = i; best_cost = cost; }
-    }
-    const int forced = knob("SSD_WGRAD_PATCH_SHAPE", -1);
-    if (forced >= 0 && forced < 3) best = forced;
-    *bh = shapes[best][0]; *bw = shapes[best][1];
-    return best;
-}
-
-static void wgrad_patch_plan(int B, int Ho, int Wo, int Cin, int Cout, int* tiles_x, int* tiles_y, int* tps, int* ns) {
-    int bh, bw;
-    wgrad_patch_shape(Ho, Wo, &bh, &bw);
-    *tiles_x = (Wo + bw - 1) / bw; *tiles_y = (Ho + bh - 1) / bh;
-    const int ntiles = B * *tiles_x * *tiles_y;
-    const int groups = (Cin / 64) * ((Cout + 63) / 64);
-    int want = 256 / groups;                                 // one workgroup per CU
-    if (want < 1) want = 1;
-    if (want > ntiles) want = ntiles;
-    *tps = (ntiles + want - 1) / want;
-    *ns = (ntiles + *tps - 1) / *tps;
-}
-
-constexpr int WG_BMO = 128, WG_BNC = 128;                    // k_conv_wgrad's tile: output channels x (tap, ci) columns
-
-static int wgrad_splits(long long M, int tiles) {
-    long long want = 768 / tiles;                            // whole rounds: <= 3 workgroups per CU in total
-    long long maxs = (M + 511) / 512;                        // at least 512 pixels per split
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    if (want > 512) want = 512;
-    return (int)want;
-}
-
-// 256x256 GEMM weight-gradient kernel: used for wide layers the patch kernel does not serve
-static bool wgrad_use_tile(long long M, int Cout, int ldy, long long ktot, long long x_elems) {
-    return knob("SSD_WGRAD_TILE", 1) && Cout > 128 && ktot >= 256 && M >= 2048 && M * ldy < (1ll << 31) - 16 &&
-           x_elems < (1ll << 31) - 16;
-}
-
-// pixel splits for that kernel (one workgroup per CU): estimated time = rounds x steps per split + slab traffic
-static int wgrad_tile_splits(long long M, int tiles, long long slab_elems) {
-    int best = 1;
-    double best_cost = 0;
-    const long long maxs = M / 256 > 0 ? M / 256 : 1;
-    for (int ns = 1; ns <= 64 && ns <= maxs; ++ns) {
-        const long long rounds = ((long long)tiles * ns + 255) / 256;
-        const long long steps = ((M + ns - 1) / ns + 63) / 64;
-        const double cost = (double)rounds * steps * 2.2 + (double)ns * slab_elems * 8.0 / 4.0e6;   // microseconds
-        if (ns == 1 || cost < best_cost) { best = ns; best_cost = cost; }
-    }
-    return best;
-}
-
-size_t ssd_conv2d_bwd_weight_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int ldy, int ksize) {
-    if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || ldy < Cout || ksize <= 0) return 0;
-    const long long ktot = (long long)ksize * ksize * Cin;
-    size_t patch_bytes = 0;
-    if (wgrad_use_patch(Ho, Wo, Ho, Wo, Cin, ksize, 1, 1, 1)) {     // upper bound if the call turns out to be a patch case
-        int tx, ty, tps, ns;
-        wgrad_patch_plan(B, Ho, Wo, Cin, Cout, &tx, &ty, &tps, &ns);
-        patch_bytes = (size_t)ns * ((size_t)ldy * ktot + ldy) * sizeof(float);
-    }
-    const int tiles = (int)(((ktot + WG_BNC - 1) / WG_BNC) * ((Cout + WG_BMO - 1) / WG_BMO));
-    const int ns = wgrad_splits((long long)B * Ho * Wo, tiles);
-    size_t gen = (size_t)ns * ((size_t)ldy * ktot + ldy) * sizeof(float);
-    if (Cin == 8 && Cout <= 64 && ldy <= 64 && ksize == 3) {  // first-layer kernel: up to 512 splits
-        const size_t first = (size_t)512 * ((size_t)ldy * ktot + ldy) * sizeof(float);
-        if (first > gen) gen = first;
-    }
-    if (Cout > 128 && ktot >= 256) {                          // the 256x256 GEMM kernel may serve the call
-        const int t2 = (int)(((ktot + 255) / 256) * ((Cout + 255) / 256));
-        const int ns2 = wgrad_tile_splits((long long)B * Ho * Wo, t2, (long long)ldy * ktot);
-        const size_t gen2 = (size_t)ns2 * ((size_t)ldy * ktot + ldy) * sizeof(float);
-        if (gen2 > gen) gen = gen2;
-    }
-    return gen > patch_bytes ? gen : patch_bytes;
-}
-
-static int conv2d_bwd_weight_impl(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout,
-                                  int ldy, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, void* ws, size_t ws_bytes,
-                                  void* stream, int* plan) {
-    // x: [B,H,W,Cin]; dy: [B,Ho,Wo,ldy] (first Cout channels used); dw: f32 [Cout][k][k][Cin]; dbias: f32 [Cout] or null
-    if (!x || !dy || !dw || !geom_ok(B, H, W, Cin, Ho, Wo, Cout, ksize) || stride <= 0 || ldy < Cout || ldy % 8) return SSD_ERR_VALUE;
-    if (!ws || ws_bytes < ssd_conv2d_bwd_weight_workspace_bytes(B, Ho, Wo, Cin, Cout, ldy, ksize)) return SSD_ERR_WORKSPACE;
-    ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, ldy, ksize, ksize, stride, 1, pad_t, pad_l);
-    const long long ktot = g.ldw;
-    if (wgrad_first_layer(H, W, Ho, Wo, Cin, Cout, ldy, ksize, stride, pad_t, pad_l)) {
-        const int tx = (Wo + 15) / 16, ty = (Ho + 15) / 16, ntiles = B * tx * ty;
-        const int ns = ntiles < 512 ? ntiles : 512;
-        const int tps = (ntiles + ns - 1) / ns;
-        SSD_PLAN(SSD_PLAN_WG_FIRST | ((ntiles + tps - 1) / tps >= 32 ? SSD_PLAN_F_REDUCE_WIDE : 0));
-        float* slab_w = static_cast<float*>(ws);
-        float* slab_b = slab_w + (size_t)ns * ldy * ktot;
-        hipStream_t s = (hipStream_t)stream;
-        static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(k_conv0_wgrad), (int)(2 * W0_BUF)) != 0) return SSD_ERR_LAUNCH;
-        hipLaunchKernelGGL(k_conv0_wgrad, dim3((unsigned)((ntiles + tps - 1) / tps)), dim3(512), 2 * W0_BUF, s,
-                           static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(dy), slab_w, dbias ? slab_b : nullptr, g,
-                           tx, ty, tps, Cout);
-        if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-        const int nsr = (ntiles + tps - 1) / tps;
-        ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, nsr);
-        return ssd_launch_status();
-    }
-    if (wgrad_use_patch(H, W, Ho, Wo, Cin, ksize, stride, pad_t, pad_l) &&
-        (long long)B * H * W * Cin * 2 < (1ll << 32) - 16 && (long long)B * Ho * Wo * ldy * 2 < (1ll << 32) - 16) {   // 32-bit DMA offsets
-        int tx, ty, tps, ns;
-        wgrad_patch_plan(B, Ho, Wo, Cin, Cout, &tx, &ty, &tps, &ns);
-        float* slab_w = static_cast<float*>(ws);
-        float* slab_b = slab_w + (size_t)ns * ldy * ktot;
-        hipStream_t s = (hipStream_t)stream;
-        const int groups = (Cin / 64) * ((Cout + 63) / 64), nunits = groups * ns;
-        // units per XCD group: the largest divisor of the channel-group count whose round-robin placement (group i on
-        // XCD i % 8) keeps every XCD within ~7 % of its fair share of workgroups
-        int xg = 1;
-        for (int d = groups; d >= 1; --d) {
-            if (groups % d) continue;
-            const int ngr = (nunits + d - 1) / d;
-            const int load = ((ngr + 7) / 8) * d, fair = (nunits + 7) / 8;
-            if (load * 100 <= fair * 107) { xg = d; break; }
-        }
-        if (!knob("SSD_WGRAD_PATCH_XCD", 1)) xg = 1;
-        const unsigned grid = (unsigned)(8 * xg * ((nunits + 8 * xg - 1) / (8 * xg)));
-        int bh, bw;
-        const int shape = wgrad_patch_shape(Ho, Wo, &bh, &bw);
-        SSD_PLAN((shape == 1 ? SSD_PLAN_WG_PATCH_6x40 : (shape == 2 ? SSD_PLAN_WG_PATCH_10x24 : SSD_PLAN_WG_PATCH_16x16)) |
-                 (ns >= 32 ? SSD_PLAN_F_REDUCE_WIDE : 0));
-#define SSD_LAUNCH_WP(BH_, BW8_)                                                                                    \
-        do {                                                                                                        \
-            using G_ = WpGeom<BH_, BW8_>;                                                                           \
-            auto kern_ = k_conv3x3_wgrad_patch<BH_, BW8_>;                                                          \
-            static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)(2 * G_::BUF)) != 0) return SSD_ERR_LAUNCH; \
-            hipLaunchKernelGGL(kern_, dim3(grid), dim3(512), (size_t)2 * G_::BUF, s,                                 \
-                               static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(dy), slab_w,          \
-                               dbias ? slab_b : nullptr, g, tx, ty, tps, ns, Cout, 0, xg);                          \
-        } while (0)
-        if (shape == 1) SSD_LAUNCH_WP(6, 5);
-        else if (shape == 2) SSD_LAUNCH_WP(10, 3);
-        else SSD_LAUNCH_WP(16, 2);
-#undef SSD_LAUNCH_WP
-        if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-        ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
-        return ssd_launch_status();
-    }
-    if (wgrad_use_tile(g.M, Cout, ldy, ktot, (long long)B * H * W * Cin)) {
-        const int ctiles = (int)((ktot + 255) / 256), mtiles = (Cout + 255) / 256;
-        const int ns = wgrad_tile_splits(g.M, ctiles * mtiles, (long long)ldy * ktot);
-        int mps = (int)(((long long)g.M + ns - 1) / ns);
-        mps = (mps + 63) / 64 * 64;
-        SSD_PLAN(SSD_PLAN_WG_TILE | (ns >= 32 ? SSD_PLAN_F_REDUCE_WIDE : 0));
-        float* slab_w = static_cast<float*>(ws);
-        float* slab_b = slab_w + (size_t)ns * ldy * ktot;
-        hipStream_t s = (hipStream_t)stream;
-        static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(k_conv_wgrad_tile), (int)(4 * WT_TILE)) != 0) return SSD_ERR_LAUNCH;
-        hipLaunchKernelGGL(k_conv_wgrad_tile, dim3(ctiles * mtiles * ns), dim3(512), 4 * WT_TILE, s,
-                           static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(dy), slab_w, dbias ? slab_b : nullptr, g,
-                           mps, ns, Cout);
-        if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-        ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
-        return ssd_launch_status();
-    }
-    const int ctiles = (int)((ktot + WG_BNC - 1) / WG_BNC), mtiles = (Cout + WG_BMO - 1) / WG_BMO;
-    const int ns = wgrad_splits(g.M, ctiles * mtiles);
-    int mps = (int)(((long long)g.M + ns - 1) / ns);
-    mps = (mps + 63) / 64 * 64;
-    SSD_PLAN(SSD_PLAN_WG_GENERIC | (ns >= 32 ? SSD_PLAN_F_REDUCE_WIDE : 0));
-    float* slab_w = static_cast<float*>(ws);
-    float* slab_b = slab_w + (size_t)ns * ldy * ktot;
-    hipStream_t s = (hipStream_t)stream;
-    const bf16_raw* xp = static_cast<const bf16_raw*>(x);
-    const bf16_raw* dyp = static_cast<const bf16_raw*>(dy);
-    float* sb = dbias ? slab_b : nullptr;
-    {
-        const size_t lds = 4 * 64 * WG_LD;
-        static OnceLds attr_set; if (ensure_lds(attr_set, reinterpret_cast<const void*>(k_conv_wgrad), (int)((int)lds)) != 0) return SSD_ERR_LAUNCH;
-        hipLaunchKernelGGL(k_conv_wgrad, dim3(ctiles, mtiles, ns), dim3(WG), lds, s, xp, dyp, slab_w, sb, g, mps);
-    }
-    if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-    ssd_launch_wgrad_reduce(s, slab_w, (long long)ldy * ktot, (long long)Cout * ktot, dw, slab_b, (long long)ldy, Cout, dbias, ns);
-    return ssd_launch_status();
-}
-
-// Several SMALL layers' weight gradients in two launches (slab kernel + slab sums) instead of two per layer: the extras on the
-// 10x10 ... 1x1 maps (reference models/ssd_model.py:124-150) are six launches of 2-70 workgroups each, ~25 us apiece on the side
-// stream beside the other streams' kernels.  Served: the layers ssd_conv2d_bwd_weight itself runs on the generic kernel (not the
-// first layer, not a patch / 256-wide tile case) with fewer than 32 splits; SSD_ERR_UNSUPPORTED otherwise, nothing launched.
-// Every layer's blocks and sums are the ones its own call would have run: results are bit-identical to separate calls.
-size_t ssd_conv2d_bwd_weight_batched_workspace_bytes(const ssd_wgrad_item* items, int count) {
-    if (!items || count <= 0) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < count; ++i)
-        tot += ssd_align_up(ssd_conv2d_bwd_weight_workspace_bytes(items[i].B, items[i].Ho, items[i].Wo, items[i].Cin, items[i].Cout,
-                                                                   items[i].ldy, items[i].ksize), 256);
-    return tot;
-}
-
-int ssd_conv2d_bwd_weight_batched(const ssd_wgrad_item* items, int count, void* ws, size_t ws_bytes, void* stream) {
-    if (!items || count <= 0) return SSD_ERR_VALUE;
-    if (count > WGB_MAX) return SSD_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < ssd_conv2d_bwd_weight_batched_workspace_bytes(items, count)) return SSD_ERR_WORKSPACE;
-    WgradBatchArgs wa;
-    ReduceBatchArgs ra;
-    wa.count = ra.count = count;
-    char* p = static_cast<char*>(ws);
-    int blk = 0, rblk = 0;
-    for (int i = 0; i < count; ++i) {
-        const ssd_wgrad_item& it = items[i];
-        if (!it.x || !it.dy || !it.dw || !geom_ok(it.B, it.H, it.W, it.Cin, it.Ho, it.Wo, it.Cout, it.ksize) || it.stride <= 0 ||
-            it.ldy < it.Cout || it.ldy % 8)
-            return SSD_ERR_VALUE;
-        const ConvGeom g = make_geom(it.B, it.H, it.W, it.Cin, it.Ho, it.Wo, it.ldy, it.ksize, it.ksize, it.stride, 1, it.pad_t, it.pad_l);
-        const long long ktot = g.ldw;
-        if (wgrad_first_layer(it.H, it.W, it.Ho, it.Wo, it.Cin, it.Cout, it.ldy, it.ksize, it.stride, it.pad_t, it.pad_l) ||
-            wgrad_use_patch(it.H, it.W, it.Ho, it.Wo, it.Cin, it.ksize, it.stride, it.pad_t, it.pad_l) ||
-            wgrad_use_tile(g.M, it.Cout, it.ldy, ktot, (long long)it.B * it.H * it.W * it.Cin))
-            return SSD_ERR_UNSUPPORTED;
-        const int ctiles = (int)((ktot + WG_BNC - 1) / WG_BNC), mtiles = (it.Cout + WG_BMO - 1) / WG_BMO;
-        const int ns = wgrad_splits(g.M, ctiles * mtiles);
-        if (ns >= 32) return SSD_ERR_UNSUPPORTED;              // (the wide reduction's case)
-        int mps = (int)(((long long)g.M + ns - 1) / ns);
-        mps = (mps + 63) / 64 * 64;
-        float* slab_w = reinterpret_cast<float*>(p);
-        float* slab_b = slab_w + (size_t)ns * it.ldy * ktot;
-        p += ssd_align_up(ssd_conv2d_bwd_weight_workspace_bytes(it.B, it.Ho, it.Wo, it.Cin, it.Cout, it.ldy, it.ksize), 256);
-        wa.it[i] = WgradBatchItem{static_cast<const bf16_raw*>(it.x), static_cast<const bf16_raw*>(it.dy), slab_w,
-                                  it.dbias ? slab_b : nullptr, g, mps, ctiles, mtiles, blk};
-        blk += ctiles * mtiles * ns;
-        const long long nw = (long long)it.Cout * ktot;
-        const unsigned nbw = (unsigned)((nw / 4 + 255) / 256), nbb = it.dbias ? (unsigned)((it.Cout + 255) / 256) : 0u;
-        ra.it[i] = ReduceBatchItem{slab_w, slab_b, it.dw, it.dbias, (long long)it.ldy * ktot, nw, (long long)it.ldy, it.Cout, ns, rblk, nbw};
-        rblk += (int)(nbw + nbb);
-    }
-    for (int i = count; i < WGB_MAX; ++i) { wa.it[i] = wa.it[0]; wa.it[i].blk0 = blk; ra.it[i] = ra.it[0]; ra.it[i].blk0 = rblk; }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t lds = 4 * 64 * WG_LD;
-    static OnceLds attr_set; if (ensure_lds(attr_set, reinterpret_cast<const void*>(k_conv_wgrad_batched), (int)lds) != 0) return SSD_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_conv_wgrad_batched, dim3(blk), dim3(WG), lds, s, wa);
-    if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_wgrad_reduce2_batched, dim3(rblk), dim3(256), 0, s, ra);
-    return ssd_launch_status();
-}
-
-int ssd_conv2d_bwd_weight(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout,
-                          int ldy, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, void* ws, size_t ws_bytes,
-                          void* stream) {
-    return conv2d_bwd_weight_impl(x, dy, dw, dbias, B, H, W, Cin, Cout, ldy, ksize, stride, pad_t, pad_l, Ho, Wo, ws, ws_bytes,
-                                  stream, nullptr);
-}
-
-// ---- dispatch queries: the same code path with `plan` set (nothing is launched, no pointer is dereferenced) ----
-static void* const PLAN_PTR = reinterpret_cast<void*>(static_cast<uintptr_t>(64));
-
-int ssd_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                        int pool, size_t ws_bytes) {
-    int plan = 0, rc;
+// ---- dispatch queries: the same code path with `plan` set (nothing is launched, no pointer is dereferenced).  plan0 = 0: which
+// kernel (ssd_conv2d_*_plan); plan0 = PLAN_WANT_WGS: ACTIVE workgroups of the (first) launch the call resolves to
+// (ssd_conv2d_*_workgroups), SSD_ERR_UNSUPPORTED where the launch site does not report one (the persistent pointwise GEMM) ----
+static int conv2d_fwd_query(int plan0, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
+                            int Wo, int pool, size_t ws_bytes) {
+    int plan = plan0, rc;
     void* ws = ws_bytes ? PLAN_PTR : nullptr;
     if (pool) {
         const int Hp = (Ho + 1) / 2, Wp = (Wo + 1) / 2;
@@ -3448,6 +1953,24 @@ int ssd_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int s
                              ws_bytes, nullptr, &plan);
     }
     return rc != SSD_OK ? rc : plan;
+}
+
+static int conv2d_bwd_data_query(int plan0, int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
+                                 int Ho, int Wo, int accumulate, size_t ws_bytes) {
+    int plan = plan0;
+    const int rc = conv2d_bwd_data_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l,
+                                        Ho, Wo, accumulate, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
+    return rc != SSD_OK ? rc : plan;
+}
+
+int ssd_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                        int pool, size_t ws_bytes) {
+    return conv2d_fwd_query(0, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
+}
+
+int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                              int pool, size_t ws_bytes) {
+    return conv2d_fwd_query(PLAN_WANT_WGS, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
 }
 
 int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int classes, size_t ws_bytes) {
@@ -3459,45 +1982,12 @@ int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int cla
 
 int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                              int Wo, int accumulate, size_t ws_bytes) {
-    int plan = 0;
-    const int rc = conv2d_bwd_data_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l,
-                                        Ho, Wo, accumulate, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
-    return rc != SSD_OK ? rc : plan;
-}
-
-// ---- launch size: ACTIVE workgroups of the (first) launch the call resolves to; SSD_ERR_UNSUPPORTED where the launch site
-// does not report one (the persistent pointwise GEMM) ----
-int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                              int pool, size_t ws_bytes) {
-    int plan = PLAN_WANT_WGS, rc;
-    void* ws = ws_bytes ? PLAN_PTR : nullptr;
-    if (pool) {
-        const int Hp = (Ho + 1) / 2, Wp = (Wo + 1) / 2;
-        rc = conv2d_fwd_pool_impl(PLAN_PTR, PLAN_PTR, nullptr, pool == 2 ? nullptr : PLAN_PTR, PLAN_PTR, PLAN_PTR, B, H, W, Cin, Cout,
-                                  ksize, stride, pad_t, pad_l, Ho, Wo, 1, Hp, Wp, ws, ws_bytes, nullptr, &plan);
-    } else {
-        rc = conv2d_fwd_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 1, ws,
-                             ws_bytes, nullptr, &plan);
-    }
-    return rc != SSD_OK ? rc : plan;
+    return conv2d_bwd_data_query(0, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
 }
 
 int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                                    int Wo, int accumulate, size_t ws_bytes) {
-    int plan = PLAN_WANT_WGS;
-    const int rc = conv2d_bwd_data_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l,
-                                        Ho, Wo, accumulate, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
-    return rc != SSD_OK ? rc : plan;
-}
-
-int ssd_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int ldy, int ksize, int stride, int pad_t, int pad_l,
-                               int Ho, int Wo) {
-    int plan = 0;
-    const size_t need = ssd_conv2d_bwd_weight_workspace_bytes(B, Ho, Wo, Cin, Cout, ldy, ksize);
-    const int rc = conv2d_bwd_weight_impl(PLAN_PTR, PLAN_PTR, reinterpret_cast<float*>(PLAN_PTR), reinterpret_cast<float*>(PLAN_PTR),
-                                          B, H, W, Cin, Cout, ldy, ksize, stride, pad_t, pad_l, Ho, Wo, PLAN_PTR, need, nullptr,
-                                          &plan);
-    return rc != SSD_OK ? rc : plan;
+    return conv2d_bwd_data_query(PLAN_WANT_WGS, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
 }
 
 const char* ssd_conv_plan_name(int plan) {
@@ -3522,92 +2012,6 @@ const char* ssd_conv_plan_name(int plan) {
         case SSD_PLAN_WG_GENERIC: return "k_conv_wgrad";
         default: return "?";
     }
-}
-
-int ssd_weight_transpose(const void* w, void* w_t, int Cout, int ksize, int Cin, int Cout_pad, void* stream) {
-    if (!w || !w_t || Cout <= 0 || ksize <= 0 || Cin <= 0 || Cout_pad < Cout || Cout_pad % 8) return SSD_ERR_VALUE;
-    const long long total = (long long)Cin * ksize * ksize * Cout_pad;
-    hipLaunchKernelGGL(k_weight_transpose, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const bf16_raw*>(w), static_cast<bf16_raw*>(w_t), Cout, ksize, ksize, Cin, Cout_pad);
-    return ssd_launch_status();
-}
-
-int ssd_weight_transpose_batched(const long long* desc, int ntensors, int max_tiles, void* stream) {
-    if (!desc || ntensors <= 0 || max_tiles <= 0) return SSD_ERR_VALUE;
-    hipLaunchKernelGGL(k_weight_transpose_batched, dim3((unsigned)max_tiles, (unsigned)ntensors), dim3(256), 0, (hipStream_t)stream, desc);
-    return ssd_launch_status();
-}
-
-int ssd_cast_bf16(const float* src, void* dst, long long n, void* stream) {
-    if (n < 0 || (n > 0 && (!src || !dst))) return SSD_ERR_VALUE;
-    if (n == 0) return SSD_OK;
-    hipLaunchKernelGGL(k_cast_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
-                       static_cast<bf16_raw*>(dst), n);
-    return ssd_launch_status();
-}
-
-int ssd_image_prep(const float* img, void* out, int B, int H, int W, int normalize, void* stream) {
-    if (!img || !out || B <= 0 || H <= 0 || W <= 0) return SSD_ERR_VALUE;
-    const long long npix = (long long)B * H * W;
-    hipLaunchKernelGGL(k_image_prep, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img,
-                       static_cast<bf16_raw*>(out), npix, normalize);
-    return ssd_launch_status();
-}
-
-int ssd_maxpool2x2_fwd(const void* x, void* y, int B, int H, int W, int C, int Ho, int Wo, void* stream) {
-    if (!x || !y || B <= 0 || C <= 0 || C % 8) return SSD_ERR_VALUE;
-    if ((Ho != H / 2 && Ho != (H + 1) / 2) || (Wo != W / 2 && Wo != (W + 1) / 2) || Ho <= 0 || Wo <= 0) return SSD_ERR_VALUE;
-    const long long total = (long long)B * Ho * Wo * (C / 8);
-    hipLaunchKernelGGL(k_maxpool_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const bf16_raw*>(x), static_cast<bf16_raw*>(y), B, H, W, C, Ho, Wo);
-    return ssd_launch_status();
-}
-
-int ssd_maxpool2x2_fwd_argmax(const void* x, void* y, void* code, int B, int H, int W, int C, int Ho, int Wo, void* stream) {
-    if (!x || !y || !code || B <= 0 || C <= 0 || C % 8) return SSD_ERR_VALUE;
-    if ((Ho != H / 2 && Ho != (H + 1) / 2) || (Wo != W / 2 && Wo != (W + 1) / 2) || Ho <= 0 || Wo <= 0) return SSD_ERR_VALUE;
-    const long long total = (long long)B * Ho * Wo * (C / 8);
-    hipLaunchKernelGGL(k_maxpool_fwd_argmax, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const bf16_raw*>(x), static_cast<bf16_raw*>(y), static_cast<unsigned*>(code), B, H, W, C, Ho, Wo);
-    return ssd_launch_status();
-}
-
-int ssd_maxpool2x2_bwd_argmax(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int Ho, int Wo,
-                              void* stream) {
-    if (!code || !dy || !dx || B <= 0 || C <= 0 || C % 8 || Ho <= 0 || Wo <= 0) return SSD_ERR_VALUE;
-    if (2 * Ho < H || 2 * Wo < W) {
-        // VALID pooling of an odd size leaves the last row/column without gradient: clear it first
-        if (hipMemsetAsync(dx, 0, (size_t)B * H * W * C * 2, (hipStream_t)stream) != hipSuccess) return SSD_ERR_LAUNCH;
-    }
-    const long long total = (long long)B * Ho * Wo * (C / 8);
-    hipLaunchKernelGGL(k_maxpool_bwd_argmax, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const unsigned*>(code), static_cast<const bf16_raw*>(dy), static_cast<bf16_raw*>(dx), B, H, W, C,
-                       Ho, Wo);
-    return ssd_launch_status();
-}
-
-int ssd_maxpool2x2_bwd(const void* x, const void* y, const void* dy, void* dx, int B, int H, int W, int C, int Ho, int Wo,
-                       void* stream) {
-    if (!x || !y || !dy || !dx || B <= 0 || C % 8) return SSD_ERR_VALUE;
-    if (2 * Ho < H || 2 * Wo < W) {
-        // VALID pooling of an odd size leaves the last row/column without gradient: clear it first
-        if (hipMemsetAsync(dx, 0, (size_t)B * H * W * C * 2, (hipStream_t)stream) != hipSuccess) return SSD_ERR_LAUNCH;
-    }
-    const long long total = (long long)B * Ho * Wo * (C / 8);
-    hipLaunchKernelGGL(k_maxpool_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(y), static_cast<const bf16_raw*>(dy),
-                       static_cast<bf16_raw*>(dx), B, H, W, C, Ho, Wo);
-    return ssd_launch_status();
-}
-
-int ssd_head_grad_pack(const void* dloc, const void* dconf, void* out, int B, int hw, int per_cell, int classes, int npad,
-                       int anchors_total, int level_off, void* stream) {
-    if (!dloc || !dconf || !out || B <= 0 || hw <= 0 || npad < per_cell * (4 + classes) || npad % 8) return SSD_ERR_VALUE;
-    const long long total = (long long)B * hw * (npad / 8);
-    hipLaunchKernelGGL(k_head_grad_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const bf16_raw*>(dloc), static_cast<const bf16_raw*>(dconf), static_cast<bf16_raw*>(out),
-                       B, hw, per_cell, classes, npad, anchors_total, level_off);
-    return ssd_launch_status();
 }
 
 }  // extern "C"

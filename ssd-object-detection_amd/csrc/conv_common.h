@@ -1,6 +1,8 @@
-// Types, geometry, epilogues and host helpers shared by the convolution translation units (conv.hip, sparse.hip, calib.hip).
+// Types, geometry, epilogues, LDS access helpers and host helpers shared by the convolution translation units (conv.hip,
+// conv_wgrad.hip, conv_aux.hip, pwgemm.hip, chain.hip, sparse.hip, wgrad_sp.hip, fp8conv.hip, calib.hip).
 #pragma once
 #include <atomic>
+#include <cstdint>
 #include <type_traits>
 #include "common.h"
 #include <hip/hip_bf16.h>
@@ -290,6 +292,38 @@ __device__ __forceinline__ void lds_st8_scoped(char* __restrict__ p, const char*
     (void)other;
     *reinterpret_cast<uint2*>(p) = v;
 }
+// LDS fragment read that carries an alias scope (see lds_read_tr16_scoped): keeps the compiler's waitcnt pass from ordering
+// it behind LDS-DMA requests that are in flight for OTHER buffers.
+__device__ __forceinline__ bf16x8_t lds_read_b128_scoped(const char* __restrict__ p, const char* __restrict__ other) {
+    (void)other;
+    return *reinterpret_cast<const bf16x8_t*>(p);
+}
+// Transposing LDS read whose access carries an alias scope (the __restrict__ pair, inlined).  The compiler's waitcnt pass
+// orders an LDS read behind every in-flight LDS-DMA (s_waitcnt vmcnt(0)) unless the read has scope information; without it
+// the first fragment read of a step waited for the NEXT tile's DMA issued just before, i.e. the double buffer never
+// overlapped a transfer with the MFMAs.  The kernels order DMA and reads themselves (s_waitcnt vmcnt + barrier per step).
+typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
+__device__ __forceinline__ s16x4_t lds_read_tr16_scoped(const char* __restrict__ p, const char* __restrict__ other) {
+    (void)other;
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
+}
+
+// LDS-DMA (global -> LDS without VGPR staging).  A lane whose chunk is padding or outside the map fetches this 16-byte zero
+// block where the kernel gives per-lane global addresses; on buffer descriptors it gets an out-of-range offset instead.
+__device__ __attribute__((aligned(16))) const unsigned g_zero16[4] = {0u, 0u, 0u, 0u};
+
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) const void gbl_void;
+
+// (a device function, not a call inside the kernel's lambda: with the builtin written there clang's HOST pass silently emitted
+//  no stub for any instantiation of k_conv_igemm_dma -- an undefined symbol at load time, no diagnostic)
+__device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t r, char* lds, unsigned off) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds, 16, off, 0, 0, 0);
+}
+
+// Halo patch of a 16x16 block of output pixels (the 3x3 / stride 1 / pad 1 kernels of conv.hip, k_conv0_wgrad)
+constexpr int PATCH_W = 18;
+constexpr int PATCH_PIX = PATCH_W * PATCH_W;               // 324
 
 // Second half of the staged epilogue: the [BM px][BN ch] bf16 tile image in LDS (layout above; FWD: bias and ReLU already
 // applied) leaves as whole 16-byte chunks of contiguous rows; DGRAD applies accumulate / ReLU mask here, FWD the fused pooling.
@@ -647,5 +681,23 @@ inline ConvGeom make_geom(int B, int H, int W, int C, int Ho, int Wo, int N, int
     }
     return g;
 }
+
+inline bool geom_ok(int B, int H, int W, int C, int Ho, int Wo, int N, int K) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || N <= 0 || K <= 0) return false;
+    if (C % 8) return false;
+    if ((long long)B * Ho * Wo >= (1ll << 31) || (long long)B * H * W >= (1ll << 31)) return false;
+    if ((long long)B * H * W * C >= (1ll << 32) || (long long)B * Ho * Wo * N >= (1ll << 32)) return false;   // 32-bit element offsets
+    return true;
+}
+
+// Which kernel a call resolves to (ssd_conv2d_*_plan): the dispatch code runs as usual and, with `plan` set, records
+// the id at the launch site and returns instead of launching -- the query cannot drift from the dispatch.
+// ssd_conv2d_*_workgroups: the caller presets *plan to PLAN_WANT_WGS and the launch sites that know their count record
+// the number of ACTIVE workgroups (the grid minus the workgroups that return at once) instead of the id.
+constexpr int PLAN_WANT_WGS = -1;
+#define SSD_PLAN(ID_) do { if (plan) { if (*plan == PLAN_WANT_WGS) return SSD_ERR_UNSUPPORTED; *plan = (ID_); return SSD_OK; } } while (0)
+#define SSD_PLAN_WGS(ID_, WGS_) do { if (plan) { *plan = *plan == PLAN_WANT_WGS ? (int)(WGS_) : (ID_); return SSD_OK; } } while (0)
+// what a query passes for every pointer argument (non-null, never dereferenced)
+void* const PLAN_PTR = reinterpret_cast<void*>(static_cast<uintptr_t>(64));
 
 }  // namespace

@@ -28,7 +28,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef int v8i __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned f8_ld4(const char* __restrict__ p, const char* __restrict__ other) { (void)other; return *reinterpret_cast<const unsigned*>(p); }
 

@@ -26,8 +26,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int PW_HALF = 128 * 128;           // one half-tile image: 128 rows x 64 k bf16
 constexpr int PW_OFF_W0 = 0, PW_OFF_X0 = PW_HALF, PW_OFF_W1 = 2 * PW_HALF, PW_OFF_X1 = 3 * PW_HALF, PW_BUF = 4 * PW_HALF;
 constexpr int PW_RING = 2 * PW_BUF;          // 128 KB: two k-tiles

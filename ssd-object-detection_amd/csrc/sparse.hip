@@ -23,7 +23,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 constexpr unsigned OOB = 0xfffffff0u;
 
 // ------------------------------------------------------------------------------------------------
@@ -243,14 +242,10 @@ __global__ __launch_bounds__(256) void k_hz_col2im(CArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Weight gradient over the compact rows (the tile scheme of k_conv_wgrad_tile, conv.hip): 256 co x 256 (tap, ci) columns
+// Weight gradient over the compact rows (the tile scheme of k_conv_wgrad_tile, conv_wgrad.hip): 256 co x 256 (tap, ci) columns
 // per workgroup, 64 rows per step; the dY image is read straight from the compact rows, the X image is gathered: row m
 // of a step comes from pixel pixel_of_row[m] shifted by the column's tap.  The index of a row is fetched one step ahead.
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-__device__ __forceinline__ s16x4_t lds_read_tr16_scoped(const char* __restrict__ p, const char* __restrict__ other) {
-    (void)other;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-}
+// (fragment reads: lds_read_tr16_scoped, conv_common.h)
 
 struct WLevel {
     const bf16_raw* x;                       // [B,H,W,Cin]

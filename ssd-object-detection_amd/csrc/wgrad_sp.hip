@@ -33,7 +33,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((__vector_size__(16 * sizeof(__bf16)))) __bf16 bf16x16_t;
 
 constexpr int SP_PW = 18, SP_PPIX = 18 * 18, SP_PINSTR = (SP_PPIX * 8 + 63) / 64, SP_PBYTES = SP_PINSTR * 1024;   // 41 KB
