@@ -584,6 +584,7 @@ class SSDEngine:
         # second layer's data gradient and first layer's weight gradient in one kernel (the gradient w.r.t. the first layer's
         # output has no other consumer and is never stored); False after a refusal
         self.fuse_first = os.environ.get("SSD_FUSE_FIRST", "1") == "1"
+        self.first_fused = False               # the last backward() ran that kernel: gacts[1] was consumed on chip, not written
         self.wgrad_probe = None                # dict(nodes={...}, events=[]): time those layers' weight-gradient launches in the step
         # inference in block-scaled fp8 (forward(x, "mxfp8")): the plan (mxfp8_vgg_plan, at the first fp8 forward), the fp8 layers'
         # quantised filters and whether the last forward ran in fp8 (backward() then refuses)
@@ -914,6 +915,12 @@ class SSDEngine:
                 main.wait_stream(tail)
         return c["loc"], c["conf"]
 
+    @staticmethod
+    def _pool_same(nd):
+        """Whether pooling node nd keeps the last row / column of an odd map (TF 'SAME': hout = ceil(hin / 2)); a VALID pooling
+        of an odd map drops it (hout = floor(hin / 2)), and on an even map the two are the same windows."""
+        return nd["hout"] * 2 > nd["hin"]
+
     def _bf16_node(self, i, c):
         """Launch trunk node i of the bf16 forward (a pool behind a convolution runs inside that convolution's call)."""
         nd, acts = self.nodes[i], c["acts"]
@@ -926,7 +933,7 @@ class SSDEngine:
                 # nothing but the pooling reads this conv's full-resolution output (the backward pass works from the
                 # pooled map and the winner codes): ask for the pooled map only, where a fused kernel serves the layer
                 pool_only = self.pool_only.get(i, self.skip_fullres)
-                args += (True, nxt["hout"] * 2 != nxt["hin"])
+                args += (True, self._pool_same(nxt))
                 kw = dict(out=acts[i + 1], pool_out=acts[i + 2], code=c["pool_code"][i + 1], ws=self._ws)
                 if pool_only:                     # (refused with SSD_ERR_VALUE: no pooling kernel for this shape)
                     pool_only = _launched(ops.conv2d_fwd_pool, *args, pool_only=True, refused=ValueError, **kw)
@@ -944,7 +951,7 @@ class SSDEngine:
                     ops.conv2d_fwd(*args, True, out=acts[i + 1], ws=self._ws)
         elif i == 0 or self.nodes[i - 1]["kind"] != "conv":
             ops.maxpool2x2_fwd_argmax(acts[i], out=acts[i + 1], code=c["pool_code"][i],
-                                      same=nd["hout"] * 2 != nd["hin"])
+                                      same=self._pool_same(nd))
 
     # ---------------------------------------------------------------- inference in block-scaled fp8 (MX e4m3)
     def vgg_mxfp8_plan(self):
@@ -1018,7 +1025,7 @@ class SSDEngine:
         kw = dict(want_bf16="bf16" in w, want_fp8="fp8" in w, out=acts[o + 1], out_q=q, out_scale=sc)
         if o != i:
             pnd = self.nodes[o]
-            ops.conv2d_fwd_pool_mxfp8(*args, pnd["hout"] * 2 != pnd["hin"], **kw)
+            ops.conv2d_fwd_pool_mxfp8(*args, self._pool_same(pnd), **kw)
         else:
             ops.conv2d_fwd_mxfp8(*args, **kw)
 
@@ -1108,6 +1115,7 @@ class SSDEngine:
         for i in range(len(self.nodes) - 1, -1, -1):   # trunk, last layer first
             p.node(i)                              # data gradient: main stream; weight gradient and optimizer bucket: side
         p.finish()                                 # joins the streams; the deferred optimizer buckets at the end of the main stream
+        self.first_fused = p.first_fused
 
     # ---------------------------------------------------------------- optimizer
     def clip_scales(self, clip=0.01):

@@ -688,6 +688,14 @@ def conv2d_fwd(x, w, bias, stride, pad_t, pad_l, Ho, Wo, relu, out=None, ws=None
     return out
 
 
+def _pooled_shapes(bhw, *buffers):
+    """The pooled outputs a caller hands in, (tensor, channels) each: contiguous [B, Hp, Wp, channels] of the window grid this
+    call computes, or ValueError -- the kernels write that grid whatever the buffer's size."""
+    for t, ch in buffers:
+        if tuple(t.shape) != tuple(bhw) + (ch,) or not t.is_contiguous():
+            raise ValueError("pooled output of shape %s, contiguous %s: this call writes %s" % (tuple(t.shape), t.is_contiguous(), tuple(bhw) + (ch,)))
+
+
 def conv2d_fwd_pool(x, w, bias, stride, pad_t, pad_l, Ho, Wo, relu, same, out=None, pool_out=None, code=None, ws=None,
                     pool_only=False):
     """conv2d_fwd followed by maxpool2x2_fwd_argmax of its output, fused on chip where the kernel allows.
@@ -706,6 +714,7 @@ def conv2d_fwd_pool(x, w, bias, stride, pad_t, pad_l, Ho, Wo, relu, same, out=No
         pool_out = torch.empty((B, Hp, Wp, Cout), dtype=torch.bfloat16, device=x.device)
     if code is None:
         code = torch.empty((B, Hp, Wp, Cout // 8), dtype=torch.int32, device=x.device)
+    _pooled_shapes((B, Hp, Wp), (pool_out, Cout), (code, Cout // 8))
     wbuf = _splitk_ws(ws)
     _lib.check(L.ssd_conv2d_fwd_pool(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(pool_out), _ptr(code), B, H, W, Cin, Cout, k,
                                      stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, Hp, Wp, _ptr(wbuf), wbuf.numel(), _stream()))
@@ -1084,6 +1093,7 @@ def maxpool2x2_fwd_argmax(x, same=False, out=None, code=None):
         out = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
     if code is None:
         code = torch.empty((B, Ho, Wo, C // 8), dtype=torch.int32, device=x.device)
+    _pooled_shapes((B, Ho, Wo), (out, C), (code, C // 8))
     _lib.check(L.ssd_maxpool2x2_fwd_argmax(_ptr(x), _ptr(out), _ptr(code), B, H, W, C, Ho, Wo, _stream()))
     return out, code
 
@@ -1201,8 +1211,7 @@ def conv2d_fwd_pool_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, re
             out_q = torch.empty((B, Hp, Wp, Cout), dtype=torch.uint8, device=xq.device)
         if out_scale is None:
             out_scale = torch.empty((B, Hp, Wp, max(Cout // 32, 1)), dtype=torch.uint8, device=xq.device)
-    for t in ((out,) if want_bf16 else ()) + ((out_q, out_scale) if want_fp8 else ()):
-        assert t.is_contiguous() and tuple(t.shape[:3]) == (B, Hp, Wp), t.shape
+    _pooled_shapes((B, Hp, Wp), *(((out, Cout),) if want_bf16 else ()) + (((out_q, Cout), (out_scale, max(Cout // 32, 1))) if want_fp8 else ()))
     rc = L.ssd_conv2d_fwd_pool_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
                                      _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
                                      k, stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, Hp, Wp, _stream())

@@ -1,0 +1,286 @@
+"""Teacher-forced float64 backward pass of the SSD networks -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
+
+The oracle's backward is LINEAR: every data-dependent decision is an input, taken from a forward pass that somebody else ran
+(the engine's on the GPU, or a float64 one on the CPU): ReLU masks are `act > 0` of the stored activations, pooling routes are the
+stored winner codes, the weight gradients multiply the stored activations, the L2 normalisation works on the stored map.  What is
+left is float64 arithmetic on the CPU (strict.ref_conv through autograd, strict.ref_unpool, l2norm_oracle.bwd64) and the wiring of
+the network.  No mask can flip, so a missing or doubled contribution, a wrong mask source, a wrong route or an overwrite where an
+accumulate belongs shows at full size.
+
+Two modes of one walk:
+  T  exact float64;
+  R  (round_maps=True) the engine's storage: a gradient map is rounded to bf16 every time a contribution has been added to it
+     (the head's first, then its consumers from the last node to the first), the rounded value is what is read downstream, and
+     the map the L2 normalisation's backward reads (the head's data gradient w.r.t. the normalised map) is rounded as well; weight
+     gradients are computed from rounded maps and not rounded.  R never sees what a kernel returned: rel_l2(R, T) is the size of
+     the bf16 storage noise, and the bound of a tensor is 3 * rel_l2(R_t, T_t) + 1e-3 (bounds()).
+
+Activation index a = node + 1 (index 0 is the image); gradient maps are named "gact<a>", parameters as the engines name them
+("conv<node>/kernel", "head<level>/bias", "l2norm0/scale").
+
+defect=(kind, arg) seeds ONE wiring error into the same walk:
+  ("no_head", level)            the head's data gradient is not added to its feature map
+  ("mask_output", node)         the convolution's data gradient is masked by its OUTPUT's sign (a shape-preserving layer)
+  ("no_mask", node)             ... is not masked at all
+  ("pool_first", node)          the pooling routes every window to position 0
+  ("pool_pitch", node)          a VALID pooling of an odd map un-pooled at the SAME pooling's pitch, ceil(hin / 2): the pooled
+                                gradient and its codes read as rows of one more window (the bug the engine had)
+  ("wgrad_before_head", level)  the weight gradient of the layer that produces the level is computed without the head's part
+  ("l2norm_scale_only", None)   the normalisation's backward is a multiplication with the scale
+  ("overwrite", (a, node))      node's contribution to map a replaces what the map held
+  ("no_identity", add) ("no_projection", add) ("no_shortcut_mask", add)   the shortcut term of an add dropped / not masked"""
+import time
+
+import torch
+
+from tests import strict as S
+from tests import l2norm_oracle as LO
+
+F64 = torch.float64
+SUM_ORDER = 1e-3                       # fp32 summation order of a weight gradient (tests/test_wgrad_unpooled_gpu.py)
+PAD_BITS = 0x4B1D5EED                  # a finite fp32 (about 1.03e7) no gradient comes near: the padding between tensors
+
+
+def rel_l2(a, b):
+    a, b = a.to(F64), b.to(F64)
+    return float((a - b).norm() / (b.norm() + 1e-300))
+
+
+def to_bf16(t):
+    return t.to(torch.float32).to(torch.bfloat16).to(F64)
+
+
+def unpack_codes(words):
+    """int32 [..., C/8] of eight 4-bit codes -> int64 [..., C] (the inverse of strict.pack_codes)"""
+    w = words.to(torch.int64) & 0xFFFFFFFF
+    return ((w[..., None] >> (4 * torch.arange(8, dtype=torch.int64))) & 15).reshape(*words.shape[:-1], words.shape[-1] * 8)
+
+
+def conv_vjp(x, w, g, k, stride, pt, pl, need_dx=True):
+    """(dx or None, dw, db): the gradients of strict.ref_conv(x, w) against g, float64"""
+    xr = x.to(F64).detach().requires_grad_(need_dx)
+    wr = w.to(F64).detach().requires_grad_(True)
+    y = S.ref_conv(xr, wr, None, k, stride, pt, pl, g.shape[1], g.shape[2], False)
+    grads = torch.autograd.grad(y, [xr, wr] if need_dx else [wr], g)
+    return (grads[0] if need_dx else None), grads[-1], g.sum((0, 1, 2))
+
+
+def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, l2norm, round_maps, defect, first_node=0):
+    rnd = to_bf16 if round_maps else (lambda t: t)
+    defect = tuple(defect) if defect else (None, None)
+    B = dloc.shape[0]
+    G, grads, head_part = {}, {}, {}
+
+    def masked(a, g):
+        return g * (acts[a] > 0)
+
+    def add(a, g, writer):
+        if a in G and defect != ("overwrite", (a, writer)):
+            g = G[a] + g
+        G[a] = rnd(g)
+
+    off = 0
+    for lvl, ((ni, h, c), n) in enumerate(zip(fm, num_priors)):
+        a, cnt = ni + 1, h * h * n
+        dy = torch.cat([dloc[:, off:off + cnt].to(F64).reshape(B, h, h, n * 4),
+                        dconf[:, off:off + cnt].to(F64).reshape(B, h, h, n * classes)], -1)
+        off += cnt
+        normed = l2norm is not None and lvl == 0
+        dx, dw, db = conv_vjp(l2norm["y"] if normed else acts[a], weights["head%d/kernel" % lvl], dy, 3, 1, 1, 1)
+        grads["head%d/kernel" % lvl], grads["head%d/bias" % lvl] = dw, db
+        dx = masked(a, dx)
+        if normed:
+            dx = rnd(dx)                                   # the gradient w.r.t. the normalised map is a stored bf16 map
+            s = l2norm["scale"].to(F64)
+            gx, ds = LO.bwd64(dx.reshape(-1, c).numpy(), acts[a].to(F64).reshape(-1, c).numpy(), s.numpy(), l2norm["eps"])
+            grads["l2norm0/scale"] = torch.from_numpy(ds)
+            dx = dx * s if defect[0] == "l2norm_scale_only" else torch.from_numpy(gx).reshape(dx.shape)
+        head_part[a] = dx
+        add(a, torch.zeros_like(dx) if defect == ("no_head", lvl) else dx, "head")
+    assert off == dloc.shape[1] == dconf.shape[1]
+
+    for i in range(len(nodes) - 1, first_node - 1, -1):
+        nd, g = nodes[i], G[i + 1]
+        kind, src = nd["kind"], nd.get("src", i - 1)
+        if kind == "add":
+            a_, sc = src
+            add(a_ + 1, g, i)                              # the block output takes the gradient unchanged
+            if nodes[sc]["kind"] == "conv" and not nodes[sc].get("relu", True):
+                add(sc + 1, torch.zeros_like(g) if defect == ("no_projection", i) else g, i)
+            else:                                          # identity shortcut: the source's own ReLU, summed with its other uses
+                t = g if defect == ("no_shortcut_mask", i) else masked(sc + 1, g)
+                add(sc + 1, torch.zeros_like(g) if defect == ("no_identity", i) else t, i)
+            continue
+        if kind in ("pool", "pool3"):
+            ks, pad, none = (2, 0, 4) if kind == "pool" else (3, nd["pt"], 15)
+            code = pool_codes[i]
+            if defect == ("pool_first", i):
+                code = torch.where(code != none, torch.zeros_like(code), code)
+            if defect == ("pool_pitch", i):
+                ho, hs = g.shape[1], (nd["hin"] + 1) // 2
+                assert kind == "pool" and hs == ho + 1, "pool_pitch needs a VALID pooling of an odd map"
+
+                def repitch(t):                            # the same bytes per image, read at the other pitch
+                    flat = torch.cat([t.reshape(B, -1), torch.zeros((B, (hs * hs - ho * ho) * t.shape[-1]), dtype=t.dtype)], 1)
+                    return flat.reshape(B, hs, hs, t.shape[-1])[:, :ho, :ho].contiguous()
+                g, code = repitch(g), repitch(code)
+            add(src + 1, S.ref_unpool(code, g, (B, nd["hin"], nd["hin"], nd["cin"]), ks, 2, pad, pad), i)
+            continue
+        assert kind == "conv"
+        x, w = acts[src + 1], weights["conv%d/kernel" % i]
+        dx, dw, db = conv_vjp(x, w, g, nd["k"], nd["stride"], nd["pt"], nd["pl"], need_dx=src >= 0)
+        if defect[0] == "wgrad_before_head" and fm[defect[1]][0] == i:
+            _, dw, db = conv_vjp(x, w, g - head_part[i + 1], nd["k"], nd["stride"], nd["pt"], nd["pl"], need_dx=False)
+        grads["conv%d/kernel" % i], grads["conv%d/bias" % i] = dw, db
+        if src < 0:
+            continue                                       # no gradient w.r.t. the image
+        if nodes[src].get("relu", nodes[src]["kind"] == "conv"):
+            if defect == ("mask_output", i):
+                assert dx.shape == g.shape, "mask_output needs a shape-preserving layer"
+                dx = masked(i + 1, dx)
+            elif defect != ("no_mask", i):
+                dx = masked(src + 1, dx)
+        add(src + 1, dx, i)                                # (behind a pooling the route alone decides: code `none` = no gradient)
+    out = dict(grads)
+    out.update(("gact%d" % a, g) for a, g in G.items() if a > first_node)     # (below it the maps are incomplete)
+    return out
+
+
+def backward_chain(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, l2norm=None, round_maps=False,
+                   defect=None, first_node=0):
+    """The VGG-style engines (SSDEngine.nodes: node i reads node i - 1).  weights: name -> tensor; acts: activation index ->
+    stored map, None where the forward stored none (pool_only); pool_codes: node -> int64 [B,Ho,Wo,C] winner codes;
+    l2norm: None or dict(scale, y = the stored normalised map, eps).  Returns {name: float64 tensor} of every parameter
+    gradient and every gradient map.  first_node: the walk ends behind that node (what it returns is complete: the gradients
+    of the nodes it visited, the maps above them) -- a defect deep in the network need not pay for the wide layers."""
+    return _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, l2norm, round_maps, defect, first_node)
+
+
+def backward_graph(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, round_maps=False, defect=None,
+                   first_node=0):
+    """The same for ResNet50SSDEngine.nodes (kind conv | pool3 | add with src and relu).  An add hands its gradient to the block
+    output unchanged, to a projection shortcut unchanged, to an identity shortcut masked by the source's ReLU and summed with
+    the source's other uses."""
+    return _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, None, round_maps, defect, first_node)
+
+
+# ---- the rule --------------------------------------------------------------------------------------------------------------
+def bounds(T, R):
+    """name -> 3 * rel_l2(R, T) + 1e-3: both terms from the reference side (module docstring)"""
+    return {k: 3.0 * rel_l2(R[k], T[k]) + SUM_ORDER for k in T}
+
+
+def compare(got, T, R, title, out=print):
+    """Prints one row per tensor of `got` (name, error against T, R's error against T, bound); returns the rows beyond their
+    bound as [(name, err, r_err, bound)] and the worst row by err / bound."""
+    bad, worst, bound = [], None, bounds(T, R)
+    out("%s\n%-22s %11s %11s %11s" % (title, "tensor", "err vs T", "R vs T", "bound"))
+    for name in got:
+        row = (name, rel_l2(got[name], T[name]), rel_l2(R[name], T[name]), bound[name])
+        err = row[1]
+        out("%-22s %11.3e %11.3e %11.3e%s" % (row + ("" if err <= row[3] else "   <-- FAIL",)))
+        if not err <= row[3]:
+            bad.append(row)
+        if worst is None or err / row[3] > worst[1] / worst[3]:
+            worst = row
+    out("worst: %s err %.3e R %.3e bound %.3e" % worst)
+    return bad, worst
+
+
+def moved(T, D, bound):
+    """The tensors a seeded defect moved to at least twice their bound: [(name, rel_l2(D, T), bound)]"""
+    return [(k, rel_l2(D[k], T[k]), bound[k]) for k in D if rel_l2(D[k], T[k]) >= 2.0 * bound[k]]
+
+
+# ---- the engine's side (GPU tensors in, CPU tensors out) -------------------------------------------------------------------
+def poison(engine, c):
+    """NaN in every gradient map and every gradient tensor, PAD_BITS in the padding between the tensors"""
+    for g in c["gacts"][1:]:
+        g.fill_(float("nan"))
+    engine.grad.view(torch.int32).fill_(PAD_BITS)
+    for t in engine.tensors:
+        engine.grad[t.offset:t.offset + t.numel].fill_(float("nan"))
+
+
+def padding_untouched(engine, grad_cpu):
+    pad = torch.ones(engine.n_flat, dtype=torch.bool)
+    for t in engine.tensors:
+        pad[t.offset:t.offset + t.numel] = False
+    return bool((grad_cpu.view(torch.int32)[pad] == PAD_BITS).all())
+
+
+def gemm_arrays(engine):
+    """The arrays the network computes with: conv kernels / biases, the fused per-level head arrays, the l2norm scale"""
+    out = [t for i in sorted(engine.conv_params) for t in engine.conv_params[i]] + [t for pair in engine.head_params for t in pair]
+    return out + ([engine.l2norm_scale] if engine.l2norm_scale is not None else [])
+
+
+def engine_weights(engine):
+    bf, f32 = engine.param_bf16.float().cpu(), engine.param.cpu()
+    return {t.name: (bf if t.name.endswith("kernel") else f32)[t.offset:t.offset + t.numel].view(t.shape).to(F64)
+            for t in gemm_arrays(engine)}
+
+
+def engine_grads(engine, c, maps):
+    """name -> CPU tensor: every parameter gradient and the gradient maps of activation indices `maps`"""
+    flat = engine.grad.cpu()
+    got = {t.name: flat[t.offset:t.offset + t.numel].view(t.shape) for t in gemm_arrays(engine)}
+    got.update(("gact%d" % a, c["gacts"][a].float().cpu()) for a in maps)
+    return got, flat
+
+
+def check_outputs(engine, c, got, flat, maps):
+    """What backward() must leave behind a poison(): everything it writes finite, nothing else touched"""
+    for name, t in got.items():
+        assert bool(torch.isfinite(t).all()), "%s is not finite: no launch produced it, or one accumulated into an unwritten map" % name
+    for a in range(1, len(c["gacts"])):
+        if a not in maps:
+            assert bool(torch.isnan(c["gacts"][a].float()).all()), "gact%d: the configuration does not write it, yet it changed" % a
+    assert padding_untouched(engine, flat), "the padding between gradient tensors changed"
+    assert float(got["conv0/kernel"][..., 3:].abs().max()) == 0.0, "conv0/kernel: the padded input channels got a gradient"
+
+
+class Forced:
+    """One engine, one forward + backward on it behind a poison(), and the oracle's T and R on what that forward stored.  A
+    subclass says which gradient maps the configuration writes (written_maps), what the forward stored (stored_forward ->
+    activations, codes, l2norm) and which walk is the engine's (walk)."""
+
+    def __init__(self, engine, B, seed, classes=81, level_scale=None):
+        import ssd_object_detection_amd.ops as ops
+        torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
+        self.engine, self.B, self.classes = engine, B, classes
+        g = torch.Generator().manual_seed(seed)
+        s = engine.in_size
+        x = ops.image_prep(torch.rand((B, s, s, 3), generator=g).cuda())
+        self.dloc = (torch.randn((B, engine.A, 4), generator=g) * 1e-3).bfloat16()
+        self.dconf = (torch.randn((B, engine.A, classes), generator=g) * 1e-3).bfloat16()
+        for lvl, f in enumerate(level_scale or ()):                     # a power of two per level: still bf16 values
+            lo, hi = engine.level_off[lvl], engine.level_off[lvl + 1]
+            self.dloc[:, lo:hi] *= f
+            self.dconf[:, lo:hi] *= f
+        engine.forward(x)
+        self.c = c = engine._acts(B)
+        poison(engine, c)
+        engine.backward(self.dloc.cuda(), self.dconf.cuda())
+        torch.cuda.synchronize()
+        self.maps = self.written_maps()
+        self.got, self.flat = engine_grads(engine, c, self.maps)
+        self.stored, self.codes, self.l2norm = self.stored_forward()
+        self.weights = engine_weights(engine)
+        t0 = time.time()
+        self.T, self.R = self.oracle(), self.oracle(round_maps=True)
+        self.bound = bounds(self.T, self.R)
+        print("oracle: T + R in %.1f s" % (time.time() - t0))
+
+    def oracle(self, **kw):
+        e = self.engine
+        return self.walk(e.nodes, e.fm, e.num_priors, self.classes, self.weights, self.stored, self.codes, self.dloc, self.dconf, **kw)
+
+    def check_forward_state(self):
+        raise NotImplementedError
+
+    def check(self, title):
+        self.check_forward_state()
+        check_outputs(self.engine, self.c, self.got, self.flat, self.maps)
+        bad, _ = compare(self.got, self.T, self.R, title)
+        assert not bad, "beyond 3 * rel_l2(R, T) + 1e-3: " + ", ".join("%s %.3e > %.3e" % (n, e, b) for n, e, _, b in bad)

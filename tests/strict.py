@@ -881,6 +881,7 @@ MX_FWD_CASES = MX_CONV3X3_CASES + MX_CONV2D_CASES + MX_POOL_CASES
 EXTRAS = {
     "pool2x2 (2,20,20,64) valid": lambda: pool2x2_case(2, 20, 20, 64, False),
     "pool2x2 (2,21,23,64) same": lambda: pool2x2_case(2, 21, 23, 64, True),
+    "pool2x2 (2,21,23,64) valid": lambda: pool2x2_case(2, 21, 23, 64, False),   # the last row / column lies in no window
     "pool3x3s2 (2,9,9,64)": lambda: pool3x3_case(2, 9, 9, 64),
     "pool3x3s2 (2,37,50,64)": lambda: pool3x3_case(2, 37, 50, 64),
     "eltwise (3,17,19,64)": lambda: eltwise_case((3, 17, 19, 64)),

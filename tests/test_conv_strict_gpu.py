@@ -328,7 +328,7 @@ def pack_fragments(w):
 
 
 # ---------------------------------------------------------------- pooling and element-wise kernels
-@pytest.mark.parametrize("case", [(2, 20, 20, 64, False), (2, 21, 23, 64, True)], ids=str)
+@pytest.mark.parametrize("case", [(2, 20, 20, 64, False), (2, 21, 23, 64, True), (2, 21, 23, 64, False)], ids=str)
 def test_maxpool2x2_strict(ops, L, case):
     B, H, W, C, same = case
     r = strict.pool2x2_case(*case)

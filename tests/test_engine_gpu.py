@@ -224,12 +224,15 @@ def test_full_batch_is_image_independent(engine):
         loc, conf = loc.clone(), conf.clone()
         engine.backward(dl, dc)
         torch.cuda.synchronize()
-        return loc, conf, engine._acts(B)["gacts"][1].clone(), engine.grad.clone()
+        # the lowest gradient map this schedule writes: the fused first pair consumes the gradient w.r.t. block1_conv1's output
+        # on chip and never stores it (gacts[1] then holds whatever the allocator handed out)
+        return loc, conf, engine._acts(B)["gacts"][2 if engine.first_fused else 1].clone(), engine.grad.clone()
 
     loc, conf, g1, grad = run(x, dloc, dconf)
     loc_p, conf_p, g1_p, grad_p = run(x[perm].contiguous(), dloc[perm].contiguous(), dconf[perm].contiguous())
     assert torch.equal(loc_p, loc[perm]) and torch.equal(conf_p, conf[perm])
-    assert torch.equal(g1_p, g1[perm])                       # gradient w.r.t. block1_conv1's output, per image
+    assert bool(torch.isfinite(g1.float()).all()) and float(g1.float().abs().max()) > 0
+    assert torch.equal(g1_p, g1[perm])                       # gradient w.r.t. block1_conv1's (fused pair: block1_conv2's) output, per image
     err = float((grad_p - grad).norm() / grad.norm())
     assert err < 1e-3, err                                   # the same products summed in another order
 
