@@ -28,7 +28,23 @@ defect=(kind, arg) seeds ONE wiring error into the same walk:
   ("wgrad_before_head", level)  the weight gradient of the layer that produces the level is computed without the head's part
   ("l2norm_scale_only", None)   the normalisation's backward is a multiplication with the scale
   ("overwrite", (a, node))      node's contribution to map a replaces what the map held
-  ("no_identity", add) ("no_projection", add) ("no_shortcut_mask", add)   the shortcut term of an add dropped / not masked"""
+  ("no_identity", add) ("no_projection", add) ("no_shortcut_mask", add)   the shortcut term of an add dropped / not masked
+
+mx=dict(dgrad, dy, wt): the MX-fp8 training backward of ResNet50SSDEngine, the same walk with one more forced operand.  A
+bf16 rounding that differs between engine and oracle flips e4m3 roundings of the next fp8 operand (measured on the CPU: 1.6e-2
+relative L2 per layer, against 1.7e-3 of bf16 storage noise), so the oracle does not quantise its own maps: the
+data gradient of a convolution i in mx["dgrad"] is the float64 one of
+  g := mx["dy"][root(i)]   the stored fp8 gradient map the launch read, dequantised (strict.ref_dequantize_mx): forward-like
+                           state, taken as given like a mask or a route;
+  w := mx["wt"][i]         the filters [Cout,k,k,Cin] as mx_filters() quantises them (the oracle's own: exact bf16 in, so
+                           nothing can flip),
+root(i) = the node whose gradient buffer node i's output shares, derived HERE from the adds the walk has passed (an add
+gives its buffer to its block output and to a linear projection shortcut), never from the product's plan.  Weight and bias
+gradients still come from the oracle's own map and the stored activation; mask, accumulate and rounding are unchanged.
+trace: a dict the walk fills with "root" (node -> root), for the caller to compare with the engine's plan.  Two more defects:
+  ("mx_wrong_dy", node)         fp8 data gradient `node` reads the stored fp8 map of the nearest other root of the same shape
+  ("mx_stale_dy", root)         every reader of `root` reads the oracle's own quantisation of that map as it stood after its
+                                FIRST writer, not its last"""
 import time
 
 import torch
@@ -65,11 +81,37 @@ def conv_vjp(x, w, g, k, stride, pt, pl, need_dx=True):
     return (grads[0] if need_dx else None), grads[-1], g.sum((0, 1, 2))
 
 
-def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, l2norm, round_maps, defect, first_node=0):
+def conv_dx(x, w, g, k, stride, pt, pl):
+    """conv_vjp's dx alone (the input's values do not enter it: the convolution is linear)"""
+    xr = x.to(F64).detach().requires_grad_(True)
+    y = S.ref_conv(xr, w.to(F64).detach(), None, k, stride, pt, pl, g.shape[1], g.shape[2], False)
+    return torch.autograd.grad(y, [xr], g.to(F64))[0]
+
+
+def mx_round(t):
+    """What an MX-fp8 operand holds of a map: the bf16 value quantised by the CPU rule (strict.ref_quantize_mx: blocks of 32
+    along the last axis) and dequantised, float64"""
+    return S.ref_dequantize_mx(*S.ref_quantize_mx(t.to(torch.float32).to(torch.bfloat16).contiguous())).to(F64)
+
+
+def flipped_transpose(w):
+    """[Cout,k,k,Cin] -> [Cin,k,k,Cout] with both spatial axes mirrored: the layout of the engines' w_t"""
+    return w.permute(3, 1, 2, 0).flip(1, 2).contiguous()
+
+
+def mx_filters(w):
+    """bf16 filters [Cout,k,k,Cin] as an fp8 data gradient holds them: quantised along Cout in blocks of 32 (the last axis of
+    the transposed filters), dequantised, back in [Cout,k,k,Cin]"""
+    return mx_round(w.permute(3, 1, 2, 0)).permute(3, 1, 2, 0).contiguous()
+
+
+def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, l2norm, round_maps, defect, first_node=0,
+          mx=None, trace=None):
     rnd = to_bf16 if round_maps else (lambda t: t)
     defect = tuple(defect) if defect else (None, None)
     B = dloc.shape[0]
     G, grads, head_part = {}, {}, {}
+    root, first = {}, {}                   # node -> the node whose gradient buffer it shares; map -> its value after its first writer
 
     def masked(a, g):
         return g * (acts[a] > 0)
@@ -78,6 +120,19 @@ def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf
         if a in G and defect != ("overwrite", (a, writer)):
             g = G[a] + g
         G[a] = rnd(g)
+        first.setdefault(a, G[a])
+
+    def mx_operand(i):                                     # the dy of fp8 data gradient i
+        r = root.get(i, i)
+        dy = mx["dy"][r]
+        if defect == ("mx_wrong_dy", i):
+            other = [q for q in sorted(mx["dy"]) if q != r and mx["dy"][q].shape == dy.shape]
+            assert other, "mx_wrong_dy needs another root of the same shape"
+            dy = mx["dy"][min(other, key=lambda q: abs(q - r))]
+        if defect == ("mx_stale_dy", r):
+            dy = mx_round(first[r + 1])
+        assert dy.shape == G[i + 1].shape, (i, r)
+        return dy
 
     off = 0
     for lvl, ((ni, h, c), n) in enumerate(zip(fm, num_priors)):
@@ -105,8 +160,10 @@ def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf
         if kind == "add":
             a_, sc = src
             add(a_ + 1, g, i)                              # the block output takes the gradient unchanged
+            root[a_] = root.get(i, i)
             if nodes[sc]["kind"] == "conv" and not nodes[sc].get("relu", True):
                 add(sc + 1, torch.zeros_like(g) if defect == ("no_projection", i) else g, i)
+                root[sc] = root.get(i, i)
             else:                                          # identity shortcut: the source's own ReLU, summed with its other uses
                 t = g if defect == ("no_shortcut_mask", i) else masked(sc + 1, g)
                 add(sc + 1, torch.zeros_like(g) if defect == ("no_identity", i) else t, i)
@@ -128,7 +185,10 @@ def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf
             continue
         assert kind == "conv"
         x, w = acts[src + 1], weights["conv%d/kernel" % i]
-        dx, dw, db = conv_vjp(x, w, g, nd["k"], nd["stride"], nd["pt"], nd["pl"], need_dx=src >= 0)
+        fp8 = mx is not None and i in mx["dgrad"]
+        dx, dw, db = conv_vjp(x, w, g, nd["k"], nd["stride"], nd["pt"], nd["pl"], need_dx=src >= 0 and not fp8)
+        if fp8:
+            dx = conv_dx(x, mx["wt"][i], mx_operand(i), nd["k"], nd["stride"], nd["pt"], nd["pl"])
         if defect[0] == "wgrad_before_head" and fm[defect[1]][0] == i:
             _, dw, db = conv_vjp(x, w, g - head_part[i + 1], nd["k"], nd["stride"], nd["pt"], nd["pl"], need_dx=False)
         grads["conv%d/kernel" % i], grads["conv%d/bias" % i] = dw, db
@@ -141,6 +201,8 @@ def _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf
             elif defect != ("no_mask", i):
                 dx = masked(src + 1, dx)
         add(src + 1, dx, i)                                # (behind a pooling the route alone decides: code `none` = no gradient)
+    if trace is not None:
+        trace["root"] = [root.get(i, i) for i in range(len(nodes))]
     out = dict(grads)
     out.update(("gact%d" % a, g) for a, g in G.items() if a > first_node)     # (below it the maps are incomplete)
     return out
@@ -157,11 +219,12 @@ def backward_chain(nodes, fm, num_priors, classes, weights, acts, pool_codes, dl
 
 
 def backward_graph(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, round_maps=False, defect=None,
-                   first_node=0):
+                   first_node=0, mx=None, trace=None):
     """The same for ResNet50SSDEngine.nodes (kind conv | pool3 | add with src and relu).  An add hands its gradient to the block
     output unchanged, to a projection shortcut unchanged, to an identity shortcut masked by the source's ReLU and summed with
-    the source's other uses."""
-    return _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, None, round_maps, defect, first_node)
+    the source's other uses.  mx, trace: the MX-fp8 training backward (module docstring)."""
+    return _walk(nodes, fm, num_priors, classes, weights, acts, pool_codes, dloc, dconf, None, round_maps, defect, first_node,
+                 mx, trace)
 
 
 # ---- the rule --------------------------------------------------------------------------------------------------------------
@@ -194,12 +257,18 @@ def moved(T, D, bound):
 
 # ---- the engine's side (GPU tensors in, CPU tensors out) -------------------------------------------------------------------
 def poison(engine, c):
-    """NaN in every gradient map and every gradient tensor, PAD_BITS in the padding between the tensors"""
+    """NaN in every gradient map and every gradient tensor, PAD_BITS in the padding between the tensors.  Behind a training-mode
+    fp8 forward also byte 0x7F (e4m3 NaN; as a scale 2^0) in every fp8 gradient map and in the fp8 transposed filters, where
+    allocated: an fp8 map nobody wrote turns its reader's output non-finite."""
     for g in c["gacts"][1:]:
         g.fill_(float("nan"))
     engine.grad.view(torch.int32).fill_(PAD_BITS)
     for t in engine.tensors:
         engine.grad[t.offset:t.offset + t.numel].fill_(float("nan"))
+    if getattr(engine, "_mx_train", False):
+        stale = [t for pair in engine.mxfp8_grads(c["acts"][1].shape[0]).values() for t in pair]
+        for t in stale + list(engine._mx_wt or ()):
+            t.fill_(0x7F)
 
 
 def padding_untouched(engine, grad_cpu):
@@ -243,7 +312,10 @@ def check_outputs(engine, c, got, flat, maps):
 class Forced:
     """One engine, one forward + backward on it behind a poison(), and the oracle's T and R on what that forward stored.  A
     subclass says which gradient maps the configuration writes (written_maps), what the forward stored (stored_forward ->
-    activations, codes, l2norm) and which walk is the engine's (walk)."""
+    activations, codes, l2norm) and which walk is the engine's (walk); it may run another forward (run_forward), pass
+    backward() keywords (backward_kwargs) and hand the walk its forced MX-fp8 operands (mx_operands).  run() does all of it
+    again on the same engine and inputs (a test that changed how the engine runs)."""
+    backward_kwargs = {}
 
     def __init__(self, engine, B, seed, classes=81, level_scale=None):
         import ssd_object_detection_amd.ops as ops
@@ -251,22 +323,33 @@ class Forced:
         self.engine, self.B, self.classes = engine, B, classes
         g = torch.Generator().manual_seed(seed)
         s = engine.in_size
-        x = ops.image_prep(torch.rand((B, s, s, 3), generator=g).cuda())
+        self.x = ops.image_prep(torch.rand((B, s, s, 3), generator=g).cuda())
         self.dloc = (torch.randn((B, engine.A, 4), generator=g) * 1e-3).bfloat16()
         self.dconf = (torch.randn((B, engine.A, classes), generator=g) * 1e-3).bfloat16()
         for lvl, f in enumerate(level_scale or ()):                     # a power of two per level: still bf16 values
             lo, hi = engine.level_off[lvl], engine.level_off[lvl + 1]
             self.dloc[:, lo:hi] *= f
             self.dconf[:, lo:hi] *= f
+        self.run()
+
+    def run_forward(self, engine, x):
         engine.forward(x)
-        self.c = c = engine._acts(B)
+
+    def mx_operands(self):
+        return None
+
+    def run(self):
+        engine = self.engine
+        self.run_forward(engine, self.x)
+        self.c = c = engine._acts(self.B)
         poison(engine, c)
-        engine.backward(self.dloc.cuda(), self.dconf.cuda())
+        engine.backward(self.dloc.cuda(), self.dconf.cuda(), **self.backward_kwargs)
         torch.cuda.synchronize()
         self.maps = self.written_maps()
         self.got, self.flat = engine_grads(engine, c, self.maps)
         self.stored, self.codes, self.l2norm = self.stored_forward()
         self.weights = engine_weights(engine)
+        self.mx = self.mx_operands()
         t0 = time.time()
         self.T, self.R = self.oracle(), self.oracle(round_maps=True)
         self.bound = bounds(self.T, self.R)
@@ -274,6 +357,8 @@ class Forced:
 
     def oracle(self, **kw):
         e = self.engine
+        if self.mx is not None:
+            kw = dict(kw, mx=self.mx)
         return self.walk(e.nodes, e.fm, e.num_priors, self.classes, self.weights, self.stored, self.codes, self.dloc, self.dconf, **kw)
 
     def check_forward_state(self):
@@ -282,5 +367,5 @@ class Forced:
     def check(self, title):
         self.check_forward_state()
         check_outputs(self.engine, self.c, self.got, self.flat, self.maps)
-        bad, _ = compare(self.got, self.T, self.R, title)
+        bad, self.worst = compare(self.got, self.T, self.R, title)
         assert not bad, "beyond 3 * rel_l2(R, T) + 1e-3: " + ", ".join("%s %.3e > %.3e" % (n, e, b) for n, e, _, b in bad)

@@ -1,7 +1,11 @@
 """CPU: the teacher-forced oracle (tests/forced_oracle.py) tested on its own, on two tiny float64 networks with their own
 forward pass: with the masks and routes of that forward, the exact walk (T) IS torch.autograd's gradient of the same network
 (1e-10 relative L2 per tensor: float64 summation order, not a tolerance on any kernel); the storage model (R) moves every trunk
-tensor and leaves every level's head alone; every seeded defect moves a tensor it touches beyond twice that tensor's bound."""
+tensor and leaves every level's head alone; every seeded defect moves a tensor it touches beyond twice that tensor's bound.
+A third network, the graph with 128-channel maps ("graph_mx": the product's mxfp8_dgrad_eligible holds on it as it stands),
+does the same for the walk's mx= mode: handed its own exact maps and unquantised filters it is still autograd's gradient;
+handed quantised operands it moves every tensor below the first fp8 data gradient and nothing above; every graph defect and
+the two fp8 ones move a tensor beyond twice its bound."""
 import pytest
 
 torch = pytest.importorskip("torch")
@@ -33,26 +37,27 @@ def chain_nodes():
     return nodes, fm
 
 
-def graph_nodes():
+def graph_nodes(mid=8, wide=16):
     """stem 7x7/2 (33 -> 17), 3x3/2 pooling (-> 9), a bottleneck with a projection and stride 2 (-> 5, feature map 0, which also
-    feeds the next block twice), one with an identity shortcut (feature map 1), an extra stage (-> 3, feature map 2)"""
+    feeds the next block twice), one with an identity shortcut (feature map 1), an extra stage (-> 3, feature map 2); `mid`
+    channels inside the blocks, `wide` at their outputs"""
     g = []
 
     def conv(src, cin, cout, k, stride, relu=True, feature=False):
         g.append(dict(kind="conv", src=src, cin=cin, cout=cout, k=k, stride=stride, relu=relu, feature=feature))
         return len(g) - 1
 
-    x = conv(-1, 8, 8, 7, 2)
-    g.append(dict(kind="pool3", src=x, cin=8, cout=8, k=3, stride=2, relu=False, feature=False))
+    x = conv(-1, 8, mid, 7, 2)
+    g.append(dict(kind="pool3", src=x, cin=mid, cout=mid, k=3, stride=2, relu=False, feature=False))
     x = 1
-    a = conv(conv(conv(x, 8, 8, 1, 1), 8, 8, 3, 2), 8, 16, 1, 1, relu=False)
-    sc = conv(x, 8, 16, 1, 2, relu=False)
-    g.append(dict(kind="add", src=(a, sc), cin=16, cout=16, k=0, stride=1, relu=True, feature=True))
+    a = conv(conv(conv(x, mid, mid, 1, 1), mid, mid, 3, 2), mid, wide, 1, 1, relu=False)
+    sc = conv(x, mid, wide, 1, 2, relu=False)
+    g.append(dict(kind="add", src=(a, sc), cin=wide, cout=wide, k=0, stride=1, relu=True, feature=True))
     x = len(g) - 1
-    a = conv(conv(conv(x, 16, 8, 1, 1), 8, 8, 3, 1), 8, 16, 1, 1, relu=False)
-    g.append(dict(kind="add", src=(a, x), cin=16, cout=16, k=0, stride=1, relu=True, feature=True))
+    a = conv(conv(conv(x, wide, mid, 1, 1), mid, mid, 3, 1), mid, wide, 1, 1, relu=False)
+    g.append(dict(kind="add", src=(a, x), cin=wide, cout=wide, k=0, stride=1, relu=True, feature=True))
     x = len(g) - 1
-    conv(conv(x, 16, 8, 1, 1), 8, 16, 3, 2, feature=True)
+    conv(conv(x, wide, mid, 1, 1), mid, wide, 3, 2, feature=True)
     sizes, fm = {-1: 33}, []
     for i, nd in enumerate(g):
         hin = sizes[nd["src"][0] if nd["kind"] == "add" else nd["src"]]
@@ -110,7 +115,8 @@ class Net:
 
     def __init__(self, kind, l2norm=False, drop_fullres=False, seed=0):
         g = torch.Generator().manual_seed(seed)
-        (self.nodes, self.fm), self.priors = (chain_nodes(), CHAIN_PRIORS) if kind == "chain" else (graph_nodes(), (2, 2, 2))
+        graph = {"graph": graph_nodes, "graph_mx": lambda: graph_nodes(128, 128)}
+        (self.nodes, self.fm), self.priors = (chain_nodes(), CHAIN_PRIORS) if kind == "chain" else (graph[kind](), (2, 2, 2))
         size = CHAIN_SIZE if kind == "chain" else 33
         self.P = make_params(self.nodes, self.fm, self.priors, g)
         x = torch.randn((2, size, size, 8), generator=g, dtype=F64)
@@ -153,7 +159,7 @@ def net(*key):
     return NETS[key]
 
 
-@pytest.mark.parametrize("key", [("chain",), ("chain", True), ("chain", True, True), ("graph",)])
+@pytest.mark.parametrize("key", [("chain",), ("chain", True), ("chain", True, True), ("graph",), ("graph_mx",)])
 def test_exact_walk_is_autograd(key):
     n = net(*key)
     assert set(n.T) == set(n.auto)
@@ -162,7 +168,7 @@ def test_exact_walk_is_autograd(key):
         assert FO.rel_l2(n.T[name], want) <= 1e-10, (name, FO.rel_l2(n.T[name], want))
 
 
-@pytest.mark.parametrize("key", [("chain",), ("chain", True), ("graph",)])
+@pytest.mark.parametrize("key", [("chain",), ("chain", True), ("graph",), ("graph_mx",)])
 def test_storage_model_moves_the_trunk_only(key):
     n = net(*key)
     for name in n.T:
@@ -203,6 +209,70 @@ def test_seeded_defect_moves_the_exact_walk(kind, defect):
     assert hit, (defect, "moves no tensor to twice its bound")
     untouched = [k for k in n.T if FO.rel_l2(D[k], n.T[k]) == 0.0]
     assert untouched, defect                               # ONE wiring error: what lies behind it in the walk stays exact
+
+
+# ---- the mx= mode, on the graph with 128-channel maps ----------------------------------------------------------------------
+MX_NET = {}
+MX_DEFECTS = GRAPH_DEFECTS + [("mx_wrong_dy", 4), ("mx_wrong_dy", 9), ("mx_stale_dy", 6), ("mx_stale_dy", 10)]
+
+
+def mx_net():
+    """The network, the fp8 data gradients the product's rule gives it, the roots the walk derived, and T / R under mx with
+    operands quantised (strict.ref_quantize_mx) from the network's own R maps and filters"""
+    if not MX_NET:
+        from ssd_object_detection_amd.resnet_engine import mxfp8_dgrad_eligible, mxfp8_bwd_plan
+        n = net("graph_mx")
+        dgrad = {i for i, nd in enumerate(n.nodes) if mxfp8_dgrad_eligible(nd)}
+        trace = {}
+        again = n.run(trace=trace)
+        assert all(torch.equal(again[k], n.T[k]) for k in n.T)             # (trace changes nothing)
+        root = trace["root"]
+        plan = mxfp8_bwd_plan(n.nodes)
+        assert plan[0] == dgrad == {2, 4, 7, 8, 9, 11} and list(plan[1]) == root, (dgrad, root)
+        roots = sorted({root[i] for i in dgrad})
+        assert roots == sorted(plan[2]) == [2, 6, 7, 8, 10, 11]
+        # feature map 0 (node 6): written by its head, by the identity shortcut of add 10 and last by fp8 data gradient 7
+        assert n.nodes[6]["feature"] and n.nodes[10]["src"][1] == 6 and n.nodes[7]["src"] == 6 and plan[2][6] == ("fp8", 7)
+        mx = dict(dgrad=dgrad, dy={r: FO.mx_round(n.R["gact%d" % (r + 1)]) for r in roots},
+                  wt={i: FO.mx_filters(n.weights["conv%d/kernel" % i]) for i in dgrad})
+        T, R = n.run(mx=mx), n.run(mx=mx, round_maps=True)
+        MX_NET.update(n=n, dgrad=dgrad, roots=roots, mx=mx, T=T, R=R, bound=FO.bounds(T, R))
+    return MX_NET
+
+
+def test_mx_walk_on_exact_operands_is_autograd():
+    m = mx_net()
+    n = m["n"]
+    mx = dict(dgrad=m["dgrad"], dy={r: n.T["gact%d" % (r + 1)] for r in m["roots"]},
+              wt={i: n.weights["conv%d/kernel" % i] for i in m["dgrad"]})
+    T = n.run(mx=mx)
+    assert set(T) == set(n.auto)
+    for name, want in n.auto.items():
+        assert FO.rel_l2(T[name], want) <= 1e-10, (name, FO.rel_l2(T[name], want))
+
+
+def test_mx_operands_move_what_lies_below_them():
+    m = mx_net()
+    n, top = m["n"], max(m["dgrad"])                        # the first fp8 data gradient of the walk: the extra stage's 1x1,
+    for name in n.T:                                        # in the network's linear tail, so every earlier node lies below it
+        err = FO.rel_l2(m["T"][name], n.T[name])
+        idx = int(name.split("/")[0][4:])                   # "conv7/kernel" -> node 7, "gact7" -> activation 7 = node 6's output
+        if (name.startswith("conv") and idx < top) or (name.startswith("gact") and idx <= top):
+            assert 0.0 < err < 0.2, (name, err)            # e4m3 operands: 2^-4 per element at the worst
+        else:
+            assert err == 0.0, (name, err)
+    assert {k for k in n.T if k.startswith("head")} and FO.rel_l2(m["T"]["gact%d" % (top + 2)], n.T["gact%d" % (top + 2)]) == 0.0
+
+
+@pytest.mark.parametrize("defect", MX_DEFECTS, ids=str)
+def test_seeded_defect_moves_the_mx_walk(defect):
+    m = mx_net()
+    D = m["n"].run(mx=m["mx"], defect=defect)
+    hit = FO.moved(m["T"], D, m["bound"])
+    print(defect, sorted(hit, key=lambda r: -r[1] / r[2])[:4])
+    assert hit, (defect, "moves no tensor to twice its bound")
+    untouched = [k for k in m["T"] if FO.rel_l2(D[k], m["T"][k]) == 0.0]
+    assert untouched, defect
 
 
 def test_engine_tells_same_from_valid_pooling():
