@@ -18,9 +18,9 @@ static inline size_t ssd_align_up(size_t x, size_t a) { return (x + a - 1) / a *
 // Development overrides (ssd_dev_knob, include/ssd_hip.h); defined in knobs.hip.  Never set by the product.
 int ssd_knob(const char* name, int dflt);
 
-// Persistent pointwise-convolution GEMM (pwgemm.hip), called from conv.hip's dispatch.  geom / epilogue: the ConvGeom / Epilogue
-// of conv_common.h (both translation units include that header).
-bool ssd_pw_gemm_serves(int epi, const void* geom, const void* epilogue);
+// Persistent pointwise-convolution GEMM (pwgemm.hip), called from conv.hip's dispatch.  geom / epi_args / epilogue: the ConvGeom /
+// EpiArgs / Epilogue of conv_common.h (both translation units include that header).
+bool ssd_pw_gemm_serves(int epi, const void* geom, const void* epi_args);
 int ssd_pw_gemm_launch(int epi, const void* x, const void* w, const void* geom, const void* epilogue, void* stream);
 
 // fixed-order sum of weight-gradient slabs (k_wgrad_reduce2 / k_wgrad_reduce_wide, conv_wgrad.hip): dW = sum over ns splits

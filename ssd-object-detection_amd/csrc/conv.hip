@@ -6,8 +6,8 @@
 //
 // Kernels (DESIGN.md section 4 has the table): k_conv3x3_patch32 / k_conv3x3_p512 (3x3 with the halo patch in LDS),
 // k_conv3x3_c64b (64 -> 64; its W0 form also produces the first layer's weight gradient), k_conv0_fwd (image layer),
-// k_conv_igemm_8ph / k_conv_igemm_dma (implicit GEMM, split-K through k_igemm_finalize).  The dispatch (launch_igemm) and the C
-// entries are at the end of the file.  The weight gradient is conv_wgrad.hip; pooling, weight transposes, casts and the
+// k_conv_igemm_8ph / k_conv_igemm_dma (implicit GEMM, split-K through k_igemm_finalize).  The dispatch (igemm_plan decides, launch_igemm launches)
+// and the C entries are at the end of the file.  The weight gradient is conv_wgrad.hip; pooling, weight transposes, casts and the
 // head-gradient packing are conv_aux.hip; the development knobs are knobs.hip.
 #include <atomic>
 #include <cstdint>
@@ -1560,213 +1560,325 @@ __global__ __launch_bounds__(512) void k_conv0_fwd(const bf16_raw* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dispatch.  SSD_PLAN / SSD_PLAN_WGS (conv_common.h) record the kernel id or the workgroup count at the launch site.
-template <int EPI>
-bool staged_ok_host(const ConvGeom& g, const Epilogue& ep) {
-    if (ep.slab) return false;
-    if (EPI == EPI_HEAD) return true;
-    return (g.N & 7) == 0 && (ep.ldo & 7) == 0;
+// Dispatch.  igemm_plan decides -- kernel, tiling, grid, refusal -- from values alone; launch_igemm launches what the plan says
+// and the queries at the end of the file answer from the same plan.  A dispatch rule is changed in igemm_plan and nowhere else.
+struct IgemmPlan {
+    int id;                                  // SSD_PLAN_* kernel
+    int flags;                               // SSD_PLAN_F_*
+    unsigned grid;                           // workgroups launched (the implicit GEMMs: x, with y = ksplit); 0: k_pw_gemm sizes its own launch
+    int wgs;                                 // ACTIVE workgroups (the grid minus those that return at once); -1: not known (k_pw_gemm)
+    int lds;                                 // dynamic LDS bytes
+    // pixel-block kernels (conv0, c64b, patch32, p512)
+    int tiles_x, tiles_y;                    // blocks across a map (16 columns each) and down it (c64b: 8 rows, patch32 / conv0: 16, p512: 32)
+    int nblocks;                             // pixel blocks of the launch (patch32 / p512: per channel tile)
+    int rowflat;                             // patch32 / p512: one strip of rows over all images
+    int pitch;                               // patch32 / p512: image pitch of that strip in rows, for ConvGeom::d_h1
+    // implicit GEMMs (8-phase, LDS-DMA)
+    int bm, bn, ksplit;
+    unsigned ntm, ntn;
+    int word() const { return id | flags; }  // what the ssd_conv2d_*_plan queries answer
+};
+
+// k_conv3x3_c64b: 8 x 16 pixel blocks walked by at most max_wgs persistent workgroups; returns the grid
+unsigned c64b_tiling(int B, int H, int W, int max_wgs, int* tiles_x, int* tiles_y) {
+    *tiles_x = (W + 15) / 16; *tiles_y = (H + C64B_ROWS - 1) / C64B_ROWS;
+    const int nblocks = B * *tiles_x * *tiles_y;
+    return (unsigned)(nblocks < max_wgs ? nblocks : max_wgs);
 }
 
-template <int EPI>
-int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue& ep_in, hipStream_t s, void* ws = nullptr,
-                 size_t ws_bytes = 0, bool* pooled = nullptr, int* plan = nullptr) {
-    const bf16_raw* xp = static_cast<const bf16_raw*>(x);
-    const bf16_raw* wp = static_cast<const bf16_raw*>(w);
-    Epilogue ep = ep_in;
-    ep.slab = nullptr;
-    ep.ksplit = 1;
-    if constexpr (EPI != EPI_HEAD) {
-        if (ssd_knob("SSD_CONV_C64", 1) && g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 &&
-            g.pad_l == 1 && g.C == 64 && g.N == 64 && g.ldw == 576 && g.H == g.Ho && g.W == g.Wo && g.H >= 16 && g.W >= 16 &&
-            !ep.accumulate && !ep.up_out && (ep.ldo & 7) == 0 && (long long)g.B * g.H * g.W * 64 < (1ll << 31) - 16) {
-            if (EPI == EPI_FWD && !ep.out && !(pooled && ep.pool_out)) return SSD_ERR_VALUE;
-            // 8 x 16 blocks, two workgroups per CU
-            const int tiles_x = (g.Wo + 15) / 16, tiles_y = (g.Ho + C64B_ROWS - 1) / C64B_ROWS;
-            const int nblocks = g.B * tiles_x * tiles_y;
-            auto kern = k_conv3x3_c64b<EPI, false>;
-            const int maxwg = ssd_knob("SSD_C64B_WGS", 512);
-            SSD_PLAN_WGS(SSD_PLAN_C64B | ((pooled && ep.pool_out) ? SSD_PLAN_F_POOL_FUSED : 0), nblocks < maxwg ? nblocks : maxwg);
-            static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(C64B_LDS)) != 0) return SSD_ERR_LAUNCH;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < maxwg ? nblocks : maxwg)), dim3(256), C64B_LDS, s, xp, wp, g, ep, tiles_x, tiles_y, C64W0{});
-            if (pooled && ep.pool_out) *pooled = true;
-            return ssd_launch_status();
-        }
+bool staged_ok_host(int epi, const ConvGeom& g, const EpiArgs& ep) {   // staged_ok (conv_common.h) of a launch without split-K
+    return epi == EPI_HEAD || ((g.N & 7) == 0 && (ep.ldo & 7) == 0);
+}
+
+// SSD_OK and *p, or the status the call is refused with (nothing launched).  Reads no pointer.
+//   epi, g, ep           EPI_* kind, geometry and epilogue facts of the call, after the entry's own argument checks (rule 1)
+//   takes_pool           the caller can use a pooling epilogue (ssd_conv2d_fwd_pool)
+//   plain_fwd            the call came in through ssd_conv2d_fwd / ssd_conv2d_fwd_relubits
+//   has_ws, ws_bytes     the caller's workspace (split-K)
+// The rules below are in the order that decides which of them wins and which status a refused call gets.
+int igemm_plan(int epi, const ConvGeom& g, const EpiArgs& ep, bool takes_pool, bool plain_fwd, bool has_ws, size_t ws_bytes,
+               IgemmPlan* p) {
+    *p = IgemmPlan{};
+    p->ksplit = 1;
+    p->pitch = g.H + 1;
+    const bool same3x3 = g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 && g.pad_l == 1 && g.H == g.Ho &&
+                         g.W == g.Wo && g.H >= 16 && g.W >= 16;
+    p->tiles_x = (g.Wo + 15) / 16; p->tiles_y = (g.Ho + 15) / 16;
+
+    // ---- 2. the image layer: k_conv0_fwd, through the plain forward entry only ----
+    if (plain_fwd && ssd_knob("SSD_CONV_FIRST", 1) && same3x3 && g.C == 8 && g.N == 64) {
+        p->id = SSD_PLAN_CONV0_FWD;
+        p->nblocks = g.B * p->tiles_x * p->tiles_y;
+        p->wgs = p->nblocks < 768 ? p->nblocks : 768;
+        p->grid = (unsigned)p->wgs;
+        return SSD_OK;
     }
-    // LDS-patch kernel: 3x3 / stride 1 / pad 1 with N <= SSD_CONV_PATCH (default 256); beyond 128 channels only when
-    // the 16x16 blocks waste little of the map (75x75 and larger: <= 14 %; 38x38 would waste 37 %)
+
+    // ---- 3. 64 -> 64: k_conv3x3_c64b, two workgroups per CU (not for the heads) ----
+    if (epi != EPI_HEAD && ssd_knob("SSD_CONV_C64", 1) && same3x3 && g.C == 64 && g.N == 64 && g.ldw == 576 && !ep.accumulate &&
+        !ep.up_out && (ep.ldo & 7) == 0 && (long long)g.B * g.H * g.W * 64 < (1ll << 31) - 16) {
+        const bool pool = takes_pool && ep.pool_out;
+        if (epi == EPI_FWD && !ep.out && !pool) return SSD_ERR_VALUE;
+        p->id = SSD_PLAN_C64B;
+        p->flags = pool ? SSD_PLAN_F_POOL_FUSED : 0;
+        p->grid = c64b_tiling(g.B, g.Ho, g.Wo, ssd_knob("SSD_C64B_WGS", 512), &p->tiles_x, &p->tiles_y);
+        p->nblocks = g.B * p->tiles_x * p->tiles_y;
+        p->wgs = (int)p->grid;
+        p->lds = C64B_LDS;
+        return SSD_OK;
+    }
+
+    // ---- 4. LDS-patch family: 3x3 / stride 1 / pad 1 with N <= SSD_CONV_PATCH (default 256); beyond 128 channels only when
+    // the 16x16 blocks waste little of the map (75x75 and larger: <= 14 %; 38x38 would waste 37 %) ----
     const int use_patch = ssd_knob("SSD_CONV_PATCH", 256);
-    const bool patch_fits = g.N <= 128 || (long long)((g.Wo + 15) / 16) * ((g.Ho + 15) / 16) * 256 * 4 <= (long long)g.Wo * g.Ho * 5;
+    const bool patch_fits = g.N <= 128 || (long long)p->tiles_x * p->tiles_y * 256 * 4 <= (long long)g.Wo * g.Ho * 5;
     // narrow maps: strip blocks, any channel count.  The patch of 256 + 2 (W + 2) positions has to fit the 341 pixel rows of
     // a 32 KB buffer; the bound on W dates from the strip's first form (row pitch W + 2, 256 + 2 (W + 3) positions) and stays:
     // which layers take the strip form is part of the tested dispatch
     const int flat_knob = ssd_knob("SSD_CONV_PATCH_FLAT", 1);
-    const bool use_flat = flat_knob && g.W <= 39 && g.W >= 16 && g.H >= 16 && (flat_knob >= 2 || !patch_fits || g.N > use_patch);
-    if (g.KH == 3 && g.KW == 3 && g.mul == 1 && g.div == 1 && g.pad_t == 1 && g.pad_l == 1 &&
-        g.C % 64 == 0 && g.H == g.Ho && g.W == g.Wo && ((g.N <= use_patch && patch_fits) || use_flat) && g.H >= 16 && g.W >= 16 &&
+    const bool flat = flat_knob && g.W <= 39 && g.W >= 16 && g.H >= 16 && (flat_knob >= 2 || !patch_fits || g.N > use_patch);
+    if (same3x3 && g.C % 64 == 0 && ((g.N <= use_patch && patch_fits) || flat) &&
         (long long)g.B * g.H * g.W * g.C < (1ll << 31) - 16 && (long long)g.N * g.ldw < (1ll << 31) - 16) {   // 31-bit buffer offsets
-        const int tiles_x = (g.Wo + 15) / 16, tiles_y = (g.Ho + 15) / 16;
-        const unsigned gx = (unsigned)(tiles_x * tiles_y * g.B);
-        {
-            const bool flat = use_flat;
-            ConvGeom gk = g;                                     // what the kernel gets: g with the row strip's image pitch
-            // wide maps: one strip of rows over all images (k_conv3x3_patch32, "rowflat") when that needs fewer blocks.
-            // Image pitch in strip rows: H + 1 (one shared zero row); under fused pooling the next even number, so that a
-            // 2x2 window never straddles two images -- nor two blocks, which start at multiples of 16 / 32 strip rows
-            const int pitch = (EPI == EPI_FWD && ep.pool_out && (g.H & 1) == 0) ? g.H + 2 : g.H + 1;
-            gk.d_h1 = make_fastdiv(pitch);
-            const unsigned strip_rows = (unsigned)(((long long)g.B * pitch + 15) / 16);
-            const int rowflat = (!flat && ssd_knob("SSD_CONV_PATCH_ROWFLAT", 1) && strip_rows < (unsigned)(tiles_y * g.B)) ? 1 : 0;
-            const unsigned gxx = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + 255) / 256)
-                                      : (rowflat ? strip_rows * (unsigned)tiles_x : gx);
-#define SSD_LAUNCH_P32(BN_, FLAT_)                                                                                  \
-            do {                                                                                                    \
-                constexpr int lds_ = 2 * P32_PATCH + 2 * (BN_ == 64 ? 128 : BN_) * 64;   /* BN = 64 stages two taps per step */ \
-                auto kern_ = k_conv3x3_patch32<BN_, EPI, FLAT_>;                                                    \
-                const unsigned ntn_ = (unsigned)((g.N + BN_ - 1) / BN_);                                            \
-                SSD_PLAN_WGS((BN_ == 64 ? SSD_PLAN_P32_64 : SSD_PLAN_P32_128) | (FLAT_ ? SSD_PLAN_F_FLAT : 0) |        \
-                             (rowflat ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0), gxx * ntn_);  \
-                static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)(lds_)) != 0) return SSD_ERR_LAUNCH; \
-                hipLaunchKernelGGL(kern_, dim3(8 * ntn_ * ((gxx + 7) / 8)), dim3(512), lds_, s, xp, wp, gk, ep, tiles_x, tiles_y, (int)gxx, rowflat); \
-            } while (0)
-            const bool can_pool = pooled && ep.pool_out && !flat && (g.N & 7) == 0 && (ep.ldo & 7) == 0 && !(g.ablate & 8);
-            if (EPI == EPI_FWD && !ep.out && !can_pool) return SSD_ERR_VALUE;
-            if ((ep.up_out || ep.relu_bits || ep.mask_bits) && (!staged_ok_host<EPI>(g, ep) || (g.ablate & 8)))
-                return SSD_ERR_UNSUPPORTED;                      // un-pooling and the sign bits live in the staged store
-            // 512 px x 128 channels, one workgroup per CU: from 256 input channels on (eight 32-channel chunks amortise its longer
-            // prologue / epilogue; measured per layer in DESIGN.md section 9).  SSD_CONV_P512: 0 never, 1 (default) that rule, 2 always
-            const int p512 = ssd_knob("SSD_CONV_P512", 1);
-            // (the heads never take it.  Head 0, 38x38 x 512 channels: its element-wise scatter epilogue has nothing to hide
-            //  behind with one workgroup per CU, 385 vs 334 us.  Head 1, 19x19 x 1024 channels, is 208 vs 222 us ALONE -- but it
-            //  runs beside the extras' chain of small launches, and a 512-pixel workgroup holds 152 of the CU's 160 KB of LDS:
-            //  not one of those launches (64 KB each) found a CU until it had drained, 190 us for a 15-GFLOP layer and the
-            //  loss 130 us later.  With the 78 KB workgroups of the patch kernel the two overlap: -0.07 ms per step.)
-            if (p512 && g.C % 64 == 0 && g.N > 64 && (p512 >= 2 || (EPI != EPI_HEAD && g.C >= 256))) {
-                const int ty32 = (g.Ho + 31) / 32;
-                const unsigned strips32 = (unsigned)(((long long)g.B * pitch + 31) / 32);
-                const int rf = (!flat && ssd_knob("SSD_CONV_PATCH_ROWFLAT", 1) && strips32 < (unsigned)(ty32 * g.B)) ? 1 : 0;
-                const unsigned nb = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + 511) / 512)
-                                         : (rf ? strips32 * (unsigned)tiles_x : (unsigned)(tiles_x * ty32 * g.B));
-                const unsigned ntn5 = (unsigned)((g.N + 127) / 128);
-                SSD_PLAN_WGS(SSD_PLAN_P512 | (flat ? SSD_PLAN_F_FLAT : 0) | (rf ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0),
-                             nb * ntn5);
-                if (flat) {
-                    auto kern5 = k_conv3x3_p512<EPI, true>;
-                    static OnceLds set5; if (ensure_lds(set5, reinterpret_cast<const void*>(kern5), P5_LDS) != 0) return SSD_ERR_LAUNCH;
-                    hipLaunchKernelGGL(kern5, dim3(8 * ntn5 * ((nb + 7) / 8)), dim3(512), P5_LDS, s, xp, wp, gk, ep, tiles_x, ty32, (int)nb, rf);
-                } else {
-                    auto kern5 = k_conv3x3_p512<EPI, false>;
-                    static OnceLds set5; if (ensure_lds(set5, reinterpret_cast<const void*>(kern5), P5_LDS) != 0) return SSD_ERR_LAUNCH;
-                    hipLaunchKernelGGL(kern5, dim3(8 * ntn5 * ((nb + 7) / 8)), dim3(512), P5_LDS, s, xp, wp, gk, ep, tiles_x, ty32, (int)nb, rf);
-                }
-                if (can_pool) *pooled = true;
-                return ssd_launch_status();
-            }
-            if (g.N <= 64) { if (flat) SSD_LAUNCH_P32(64, true); else SSD_LAUNCH_P32(64, false); }
-            else { if (flat) SSD_LAUNCH_P32(128, true); else SSD_LAUNCH_P32(128, false); }
-#undef SSD_LAUNCH_P32
-            if (can_pool) *pooled = true;
-            return ssd_launch_status();
-        }
+        const bool can_pool = takes_pool && ep.pool_out && !flat && (g.N & 7) == 0 && (ep.ldo & 7) == 0 && !(g.ablate & 8);
+        if (epi == EPI_FWD && !ep.out && !can_pool) return SSD_ERR_VALUE;
+        if ((ep.up_out || ep.relu_bits || ep.mask_bits) && (!staged_ok_host(epi, g, ep) || (g.ablate & 8)))
+            return SSD_ERR_UNSUPPORTED;                          // un-pooling and the sign bits live in the staged store
+        // k_conv3x3_p512, 512 px x 128 channels, one workgroup per CU: from 256 input channels on (eight 32-channel chunks amortise
+        // its longer prologue / epilogue; measured per layer in DESIGN.md section 9).  SSD_CONV_P512: 0 never, 1 (default) that rule,
+        // 2 always
+        // (the heads never take it.  Head 0, 38x38 x 512 channels: its element-wise scatter epilogue has nothing to hide
+        //  behind with one workgroup per CU, 385 vs 334 us.  Head 1, 19x19 x 1024 channels, is 208 vs 222 us ALONE -- but it
+        //  runs beside the extras' chain of small launches, and a 512-pixel workgroup holds 152 of the CU's 160 KB of LDS:
+        //  not one of those launches (64 KB each) found a CU until it had drained, 190 us for a 15-GFLOP layer and the
+        //  loss 130 us later.  With the 78 KB workgroups of the patch kernel the two overlap: -0.07 ms per step.)
+        const int p512_knob = ssd_knob("SSD_CONV_P512", 1);
+        const bool p512 = p512_knob && g.N > 64 && (p512_knob >= 2 || (epi != EPI_HEAD && g.C >= 256));
+        const int rows = p512 ? 32 : 16;                         // block = rows x 16 pixels, or rows * 16 strip positions
+        p->bn = p512 || g.N > 64 ? 128 : 64;
+        p->id = p512 ? SSD_PLAN_P512 : (p->bn == 64 ? SSD_PLAN_P32_64 : SSD_PLAN_P32_128);
+        p->lds = p512 ? P5_LDS : 2 * P32_PATCH + 2 * 128 * 64;   // patch32: BN = 64 stages two taps per step
+        p->tiles_y = (g.Ho + rows - 1) / rows;
+        // wide maps: one strip of rows over all images ("rowflat") when that needs fewer blocks.  Image pitch in strip rows:
+        // H + 1 (one shared zero row); under fused pooling the next even number, so that a 2x2 window never straddles two
+        // images -- nor two blocks, which start at multiples of 16 / 32 strip rows
+        p->pitch = (epi == EPI_FWD && ep.pool_out && (g.H & 1) == 0) ? g.H + 2 : g.H + 1;
+        const unsigned strips = (unsigned)(((long long)g.B * p->pitch + rows - 1) / rows);
+        p->rowflat = (!flat && ssd_knob("SSD_CONV_PATCH_ROWFLAT", 1) && strips < (unsigned)(p->tiles_y * g.B)) ? 1 : 0;
+        const unsigned nb = flat ? (unsigned)(((long long)g.B * (g.H + 1) * (g.W + 1) + rows * 16 - 1) / (rows * 16))
+                                 : (p->rowflat ? strips * (unsigned)p->tiles_x : (unsigned)(p->tiles_x * p->tiles_y * g.B));
+        p->nblocks = (int)nb;
+        p->ntn = (unsigned)((g.N + p->bn - 1) / p->bn);
+        p->flags = (flat ? SSD_PLAN_F_FLAT : 0) | (p->rowflat ? SSD_PLAN_F_ROWFLAT : 0) | (can_pool ? SSD_PLAN_F_POOL_FUSED : 0);
+        p->wgs = (int)(nb * p->ntn);
+        p->grid = 8 * p->ntn * ((nb + 7) / 8);
+        return SSD_OK;
     }
-    if (EPI == EPI_FWD && !ep.out) return SSD_ERR_VALUE;         // pool-only needs a pooling kernel
-    if (ep.up_out) return SSD_ERR_UNSUPPORTED;                   // only the LDS-patch kernels un-pool in their epilogue
-    if constexpr (EPI != EPI_HEAD) {
-        // 1x1 / stride 1 on a large map: the persistent GEMM (pwgemm.hip) -- the DMA stream runs on across tile boundaries
-        // (SSD_CONV_PW: bit 0 forward, bit 1 data gradient)
-        if ((ssd_knob("SSD_CONV_PW", 3) & (EPI == EPI_FWD ? 1 : 2)) && !(g.ablate & 8) && ssd_pw_gemm_serves(EPI, &g, &ep)) {
-            SSD_PLAN(SSD_PLAN_PW);
-            return ssd_pw_gemm_launch(EPI, x, w, &g, &ep, s);
-        }
+
+    // ---- 5. outside the patch family nothing pools or un-pools in its epilogue ----
+    if (epi == EPI_FWD && !ep.out) return SSD_ERR_VALUE;         // pool-only needs a pooling kernel
+    if (ep.up_out) return SSD_ERR_UNSUPPORTED;
+
+    // ---- 6. 1x1 / stride 1 on a large map: the persistent GEMM (pwgemm.hip) -- the DMA stream runs on across tile boundaries
+    // (SSD_CONV_PW: bit 0 forward, bit 1 data gradient) ----
+    if (epi != EPI_HEAD && (ssd_knob("SSD_CONV_PW", 3) & (epi == EPI_FWD ? 1 : 2)) && !(g.ablate & 8) && ssd_pw_gemm_serves(epi, &g, &ep)) {
+        p->id = SSD_PLAN_PW;
+        p->wgs = -1;
+        return SSD_OK;
     }
+
+    // ---- 7. implicit GEMM.  Tile choice: the CU ingests ~28 B/clk from L2, so MACs per staged byte decide the ceiling: prefer the
+    // largest tile that still gives every CU work (>= ~2 workgroups per CU), SSD_CONV_TILE overrides (testing) ----
+    const int force = ssd_knob("SSD_CONV_TILE", 0);
+    const long long wg_256 = (long long)((g.M + 255) / 256);
+    int bm = 128, bn = g.N <= 64 ? 64 : 128;
+    const long long pad256 = (long long)((g.N + 255) / 256) * 256, pad128 = (long long)((g.N + 127) / 128) * 128;
+    // (>= 352 rather than 384 workgroups: at 364 -- the 19x19 maps with 1024 channels -- the 8-phase kernel's deeper
+    //  pipeline beats the 256x128 kernel's better fill by 12 %.  A third / fourth LDS stage in k_conv_igemm_dma itself was
+    //  tried for the skinny layers and was neutral to 60 % slower: not the DMA latency bounds them)
+    if (g.N > 128 && wg_256 * ((g.N + 255) / 256) >= 352 && pad256 * 4 <= pad128 * 5) { bm = 256; bn = 256; }
+    else if (g.N > 64 && wg_256 * ((g.N + 127) / 128) >= 384) { bm = 256; bn = 128; }
+    else if (g.N <= 64 && wg_256 >= 384) { bm = 256; bn = 64; }
+    if (force == 1) { bm = 128; bn = g.N <= 64 ? 64 : 128; }
+    if ((force == 2 || force == 4) && g.N > 128) { bm = 256; bn = 256; }   // (4: the LDS-DMA kernel instead of the 8-phase one)
+    if (force == 3 && g.N > 64) { bm = 256; bn = 128; }
+    // split-K for skinny problems (few tiles, long k loop): partial sums to the caller's workspace
     {
-        // tile choice: the CU ingests ~28 B/clk from L2, so MACs per staged byte decide the ceiling: prefer the
-        // largest tile that still gives every CU work (>= ~2 workgroups per CU), SSD_CONV_TILE overrides (testing)
-        const int force = ssd_knob("SSD_CONV_TILE", 0);
-        const long long wg_256 = (long long)((g.M + 255) / 256);
-        int bm = 128, bn = g.N <= 64 ? 64 : 128;
-        const long long pad256 = (long long)((g.N + 255) / 256) * 256, pad128 = (long long)((g.N + 127) / 128) * 128;
-        // (>= 352 rather than 384 workgroups: at 364 -- the 19x19 maps with 1024 channels -- the 8-phase kernel's deeper
-        //  pipeline beats the 256x128 kernel's better fill by 12 %.  A third / fourth LDS stage in k_conv_igemm_dma itself was
-        //  tried for the skinny layers and was neutral to 60 % slower: not the DMA latency bounds them)
-        if (g.N > 128 && wg_256 * ((g.N + 255) / 256) >= 352 && pad256 * 4 <= pad128 * 5) { bm = 256; bn = 256; }
-        else if (g.N > 64 && wg_256 * ((g.N + 127) / 128) >= 384) { bm = 256; bn = 128; }
-        else if (g.N <= 64 && wg_256 >= 384) { bm = 256; bn = 64; }
-        if (force == 1) { bm = 128; bn = g.N <= 64 ? 64 : 128; }
-        if ((force == 2 || force == 4) && g.N > 128) { bm = 256; bn = 256; }   // (4: the LDS-DMA kernel instead of the 8-phase one)
-        if (force == 3 && g.N > 64) { bm = 256; bn = 128; }
-        // split-K for skinny problems (few tiles, long k loop): partial sums to the caller's workspace
-        unsigned ksplit = 1;
-        {
-            const int sk_on = ssd_knob("SSD_SPLITK", 1);
-            const long long tiles = (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
-            const int nks_all = g.s2 ? 0 : (g.nchunks + 7) / 8;
-            if (sk_on && ws && tiles < 160 && nks_all >= 8) {
-                long long want = (256 + tiles - 1) / tiles;
-                if (want > nks_all / 2) want = nks_all / 2;
-                if (want > 32) want = 32;
-                while (want > 1 && (size_t)want * g.M * g.N * sizeof(float) > ws_bytes) --want;
-                if (want > 1) { ksplit = (unsigned)want; ep.slab = static_cast<float*>(ws); ep.ksplit = (int)want; }
-            }
+        const long long tiles = (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
+        const int nks_all = g.s2 ? 0 : (g.nchunks + 7) / 8;
+        if (ssd_knob("SSD_SPLITK", 1) && has_ws && tiles < 160 && nks_all >= 8) {
+            long long want = (256 + tiles - 1) / tiles;
+            if (want > nks_all / 2) want = nks_all / 2;
+            if (want > 32) want = 32;
+            while (want > 1 && (size_t)want * g.M * g.N * sizeof(float) > ws_bytes) --want;
+            if (want > 1) p->ksplit = (int)want;
         }
-        // the sign bits are written / read by the staged store only (not by the split-K finalize or the scattered epilogue)
-        if ((ep.relu_bits || ep.mask_bits) && (ksplit > 1 || !staged_ok_host<EPI>(g, ep) || (g.ablate & 8))) return SSD_ERR_UNSUPPORTED;
-#define SSD_LAUNCH_DMA(BM_, BN_)                                                                                   \
-        do {                                                                                                       \
-            constexpr int PT_ = (BM_ == 256 && BN_ == 256) ? SSD_PT256 : 4;                                         \
-            constexpr int NT_ = (BM_ / (16 * PT_)) * (BN_ >= 128 ? BN_ / 64 : 2) * 64;                              \
-            const size_t lds_ = 2 * (BM_ + BN_) * 128;                                                             \
-            auto kern_ = k_conv_igemm_dma<BM_, BN_, EPI, PT_>;                                                     \
-            unsigned ntm_ = (unsigned)((g.M + BM_ - 1) / BM_);                                                      \
-            const unsigned ntn_ = (unsigned)((g.N + BN_ - 1) / BN_);                                               \
-            if (g.s2) { ntm_ = 0; for (int c_ = 0; c_ < 4; ++c_) ntm_ += (unsigned)((g.cls_n[c_] + BM_ - 1) / BM_); } \
-            SSD_PLAN_WGS((BM_ == 256 ? (BN_ == 256 ? SSD_PLAN_DMA_256_256 : (BN_ == 128 ? SSD_PLAN_DMA_256_128 : SSD_PLAN_DMA_256_64)) \
-                                     : (BN_ == 64 ? SSD_PLAN_DMA_128_64 : SSD_PLAN_DMA_128_128)) |                   \
-                         (ksplit > 1 ? SSD_PLAN_F_SPLITK : 0) | (g.s2 ? SSD_PLAN_F_S2 : 0), ntm_ * ntn_ * ksplit);    \
-            if (lds_ > 65536) {                                                                                    \
-                static OnceLds set_; if (ensure_lds(set_, reinterpret_cast<const void*>(kern_), (int)((int)lds_)) != 0) return SSD_ERR_LAUNCH; \
-            }                                                                                                      \
-            hipLaunchKernelGGL(kern_, dim3(8 * ntn_ * ((ntm_ + 7) / 8), ksplit), dim3(NT_), lds_, s, xp, wp, g, ep); \
-        } while (0)
-        if (bm == 256 && bn == 256 && force != 4 && !g.s2 && ksplit == 1 && g.cpt >= 8 &&
-            (long long)g.B * g.H * g.W * g.C < (1ll << 31) - 16 && (long long)g.N * g.ldw < (1ll << 31) - 16) {
-            const unsigned ntm = (unsigned)((g.M + 255) / 256), ntn = (unsigned)((g.N + 255) / 256);
-#define SSD_LAUNCH_8PH(ABL_)                                                                                        \
-            do {                                                                                                    \
-                auto kern = k_conv_igemm_8ph<EPI, ABL_>;                                                            \
-                SSD_PLAN_WGS(SSD_PLAN_8PH, ntm * ntn);                                                              \
-                static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(131072)) != 0) return SSD_ERR_LAUNCH; \
-                hipLaunchKernelGGL(kern, dim3(8 * ntn * ((ntm + 7) / 8)), dim3(512), 131072, s, xp, wp, g, ep);      \
-            } while (0)
+    }
+    // the sign bits are written / read by the staged store only (not by the split-K finalize or the scattered epilogue)
+    if ((ep.relu_bits || ep.mask_bits) && (p->ksplit > 1 || !staged_ok_host(epi, g, ep) || (g.ablate & 8))) return SSD_ERR_UNSUPPORTED;
+    p->bm = bm; p->bn = bn;
+    p->ntm = (unsigned)((g.M + bm - 1) / bm);
+    p->ntn = (unsigned)((g.N + bn - 1) / bn);
+    if (bm == 256 && bn == 256 && force != 4 && !g.s2 && p->ksplit == 1 && g.cpt >= 8 &&
+        (long long)g.B * g.H * g.W * g.C < (1ll << 31) - 16 && (long long)g.N * g.ldw < (1ll << 31) - 16) {
+        p->id = SSD_PLAN_8PH;
+        p->lds = 131072;
+    } else {
+        p->id = bm == 256 ? (bn == 256 ? SSD_PLAN_DMA_256_256 : (bn == 128 ? SSD_PLAN_DMA_256_128 : SSD_PLAN_DMA_256_64))
+                          : (bn == 64 ? SSD_PLAN_DMA_128_64 : SSD_PLAN_DMA_128_128);
+        p->flags = (p->ksplit > 1 ? SSD_PLAN_F_SPLITK : 0) | (g.s2 ? SSD_PLAN_F_S2 : 0);
+        p->lds = 2 * (bm + bn) * 128;
+        if (g.s2) { p->ntm = 0; for (int c = 0; c < 4; ++c) p->ntm += (unsigned)((g.cls_n[c] + bm - 1) / bm); }   // whole tiles per parity class
+    }
+    p->wgs = (int)(p->ntm * p->ntn * (unsigned)p->ksplit);
+    p->grid = 8 * p->ntn * ((p->ntm + 7) / 8);
+    return SSD_OK;
+}
+
+// ---- one launch helper per kernel family; launch_igemm's switch picks the template arguments.  SSD_ERR_LAUNCH when the
+// kernel's LDS size cannot be registered, else SSD_OK (the launch itself is checked by the caller) ----
+template <int EPI, bool W0>
+int launch_c64b(unsigned grid, int lds, const bf16_raw* x, const bf16_raw* w, const ConvGeom& g, const Epilogue& ep, int tiles_x,
+                int tiles_y, const C64W0& w0, hipStream_t s) {
+    auto kern = k_conv3x3_c64b<EPI, W0>;
+    static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), lds) != 0) return SSD_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, x, w, g, ep, tiles_x, tiles_y, w0);
+    return SSD_OK;
+}
+
+template <auto KERN>                         // k_conv3x3_patch32<BN, EPI, FLAT> or k_conv3x3_p512<EPI, FLAT>
+int launch_patch(const IgemmPlan& p, const bf16_raw* x, const bf16_raw* w, const ConvGeom& g, const Epilogue& ep, hipStream_t s) {
+    ConvGeom gk = g;                         // what the kernel gets: g with the row strip's image pitch
+    gk.d_h1 = make_fastdiv(p.pitch);
+    auto kern = KERN;
+    static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), p.lds) != 0) return SSD_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.lds, s, x, w, gk, ep, p.tiles_x, p.tiles_y, p.nblocks, p.rowflat);
+    return SSD_OK;
+}
+
+template <int BM, int BN, int EPI>
+int launch_dma(const IgemmPlan& p, const bf16_raw* x, const bf16_raw* w, const ConvGeom& g, const Epilogue& ep, hipStream_t s) {
+    constexpr int PT = (BM == 256 && BN == 256) ? SSD_PT256 : 4;
+    constexpr int NT = (BM / (16 * PT)) * (BN >= 128 ? BN / 64 : 2) * 64;
+    auto kern = k_conv_igemm_dma<BM, BN, EPI, PT>;
+    if (p.lds > 65536) {
+        static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), p.lds) != 0) return SSD_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(kern, dim3(p.grid, (unsigned)p.ksplit), dim3(NT), p.lds, s, x, w, g, ep);
+    return SSD_OK;
+}
+
+template <int EPI, int ABL>
+int launch_8ph(const IgemmPlan& p, const bf16_raw* x, const bf16_raw* w, const ConvGeom& g, const Epilogue& ep, hipStream_t s) {
+    auto kern = k_conv_igemm_8ph<EPI, ABL>;
+    static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), p.lds) != 0) return SSD_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.lds, s, x, w, g, ep);
+    return SSD_OK;
+}
+
+// Plan the call, launch the plan.  *pooled (ssd_conv2d_fwd_pool): the launch pooled in its epilogue.
+template <int EPI>
+int launch_igemm(const void* x, const void* w, const ConvGeom& g, const Epilogue& ep_in, hipStream_t s, void* ws, size_t ws_bytes,
+                 bool* pooled = nullptr, bool plain_fwd = false) {
+    IgemmPlan p;
+    int rc = igemm_plan(EPI, g, epi_args(ep_in), pooled != nullptr, plain_fwd, ws != nullptr, ws_bytes, &p);
+    if (rc != SSD_OK) return rc;
+    const bf16_raw* xp = static_cast<const bf16_raw*>(x);
+    const bf16_raw* wp = static_cast<const bf16_raw*>(w);
+    Epilogue ep = ep_in;
+    ep.slab = p.ksplit > 1 ? static_cast<float*>(ws) : nullptr;
+    ep.ksplit = p.ksplit;
+    const bool flat = p.flags & SSD_PLAN_F_FLAT;
+    switch (p.id) {
+        case SSD_PLAN_CONV0_FWD:
+            if constexpr (EPI == EPI_FWD)
+                hipLaunchKernelGGL(k_conv0_fwd, dim3(p.grid), dim3(512), 0, s, xp, wp, ep.bias, ep.out, g, ep.relu, p.tiles_x, p.tiles_y,
+                                   ep.relu_bits);
+            break;
+        case SSD_PLAN_C64B:
+            if constexpr (EPI != EPI_HEAD) rc = launch_c64b<EPI, false>(p.grid, p.lds, xp, wp, g, ep, p.tiles_x, p.tiles_y, C64W0{}, s);
+            break;
+        case SSD_PLAN_P32_64:
+            rc = flat ? launch_patch<k_conv3x3_patch32<64, EPI, true>>(p, xp, wp, g, ep, s)
+                      : launch_patch<k_conv3x3_patch32<64, EPI, false>>(p, xp, wp, g, ep, s);
+            break;
+        case SSD_PLAN_P32_128:
+            rc = flat ? launch_patch<k_conv3x3_patch32<128, EPI, true>>(p, xp, wp, g, ep, s)
+                      : launch_patch<k_conv3x3_patch32<128, EPI, false>>(p, xp, wp, g, ep, s);
+            break;
+        case SSD_PLAN_P512:
+            rc = flat ? launch_patch<k_conv3x3_p512<EPI, true>>(p, xp, wp, g, ep, s)
+                      : launch_patch<k_conv3x3_p512<EPI, false>>(p, xp, wp, g, ep, s);
+            break;
+        case SSD_PLAN_PW: return ssd_pw_gemm_launch(EPI, x, w, &g, &ep, s);
+        case SSD_PLAN_8PH:
 #ifdef SSD_DEV_ABLATE
             if constexpr (EPI == EPI_FWD) {
                 switch (g.ablate) {
-                    case 1: SSD_LAUNCH_8PH(1); break;
-                    case 4: SSD_LAUNCH_8PH(4); break;
-                    case 5: SSD_LAUNCH_8PH(5); break;
-                    case 20: SSD_LAUNCH_8PH(20); break;
-                    case 21: SSD_LAUNCH_8PH(21); break;
-                    case 23: SSD_LAUNCH_8PH(23); break;
-                    default: SSD_LAUNCH_8PH(0); break;
+                    case 1: rc = launch_8ph<EPI, 1>(p, xp, wp, g, ep, s); break;
+                    case 4: rc = launch_8ph<EPI, 4>(p, xp, wp, g, ep, s); break;
+                    case 5: rc = launch_8ph<EPI, 5>(p, xp, wp, g, ep, s); break;
+                    case 20: rc = launch_8ph<EPI, 20>(p, xp, wp, g, ep, s); break;
+                    case 21: rc = launch_8ph<EPI, 21>(p, xp, wp, g, ep, s); break;
+                    case 23: rc = launch_8ph<EPI, 23>(p, xp, wp, g, ep, s); break;
+                    default: rc = launch_8ph<EPI, 0>(p, xp, wp, g, ep, s); break;
                 }
-            } else
+                break;
+            }
 #endif
-            SSD_LAUNCH_8PH(0);
-#undef SSD_LAUNCH_8PH
-        }
-        else if (bm == 256 && bn == 256) SSD_LAUNCH_DMA(256, 256);
-        else if (bm == 256 && bn == 128) SSD_LAUNCH_DMA(256, 128);
-        else if (bm == 256 && bn == 64) SSD_LAUNCH_DMA(256, 64);
-        else if (bn == 64) SSD_LAUNCH_DMA(128, 64);
-        else SSD_LAUNCH_DMA(128, 128);
-#undef SSD_LAUNCH_DMA
-        if (ksplit > 1) {
-            if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
-            const long long nthr = (long long)g.M * ((g.N + 3) / 4);
-            hipLaunchKernelGGL(k_igemm_finalize<EPI>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, g, ep);
-        }
-        return ssd_launch_status();
+            rc = launch_8ph<EPI, 0>(p, xp, wp, g, ep, s);
+            break;
+        case SSD_PLAN_DMA_256_256: rc = launch_dma<256, 256, EPI>(p, xp, wp, g, ep, s); break;
+        case SSD_PLAN_DMA_256_128: rc = launch_dma<256, 128, EPI>(p, xp, wp, g, ep, s); break;
+        case SSD_PLAN_DMA_256_64: rc = launch_dma<256, 64, EPI>(p, xp, wp, g, ep, s); break;
+        case SSD_PLAN_DMA_128_64: rc = launch_dma<128, 64, EPI>(p, xp, wp, g, ep, s); break;
+        default: rc = launch_dma<128, 128, EPI>(p, xp, wp, g, ep, s); break;   // SSD_PLAN_DMA_128_128
     }
+    if (rc != SSD_OK) return rc;
+    if (p.ksplit > 1) {
+        if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
+        const long long nthr = (long long)g.M * ((g.N + 3) / 4);
+        hipLaunchKernelGGL(k_igemm_finalize<EPI>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, g, ep);
+    }
+    if (p.flags & SSD_PLAN_F_POOL_FUSED) *pooled = true;
+    return ssd_launch_status();
+}
+
+// ---- the geometry of a call, per entry, after the entry's checks of its sizes (SSD_ERR_VALUE): the entry and its query share it ----
+int fwd_geom(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, ConvGeom* g) {
+    if (!geom_ok(B, H, W, Cin, Ho, Wo, Cout, ksize) || stride <= 0) return SSD_ERR_VALUE;
+    *g = make_geom(B, H, W, Cin, Ho, Wo, Cout, ksize, ksize, stride, 1, pad_t, pad_l);
+    return SSD_OK;
+}
+
+int fwd_pool_geom(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int Hp, int Wp,
+                  ConvGeom* g) {
+    if (Cout % 8) return SSD_ERR_VALUE;
+    if ((Hp != Ho / 2 && Hp != (Ho + 1) / 2) || (Wp != Wo / 2 && Wp != (Wo + 1) / 2) || Hp <= 0 || Wp <= 0) return SSD_ERR_VALUE;
+    return fwd_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, g);
+}
+
+int head_geom(int B, int H, int W, int Cin, int per_cell, int classes, ConvGeom* g) {
+    const int N = per_cell * (4 + classes);
+    if (!geom_ok(B, H, W, Cin, H, W, N, 3) || per_cell <= 0 || classes <= 0) return SSD_ERR_VALUE;
+    *g = make_geom(B, H, W, Cin, H, W, N, 3, 3, 1, 1, 1, 1);   // 3x3 SAME stride 1 (models/ssd_model.py:155-162)
+    return SSD_OK;
+}
+
+// dy: [B,Ho,Wo,Cout_pad] is the source, dx: [B,H,W,Cin] the destination
+int bwd_data_geom(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, ConvGeom* g) {
+    if (!geom_ok(B, Ho, Wo, Cout_pad, H, W, Cin, ksize) || stride <= 0) return SSD_ERR_VALUE;
+    *g = make_geom(B, Ho, Wo, Cout_pad, H, W, Cin, ksize, ksize, 1, stride, ksize - 1 - pad_t, ksize - 1 - pad_l);
+    return SSD_OK;
+}
+
+// what a query answers from the plan: the plan word, or the ACTIVE workgroups of the (first) launch the call resolves to --
+// SSD_ERR_UNSUPPORTED where the plan does not know them (the persistent pointwise GEMM)
+int igemm_answer(int epi, const ConvGeom& g, const EpiArgs& ea, bool takes_pool, bool plain_fwd, size_t ws_bytes, bool want_wgs) {
+    IgemmPlan p;
+    const int rc = igemm_plan(epi, g, ea, takes_pool, plain_fwd, ws_bytes != 0, ws_bytes, &p);
+    if (rc != SSD_OK) return rc;
+    if (!want_wgs) return p.word();
+    return p.wgs < 0 ? SSD_ERR_UNSUPPORTED : p.wgs;
 }
 
 }  // namespace
@@ -1775,94 +1887,68 @@ extern "C" {
 
 static int conv2d_fwd_impl(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
                            int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, void* ws, size_t ws_bytes,
-                           void* stream, int* plan, void* relu_bits = nullptr) {
-    if (!x || !w || !y || !geom_ok(B, H, W, Cin, Ho, Wo, Cout, ksize) || stride <= 0) return SSD_ERR_VALUE;
-    const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, ksize, ksize, stride, 1, pad_t, pad_l);
-    if (ssd_knob("SSD_CONV_FIRST", 1) && Cin == 8 && Cout == 64 && ksize == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && H == Ho &&
-        W == Wo && H >= 16 && W >= 16) {                     // the image layer
-        const int tx = (Wo + 15) / 16, ty = (Ho + 15) / 16;
-        SSD_PLAN_WGS(SSD_PLAN_CONV0_FWD, B * tx * ty < 768 ? B * tx * ty : 768);
-        hipLaunchKernelGGL(k_conv0_fwd, dim3((unsigned)(B * tx * ty < 768 ? B * tx * ty : 768)), dim3(512), 0, (hipStream_t)stream,
-                           static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(w), bias, static_cast<bf16_raw*>(y), g, relu,
-                           tx, ty, static_cast<unsigned char*>(relu_bits));
-        return ssd_launch_status();
-    }
+                           void* stream, void* relu_bits = nullptr) {
+    ConvGeom g;
+    if (!x || !w || !y || fwd_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, &g) != SSD_OK) return SSD_ERR_VALUE;
     Epilogue ep = {};
     ep.bias = bias; ep.relu = relu; ep.out = static_cast<bf16_raw*>(y); ep.ldo = Cout;
     ep.relu_bits = static_cast<unsigned char*>(relu_bits);
-    return launch_igemm<EPI_FWD>(x, w, g, ep, (hipStream_t)stream, ws, ws_bytes, nullptr, plan);
+    return launch_igemm<EPI_FWD>(x, w, g, ep, (hipStream_t)stream, ws, ws_bytes, nullptr, true);
 }
 
 int ssd_conv2d_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
                    int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, void* ws, size_t ws_bytes,
                    void* stream) {
-    return conv2d_fwd_impl(x, w, bias, y, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, relu, ws, ws_bytes, stream,
-                           nullptr);
-}
-
-static int conv2d_fwd_pool_impl(const void* x, const void* w, const float* bias, void* y, void* y_pool, void* pool_code, int B,
-                                int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                                int relu, int Hp, int Wp, void* ws, size_t ws_bytes, void* stream, int* plan) {
-    if (!x || !w || !y_pool || !pool_code || !geom_ok(B, H, W, Cin, Ho, Wo, Cout, ksize) || stride <= 0 || Cout % 8)
-        return SSD_ERR_VALUE;
-    // y == NULL: the caller has no use for the full-resolution map (nothing but the pooling reads it): served only by the
-    // kernels that pool in their epilogue, SSD_ERR_VALUE (before anything is launched) for any other layer shape
-    if ((Hp != Ho / 2 && Hp != (Ho + 1) / 2) || (Wp != Wo / 2 && Wp != (Wo + 1) / 2) || Hp <= 0 || Wp <= 0) return SSD_ERR_VALUE;
-    const ConvGeom g = make_geom(B, H, W, Cin, Ho, Wo, Cout, ksize, ksize, stride, 1, pad_t, pad_l);
-    Epilogue ep = {};
-    ep.bias = bias; ep.relu = relu; ep.out = static_cast<bf16_raw*>(y); ep.ldo = Cout;
-    if (!y && !ssd_knob("SSD_CONV_POOL_FUSE", 1)) return SSD_ERR_VALUE;
-    if (ssd_knob("SSD_CONV_POOL_FUSE", 1)) {
-        ep.pool_out = static_cast<bf16_raw*>(y_pool); ep.pool_code = static_cast<unsigned*>(pool_code); ep.pool_h = Hp; ep.pool_w = Wp;
-    }
-    bool pooled = false;
-    const int rc = launch_igemm<EPI_FWD>(x, w, g, ep, (hipStream_t)stream, ws, ws_bytes, &pooled, plan);
-    if (rc != SSD_OK || pooled || plan) return rc;
-    // this layer is not served by a 16x16-block kernel: pool in a second launch
-    return ssd_maxpool2x2_fwd_argmax(y, y_pool, pool_code, B, Ho, Wo, Cout, Hp, Wp, stream);
+    return conv2d_fwd_impl(x, w, bias, y, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, relu, ws, ws_bytes, stream);
 }
 
 int ssd_conv2d_fwd_pool(const void* x, const void* w, const float* bias, void* y, void* y_pool, void* pool_code, int B, int H,
                         int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, int Hp,
                         int Wp, void* ws, size_t ws_bytes, void* stream) {
-    return conv2d_fwd_pool_impl(x, w, bias, y, y_pool, pool_code, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, relu,
-                                Hp, Wp, ws, ws_bytes, stream, nullptr);
-}
-
-static int conv2d_head_fwd_impl(const void* x, const void* w, const float* bias, void* loc, void* conf, int B, int H, int W,
-                                int Cin, int per_cell, int classes, int anchors_total, int level_off, void* ws, size_t ws_bytes,
-                                void* stream, int* plan) {
-    const int N = per_cell * (4 + classes);
-    if (!x || !w || !loc || !conf || !geom_ok(B, H, W, Cin, H, W, N, 3) || per_cell <= 0 || classes <= 0) return SSD_ERR_VALUE;
-    const ConvGeom g = make_geom(B, H, W, Cin, H, W, N, 3, 3, 1, 1, 1, 1);   // 3x3 SAME stride 1 (models/ssd_model.py:155-162)
+    ConvGeom g;
+    if (!x || !w || !y_pool || !pool_code ||
+        fwd_pool_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, Hp, Wp, &g) != SSD_OK)
+        return SSD_ERR_VALUE;
+    // y == NULL: the caller has no use for the full-resolution map (nothing but the pooling reads it): served only by the
+    // kernels that pool in their epilogue, SSD_ERR_VALUE (before anything is launched) for any other layer shape
     Epilogue ep = {};
-    ep.bias = bias; ep.loc = static_cast<bf16_raw*>(loc); ep.conf = static_cast<bf16_raw*>(conf);
-    ep.n_loc = per_cell * 4; ep.n_conf = per_cell * classes; ep.anchors_total = anchors_total;
-    ep.level_off = level_off; ep.per_cell = per_cell; ep.classes = classes;
-    return launch_igemm<EPI_HEAD>(x, w, g, ep, (hipStream_t)stream, ws, ws_bytes, nullptr, plan);
+    ep.bias = bias; ep.relu = relu; ep.out = static_cast<bf16_raw*>(y); ep.ldo = Cout;
+    if (ssd_knob("SSD_CONV_POOL_FUSE", 1)) {
+        ep.pool_out = static_cast<bf16_raw*>(y_pool); ep.pool_code = static_cast<unsigned*>(pool_code); ep.pool_h = Hp; ep.pool_w = Wp;
+    }
+    bool pooled = false;
+    const int rc = launch_igemm<EPI_FWD>(x, w, g, ep, (hipStream_t)stream, ws, ws_bytes, &pooled);
+    if (rc != SSD_OK || pooled) return rc;
+    // this layer is not served by a 16x16-block kernel: pool in a second launch
+    return ssd_maxpool2x2_fwd_argmax(y, y_pool, pool_code, B, Ho, Wo, Cout, Hp, Wp, stream);
 }
 
 int ssd_conv2d_head_fwd(const void* x, const void* w, const float* bias, void* loc, void* conf, int B, int H, int W,
                         int Cin, int per_cell, int classes, int anchors_total, int level_off, void* ws, size_t ws_bytes,
                         void* stream) {
-    return conv2d_head_fwd_impl(x, w, bias, loc, conf, B, H, W, Cin, per_cell, classes, anchors_total, level_off, ws, ws_bytes,
-                                stream, nullptr);
+    ConvGeom g;
+    if (!x || !w || !loc || !conf || head_geom(B, H, W, Cin, per_cell, classes, &g) != SSD_OK) return SSD_ERR_VALUE;
+    Epilogue ep = {};
+    ep.bias = bias; ep.loc = static_cast<bf16_raw*>(loc); ep.conf = static_cast<bf16_raw*>(conf);
+    ep.n_loc = per_cell * 4; ep.n_conf = per_cell * classes; ep.anchors_total = anchors_total;
+    ep.level_off = level_off; ep.per_cell = per_cell; ep.classes = classes;
+    return launch_igemm<EPI_HEAD>(x, w, g, ep, (hipStream_t)stream, ws, ws_bytes);
 }
 
 static int conv2d_bwd_data_impl(const void* dy, const void* w_t, const void* relu_src, void* dx, int B, int H, int W, int Cin,
                                 int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int accumulate,
-                                void* ws, size_t ws_bytes, void* stream, int* plan, const void* up_code = nullptr,
+                                void* ws, size_t ws_bytes, void* stream, const void* up_code = nullptr,
                                 void* up_dx = nullptr, int up_h = 0, int up_w = 0, const void* mask_bits = nullptr) {
     // dy: [B,Ho,Wo,Cout_pad]; w_t: [Cin][k][k][Cout_pad] (ssd_weight_transpose); dx, relu_src: [B,H,W,Cin]
-    if (!dy || !w_t || (!dx && !up_dx) || !geom_ok(B, Ho, Wo, Cout_pad, H, W, Cin, ksize) || stride <= 0) return SSD_ERR_VALUE;
-    const ConvGeom g = make_geom(B, Ho, Wo, Cout_pad, H, W, Cin, ksize, ksize, 1, stride, ksize - 1 - pad_t,
-                                 ksize - 1 - pad_l);
+    ConvGeom g;
+    if (!dy || !w_t || (!dx && !up_dx) || bwd_data_geom(B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, &g) != SSD_OK)
+        return SSD_ERR_VALUE;
     Epilogue ep = {};
     ep.out = static_cast<bf16_raw*>(dx); ep.ldo = Cin; ep.mask_src = static_cast<const bf16_raw*>(relu_src);
     ep.accumulate = accumulate;
     ep.up_code = static_cast<const unsigned*>(up_code); ep.up_out = static_cast<bf16_raw*>(up_dx); ep.up_h = up_h; ep.up_w = up_w;
     ep.mask_bits = static_cast<const unsigned char*>(mask_bits);
-    return launch_igemm<EPI_DGRAD>(dy, w_t, g, ep, (hipStream_t)stream, ws, ws_bytes, nullptr, plan);
+    return launch_igemm<EPI_DGRAD>(dy, w_t, g, ep, (hipStream_t)stream, ws, ws_bytes);
 }
 
 int ssd_conv2d_fwd_relubits(const void* x, const void* w, const float* bias, void* y, void* relu_bits, int B, int H, int W, int Cin,
@@ -1870,8 +1956,7 @@ int ssd_conv2d_fwd_relubits(const void* x, const void* w, const float* bias, voi
                             void* stream) {
     // ssd_conv2d_fwd with ReLU that also writes the sign bits of its output: relu_bits [B*Ho*Wo][Cout/8] bytes
     if (!relu_bits || Cout % 8) return SSD_ERR_VALUE;
-    return conv2d_fwd_impl(x, w, bias, y, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 1, ws, ws_bytes, stream, nullptr,
-                           relu_bits);
+    return conv2d_fwd_impl(x, w, bias, y, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 1, ws, ws_bytes, stream, relu_bits);
 }
 
 int ssd_conv2d_bwd_data_bits(const void* dy, const void* w_t, const void* relu_bits, void* dx, int B, int H, int W, int Cin,
@@ -1880,7 +1965,7 @@ int ssd_conv2d_bwd_data_bits(const void* dy, const void* w_t, const void* relu_b
     // ssd_conv2d_bwd_data with the ReLU mask given as sign bits ([B*H*W][Cin/8] bytes of ssd_conv2d_fwd_relubits)
     if (!relu_bits || Cin % 8) return SSD_ERR_VALUE;
     return conv2d_bwd_data_impl(dy, w_t, nullptr, dx, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws,
-                                ws_bytes, stream, nullptr, nullptr, nullptr, 0, 0, relu_bits);
+                                ws_bytes, stream, nullptr, nullptr, 0, 0, relu_bits);
 }
 
 int ssd_conv2d_bwd_data_unpool(const void* dy, const void* w_t, const void* relu_src, const void* pool_code, void* dx_pooled,
@@ -1892,7 +1977,7 @@ int ssd_conv2d_bwd_data_unpool(const void* dy, const void* w_t, const void* relu
     if ((H != Hf / 2 && H != (Hf + 1) / 2) || (W != Wf / 2 && W != (Wf + 1) / 2)) return SSD_ERR_VALUE;
     if (2 * H < Hf || 2 * W < Wf) return SSD_ERR_UNSUPPORTED;     // VALID pooling of an odd size: the uncovered row / column is not written here
     if ((long long)B * Hf * Wf * Cin >= (1ll << 32)) return SSD_ERR_VALUE;
-    return conv2d_bwd_data_impl(dy, w_t, relu_src, dx_pooled, B, H, W, Cin, Cout_pad, 3, 1, 1, 1, H, W, 0, ws, ws_bytes, stream, nullptr,
+    return conv2d_bwd_data_impl(dy, w_t, relu_src, dx_pooled, B, H, W, Cin, Cout_pad, 3, 1, 1, 1, H, W, 0, ws, ws_bytes, stream,
                                 pool_code, dx_full, Hf, Wf);
 }
 
@@ -1900,7 +1985,7 @@ int ssd_conv2d_bwd_data(const void* dy, const void* w_t, const void* relu_src, v
                         int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, int accumulate,
                         void* ws, size_t ws_bytes, void* stream) {
     return conv2d_bwd_data_impl(dy, w_t, relu_src, dx, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate,
-                                ws, ws_bytes, stream, nullptr);
+                                ws, ws_bytes, stream);
 }
 
 // Data gradient of the second layer (64 -> 64, 3x3 / stride 1 / pad 1) fused with the weight gradient of the first
@@ -1922,72 +2007,66 @@ int ssd_conv2d_bwd_data_wgrad_first(const void* dy, const void* w_t, const void*
     Epilogue ep = {};
     ep.ldo = 64;
     ep.mask_bits = static_cast<const unsigned char*>(relu_bits);
-    const int tiles_x = (W + 15) / 16, tiles_y = (H + C64B_ROWS - 1) / C64B_ROWS;
-    const int nblocks = B * tiles_x * tiles_y;
-    const unsigned grid = (unsigned)(nblocks < 512 ? nblocks : 512);   // (one workgroup per CU, to run beside the next weight gradient: slower)
+    int tiles_x, tiles_y;
+    const unsigned grid = c64b_tiling(B, H, W, 512, &tiles_x, &tiles_y);   // (one workgroup per CU, to run beside the next weight gradient: slower)
     float* slab_w = static_cast<float*>(ws);
     float* slab_b = slab_w + (size_t)512 * 64 * 72;
     hipStream_t s = (hipStream_t)stream;
-    auto kern = k_conv3x3_c64b<EPI_DGRAD, true>;
-    static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), (int)(C64B_W0_LDS)) != 0) return SSD_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), C64B_W0_LDS, s, static_cast<const bf16_raw*>(dy), static_cast<const bf16_raw*>(w_t),
-                       g, ep, tiles_x, tiles_y, C64W0{static_cast<const bf16_raw*>(image), slab_w, dbias0 ? slab_b : nullptr});
-    if (hipGetLastError() != hipSuccess) return SSD_ERR_LAUNCH;
+    const C64W0 w0 = {static_cast<const bf16_raw*>(image), slab_w, dbias0 ? slab_b : nullptr};
+    if (launch_c64b<EPI_DGRAD, true>(grid, C64B_W0_LDS, static_cast<const bf16_raw*>(dy), static_cast<const bf16_raw*>(w_t), g, ep,
+                                     tiles_x, tiles_y, w0, s) != SSD_OK || hipGetLastError() != hipSuccess)
+        return SSD_ERR_LAUNCH;
     ssd_launch_wgrad_reduce(s, slab_w, 64ll * 72, 64ll * 72, dw0, slab_b, 64ll, 64, dbias0, (int)grid);
     return ssd_launch_status();
 }
 
-// ---- dispatch queries: the same code path with `plan` set (nothing is launched, no pointer is dereferenced).  plan0 = 0: which
-// kernel (ssd_conv2d_*_plan); plan0 = PLAN_WANT_WGS: ACTIVE workgroups of the (first) launch the call resolves to
-// (ssd_conv2d_*_workgroups), SSD_ERR_UNSUPPORTED where the launch site does not report one (the persistent pointwise GEMM) ----
-static int conv2d_fwd_query(int plan0, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
+// ---- dispatch queries: the entry's geometry, the epilogue facts of the call the query stands for (bias and ReLU, every output
+// the entry requires, no ReLU mask), and igemm_plan's answer.  Nothing is launched and no pointer exists ----
+static int conv2d_fwd_query(bool want_wgs, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
                             int Wo, int pool, size_t ws_bytes) {
-    int plan = plan0, rc;
-    void* ws = ws_bytes ? PLAN_PTR : nullptr;
-    if (pool) {
-        const int Hp = (Ho + 1) / 2, Wp = (Wo + 1) / 2;
-        rc = conv2d_fwd_pool_impl(PLAN_PTR, PLAN_PTR, nullptr, pool == 2 ? nullptr : PLAN_PTR, PLAN_PTR, PLAN_PTR, B, H, W, Cin, Cout,
-                                  ksize, stride, pad_t, pad_l, Ho, Wo, 1, Hp, Wp, ws, ws_bytes, nullptr, &plan);
-    } else {
-        rc = conv2d_fwd_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 1, ws,
-                             ws_bytes, nullptr, &plan);
-    }
-    return rc != SSD_OK ? rc : plan;
+    ConvGeom g;
+    EpiArgs ea = {};
+    ea.out = pool != 2;                                          // pool = 2: ssd_conv2d_fwd_pool without y
+    ea.ldo = Cout;
+    ea.pool_out = pool && ssd_knob("SSD_CONV_POOL_FUSE", 1);
+    const int rc = pool ? fwd_pool_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, (Ho + 1) / 2, (Wo + 1) / 2, &g)
+                        : fwd_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, &g);
+    return rc != SSD_OK ? rc : igemm_answer(EPI_FWD, g, ea, pool != 0, pool == 0, ws_bytes, want_wgs);
 }
 
-static int conv2d_bwd_data_query(int plan0, int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
+static int conv2d_bwd_data_query(bool want_wgs, int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
                                  int Ho, int Wo, int accumulate, size_t ws_bytes) {
-    int plan = plan0;
-    const int rc = conv2d_bwd_data_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l,
-                                        Ho, Wo, accumulate, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
-    return rc != SSD_OK ? rc : plan;
+    ConvGeom g;
+    EpiArgs ea = {};
+    ea.out = true; ea.ldo = Cin; ea.accumulate = accumulate;
+    const int rc = bwd_data_geom(B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, &g);
+    return rc != SSD_OK ? rc : igemm_answer(EPI_DGRAD, g, ea, false, false, ws_bytes, want_wgs);
 }
 
 int ssd_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
                         int pool, size_t ws_bytes) {
-    return conv2d_fwd_query(0, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
+    return conv2d_fwd_query(false, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
 }
 
 int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
                               int pool, size_t ws_bytes) {
-    return conv2d_fwd_query(PLAN_WANT_WGS, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
+    return conv2d_fwd_query(true, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
 }
 
 int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int classes, size_t ws_bytes) {
-    int plan = 0;
-    const int rc = conv2d_head_fwd_impl(PLAN_PTR, PLAN_PTR, nullptr, PLAN_PTR, PLAN_PTR, B, H, W, Cin, per_cell, classes,
-                                        H * W * per_cell, 0, ws_bytes ? PLAN_PTR : nullptr, ws_bytes, nullptr, &plan);
-    return rc != SSD_OK ? rc : plan;
+    ConvGeom g;
+    const int rc = head_geom(B, H, W, Cin, per_cell, classes, &g);
+    return rc != SSD_OK ? rc : igemm_answer(EPI_HEAD, g, EpiArgs{}, false, false, ws_bytes, false);
 }
 
 int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                              int Wo, int accumulate, size_t ws_bytes) {
-    return conv2d_bwd_data_query(0, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
+    return conv2d_bwd_data_query(false, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
 }
 
 int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                                    int Wo, int accumulate, size_t ws_bytes) {
-    return conv2d_bwd_data_query(PLAN_WANT_WGS, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
+    return conv2d_bwd_data_query(true, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
 }
 
 const char* ssd_conv_plan_name(int plan) {

@@ -690,14 +690,15 @@ inline bool geom_ok(int B, int H, int W, int C, int Ho, int Wo, int N, int K) {
     return true;
 }
 
-// Which kernel a call resolves to (ssd_conv2d_*_plan): the dispatch code runs as usual and, with `plan` set, records
-// the id at the launch site and returns instead of launching -- the query cannot drift from the dispatch.
-// ssd_conv2d_*_workgroups: the caller presets *plan to PLAN_WANT_WGS and the launch sites that know their count record
-// the number of ACTIVE workgroups (the grid minus the workgroups that return at once) instead of the id.
-constexpr int PLAN_WANT_WGS = -1;
-#define SSD_PLAN(ID_) do { if (plan) { if (*plan == PLAN_WANT_WGS) return SSD_ERR_UNSUPPORTED; *plan = (ID_); return SSD_OK; } } while (0)
-#define SSD_PLAN_WGS(ID_, WGS_) do { if (plan) { *plan = *plan == PLAN_WANT_WGS ? (int)(WGS_) : (ID_); return SSD_OK; } } while (0)
-// what a query passes for every pointer argument (non-null, never dereferenced)
-void* const PLAN_PTR = reinterpret_cast<void*>(static_cast<uintptr_t>(64));
+// All that a dispatch decision (igemm_plan in conv.hip, ssd_pw_gemm_serves) may know of an Epilogue: which of its pointers are
+// set, ldo and accumulate.  A launch derives it from its Epilogue, a query states it -- no pointer is needed to ask.
+struct EpiArgs {
+    bool out, pool_out, up_out, mask_src, relu_bits, mask_bits;
+    int ldo, accumulate;
+};
+inline EpiArgs epi_args(const Epilogue& ep) {
+    return EpiArgs{ep.out != nullptr, ep.pool_out != nullptr, ep.up_out != nullptr, ep.mask_src != nullptr, ep.relu_bits != nullptr,
+                   ep.mask_bits != nullptr, ep.ldo, ep.accumulate};
+}
 
 }  // namespace

@@ -1074,12 +1074,11 @@ size_t ssd_conv2d_bwd_weight_workspace_bytes(int B, int Ho, int Wo, int Cin, int
     return slab_bytes(ns, ldy, ktot);
 }
 
-static int conv2d_bwd_weight_impl(const ssd_wgrad_item& it, void* ws, size_t ws_bytes, void* stream, int* plan) {
+static int conv2d_bwd_weight_impl(const ssd_wgrad_item& it, void* ws, size_t ws_bytes, void* stream) {
     // x: [B,H,W,Cin]; dy: [B,Ho,Wo,ldy] (first Cout channels used); dw: f32 [Cout][k][k][Cin]; dbias: f32 [Cout] or null
     WgradPlan p;
     if (!it.x || !it.dy || !it.dw || wgrad_plan(it, &p) != SSD_OK) return SSD_ERR_VALUE;
     if (!ws || ws_bytes < wgrad_ws_bytes(it)) return SSD_ERR_WORKSPACE;
-    SSD_PLAN(p.word());
     const ConvGeom g = wgrad_geom(it);
     const bf16_raw* x = static_cast<const bf16_raw*>(it.x);
     const bf16_raw* dy = static_cast<const bf16_raw*>(it.dy);
@@ -1126,17 +1125,16 @@ int ssd_conv2d_bwd_weight(const void* x, const void* dy, float* dw, float* dbias
                           int ldy, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo, void* ws, size_t ws_bytes,
                           void* stream) {
     const ssd_wgrad_item it = {x, dy, dw, dbias, B, H, W, Cin, Cout, ldy, ksize, stride, pad_t, pad_l, Ho, Wo};
-    return conv2d_bwd_weight_impl(it, ws, ws_bytes, stream, nullptr);
+    return conv2d_bwd_weight_impl(it, ws, ws_bytes, stream);
 }
 
-// dispatch query: the same code path with `plan` set (nothing is launched, no pointer is dereferenced)
+// dispatch query: the plan of the layer (wgrad_plan reads no pointer of the item)
 int ssd_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int ldy, int ksize, int stride, int pad_t, int pad_l,
                                int Ho, int Wo) {
-    const ssd_wgrad_item it = {PLAN_PTR, PLAN_PTR, static_cast<float*>(PLAN_PTR), static_cast<float*>(PLAN_PTR),
-                               B, H, W, Cin, Cout, ldy, ksize, stride, pad_t, pad_l, Ho, Wo};
-    int plan = 0;
-    const int rc = conv2d_bwd_weight_impl(it, PLAN_PTR, wgrad_ws_bytes(it), nullptr, &plan);
-    return rc != SSD_OK ? rc : plan;
+    const ssd_wgrad_item it = {nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Cout, ldy, ksize, stride, pad_t, pad_l, Ho, Wo};
+    WgradPlan p;
+    const int rc = wgrad_plan(it, &p);
+    return rc != SSD_OK ? rc : p.word();
 }
 
 // Several SMALL layers' weight gradients in two launches (slab kernel + slab sums) instead of two per layer: the extras on the

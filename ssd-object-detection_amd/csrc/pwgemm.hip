@@ -363,15 +363,16 @@ OnceLds g_pw_once[3];
 
 }  // namespace
 
-// Called from conv.hip's dispatch (launch_igemm); geometry / epilogue are the structs of conv_common.h (same header, both
-// translation units).  Returns SSD_ERR_UNSUPPORTED (nothing launched) for shapes this kernel does not serve.
-bool ssd_pw_gemm_serves(int epi, const void* geom, const void* epilogue) {
+// Called from conv.hip's dispatch (igemm_plan asks, launch_igemm launches); geometry / epilogue / epi_args are the structs of
+// conv_common.h (same header, both translation units).  The launch returns SSD_ERR_UNSUPPORTED (nothing launched) for shapes
+// this kernel does not serve.
+bool ssd_pw_gemm_serves(int epi, const void* geom, const void* epi_args) {
     const ConvGeom& g = *static_cast<const ConvGeom*>(geom);
-    const Epilogue& ep = *static_cast<const Epilogue*>(epilogue);
+    const EpiArgs& ep = *static_cast<const EpiArgs*>(epi_args);
     if (epi != EPI_FWD && epi != EPI_DGRAD) return false;
     if (g.KH != 1 || g.KW != 1 || g.mul != 1 || g.div != 1 || g.pad_t != 0 || g.pad_l != 0 || g.H != g.Ho || g.W != g.Wo) return false;
     if (g.C % 64 || g.C < 256 || (g.N & 7) || (ep.ldo & 7) || g.ldw != g.C || !ep.out) return false;
-    if (ep.slab || ep.pool_out || ep.up_out || ep.mask_src) return false;     // (the ReLU mask as sign bytes only)
+    if (ep.pool_out || ep.up_out || ep.mask_src) return false;                // (the ReLU mask as sign bytes only)
     if (epi == EPI_FWD && ep.accumulate) return false;
     if ((long long)(g.M + 256) * g.C * 2 >= (1ll << 31) || (long long)(g.N + 256) * g.C * 2 >= (1ll << 31)) return false;   // 31-bit stream offsets
     if (g.N > 2048) return false;                 // the bias / sign-byte region of the LDS image
@@ -384,9 +385,10 @@ bool ssd_pw_gemm_serves(int epi, const void* geom, const void* epilogue) {
 }
 
 int ssd_pw_gemm_launch(int epi, const void* x, const void* w, const void* geom, const void* epilogue, void* stream) {
-    if (!ssd_pw_gemm_serves(epi, geom, epilogue)) return SSD_ERR_UNSUPPORTED;
     const ConvGeom& g = *static_cast<const ConvGeom*>(geom);
     const Epilogue& ep = *static_cast<const Epilogue*>(epilogue);
+    const EpiArgs ea = epi_args(ep);
+    if (ep.slab || !ssd_pw_gemm_serves(epi, geom, &ea)) return SSD_ERR_UNSUPPORTED;
     PwSched sc;
     sc.ntm = (g.M + 255) / 256;
     sc.ntn = (g.N + 255) / 256;
