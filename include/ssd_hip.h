@@ -740,6 +740,34 @@ int ssd_l2norm_bwd(const void* dy, const void* x, const float* scale, const floa
                    float* dscale, void* ws, size_t ws_bytes, long long P, int C, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batch normalisation over the rows of an NHWC map (no reference counterpart: the ResNet-50 SSD512 trunk's opt-in training
+ * mode).  x, y, dy, dx: bf16 [P][C], P = B H W rows, the channel fastest; gamma, beta, mean, rstd, running_mean, running_var,
+ * dgamma, dbeta: fp32 [C].  All arithmetic in fp32, per channel c:
+ *   training forward   mu = (1/P) sum_p x_pc      v = (1/P) sum_p (x_pc - mu)^2 (biased)      rstd = 1 / sqrt(v + eps)
+ *                      y_pc = bf16(gamma_c (x_pc - mu) rstd + beta_c), through max(., 0) where relu;  mean <- mu, rstd <- rstd
+ *                      running_mean <- (1 - m) running_mean + m mu     running_var <- (1 - m) running_var + m v P / (P - 1)
+ *                      (PyTorch's convention; both running pointers NULL: no running update)
+ *   inference forward  a = gamma / sqrt(running_var + eps)   b = beta - running_mean a   y = bf16(x a + b) [max(., 0)]
+ *   backward           xh = (x - mu) rstd (rebuilt from x and the saved mean / rstd, never from y)
+ *                      dbeta = sum_p dy     dgamma = sum_p dy xh     dx = bf16(gamma rstd (dy - dbeta / P - xh dgamma / P))
+ *                      dy is expected masked by the node's own ReLU already; dgamma, dbeta are written, not accumulated.
+ * The variance is never formed as E[x^2] - mu^2: per-thread shifted sums give (n, mean, M2) partials, merged by Chan's formula.
+ * Per-channel sums come from fixed-order partial sums in ws (no atomics): bitwise reproducible.  ws: exactly ssd_bn_ws_bytes
+ * bytes of scratch without initial-content requirements.  y may not alias x; dx may alias neither x nor dy.
+ * Shapes: C % 64 == 0 and 64 <= C <= 2048, else SSD_ERR_UNSUPPORTED (ssd_bn_ws_bytes: 0); P >= 2 for training and backward,
+ * P >= 1 for inference.  SSD_ERR_VALUE: a NULL required pointer, only one of the two running pointers, an aliased output,
+ * eps <= 0, momentum outside (0, 1], P too small or a workspace that is too small.  Nothing is launched on either error.
+ * ---------------------------------------------------------------------------------------- */
+size_t ssd_bn_ws_bytes(long long P, int C);
+int ssd_bn_fwd_train(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                     float* running_mean, float* running_var, float momentum, float eps, int relu, void* ws, size_t ws_bytes,
+                     long long P, int C, void* stream);
+int ssd_bn_fwd_infer(const void* x, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                     void* y, float eps, int relu, long long P, int C, void* stream);
+int ssd_bn_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+               float* dbeta, void* ws, size_t ws_bytes, long long P, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Dispatch queries (no reference counterpart; testing / reports): which kernel a convolution call with this shape
  * resolves to.  They run the library's own dispatch code with launching switched off, so the answer cannot drift from
  * what the call does.  Return: a plan word >= 0 (kernel id in SSD_PLAN_KERNEL_MASK, path flags above it) or a negative

@@ -154,6 +154,11 @@ _SIGNATURES = {
     "ssd_l2norm_fwd": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_longlong, ctypes.c_int, ctypes.c_float, VP]),
     "ssd_l2norm_bwd": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int, VP, VP, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int,
                                       ctypes.c_float, VP]),
+    "ssd_bn_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
+    "ssd_bn_fwd_train": (ctypes.c_int, [VP] * 8 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, VP, ctypes.c_size_t,
+                                                   ctypes.c_longlong, ctypes.c_int, VP]),
+    "ssd_bn_fwd_infer": (ctypes.c_int, [VP] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP]),
+    "ssd_bn_bwd": (ctypes.c_int, [VP] * 9 + [ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int, VP]),
     "ssd_dev_knob": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "ssd_dev_mfma_calibration_workgroups": (ctypes.c_int, []),
     "ssd_dev_mfma_calibration_flops": (ctypes.c_double, [ctypes.c_int]),

@@ -668,8 +668,12 @@ class SSDEngine:
             if c0 % 128 or not 128 <= c0 <= 1024:
                 raise ValueError("l2norm: feature map 0 has %d channels; the kernels serve multiples of 128 in 128 .. 1024" % c0)
             self.l2norm_scale = add("l2norm0/scale", (c0,))
+        self._plan_extra_params(add)
         self.n_flat = off
         self.n_params = sum(t.numel for t in self.tensors)
+
+    def _plan_extra_params(self, add):
+        """Variables of a subclass, behind every tensor planned above (which keep their index, offset and block)."""
 
     def _alloc_params(self):
         dev, n = self.device, self.n_flat
@@ -1187,7 +1191,8 @@ class SSDEngine:
     def decay_table(self, weight_decay, decay_bias=False):
         """Device fp32 [len(tensors)]: the L2 coefficient of every tensor for ssd_sgd_momentum_step -- weight_decay on the
         filters (names ending in "kernel"), on the biases only with decay_bias (Caffe SSD: decay_mult 0), else 0.  The l2norm
-        scale ("l2norm0/scale") counts as a bias: an L2 term only with decay_bias.
+        scale ("l2norm0/scale") and the batch normalisation's gamma / beta ("bn*/gamma", "bn*/beta") count as biases: an L2 term
+        only with decay_bias.
         Cached per (weight_decay, decay_bias)."""
         key = (float(weight_decay), bool(decay_bias))
         if not hasattr(self, "_decay_tables"):

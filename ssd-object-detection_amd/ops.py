@@ -391,6 +391,131 @@ def l2norm_bwd(dy, x, scale, rnorm=None, out=None, accumulate=False, dscale=None
     return out, dscale
 
 
+class BatchNormSpec:
+    """Batch normalisation of the ResNet-50 SSD512 trunk in training mode (batchnorm_fwd_train / batchnorm_fwd_infer /
+    batchnorm_bwd): `momentum` is the weight of the batch statistics in the running ones (PyTorch's convention and default),
+    `eps` is added to the variance under the root."""
+
+    def __init__(self, momentum=0.1, eps=1e-5):
+        for name, v in (("momentum", momentum), ("eps", eps)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("batchnorm %s must be a number, not %r" % (name, v))
+            if not (np.isfinite(v) and v > 0):
+                raise ValueError("batchnorm %s must be finite and > 0, not %r" % (name, v))
+        if momentum > 1:
+            raise ValueError("batchnorm momentum must lie in (0, 1], not %r" % (momentum,))
+        self.momentum = float(momentum)
+        self.eps = float(eps)
+
+    @classmethod
+    def of(cls, v):
+        """None / False -> None (no batch normalisation); True -> the defaults; a BatchNormSpec -> itself; a dict with the
+        keys momentum / eps -> a spec.  ValueError for anything else."""
+        if v is None or v is False:
+            return None
+        if v is True:
+            return cls()
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, dict):
+            unknown = sorted(set(v) - {"momentum", "eps"}, key=str)
+            if unknown:
+                raise ValueError("batchnorm: unknown key(s) %s (known: momentum, eps)" % ", ".join(repr(k) for k in unknown))
+            return cls(**v)
+        raise ValueError("batchnorm must be None, a bool, a dict(momentum, eps) or an ops.BatchNormSpec, not %r" % (v,))
+
+    def __repr__(self):
+        return "BatchNormSpec(momentum=%r, eps=%r)" % (self.momentum, self.eps)
+
+
+_bn_ws = MatchWorkspace()
+_BN_SHAPES = "batchnorm serves multiples of 64 channels in 64 .. 2048, not C = %d"
+
+
+def _bn_vec(t, C):
+    if t is not None:
+        assert _dev(t, torch.float32).numel() == C
+    return t
+
+
+def batchnorm_fwd_train(x, gamma, beta, out=None, mean=None, rstd=None, running_mean=None, running_var=None, momentum=0.1,
+                        eps=1e-5, relu=False, ws=None):
+    """ssd_bn_fwd_train: y = bf16(gamma_c (x_pc - mu_c) rstd_c + beta_c), through max(., 0) where relu, with the statistics of
+    the rows of x (bf16 [..., C]; mu the mean, rstd = 1 / sqrt(biased variance + eps), fp32, bitwise reproducible).  mean /
+    rstd: fp32 [C] tensors that receive what batchnorm_bwd needs (allocated when None).  running_mean / running_var: both or
+    neither; updated in place with weight `momentum` for the batch (the variance unbiased, P / (P - 1): PyTorch's
+    convention).  Returns (y, mean, rstd).  NotImplementedError (SSD_ERR_UNSUPPORTED, nothing launched) unless C % 64 == 0
+    and 64 <= C <= 2048."""
+    L = _lib.lib()
+    _bf(x)
+    C = x.shape[-1]
+    P = x.numel() // C
+    if out is None:
+        out = torch.empty_like(x)
+    assert _bf(out).shape == x.shape
+    if mean is None:
+        mean = torch.empty((C,), dtype=torch.float32, device=x.device)
+    if rstd is None:
+        rstd = torch.empty((C,), dtype=torch.float32, device=x.device)
+    for t in (gamma, beta, mean, rstd, running_mean, running_var):
+        _bn_vec(t, C)
+    wbuf = (ws or _bn_ws).get(L.ssd_bn_ws_bytes(P, C), x.device)
+    rc = L.ssd_bn_fwd_train(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(mean), _ptr(rstd), _ptr(running_mean),
+                            _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, _ptr(wbuf), wbuf.numel(), P, C,
+                            _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError(_BN_SHAPES % C)
+    _lib.check(rc)
+    return out, mean, rstd
+
+
+def batchnorm_fwd_infer(x, gamma, beta, running_mean, running_var, out=None, eps=1e-5, relu=False):
+    """ssd_bn_fwd_infer: y = bf16(x a_c + b_c), through max(., 0) where relu, with a = gamma / sqrt(running_var + eps) and
+    b = beta - running_mean a: one pass, no workspace.  Shapes and errors as batchnorm_fwd_train."""
+    L = _lib.lib()
+    _bf(x)
+    C = x.shape[-1]
+    P = x.numel() // C
+    if out is None:
+        out = torch.empty_like(x)
+    assert _bf(out).shape == x.shape
+    for t in (gamma, beta, running_mean, running_var):
+        _bn_vec(t, C)
+    rc = L.ssd_bn_fwd_infer(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(out), float(eps),
+                            1 if relu else 0, P, C, _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError(_BN_SHAPES % C)
+    _lib.check(rc)
+    return out
+
+
+def batchnorm_bwd(dy, x, gamma, mean, rstd, out=None, dgamma=None, dbeta=None, ws=None):
+    """ssd_bn_bwd: the gradients of batchnorm_fwd_train w.r.t. x (bf16 like x, into `out`), gamma and beta (fp32 [C], written,
+    bitwise reproducible) from dy -- which the caller has masked by the layer's own ReLU already -- x and the mean / rstd the
+    forward pass saved.  Returns (dx, dgamma, dbeta)."""
+    L = _lib.lib()
+    _bf(dy); _bf(x)
+    assert dy.shape == x.shape
+    C = x.shape[-1]
+    P = x.numel() // C
+    if out is None:
+        out = torch.empty_like(x)
+    assert _bf(out).shape == x.shape
+    if dgamma is None:
+        dgamma = torch.empty((C,), dtype=torch.float32, device=x.device)
+    if dbeta is None:
+        dbeta = torch.empty((C,), dtype=torch.float32, device=x.device)
+    for t in (gamma, mean, rstd, dgamma, dbeta):
+        _bn_vec(t, C)
+    wbuf = (ws or _bn_ws).get(L.ssd_bn_ws_bytes(P, C), x.device)
+    rc = L.ssd_bn_bwd(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(out), _ptr(dgamma), _ptr(dbeta), _ptr(wbuf),
+                      wbuf.numel(), P, C, _stream())
+    if rc == _lib.SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError(_BN_SHAPES % C)
+    _lib.check(rc)
+    return out, dgamma, dbeta
+
+
 _multibox_ws = MatchWorkspace()
 
 

@@ -10,6 +10,9 @@ shift into the bias: every convolution is conv + bias, trainable) -- 7x7/2 stem,
 levels 64, 32, 16, 8, 4, 2, 1 with 4, 6, 6, 6, 6, 4, 4 default boxes per cell = 24 564 anchors, heads as in the reference
 (:153-162).  TF "SAME" padding everywhere (Keras semantics, as the rest of the engine).
 
+Opt-in (batchnorm=...): LIVE batch normalisation behind each of the 43 trunk convolutions (csrc/batchnorm.hip), to train the
+trunk from scratch; fold_batchnorm_params / engine.folded() turn the trained network into the folded one above.
+
 The network is a DAG (residual adds), so forward / backward are a plain topological walk on ONE stream over the same C-ABI
 entry points SSDEngine uses (1x1 layers on k_pw_gemm, 3x3 layers on the LDS-patch kernels, strided layers on the implicit-GEMM
 kernels, heads' backward from the loss's compact rows) plus csrc/eltwise.hip (Add + ReLU, its gradient, 3x3/2 pooling).
@@ -20,15 +23,24 @@ from . import ops
 from .engine import SSDEngine, SSD512_NUM_PRIORS
 
 
-def resnet50_ssd512_graph():
+def resnet50_ssd512_graph(batchnorm=False):
     """Topologically ordered nodes: dict(op, src, cin, cout, k, stride, relu, feature).  src = producing node index
-    (-1: the network input), for "add": (block output, shortcut)."""
+    (-1: the network input), for "add": (block output, shortcut).  batchnorm=True: each of the 43 trunk convolutions (stem,
+    39 bottleneck convolutions, 3 projections) is followed by a node op="bn" with src = that convolution, which carries the
+    convolution's ReLU flag (the convolution's own becomes False); consumers and adds read the bn node.  The ten extras stay
+    conv + bias + ReLU."""
     g = []
 
-    def conv(src, cin, cout, k, stride, relu=True, feature=False):
+    def plain(src, cin, cout, k, stride, relu=True, feature=False):
         g.append(dict(op="conv", src=src, cin=cin, cout=cout, k=k, stride=stride, relu=relu, feature=feature))
         return len(g) - 1
 
+    def normed(src, cin, cout, k, stride, relu=True):
+        c = plain(src, cin, cout, k, stride, relu=False)
+        g.append(dict(op="bn", src=c, cin=cout, cout=cout, k=1, stride=1, relu=relu, feature=False))
+        return len(g) - 1
+
+    conv = normed if batchnorm else plain
     x = conv(-1, 8, 64, 7, 2)                                  # stem (image carried in 8 zero-padded channels)
     g.append(dict(op="pool3", src=x, cin=64, cout=64, k=3, stride=2, relu=False, feature=False))
     x, cin = len(g) - 1, 64
@@ -43,8 +55,8 @@ def resnet50_ssd512_graph():
                           feature=feat and b == blocks - 1))
             x, cin = len(g) - 1, 4 * width
     for mid, out in ((256, 512), (128, 256), (128, 256), (128, 256), (128, 256)):   # extras: 32 -> 16 -> 8 -> 4 -> 2 -> 1
-        x = conv(x, cin, mid, 1, 1)
-        x = conv(x, mid, out, 3, 2, feature=True)
+        x = plain(x, cin, mid, 1, 1)
+        x = plain(x, mid, out, 3, 2, feature=True)
         cin = out
     return g
 
@@ -137,30 +149,97 @@ def mxfp8_bwd_plan(nodes):
     return dgrad, root, maps
 
 
+def fold_batchnorm_params(graph_bn, params, running, eps):
+    """The parameters of the default (folded) network that computes what the batch-normalised one computes in inference mode.
+    Pure: no device, no engine; works on any {name: tensor} dict (CPU, any float dtype).  graph_bn:
+    resnet50_ssd512_graph(batchnorm=True); params: conv{i}/kernel [Cout,k,k,Cin], conv{i}/bias, bn{i}/gamma, bn{i}/beta by
+    node index of graph_bn, head*/...; running: (running_mean, running_var), each ONE flat tensor over the bn nodes in node
+    order (the engine's bn_running_mean / bn_running_var).  With a = gamma / sqrt(running_var + eps) per output channel:
+        w' = w a[cout]        b' = (b - running_mean) a + beta
+    The k-th convolution of graph_bn becomes conv{k'}, k' = the node index of the k-th convolution of the default graph; a
+    convolution without a bn node behind it (the extras) and the heads are copied."""
+    rm, rv = running
+    bn_of, off = {}, 0
+    for i, nd in enumerate(graph_bn):
+        if nd["op"] == "bn":
+            bn_of[nd["src"]] = (i, off)
+            off += nd["cout"]
+    assert rm.numel() == off and rv.numel() == off, (rm.numel(), rv.numel(), off)
+    convs_bn = [i for i, nd in enumerate(graph_bn) if nd["op"] == "conv"]
+    convs = [i for i, nd in enumerate(resnet50_ssd512_graph()) if nd["op"] == "conv"]
+    assert len(convs_bn) == len(convs)
+    out = {n: t for n, t in params.items() if n.startswith("head")}
+    for i, k in zip(convs_bn, convs):
+        w, b = params["conv%d/kernel" % i], params["conv%d/bias" % i]
+        if i in bn_of:
+            j, o = bn_of[i]
+            c = graph_bn[i]["cout"]
+            a = params["bn%d/gamma" % j] / torch.sqrt(rv[o:o + c].to(w.dtype) + eps)
+            w = w * a.view(-1, 1, 1, 1)
+            b = (b - rm[o:o + c].to(b.dtype)) * a + params["bn%d/beta" % j]
+        out["conv%d/kernel" % k], out["conv%d/bias" % k] = w, b
+    return out
+
+
 class ResNet50SSDEngine(SSDEngine):
-    def __init__(self, classes=81, in_size=512, device="cuda", seed=0):
-        self.graph = resnet50_ssd512_graph()
+    def __init__(self, classes=81, in_size=512, device="cuda", seed=0, batchnorm=None):
+        """batchnorm: live batch normalisation behind each trunk convolution (ops.BatchNormSpec.of: None / False = off, the
+        folded network of the module docstring; True, a dict(momentum, eps) or a spec).  Off, the engine plans the same
+        graph and tensors and launches what it did without the option.  On: the graph of resnet50_ssd512_graph(True); 86
+        more variables "bn{i}/gamma" (1) and "bn{i}/beta" (0), i the bn node's index, behind every other one, trained, clipped
+        and saved like the rest; the running mean / variance are plain fp32 buffers (bn_running_mean / bn_running_var, one flat
+        tensor each in bn-node order, no optimizer variables).  forward(x, train=True) normalises with the batch's statistics
+        and updates the running ones, forward(x) uses the running ones; the block-scaled fp8 paths rest on producer epilogues
+        and refuse a batchnorm engine: fold first (folded()).  The bias of a normalised convolution stays in the table (it is
+        zero and its gradient slot is never written: batch normalisation cancels it).  The statistics are those of THIS
+        process's batch: under data parallelism every rank normalises with its own (no synchronised batch norm); the running
+        buffers are per rank too."""
+        self.batchnorm = ops.BatchNormSpec.of(batchnorm)
+        self.graph = resnet50_ssd512_graph(batchnorm=self.batchnorm is not None)
         super().__init__(classes=classes, in_size=in_size, trunk=[], num_priors=SSD512_NUM_PRIORS, device=device, seed=seed,
                          sparse_heads=True)
         self.relu_bits = None                  # ReLU masks from the bf16 activations (the sign-byte forms are a VGG-chain fusion)
         self.overlap_heads = False
-        self.mx_fp8, self.mx_writes = mxfp8_plan(self.nodes)
+        self._bn_train = False                 # the last forward of a batchnorm engine used (and saved) batch statistics
+        self._ws_bn = ops.MatchWorkspace()     # slab partials of the batch normalisation kernels
+        bn = self.batchnorm is not None        # a batchnorm engine has no fp8 plan: forward(x, "mxfp8") refuses
+        self.mx_fp8, self.mx_writes = (set(), {}) if bn else mxfp8_plan(self.nodes)
         # filters of the fp8 layers: ONE ssd_quantize_mx_fp8 over the trunk's part of param_bf16 at every fp8 forward (conv
         # filters start on optimizer-block boundaries, multiples of 32 elements, so each layer's (q, scale) is a slice of it);
         # nothing is cached against the weights, so no path that writes param_bf16 can leave a stale copy behind
         self.n_trunk = max(bt.block0 + bt.nblocks for _, bt in self.conv_params.values()) * self.block
         self._mx_w = None                      # (q u8 [n_trunk], scale u8 [n_trunk / 32]), allocated at the first fp8 forward
         self._mx_forward = False               # the last forward ran in fp8: the bf16 activations backward() needs are incomplete
-        self.mx_train_writes = mxfp8_plan(self.nodes, train=True)[1]
+        self.mx_train_writes = {} if bn else mxfp8_plan(self.nodes, train=True)[1]
         self._mx_train = False                 # ... in training mode: every bf16 map backward() reads was written
         self._mx_wt = None                     # (q, scale) of the fp8 data gradients' transposed filters, at every fp8 backward
 
     # ---------------------------------------------------------------- static planning
+    def _plan_extra_params(self, add):
+        self.bn_params, self.bn_off, off = {}, {}, 0          # bn node -> (gamma, beta); -> offset in the flat statistics
+        for i, nd in enumerate(self.nodes):
+            if nd["kind"] == "bn":
+                self.bn_params[i] = (add("bn%d/gamma" % i, (nd["cout"],)), add("bn%d/beta" % i, (nd["cout"],)))
+                self.bn_off[i] = off
+                off += nd["cout"]
+        self.bn_channels = off
+        self.bn_convs = {self.nodes[i]["src"] for i in self.bn_params}      # the normalised convolutions
+
     def _alloc_params(self):
         super()._alloc_params()
+        if self.batchnorm is not None:
+            dev, n = self.device, self.bn_channels
+            self.bn_running_mean = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.bn_running_var = torch.ones(n, dtype=torch.float32, device=dev)
+            self._bn_mean = torch.empty(n, dtype=torch.float32, device=dev)        # the batch's, saved by forward(train=True)
+            self._bn_rstd = torch.empty(n, dtype=torch.float32, device=dev)
+            # where conv2d_bwd_weight puts the bias gradient of a normalised convolution: never read (the true gradient is 0)
+            self._bn_dbias = torch.empty(max(nd["cout"] for nd in self.nodes), dtype=torch.float32, device=dev)
+            self.mx_dgrad, self.mx_groot, self.mx_gmaps = set(), list(range(len(self.nodes))), {}
+        else:
+            self.mx_dgrad, self.mx_groot, self.mx_gmaps = mxfp8_bwd_plan(self.nodes)
         # the transposed filters as slices of ONE buffer, the fp8 data gradients' first: their MX-fp8 form is then one
         # ssd_quantize_mx_fp8 over its front (every slice starts on a 32-element block: Cout % 32 == 0 for all of them)
-        self.mx_dgrad, self.mx_groot, self.mx_gmaps = mxfp8_bwd_plan(self.nodes)
         order = sorted(self.w_t, key=lambda i: (i not in self.mx_dgrad, i))
         sizes = [self.w_t[i].numel() for i in order]
         assert all(v % 32 == 0 for v in sizes)
@@ -172,6 +251,20 @@ class ResNet50SSDEngine(SSDEngine):
             off += v
         self.n_wt8 = sum(v for i, v in zip(order, sizes) if i in self.mx_dgrad)
         self._wt_flat = flat
+
+    def init_params(self, seed=0):
+        """As SSDEngine.init_params; a batchnorm engine's gammas start at 1 (betas at 0), its running statistics at (0, 1)."""
+        super().init_params(seed)
+        if self.batchnorm is not None:
+            for gamma, _ in self.bn_params.values():
+                self.view(gamma, self.param).fill_(1.0)
+            self.bn_running_mean.zero_()
+            self.bn_running_var.fill_(1.0)
+            self.refresh_weights(cast=True)
+
+    def _bn_stat(self, i, buf):
+        o = self.bn_off[i]
+        return buf[o:o + self.nodes[i]["cout"]]
 
     def _plan_shapes(self):
         self.nodes, self.fm = [], []
@@ -272,12 +365,18 @@ class ResNet50SSDEngine(SSDEngine):
         """(loc, conf) of image batch x.  precision="mxfp8": the trunk's fp8 layers (mxfp8_plan) on block-scaled fp8
         operands, each fed directly by the layer before it; the rest and the heads in bf16.  Inference only unless
         train=True, which also writes every bf16 map backward() reads (same fp8 launches, same (loc, conf)); backward()
-        then runs the stride-1 data gradients in fp8 (mxfp8_bwd_plan)."""
+        then runs the stride-1 data gradients in fp8 (mxfp8_bwd_plan).
+        A batchnorm engine (bf16 only): train=True normalises with the batch's statistics, saves them for backward() and
+        updates the running ones; train=False normalises with the running ones."""
         if precision == "mxfp8":
+            if self.batchnorm is not None:
+                raise ValueError("forward(x, 'mxfp8') on a batchnorm engine: the fp8 plan rests on producer epilogues; fold "
+                                 "the trained network first (folded()) and run that engine in fp8")
             return self._forward_mxfp8(x, train)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         self._mx_forward = self._mx_train = False
+        self._bn_train = self.batchnorm is not None and bool(train)
         B = x.shape[0]
         c = self._acts(B)
         acts = c["acts"]
@@ -288,6 +387,17 @@ class ResNet50SSDEngine(SSDEngine):
                 wt, bt = self.conv_params[i]
                 ops.conv2d_fwd(self._in(acts, nd["src"]), self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"],
                                nd["pt"], nd["pl"], nd["hout"], nd["hout"], nd["relu"], out=acts[i + 1], ws=self._ws)
+            elif nd["kind"] == "bn":
+                gamma, beta = (self.view(t, self.param) for t in self.bn_params[i])
+                rm, rv = self._bn_stat(i, self.bn_running_mean), self._bn_stat(i, self.bn_running_var)
+                if self._bn_train:
+                    ops.batchnorm_fwd_train(self._in(acts, nd["src"]), gamma, beta, out=acts[i + 1],
+                                            mean=self._bn_stat(i, self._bn_mean), rstd=self._bn_stat(i, self._bn_rstd),
+                                            running_mean=rm, running_var=rv, momentum=self.batchnorm.momentum,
+                                            eps=self.batchnorm.eps, relu=nd["relu"], ws=self._ws_bn)
+                else:
+                    ops.batchnorm_fwd_infer(self._in(acts, nd["src"]), gamma, beta, rm, rv, out=acts[i + 1],
+                                            eps=self.batchnorm.eps, relu=nd["relu"])
             elif nd["kind"] == "pool3":
                 ops.maxpool3x3s2_fwd(self._in(acts, nd["src"]), out=acts[i + 1], code=c["pool3_code"][i])
             else:
@@ -346,6 +456,9 @@ class ResNet50SSDEngine(SSDEngine):
         if self._mx_forward and not self._mx_train:
             raise RuntimeError("backward() after an inference mxfp8 forward: the bf16 activations it needs were not all "
                                "written; run forward(x) in bf16 or forward(x, 'mxfp8', train=True) first")
+        if self.batchnorm is not None and not self._bn_train:
+            raise RuntimeError("backward() after an inference-mode forward of a batchnorm engine: no batch statistics were "
+                               "saved; run forward(x, train=True) first")
         if dgrad_precision not in (None, "bf16", "mxfp8"):
             raise ValueError("dgrad_precision must be 'bf16' or 'mxfp8', not %r" % (dgrad_precision,))
         if dgrad_precision == "mxfp8" and not self._mx_train:
@@ -388,7 +501,7 @@ class ResNet50SSDEngine(SSDEngine):
                 assert not written[a + 1] and not self.nodes[a]["relu"]
                 gacts[a + 1] = g
                 written[a + 1] = True
-                if self.nodes[sc]["kind"] == "conv" and not self.nodes[sc]["relu"]:      # projection shortcut: linear too
+                if self.nodes[sc]["kind"] in ("conv", "bn") and not self.nodes[sc]["relu"]:      # projection shortcut: linear too
                     assert not written[sc + 1]
                     gacts[sc + 1] = g
                 else:                           # identity shortcut: masked by the source's own ReLU, summed with its other uses
@@ -403,9 +516,24 @@ class ResNet50SSDEngine(SSDEngine):
                 wrote(src, "pool", i)
                 written[src + 1] = True
                 continue
+            if nd["kind"] == "bn":
+                # g is masked by this node's own ReLU already (its consumers' data gradients did that); xh is rebuilt from the
+                # convolution's output and the statistics the forward pass saved
+                assert not written[src + 1]
+                gamma, beta = self.bn_params[i]
+                ops.batchnorm_bwd(g, acts[src + 1], self.view(gamma, self.param), self._bn_stat(i, self._bn_mean),
+                                  self._bn_stat(i, self._bn_rstd), out=gacts[src + 1], dgamma=self.view(gamma, self.grad),
+                                  dbeta=self.view(beta, self.grad), ws=self._ws_bn)
+                if on_ready:
+                    on_ready([gamma.index, beta.index])
+                written[src + 1] = True
+                continue
             wt, bt = self.conv_params[i]
+            # a normalised convolution's bias gradient is zero (the mean subtraction cancels the bias): the kernel's sum goes
+            # to scratch and the variable's slot in grad is never written
+            normed = self.batchnorm is not None and i in self.bn_convs
             ops.conv2d_bwd_weight(acts[src + 1], g, nd["cout"], nd["k"], nd["stride"], nd["pt"], nd["pl"], dw=self.view(wt, self.grad),
-                                  dbias=self.view(bt, self.grad), ws=self._ws)
+                                  dbias=self._bn_dbias[:nd["cout"]] if normed else self.view(bt, self.grad), ws=self._ws)
             if on_ready:
                 on_ready([wt.index, bt.index])
             if src < 0:
@@ -425,3 +553,34 @@ class ResNet50SSDEngine(SSDEngine):
             written[src + 1] = True
         if on_ready:
             on_ready([i for wt, bt in self.head_params for t in (wt, bt) for i in t.indices])
+
+    # ---------------------------------------------------------------- batchnorm: state and folding
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.batchnorm is not None:
+            sd.update(bn_running_mean=self.bn_running_mean.cpu(), bn_running_var=self.bn_running_var.cpu(),
+                      bn=dict(momentum=self.batchnorm.momentum, eps=self.batchnorm.eps))
+        return sd
+
+    def load_state_dict(self, sd):
+        """As SSDEngine.load_state_dict (a default engine's and a batchnorm engine's layouts refuse each other through the
+        variable names); a batchnorm engine also restores its running statistics."""
+        super().load_state_dict(sd)
+        if self.batchnorm is not None:
+            self.bn_running_mean.copy_(sd["bn_running_mean"])
+            self.bn_running_var.copy_(sd["bn_running_var"])
+
+    def folded(self):
+        """A default ResNet50SSDEngine (no batch normalisation) loaded with fold_batchnorm_params of this engine's parameters
+        and running statistics: what this engine computes in inference mode, on every path of the default engine, the
+        block-scaled fp8 ones included.  Fresh optimizer slots."""
+        if self.batchnorm is None:
+            raise ValueError("folded() needs a batchnorm engine")
+        names = {t.name: t for t in self.tensors}
+        params = {n: self.view(t, self.param) for n, t in names.items()}
+        out = fold_batchnorm_params(self.graph, params, (self.bn_running_mean, self.bn_running_var), self.batchnorm.eps)
+        eng = ResNet50SSDEngine(classes=self.classes, in_size=self.in_size, device=self.device)
+        for t in eng.tensors:
+            eng.view(t, eng.param).copy_(out[t.name])
+        eng.refresh_weights(cast=True)
+        return eng
