@@ -198,22 +198,23 @@ __global__ __launch_bounds__((BM / (16 * PT)) * (BN >= 128 ? BN / 64 : 2) * 64) 
 
     int nks = (g.nchunks + 7) >> 3;
     // stride-2 data gradient: only the taps whose parity matches the tile's class contribute; steps are addressed
-    // absolutely as (valid tap vt, sub-step) instead of incrementally
-    int vtaps = 0, nvt = 0;                     // 4 bits per valid tap index
+    // absolutely as (valid tap vt, sub-step) instead of incrementally.  The valid taps are rows th0, th0 + 2, .. by columns
+    // tw0, tw0 + 2, .. in tap order; KH, KW <= 8 (make_geom), so at most 4 x 4 of them: 2 bits of row and of column each.
+    unsigned vrow = 0, vcol = 0;
+    int nvt = 0;
+    const int th0 = (g.pad_t - cls_py) & 1, tw0 = (g.pad_l - cls_px) & 1;
     const int spt = g.cpt >> 3;                 // k-steps per tap (s2 only)
     if (g.s2) {
-        for (int t = 0; t < g.KH * g.KW; ++t) {
-            const int th = t / g.KW, tw = t - th * g.KW;
-            if ((((cls_py - g.pad_t + th) | (cls_px - g.pad_l + tw)) & 1) == 0) { vtaps |= t << (4 * nvt); ++nvt; }
-        }
+        for (int a = 0; th0 + 2 * a < g.KH; ++a)
+            for (int b = 0; tw0 + 2 * b < g.KW; ++b) { vrow |= (unsigned)a << (2 * nvt); vcol |= (unsigned)b << (2 * nvt); ++nvt; }
         nks = nvt * spt;
     }
     auto set_step = [&](int step) {             // s2: position the k state on valid step `step`
         const int vt = step / spt, sub = step - vt * spt;
-        const int t = (vtaps >> (4 * vt)) & 15;
-        kh = t / g.KW; kw = t - kh * g.KW;
+        kh = th0 + 2 * (int)((vrow >> (2 * vt)) & 3);
+        kw = tw0 + 2 * (int)((vcol >> (2 * vt)) & 3);
         cc = sub * 8 + slot;
-        q = t * g.cpt + cc;
+        q = (kh * g.KW + kw) * g.cpt + cc;
     };
     // split-K: this workgroup covers k-steps [ks0, ks1)
     int ks0 = 0, ks1 = nks;

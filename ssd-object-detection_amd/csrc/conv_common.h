@@ -674,7 +674,7 @@ inline ConvGeom make_geom(int B, int H, int W, int C, int Ho, int Wo, int N, int
     g.dma32 = ((long long)B * H * W * C < (1ll << 31) - 16 && (long long)N * g.ldw < (1ll << 31) - 16) ? 1 : 0;
     g.s2 = 0;
     const int s2on = ssd_knob("SSD_DGRAD_S2", 1);
-    if (div == 2 && s2on && g.cpt % 8 == 0) {
+    if (div == 2 && s2on && g.cpt % 8 == 0 && KH <= 8 && KW <= 8) {      // (the kernel lists at most 4 x 4 taps per class)
         g.s2 = 1;
         for (int p = 0; p < 2; ++p) { g.cls_h[p] = (Ho + 1 - p) / 2; g.cls_w[p] = (Wo + 1 - p) / 2; }
         for (int c = 0; c < 4; ++c) g.cls_n[c] = B * g.cls_h[c >> 1] * g.cls_w[c & 1];

@@ -1,4 +1,5 @@
-"""Convolution test shapes shared by tests/test_conv_gpu.py (numerics vs the fp32 reference, -m gpu) and
+"""Convolution test shapes shared by tests/test_conv_gpu.py (numerics vs the fp32 reference, -m gpu),
+tests/test_conv_strict_gpu.py (exact operands in a guarded arena, -m gpu), tests/test_strict_cpu.py (their regime, CPU) and
 tests/test_conv_plan_cpu.py (dispatch coverage, CPU).  Every case names the kernels it is there to test -- (forward,
 data gradient, weight gradient) as the library's dispatch query reports them (ssd_conv2d_*_plan: the dispatch code
 itself with launching switched off, a host function, so it runs without a GPU).  Both test files assert the names."""
@@ -86,6 +87,46 @@ FULL_SIZE_CASES = [
     (64, 10, 10, 128, 256, 3, 2, "same", (DMA % "128,128" + "+splitk", DMA % "128,128" + "+s2", "k_conv_wgrad")),       # conv18
     (64, 5, 5, 128, 256, 3, 1, "valid", (DMA % "128,128" + "+splitk", DMA % "128,128" + "+splitk", "k_conv_wgrad")),    # conv20
     (64, 5, 5, 256, 510, 3, 1, "same", (DMA % "128,128" + "+splitk", DMA % "128,128" + "+splitk", "k_conv_wgrad")),     # head 3 (510 filters, 512 padded)
+]
+
+# The regimes of the ResNet-50 SSD512 trunk (resnet_engine.resnet50_ssd512_graph) that the VGG-style lists above never enter:
+#   R1 the 7x7 stride-2 stem (Cin = 8: ldw = 392, 49 one-tap k-chunks; SAME pads 2/3 at even sizes, 3/3 at odd ones);
+#   R2 1x1 stride 2 (the projection shortcuts): a data gradient by parity classes of which three have no tap at all, so three
+#      quarters of dx are exact zeros (the masked base under accumulate);
+#   R3 k_conv_igemm_8ph with a k loop of one or two k-tiles (1x1 with 64 / 128 channels on the K side);
+#   R4 k_conv3x3_p512 in plain block mode (one 32-row block per image: conv4_x's 3x3 layers at 32x32);
+#   R5 data-gradient tiles no other case names: <256,64> without parity classes, <256,128>+s2;
+#   R6 the extras' maps of 4x4, 2x2 and 1x1 (M of 3 to 12 rows in a 128-row tile, parity classes of one pixel or none).
+# The first ten are small (about 1 MB of operands).  The others are one image on a map just large enough for the plan, with
+# few channels so that the operands stay small: not the workload's shapes, but its kernels and its k loops.
+RESNET_CASES = [
+    (2, 37, 37, 8, 64, 7, 2, "same", (DMA % "128,64", DMA % "128,64" + "+s2", "k_conv_wgrad")),             # R1 the stem at an odd size: pad 3/3; ktot = 392 leaves the weight gradient a ragged last column tile
+    (2, 32, 32, 8, 64, 7, 2, "same", (DMA % "128,64", DMA % "128,64" + "+s2", "k_conv_wgrad")),             # R1 the stem at an even size (as 512, 256): pad 2/3
+    (3, 17, 17, 64, 128, 1, 2, "same", (DMA % "128,128", DMA % "128,64" + "+s2", "k_conv_wgrad")),          # R2 a projection shortcut, odd size (17 -> 9): the last row and column are read
+    (2, 18, 18, 128, 256, 1, 2, "same", (DMA % "128,128", DMA % "128,128" + "+s2", "k_conv_wgrad")),        # R2 conv3_x's projection (256 -> 512 there), even size: the last row and column are never read
+    (2, 18, 17, 64, 72, 1, 2, "same", (DMA % "128,128", DMA % "128,64", "k_conv_wgrad")),                   # R2 1x1 stride 2 without parity classes (72 % 64 != 0), non-square
+    (2, 16, 16, 64, 256, 1, 1, "same", (DMA % "128,128", DMA % "128,64", "k_conv_wgrad")),                  # R3's k loop on the LDS-DMA kernel: conv2_x's 1x1 expand (64 -> 256), K = 64 is ONE k-step
+    (3, 4, 4, 128, 256, 3, 2, "same", (DMA % "128,128" + "+splitk", DMA % "128,128" + "+s2", "k_conv_wgrad")),   # R6 extras 4x4 -> 2x2, pad (0,1): M = 12
+    (3, 2, 2, 128, 256, 3, 2, "same", (DMA % "128,128" + "+splitk", DMA % "128,128" + "+s2", "k_conv_wgrad")),   # R6 extras 2x2 -> 1x1: M = 3, parity classes of one pixel
+    (3, 1, 1, 256, 128, 1, 1, "same", (DMA % "128,128", DMA % "128,128", "k_conv_wgrad")),                  # R6 a 1x1 reduce on a 1x1 map (the bottleneck in front of a head-only level)
+    (2, 32, 32, 256, 256, 3, 1, "same", (P512, P512, WP16)),                                                # R4 conv4_x's 3x3 at 32x32: one 32-row block per image, forward and data gradient
+    (1, 151, 151, 64, 1024, 1, 1, "same", ("k_conv_igemm_8ph", DMA % "128,64", "k_conv_wgrad+rwide")),      # R3 conv2_x's expand forward on the 8-phase kernel: one k-tile
+    (1, 301, 301, 128, 1024, 1, 2, "same", ("k_conv_igemm_8ph", DMA % "128,128" + "+s2", "k_conv_wgrad+rwide")),   # R3 + R2 a projection forward on the 8-phase kernel: stride 2, two k-tiles
+    (1, 151, 151, 1024, 64, 1, 1, "same", (DMA % "128,64", "k_conv_igemm_8ph", "k_conv_wgrad+rwide")),      # R3 the data gradient of a 1x1 reduce to 64 channels on the 8-phase kernel: one k-tile
+    (1, 314, 314, 8, 64, 7, 2, "same", (DMA % "128,64", DMA % "256,64" + "+s2", "k_conv_wgrad+rwide")),     # R1 the stem, many tiles; data gradient on 256-row tiles by parity classes
+    (1, 314, 314, 64, 64, 1, 1, "same", (DMA % "256,64", DMA % "256,64", "k_conv_wgrad+rwide")),            # R5 conv2_x's 1x1 reduce at batch >= 8: <256,64> forward and data gradient
+    (1, 314, 314, 128, 64, 1, 2, "same", (DMA % "128,64", DMA % "256,128" + "+s2", "k_conv_wgrad+rwide")),  # R5 + R2 <256,128>+s2 with a single tap
+    (1, 300, 300, 256, 64, 1, 2, "same", (DMA % "128,64", DMA % "256,256" + "+s2", "k_conv_wgrad+rwide")),  # R2 a projection's data gradient at batch >= 8: <256,256>+s2 with a single tap
+    # Kernels the cases above name, at a (kernel size, stride) under which only the ResNet runs them: the k loop's tap stepping and
+    # the row gather depend on both, so tests/test_conv_plan_cpu.py compares (pass, kernel, kernel size, stride) of every trunk layer
+    (1, 628, 628, 8, 64, 7, 2, "same", (DMA % "256,64", DMA % "256,64" + "+s2", "k_conv_wgrad+rwide")),     # R1 the stem's forward as input 512 runs it from batch 2 on: 256-row tiles (>= 384 of them)
+    (2, 8, 8, 128, 512, 1, 1, "same", (DMA % "128,128", DMA % "128,128" + "+splitk", "k_conv_wgrad")),      # conv3_x's expand (128 -> 512): a 1x1 data gradient split over K = 512
+    (1, 314, 314, 128, 128, 3, 2, "same", (DMA % "128,128", DMA % "256,128" + "+s2", "k_conv_wgrad+rwide")),   # conv3_x's strided 3x3 at batch >= 8: forward without split-K, <256,128>+s2 with 3x3 taps, wide reduction
+    (2, 16, 16, 512, 1024, 1, 2, "same", (DMA % "128,128" + "+splitk", DMA % "128,128" + "+s2", "k_conv_wgrad")),   # conv4_x's projection at batch 1, 2: a strided 1x1 forward split over K
+    (1, 314, 314, 64, 512, 1, 2, "same", (DMA % "256,128", DMA % "256,64" + "+s2", "k_conv_wgrad+rwide")),  # a projection's forward at batch >= 8: <256,128>, strided 1x1
+    (1, 314, 314, 64, 512, 3, 2, "same", (DMA % "256,128", DMA % "256,64" + "+s2", "k_conv_wgrad_tile+rwide")),   # conv3_x's strided 3x3 at batch 32: <256,128> forward
+    (1, 128, 128, 256, 512, 1, 2, "same", (DMA % "128,128", DMA % "128,128" + "+s2", "k_conv_wgrad_tile")),   # conv3_x's projection: the 256x256 weight-gradient GEMM gathering every second pixel
+    (2, 128, 128, 256, 512, 1, 2, "same", (DMA % "128,128", DMA % "128,128" + "+s2", "k_conv_wgrad_tile+rwide")),   # the same with >= 32 splits
 ]
 
 # tests/test_conv_gpu.py::test_first_layer_kernels_full_size (forward + weight gradient of the image layer at 300x300)

@@ -29,7 +29,7 @@ def ref_conv(x, w, bias, k, stride, pad_t, pad_l, Ho, Wo, relu):
     return y.permute(0, 2, 3, 1).contiguous()
 
 
-from tests.conv_cases import CASES, FIRST_LAYER_CASE, FULL_SIZE_CASES, plan_names          # noqa: E402  (shared with the CPU coverage test)
+from tests.conv_cases import CASES, FIRST_LAYER_CASE, FULL_SIZE_CASES, RESNET_CASES, plan_names          # noqa: E402  (shared with the CPU coverage test)
 
 
 def geometry(ops, H, W, k, stride, mode):
@@ -43,6 +43,17 @@ def geometry(ops, H, W, k, stride, mode):
 
 @pytest.mark.parametrize("case", CASES, ids=[str(c[:8]) for c in CASES])
 def test_conv_fwd_bwd(ops, case):
+    run_fwd_bwd(ops, case)
+
+
+@pytest.mark.parametrize("case", RESNET_CASES, ids=[str(c[:8]) for c in RESNET_CASES])
+def test_conv_fwd_bwd_resnet_shapes(ops, case):
+    """The ResNet-50 SSD512 trunk's regimes (tests/conv_cases.py) on real-valued operands: what the exact integer operands of
+    tests/test_conv_strict_gpu.py cannot show -- a wrong rounding, a lost low-order term -- under test_conv_fwd_bwd's bounds."""
+    run_fwd_bwd(ops, case)
+
+
+def run_fwd_bwd(ops, case):
     B, H, W, Cin, Cout, k, stride, mode = case[:8]
     assert plan_names(case[:8]) == case[8], "the dispatch rules moved: this case no longer tests the kernels it names"
     Ho, pt = geometry(ops, H, H, k, stride, mode)[0], geometry(ops, H, H, k, stride, mode)[2]

@@ -4,10 +4,12 @@ without a GPU:
   * every (forward, data-gradient, weight-gradient) kernel the batch-64 SSD300 train step launches is reached by at
     least one oracle-compared case of tests/test_conv_gpu.py (tests/conv_cases.py), so no kernel of the benchmarked
     step runs unchecked;
+  * every (pass, kernel, kernel size, stride) the ResNet-50 SSD512 trunk's convolutions run at input 512 and 256, batch 1
+    to 32, is reached by a case of the strict and the oracle-compared tests (RESNET_CASES were written from this walk);
   * every case still names the kernels it was written for (the GPU tests assert the same before computing)."""
 import pytest
 
-from tests.conv_cases import CASES, FIRST_LAYER_CASE, FULL_SIZE_CASES, WS_BYTES, _geom, plan_name, plan_names
+from tests.conv_cases import CASES, FIRST_LAYER_CASE, FULL_SIZE_CASES, RESNET_CASES, WS_BYTES, _geom, plan_name, plan_names
 
 
 def _network_plans(B):
@@ -35,8 +37,58 @@ def _network_plans(B):
 
 
 def test_cases_name_the_kernels_they_reach():
-    for case in CASES + FULL_SIZE_CASES + [FIRST_LAYER_CASE]:
+    for case in CASES + FULL_SIZE_CASES + RESNET_CASES + [FIRST_LAYER_CASE]:
         assert plan_names(case[:8]) == case[8], case[:8]
+
+
+def _resnet_plans(in_size, B):
+    """(node, pass, kernel name, (kernel size, stride)) of every convolution of the ResNet-50 SSD512 trunk as
+    ResNet50SSDEngine calls the library: forward and weight gradient of each, the data gradient of each but the stem,
+    accumulating where a later node (processed earlier by backward) has already written the same map's gradient."""
+    from ssd_object_detection_amd import _lib
+    from ssd_object_detection_amd.resnet_engine import resnet50_ssd512_graph
+    L, g = _lib.lib(), resnet50_ssd512_graph()
+    size, out = {-1: in_size}, []
+    for i, nd in enumerate(g):
+        src = nd["src"][0] if nd["op"] == "add" else nd["src"]
+        h = size[src]
+        if nd["op"] not in ("conv", "pool3"):
+            size[i] = h
+            continue
+        ho, _, pt, _ = _geom(h, h, nd["k"], nd["stride"], "same")
+        size[i] = ho
+        if nd["op"] != "conv":
+            continue
+        cin, cout, k, s = nd["cin"], nd["cout"], nd["k"], nd["stride"]
+        assert cout % 8 == 0
+        out.append((i, 0, plan_name(L, L.ssd_conv2d_fwd_plan(B, h, h, cin, cout, k, s, pt, pt, ho, ho, 0, WS_BYTES)), (k, s)))
+        if src >= 0:
+            acc = any(j > i and (src in n["src"] if n["op"] == "add" else n["src"] == src) for j, n in enumerate(g))
+            out.append((i, 1, plan_name(L, L.ssd_conv2d_bwd_data_plan(B, h, h, cin, cout, k, s, pt, pt, ho, ho, int(acc), WS_BYTES)), (k, s)))
+        out.append((i, 2, plan_name(L, L.ssd_conv2d_bwd_weight_plan(B, h, h, cin, cout, cout, k, s, pt, pt, ho, ho)), (k, s)))
+    return out
+
+
+@pytest.mark.parametrize("in_size", [512, 256])
+def test_every_kernel_of_the_resnet_trunk_has_a_strict_case(in_size):
+    """Every (pass, kernel name with its flags) the trunk's convolutions resolve to at batch 1 .. 32 is named, for the same
+    pass, with the same flags and at the same kernel size and stride, by a case that tests/test_conv_strict_gpu.py and
+    tests/test_conv_gpu.py run.  A dispatch change that sends a ResNet layer to a kernel (or a mode of one) no case reaches
+    fails here, on the CPU.  (Kernel size and stride belong to the key: the parity-class data gradient was right at 3x3 and
+    1x1 and wrong at 7x7.)"""
+    tested = [set(), set(), set()]
+    for case in CASES + FULL_SIZE_CASES + RESNET_CASES:
+        for p in range(3):
+            tested[p].add((case[8][p], case[5], case[6]))
+    nconv = 0
+    for B in (1, 2, 4, 8, 16, 32):
+        plans = _resnet_plans(in_size, B)
+        nconv = len({i for i, _, _, _ in plans})
+        for i, p, name, ks in plans:
+            assert not name.startswith("error"), (i, B, name)
+            assert (name,) + ks in tested[p], "node %d at input %d, batch %d: the %s runs %s at k = %d, stride %d, which no case names" % (
+                (i, in_size, B, ("forward", "data gradient", "weight gradient")[p], name) + ks)
+    assert nconv == 53                                       # the stem, 39 bottleneck convolutions, 3 projections, 10 extras
 
 
 @pytest.mark.parametrize("B", [64, 32, 4])

@@ -13,7 +13,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import strict                                                                         # noqa: E402
-from tests.conv_cases import CASES, FULL_SIZE_CASES, WS_BYTES, plan_name, plan_names             # noqa: E402
+from tests.conv_cases import CASES, FULL_SIZE_CASES, RESNET_CASES, WS_BYTES, plan_name, plan_names   # noqa: E402
 
 BF, F32, U8, I32 = torch.bfloat16, torch.float32, torch.uint8, torch.int32
 
@@ -108,6 +108,31 @@ def test_conv_strict_large_problem_kernels(ops, L, case):
     case = (B,) + tuple(case[1:])
     assert plan_names(case[:8]) == case[8]
     run_conv_case(ops, L, case)
+
+
+@pytest.mark.parametrize("case", RESNET_CASES, ids=[str(c[:8]) for c in RESNET_CASES])
+def test_conv_strict_resnet_shapes(ops, L, case):
+    """The regimes of the ResNet-50 SSD512 trunk (tests/conv_cases.py: the 7x7 stem, 1x1 stride 2, one- and two-tile k loops
+    of the 8-phase kernel, the 512-pixel kernel in plain block mode, the extras' 4x4 .. 1x1 maps).  The engine never asks for
+    the stem's data gradient; the entry point documents no limit on the kernel size, so it is run here all the same.  A case
+    whose data gradient the library refuses names the refusal ("error -2": SSD_ERR_VALUE, a bad argument, before any launch)
+    where the others name a kernel; the call must then raise and write nothing."""
+    assert plan_names(case[:8]) == case[8], "the dispatch rules moved: this case no longer tests the kernels it names"
+    refused = case[8][1].startswith("error")
+    run_conv_case(ops, L, case, dgrad=not refused)
+    if refused:
+        from ssd_object_detection_amd._lib import SSD_ERR_VALUE
+        assert case[8][1] == "error %d" % SSD_ERR_VALUE
+        B, H, W, Cin, Cout, k, stride, mode = case[:8]
+        r = strict.conv_reference(case)
+        a = arena_for(r, 2 * WS_BYTES)
+        dyp, w_t, ws = a.put(r["dy_pad"], "dy"), a.put(r["w_t"], "w_t"), a.workspace()
+        dx = a.out((B, H, W, Cin), BF, "dx")
+
+        def call():
+            with pytest.raises(ValueError):
+                ops.conv2d_bwd_data(dyp, w_t, None, (B, H, W, Cin), stride, r["geom"][2], r["geom"][3], out=dx, ws=ws)
+        a.run(call, [])
 
 
 @pytest.mark.parametrize("shape", [0, 1, 2])
@@ -252,10 +277,22 @@ def test_bwd_weight_batched_strict(ops, L):
 
 
 # ---------------------------------------------------------------- heads
-@pytest.mark.parametrize("shape", [(2, 5, 5, 64, 6, 1), (2, 19, 19, 256, 4, 1), (2, 19, 19, 1024, 6, 1), (3, 19, 19, 256, 6, 2)], ids=str)
+# the heads of the ResNet-50 SSD512's small maps (1x1, 2x2, 4x4: M = 2 .. 32 rows of a 128-row tile), of its 16x16 map, and a
+# head wide and tall enough for the generic kernel WITHOUT split-K (>= 160 tiles of 128x128; 340 filters: EPI_HEAD's scattered
+# epilogue over three channel tiles, the last one ragged), with the kernel each must reach
+RESNET_HEADS = {(2, 1, 1, 256, 4, 1): "k_conv_igemm_dma<128,128>+splitk", (2, 2, 2, 256, 4, 1): "k_conv_igemm_dma<128,128>+splitk",
+                (2, 4, 4, 256, 6, 1): "k_conv_igemm_dma<128,128>+splitk", (2, 16, 16, 512, 6, 1): "k_conv3x3_patch32<128>+flat",
+                (2, 60, 58, 64, 4, 1): "k_conv_igemm_dma<128,128>"}
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 5, 64, 6, 1), (2, 19, 19, 256, 4, 1), (2, 19, 19, 1024, 6, 1), (3, 19, 19, 256, 6, 2)]
+                         + list(RESNET_HEADS), ids=str)
 def test_head_fwd_and_grad_pack_strict(ops, L, shape):
-    """the three shapes of test_head_fwd_layout, and SSD_CONV_P512=2 at the smallest map of its head test"""
+    """the three shapes of test_head_fwd_layout, SSD_CONV_P512=2 at the smallest map of its head test, and RESNET_HEADS"""
     B, H, W, Cin, n, p512 = shape
+    if shape in RESNET_HEADS:
+        assert plan_name(L, L.ssd_conv2d_head_fwd_plan(B, H, W, Cin, n, 81, WS_BYTES)) == RESNET_HEADS[shape], \
+            "the dispatch rules moved: this head no longer tests the kernel it names"
     r = strict.head_case(B, H, W, Cin, n)
     strict.check_regime(r)
     C, off, npad, A = r["classes"], r["off"], r["npad"], r["loc"].shape[1]

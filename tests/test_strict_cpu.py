@@ -8,7 +8,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import strict                                                              # noqa: E402
-from tests.conv_cases import CASES, FULL_SIZE_CASES                                   # noqa: E402
+from tests.conv_cases import CASES, FULL_SIZE_CASES, RESNET_CASES                     # noqa: E402
 
 
 # ---------------------------------------------------------------- the regime
@@ -27,6 +27,34 @@ def test_full_size_case_regime(case):
     print("batch used for %s: %d" % (str(case[:8]), B))
     case = (B,) + tuple(case[1:])
     strict.check_conv_regime(case, strict.conv_reference(case))
+
+
+@pytest.mark.parametrize("case", RESNET_CASES, ids=[str(c[:8]) for c in RESNET_CASES])
+def test_resnet_case_regime(case):
+    """as test_conv_case_regime; fp32 == float64 where no tensor of the case has 4M elements (the one-image cases on large maps
+    are in the regime by the same conditions, which do not depend on the map's size)"""
+    r = strict.conv_reference(case)
+    strict.check_conv_regime(case, r)
+    if max(r["x"].numel(), r["y"].numel()) < 1 << 22:
+        r64 = strict.conv_reference(case, dtype=torch.float64)
+        for name in ("y", "y_relu", "dx", "dx_acc", "dw", "dbias"):
+            assert torch.equal(r[name].double(), r64[name]), name
+    if case[5] == 1 and case[6] == 2:
+        # 1x1 stride 2: only the pixels (2i, 2j) have a tap, so about three quarters of dx are exact zeros
+        B, H, W = case[:3]
+        zeros = float((r["dx"] == 0).float().mean())
+        assert zeros >= 1 - (-(-H // 2) * -(-W // 2)) / (H * W), zeros
+        assert bool((r["dx"][:, 1::2] == 0).all()) and bool((r["dx"][:, :, 1::2] == 0).all())
+        assert bool((r["dx_acc"][:, 1::2] != 0).any()), "the masked base must show where no tap reaches"
+
+
+RESNET_HEADS = [(2, 1, 1, 256, 4), (2, 2, 2, 256, 4), (2, 4, 4, 256, 6), (2, 16, 16, 512, 6), (2, 60, 58, 64, 4)]
+
+
+@pytest.mark.parametrize("shape", RESNET_HEADS, ids=str)
+def test_resnet_head_regime(shape):
+    """the head shapes tests/test_conv_strict_gpu.py::test_head_fwd_and_grad_pack_strict adds for the ResNet-50 SSD512"""
+    strict.check_regime(strict.head_case(*shape))
 
 
 @pytest.mark.parametrize("name", sorted(strict.EXTRAS), ids=str)
@@ -205,8 +233,72 @@ def test_arena_reports_an_output_the_call_does_not_list():
     check_reported(a, bad, [(y, x.clone() * 2)], "z was written although the call does not list it")
 
 
+# ---------------------------------------------------------------- seeded faults of the ResNet regimes (torch restatements)
+def conv_fault_arena(case):
+    r = strict.conv_reference(case)
+    strict.check_conv_regime(case, r)
+    B, H, W, Cin, Cout = case[:5]
+    Ho, Wo = r["geom"][:2]
+    a = strict.Arena("cpu", 64 << 20)
+    t = dict(y=a.out((B, Ho, Wo, Cout), torch.bfloat16, "y"), dx=a.out((B, H, W, Cin), torch.bfloat16, "dx"),
+             acc=a.inout(r["base"], "dx (accumulated onto)"))
+    return r, a, t
+
+
+def test_arena_reports_a_strided_1x1_data_gradient_that_skips_the_classes_without_a_tap():
+    """1x1 stride 2: of the four parity classes of dx only (even, even) has a tap; a kernel that returns from a class whose k
+    loop is empty leaves three quarters of dx unwritten"""
+    case = (3, 17, 17, 64, 128, 1, 2, "same")
+    r, a, t = conv_fault_arena(case)
+    want = r["dx"].to(torch.bfloat16)
+
+    def good():
+        t["dx"].zero_()
+        t["dx"][:, ::2, ::2] = want[:, ::2, ::2]
+
+    def bad():
+        t["dx"][:, ::2, ::2] = want[:, ::2, ::2]
+    a.run(good, [(t["dx"], want)])
+    untouched = want.numel() - want[:, ::2, ::2].numel()
+    check_reported(a, bad, [(t["dx"], want)], r"dx differs from the reference: %d of %d elements differ, first at \(0, 0, 1, 0\)"
+                   % (untouched, want.numel()))
+
+
+def test_arena_reports_a_strided_1x1_data_gradient_that_zeroes_the_base_it_accumulates_onto():
+    """the same under accumulate with a ReLU mask: a class without a tap must hold the masked base, not 0"""
+    case = (2, 18, 18, 128, 256, 1, 2, "same")
+    r, a, t = conv_fault_arena(case)
+    want = r["dx_acc"].to(torch.bfloat16)
+    keep = r["mask_src"].float() > 0
+
+    def good():
+        dx = torch.zeros_like(r["dx"])
+        dx[:, ::2, ::2] = r["dx"][:, ::2, ::2]
+        t["acc"].copy_(strict.masked(dx + t["acc"].float(), keep))
+
+    def bad():
+        out = strict.masked(r["dx"] + t["acc"].float(), keep)
+        t["acc"].zero_()                                       # the classes without a tap: "no gradient" stored as 0
+        t["acc"][:, ::2, ::2] = out[:, ::2, ::2].to(torch.bfloat16)
+    a.run(good, [(t["acc"], want)])
+    check_reported(a, bad, [(t["acc"], want)], r"dx \(accumulated onto\) differs from the reference")
+
+
+def test_arena_reports_a_7x7_stem_padded_3_3_where_same_gives_2_3():
+    """7x7 stride 2 at an even size: SAME pads 5 in all, 2 before and 3 after; 3 before shifts every tap by one pixel"""
+    case = (2, 32, 32, 8, 64, 7, 2, "same")
+    r, a, t = conv_fault_arena(case)
+    Ho, Wo, pt, pl = r["geom"]
+    assert (pt, pl) == (2, 2) and strict.geometry(37, 37, 7, 2, "same")[2:] == (3, 3)
+
+    def conv(pad):
+        return lambda: t["y"].copy_(strict.ref_conv(r["x"].float(), r["w"].float(), r["bias"], 7, 2, pad, pad, Ho, Wo, False))
+    a.run(conv(2), [(t["y"], r["y"].to(torch.bfloat16))])
+    check_reported(a, conv(3), [(t["y"], r["y"].to(torch.bfloat16))], "y differs from the reference")
+
+
 # ---------------------------------------------------------------- the exact loss cases
-import numpy as np                                                                    # noqa: E402
+import numpy as np                                                                  # noqa: E402
 
 
 @pytest.mark.parametrize("name", sorted(strict.LOSS_CASES), ids=str)
