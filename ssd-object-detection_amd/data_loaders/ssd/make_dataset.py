@@ -1,7 +1,7 @@
 """SSDDataLoader with the reference's contract (data_loaders/ssd/make_dataset.py:15-74 of the reference):
 
-    SSDDataLoader(dataset_root, dataset="coco", shuffle=True, mini_batch=0)
-    .get_dataset() -> (train, val) iterables of (image f32[300,300,3] RGB in [0,1], cls f32[n], box f32[n,4])
+    SSDDataLoader(dataset_root, dataset="coco", shuffle=True, mini_batch=0, input_size=300)
+    .get_dataset() -> (train, val) iterables of (image f32[S,S,3] RGB in [0,1], S = input_size, cls f32[n], box f32[n,4])
                       with boxes (cx, cy, w, h) normalised to [0,1]
     .get_names_and_colors() -> (names, colors)
 
@@ -76,8 +76,12 @@ class RawSplit:
 
 
 class SSDDataLoader:
-    def __init__(self, dataset_root, dataset="coco", shuffle=True, mini_batch=0):
-        self._train_resize = (300, 300)
+    def __init__(self, dataset_root, dataset="coco", shuffle=True, mini_batch=0, input_size=300):
+        """input_size: the network's input (300: the reference's; 512 or 256 for the ResNet-50 SSD512 network).  The synthetic
+        splits produce images of that size; reader-contract splits are resized on the device to the model's own input."""
+        if isinstance(input_size, bool) or not isinstance(input_size, (int, np.integer)) or input_size < 1:
+            raise ValueError("input_size must be a positive integer, not %r" % (input_size,))
+        self._train_resize = (int(input_size), int(input_size))
         if not isinstance(dataset, str):                                 # a reader object: the _coco2ssd seam
             if not hasattr(dataset, "get_dataset"):
                 raise ValueError

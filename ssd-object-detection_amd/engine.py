@@ -530,6 +530,13 @@ class _BackwardPass:
 
 
 class SSDEngine:
+    # backward() takes the per-bucket optimizer schedule (fused_adam / on_dgrad); an engine without it is stepped by
+    # backward -> clip_scales -> one optimizer launch over the flat buffer
+    bucket_optimizer = True
+    # backward() spreads its work over side streams (weight gradients, heads, optimizer buckets) around the data-gradient
+    # chain on the caller's stream: what a high-priority stream for that chain is good for
+    side_streams = True
+
     def __init__(self, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, device="cuda",
                  seed=0, sparse_heads=None, l2norm=None):
         """l2norm: the SSD paper's L2 normalisation of feature map 0 in front of its head (ops.L2NormSpec.of: None / False = off,

@@ -76,10 +76,21 @@ class SSDObjectDetectionModel:
             self.classes = classes + 1               # background is the LAST class index
             self.thresh = 0.5
 
-    def __init__(self, classes, log_dir, device="cuda", seed=0, distributed=False, timestamp_dir=True, l2norm=None):
+    def __init__(self, classes, log_dir, device="cuda", seed=0, distributed=False, timestamp_dir=True, l2norm=None,
+                 network=None):
         """l2norm: the SSD paper's L2 normalisation of the 38x38 feature map in front of its head, with a learned per-channel
         scale (ops.L2NormSpec.of: None / False = off as in the reference, True = the paper's initial scale 20, a number, a dict
-        or a spec).  The scale is one more variable of the engine: trained, clipped, saved and loaded like the others."""
+        or a spec).  The scale is one more variable of the engine: trained, clipped, saved and loaded like the others.
+
+        network (ops.NetworkSpec.of: None / "ssd300" = the reference's network, as without the argument; "resnet50_ssd512", a
+        dict or a spec): the ResNet-50 SSD512 network (resnet_engine.ResNet50SSDEngine) at a 512 or 256 input, optionally with
+        live batch normalisation or an MX-fp8 training forward.  Its step is backward -> clip -> one optimizer launch over the
+        flat buffer (the engine has no per-bucket schedule); everything else -- targets, both losses, the three optimizers,
+        split_batch, data parallelism, validation, checkpoints, the scalar log -- is the same code.  With split_batch a
+        batchnorm network normalises each micro-batch with that micro-batch's statistics and updates its running statistics
+        once per micro-batch; under data parallelism every rank normalises with its own batch (no synchronised batch norm).
+        ValueError for l2norm together with the ResNet."""
+        self.network = ops.NetworkSpec.of(network, l2norm=l2norm)
         self.distributed = bool(distributed)
         if timestamp_dir:
             stamp = [time.strftime("%Y-%m-%d-%H%M%S", time.localtime())]
@@ -88,10 +99,29 @@ class SSDObjectDetectionModel:
             log_dir = os.path.join(log_dir, stamp[0])
         self.cfg = SSDObjectDetectionModel.Config(classes, log_dir)
         self.device = torch.device(device)
-        self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed,
-                                 l2norm=l2norm)
-        self._pset = ops.build_priors(grids=self._engine.grids, device=device)
+        net = self.network
+        if net.kind == "ssd300":
+            self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed,
+                                     l2norm=l2norm)
+            self._pset = ops.build_priors(grids=self._engine.grids, device=device)
+            self._forward_train = self._engine.forward
+            self._backward_args = {}
+        else:
+            from ..resnet_engine import ResNet50SSDEngine
+            self.cfg.input_shape = (net.in_size, net.in_size, 3)
+            self._engine = eng = ResNet50SSDEngine(classes=self.cfg.classes, in_size=net.in_size, device=device, seed=seed,
+                                                   batchnorm=net.batchnorm)
+            self._pset = ops.build_priors(grids=eng.grids, s_ref=ops.ssd512_s_ref(net.in_size), ratios=ops.SSD512_RATIOS,
+                                          in_size=net.in_size, device=device)
+            # train=True: a batchnorm engine uses (and saves) batch statistics, an fp8 forward writes the maps backward() reads
+            self._forward_train = lambda x: eng.forward(x, net.precision, train=True)
+            self._backward_args = dict(dgrad_precision=net.dgrad_precision)
         assert self._pset.A == self._engine.A
+        # bumped by every training forward (running statistics), every optimizer launch and load(): what a cached inference
+        # engine (the folded fp8 one of a batchnorm network) was made from
+        self._version = 0
+        self._folded = None                          # (version, engine.folded())
+        self.folds_built = 0
         self._prior_box = None
         self._comm_stream = None
         self._slot_owner = None                      # optimizer object whose Adam moments the engine holds
@@ -103,7 +133,10 @@ class SSDObjectDetectionModel:
         # the step's main chain (forward, loss, data gradients) runs on a HIGH-priority stream: its kernels are the critical
         # path, the weight gradients / optimizer on the engine's side stream fill in around them (measured: -0.04 ms per step;
         # the other way round, side stream high, +0.13 ms)
-        self.high_priority_main = os.environ.get("SSD_MAIN_PRIO", "-1") == "-1"
+        # An engine that walks its network on ONE stream (side_streams False: the ResNet) has nothing to fill in: there the
+        # priority stream only costs its two hand-overs per step (measured at batch 16, input 512: +0.14 ms, +0.33 ms with
+        # batchnorm), so its step stays on the caller's stream
+        self.high_priority_main = os.environ.get("SSD_MAIN_PRIO", "-1") == "-1" and self._engine.side_streams
         self._main_hi = None
 
     # ------------------------------------------------------------------ accessors
@@ -316,7 +349,7 @@ class SSDObjectDetectionModel:
         decay = None
         if momentum and ssd_optimizer.weight_decay > 0.0:
             decay = eng.decay_table(ssd_optimizer.weight_decay, ssd_optimizer.decay_bias)
-        per_bucket = (isinstance(ssd_optimizer, _opt.Adam) or momentum) and self.fused_optimizer
+        per_bucket = (isinstance(ssd_optimizer, _opt.Adam) or momentum) and self.fused_optimizer and eng.bucket_optimizer
         fused = single and per_bucket
         fused_dp = overlap and per_bucket
         if fused_dp:
@@ -336,7 +369,8 @@ class SSDObjectDetectionModel:
                 x = image[i:i + batch_step]
             else:
                 x = ops.image_prep(image[i:i + batch_step].contiguous(), normalize=False)
-            pred_loc, pred_conf = eng.forward(x)
+            pred_loc, pred_conf = self._forward_train(x)
+            self._version += 1
             if self._targets_event is not None:        # targets assigned on the side stream (match_async)
                 torch.cuda.current_stream().wait_event(self._targets_event)
                 self._targets_event = None
@@ -362,16 +396,17 @@ class SSDObjectDetectionModel:
                     gates = eng.bucket_gates(self._reducer.buckets)
                 self._reducer.begin(post, gates)
                 eng.backward(info["dloc"], info["dconf"], on_ready=self._reducer.tensor_ready, heads=info["heads"],
-                             on_dgrad=self._reducer.dgrad_done if fused_dp else None)
+                             on_dgrad=self._reducer.dgrad_done if fused_dp else None, **self._backward_args)
                 self._reducer.finish()                 # clipped per bucket, summed over ranks (RCCL over xGMI)
             elif fused:
                 eng.backward(info["dloc"], info["dconf"], fused_adam=fused_adam, heads=info["heads"])
             else:
-                eng.backward(info["dloc"], info["dconf"], heads=info["heads"])
+                eng.backward(info["dloc"], info["dconf"], heads=info["heads"], **self._backward_args)
                 eng.clip_scales(clip)                  # tf.clip_by_norm(x, 0.01) per tensor, reference :249
                 if not single:
                     eng.accumulate_clipped(first=(n_micro == 0))
             n_micro += 1
+        self._version += 1                             # the optimizer has run, or runs below
         if fused or fused_dp:
             ssd_optimizer.iterations += 1
             return self._finish_step(info, lr, pred_conf, pred_loc)
@@ -444,9 +479,12 @@ class SSDObjectDetectionModel:
         if world == 1:
             return
         eng = self._engine
-        sums = torch.stack([eng.param.double().sum(), eng.param.double().abs().sum(), eng.adam_m.double().abs().sum(),
-                            eng.adam_v.double().sum(), torch.tensor(float(eng.step_count), dtype=torch.float64,
-                                                                    device=eng.param.device)])
+        sums = [eng.param.double().sum(), eng.param.double().abs().sum(), eng.adam_m.double().abs().sum(),
+                eng.adam_v.double().sum(), torch.tensor(float(eng.step_count), dtype=torch.float64, device=eng.param.device)]
+        if getattr(eng, "batchnorm", None) is not None:       # the running statistics are state too (per rank afterwards)
+            sums += [eng.bn_running_mean.double().sum(), eng.bn_running_mean.double().abs().sum(),
+                     eng.bn_running_var.double().sum()]
+        sums = torch.stack(sums)
         lo, hi = sums.clone(), sums.clone()
         torch.distributed.all_reduce(lo, op=torch.distributed.ReduceOp.MIN)
         torch.distributed.all_reduce(hi, op=torch.distributed.ReduceOp.MAX)
@@ -542,9 +580,20 @@ class SSDObjectDetectionModel:
         return self._detect_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh, max_cand,
                                      precision)
 
+    def _forward_infer(self, x, precision):
+        """(loc, conf) of the inference forward: the engine's own (running statistics for a batchnorm network); "mxfp8" on a
+        batchnorm network runs the folded network (engine.folded(): fold_batchnorm_params of the current parameters and
+        running statistics), cached until a training forward, an optimizer launch or load() changes what it was made from."""
+        if precision == "mxfp8" and self.network.batchnorm is not None:
+            if self._folded is None or self._folded[0] != self._version:
+                self._folded = (self._version, self._engine.folded())
+                self.folds_built += 1
+            return self._folded[1].forward(x, "mxfp8")
+        return self._engine.forward(x, precision)
+
     def _detect_prepared(self, x, score_thresh, iou_thresh, max_cand=400, precision="bf16"):
         """detect() from the prepared network input bf16 [B,S,S,8]."""
-        loc, conf = self._engine.forward(x, precision)
+        loc, conf = self._forward_infer(x, precision)
         score, cls, box, cand = ops.score_decode(conf, loc, self._pset, score_thresh, float(self.cfg.input_shape[0]))
         keep = ops.nms(score, cls, box, cand, iou_thresh, max_cand)
         return score, cls, box, keep
@@ -559,7 +608,7 @@ class SSDObjectDetectionModel:
 
     def _detections_prepared(self, x, score_thresh, iou_thresh, max_cand=None, keep_top_k=200, precision="bf16"):
         """detections() from the prepared network input bf16 [B,S,S,8]."""
-        loc, conf = self._engine.forward(x, precision)
+        loc, conf = self._forward_infer(x, precision)
         return ops.detect_pairs(conf, loc, self._pset, score_thresh, iou_thresh, max_cand, keep_top_k,
                                 float(self.cfg.input_shape[0]))
 
@@ -717,6 +766,7 @@ class SSDObjectDetectionModel:
             if d:
                 os.makedirs(d, exist_ok=True)
             sd = self._engine.state_dict()
+            sd["network"] = self.network.as_dict()
             if extra:
                 sd["extra"] = dict(extra)
             torch.save(sd, path)
@@ -726,7 +776,12 @@ class SSDObjectDetectionModel:
 
     def load(self, path="model_weight.pt"):
         sd = torch.load(path, map_location="cpu", weights_only=True)     # tensors, lists, ints and strings only
+        theirs = ops.NetworkSpec.of(sd.get("network"))                   # a checkpoint without the key is an ssd300 one
+        if theirs.identity() != self.network.identity():
+            raise ValueError("checkpoint %s holds the network %s, this model is %s" % (path, theirs.describe(),
+                                                                                     self.network.describe()))
         self._engine.load_state_dict(sd)
+        self._version += 1
         self._slot_owner = _RESTORED
         logger.info("Model is loaded from %s", path)
         return sd.get("extra", {})

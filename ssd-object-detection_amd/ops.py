@@ -12,6 +12,15 @@ from . import _lib
 SSD300_GRIDS = ((38, 38), (19, 19), (10, 10), (5, 5), (3, 3), (1, 1))
 SSD300_S_REF = (21, 45, 99, 153, 207, 261, 315)
 SSD300_RATIOS = ((2,), (2, 3), (2, 3), (2, 3), (2,), (2,))
+# SSD512 geometry of the ResNet-50 network (resnet_engine.py; seven levels, 24 564 anchors at a 512 x 512 input).  The scales
+# are pixels of a 512 input: at input S they are S_REF * S / 512 (ssd512_s_ref)
+SSD512_S_REF = (20, 51, 133, 215, 297, 379, 461, 543)
+SSD512_RATIOS = ((2,), (2, 3), (2, 3), (2, 3), (2, 3), (2,), (2,))
+
+
+def ssd512_s_ref(in_size):
+    """SSD512_S_REF scaled to an input of in_size pixels."""
+    return tuple(v * in_size / 512.0 for v in SSD512_S_REF)
 
 
 def _ptr(t):
@@ -426,6 +435,89 @@ class BatchNormSpec:
 
     def __repr__(self):
         return "BatchNormSpec(momentum=%r, eps=%r)" % (self.momentum, self.eps)
+
+
+class NetworkSpec:
+    """Which network SSDObjectDetectionModel builds and how it trains it.
+      kind             "ssd300": the reference's 300 x 300 network (SSDEngine), the default; "resnet50_ssd512": the ResNet-50
+                       SSD512 network (ResNet50SSDEngine)
+      in_size          300 for ssd300; 512 (default) or 256 for the ResNet
+      batchnorm        ResNet only: anything BatchNormSpec.of takes (None / False: the folded network)
+      precision        of the TRAINING forward: "bf16" or "mxfp8" (ResNet only; not together with batchnorm, whose engine has no
+                       fp8 plan)
+      dgrad_precision  of the data gradients behind an mxfp8 training forward: None (fp8 where planned), "bf16" or "mxfp8"
+    """
+    KINDS = ("ssd300", "resnet50_ssd512")
+    FIELDS = ("kind", "in_size", "batchnorm", "precision", "dgrad_precision")
+    IN_SIZES = {"ssd300": (300,), "resnet50_ssd512": (512, 256)}           # the first one is the default
+
+    def __init__(self, kind="ssd300", in_size=None, batchnorm=None, precision="bf16", dgrad_precision=None):
+        if not isinstance(kind, str) or kind not in self.KINDS:
+            raise ValueError("network kind must be one of %s, not %r" % (", ".join(self.KINDS), kind))
+        sizes = self.IN_SIZES[kind]
+        if in_size is None:
+            in_size = sizes[0]
+        if isinstance(in_size, bool) or not isinstance(in_size, (int, np.integer)) or int(in_size) not in sizes:
+            raise ValueError("network in_size of %s must be %s, not %r" % (kind, " or ".join(str(s) for s in sizes), in_size))
+        batchnorm = BatchNormSpec.of(batchnorm)
+        if not isinstance(precision, str) or precision not in ("bf16", "mxfp8"):
+            raise ValueError("network precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
+        if dgrad_precision is not None and (not isinstance(dgrad_precision, str) or dgrad_precision not in ("bf16", "mxfp8")):
+            raise ValueError("network dgrad_precision must be None, 'bf16' or 'mxfp8', not %r" % (dgrad_precision,))
+        if kind == "ssd300":
+            if batchnorm is not None:
+                raise ValueError("network batchnorm: the ssd300 network has no batch normalisation")
+            if precision != "bf16" or dgrad_precision is not None:
+                raise ValueError("network precision / dgrad_precision: the ssd300 network trains in bf16 (precision=%r, "
+                                 "dgrad_precision=%r)" % (precision, dgrad_precision))
+        if batchnorm is not None and precision == "mxfp8":
+            raise ValueError("network batchnorm together with precision='mxfp8': a batchnorm engine has no fp8 training "
+                             "forward (its fp8 inference runs on the folded network)")
+        if dgrad_precision == "mxfp8" and precision != "mxfp8":
+            raise ValueError("network dgrad_precision='mxfp8' needs precision='mxfp8': fp8 data gradients read what the fp8 "
+                             "training forward writes")
+        self.kind, self.in_size, self.batchnorm = kind, int(in_size), batchnorm
+        self.precision, self.dgrad_precision = precision, dgrad_precision
+
+    @classmethod
+    def of(cls, v, l2norm=None):
+        """None -> the ssd300 default; a kind name; a dict with keys of FIELDS; a NetworkSpec -> itself.  l2norm: the model's
+        l2norm argument, which only the ssd300 network serves.  ValueError (naming the key or value) for anything else."""
+        if v is None:
+            spec = cls()
+        elif isinstance(v, cls):
+            spec = v
+        elif isinstance(v, str):
+            spec = cls(kind=v)
+        elif isinstance(v, dict):
+            unknown = sorted(set(v) - set(cls.FIELDS), key=str)
+            if unknown:
+                raise ValueError("network: unknown key(s) %s (known: %s)" % (", ".join(repr(k) for k in unknown),
+                                                                            ", ".join(cls.FIELDS)))
+            spec = cls(**v)
+        else:
+            raise ValueError("network must be None, a kind name, a dict or an ops.NetworkSpec, not %r" % (v,))
+        if spec.kind != "ssd300" and L2NormSpec.of(l2norm) is not None:
+            raise ValueError("l2norm together with network kind %r: L2Norm is wired for the ssd300 network only" % spec.kind)
+        return spec
+
+    def as_dict(self):
+        """Plain values only (what a checkpoint and config.json carry); NetworkSpec.of(d) gives the spec back."""
+        bn = None if self.batchnorm is None else dict(momentum=self.batchnorm.momentum, eps=self.batchnorm.eps)
+        return dict(kind=self.kind, in_size=self.in_size, batchnorm=bn, precision=self.precision,
+                    dgrad_precision=self.dgrad_precision)
+
+    def identity(self):
+        """What makes two specs the same NETWORK (a checkpoint of one loads into the other): kind, input size and whether
+        batch normalisation is live.  The precisions are how a run trains it, not what it is."""
+        return (self.kind, self.in_size, self.batchnorm is not None)
+
+    def describe(self):
+        return "%s(in_size=%d%s)" % (self.kind, self.in_size, ", batchnorm" if self.batchnorm is not None else "")
+
+    def __repr__(self):
+        return "NetworkSpec(kind=%r, in_size=%d, batchnorm=%r, precision=%r, dgrad_precision=%r)" % (
+            self.kind, self.in_size, self.batchnorm, self.precision, self.dgrad_precision)
 
 
 _bn_ws = MatchWorkspace()

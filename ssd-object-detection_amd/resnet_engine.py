@@ -19,7 +19,7 @@ kernels, heads' backward from the loss's compact rows) plus csrc/eltwise.hip (Ad
 Parameter storage, clip + Adam, checkpoints: inherited."""
 import torch
 
-from . import ops
+from . import _lib, ops
 from .engine import SSDEngine, SSD512_NUM_PRIORS
 
 
@@ -182,6 +182,9 @@ def fold_batchnorm_params(graph_bn, params, running, eps):
 
 
 class ResNet50SSDEngine(SSDEngine):
+    bucket_optimizer = False                   # one-stream DAG walk: backward() refuses fused_adam / on_dgrad
+    side_streams = False                       # ... and nothing runs beside it that a high-priority main stream could overtake
+
     def __init__(self, classes=81, in_size=512, device="cuda", seed=0, batchnorm=None):
         """batchnorm: live batch normalisation behind each trunk convolution (ops.BatchNormSpec.of: None / False = off, the
         folded network of the module docstring; True, a dict(momentum, eps) or a spec).  Off, the engine plans the same
@@ -215,6 +218,37 @@ class ResNet50SSDEngine(SSDEngine):
         self._mx_wt = None                     # (q, scale) of the fp8 data gradients' transposed filters, at every fp8 backward
 
     # ---------------------------------------------------------------- static planning
+    @classmethod
+    def planned(cls, classes=81, in_size=512, batchnorm=None):
+        """The static plan alone -- graph, nodes, grids, A, tensors (names, indices, blocks) -- without a device: nothing is
+        allocated or launched.  For what needs the layout only: decay_table(), ready_order(), bucket plans."""
+        eng = cls.__new__(cls)
+        eng.L = _lib.lib()
+        eng.l2norm = None
+        eng.batchnorm = ops.BatchNormSpec.of(batchnorm)
+        eng.graph = resnet50_ssd512_graph(batchnorm=eng.batchnorm is not None)
+        eng.classes, eng.in_size, eng.device = classes, in_size, torch.device("cpu")
+        eng.trunk, eng.num_priors, eng.sparse_heads = [], tuple(SSD512_NUM_PRIORS), True
+        eng.block = eng.L.ssd_opt_block_elems()
+        eng._plan_shapes()
+        eng._plan_params()
+        return eng
+
+    def ready_order(self):
+        """The tensor indices backward() hands to on_ready, call by call: the trunk from the last node to the first (a bn
+        node's gamma / beta, a convolution's kernel / bias), then every head at once.  The flat buffer is therefore NOT
+        completed from its end -- the heads sit behind the trunk and are reported last, a batchnorm engine's gamma / beta sit
+        behind the heads and are reported throughout -- which parallel.GradReducer tolerates: it launches a bucket only once
+        every tensor of it was reported, buckets in order, so here the exchange starts when the pass ends."""
+        calls = []
+        for i in range(len(self.nodes) - 1, -1, -1):
+            if i in self.bn_params:
+                calls.append([t.index for t in self.bn_params[i]])
+            elif i in self.conv_params:
+                calls.append([t.index for t in self.conv_params[i]])
+        calls.append([i for wt, bt in self.head_params for t in (wt, bt) for i in t.indices])
+        return calls
+
     def _plan_extra_params(self, add):
         self.bn_params, self.bn_off, off = {}, {}, 0          # bn node -> (gamma, beta); -> offset in the flat statistics
         for i, nd in enumerate(self.nodes):
@@ -553,6 +587,22 @@ class ResNet50SSDEngine(SSDEngine):
             written[src + 1] = True
         if on_ready:
             on_ready([i for wt, bt in self.head_params for t in (wt, bt) for i in t.indices])
+
+    # ---------------------------------------------------------------- micro-batches
+    def accumulate_clipped(self, first):
+        """grad_acc (+)= the clipped gradient of this micro-batch, with the roundings of the data-parallel exchange: the
+        gradient is clipped IN PLACE (fp32(g * scale), what a rank sends: clip_range_in_place) and then added (ssd_grad_accumulate
+        without a scale table), as tf.clip_by_norm followed by the sum does it (reference models/ssd_model.py:249-255).
+        SSDEngine's form rounds once, fma(g, scale, acc), so its sum and a two-rank exchange differ in the last bit of some
+        elements.  SSD300 absorbs that; this network does not (measured: 64 280 parameters apart by <= 1.5e-8 after one Adam
+        step put the next step's gradients 1.25 % apart in relative l2 -- 50 bf16 layers and hard-negative mining in between).
+        With this form two ranks and one process running the same two micro-batches hold the same bits.  One more pass over
+        the flat gradient per micro-batch."""
+        if self.grad_acc is None:
+            self.grad_acc = torch.empty_like(self.grad)
+        self.apply_clip_in_place()
+        _lib.check(self.L.ssd_grad_accumulate(ops._ptr(self.grad_acc), ops._ptr(self.grad), self.n_flat, None, None,
+                                              1 if first else 0, ops._stream()))
 
     # ---------------------------------------------------------------- batchnorm: state and folding
     def state_dict(self):

@@ -115,6 +115,36 @@ def l2norm_from_config(config):
     return spec if enable else None
 
 
+def network_from_config(config):
+    """`model: network: {kind, in_size, batchnorm: {enable, momentum, eps}, precision, dgrad_precision}` (no reference
+    counterpart) -> ops.NetworkSpec, or None when the key is absent: the default run builds the reference's 300 x 300 network.
+    `batchnorm` absent, null or with enable false: no batch normalisation.  ValueError for an unknown key, a section that is
+    no mapping or bad values."""
+    section = (config.get("model") or {}).get("network")
+    if section is None:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError("model.network must be a mapping, not %r" % (section,))
+    from ..ops import BatchNormSpec, NetworkSpec
+    unknown = set(section) - set(NetworkSpec.FIELDS)
+    if unknown:
+        raise ValueError("unknown model.network keys: %s" % sorted(unknown, key=str))
+    fields = dict(section)
+    bn = fields.get("batchnorm")
+    if bn is not None:
+        if not isinstance(bn, dict):
+            raise ValueError("model.network.batchnorm must be a mapping, not %r" % (bn,))
+        unknown = set(bn) - {"enable", "momentum", "eps"}
+        if unknown:
+            raise ValueError("unknown model.network.batchnorm keys: %s" % sorted(unknown, key=str))
+        spec = BatchNormSpec(**{k: bn[k] for k in ("momentum", "eps") if k in bn})     # (bad values raise when disabled too)
+        enable = bn.get("enable", False)
+        if not isinstance(enable, bool):
+            raise ValueError("model.network.batchnorm.enable must be true or false, not %r" % (enable,))
+        fields["batchnorm"] = spec if enable else None
+    return NetworkSpec.of(fields, l2norm=l2norm_from_config(config))
+
+
 def schedule_from_config(section):
     """`model: train: lr:` -> a learning-rate schedule.  `kind: exponential` (the default when the key is absent: the
     reference's schema) reads `initial`, `decay_step`, `decay_rate`; `kind: piecewise` (no reference counterpart: the SSD
@@ -196,10 +226,12 @@ def train(config):
     rank, world = _init_distributed()
     data_cfg, model_cfg = config["data"], config["model"]
     subset = data_cfg["mini_batch"]
+    network = network_from_config(config)
     data = SSDDataLoader(dataset_root=data_cfg["dataset_root"], dataset=data_cfg["dataset"], shuffle=data_cfg["shuffle"],
-                         mini_batch=subset["num_data"] if subset["enable"] else 0)
+                         mini_batch=subset["num_data"] if subset["enable"] else 0,
+                         input_size=network.in_size if network is not None else 300)
     model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1,
-                                    l2norm=l2norm_from_config(config))
+                                    l2norm=l2norm_from_config(config), network=network)
 
     lr, wlr = model_cfg["train"]["lr"], model_cfg["warmup"]["lr"]
     optimizer = _make_optimizer(model_cfg["train"]["optimizer"], schedule_from_config(lr))
