@@ -301,6 +301,42 @@ int ssd_detect_pairs(const void* conf, const void* loc, int dtype, const double*
  *   none), mean of the samples summed in numpy's pairwise order.  0 for classes with n_gt == 0 (the caller leaves them out
  *   of its means) and for classes without detections.  Segments of any length.
  * Both return SSD_ERR_VALUE before any launch for B <= 0, A <= 0, C <= 0, max_dets out of range or a NULL pointer.
+ *
+ * The full COCO box protocol -- area ranges, crowd boxes, average recall -- is a second pair of entry points beside those two;
+ * its definition and oracle is utils/metrics.py:coco_summary (coco_match_image for the first stage, coco_tables_from_rows for
+ * the second).  ssd_eval_match and ssd_eval_ap are unchanged by it.
+ *
+ * ssd_eval_match_coco: ssd_eval_match's inputs, and
+ *   gt_crowd uint8[total_gt]  non-zero: a crowd region; NULL: none
+ *   area_scale double[B]      per image (source width x source height) / (S x S); NULL: 1
+ *   area_ranges HOST double[8]  (lo, hi) of the four ranges all / small / medium / large, bounds inclusive
+ * The selection and order of the detections are ssd_eval_match's.  The area of a box, detection or ground truth, is
+ * double(w) * double(h) * area_scale[image], left to right, without fused multiply-adds.  A ground truth is ignored in range a
+ * when it is crowd or its area is < lo[a] or > hi[a].  IoU against a crowd box is intersection / area of the detection (the
+ * corner-form area iou_matrix computes; 0 where it is not positive).  Per class, range and threshold the detections in order
+ * each take the unclaimed non-ignored box of their class with the highest IoU >= threshold, the LAST index winning among equal
+ * IoUs, and only when there is none an ignored one by the same rule, where a crowd box may be claimed again.  A matched
+ * detection is a true positive and inherits the ignore flag of its match; an unmatched one is ignored when its own area is
+ * outside the range.
+ *   n_det, det_score, det_cls, det_box  as ssd_eval_match
+ *   det_flags uint16[B*max_dets]    bit t: true positive at threshold t and not ignored, in range 0 -- ssd_eval_match's flags
+ *                                   when no box is crowd and range 0 holds every area
+ *   det_tp uint16[B*max_dets*4]     [image][slot][range], bit t: true positive at threshold t
+ *   det_ig uint16[B*max_dets*4]     [image][slot][range], bit t: ignored at threshold t
+ *   det_pos int32[B*max_dets]       rank of the detection among its image's detections of its class
+ *   gt_ignore uint8[total_gt]       bit a: ignored in range a (NULL allowed when gt_off[B] == 0)
+ * All fully written (gt_ignore: the boxes gt_off covers); slots at or beyond n_det hold zeros (class -1).  Images with more
+ * than 48 ground truths take a path without the IoU cache, with identical results; any number of boxes per image.
+ *
+ * ssd_eval_ap_coco: after the last batch, a grid of (class, range), from rows sorted as for ssd_eval_ap.
+ *   tp_sorted, ig_sorted uint16[N*4] ([row][range]; not NULL, even for N = 0), pos_sorted int32[N], seg_off int32[C+1],
+ *   n_gt int32[4*C] ([range][class]: ground truths not ignored in the range), max_dets 1 .. ssd_eval_max_dets(),
+ *   recall_points HOST double[101]
+ *   ap double[C*4*10]  [class][range][threshold]: ssd_eval_ap's AP over the rows whose ignore bit is clear -- the row index is
+ *                      the running count of such rows, a true positive counts when its ignore bit is clear
+ *   tp_count int32[C*4*3*10]  [class][range][m][threshold]: true positives not ignored with pos < (1, 10, max_dets)[m]
+ *   Both are 0 where n_gt == 0 (the caller leaves the class out of that range's means).
+ * Both return SSD_ERR_VALUE before any launch on the conditions of ssd_eval_match / ssd_eval_ap.
  * ---------------------------------------------------------------------------------------- */
 int ssd_eval_max_dets(void);
 int ssd_eval_match(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
@@ -309,6 +345,14 @@ int ssd_eval_match(const float* score, const int32_t* cls, const float* box, con
                    void* stream);
 int ssd_eval_ap(const uint16_t* flags_sorted, const int32_t* seg_off, const int32_t* n_gt, int C, const double* recall_points,
                 double* ap, void* stream);
+int ssd_eval_match_coco(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
+                        const int32_t* gt_cls, const double* gt_box, const int32_t* gt_off, const uint8_t* gt_crowd,
+                        const double* area_scale, const double* area_ranges, const double* iou_thresholds, int max_dets,
+                        int32_t* n_det, float* det_score, int32_t* det_cls, float* det_box, uint16_t* det_flags, uint16_t* det_tp,
+                        uint16_t* det_ig, int32_t* det_pos, uint8_t* gt_ignore, void* stream);
+int ssd_eval_ap_coco(const uint16_t* tp_sorted, const uint16_t* ig_sorted, const int32_t* pos_sorted, const int32_t* seg_off,
+                     const int32_t* n_gt, int C, int max_dets, const double* recall_points, double* ap, int32_t* tp_count,
+                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Convolution stack (NHWC bf16 activations, bf16 weights [Cout][k][k][Cin], fp32 accumulate on MFMA).

@@ -100,6 +100,9 @@ _SIGNATURES = {
     "ssd_eval_match": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP, VP, VP, _c_double_p, ctypes.c_int,
                                       VP, VP, VP, VP, VP, VP]),
     "ssd_eval_ap": (ctypes.c_int, [VP, VP, VP, ctypes.c_int, _c_double_p, VP, VP]),
+    "ssd_eval_match_coco": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP, VP, VP, VP, VP, _c_double_p,
+                                           _c_double_p, ctypes.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "ssd_eval_ap_coco": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, _c_double_p, VP, VP, VP]),
     "ssd_conv2d_fwd": (ctypes.c_int, [VP, VP, VP, VP] + [ctypes.c_int] * 12 + [VP, ctypes.c_size_t, VP]),
     "ssd_conv2d_fwd_pool": (ctypes.c_int, [VP, VP, VP, VP, VP, VP] + [ctypes.c_int] * 14 + [VP, ctypes.c_size_t, VP]),
     "ssd_conv2d_head_fwd": (ctypes.c_int, [VP, VP, VP, VP, VP] + [ctypes.c_int] * 8 + [VP, ctypes.c_size_t, VP]),

@@ -382,6 +382,437 @@ __global__ __launch_bounds__(AWG) void k_eval_ap(const uint16_t* __restrict__ fl
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The full COCO box protocol (utils/metrics.coco_summary): area ranges, crowd boxes, positions for AR.
+//
+//   k_eval_match_coco  k_eval_match's selection, rank sort and class segments, then one THREAD per (class segment, area range,
+//                      threshold).  A ground truth is ignored in a range when it is crowd or its area lies outside it; the
+//                      class's ground truths are two bit masks, valid and ignored, each walked in ascending index order: a
+//                      detection looks at the unclaimed valid ones first and only without a match at the ignored ones, of which
+//                      a crowd box may be claimed again.  The IoU against a crowd box (intersection / detection area) sits in
+//                      the same LDS matrix.  An unmatched detection whose own area lies outside the range is ignored: that is
+//                      the start value of its ignore word, which a match replaces bit by bit.
+//   k_eval_ap_coco     k_eval_ap's scan per (class, area range) over the rows not ignored: the row index is the running count
+//                      of non-ignored rows, the true-positive bits are masked by ~ig; beside it the true positives among the
+//                      first 1 / 10 / max_dets detections of their (image, class) for the recall columns.
+constexpr int NA = 4;                        // area ranges
+
+struct AreaRanges { double lo[NA], hi[NA]; };
+
+__device__ __forceinline__ bool outside(double area, double lo, double hi) { return area < lo || area > hi; }
+
+// the pair's intersection over the detection's area (COCO's IoU against a crowd region); metrics.iou_matrix_crowd
+__device__ __forceinline__ double ioa_f64(float4 d, double gx, double gy, double gw, double gh) {
+    const double dx = (double)d.x, dy = (double)d.y, dw = (double)d.z, dh = (double)d.w;
+    const double a0 = dx - dw / 2, a1 = dy - dh / 2, a2 = dx + dw / 2, a3 = dy + dh / 2;
+    const double b0 = gx - gw / 2, b1 = gy - gh / 2, b2 = gx + gw / 2, b3 = gy + gh / 2;
+    const double w = fmax(fmin(a2, b2) - fmax(a0, b0), 0.0);
+    const double h = fmax(fmin(a3, b3) - fmax(a1, b1), 0.0);
+    const double inter = w * h;
+    const double area_a = (a2 - a0) * (a3 - a1);
+    return area_a > 0.0 ? inter / fmax(area_a, 1e-300) : 0.0;
+}
+
+__global__ __launch_bounds__(WG) void k_eval_match_coco(
+    const float* __restrict__ score, const int* __restrict__ cls, const float4* __restrict__ box,
+    const uint8_t* __restrict__ keep, int A, const int* __restrict__ gt_cls, const double* __restrict__ gt_box,
+    const int* __restrict__ gt_off, const uint8_t* __restrict__ gt_crowd, const double* __restrict__ area_scale, Thresholds thr,
+    AreaRanges rng, int max_dets, int* __restrict__ n_det, float* __restrict__ det_score, int* __restrict__ det_cls,
+    float4* __restrict__ det_box, uint16_t* __restrict__ det_flags, uint16_t* __restrict__ det_tp, uint16_t* __restrict__ det_ig,
+    int* __restrict__ det_pos, uint8_t* __restrict__ gt_ignore) {
+    // s_big: the sort keys [CAP] u64 + the candidate list [CAP] int during the selection; afterwards the IoU matrix [MAXD][GL]
+    // or, uncached, s_match [NA][NT][MAXD]: the ground truth claimed by the detection at a position, -1 none
+    __shared__ __attribute__((aligned(16))) double s_big[MAXD * GL];
+    __shared__ float4 s_dbox[MAXD];
+    __shared__ int s_dcls[MAXD];
+    __shared__ int s_danchor[MAXD];
+    __shared__ unsigned s_tp[NA][MAXD];
+    __shared__ unsigned s_ig[NA][MAXD];
+    __shared__ int s_ord[MAXD];                  // detection ranks ordered by (class, rank)
+    __shared__ int s_seg[MAXD];                  // first position in s_ord of every class segment (any order)
+    __shared__ double s_gbox[GL][4];
+    __shared__ int s_gcls[GL];
+    __shared__ unsigned s_gign[GL];              // bit a: ignored in range a; bit 8: crowd
+    __shared__ int s_hist[256];
+    __shared__ int s_wave[WG / 64];
+    __shared__ int s_misc[4];
+    static_assert(sizeof(double) * MAXD * GL >= sizeof(int) * NA * NT * MAXD, "the match list fits");
+    unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_big);
+    int* s_idx = reinterpret_cast<int*>(s_key + CAP);
+    int (*s_match)[NT][MAXD] = reinterpret_cast<int (*)[NT][MAXD]>(s_big);
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t off = (size_t)b * A;
+    const float* sc = score + off;
+    const uint8_t* kp = keep + off;
+    const double scale = area_scale ? area_scale[b] : 1.0;
+
+    if (tid < 4) s_misc[tid] = 0;
+    __syncthreads();
+    // the kept anchors, unordered (the sort orders them completely: the anchor index is part of the key)
+    auto note = [&](int a) {
+        const int slot = atomicAdd(&s_misc[0], 1);
+        if (slot < CAP) s_idx[slot] = a;
+    };
+    if ((A & 3) == 0) {                          // rows of keep are 4-byte aligned: four anchors per load
+        const unsigned* kp4 = reinterpret_cast<const unsigned*>(kp);
+        const int nq = A >> 2;
+        for (int q = tid; q < nq; q += WG) {
+            const unsigned v = kp4[q];
+            if (!v) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if ((v >> (8 * e)) & 0xffu) note(4 * q + e);
+        }
+    } else {
+        for (int a = tid; a < A; a += WG)
+            if (kp[a]) note(a);
+    }
+    __syncthreads();
+    const int total = s_misc[0];
+    int n_in;                                    // keys that enter the sort
+    if (total <= CAP) {
+        n_in = total;
+        if (tid < total) {
+            const int a = s_idx[tid];
+            s_key[tid] = ((unsigned long long)(~ordered_bits(sc[a])) << 32) | (unsigned long long)(unsigned)a;
+        }
+    } else {
+        // more kept anchors than sort slots: k_eval_match's exact radix cut to the max_dets best
+        unsigned prefix = 0;
+        int k = max_dets;                        // rank (1-based, from the top) still to locate
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) s_hist[tid] = 0;
+            __syncthreads();
+            for (int a = tid; a < A; a += WG)
+                if (kp[a]) {
+                    const unsigned key = ordered_bits(sc[a]);
+                    if (shift == 24 || (key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
+                }
+            __syncthreads();
+            if (tid == 0) {
+                int run = 0, d = 255;
+                for (; d > 0; --d) {
+                    if (run + s_hist[d] >= k) break;
+                    run += s_hist[d];
+                }
+                s_misc[1] = d;
+                s_misc[2] = k - run;
+            }
+            __syncthreads();
+            prefix = (prefix << 8) | (unsigned)s_misc[1];
+            k = s_misc[2];
+            __syncthreads();
+        }
+        const unsigned cut_bits = prefix;        // take score > cut, and the first `k` (anchor order) with score == cut
+        int filled = 0, eq_seen = 0;
+        for (int a0 = 0; a0 < A; a0 += WG) {
+            const int a = a0 + tid;
+            bool is_c = a < A && kp[a];
+            const unsigned key = is_c ? ordered_bits(sc[a]) : 0u;
+            const bool is_eq = is_c && key == cut_bits;
+            is_c = is_c && key >= cut_bits;
+            int tot_eq = 0;
+            const int eq_rank = wg_prefix(is_eq, s_wave, tot_eq);
+            if (is_eq && eq_seen + eq_rank >= k) is_c = false;
+            eq_seen += tot_eq;
+            int tot = 0;
+            const int pos = wg_prefix(is_c, s_wave, tot);
+            if (is_c && filled + pos < CAP)
+                s_key[filled + pos] = ((unsigned long long)(~key) << 32) | (unsigned long long)(unsigned)a;
+            filled += tot;
+        }
+        n_in = min(filled, max_dets);            // == max_dets
+    }
+    __syncthreads();
+    // sort by rank: keys are unique, every thread counts the keys below its own (broadcast LDS reads)
+    const int nd = min(n_in, max_dets);
+    {
+        const unsigned long long mine = tid < n_in ? s_key[tid] : ~0ull;
+        int rank = 0;
+        for (int j = 0; j < n_in; ++j) rank += s_key[j] < mine ? 1 : 0;
+        if (tid < n_in && rank < nd) s_danchor[rank] = (int)(unsigned)(mine & 0xffffffffull);
+    }
+    __syncthreads();                             // s_key / s_idx are dead from here on
+    // the detections: outputs fully written (slots at or beyond nd: score 0, class -1, box 0)
+    if (tid < max_dets) {
+        const size_t o = (size_t)b * max_dets + tid;
+        float s = 0.f;
+        int c = -1;
+        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < nd) {
+            const int a = s_danchor[tid];
+            s = sc[a];
+            c = cls[off + a];
+            bx = box[off + a];
+            s_dcls[tid] = c;
+            s_dbox[tid] = bx;
+            const double area = (double)bx.z * (double)bx.w * scale;
+#pragma unroll
+            for (int a2 = 0; a2 < NA; ++a2) {    // unmatched: ignored where its own area lies outside the range
+                s_tp[a2][tid] = 0u;
+                s_ig[a2][tid] = outside(area, rng.lo[a2], rng.hi[a2]) ? 0x3ffu : 0u;
+            }
+        }
+        det_score[o] = s;
+        det_cls[o] = c;
+        det_box[o] = bx;
+    }
+    if (tid == 0) n_det[b] = nd;
+    __syncthreads();
+    // class segments: position of a detection among those ordered by (class, rank); det_pos = its rank inside the class
+    if (tid < max_dets) {
+        int inside = 0;
+        if (tid < nd) {
+            const int c = s_dcls[tid];
+            int pos = 0;
+            for (int r = 0; r < nd; ++r) {
+                const int cr = s_dcls[r];
+                pos += (cr < c || (cr == c && r < tid)) ? 1 : 0;
+                inside += (cr == c && r < tid) ? 1 : 0;
+            }
+            s_ord[pos] = tid;
+        }
+        det_pos[(size_t)b * max_dets + tid] = inside;
+    }
+    __syncthreads();
+    if (tid < nd) {
+        const bool start = tid == 0 || s_dcls[s_ord[tid]] != s_dcls[s_ord[tid - 1]];
+        if (start) s_seg[atomicAdd(&s_misc[3], 1)] = tid;
+    }
+    const int g0 = gt_off[b];
+    const int G = max(gt_off[b + 1] - g0, 0);
+    const bool cached = G <= GL;
+    double* s_iou = s_big;
+    // the ground truths' ignore bits: crowd, or the area outside the range
+    for (int j = tid; j < G; j += WG) {
+        const double* g = gt_box + 4 * (size_t)(g0 + j);
+        const double area = g[2] * g[3] * scale;
+        const bool crowd = gt_crowd && gt_crowd[g0 + j];
+        unsigned bits = 0u;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) bits |= (crowd || outside(area, rng.lo[a], rng.hi[a])) ? (1u << a) : 0u;
+        gt_ignore[g0 + j] = (uint8_t)bits;
+        if (cached) {
+            s_gign[j] = bits | (crowd ? 0x100u : 0u);
+            s_gcls[j] = gt_cls[g0 + j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s_gbox[j][e] = g[e];
+        }
+    }
+    if (cached) {
+        __syncthreads();
+        // every class-matched IoU once (against a crowd box: intersection / detection area)
+        for (int p = tid; p < nd * G; p += WG) {
+            const int r = p / G, j = p - r * G;
+            if (s_gcls[j] == s_dcls[r])
+                s_iou[r * GL + j] = (s_gign[j] & 0x100u)
+                                        ? ioa_f64(s_dbox[r], s_gbox[j][0], s_gbox[j][1], s_gbox[j][2], s_gbox[j][3])
+                                        : iou_f64(s_dbox[r], s_gbox[j][0], s_gbox[j][1], s_gbox[j][2], s_gbox[j][3]);
+        }
+    }
+    __syncthreads();
+    const int nseg = s_misc[3];
+    // the greedy pass: one thread per (class segment, area range, threshold)
+    if (nd > 0 && G > 0) {
+        for (int w = tid; w < nseg * NA * NT; w += WG) {
+            const int sg = w / (NA * NT), a = (w / NT) % NA, t = w % NT;
+            const int p0 = s_seg[sg];
+            const int c = s_dcls[s_ord[p0]];
+            const double th = thr.v[t];
+            if (cached) {
+                unsigned long long valid = 0ull, ign = 0ull, again = 0ull;      // this class's ground truths, by kind
+                for (int j = 0; j < G; ++j) {
+                    if (s_gcls[j] != c) continue;
+                    const unsigned gi = s_gign[j];
+                    if ((gi >> a) & 1u) ign |= 1ull << j; else valid |= 1ull << j;
+                    if (gi & 0x100u) again |= 1ull << j;
+                }
+                if (!(valid | ign)) continue;
+                unsigned long long taken = 0ull;
+                for (int p = p0; p < nd; ++p) {
+                    const int r = s_ord[p];
+                    if (s_dcls[r] != c) break;
+                    double best = th;
+                    int bj = -1;
+                    unsigned long long open = valid & ~taken;
+                    while (open) {                   // ascending j, >=: the last index wins among equal IoUs
+                        const int j = __ffsll((long long)open) - 1;
+                        open &= open - 1ull;
+                        const double v = s_iou[r * GL + j];
+                        if (v >= best) { best = v; bj = j; }
+                    }
+                    if (bj < 0) {
+                        open = ign & (~taken | again);
+                        while (open) {
+                            const int j = __ffsll((long long)open) - 1;
+                            open &= open - 1ull;
+                            const double v = s_iou[r * GL + j];
+                            if (v >= best) { best = v; bj = j; }
+                        }
+                    }
+                    if (bj >= 0) {
+                        taken |= 1ull << bj;
+                        atomicOr(&s_tp[a][r], 1u << t);
+                        if ((ign >> bj) & 1ull) atomicOr(&s_ig[a][r], 1u << t); else atomicAnd(&s_ig[a][r], ~(1u << t));
+                    }
+                }
+            } else {
+                const double lo = rng.lo[a], hi = rng.hi[a];
+                for (int p = p0; p < nd; ++p) {
+                    const int r = s_ord[p];
+                    if (s_dcls[r] != c) break;
+                    const float4 d = s_dbox[r];
+                    int bj = -1;
+                    bool bign = false;
+                    for (int pass = 0; pass < 2 && bj < 0; ++pass) {     // the valid ground truths, then the ignored ones
+                        double best = th;
+                        for (int j = 0; j < G; ++j) {
+                            if (gt_cls[g0 + j] != c) continue;
+                            const double* g = gt_box + 4 * (size_t)(g0 + j);
+                            const bool crowd = gt_crowd && gt_crowd[g0 + j];
+                            const bool gign = crowd || outside(g[2] * g[3] * scale, lo, hi);
+                            if (gign != (pass == 1)) continue;
+                            const double v = crowd ? ioa_f64(d, g[0], g[1], g[2], g[3]) : iou_f64(d, g[0], g[1], g[2], g[3]);
+                            if (!(v >= best)) continue;
+                            bool taken = false;      // claimed by an earlier detection of the segment?
+                            if (!crowd)
+                                for (int q = p0; q < p && !taken; ++q) taken = s_match[a][t][q] == j;
+                            if (!taken) { best = v; bj = j; bign = gign; }
+                        }
+                    }
+                    s_match[a][t][p] = bj;
+                    if (bj >= 0) {
+                        atomicOr(&s_tp[a][r], 1u << t);
+                        if (bign) atomicOr(&s_ig[a][r], 1u << t); else atomicAnd(&s_ig[a][r], ~(1u << t));
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < max_dets) {
+        const size_t o = (size_t)b * max_dets + tid;
+        const bool live = tid < nd;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            det_tp[o * NA + a] = live ? (uint16_t)s_tp[a][tid] : (uint16_t)0;
+            det_ig[o * NA + a] = live ? (uint16_t)s_ig[a][tid] : (uint16_t)0;
+        }
+        det_flags[o] = live ? (uint16_t)(s_tp[0][tid] & ~s_ig[0][tid]) : (uint16_t)0;
+    }
+}
+
+// AP of one (class, area range) at the ten thresholds over the rows that are not ignored, and the true positives among the
+// first 1 / 10 / max_dets detections of their (image, class).  tp, ig: [N][NA] words of every detection of the data set, sorted.
+__global__ __launch_bounds__(AWG) void k_eval_ap_coco(const uint16_t* __restrict__ tp, const uint16_t* __restrict__ ig,
+                                                     const int* __restrict__ pos, const int* __restrict__ seg_off,
+                                                     const int* __restrict__ n_gt, int C, int max_dets, RecallPoints pts,
+                                                     double* __restrict__ ap, int* __restrict__ tp_count) {
+    __shared__ unsigned long long s_best[NT][NP];    // bits of the best precision whose last recall point <= recall is k
+    __shared__ double s_pts[NP];
+    __shared__ int s_wtot[2][AWG / 64][2 * NT];
+    __shared__ int s_cnt[3][NT];                     // true positives with pos < 1, pos < 10, pos < max_dets
+    const int c = blockIdx.x, a = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t cell = (size_t)c * NA + a;
+    const int ngt = n_gt[(size_t)a * C + c];
+    if (ngt <= 0) {                                  // not part of any mean (the caller excludes it)
+        if (tid < NT) ap[cell * NT + tid] = 0.0;
+        if (tid < 3 * NT) tp_count[cell * 3 * NT + tid] = 0;
+        return;
+    }
+    for (int i = tid; i < NT * NP; i += AWG) (&s_best[0][0])[i] = 0ull;
+    if (tid < 3 * NT) (&s_cnt[0][0])[tid] = 0;
+    if (tid == 0) {                                  // constant indices: a lane-indexed read would copy the argument to scratch
+#pragma unroll
+        for (int k = 0; k < NP; ++k) s_pts[k] = pts.v[k];
+    }
+    const long long lo = seg_off[c], hi = seg_off[c + 1];
+    const double dngt = (double)ngt;
+    int carry_tp[NT], carry_n[NT], first1[NT], first10[NT], firstm[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) carry_tp[t] = carry_n[t] = first1[t] = first10[t] = firstm[t] = 0;
+    __syncthreads();
+    int par = 0;
+    for (long long i0 = lo; i0 < hi; i0 += AWG, par ^= 1) {
+        const long long i = i0 + tid;
+        const bool in = i < hi;
+        const unsigned live = in ? (~(unsigned)ig[i * NA + a] & 0x3ffu) : 0u;    // bit t: the row counts at threshold t
+        const unsigned f = in ? ((unsigned)tp[i * NA + a] & live) : 0u;
+        const int ps = in ? pos[i] : INT_MAX;
+        int incl_tp[NT], incl_n[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const unsigned long long m = __ballot((f >> t) & 1u);
+            const unsigned long long n = __ballot((live >> t) & 1u);
+            incl_tp[t] = __popcll(m & ((2ull << lane) - 1ull));
+            incl_n[t] = __popcll(n & ((2ull << lane) - 1ull));
+            if (lane == 0) {
+                s_wtot[par][wave][t] = __popcll(m);
+                s_wtot[par][wave][NT + t] = __popcll(n);
+            }
+        }
+        __syncthreads();                             // (double-buffered totals: one barrier per chunk)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            int base = carry_tp[t], tot = 0, nbase = carry_n[t], ntot = 0;
+#pragma unroll
+            for (int w = 0; w < AWG / 64; ++w) {
+                const int v = s_wtot[par][w][t], u = s_wtot[par][w][NT + t];
+                if (w < wave) { base += v; nbase += u; }
+                tot += v;
+                ntot += u;
+            }
+            carry_tp[t] += tot;
+            carry_n[t] += ntot;
+            if ((f >> t) & 1u) {
+                first1[t] += ps < 1 ? 1 : 0;
+                first10[t] += ps < 10 ? 1 : 0;
+                firstm[t] += ps < max_dets ? 1 : 0;
+                const int ctp = base + incl_tp[t];
+                const double prec = (double)ctp / (double)(nbase + incl_n[t]);
+                const double rec = (double)ctp / dngt;
+                int a2 = 0, z = NP - 1;              // last k with pts[k] <= rec (pts[0] = 0 <= rec)
+                while (a2 < z) {
+                    const int mid = (a2 + z + 1) >> 1;
+                    if (s_pts[mid] <= rec) a2 = mid; else z = mid - 1;
+                }
+                atomicMax(&s_best[t][a2], (unsigned long long)__double_as_longlong(prec));
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if (first1[t]) atomicAdd(&s_cnt[0][t], first1[t]);
+        if (first10[t]) atomicAdd(&s_cnt[1][t], first10[t]);
+        if (firstm[t]) atomicAdd(&s_cnt[2][t], firstm[t]);
+    }
+    __syncthreads();
+    if (tid < NT) {
+        // k_eval_ap's envelope and its mean in numpy's summation order
+        unsigned long long* row = s_best[tid];
+        unsigned long long run = 0ull;
+        for (int k = NP - 1; k >= 0; --k) {
+            run = row[k] > run ? row[k] : run;
+            row[k] = run;
+        }
+        double r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = __longlong_as_double((long long)row[j]);
+        int k = 8;
+        for (; k + 8 <= NP; k += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] += __longlong_as_double((long long)row[k + j]);
+        }
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; k < NP; ++k) res += __longlong_as_double((long long)row[k]);
+        ap[cell * NT + tid] = res / (double)NP;
+        tp_count[(cell * 3 + 0) * NT + tid] = s_cnt[0][tid];
+        tp_count[(cell * 3 + 1) * NT + tid] = s_cnt[1][tid];
+        tp_count[(cell * 3 + 2) * NT + tid] = s_cnt[2][tid];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -409,6 +840,40 @@ int ssd_eval_ap(const uint16_t* flags_sorted, const int32_t* seg_off, const int3
     RecallPoints pts;
     for (int k = 0; k < NP; ++k) pts.v[k] = recall_points[k];
     hipLaunchKernelGGL(k_eval_ap, dim3(C), dim3(AWG), 0, (hipStream_t)stream, flags_sorted, seg_off, n_gt, pts, ap);
+    return ssd_launch_status();
+}
+
+int ssd_eval_match_coco(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
+                        const int32_t* gt_cls, const double* gt_box, const int32_t* gt_off, const uint8_t* gt_crowd,
+                        const double* area_scale, const double* area_ranges, const double* iou_thresholds, int max_dets,
+                        int32_t* n_det, float* det_score, int32_t* det_cls, float* det_box, uint16_t* det_flags, uint16_t* det_tp,
+                        uint16_t* det_ig, int32_t* det_pos, uint8_t* gt_ignore, void* stream) {
+    if (B <= 0 || A <= 0 || max_dets <= 0 || max_dets > MAXD) return SSD_ERR_VALUE;
+    if (!score || !cls || !box || !keep || !gt_off || !iou_thresholds || !area_ranges) return SSD_ERR_VALUE;
+    if (!n_det || !det_score || !det_cls || !det_box || !det_flags || !det_tp || !det_ig || !det_pos) return SSD_ERR_VALUE;
+    Thresholds thr;
+    for (int t = 0; t < NT; ++t) thr.v[t] = iou_thresholds[t];
+    AreaRanges rng;
+    for (int a = 0; a < NA; ++a) {
+        rng.lo[a] = area_ranges[2 * a];
+        rng.hi[a] = area_ranges[2 * a + 1];
+    }
+    hipLaunchKernelGGL(k_eval_match_coco, dim3(B), dim3(WG), 0, (hipStream_t)stream, score, cls,
+                       reinterpret_cast<const float4*>(box), keep, A, gt_cls, gt_box, gt_off, gt_crowd, area_scale, thr, rng,
+                       max_dets, n_det, det_score, det_cls, reinterpret_cast<float4*>(det_box), det_flags, det_tp, det_ig, det_pos,
+                       gt_ignore);
+    return ssd_launch_status();
+}
+
+int ssd_eval_ap_coco(const uint16_t* tp_sorted, const uint16_t* ig_sorted, const int32_t* pos_sorted, const int32_t* seg_off,
+                     const int32_t* n_gt, int C, int max_dets, const double* recall_points, double* ap, int32_t* tp_count,
+                     void* stream) {
+    if (C <= 0 || max_dets <= 0 || max_dets > MAXD) return SSD_ERR_VALUE;
+    if (!tp_sorted || !ig_sorted || !pos_sorted || !seg_off || !n_gt || !recall_points || !ap || !tp_count) return SSD_ERR_VALUE;
+    RecallPoints pts;
+    for (int k = 0; k < NP; ++k) pts.v[k] = recall_points[k];
+    hipLaunchKernelGGL(k_eval_ap_coco, dim3(C, NA), dim3(AWG), 0, (hipStream_t)stream, tp_sorted, ig_sorted, pos_sorted, seg_off,
+                       n_gt, C, max_dets, pts, ap, tp_count);
     return ssd_launch_status();
 }
 

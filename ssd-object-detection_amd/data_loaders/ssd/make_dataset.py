@@ -62,9 +62,10 @@ class RawSplit:
         self._source, self._limit = source, int(limit)
 
     def __iter__(self):
-        for i, (image, cls, box) in enumerate(self._source):
+        for i, sample in enumerate(self._source):
             if self._limit and i >= self._limit:
                 break
+            image, cls, box = sample[:3]                                 # a fourth element (crowd flags) passes through
             image = np.asarray(image)
             if image.ndim == 2:                                          # grey image: reference coco/make_dataset.py:129-130
                 image = np.stack([image, image, image], axis=2)
@@ -72,7 +73,7 @@ class RawSplit:
                 image = np.rint(np.asarray(image, np.float64) * 255.0).astype(np.uint8)
             box = np.asarray(box, np.float32).reshape(-1, 4).copy()
             box[:, :2] -= box[:, 2:] / np.float32(2.0)                   # centre (reference :132) back to top-left
-            yield np.ascontiguousarray(image[..., :3]), np.asarray(cls, np.float32), box
+            yield (np.ascontiguousarray(image[..., :3]), np.asarray(cls, np.float32), box) + tuple(sample[3:4])
 
 
 class SSDDataLoader:

@@ -63,9 +63,12 @@ class SSDObjectDetectionModel:
             # validation during the run (None = off): dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
             # max_dets=100, num_data=0, precision="bf16"); missing keys take these defaults.  After every `every`-th epoch
             # the validation split (its first num_data samples if > 0) is evaluated with metric="device".  An optional key
-            # scoring="best" | "all" (evaluate()'s; absent = "best") is kept only when given
+            # scoring="best" | "all" (evaluate()'s; absent = "best") is kept only when given, and so is protocol="map" | "coco"
+            # (evaluate()'s; absent = "map": val/mAP, val/AP50, val/AP75; "coco": COCO's twelve values)
             if val is not None and val.get("scoring", "best") not in ("best", "all"):
                 raise ValueError("val['scoring'] must be 'best' or 'all', not %r" % (val["scoring"],))
+            if val is not None and val.get("protocol", "map") not in ("map", "coco"):
+                raise ValueError("val['protocol'] must be 'map' or 'coco', not %r" % (val["protocol"],))
             self.val = None if val is None else dict(dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
                                                           max_dets=100, num_data=0, precision="bf16"), **val)
 
@@ -550,7 +553,12 @@ class SSDObjectDetectionModel:
                 samples = _RawList(samples)
         r = self.evaluate(samples, batch_size=val["batch_size"], score_thresh=val["score_thresh"], iou_thresh=val["iou_thresh"],
                           max_dets=val["max_dets"], precision=val["precision"], metric="device",
-                          scoring=val.get("scoring", "best"))
+                          scoring=val.get("scoring", "best"), protocol=val.get("protocol", "map"))
+        if val.get("protocol", "map") == "coco":
+            from ..utils.metrics import COCO_SUMMARY_KEYS
+            self._scalars.write_values("val", step, {k: r[k] for k in COCO_SUMMARY_KEYS})
+            logger.info("validation at step %d: %s", step, " ".join("%s %.4f" % (k, r[k]) for k in COCO_SUMMARY_KEYS))
+            return r
         self._scalars.write_values("val", step, {k: r[k] for k in ("mAP", "AP50", "AP75")})
         logger.info("validation at step %d: mAP %.4f AP50 %.4f AP75 %.4f", step, r["mAP"], r["AP50"], r["AP75"])
         return r
@@ -640,12 +648,28 @@ class SSDObjectDetectionModel:
             box_d = ops.box_prep(box_d, self._to_device(gt_off), hw_d)
         return x, box_d, counts
 
+    def _coco_batch_extras(self, buf, raw):
+        """(crowd u8 [total] or None when no sample carries flags, area_scale f64 [B] or None for prepared samples) of a
+        batch of evaluation samples: the COCO protocol's extra inputs."""
+        crowd = None
+        if any(len(b) > 3 and b[3] is not None for b in buf):
+            crowd = np.concatenate([np.asarray(b[3]).astype(bool).reshape(-1) if len(b) > 3 and b[3] is not None
+                                    else np.zeros(int(np.shape(b[1])[0]), bool) for b in buf]).astype(np.uint8)
+        scale = None
+        if raw:
+            s2 = float(self.cfg.input_shape[0]) * float(self.cfg.input_shape[0])
+            scale = np.array([float(np.shape(b[0])[1]) * float(np.shape(b[0])[0]) / s2 for b in buf], np.float64)
+        return crowd, scale
+
     def evaluate_into(self, acc, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, precision="bf16", scoring="best"):
         """The batch loop of evaluate(metric="device"): every batch of `samples` through the network, scoring/decoding, NMS
         and acc.add (utils.device_map.DeviceMapAccumulator) on the current stream.  Host arrays reach the device through
         pinned memory; nothing in the loop reads the device or waits for it.  scoring="all": the compact rows of
         ops.detect_pairs (keep_top_k = acc.max_dets) go to acc.add as they are -- ssd_eval_match takes any row count, and its
-        (score desc, index asc) order is the rows' own."""
+        (score desc, index asc) order is the rows' own.  An accumulator of the COCO protocol (DeviceCocoAccumulator) also gets
+        the samples' crowd flags (a fourth element, absent = none) and, for reader-contract samples, the area scale
+        (source width x source height) / (S x S)."""
+        coco = getattr(acc, "protocol", "map") == "coco"
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         if scoring not in ("best", "all"):
@@ -671,7 +695,12 @@ class SSDObjectDetectionModel:
                 score, cls, box, keep = d.score, d.cls, d.box, d.valid
             else:
                 score, cls, box, keep = self._detect_prepared(x, score_thresh, iou_thresh, precision=precision)
-            acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off))
+            if coco:
+                crowd, scale = self._coco_batch_extras(buf, raw)
+                acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off),
+                        None if crowd is None else self._to_device(crowd), None if scale is None else self._to_device(scale))
+            else:
+                acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off))
             buf.clear()
 
         for sample in samples:
@@ -681,7 +710,7 @@ class SSDObjectDetectionModel:
         flush()
 
     def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False,
-                 precision="bf16", metric="host", scoring="best"):
+                 precision="bf16", metric="host", scoring="best", protocol="map"):
         """Evaluation pass (the reference fetches its val split at models/ssd_model.py:291 and drops it):
         samples = iterable of (image f32 [S,S,3] in [0,1], cls [n], box [n,4] relative cx,cy,w,h) as the loaders yield
         them, or a split of reader-contract samples (getattr(samples, "raw"): decoded uint8 images of any size, COCO top-left
@@ -697,15 +726,23 @@ class SSDObjectDetectionModel:
         scoring="best" (default): one label per anchor, as detect().  scoring="all": the SSD detection-output protocol, as
         detections() -- every (anchor, class) pair above score_thresh, per-class NMS, the best max_dets rows per image
         (keep_top_k = max_dets <= ops.detect_max_keep(); the top max_dets rows of a longer list are the same rows); "host"
-        then copies the compact rows once per batch.  Any other value raises ValueError."""
+        then copies the compact rows once per batch.  Any other value raises ValueError.
+        protocol="map" (default): the metric above.  protocol="coco": COCO's twelve box metrics (utils.metrics.coco_summary:
+        AP, AP50, AP75, AP and AR by area range, AR at 1 / 10 / max_dets detections), with either metric mode; samples may
+        carry a fourth element `crowd` (bool [n]); for reader-contract samples areas are in source pixels (area_scale =
+        source width x source height / S^2), for prepared samples in evaluation pixels.  Returns coco_summary's dict.  Any
+        other value raises ValueError."""
         from ..utils.metrics import coco_map
+        if protocol not in ("map", "coco"):
+            raise ValueError("protocol must be 'map' or 'coco', not %r" % (protocol,))
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         if scoring not in ("best", "all"):
             raise ValueError("scoring must be 'best' or 'all', not %r" % (scoring,))
         if metric == "device":
-            from ..utils.device_map import DeviceMapAccumulator
-            acc = DeviceMapAccumulator(self.cfg.classes - 1, max_dets, self.device)
+            from ..utils.device_map import DeviceCocoAccumulator, DeviceMapAccumulator
+            acc = (DeviceCocoAccumulator if protocol == "coco" else DeviceMapAccumulator)(self.cfg.classes - 1, max_dets,
+                                                                                          self.device)
             self.evaluate_into(acc, samples, batch_size, score_thresh, iou_thresh, precision, scoring)
             result = acc.result()
             return (result, acc.detections()) if return_detections else result
@@ -714,10 +751,16 @@ class SSDObjectDetectionModel:
         size = float(self.cfg.input_shape[0])
         raw = bool(getattr(samples, "raw", False))
         dets, gts, buf = [], [], []
+        crowds, scales = [], []                                       # protocol="coco": per image
 
         def flush():
             if not buf:
                 return
+            if protocol == "coco":
+                scale = self._coco_batch_extras(buf, raw)[1]
+                scales.extend([1.0] * len(buf) if scale is None else scale.tolist())
+                crowds.extend(np.asarray(b[3]).astype(bool).reshape(-1) if len(b) > 3 and b[3] is not None
+                              else np.zeros(int(np.shape(b[1])[0]), bool) for b in buf)
             if raw:
                 x, box_d, counts = self._eval_batch_raw(buf)
                 gboxes = np.split(box_d.cpu().numpy(), np.cumsum(counts)[:-1])
@@ -729,7 +772,7 @@ class SSDObjectDetectionModel:
                     x = ops.image_prep(((img - 0.5) * 2).contiguous(), normalize=False)
                 d = self._detections_prepared(x, score_thresh, iou_thresh, keep_top_k=max_dets, precision=precision)
                 n, score, cls, box = d.n_det.cpu().numpy(), d.score.cpu().numpy(), d.cls.cpu().numpy(), d.box.cpu().numpy()
-                for i, (_, gcls, _) in enumerate(buf):
+                for i, gcls in enumerate(b[1] for b in buf):
                     dets.append((score[i, :n[i]].copy(), cls[i, :n[i]].copy(), box[i, :n[i]].copy()))
                     gts.append((np.asarray(gcls), np.asarray(gboxes[i], np.float64) * size))
                 buf.clear()
@@ -740,7 +783,7 @@ class SSDObjectDetectionModel:
                 img = torch.from_numpy(np.stack([b[0] for b in buf], 0)).to(self.device)
                 score, cls, box, keep = self.detect((img - 0.5) * 2, score_thresh, iou_thresh, precision=precision)
             score, cls, box, keep = score.cpu().numpy(), cls.cpu().numpy(), box.cpu().numpy(), keep.cpu().numpy().astype(bool)
-            for i, (_, gcls, _) in enumerate(buf):
+            for i, gcls in enumerate(b[1] for b in buf):
                 k = keep[i]
                 dets.append((score[i][k], cls[i][k], box[i][k]))
                 gts.append((np.asarray(gcls), np.asarray(gboxes[i], np.float64) * size))     # pixels, like the decoded boxes
@@ -751,7 +794,12 @@ class SSDObjectDetectionModel:
             if len(buf) == batch_size:
                 flush()
         flush()
-        result = coco_map(dets, gts, max_dets=max_dets)
+        if protocol == "coco":
+            from ..utils.metrics import coco_summary
+            result = coco_summary(dets, [g + (c,) for g, c in zip(gts, crowds)], max_dets=max_dets,
+                                  area_scale=np.asarray(scales, np.float64))
+        else:
+            result = coco_map(dets, gts, max_dets=max_dets)
         return (result, dets) if return_detections else result
 
     # ------------------------------------------------------------------ checkpoint

@@ -852,6 +852,74 @@ def eval_ap(flags_sorted, seg_off, n_gt):
     return ap
 
 
+COCO_AREA_RANGES = ((0, 1e10), (0, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e10))     # utils.metrics.COCO_AREA_RANGES
+EvalMatchCoco = collections.namedtuple("EvalMatchCoco", "n_det score cls box flags tp ig pos gt_ignore")
+
+
+def eval_match_coco(score, cls, box, keep, gt_cls, gt_box, gt_off, max_dets=100, gt_crowd=None, area_scale=None,
+                    area_ranges=COCO_AREA_RANGES):
+    """ssd_eval_match_coco: eval_match with COCO's area ranges and crowd boxes (utils.metrics.coco_match_image).  gt_crowd u8
+    [total] or None (no crowd box), area_scale f64 [B] or None (1), area_ranges four (lo, hi) pairs.  Returns
+    EvalMatchCoco(n_det i32 [B], score f32 [B,max_dets], cls i32 [B,max_dets], box f32 [B,max_dets,4], flags int16
+    [B,max_dets], tp int16 [B,max_dets,4], ig int16 [B,max_dets,4], pos i32 [B,max_dets], gt_ignore u8 [total]); the int16
+    tensors hold uint16 words: bit t = threshold t; the last axis of tp / ig is the area range; bit a of gt_ignore = range a."""
+    L = _lib.lib()
+    B, A = score.shape
+    _dev(score, torch.float32); _dev(cls, torch.int32); _dev(box, torch.float32); _dev(keep, torch.uint8)
+    _dev(gt_cls, torch.int32); _dev(gt_box, torch.float64); _dev(gt_off, torch.int32)
+    assert gt_off.numel() == B + 1 and gt_box.shape[0] == gt_cls.shape[0]
+    if gt_crowd is not None:
+        _dev(gt_crowd, torch.uint8)
+        assert gt_crowd.numel() == gt_cls.numel()
+    if area_scale is not None:
+        _dev(area_scale, torch.float64)
+        assert area_scale.numel() == B
+    rng = np.ascontiguousarray(np.asarray(area_ranges, np.float64).reshape(-1))
+    assert rng.size == 8
+    max_dets = int(max_dets)
+    dev = score.device
+    md = max(max_dets, 1)
+    n_det = torch.empty((B,), dtype=torch.int32, device=dev)
+    det_score = torch.empty((B, md), dtype=torch.float32, device=dev)
+    det_cls = torch.empty((B, md), dtype=torch.int32, device=dev)
+    det_box = torch.empty((B, md, 4), dtype=torch.float32, device=dev)
+    det_flags = torch.empty((B, md), dtype=torch.int16, device=dev)
+    det_tp = torch.empty((B, md, 4), dtype=torch.int16, device=dev)
+    det_ig = torch.empty((B, md, 4), dtype=torch.int16, device=dev)
+    det_pos = torch.empty((B, md), dtype=torch.int32, device=dev)
+    gt_ignore = torch.empty((gt_cls.numel(),), dtype=torch.uint8, device=dev)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _lib.check(L.ssd_eval_match_coco(_ptr(score), _ptr(cls), _ptr(box), _ptr(keep), B, A, _ptr(gt_cls), _ptr(gt_box),
+                                     _ptr(gt_off), _ptr(gt_crowd) if gt_crowd is not None else None,
+                                     _ptr(area_scale) if area_scale is not None else None, rng.ctypes.data_as(dp),
+                                     _EVAL_THRESHOLDS.ctypes.data_as(dp), max_dets, _ptr(n_det), _ptr(det_score), _ptr(det_cls),
+                                     _ptr(det_box), _ptr(det_flags), _ptr(det_tp), _ptr(det_ig), _ptr(det_pos), _ptr(gt_ignore),
+                                     _stream()))
+    return EvalMatchCoco(n_det, det_score, det_cls, det_box, det_flags, det_tp, det_ig, det_pos, gt_ignore)
+
+
+def eval_ap_coco(tp_sorted, ig_sorted, pos_sorted, seg_off, n_gt, max_dets=100):
+    """ssd_eval_ap_coco: tp / ig int16 [N,4] (uint16 words per area range) and pos i32 [N] sorted by (class, score desc, image,
+    rank), seg_off i32 [C+1], n_gt i32 [4,C] (non-ignored ground truths per range and class) -> (ap f64 [C,4,10], tp_count i32
+    [C,4,3,10]: true positives not ignored with pos < (1, 10, max_dets)); zeros where n_gt == 0."""
+    L = _lib.lib()
+    _dev(tp_sorted, torch.int16); _dev(ig_sorted, torch.int16); _dev(pos_sorted, torch.int32)
+    _dev(seg_off, torch.int32); _dev(n_gt, torch.int32)
+    C = n_gt.shape[1]
+    assert n_gt.shape[0] == 4 and seg_off.numel() == C + 1
+    assert tp_sorted.shape == ig_sorted.shape == (pos_sorted.numel(), 4)
+    dev = n_gt.device
+    if pos_sorted.numel() == 0:                        # the entry point wants pointers even when there is nothing to read
+        tp_sorted = ig_sorted = torch.zeros((1, 4), dtype=torch.int16, device=dev)
+        pos_sorted = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ap = torch.empty((C, 4, 10), dtype=torch.float64, device=dev)
+    tp_count = torch.empty((C, 4, 3, 10), dtype=torch.int32, device=dev)
+    pts = _EVAL_RECALL_POINTS.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    _lib.check(L.ssd_eval_ap_coco(_ptr(tp_sorted), _ptr(ig_sorted), _ptr(pos_sorted), _ptr(seg_off), _ptr(n_gt), C, int(max_dets),
+                                  pts, _ptr(ap), _ptr(tp_count), _stream()))
+    return ap, tp_count
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution stack (NHWC bf16)
 # ------------------------------------------------------------------------------------------------

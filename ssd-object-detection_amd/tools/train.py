@@ -59,11 +59,12 @@ def val_from_config(config):
     counterpart: the reference drops its validation split) -> the `val` dict of TrainConfig, or None when the key is absent or
     enable is false: the default run does not validate, as the reference does not.  The optional key `scoring` ("best": one
     label per anchor, the default when absent; "all": the multi-label detection output, evaluate(scoring="all")) is in the
-    dict only when the config gives it."""
+    dict only when the config gives it, and so is `protocol` ("map", the default when absent: val/mAP, val/AP50, val/AP75;
+    "coco": COCO's twelve box metrics, evaluate(protocol="coco"))."""
     section = (config.get("model") or {}).get("eval")
     if not section or not section.get("enable", False):
         return None
-    unknown = set(section) - set(VAL_DEFAULTS) - {"enable", "scoring"}
+    unknown = set(section) - set(VAL_DEFAULTS) - {"enable", "scoring", "protocol"}
     if unknown:
         raise ValueError("unknown model.eval keys: %s" % sorted(unknown))
     val = {k: type(d)(section.get(k, d)) for k, d in VAL_DEFAULTS.items()}
@@ -75,6 +76,10 @@ def val_from_config(config):
         if section["scoring"] not in ("best", "all"):
             raise ValueError("model.eval.scoring must be 'best' or 'all', not %r" % (section["scoring"],))
         val["scoring"] = str(section["scoring"])
+    if "protocol" in section:
+        if section["protocol"] not in ("map", "coco"):
+            raise ValueError("model.eval.protocol must be 'map' or 'coco', not %r" % (section["protocol"],))
+        val["protocol"] = str(section["protocol"])
     return val
 
 
