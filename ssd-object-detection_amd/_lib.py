@@ -1,199 +1,119 @@
-"""ctypes binding of libssd_hip.so (include/ssd_hip.h).  Fails loudly when the library is absent."""
+"""ctypes binding of libssd_hip.so.  include/ssd_hip.h is the only statement of the ABI: its constants, enumerators, structs
+and prototypes are parsed here, once per process.  Fails loudly when the header or the library is absent, and on any
+declaration the parser does not know."""
 import ctypes
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # (SSD_HIP_LIB: development only -- another build of the library next to the default one, for same-box A/B runs)
 LIB_PATH = os.path.join(HERE, os.environ.get("SSD_HIP_LIB", "libssd_hip.so"))
+HEADER_PATH = os.path.join(HERE, "..", "include", "ssd_hip.h")
 
-SSD_OK, SSD_ERR_ASSERT, SSD_ERR_VALUE, SSD_ERR_WORKSPACE, SSD_ERR_LAUNCH, SSD_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
-SSD_MAX_LEVELS = 8
-
-_c_int_p = ctypes.POINTER(ctypes.c_int)
-_c_double_p = ctypes.POINTER(ctypes.c_double)
-VP = ctypes.c_void_p
-
-
-class PriorGrid(ctypes.Structure):
-    _fields_ = [("levels", ctypes.c_int),
-                ("grid_h", ctypes.c_int * SSD_MAX_LEVELS),
-                ("grid_w", ctypes.c_int * SSD_MAX_LEVELS),
-                ("per_cell", ctypes.c_int * SSD_MAX_LEVELS),
-                ("verified", ctypes.c_int)]
+# The closed type map.  A pointer to a header struct is POINTER(its Structure), `const char*` is c_char_p, every other pointer
+# is c_void_p: the header cannot say whether a `const double*` is a host array or a device address, and c_void_p takes
+# ctypes arrays, integers and None alike.  _DEVICE_RECORDS: structs that live in device memory only (the library writes and
+# reads arrays of them there); a pointer to one is an address like any tensor's, so c_void_p as well.
+_DEVICE_RECORDS = {"ssd_augment_params"}
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64}
 
 
-class HeadGrads(ctypes.Structure):
-    """ssd_head_grads: the loss gradient as compact per-level pixel rows."""
-    _fields_ = [("levels", ctypes.c_int),
-                ("hw", ctypes.c_int * SSD_MAX_LEVELS),
-                ("per_cell", ctypes.c_int * SSD_MAX_LEVELS),
-                ("npad", ctypes.c_int * SSD_MAX_LEVELS),
-                ("rows", VP * SSD_MAX_LEVELS),
-                ("row_of_pixel", VP * SSD_MAX_LEVELS),
-                ("pixel_of_row", VP * SSD_MAX_LEVELS),
-                ("count", VP)]
+def _ctype(text, structs, where):
+    """The ctypes type of a C type as written (`const float*`, `long long`, ...); `where` names the declaration in errors."""
+    t = " ".join(re.sub(r"\bconst\b", " ", text).replace("*", " * ").split())
+    if t.endswith("*"):
+        base = t[:-1].strip()
+        if base in structs and base not in _DEVICE_RECORDS:
+            return ctypes.POINTER(structs[base])
+        return ctypes.c_char_p if base == "char" else ctypes.c_void_p
+    if t not in _SCALARS:
+        raise TypeError("ssd_hip.h: no ctypes mapping for the type `%s` in `%s`" % (t, " ".join(where.split())))
+    return _SCALARS[t]
 
 
-class HeadLayers(ctypes.Structure):
-    """ssd_head_layers: operands and outputs of the head convolutions' backward pass."""
-    _fields_ = [("levels", ctypes.c_int),
-                ("H", ctypes.c_int * SSD_MAX_LEVELS),
-                ("W", ctypes.c_int * SSD_MAX_LEVELS),
-                ("Cin", ctypes.c_int * SSD_MAX_LEVELS),
-                ("cout", ctypes.c_int * SSD_MAX_LEVELS),
-                ("x", VP * SSD_MAX_LEVELS),
-                ("w_tap", VP * SSD_MAX_LEVELS),
-                ("relu_bits", VP * SSD_MAX_LEVELS),
-                ("relu_src", VP * SSD_MAX_LEVELS),
-                ("dx", VP * SSD_MAX_LEVELS),
-                ("dw", VP * SSD_MAX_LEVELS),
-                ("dbias", VP * SSD_MAX_LEVELS)]
+def _enumerators(body):
+    value = -1
+    for item in filter(None, (s.strip() for s in body.split(","))):
+        name, _, literal = (s.strip() for s in item.partition("="))
+        value = int(literal, 0) if literal else value + 1
+        yield name, value
 
 
-class ChainLayer(ctypes.Structure):
-    """ssd_chain_layer: one convolution of ssd_conv_chain."""
-    _fields_ = [("w", VP), ("bias", VP), ("out", VP), ("mask_bits", VP), ("mask_src", VP), ("relu_bits", VP)] + \
-               [(n, ctypes.c_int) for n in ("Hi", "Wi", "Kc", "Ho", "Wo", "N", "ksize", "mul", "div", "pad_t", "pad_l", "relu",
-                                            "accumulate")]
+def _fields(body, constants, structs, where):
+    """_fields_ of a struct body: `int a, b;`, `int h[N], w[N];` and pointer members, N a literal or a #define."""
+    declarator = r"\s*(\**)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*$"
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        base = ""
+        for i, decl in enumerate(stmt.split(",")):
+            m = re.match(declarator if i else r"(.*?)" + declarator, decl, re.S)
+            if not m:
+                raise TypeError("ssd_hip.h: cannot parse the member `%s` of %s" % (stmt, where))
+            if i == 0:
+                base = m.group(1)
+            stars, name, bound = m.groups()[-3:]             # a `*` binds to its declarator, not to the comma list
+            ctype = _ctype(base + stars, structs, "%s: %s" % (where, stmt))
+            if bound:
+                if not bound.isdigit() and bound not in constants:
+                    raise TypeError("ssd_hip.h: unknown array bound `%s` in `%s` of %s" % (bound, stmt, where))
+                ctype = ctype * (int(bound) if bound.isdigit() else constants[bound])
+            yield name, ctype
 
 
-class WgradItem(ctypes.Structure):
-    """ssd_wgrad_item: one layer of ssd_conv2d_bwd_weight_batched."""
-    _fields_ = [("x", VP), ("dy", VP), ("dw", VP), ("dbias", VP)] + \
-               [(n, ctypes.c_int) for n in ("B", "H", "W", "Cin", "Cout", "ldy", "ksize", "stride", "pad_t", "pad_l", "Ho", "Wo")]
+def parse_header(text):
+    """(constants, structs, signatures) of a C header in the style of ssd_hip.h: {name: int} for the integer #defines and
+    every enumerator, {typedef name: ctypes.Structure class}, {function: (restype, [argtypes])}.  Anything it cannot type or
+    does not recognise raises TypeError; nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2), 0)
+                 for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(SSD_\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)          # extern "C" { and its }
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def enum(m):
+        constants.update(_enumerators(m.group(1)))
+        return " "
+
+    text = re.sub(r"(?:typedef\s+)?enum\s*\w*\s*\{(.*?)\}\s*\w*\s*;", enum, text, flags=re.S)
+    structs = {}
+
+    def struct(m):
+        cls = type(m.group(2), (ctypes.Structure,), {"__doc__": "%s of include/ssd_hip.h." % m.group(2)})
+        cls._fields_ = list(_fields(m.group(1), constants, structs, m.group(2)))
+        structs[m.group(2)] = cls
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    signatures = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.match(r"(.+?)\b(ssd_\w+)\s*\((.*)\)$", stmt, re.S)
+        if not m:
+            raise TypeError("ssd_hip.h: not a prototype, struct, enum or #define: `%s`" % " ".join(stmt.split()))
+        params = [p.strip() for p in m.group(3).split(",")]
+        params = [] if params == ["void"] else [re.match(r"(.*?)\w+$", p, re.S).group(1) for p in params]
+        restype = _ctype(m.group(1), structs, stmt)
+        signatures[m.group(2)] = (restype, [_ctype(p, structs, stmt) for p in params])
+    return constants, structs, signatures
 
 
-class ChainPack(ctypes.Structure):
-    """ssd_chain_pack: one filter tensor of ssd_chain_pack_weights."""
-    _fields_ = [("src", VP), ("dst", VP), ("N", ctypes.c_int), ("K", ctypes.c_int)]
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError("include/ssd_hip.h is missing (%s): the ctypes binding is derived from it and there is no "
+                           "hand-written copy to fall back to." % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return f.read()
 
 
-SSD_CHAIN_MAX_LAYERS = 8
-SSD_CHAIN_PACK_MAX = 16
-_HG = ctypes.POINTER(HeadGrads)
-_HL = ctypes.POINTER(HeadLayers)
-
-_SIGNATURES = {
-    "ssd_hip_abi_version": (ctypes.c_int, []),
-    "ssd_status_string": (ctypes.c_char_p, [ctypes.c_int]),
-    "ssd_priors_count": (ctypes.c_int, [_c_int_p, ctypes.c_int, _c_int_p]),
-    "ssd_priors": (ctypes.c_int, [_c_int_p, ctypes.c_int, _c_double_p, _c_int_p, _c_int_p, ctypes.c_double, VP, VP]),
-    "ssd_encode_zero": (ctypes.c_int, [VP, ctypes.c_int, VP, VP]),
-    "ssd_prior_grid_verify": (ctypes.c_int, [VP, ctypes.c_int, ctypes.POINTER(PriorGrid), VP, VP]),
-    "ssd_match_encode_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ssd_match_encode": (ctypes.c_int, [VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP, VP, ctypes.c_int,
-                                        ctypes.POINTER(PriorGrid), ctypes.c_double, VP, VP, VP, VP, VP, ctypes.c_size_t, VP]),
-    "ssd_apply_anchor_box": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP]),
-    "ssd_iou_n": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP]),
-    "ssd_score_decode": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_float, ctypes.c_double, VP, VP, VP, VP, VP]),
-    "ssd_nms_max_candidates": (ctypes.c_int, []),
-    "ssd_nms": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, VP, VP, VP]),
-    "ssd_detect_max_candidates": (ctypes.c_int, []),
-    "ssd_detect_max_keep": (ctypes.c_int, []),
-    "ssd_class_scores": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP, VP]),
-    "ssd_detect_pairs_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ssd_detect_pairs": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
-                                        ctypes.c_double, ctypes.c_float, ctypes.c_int, ctypes.c_int, VP, VP, VP, VP, VP, VP, VP,
-                                        VP, ctypes.c_size_t, VP]),
-    "ssd_eval_max_dets": (ctypes.c_int, []),
-    "ssd_eval_match": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP, VP, VP, _c_double_p, ctypes.c_int,
-                                      VP, VP, VP, VP, VP, VP]),
-    "ssd_eval_ap": (ctypes.c_int, [VP, VP, VP, ctypes.c_int, _c_double_p, VP, VP]),
-    "ssd_eval_match_coco": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP, VP, VP, VP, VP, _c_double_p,
-                                           _c_double_p, ctypes.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
-    "ssd_eval_ap_coco": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, _c_double_p, VP, VP, VP]),
-    "ssd_conv2d_fwd": (ctypes.c_int, [VP, VP, VP, VP] + [ctypes.c_int] * 12 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_fwd_pool": (ctypes.c_int, [VP, VP, VP, VP, VP, VP] + [ctypes.c_int] * 14 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_head_fwd": (ctypes.c_int, [VP, VP, VP, VP, VP] + [ctypes.c_int] * 8 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_bwd_data": (ctypes.c_int, [VP, VP, VP, VP] + [ctypes.c_int] * 12 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_fwd_relubits": (ctypes.c_int, [VP] * 5 + [ctypes.c_int] * 11 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_bwd_data_bits": (ctypes.c_int, [VP] * 4 + [ctypes.c_int] * 12 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_bwd_data_unpool": (ctypes.c_int, [VP] * 6 + [ctypes.c_int] * 7 + [VP, ctypes.c_size_t, VP]),
-    "ssd_quantize_mx_fp8": (ctypes.c_int, [VP, VP, VP, ctypes.c_longlong, VP]),
-    "ssd_conv3x3_fwd_mxfp8": (ctypes.c_int, [VP] * 6 + [ctypes.c_int] * 6 + [VP]),
-    "ssd_conv2d_fwd_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 12 + [VP]),
-    "ssd_add_relu_fwd_mxfp8": (ctypes.c_int, [VP] * 5 + [ctypes.c_longlong, VP]),
-    "ssd_conv2d_bwd_data_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 11 + [VP]),
-    "ssd_conv2d_fwd_pool_mxfp8": (ctypes.c_int, [VP] * 8 + [ctypes.c_int] * 14 + [VP]),
-    "ssd_chain_pack_weights": (ctypes.c_int, [ctypes.POINTER(ChainPack), ctypes.c_int, VP]),
-    "ssd_chain_prefetch": (ctypes.c_int, [ctypes.POINTER(ChainPack), ctypes.c_int, VP]),
-    "ssd_conv2d_bwd_weight_batched_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(WgradItem), ctypes.c_int]),
-    "ssd_conv2d_bwd_weight_batched": (ctypes.c_int, [ctypes.POINTER(WgradItem), ctypes.c_int, VP, ctypes.c_size_t, VP]),
-    "ssd_conv_chain": (ctypes.c_int, [VP, ctypes.POINTER(ChainLayer), ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_add_relu_fwd": (ctypes.c_int, [VP, VP, VP, ctypes.c_longlong, VP]),
-    "ssd_relu_mask_bwd": (ctypes.c_int, [VP, VP, VP, ctypes.c_int, ctypes.c_longlong, VP]),
-    "ssd_maxpool3x3s2_fwd": (ctypes.c_int, [VP, VP, VP] + [ctypes.c_int] * 8 + [VP]),
-    "ssd_maxpool3x3s2_bwd": (ctypes.c_int, [VP, VP, VP] + [ctypes.c_int] * 8 + [VP]),
-    "ssd_conv2d_bwd_weight_unpooled_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
-    "ssd_conv2d_bwd_weight_unpooled": (ctypes.c_int, [VP] * 5 + [ctypes.c_int] * 7 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_bwd_data_wgrad_first_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
-    "ssd_conv2d_bwd_data_wgrad_first": (ctypes.c_int, [VP] * 6 + [ctypes.c_int] * 3 + [VP, ctypes.c_size_t, VP]),
-    "ssd_conv2d_bwd_weight_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
-    "ssd_conv2d_bwd_weight": (ctypes.c_int, [VP, VP, VP, VP] + [ctypes.c_int] * 12 + [VP, ctypes.c_size_t, VP]),
-    "ssd_weight_transpose": (ctypes.c_int, [VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_cast_bf16": (ctypes.c_int, [VP, VP, ctypes.c_longlong, VP]),
-    "ssd_image_prep": (ctypes.c_int, [VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_image_resize_prep": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_box_prep": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_augment_plan": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
-                                        ctypes.c_int64, VP, VP, VP, VP, VP]),
-    "ssd_augment_image": (ctypes.c_int, [VP, ctypes.c_int, VP, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_maxpool2x2_fwd": (ctypes.c_int, [VP, VP] + [ctypes.c_int] * 6 + [VP]),
-    "ssd_maxpool2x2_bwd": (ctypes.c_int, [VP, VP, VP, VP] + [ctypes.c_int] * 6 + [VP]),
-    "ssd_weight_transpose_batched": (ctypes.c_int, [VP, ctypes.c_int, ctypes.c_int, VP]),
-    "ssd_maxpool2x2_fwd_argmax": (ctypes.c_int, [VP, VP, VP] + [ctypes.c_int] * 6 + [VP]),
-    "ssd_maxpool2x2_bwd_argmax": (ctypes.c_int, [VP, VP, VP] + [ctypes.c_int] * 6 + [VP]),
-    "ssd_head_grad_pack": (ctypes.c_int, [VP, VP, VP] + [ctypes.c_int] * 7 + [VP]),
-    "ssd_opt_block_elems": (ctypes.c_int, []),
-    "ssd_grad_clip_scales": (ctypes.c_int, [VP, ctypes.c_longlong, VP, ctypes.c_int, ctypes.c_float, VP, VP, VP, VP]),
-    "ssd_grad_apply_scale": (ctypes.c_int, [VP, ctypes.c_longlong, VP, VP, VP]),
-    "ssd_grad_accumulate": (ctypes.c_int, [VP, VP, ctypes.c_longlong, VP, VP, ctypes.c_int, VP]),
-    "ssd_adam_step": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_longlong, VP, VP] + [ctypes.c_float] * 5 + [VP]),
-    "ssd_sgd_step": (ctypes.c_int, [VP, VP, VP, ctypes.c_longlong, VP, VP, ctypes.c_float, ctypes.c_float, VP]),
-    "ssd_sgd_momentum_step": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_longlong, VP, VP, VP] + [ctypes.c_float] * 3
-                              + [ctypes.c_int, VP]),
-    "ssd_l2norm_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
-    "ssd_l2norm_fwd": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_longlong, ctypes.c_int, ctypes.c_float, VP]),
-    "ssd_l2norm_bwd": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_int, VP, VP, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int,
-                                      ctypes.c_float, VP]),
-    "ssd_bn_ws_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
-    "ssd_bn_fwd_train": (ctypes.c_int, [VP] * 8 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, VP, ctypes.c_size_t,
-                                                   ctypes.c_longlong, ctypes.c_int, VP]),
-    "ssd_bn_fwd_infer": (ctypes.c_int, [VP] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, VP]),
-    "ssd_bn_bwd": (ctypes.c_int, [VP] * 9 + [ctypes.c_size_t, ctypes.c_longlong, ctypes.c_int, VP]),
-    "ssd_dev_knob": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
-    "ssd_dev_mfma_calibration_workgroups": (ctypes.c_int, []),
-    "ssd_dev_mfma_calibration_flops": (ctypes.c_double, [ctypes.c_int]),
-    "ssd_dev_mfma_calibration": (ctypes.c_int, [ctypes.c_int, VP, VP, VP]),
-    "ssd_conv2d_fwd_plan": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
-    "ssd_conv2d_head_fwd_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_size_t]),
-    "ssd_conv2d_bwd_data_plan": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
-    "ssd_conv2d_fwd_workgroups": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
-    "ssd_conv2d_bwd_data_workgroups": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_size_t]),
-    "ssd_conv2d_bwd_weight_plan": (ctypes.c_int, [ctypes.c_int] * 12),
-    "ssd_conv_plan_name": (ctypes.c_char_p, [ctypes.c_int]),
-    "ssd_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ssd_loss_heads_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ssd_loss_fwd_bwd_heads": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_float, VP, _HG, VP, ctypes.c_size_t, ctypes.c_int, VP]),
-    "ssd_heads_bwd_data_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, _HL]),
-    "ssd_heads_bwd_data_sparse": (ctypes.c_int, [_HG, _HL, ctypes.c_int, VP, ctypes.c_size_t, VP]),
-    "ssd_heads_bwd_data_sparse_levels": (ctypes.c_int, [_HG, _HL, ctypes.c_int, ctypes.c_uint, VP, ctypes.c_size_t, VP]),
-    "ssd_heads_bwd_weight_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, _HG, _HL]),
-    "ssd_heads_bwd_weight_sparse": (ctypes.c_int, [_HG, _HL, ctypes.c_int, VP, ctypes.c_size_t, VP]),
-    "ssd_loss_fwd_bwd": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_float, VP, VP, VP, VP, ctypes.c_size_t, VP]),
-    "ssd_multibox_loss_max_anchors": (ctypes.c_int, []),
-    "ssd_multibox_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ssd_multibox_loss_heads_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "ssd_multibox_loss_fwd_bwd": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP, VP, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_int, ctypes.c_float, ctypes.c_float, VP, VP, VP, VP, ctypes.c_size_t,
-                                                 VP]),
-    "ssd_multibox_loss_fwd_bwd_heads": (ctypes.c_int, [VP, VP, ctypes.c_int, VP, VP, VP, ctypes.c_int, ctypes.c_int,
-                                                       ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, VP, _HG, VP,
-                                                       ctypes.c_size_t, VP]),
-}
+CONSTANTS, STRUCTS, _SIGNATURES = parse_header(_read_header())
+globals().update(CONSTANTS)         # SSD_OK, SSD_ERR_*, SSD_MAX_LEVELS, SSD_CHAIN_MAX_LAYERS, SSD_CHAIN_PACK_MAX, SSD_AUG_*, ...
+PriorGrid = STRUCTS["ssd_prior_grid"]
+HeadGrads = STRUCTS["ssd_head_grads"]                # the loss gradient as compact per-level pixel rows
+HeadLayers = STRUCTS["ssd_head_layers"]              # operands and outputs of the head convolutions' backward pass
+ChainLayer = STRUCTS["ssd_chain_layer"]              # one convolution of ssd_conv_chain
+ChainPack = STRUCTS["ssd_chain_pack"]                # one filter tensor of ssd_chain_pack_weights
+WgradItem = STRUCTS["ssd_wgrad_item"]                # one layer of ssd_conv2d_bwd_weight_batched
+AugmentParams = STRUCTS["ssd_augment_params"]        # what ssd_augment_plan drew and applied for one image
 
 _lib = None
 
@@ -219,10 +139,13 @@ def lib():
     return _lib
 
 
-def check(status):
-    """Map a C-ABI status to the exception type the reference raises at the same seam."""
+def check(status, unsupported=None):
+    """Map a C-ABI status to the exception type the reference raises at the same seam.  `unsupported`: the message of the
+    NotImplementedError a wrapper raises instead where the library refuses a shape (SSD_ERR_UNSUPPORTED)."""
     if status == SSD_OK:
         return
+    if unsupported is not None and status == SSD_ERR_UNSUPPORTED:
+        raise NotImplementedError(unsupported)
     msg = lib().ssd_status_string(status).decode()
     if status == SSD_ERR_ASSERT:
         raise AssertionError(msg)

@@ -364,9 +364,7 @@ def l2norm_fwd(x, scale, out=None, rnorm=None, eps=1e-10):
     if rnorm is not None:
         assert _dev(rnorm, torch.float32).numel() == P
     rc = L.ssd_l2norm_fwd(_ptr(x), _ptr(scale), _ptr(out), _ptr(rnorm), P, C, float(eps), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("l2norm serves multiples of 128 channels in 128 .. 1024, not C = %d" % C)
-    _lib.check(rc)
+    _lib.check(rc, unsupported="l2norm serves multiples of 128 channels in 128 .. 1024, not C = %d" % C)
     return (out, rnorm) if want else out
 
 
@@ -394,9 +392,7 @@ def l2norm_bwd(dy, x, scale, rnorm=None, out=None, accumulate=False, dscale=None
     wbuf = (ws or _l2norm_ws).get(L.ssd_l2norm_ws_bytes(P, C), x.device)
     rc = L.ssd_l2norm_bwd(_ptr(dy), _ptr(x), _ptr(scale), _ptr(rnorm), _ptr(out), 1 if accumulate else 0, _ptr(dscale),
                           _ptr(wbuf), wbuf.numel(), P, C, float(eps), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("l2norm serves multiples of 128 channels in 128 .. 1024, not C = %d" % C)
-    _lib.check(rc)
+    _lib.check(rc, unsupported="l2norm serves multiples of 128 channels in 128 .. 1024, not C = %d" % C)
     return out, dscale
 
 
@@ -555,9 +551,7 @@ def batchnorm_fwd_train(x, gamma, beta, out=None, mean=None, rstd=None, running_
     rc = L.ssd_bn_fwd_train(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(mean), _ptr(rstd), _ptr(running_mean),
                             _ptr(running_var), float(momentum), float(eps), 1 if relu else 0, _ptr(wbuf), wbuf.numel(), P, C,
                             _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError(_BN_SHAPES % C)
-    _lib.check(rc)
+    _lib.check(rc, unsupported=_BN_SHAPES % C)
     return out, mean, rstd
 
 
@@ -575,9 +569,7 @@ def batchnorm_fwd_infer(x, gamma, beta, running_mean, running_var, out=None, eps
         _bn_vec(t, C)
     rc = L.ssd_bn_fwd_infer(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(out), float(eps),
                             1 if relu else 0, P, C, _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError(_BN_SHAPES % C)
-    _lib.check(rc)
+    _lib.check(rc, unsupported=_BN_SHAPES % C)
     return out
 
 
@@ -602,9 +594,7 @@ def batchnorm_bwd(dy, x, gamma, mean, rstd, out=None, dgamma=None, dbeta=None, w
     wbuf = (ws or _bn_ws).get(L.ssd_bn_ws_bytes(P, C), x.device)
     rc = L.ssd_bn_bwd(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(out), _ptr(dgamma), _ptr(dbeta), _ptr(wbuf),
                       wbuf.numel(), P, C, _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError(_BN_SHAPES % C)
-    _lib.check(rc)
+    _lib.check(rc, unsupported=_BN_SHAPES % C)
     return out, dgamma, dbeta
 
 
@@ -1110,9 +1100,7 @@ def conv_chain(in0, layers):
         d.relu, d.accumulate = int(bool(s.get("relu"))), int(bool(s.get("accumulate")))
         Hi, Wi, Kc = out.shape[1], out.shape[2], s["N"]
     rc = L.ssd_conv_chain(_ptr(in0), arr, len(layers), B, _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("ssd_conv_chain does not serve these layers")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="ssd_conv_chain does not serve these layers")
 
 
 def conv2d_fwd_relubits(x, w, bias, stride, pad_t, pad_l, Ho, Wo, bits, out=None, ws=None):
@@ -1128,9 +1116,7 @@ def conv2d_fwd_relubits(x, w, bias, stride, pad_t, pad_l, Ho, Wo, bits, out=None
     wbuf = _splitk_ws(ws)
     rc = L.ssd_conv2d_fwd_relubits(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(bits), B, H, W, Cin, Cout, k, stride, pad_t, pad_l,
                                    Ho, Wo, _ptr(wbuf), wbuf.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("this layer's kernel does not write sign bits")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="this layer's kernel does not write sign bits")
     return out
 
 
@@ -1148,9 +1134,7 @@ def conv2d_bwd_data_bits(dy, w_t, bits, x_shape, stride, pad_t, pad_l, accumulat
     wbuf = _splitk_ws(ws)
     rc = L.ssd_conv2d_bwd_data_bits(_ptr(dy), _ptr(w_t), _ptr(bits), _ptr(out), B, H, W, Cin, cpad, k, stride, pad_t, pad_l, Ho, Wo,
                                     1 if accumulate else 0, _ptr(wbuf), wbuf.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("this layer's kernel does not read sign bits")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="this layer's kernel does not read sign bits")
     return out
 
 
@@ -1171,9 +1155,7 @@ def conv2d_bwd_data_wgrad_first(dy, w_t, bits, image, dw=None, dbias=None, ws=No
     wbuf = (ws or _conv_ws).get(L.ssd_conv2d_bwd_data_wgrad_first_workspace_bytes(B, H, W), dy.device)
     rc = L.ssd_conv2d_bwd_data_wgrad_first(_ptr(dy), _ptr(w_t), _ptr(bits), _ptr(image), _ptr(dw), _ptr(dbias), B, H, W, _ptr(wbuf),
                                            wbuf.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("maps smaller than 16x16 take the two separate calls")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="maps smaller than 16x16 take the two separate calls")
     return dw, dbias
 
 
@@ -1194,9 +1176,7 @@ def conv2d_bwd_data_unpool(dy, w_t, relu_src, pool_code, full_shape, out=None, w
         assert pooled_out.shape == (B, H, W, Cin)
     rc = L.ssd_conv2d_bwd_data_unpool(_ptr(dy), _ptr(w_t), _ptr(relu_src), _ptr(pool_code), _ptr(pooled_out), _ptr(out), B, H, W, Cin,
                                       cpad, Hf, Wf, _ptr(wbuf), wbuf.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("no LDS-patch kernel for this layer")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="no LDS-patch kernel for this layer")
     return out
 
 
@@ -1232,9 +1212,7 @@ def conv2d_bwd_weight_batched(layers, ws=None):
     nbytes = L.ssd_conv2d_bwd_weight_batched_workspace_bytes(arr, len(layers))
     wbuf = (ws or _conv_ws).get(nbytes, layers[0][0].device)
     rc = L.ssd_conv2d_bwd_weight_batched(arr, len(layers), _ptr(wbuf), wbuf.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("ssd_conv2d_bwd_weight_batched does not serve these layers")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="ssd_conv2d_bwd_weight_batched does not serve these layers")
 
 
 def conv2d_bwd_weight_unpooled(x, dpool, pool_code, dw=None, dbias=None, want_bias=True, ws=None):
@@ -1256,9 +1234,7 @@ def conv2d_bwd_weight_unpooled(x, dpool, pool_code, dw=None, dbias=None, want_bi
     wbuf = (ws or _conv_ws).get(nbytes, x.device)
     rc = L.ssd_conv2d_bwd_weight_unpooled(_ptr(x), _ptr(dpool), _ptr(pool_code), _ptr(dw), _ptr(dbias), B, H, W, Cin, Cout, Hp, Wp,
                                           _ptr(wbuf), wbuf.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("no structured-sparse weight-gradient kernel for this layer")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="no structured-sparse weight-gradient kernel for this layer")
     return dw, dbias
 
 
@@ -1284,12 +1260,24 @@ def box_prep(box_tlwh, gt_off, src_hw):
     return out
 
 
-AUG_PHOTO, AUG_EXPAND, AUG_CROP, AUG_FLIP = 1, 2, 4, 8
-AUG_ALL = AUG_PHOTO | AUG_EXPAND | AUG_CROP | AUG_FLIP
-# one ssd_augment_params record (include/ssd_hip.h): 16 int32 fields, then 4 float32
-AUG_PARAM_FIELDS = ("stages", "mode", "trial", "photo", "canvas_w", "canvas_h", "off_x", "off_y", "patch_x", "patch_y",
-                    "patch_w", "patch_h", "flip", "n_boxes", "reserved0", "reserved1", "delta", "alpha", "saturation", "hue")
-AUG_PARAM_DTYPE = np.dtype([(n, np.int32) for n in AUG_PARAM_FIELDS[:16]] + [(n, np.float32) for n in AUG_PARAM_FIELDS[16:]])
+AUG_PHOTO, AUG_EXPAND, AUG_CROP, AUG_FLIP, AUG_ALL = (_lib.CONSTANTS["SSD_AUG_" + n] for n in ("PHOTO", "EXPAND", "CROP", "FLIP", "ALL"))
+
+
+def _record_dtype(struct):
+    """A header struct of scalars as a numpy record dtype at the struct's own offsets; `reserved[2]` -> reserved0, reserved1."""
+    names, formats, offsets = [], [], []
+    for name, ctype in struct._fields_:
+        array = hasattr(ctype, "_length_")
+        elem = ctype._type_ if array else ctype
+        for i in range(ctype._length_ if array else 1):
+            names.append(name + str(i) if array else name)
+            formats.append(np.dtype(elem))
+            offsets.append(getattr(struct, name).offset + i * ctypes.sizeof(elem))
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": ctypes.sizeof(struct)})
+
+
+AUG_PARAM_DTYPE = _record_dtype(_lib.AugmentParams)               # one ssd_augment_params record
+AUG_PARAM_FIELDS = AUG_PARAM_DTYPE.names
 
 
 class AugmentSpec:
@@ -1439,9 +1427,7 @@ def conv3x3_fwd_mxfp8(xq, xs, wq, ws, bias, relu=True, out=None):
         out = torch.empty((B, H, W, Cout), dtype=torch.bfloat16, device=xq.device)
     rc = L.ssd_conv3x3_fwd_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out), B, H, W, Cin, Cout, 1 if relu else 0,
                                  _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("block-scaled fp8 forward needs Cin % 128 == 0")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="block-scaled fp8 forward needs Cin % 128 == 0")
     return out
 
 
@@ -1467,10 +1453,8 @@ def conv2d_fwd_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, w
     rc = L.ssd_conv2d_fwd_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
                                 _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout, k,
                                 stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("block-scaled fp8 forward needs Cin % 128 == 0, k in (1, 3), stride in (1, 2), Cout % 8 == 0 "
-                                  "and Cout % 32 == 0 for an fp8 output")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="block-scaled fp8 forward needs Cin % 128 == 0, k in (1, 3), stride in (1, 2), Cout % 8 == 0 "
+                               "and Cout % 32 == 0 for an fp8 output")
     if want_bf16 and want_fp8:
         return out, out_q, out_scale
     return out if want_bf16 else (out_q, out_scale)
@@ -1500,9 +1484,7 @@ def conv2d_fwd_pool_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, re
     rc = L.ssd_conv2d_fwd_pool_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
                                      _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
                                      k, stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, Hp, Wp, _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("pooled block-scaled fp8 forward needs k = 3, stride 1, Cin % 128 == 0 and Cout % 32 == 0")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="pooled block-scaled fp8 forward needs k = 3, stride 1, Cin % 128 == 0 and Cout % 32 == 0")
     if want_bf16 and want_fp8:
         return out, out_q, out_scale
     return out if want_bf16 else (out_q, out_scale)
@@ -1538,9 +1520,7 @@ def conv2d_bwd_data_mxfp8(dyq, dys, wtq, wts, relu_src, x_shape, stride, pad_t, 
     rc = L.ssd_conv2d_bwd_data_mxfp8(_ptr(dyq), _ptr(dys), _ptr(wtq), _ptr(wts), _ptr(relu_src), _ptr(out) if want_bf16 else None,
                                      _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
                                      k, pad_t, pad_l, Ho, Wo, 1 if accumulate else 0, _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("block-scaled fp8 data gradient needs Cout % 128 == 0, Cin % 32 == 0 and k in (1, 3)")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="block-scaled fp8 data gradient needs Cout % 128 == 0, Cin % 32 == 0 and k in (1, 3)")
     if want_bf16 and want_fp8:
         return out, out_q, out_scale
     return out if want_bf16 else (out_q, out_scale)
@@ -1558,9 +1538,7 @@ def add_relu_fwd_mxfp8(a, b, out=None, q=None, scale=None):
     if scale is None:
         scale = torch.empty(a.shape[:-1] + (a.shape[-1] // 32,), dtype=torch.uint8, device=a.device)
     rc = L.ssd_add_relu_fwd_mxfp8(_ptr(a), _ptr(b), _ptr(out), _ptr(q), _ptr(scale), a.numel(), _stream())
-    if rc == _lib.SSD_ERR_UNSUPPORTED:
-        raise NotImplementedError("add_relu_fwd_mxfp8")
-    _lib.check(rc)
+    _lib.check(rc, unsupported="add_relu_fwd_mxfp8")
     return out, q, scale
 
 

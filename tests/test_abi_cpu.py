@@ -83,6 +83,166 @@ def test_round4_entries_refuse_on_the_host():
     assert L.ssd_heads_bwd_data_sparse_levels(None, None, 4, 3, None, 0, None) != _lib.SSD_OK
 
 
+def test_every_declared_function_has_a_derived_prototype():
+    """The binding is parsed from the header: no prototype may be lost on the way."""
+    from ssd_object_detection_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssd_hip.h")).read(), flags=re.S)
+    assert len(_lib._SIGNATURES) == len(re.findall(r"\b(ssd_[a-z0-9_]+)\s*\(", text)) == len(declared_functions())
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "ssd_hip.h"))
+    assert (_lib.SSD_OK, _lib.SSD_ERR_ASSERT, _lib.SSD_ERR_VALUE, _lib.SSD_ERR_WORKSPACE, _lib.SSD_ERR_LAUNCH,
+            _lib.SSD_ERR_UNSUPPORTED) == (0, -1, -2, -3, -4, -5)
+    assert (_lib.SSD_MAX_LEVELS, _lib.SSD_CHAIN_MAX_LAYERS, _lib.SSD_CHAIN_PACK_MAX) == (8, 8, 16)
+    assert _lib.SSD_GRID_VERIFIED == 0x5D5D0001 and _lib.SSD_LOSS_MAX_CLASSES == 303          # a hex and a decimal #define
+    from ssd_object_detection_amd import ops
+    assert (ops.AUG_PHOTO, ops.AUG_EXPAND, ops.AUG_CROP, ops.AUG_FLIP, ops.AUG_ALL) == (1, 2, 4, 8, 15)
+
+
+def test_pinned_signatures():
+    """Entry points spelled out by hand, one or more for every row of the type map and of the pointer rule."""
+    from ssd_object_detection_amd import _lib
+    VP, I, F, D, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+    P = ctypes.POINTER
+    want = {
+        "ssd_adam_step": (I, [VP, VP, VP, VP, VP, ctypes.c_longlong, VP, VP, F, F, F, F, F, VP]),
+        "ssd_match_encode": (I, [VP, VP, VP, I, I, I, VP, VP, I, P(_lib.PriorGrid), D, VP, VP, VP, VP, VP, Z, VP]),
+        "ssd_augment_plan": (I, [VP, VP, VP, VP, I, I, I, ctypes.c_uint64, ctypes.c_int64, VP, VP, VP, VP, VP]),
+        "ssd_heads_bwd_data_sparse_levels": (I, [P(_lib.HeadGrads), P(_lib.HeadLayers), I, ctypes.c_uint, VP, Z, VP]),
+        "ssd_conv2d_bwd_weight_workspace_bytes": (Z, [I] * 7),
+        "ssd_dev_mfma_calibration_flops": (D, [I]),
+        "ssd_status_string": (ctypes.c_char_p, [I]),
+        "ssd_conv2d_fwd": (I, [VP, VP, VP, VP, I, I, I, I, I, I, I, I, I, I, I, I, VP, Z, VP]),
+        "ssd_priors": (I, [VP, I, VP, VP, VP, D, VP, VP]),                      # host arrays: addresses like any other
+        "ssd_dev_knob": (I, [ctypes.c_char_p, I]),
+        "ssd_conv_chain": (I, [VP, P(_lib.ChainLayer), I, I, VP]),
+        "ssd_hip_abi_version": (I, []),
+    }
+    for name, (res, args) in want.items():
+        got_res, got_args = _lib._SIGNATURES[name]
+        assert got_res is res, (name, got_res)
+        assert got_args == args, (name, got_args)
+    fn = _lib.lib().ssd_adam_step
+    assert fn.restype is I and list(fn.argtypes) == want["ssd_adam_step"][1]
+
+
+LAYOUT_STRUCTS = (("ssd_prior_grid", "PriorGrid"), ("ssd_head_grads", "HeadGrads"), ("ssd_head_layers", "HeadLayers"),
+                  ("ssd_chain_layer", "ChainLayer"), ("ssd_chain_pack", "ChainPack"), ("ssd_wgrad_item", "WgradItem"),
+                  ("ssd_augment_params", "AugmentParams"))
+
+
+def test_struct_layouts_equal_the_compilers(tmp_path):
+    """sizeof and every offsetof as the host C++ compiler lays the header's structs out, against the derived ctypes classes
+    and the numpy record of ssd_augment_params."""
+    import subprocess
+    from ssd_object_detection_amd import _lib, ops
+    assert set(_lib.STRUCTS) == {c for c, _ in LAYOUT_STRUCTS}
+    lines = ['#include <cstdio>', '#include <cstddef>', '#include "ssd_hip.h"', 'int main() {']
+    for cname, pyname in LAYOUT_STRUCTS:
+        cls = getattr(_lib, pyname)
+        assert cls is _lib.STRUCTS[cname]
+        lines.append('    std::printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
+        for field, _ in cls._fields_:
+            lines.append('    std::printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (cname, field, cname, field, cname, field))
+    lines += ['    return 0;', '}', '']
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    subprocess.check_call([os.environ.get("CXX", "c++"), "-std=c++11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    seen = {}
+    for row in subprocess.check_output([str(exe)], text=True).split("\n"):
+        if row:
+            cname, key, *nums = row.split()
+            seen.setdefault(cname, {})[key] = tuple(int(v) for v in nums)
+    for cname, pyname in LAYOUT_STRUCTS:
+        cls = getattr(_lib, pyname)
+        got = {"sizeof": (ctypes.sizeof(cls),)}
+        got.update({f: (getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_})
+        assert got == seen[cname], (cname, got, seen[cname])
+    # the field names the six hand-written classes had
+    assert [f for f, _ in _lib.PriorGrid._fields_] == ["levels", "grid_h", "grid_w", "per_cell", "verified"]
+    assert [f for f, _ in _lib.HeadGrads._fields_] == ["levels", "hw", "per_cell", "npad", "rows", "row_of_pixel", "pixel_of_row",
+                                                       "count"]
+    assert [f for f, _ in _lib.HeadLayers._fields_] == ["levels", "H", "W", "Cin", "cout", "x", "w_tap", "relu_bits", "relu_src",
+                                                        "dx", "dw", "dbias"]
+    assert [f for f, _ in _lib.ChainLayer._fields_] == ["w", "bias", "out", "mask_bits", "mask_src", "relu_bits", "Hi", "Wi", "Kc",
+                                                        "Ho", "Wo", "N", "ksize", "mul", "div", "pad_t", "pad_l", "relu", "accumulate"]
+    assert [f for f, _ in _lib.ChainPack._fields_] == ["src", "dst", "N", "K"]
+    assert [f for f, _ in _lib.WgradItem._fields_] == ["x", "dy", "dw", "dbias", "B", "H", "W", "Cin", "Cout", "ldy", "ksize", "stride",
+                                                       "pad_t", "pad_l", "Ho", "Wo"]
+    # the numpy record of ssd_augment_params: the compiler's size and offsets, arrays flattened
+    aug = seen["ssd_augment_params"]
+    dt = ops.AUG_PARAM_DTYPE
+    assert dt.itemsize == aug["sizeof"][0] == 80
+    assert ops.AUG_PARAM_FIELDS == ("stages", "mode", "trial", "photo", "canvas_w", "canvas_h", "off_x", "off_y", "patch_x",
+                                    "patch_y", "patch_w", "patch_h", "flip", "n_boxes", "reserved0", "reserved1", "delta", "alpha",
+                                    "saturation", "hue") == dt.names
+    for name in dt.names:
+        want = aug["reserved"][0] + 4 * int(name[-1]) if name.startswith("reserved") else aug[name][0]
+        assert dt.fields[name][1] == want, name
+        assert dt.fields[name][0] == (np.float32 if name in ("delta", "alpha", "saturation", "hue") else np.int32), name
+
+
+PARSER_FRAGMENT = """
+#define SSD_N 3   /* a bound */
+typedef enum { SSD_A = 2, SSD_B, SSD_C = 0x10 } ssd_e;
+typedef struct {
+    int a, b[SSD_N];     /* a comma list with an array in it */
+    const void* p;
+    float* q[2], *r;
+    int32_t c;
+} ssd_t;
+int ssd_f(const ssd_t* t, long long n,
+          const float* x, size_t bytes);
+size_t ssd_g(void);
+"""
+
+
+def test_parser_reads_the_headers_idioms_and_refuses_the_rest():
+    import pytest
+    from ssd_object_detection_amd import _lib
+    VP = ctypes.c_void_p
+    constants, structs, signatures = _lib.parse_header(PARSER_FRAGMENT)
+    assert constants == {"SSD_N": 3, "SSD_A": 2, "SSD_B": 3, "SSD_C": 16}
+    assert list(structs) == ["ssd_t"]
+    assert structs["ssd_t"]._fields_ == [("a", ctypes.c_int), ("b", ctypes.c_int * 3), ("p", VP), ("q", VP * 2), ("r", VP),
+                                         ("c", ctypes.c_int32)]
+    assert signatures == {"ssd_f": (ctypes.c_int, [ctypes.POINTER(structs["ssd_t"]), ctypes.c_longlong, VP, ctypes.c_size_t]),
+                          "ssd_g": (ctypes.c_size_t, [])}
+    for bad in ("int ssd_x(short a);",                                    # a scalar outside the type map
+                "short ssd_x(int a);",                                    # ... as the return type
+                "int ssd_x(unsigned int a);",                             # a spelling the header does not use
+                "typedef struct { int a; short b; } ssd_s;",              # a member outside the type map
+                "typedef struct { int a[SSD_UNKNOWN]; } ssd_s;",          # a bound that is no literal and no #define
+                "typedef struct { int (*fn)(int); } ssd_s;",              # not a plain member
+                "int ssd_ok(int a); static int x = 3;"):                  # not a prototype at all
+        with pytest.raises(TypeError, match="ssd_hip.h"):
+            _lib.parse_header(bad)
+
+
+def test_a_missing_header_is_reported(monkeypatch):
+    import pytest
+    from ssd_object_detection_amd import _lib
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    with pytest.raises(RuntimeError, match="ssd_hip.h is missing"):
+        _lib._read_header()
+
+
+def test_check_maps_statuses_to_exceptions():
+    import pytest
+    from ssd_object_detection_amd import _lib
+    with pytest.raises(ValueError):
+        _lib.check(_lib.SSD_ERR_UNSUPPORTED)
+    with pytest.raises(NotImplementedError) as e:
+        _lib.check(_lib.SSD_ERR_UNSUPPORTED, unsupported="m")
+    assert e.value.args == ("m",)
+    with pytest.raises(ValueError):
+        _lib.check(_lib.SSD_ERR_VALUE, unsupported="m")
+    with pytest.raises(AssertionError):
+        _lib.check(_lib.SSD_ERR_ASSERT, unsupported="m")
+    with pytest.raises(RuntimeError):
+        _lib.check(_lib.SSD_ERR_WORKSPACE, unsupported="m")
+    assert _lib.check(_lib.SSD_OK, unsupported="m") is None and _lib.check(_lib.SSD_OK) is None
+
+
 def test_synthetic_generator_matches_fixture_inputs():
     from ssd_object_detection_amd.data_loaders.synthetic import synth_gt
     z = np.load(os.path.join(ROOT, "tests", "golden", "match_synth.npz"))
