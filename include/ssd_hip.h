@@ -686,6 +686,47 @@ int ssd_maxpool3x3s2_fwd(const void* x, void* y, void* code, int B, int H, int W
 int ssd_maxpool3x3s2_bwd(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int Ho, int Wo, int pad_t, int pad_l,
                          void* stream);
 /* ------------------------------------------------------------------------------------------
+ * Pieces of the SSD paper's VGG-16 trunk (Liu et al. 2016, section 3.1: `pool5` 3x3 / stride 1 and the dilated `fc6`, 3x3,
+ * dilation 6, 512 -> 1024 on the 19x19 map; no reference counterpart: the reference truncates VGG-16 at block3 and has no
+ * dilation).  Semantics are Keras / TensorFlow's Conv2D(3, dilation_rate=d, padding="same"), MaxPooling2D(3, strides=1,
+ * padding="same") and their tape.gradient.  No network of this project launches them yet.
+ *
+ * Atrous convolution: kernel 3x3, stride 1, padding `dilation` on every side, output H x W.  Tap (ty, tx) of output pixel
+ * (oy, ox) reads input pixel (oy + (ty-1) d, ox + (tx-1) d), or zero outside the map; a tap that is outside for every pixel
+ * (d >= H for ty != 1, d >= W for tx != 1) is skipped, so any d >= max(H, W) leaves the centre tap alone.  Layouts are those of
+ * ssd_conv2d_*: x, y, dy, dx bf16 NHWC; w bf16 [Cout][3][3][Cin]; w_t exactly what ssd_weight_transpose produces,
+ * [Cin][3][3][Cout_pad], spatially flipped (with symmetric padding the data gradient is the same dilated convolution of dy with
+ * w_t); bias fp32 [Cout] or NULL; dw fp32 [Cout][3][3][Cin], written, not accumulated (the dead taps: zeros); dbias fp32 [Cout]
+ * or NULL; dy of the weight gradient [B,H,W,ldy], first Cout channels used.
+ * Arithmetic: bf16 products accumulated in fp32 on the MFMA; y is rounded to bf16 once, after the bias and after max(., 0)
+ * where relu; ssd_conv2d_atrous_bwd_data writes dx = bf16(conv_T), with accumulate dx = bf16(float(dx) + conv_T), either then
+ * zeroed where relu_src <= 0 (relu_src: NULL, or the forward activation, which may be stored in dx's place as for
+ * ssd_conv2d_bwd_data).  No floating-point atomics: dw and dbias are fixed-order sums of partial sums in ws, bitwise
+ * reproducible; ws needs no initial contents and exactly ssd_conv2d_atrous_bwd_weight_workspace_bytes(...) bytes.
+ * Supported: Cin % 64 == 0 (64 ... 1024 and beyond), Cout % 8 == 0 and Cout_pad % 8 == 0 (8 ... 1024 and beyond), ldy >= Cout
+ * and ldy % 8 == 0, every operand and output below 2^31 bytes (32-bit offsets into buffer descriptors); any d >= 1.
+ *
+ * ssd_maxpool3x3s1_fwd / _bwd: windows clipped at the map's edge; code u32 [B*H*W*C/8], one nibble per element in the packing
+ * of ssd_maxpool3x3s2_fwd = 3 dy + dx of the FIRST maximum in window order, 15 = the maximum is <= 0; the backward pass writes
+ * dx[p] = the sum of dy over the (up to nine) windows whose code names p, gathered per input pixel in window order, in fp32,
+ * rounded once: deterministic.  C % 8 == 0, B*H*W*C < 2^31.
+ *
+ * Refusals, decided on the host before anything is launched.  SSD_ERR_VALUE: a NULL required pointer (everything but bias,
+ * relu_src and dbias); B, H, W, a channel count or dilation < 1; an output that overlaps an input (relu_src excepted).
+ * SSD_ERR_WORKSPACE: ws NULL or smaller than the query (as ssd_conv2d_bwd_weight).  SSD_ERR_UNSUPPORTED (the size query
+ * returns 0): a shape outside the supported range above.
+ * ---------------------------------------------------------------------------------------- */
+int ssd_conv2d_atrous_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                          int dilation, int relu, void* stream);
+int ssd_conv2d_atrous_bwd_data(const void* dy, const void* w_t, const void* relu_src, void* dx, int B, int H, int W, int Cin,
+                               int Cout_pad, int dilation, int accumulate, void* stream);
+size_t ssd_conv2d_atrous_bwd_weight_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ldy, int dilation);
+int ssd_conv2d_atrous_bwd_weight(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout,
+                                 int ldy, int dilation, void* ws, size_t ws_bytes, void* stream);
+int ssd_maxpool3x3s1_fwd(const void* x, void* y, void* code, int B, int H, int W, int C, void* stream);
+int ssd_maxpool3x3s1_bwd(const void* code, const void* dy, void* dx, int B, int H, int W, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward pass of ALL head convolutions (models/ssd_model.py:153-162; 3x3, stride 1, SAME, no activation) from the compact
  * gradient rows of ssd_loss_fwd_bwd_heads -- the part of tape.gradient (:248) behind the loc / conf outputs.  Work is
  * proportional to the rows that carry a gradient (4P of B*A anchors), not to the feature maps; results equal the dense

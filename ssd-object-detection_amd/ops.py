@@ -1593,6 +1593,100 @@ def maxpool3x3s2_bwd(code, dy, x_shape, out=None):
     return out
 
 
+# ---- the SSD paper's VGG-16 pieces: dilated fc6 and the 3x3 / stride-1 pool5 (no network uses them yet) ---------------------
+_ATROUS_RANGE = ("atrous 3x3 convolution: Cin must be a multiple of 64, Cout / Cout_pad / ldy multiples of 8, ldy >= Cout, "
+                 "every tensor below 2^31 bytes; got %s")
+_POOL3S1_RANGE = "3x3 / stride-1 max pooling: C must be a multiple of 8 and the map below 2^31 elements; got %s"
+
+
+def _same_shape(name, t, shape):
+    """A caller's output buffer: contiguous and of the shape this call writes, or ValueError (as _pooled_shapes)."""
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s of shape %s, contiguous %s: this call writes %s" % (name, tuple(t.shape), t.is_contiguous(), tuple(shape)))
+
+
+def conv2d_atrous_fwd(x, w, bias, dilation, relu, out=None):
+    """Conv2D(3, dilation_rate=dilation, padding="same") + bias (+ ReLU): x bf16 [B,H,W,Cin], w bf16 [Cout,3,3,Cin]."""
+    L = _lib.lib()
+    _bf(x); _bf(w)
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    assert w.shape == (Cout, 3, 3, Cin)
+    if out is None:
+        out = torch.empty((B, H, W, Cout), dtype=torch.bfloat16, device=x.device)
+    _same_shape("out", out, (B, H, W, Cout))
+    _lib.check(L.ssd_conv2d_atrous_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), B, H, W, Cin, Cout, dilation, 1 if relu else 0,
+                                       _stream()),
+               unsupported=_ATROUS_RANGE % ((B, H, W, Cin, Cout),))
+    return out
+
+
+def conv2d_atrous_bwd_data(dy, w_t, relu_src, x_shape, dilation, accumulate=False, out=None):
+    """Its data gradient: dy bf16 [B,H,W,Cout_pad], w_t = weight_transpose(w) [Cin,3,3,Cout_pad]; out (+)= conv_T, then zeroed
+    where relu_src <= 0 (relu_src may be `out` itself)."""
+    L = _lib.lib()
+    _bf(dy); _bf(w_t)
+    B, H, W, Cin = x_shape
+    cpad = dy.shape[3]
+    assert dy.shape == (B, H, W, cpad) and w_t.shape == (Cin, 3, 3, cpad)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dy.device)
+    _same_shape("out", out, x_shape)
+    _lib.check(L.ssd_conv2d_atrous_bwd_data(_ptr(dy), _ptr(w_t), _ptr(relu_src), _ptr(out), B, H, W, Cin, cpad, dilation,
+                                            1 if accumulate else 0, _stream()),
+               unsupported=_ATROUS_RANGE % ((B, H, W, Cin, cpad),))
+    return out
+
+
+def conv2d_atrous_bwd_weight(x, dy, Cout, dilation, dw=None, dbias=None, want_bias=True, ws=None):
+    """Its weight and bias gradient (fp32, written): x bf16 [B,H,W,Cin], dy bf16 [B,H,W,ldy] (first Cout channels used)."""
+    L = _lib.lib()
+    _bf(x); _bf(dy)
+    B, H, W, Cin = x.shape
+    ldy = dy.shape[3]
+    assert dy.shape == (B, H, W, ldy)
+    if dw is None:
+        dw = torch.empty((Cout, 3, 3, Cin), dtype=torch.float32, device=x.device)
+    if dbias is None and want_bias:
+        dbias = torch.empty((Cout,), dtype=torch.float32, device=x.device)
+    _same_shape("dw", dw, (Cout, 3, 3, Cin))
+    if dbias is not None:
+        _same_shape("dbias", dbias, (Cout,))
+    nbytes = L.ssd_conv2d_atrous_bwd_weight_workspace_bytes(B, H, W, Cin, Cout, ldy, dilation)
+    wbuf = (ws or _conv_ws).get(nbytes, x.device)
+    _lib.check(L.ssd_conv2d_atrous_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(dbias), B, H, W, Cin, Cout, ldy, dilation,
+                                              _ptr(wbuf), wbuf.numel(), _stream()),
+               unsupported=_ATROUS_RANGE % ((B, H, W, Cin, Cout, ldy),))
+    return dw, dbias
+
+
+def maxpool3x3s1_fwd(x, out=None, code=None):
+    """MaxPooling2D(3, strides=1, padding="same"); returns (y, code), code int32 [B,H,W,C/8] in maxpool3x3s2_fwd's packing."""
+    L = _lib.lib()
+    _bf(x)
+    B, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.bfloat16, device=x.device)
+    if code is None:
+        code = torch.empty((B, H, W, C // 8), dtype=torch.int32, device=x.device)
+    _pooled_shapes((B, H, W), (out, C), (code, C // 8))
+    _lib.check(L.ssd_maxpool3x3s1_fwd(_ptr(x), _ptr(out), _ptr(code), B, H, W, C, _stream()), unsupported=_POOL3S1_RANGE % ((B, H, W, C),))
+    return out, code
+
+
+def maxpool3x3s1_bwd(code, dy, x_shape, out=None):
+    L = _lib.lib()
+    _bf(dy)
+    B, H, W, C = x_shape
+    assert dy.shape == (B, H, W, C) and code.shape == (B, H, W, C // 8) and code.is_contiguous()
+    if out is None:
+        out = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dy.device)
+    _pooled_shapes((B, H, W), (out, C))
+    _lib.check(L.ssd_maxpool3x3s1_bwd(_ptr(code), _ptr(dy), _ptr(out), B, H, W, C, _stream()), unsupported=_POOL3S1_RANGE % ((B, H, W, C),))
+    return out
+
+
 def head_grad_pack(dloc, dconf, hw, per_cell, classes, npad, level_off, out=None):
     L = _lib.lib()
     _bf(dloc); _bf(dconf)
