@@ -891,6 +891,13 @@ int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize,
                               int Wo, int pool, size_t ws_bytes);
 int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
                                    int Ho, int Wo, int accumulate, size_t ws_bytes);
+/* Dynamic LDS bytes of that launch (same dispatch code, same arguments): what the kernel is registered and launched with, to
+ * be set against the 163840 bytes a workgroup may have.  Return: a byte count >= 0 (0: the kernel uses static LDS only), a
+ * negative ssd_status for a shape the call would reject, SSD_ERR_UNSUPPORTED for the persistent pointwise GEMM. */
+int ssd_conv2d_fwd_lds_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
+                             int Wo, int pool, size_t ws_bytes);
+int ssd_conv2d_bwd_data_lds_bytes(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
+                                  int Ho, int Wo, int accumulate, size_t ws_bytes);
 
 /* Development only (no reference counterpart): override one of the library's kernel-selection defaults (names in DESIGN.md
  * section 4, e.g. "SSD_CONV_TILE") for A/B timing of kernel variants or to force a dispatch path in a test, inside one

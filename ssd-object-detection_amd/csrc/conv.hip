@@ -517,6 +517,10 @@ __global__ __launch_bounds__(512) void k_conv_igemm_8ph(const bf16_raw* __restri
 //     left in flight across the barrier (counted vmcnt).
 constexpr int P32_PITCH = 96;
 constexpr int P32_PATCH = 32 * 1024;                       // 324 px x 96 B = 31104 B, rounded to 32 DMA instructions
+// Store stage of k_conv3x3_patch32 / k_conv3x3_p512: side tables in LDS (LdsSide, conv_common.h) unless the launch carries this
+// bit in ConvGeom::ablate -- SSD_EPI_PREFETCH = 0, set by launch_patch: the stage then runs as it did without the tables
+constexpr int EPI_NO_PREFETCH = 256;
+constexpr int P32_OFF_MAP = 2 * P32_PATCH;                 // row map [256] int: over the weight buffers, once the last tap has been read
 
 template <int BN, int EPI, bool FLAT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_conv3x3_patch32(
@@ -760,7 +764,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
             return (gy < ep.pool_h && gx < ep.pool_w) ? ((long long)bb * ep.pool_h + gy) * ep.pool_w + gx : -1;
         };
-        staged_epilogue<EPI, 256, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 64, wave_n * (16 * CT), tid, row_to_m, pool_index);
+        if constexpr (FLAT && (BN == 128 || EPI == EPI_DGRAD)) {
+            // strips: row_to_m is two runtime integer divisions, asked for once per chunk.  The row map goes where the weight
+            // slices were: staged_epilogue writes it behind its first barrier, i.e. after every wave's last fragment read has
+            // retired.  (Block form: row_to_m is a multiply-high; with the table two of its instantiations spilled 4 and 8
+            // bytes more than without, so it keeps calling it.)
+            LdsSide<P32_OFF_MAP, -1, -1> side;
+            side.map = side.fill = !(g.ablate & EPI_NO_PREFETCH);
+            side.signs = side.bias = false;
+            staged_epilogue<EPI, 256, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 64, wave_n * (16 * CT), tid, row_to_m, pool_index, side);
+        } else {
+            staged_epilogue<EPI, 256, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 64, wave_n * (16 * CT), tid, row_to_m, pool_index);
+        }
         return;
     }
     int mrow[PT];
@@ -789,7 +804,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 //   * vmcnt is counted per tap (the tap loop is unrolled and the number of DMA instructions a wave issues per tap is fixed:
 //     table N(T) below), so no wait includes a younger request;
 //   * step s runs on fragments that were read from LDS during step s - 1 (second register set), so its MFMAs start right
-//     after the barrier.
+//     after the barrier;
+//   * the store stage fetches nothing and divides nothing per chunk: the tile's ReLU sign bytes (data gradient) or bias
+//     (forward, heads) are requested in the prologue, ahead of the first patch piece, into LDS above everything the loop uses,
+//     and the tile's row -> pixel map is computed once per row (P5_OFF_SIGNS / _MAP / _BIAS).
 // Measured: within +-10 % of k_conv3x3_patch32 layer by layer (faster on the deep narrow maps,
 // slower at 150x150) -- with either kernel the matrix pipes are busy ~60 % of the time and the waves are parked at the
 // per-tap wait / barrier for most of the rest.
@@ -799,7 +817,14 @@ constexpr int P5_PATCH = P5_NDMA * 1024;                    // 59392 B per buffe
 constexpr int P5_WSLOT = 128 * 64;                          // weight slice of one tap: [128 co][32 k]
 constexpr int P5_OFF_W = 2 * P5_PATCH;
 constexpr int P5_OFF_DUMMY = P5_OFF_W + 4 * P5_WSLOT;       // landing zone of the DMA instructions beyond the patch
-constexpr int P5_LDS = P5_OFF_DUMMY + 1024;
+constexpr int P5_LOOP_LDS = P5_OFF_DUMMY + 1024;           // 152576 B: what the main loop uses
+// side tables of the store stage (LdsSide, conv_common.h), above everything the main loop touches: 163328 of the 163840 B a
+// workgroup may have
+constexpr int P5_OFF_SIGNS = P5_LOOP_LDS;                   // [512][16] ReLU sign bytes of the tile (data gradient)
+constexpr int P5_OFF_MAP = P5_OFF_SIGNS + 512 * 16;         // [512] int: tile row -> output pixel
+constexpr int P5_OFF_BIAS = P5_OFF_MAP + 512 * 4;           // [128] float (forward, heads)
+constexpr int P5_LDS = P5_OFF_BIAS + 128 * 4;
+static_assert(P5_LDS <= 160 * 1024, "k_conv3x3_p512: LDS of one workgroup");
 
 template <int EPI, bool FLAT>
 __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ w, ConvGeom g,
@@ -906,6 +931,41 @@ __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict
 #pragma unroll
         for (int c = 0; c < CT; ++c) fw[c] = ldf(wb + wbase + c * 1024);
     };
+    auto row_to_m = [&](int row) {                          // tile row -> flat output pixel or -1
+        if constexpr (FLAT) return flat_pixel(f0 + row);
+        const int ir = image_row(row >> 4), xx = x0 + (row & 15);
+        return (ir >= 0 && xx < g.Wo) ? ir * g.Wo + xx : -1;
+    };
+    // Side tables of the store stage, requested FIRST: they are the oldest requests in flight, so the prologue's counted wait
+    // below covers them and no count of the tap loop sees them (every N(T) counts requests younger than a weight slice).
+    LdsSide<P5_OFF_MAP, P5_OFF_SIGNS, P5_OFF_BIAS> side;
+    side.map = side.fill = !(g.ablate & EPI_NO_PREFETCH) && staged_ok<EPI>(g, ep);
+    side.signs = side.bias = false;
+    if constexpr (EPI == EPI_DGRAD) {
+        // ReLU sign bytes: one 16-byte piece per tile row, lane = row (wave i: rows 64 i .. 64 i + 63), rows outside the map
+        // out of range = zeros.  Only where every row's piece is whole and 16-byte aligned -- N a multiple of 128, so that all
+        // channel tiles are full and the row pitch N / 8 is a multiple of 16 -- and within the descriptor's 32-bit range;
+        // otherwise, and under mask_src, the store stage reads its signs from global memory as before
+        const long long sign_bytes = (long long)g.M * (g.N >> 3);
+        side.signs = side.map && ep.mask_bits && !ep.mask_src && (g.N & 127) == 0 &&
+                     (reinterpret_cast<unsigned long long>(ep.mask_bits) & 15ull) == 0 && sign_bytes < (1ll << 31) - 16;
+        if (side.signs) {
+            const int m = row_to_m(tid);
+            lds_st4_scoped(smem + P5_OFF_MAP + tid * 4, smem, m);
+            side.fill = false;
+            const __amdgpu_buffer_rsrc_t sres = __builtin_amdgcn_make_buffer_rsrc((void*)ep.mask_bits, 0, (unsigned)sign_bytes, 0x00020000);
+            dma16_buf(sres, smem + P5_OFF_SIGNS + wave * 1024, m >= 0 ? (unsigned)m * (unsigned)(g.N >> 3) + (unsigned)(n0 >> 3) : OOB);
+        }
+    } else {
+        // bias of the tile: 128 floats, waves 0 and 1 (the others request nothing, into the dummy zone: one instruction per wave)
+        side.bias = side.map;
+        if (side.bias) {
+            const __amdgpu_buffer_rsrc_t bres = __builtin_amdgcn_make_buffer_rsrc((void*)ep.bias, 0, ep.bias ? (unsigned)g.N * 4u : 0u, 0x00020000);
+            const int n = n0 + wave * 64 + lane;
+            char* dst = wave < 2 ? smem + P5_OFF_BIAS + wave * 256 : smem + P5_OFF_DUMMY;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(bres, (lds_void*)dst, 4, (wave < 2 && n < g.N) ? (unsigned)n * 4u : OOB, 0, 0, 0);
+        }
+    }
     // prologue: the whole first patch and the first three weight slices; fragments of step 0
 #pragma unroll
     for (int j = 0; j < 8; ++j) dma_piece(0, 0, j, true);
@@ -971,11 +1031,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the refetches past the end have landed before LDS is reused
     if (staged_ok<EPI>(g, ep)) {                             // tile image [512 block pixels][128] over the patch buffers + ring
-        auto row_to_m = [&](int row) {
-            if constexpr (FLAT) return flat_pixel(f0 + row);
-            const int ir = image_row(row >> 4), xx = x0 + (row & 15);
-            return (ir >= 0 && xx < g.Wo) ? ir * g.Wo + xx : -1;
-        };
         auto pool_index = [&](int py, int px) -> long long {    // as in k_conv3x3_patch32
             if (FLAT) return -1;
             int bb = b, gy = (y0 >> 1) + py;
@@ -988,7 +1043,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_p512(const bf16_raw* __restrict
             }
             return (gy < ep.pool_h && gx < ep.pool_w) ? ((long long)bb * ep.pool_h + gy) * ep.pool_w + gx : -1;
         };
-        staged_epilogue<EPI, 512, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 128, wave_n * 64, tid, row_to_m, pool_index);
+        staged_epilogue<EPI, 512, BN, CT, PT, 512>(acc, smem, g, ep, n0, wave_m * 128, wave_n * 64, tid, row_to_m, pool_index, side);
         return;
     }
     int mrow[PT];
@@ -1750,6 +1805,7 @@ template <auto KERN>                         // k_conv3x3_patch32<BN, EPI, FLAT>
 int launch_patch(const IgemmPlan& p, const bf16_raw* x, const bf16_raw* w, const ConvGeom& g, const Epilogue& ep, hipStream_t s) {
     ConvGeom gk = g;                         // what the kernel gets: g with the row strip's image pitch
     gk.d_h1 = make_fastdiv(p.pitch);
+    if (!ssd_knob("SSD_EPI_PREFETCH", 1)) gk.ablate |= EPI_NO_PREFETCH;   // dev: the store stage without its LDS side tables
     auto kern = KERN;
     static OnceLds set; if (ensure_lds(set, reinterpret_cast<const void*>(kern), p.lds) != 0) return SSD_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.lds, s, x, w, gk, ep, p.tiles_x, p.tiles_y, p.nblocks, p.rowflat);
@@ -1874,11 +1930,12 @@ int bwd_data_geom(int B, int H, int W, int Cin, int Cout_pad, int ksize, int str
 
 // what a query answers from the plan: the plan word, or the ACTIVE workgroups of the (first) launch the call resolves to --
 // SSD_ERR_UNSUPPORTED where the plan does not know them (the persistent pointwise GEMM)
-int igemm_answer(int epi, const ConvGeom& g, const EpiArgs& ea, bool takes_pool, bool plain_fwd, size_t ws_bytes, bool want_wgs) {
-    IgemmPlan p;
+int igemm_answer(int epi, const ConvGeom& g, const EpiArgs& ea, bool takes_pool, bool plain_fwd, size_t ws_bytes, int want) {
+    IgemmPlan p;                             // want: 0 the plan word, 1 its active workgroups, 2 its dynamic LDS bytes
     const int rc = igemm_plan(epi, g, ea, takes_pool, plain_fwd, ws_bytes != 0, ws_bytes, &p);
     if (rc != SSD_OK) return rc;
-    if (!want_wgs) return p.word();
+    if (want == 0) return p.word();
+    if (want == 2) return p.id == SSD_PLAN_PW ? SSD_ERR_UNSUPPORTED : p.lds;
     return p.wgs < 0 ? SSD_ERR_UNSUPPORTED : p.wgs;
 }
 
@@ -2023,7 +2080,7 @@ int ssd_conv2d_bwd_data_wgrad_first(const void* dy, const void* w_t, const void*
 
 // ---- dispatch queries: the entry's geometry, the epilogue facts of the call the query stands for (bias and ReLU, every output
 // the entry requires, no ReLU mask), and igemm_plan's answer.  Nothing is launched and no pointer exists ----
-static int conv2d_fwd_query(bool want_wgs, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
+static int conv2d_fwd_query(int want, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho,
                             int Wo, int pool, size_t ws_bytes) {
     ConvGeom g;
     EpiArgs ea = {};
@@ -2032,26 +2089,26 @@ static int conv2d_fwd_query(bool want_wgs, int B, int H, int W, int Cin, int Cou
     ea.pool_out = pool && ssd_knob("SSD_CONV_POOL_FUSE", 1);
     const int rc = pool ? fwd_pool_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, (Ho + 1) / 2, (Wo + 1) / 2, &g)
                         : fwd_geom(B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, &g);
-    return rc != SSD_OK ? rc : igemm_answer(EPI_FWD, g, ea, pool != 0, pool == 0, ws_bytes, want_wgs);
+    return rc != SSD_OK ? rc : igemm_answer(EPI_FWD, g, ea, pool != 0, pool == 0, ws_bytes, want);
 }
 
-static int conv2d_bwd_data_query(bool want_wgs, int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
+static int conv2d_bwd_data_query(int want, int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l,
                                  int Ho, int Wo, int accumulate, size_t ws_bytes) {
     ConvGeom g;
     EpiArgs ea = {};
     ea.out = true; ea.ldo = Cin; ea.accumulate = accumulate;
     const int rc = bwd_data_geom(B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, &g);
-    return rc != SSD_OK ? rc : igemm_answer(EPI_DGRAD, g, ea, false, false, ws_bytes, want_wgs);
+    return rc != SSD_OK ? rc : igemm_answer(EPI_DGRAD, g, ea, false, false, ws_bytes, want);
 }
 
 int ssd_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
                         int pool, size_t ws_bytes) {
-    return conv2d_fwd_query(false, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
+    return conv2d_fwd_query(0, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
 }
 
 int ssd_conv2d_fwd_workgroups(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
                               int pool, size_t ws_bytes) {
-    return conv2d_fwd_query(true, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
+    return conv2d_fwd_query(1, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
 }
 
 int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int classes, size_t ws_bytes) {
@@ -2062,12 +2119,22 @@ int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int cla
 
 int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                              int Wo, int accumulate, size_t ws_bytes) {
-    return conv2d_bwd_data_query(false, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
+    return conv2d_bwd_data_query(0, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
 }
 
 int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                                    int Wo, int accumulate, size_t ws_bytes) {
-    return conv2d_bwd_data_query(true, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
+    return conv2d_bwd_data_query(1, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
+}
+
+int ssd_conv2d_fwd_lds_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                             int pool, size_t ws_bytes) {
+    return conv2d_fwd_query(2, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, pool, ws_bytes);
+}
+
+int ssd_conv2d_bwd_data_lds_bytes(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
+                                  int Wo, int accumulate, size_t ws_bytes) {
+    return conv2d_bwd_data_query(2, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
 }
 
 const char* ssd_conv_plan_name(int plan) {

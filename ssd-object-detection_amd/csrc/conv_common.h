@@ -276,6 +276,27 @@ __device__ __forceinline__ bool staged_ok(const ConvGeom& g, const Epilogue& ep)
 
 struct NoPool { __device__ long long operator()(int, int) const { return -1; } };
 
+// Side tables of the store stage (k_conv3x3_patch32, k_conv3x3_p512): what the stage would otherwise fetch from global memory or
+// recompute per chunk, held in LDS outside the tile image.  Offsets are bytes from the kernel's LDS base, -1 = the kernel has no
+// such table; the flags are wave-uniform and say whether the launch uses it (SSD_EPI_PREFETCH = 0, or a shape the prefetch does
+// not serve: the stage then works as it does without tables).  Values, operands and their order are the same either way.
+//   row map  [BM] int          row_to_m(row) of every tile row: on strips row_to_m is two runtime integer divisions, and the
+//                              store loop asked for it once per chunk
+//   signs    [BM][16] bytes    DGRAD: the ReLU sign bytes of the tile (mask_bits), fetched by LDS-DMA in the kernel's prologue
+//   bias     [BN] float        FWD / HEAD: the tile's bias (zeros past N), fetched there too
+struct NoSide {
+    static constexpr int MAP_OFF = -1, SIGN_OFF = -1, BIAS_OFF = -1;
+    bool map = false, fill = false, signs = false, bias = false;
+};
+template <int MAP_OFF_, int SIGN_OFF_, int BIAS_OFF_>
+struct LdsSide {
+    static constexpr int MAP_OFF = MAP_OFF_, SIGN_OFF = SIGN_OFF_, BIAS_OFF = BIAS_OFF_;
+    bool map;                                 // the store stage reads m from the row map
+    bool fill;                                // ... which staged_epilogue writes first (false: the kernel already has)
+    bool signs;                               // the sign bytes of the tile are in LDS
+    bool bias;                                // the bias of the tile is in LDS
+};
+
 // LDS accesses that carry an alias scope (the __restrict__ pair, inlined).  The compiler's waitcnt pass puts s_waitcnt vmcnt(0)
 // in front of every LDS access WITHOUT scope information while an LDS-DMA is in flight -- in a persistent kernel that
 // prefetches its next block by DMA (k_conv3x3_c64b) that is a wait for the next block's patch in the middle of the epilogue.
@@ -291,6 +312,10 @@ __device__ __forceinline__ void lds_st16_scoped(char* __restrict__ p, const char
 __device__ __forceinline__ void lds_st8_scoped(char* __restrict__ p, const char* __restrict__ other, uint2 v) {
     (void)other;
     *reinterpret_cast<uint2*>(p) = v;
+}
+__device__ __forceinline__ void lds_st4_scoped(char* __restrict__ p, const char* __restrict__ other, int v) {
+    (void)other;
+    *reinterpret_cast<int*>(p) = v;
 }
 // LDS fragment read that carries an alias scope (see lds_read_tr16_scoped): keeps the compiler's waitcnt pass from ordering
 // it behind LDS-DMA requests that are in flight for OTHER buffers.
@@ -328,10 +353,16 @@ constexpr int PATCH_PIX = PATCH_W * PATCH_W;               // 324
 // Second half of the staged epilogue: the [BM px][BN ch] bf16 tile image in LDS (layout above; FWD: bias and ReLU already
 // applied) leaves as whole 16-byte chunks of contiguous rows; DGRAD applies accumulate / ReLU mask here, FWD the fused pooling.
 // Caller: a barrier between the last write of the image and this call.
-template <int EPI, int BM, int BN, int NT, typename RowMap, typename PoolMap, bool DG_BATCHED = true>
-__device__ __forceinline__ void staged_store(char* smem, const ConvGeom& g, const Epilogue& ep, int n0, int tid, RowMap row_to_m,
-                                             PoolMap pool_index) {
+template <int EPI, int BM, int BN, int NT, typename RowMap, typename PoolMap, bool DG_BATCHED = true, typename Side = NoSide>
+__device__ __forceinline__ void staged_store(char* smem, const ConvGeom& g, const Epilogue& ep, int n0, int tid, RowMap row_to_m_fn,
+                                             PoolMap pool_index, Side side = Side{}) {
     constexpr int CPR = BN / 8;                 // 16-byte chunks per tile row
+    auto row_to_m = [&](int row) -> int {       // from the row map where the launch keeps one
+        if constexpr (Side::MAP_OFF >= 0) {
+            if (side.map) return *reinterpret_cast<const int*>(smem + Side::MAP_OFF + row * 4);
+        }
+        return row_to_m_fn(row);
+    };
     if constexpr (EPI == EPI_HEAD) {
         // A pixel's loc run (per_cell x 4) and conf run (per_cell x classes) are contiguous in the outputs but only 2-byte
         // aligned in general.  When the anchor counts are even (all six SSD levels: 4 or 6 per cell, even level offsets and
@@ -383,6 +414,25 @@ __device__ __forceinline__ void staged_store(char* smem, const ConvGeom& g, cons
             // finished: one round trip per batch.  (The registers are free: the accumulators went to LDS above.)
             constexpr int DG_BATCH = ITER % 4 == 0 ? 4 : (ITER % 2 == 0 ? 2 : 1);
             const long long nb8 = g.N >> 3;
+            bool lds_signs = false;             // the sign bytes are in LDS (the caller saw mask_bits and no mask_src)
+            if constexpr (Side::SIGN_OFF >= 0) {
+                static_assert(Side::SIGN_OFF < 0 || CPR == 16, "sign table: 16 bytes per tile row");
+                lds_signs = side.signs;
+            }
+            if (lds_signs && !ep.accumulate && !ep.up_code) {
+                // nothing to fetch: LDS read, gate, store -- no batches, no wait on a load
+#pragma unroll 4
+                for (int it = 0; it < ITER; ++it) {
+                    const int idx = it * NT + tid;
+                    const int row = idx / CPR, ch = idx - row * CPR;
+                    const int n = n0 + ch * 8;
+                    const int m = row_to_m(row);
+                    if (m < 0 || n >= g.N) continue;
+                    const uint4 v = lds_ld16_scoped(smem + row * (BN * 2) + (((ch ^ row) & (CPR - 1)) << 4), smem);
+                    const unsigned sb = *reinterpret_cast<const unsigned char*>(smem + Side::SIGN_OFF + idx);
+                    *reinterpret_cast<uint4*>(ep.out + ((long long)m * ep.ldo + n)) = gate_bits8(v, sb);
+                }
+            } else
             for (int it0 = 0; it0 < ITER; it0 += DG_BATCH) {
                 int mm[DG_BATCH], rr[DG_BATCH], cc[DG_BATCH];
                 long long oo[DG_BATCH];
@@ -407,7 +457,7 @@ __device__ __forceinline__ void staged_store(char* smem, const ConvGeom& g, cons
                 if (ep.mask_src) {
 #pragma unroll
                     for (int j = 0; j < DG_BATCH; ++j) mk[j] = *reinterpret_cast<const uint4*>(ep.mask_src + oo[j]);
-                } else if (ep.mask_bits) {
+                } else if (ep.mask_bits && !lds_signs) {
 #pragma unroll
                     for (int j = 0; j < DG_BATCH; ++j) mb[j] = ep.mask_bits[ok[j] ? (long long)mm[j] * nb8 + ((n0 >> 3) + cc[j]) : 0];
                 }
@@ -437,6 +487,7 @@ __device__ __forceinline__ void staged_store(char* smem, const ConvGeom& g, cons
                         };
                         v.x = gate(v.x, mk[j].x); v.y = gate(v.y, mk[j].y); v.z = gate(v.z, mk[j].z); v.w = gate(v.w, mk[j].w);
                     } else if (ep.mask_bits) {
+                        if (lds_signs) mb[j] = *reinterpret_cast<const unsigned char*>(smem + Side::SIGN_OFF + row * CPR + ch);
                         v = gate_bits8(v, mb[j]);
                     }
                     if (ep.up_code) {                             // un-pool: the four positions of the window, winner or zero
@@ -604,18 +655,32 @@ __device__ __forceinline__ void staged_store(char* smem, const ConvGeom& g, cons
 
 // DG_BATCHED = false: the data gradient's chunk-by-chunk store loop (fewer registers: for a kernel at its register limit whose
 // data gradient normally leaves through its own path, k_conv3x3_c64b)
-template <int EPI, int BM, int BN, int CT, int PT, int NT, typename RowMap, typename PoolMap, bool DG_BATCHED = true>
+template <int EPI, int BM, int BN, int CT, int PT, int NT, typename RowMap, typename PoolMap, bool DG_BATCHED = true,
+          typename Side = NoSide>
 __device__ __forceinline__ void staged_epilogue(f32x4_t (&acc)[CT][PT], char* smem, const ConvGeom& g, const Epilogue& ep,
-                                                int n0, int wrow0, int wcol0, int tid, RowMap row_to_m, PoolMap pool_index) {
+                                                int n0, int wrow0, int wcol0, int tid, RowMap row_to_m, PoolMap pool_index,
+                                                Side side = Side{}) {
     constexpr int CPR = BN / 8;                 // 16-byte chunks per tile row
     const int lane = tid & 63;
     __syncthreads();
+    if constexpr (Side::MAP_OFF >= 0) {
+        // one row_to_m per thread covers the tile (after the barrier: the table may lie in a buffer the main loop read from)
+        static_assert(Side::MAP_OFF < 0 || NT >= BM, "row map: one row per thread");
+        if (side.map && side.fill && tid < BM) *reinterpret_cast<int*>(smem + Side::MAP_OFF + tid * 4) = row_to_m(tid);
+    }
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         const int col = wcol0 + c * 16 + (lane >> 4) * 4;
         const int n = n0 + col;
         float b4[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (EPI != EPI_DGRAD) { if (n < g.N) load_bias4(ep, n, g.N, n + 3 < g.N, b4); }
+        bool lds_bias = false;
+        if constexpr (Side::BIAS_OFF >= 0) lds_bias = side.bias;
+        if constexpr (EPI != EPI_DGRAD) {
+            if (lds_bias) {                     // the prologue's copy: bias[n0 + col ..], zeros past N (and without a bias)
+                const float4 bv = *reinterpret_cast<const float4*>(smem + Side::BIAS_OFF + col * 4);
+                b4[0] = bv.x; b4[1] = bv.y; b4[2] = bv.z; b4[3] = bv.w;
+            } else if (n < g.N) load_bias4(ep, n, g.N, n + 3 < g.N, b4);
+        }
 #pragma unroll
         for (int p = 0; p < PT; ++p) {
             const int row = wrow0 + p * 16 + (lane & 15);
@@ -631,7 +696,7 @@ __device__ __forceinline__ void staged_epilogue(f32x4_t (&acc)[CT][PT], char* sm
         }
     }
     __syncthreads();
-    staged_store<EPI, BM, BN, NT, RowMap, PoolMap, DG_BATCHED>(smem, g, ep, n0, tid, row_to_m, pool_index);
+    staged_store<EPI, BM, BN, NT, RowMap, PoolMap, DG_BATCHED, Side>(smem, g, ep, n0, tid, row_to_m, pool_index, side);
 }
 
 // callers without a pooling stage
