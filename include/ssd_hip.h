@@ -418,7 +418,8 @@ int ssd_conv2d_bwd_data_wgrad_first(const void* dy, const void* w_t, const void*
  * pooling that produced the map: dx_full[B,Hf,Wf,Cin] = ssd_maxpool2x2_bwd_argmax(pool_code, ssd_conv2d_bwd_data(...)) in
  * one launch, bit-identical (the un-pooling runs in the convolution's store stage: no pooled gradient in HBM, no second
  * kernel).  Served by the LDS-patch kernels only: SSD_ERR_UNSUPPORTED (nothing launched) for any other layer shape --
- * call the two functions then.
+ * call the two functions then.  H = Hf/2 or (Hf+1)/2, W likewise (VALID / SAME pooling); VALID pooling of an odd Hf or Wf
+ * (2 H < Hf or 2 W < Wf) is SSD_ERR_UNSUPPORTED as well: the row / column that no window covers would not be written.
  * dx_pooled (may be NULL): also receives the gradient w.r.t. the pooled map itself [B,H,W,Cin] -- the compressed form
  * ssd_conv2d_bwd_weight_unpooled reads. */
 int ssd_conv2d_bwd_data_unpool(const void* dy, const void* w_t, const void* relu_src, const void* pool_code, void* dx_pooled,
@@ -878,6 +879,11 @@ int ssd_conv2d_fwd_plan(int B, int H, int W, int Cin, int Cout, int ksize, int s
 int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int classes, size_t ws_bytes);
 int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                              int Wo, int accumulate, size_t ws_bytes);
+/* ssd_conv2d_bwd_data_unpool (arguments as there; has_relu_src: relu_src != NULL): the data-gradient dispatch with the
+ * un-pooling store, which ssd_conv2d_bwd_data_plan does not model (64 -> 64 never runs on k_conv3x3_c64b then).  Answers what
+ * the call would return, its refusals included. */
+int ssd_conv2d_bwd_data_unpool_plan(int B, int H, int W, int Cin, int Cout_pad, int Hf, int Wf, int has_relu_src,
+                                    size_t ws_bytes);
 int ssd_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int ldy, int ksize, int stride, int pad_t, int pad_l,
                                int Ho, int Wo);
 const char* ssd_conv_plan_name(int plan);

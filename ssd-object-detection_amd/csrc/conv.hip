@@ -1928,6 +1928,16 @@ int bwd_data_geom(int B, int H, int W, int Cin, int Cout_pad, int ksize, int str
     return SSD_OK;
 }
 
+// ssd_conv2d_bwd_data_unpool: the pooled map [B,H,W,Cin] against the map before the pooling [B,Hf,Wf,Cin], then the geometry of
+// the 3x3 / stride 1 / pad 1 data gradient in front of the un-pooling store
+int unpool_geom(int B, int H, int W, int Cin, int Cout_pad, int Hf, int Wf, ConvGeom* g) {
+    if (Cin % 8 || Hf <= 0 || Wf <= 0) return SSD_ERR_VALUE;
+    if ((H != Hf / 2 && H != (Hf + 1) / 2) || (W != Wf / 2 && W != (Wf + 1) / 2)) return SSD_ERR_VALUE;
+    if (2 * H < Hf || 2 * W < Wf) return SSD_ERR_UNSUPPORTED;     // VALID pooling of an odd size: the uncovered row / column is not written here
+    if ((long long)B * Hf * Wf * Cin >= (1ll << 32)) return SSD_ERR_VALUE;
+    return bwd_data_geom(B, H, W, Cin, Cout_pad, 3, 1, 1, 1, H, W, g);
+}
+
 // what a query answers from the plan: the plan word, or the ACTIVE workgroups of the (first) launch the call resolves to --
 // SSD_ERR_UNSUPPORTED where the plan does not know them (the persistent pointwise GEMM)
 int igemm_answer(int epi, const ConvGeom& g, const EpiArgs& ea, bool takes_pool, bool plain_fwd, size_t ws_bytes, int want) {
@@ -2031,10 +2041,10 @@ int ssd_conv2d_bwd_data_unpool(const void* dy, const void* w_t, const void* relu
                                void* stream) {
     // 3x3 / stride 1 / pad 1 data gradient w.r.t. a POOLED map [B,H,W,Cin], carried on through the 2x2 / stride-2 max pooling
     // that produced the map (pool_code [B,H,W,Cin/8] of ssd_maxpool2x2_fwd_argmax / ssd_conv2d_fwd_pool): dx_full [B,Hf,Wf,Cin]
-    if (!pool_code || !dx_full || Cin % 8 || Hf <= 0 || Wf <= 0) return SSD_ERR_VALUE;
-    if ((H != Hf / 2 && H != (Hf + 1) / 2) || (W != Wf / 2 && W != (Wf + 1) / 2)) return SSD_ERR_VALUE;
-    if (2 * H < Hf || 2 * W < Wf) return SSD_ERR_UNSUPPORTED;     // VALID pooling of an odd size: the uncovered row / column is not written here
-    if ((long long)B * Hf * Wf * Cin >= (1ll << 32)) return SSD_ERR_VALUE;
+    if (!pool_code || !dx_full) return SSD_ERR_VALUE;
+    ConvGeom g;
+    const int rc = unpool_geom(B, H, W, Cin, Cout_pad, Hf, Wf, &g);
+    if (rc != SSD_OK) return rc;
     return conv2d_bwd_data_impl(dy, w_t, relu_src, dx_pooled, B, H, W, Cin, Cout_pad, 3, 1, 1, 1, H, W, 0, ws, ws_bytes, stream,
                                 pool_code, dx_full, Hf, Wf);
 }
@@ -2120,6 +2130,14 @@ int ssd_conv2d_head_fwd_plan(int B, int H, int W, int Cin, int per_cell, int cla
 int ssd_conv2d_bwd_data_plan(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,
                              int Wo, int accumulate, size_t ws_bytes) {
     return conv2d_bwd_data_query(0, B, H, W, Cin, Cout_pad, ksize, stride, pad_t, pad_l, Ho, Wo, accumulate, ws_bytes);
+}
+
+int ssd_conv2d_bwd_data_unpool_plan(int B, int H, int W, int Cin, int Cout_pad, int Hf, int Wf, int has_relu_src, size_t ws_bytes) {
+    ConvGeom g;
+    EpiArgs ea = {};
+    ea.up_out = true; ea.mask_src = has_relu_src != 0; ea.ldo = Cin;   // (dx_pooled is optional and decides nothing)
+    const int rc = unpool_geom(B, H, W, Cin, Cout_pad, Hf, Wf, &g);
+    return rc != SSD_OK ? rc : igemm_answer(EPI_DGRAD, g, ea, false, false, ws_bytes, 0);
 }
 
 int ssd_conv2d_bwd_data_workgroups(int B, int H, int W, int Cin, int Cout_pad, int ksize, int stride, int pad_t, int pad_l, int Ho,

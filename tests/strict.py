@@ -519,12 +519,14 @@ def conv_case(case):
     return r
 
 
-def fwd_pool_case(case, same):
-    r = conv_case(case)
+def fwd_pool_case(case, same, relu=True, r=None):
+    """conv_case plus the pooled map and the winner codes of its output -- of y_relu, or with relu=False of y: a window whose
+    maximum is <= 0 then keeps its (negative) value under the code 4.  r: a conv_case of `case` to build on (it is copied)."""
+    r = dict(r) if r is not None else conv_case(case)
     Ho, Wo = r["geom"][:2]
     Hp, Wp = ((Ho + 1) // 2, (Wo + 1) // 2) if same else (Ho // 2, Wo // 2)
-    r["yp"], r["code"] = ref_pool(r["y_relu"], 2, 2, 0, 0, Hp, Wp, 4)
-    r["bf16"] += ("yp",)
+    r["yp"], r["code"] = ref_pool(r["y_relu" if relu else "y"], 2, 2, 0, 0, Hp, Wp, 4)
+    r["bf16"] = tuple(r["bf16"]) + ("yp",)
     return r
 
 
@@ -535,7 +537,7 @@ def unpool_case(B, Hf, Wf, C, Cout, same):
     full = ints(g, (B, Hf, Wf, C), (-1, 0, 0, 1, 1, 2, 3))
     _, code = ref_pool(full.float(), 2, 2, 0, 0, H, W, 4)
     r = conv_case((B, H, W, C, Cout, 3, 1, "same"))
-    r["code"], r["full_shape"] = code, (B, Hf, Wf, C)
+    r["code"], r["full_shape"], r["full"] = code, (B, Hf, Wf, C), full
     r["dfull"] = ref_unpool(code, r["dx"], r["full_shape"], 2, 2, 0, 0)
     r["dfull_masked"] = ref_unpool(code, r["dx_masked"], r["full_shape"], 2, 2, 0, 0)
     r["bf16"] += ("dfull", "dfull_masked")
@@ -560,7 +562,7 @@ def wgrad_unpooled_case(B, H, W, Cin, Cout, same, dtype=torch.float32):
     dp = ints(g, (B, Hp, Wp, Cout), (-2, -1, 1, 2))
     dyf = ref_unpool(code, dp.float(), y.shape, 2, 2, 0, 0)
     dw, db = _wgrad(x, dyf, 3, 1, 1, 1, dtype)
-    return dict(x=x, code=code, dp=dp, dw=dw, dbias=db, fp32=((B * H * W, x, dp),), exact=("dw", "dbias"),
+    return dict(x=x, y=y, code=code, dp=dp, dy_full=dyf, dw=dw, dbias=db, fp32=((B * H * W, x, dp),), exact=("dw", "dbias"),
                 f64=lambda: wgrad_unpooled_case(B, H, W, Cin, Cout, same, torch.float64))
 
 
