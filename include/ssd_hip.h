@@ -230,6 +230,10 @@ int ssd_multibox_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype
  *   cls    int32[B*A]  its class (== argmax over all classes wherever cand is set)
  *   box    float[B*A*4] decoded (cx,cy,w,h) in pixels (in_size = 300) for candidates, 0 elsewhere
  *   cand   uint8[B*A]  score > score_thresh && !(p_background > score_thresh)
+ * cls is written for every row (the first index among equal maxima), not only for candidates.  A block of 128 rows of C
+ * floats is staged in dynamic LDS and must fit 150 KiB: C <= 300, SSD_ERR_UNSUPPORTED (nothing launched, nothing written)
+ * beyond; ssd_class_scores and ssd_detect_pairs share the bound.  Launches above 64 KiB (C >= 129) are granted without a
+ * hipFuncAttributeMaxDynamicSharedMemorySize registration (tests/test_detect_strict_gpu.py runs C = 129, 300 and 301).
  * ---------------------------------------------------------------------------------------- */
 int ssd_score_decode(const void* conf, const void* loc, int dtype, const double* priors, int B, int A, int C,
                      float score_thresh, double in_size, float* score, int32_t* cls, float* box,
