@@ -576,6 +576,13 @@ int ssd_maxpool2x2_bwd(const void* x, const void* y, const void* dy, void* dx, i
 int ssd_maxpool2x2_fwd_argmax(const void* x, void* y, void* code, int B, int H, int W, int C, int Ho, int Wo, void* stream);
 int ssd_maxpool2x2_bwd_argmax(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int Ho, int Wo,
                               void* stream);
+/* The un-pooling added onto a dx that already holds a gradient (an activation that feeds a head and a pooling: conv4_3 of
+ * the VGG-16 SSD300): dx[p] = bf16(float(dx[p]) + g) where ssd_maxpool2x2_bwd_argmax would have written a winner's
+ * gradient g at p (one fp32 addition, one rounding); every other element of dx keeps its bits: the losers of a window, code
+ * 4, and the last row / column that a VALID pooling of an odd map does not cover.  No memset, no atomics; codes, packing
+ * and shape rules as above (C % 8 == 0, SAME when 2*Ho > H).  SSD_ERR_VALUE before any launch otherwise. */
+int ssd_maxpool2x2_bwd_argmax_accumulate(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int Ho,
+                                         int Wo, void* stream);
 /* Block-scaled fp8 forward convolution (BASELINE configs[4]: "fp8 MFMA convs"; no reference counterpart -- the reference's
  * convolutions are fp32 TensorFlow ops, models/ssd_model.py:86-93 for the >= 256-channel 3x3 layers this serves).  MX format: OCP
  * e4m3 elements, one E8M0 scale byte (2^(s-127)) per 32 consecutive channels, multiplied on v_mfma_scale_f32_16x16x128_f8f6f4.
@@ -694,7 +701,7 @@ int ssd_maxpool3x3s2_bwd(const void* code, const void* dy, void* dx, int B, int 
  * Pieces of the SSD paper's VGG-16 trunk (Liu et al. 2016, section 3.1: `pool5` 3x3 / stride 1 and the dilated `fc6`, 3x3,
  * dilation 6, 512 -> 1024 on the 19x19 map; no reference counterpart: the reference truncates VGG-16 at block3 and has no
  * dilation).  Semantics are Keras / TensorFlow's Conv2D(3, dilation_rate=d, padding="same"), MaxPooling2D(3, strides=1,
- * padding="same") and their tape.gradient.  No network of this project launches them yet.
+ * padding="same") and their tape.gradient.  Launched by SSDEngine on engine.VGG16_SSD300_TRUNK (nodes 17 and 18).
  *
  * Atrous convolution: kernel 3x3, stride 1, padding `dilation` on every side, output H x W.  Tap (ty, tx) of output pixel
  * (oy, ox) reads input pixel (oy + (ty-1) d, ox + (tx-1) d), or zero outside the map; a tap that is outside for every pixel

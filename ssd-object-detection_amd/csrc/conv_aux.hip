@@ -225,6 +225,52 @@ __global__ void k_maxpool_bwd_argmax(const unsigned* __restrict__ code, const bf
         }
 }
 
+// The same un-pooling added onto a dx that already holds a gradient (an activation that feeds a head as well as the
+// pooling): dx[p] = bf16(float(dx[p]) + dy) at each window's winner, one fp32 addition and one rounding; every other
+// element keeps its bits (code 4, the losers of a window, and the row / column a VALID pooling of an odd map leaves out,
+// which no thread visits).  A window has one owner thread, so its four dx chunks are read and written by that thread
+// alone: no memset, no atomics.  The four loads are issued before the first store.  Per dx element 2 B read + 2 B
+// written + 1/4 of (2 B dy + 1/2 B code), against 2 B written + the same quarter for the overwrite form.
+__global__ void k_maxpool_bwd_argmax_acc(const unsigned* __restrict__ code, const bf16_raw* __restrict__ dy, bf16_raw* __restrict__ dx,
+                                         int B, int H, int W, int C, int Ho, int Wo) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c8 = C >> 3;
+    if (i >= (long long)B * Ho * Wo * c8) return;
+    const int c = (int)(i % c8);
+    long long r = i / c8;
+    const int ox = (int)(r % Wo); r /= Wo;
+    const int oy = (int)(r % Ho);
+    const int b = (int)(r / Ho);
+    const uint4 gv = *reinterpret_cast<const uint4*>(dy + ((((long long)b * Ho + oy) * Wo + ox) * C + c * 8));
+    const unsigned g[4] = {gv.x, gv.y, gv.z, gv.w};
+    const unsigned cw = code[i];
+    uint4 old[4];
+    bool in[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int iy = 2 * oy + (p >> 1), ix = 2 * ox + (p & 1);
+        in[p] = iy < H && ix < W;
+        old[p] = make_uint4(0u, 0u, 0u, 0u);
+        if (in[p]) old[p] = *reinterpret_cast<const uint4*>(dx + ((((long long)b * H + iy) * W + ix) * C + c * 8));
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        if (!in[p]) continue;
+        const int iy = 2 * oy + (p >> 1), ix = 2 * ox + (p & 1);
+        const unsigned d[4] = {old[p].x, old[p].y, old[p].z, old[p].w};
+        unsigned o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned s = pack_bf16x2(__uint_as_float(d[k] << 16) + __uint_as_float(g[k] << 16),
+                                           __uint_as_float(d[k] & 0xffff0000u) + __uint_as_float(g[k] & 0xffff0000u));
+            const unsigned lo = ((cw >> (8 * k)) & 15u) == (unsigned)p ? 0x0000ffffu : 0u;
+            const unsigned hi = ((cw >> (8 * k + 4)) & 15u) == (unsigned)p ? 0xffff0000u : 0u;
+            o[k] = (s & (lo | hi)) | (d[k] & ~(lo | hi));
+        }
+        *reinterpret_cast<uint4*>(dx + ((((long long)b * H + iy) * W + ix) * C + c * 8)) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+
 // dloc [B][A][4], dconf [B][A][classes] (bf16) -> one level's padded NHWC gradient [B][H*W][npad].  A pixel's row is the
 // concatenation of its per_cell*4 loc values, its per_cell*classes conf values (both contiguous in the sources) and
 // zero padding.  One thread per 16-byte chunk of the output (8 channels): the sources are only 2-byte aligned
@@ -326,6 +372,16 @@ int ssd_maxpool2x2_bwd_argmax(const void* code, const void* dy, void* dx, int B,
     }
     const long long total = (long long)B * Ho * Wo * (C / 8);
     hipLaunchKernelGGL(k_maxpool_bwd_argmax, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const unsigned*>(code), static_cast<const bf16_raw*>(dy), static_cast<bf16_raw*>(dx), B, H, W, C,
+                       Ho, Wo);
+    return ssd_launch_status();
+}
+
+int ssd_maxpool2x2_bwd_argmax_accumulate(const void* code, const void* dy, void* dx, int B, int H, int W, int C, int Ho, int Wo,
+                                         void* stream) {
+    if (!code || !dy || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Ho <= 0 || Wo <= 0) return SSD_ERR_VALUE;
+    const long long total = (long long)B * Ho * Wo * (C / 8);
+    hipLaunchKernelGGL(k_maxpool_bwd_argmax_acc, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const unsigned*>(code), static_cast<const bf16_raw*>(dy), static_cast<bf16_raw*>(dx), B, H, W, C,
                        Ho, Wo);
     return ssd_launch_status();

@@ -6,6 +6,7 @@ Network = SSDObjectDetectionModel._build of the reference (models/ssd_model.py:7
 block3_conv3, a SAME max-pool, three 38x38 convolutions, five extra stages, and per-level 3x3 loc/conf heads.
 Activations are NHWC bf16, weights [Cout][k][k][Cin] bf16 (fp32 masters), accumulation fp32 on MFMA.
 The 3-channel image is carried in 8 zero-padded channels (first-layer weights of channels 3..7 are and stay 0).
+The same engine runs the SSD paper's VGG-16 SSD300 (VGG16_SSD300_TRUNK below: no reference counterpart).
 """
 import math
 import os
@@ -62,6 +63,25 @@ SSD512_TRUNK = SSD300_TRUNK[:13] + [
     ("conv", 128, 256, 3, 2, "same", True),      # feature map 6 (1x1x256)
 ]
 SSD512_NUM_PRIORS = (4, 6, 6, 6, 6, 4, 4)
+
+# The SSD paper's own 300 x 300 network (Liu et al. 2016, section 3.1 / Caffe SSD's VGG_VOC0712_SSD_300): VGG-16 through
+# conv5_3, pool5 as 3x3 / stride 1, fc6 as a 3x3 convolution with dilation 6, fc7 as a 1x1, then the extras above.  Feature
+# maps conv4_3 (38x38x512, the one the paper L2-normalises), fc7 (19x19x1024), conv8_2 .. conv11_2: grids 38, 19, 10, 5, 3, 1
+# and 4, 6, 6, 6, 4, 4 default boxes per cell = 8732 anchors.  Keras padding throughout (pool3 here is the SAME one of
+# SSD300_TRUNK, 75 -> 38, where Caffe rounds up).  An eighth element is the dilation; "pool3s1" is the 3x3 / stride-1 SAME pooling.
+VGG16_SSD300_TRUNK = SSD300_TRUNK[:10] + [
+    ("conv", 256, 512, 3, 1, "same", False),     # conv4_1
+    ("conv", 512, 512, 3, 1, "same", False),     # conv4_2
+    ("conv", 512, 512, 3, 1, "same", True),      # conv4_3  -> feature map 0 (38x38x512); also pooled
+    ("pool", 512, 512, 2, 2, "valid", False),    # pool4 38 -> 19
+    ("conv", 512, 512, 3, 1, "same", False),     # conv5_1
+    ("conv", 512, 512, 3, 1, "same", False),     # conv5_2
+    ("conv", 512, 512, 3, 1, "same", False),     # conv5_3
+    ("pool3s1", 512, 512, 3, 1, "same", False),  # pool5 19 -> 19
+    ("conv", 512, 1024, 3, 1, "same", False, 6), # fc6, dilation 6
+    ("conv", 1024, 1024, 1, 1, "same", True),    # fc7      -> feature map 1 (19x19x1024)
+] + SSD300_TRUNK[15:]                            # conv8_1 .. conv11_2 -> feature maps 2 .. 5
+VGG16_SSD300_NUM_PRIORS = (4, 6, 6, 6, 4, 4)
 
 
 def _mx_conv(nd):
@@ -368,9 +388,21 @@ class _BackwardPass:
         main stream, then the optimizer bucket that waited for that data gradient."""
         e, nd, written = self.eng, self.eng.nodes[i], self.written
         assert written[i + 1]
+        if nd["kind"] == "pool3s1":
+            assert not written[i], "the 3x3 / stride-1 un-pooling overwrites: its input cannot also feed a head"
+            ops.maxpool3x3s1_bwd(self.c["pool_code"][i], self.gacts[i + 1], self.acts[i].shape, out=self.gacts[i])
+            written[i] = True
+            return
         if nd["kind"] == "pool":
-            assert not written[i], "a pooled activation cannot also feed a head (the pool gradient overwrites)"
-            if i not in self.unpooled:                     # (else the convolution behind the pooling already wrote gacts[i])
+            if written[i]:
+                # the pooled activation feeds a head as well (conv4_3 of the VGG-16 SSD300): the head's gradient is in
+                # gacts[i], possibly written on another stream; the un-pooling adds to it (dgrad() declined to un-pool
+                # in the convolution's store stage, which overwrites)
+                assert i not in self.unpooled
+                self.wait_for_head(i)
+                ops.maxpool2x2_bwd_argmax(self.c["pool_code"][i], self.gacts[i + 1], self.acts[i].shape, out=self.gacts[i],
+                                          accumulate=True)
+            elif i not in self.unpooled:                   # (else the convolution behind the pooling already wrote gacts[i])
                 ops.maxpool2x2_bwd_argmax(self.c["pool_code"][i], self.gacts[i + 1], self.acts[i].shape, out=self.gacts[i])
             written[i] = True
             return
@@ -492,8 +524,12 @@ class _BackwardPass:
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        ops.conv2d_bwd_weight(self.acts[i], self.gacts[i + 1], nd["cout"], nd["k"], nd["stride"], nd["pt"], nd["pl"],
-                              dw=e.view(wt, e.grad), dbias=e.view(bt, e.grad), ws=ws)
+        if nd["dilation"] != 1:                            # (a workspace of its own size, from the same stream's buffer)
+            ops.conv2d_atrous_bwd_weight(self.acts[i], self.gacts[i + 1], nd["cout"], nd["dilation"], dw=e.view(wt, e.grad),
+                                         dbias=e.view(bt, e.grad), ws=ws)
+        else:
+            ops.conv2d_bwd_weight(self.acts[i], self.gacts[i + 1], nd["cout"], nd["k"], nd["stride"], nd["pt"], nd["pl"],
+                                  dw=e.view(wt, e.grad), dbias=e.view(bt, e.grad), ws=ws)
         if timed:
             e1.record()
             probe["events"].append((i, e0, e1))
@@ -521,7 +557,12 @@ class _BackwardPass:
                                                  tuple(self.gacts[i - 1].shape), out=self.gacts[i - 1], ws=e._ws)
             if fused:
                 self.unpooled.add(i - 1)
-        if not fused and e.nodes[i - 1]["kind"] == "conv": # (its ReLU masks the gradient)
+        if nd["dilation"] != 1:
+            # fc6 behind pool5: the pooling's codes carry the ReLU of the layer in front of it, nothing to mask here
+            assert e.nodes[i - 1]["kind"] != "conv", "a dilated convolution behind a convolution: no masked launch planned"
+            ops.conv2d_atrous_bwd_data(g_out, e.w_t[i], None, self.acts[i].shape, nd["dilation"], accumulate=written[i],
+                                       out=self.gacts[i])
+        elif not fused and e.nodes[i - 1]["kind"] == "conv": # (its ReLU masks the gradient)
             self.masked_dgrad("conv%d" % i, g_out, e.w_t[i], i, nd["stride"], nd["pt"], nd["pl"], written[i], e._ws)
         elif not fused:
             ops.conv2d_bwd_data(g_out, e.w_t[i], None, self.acts[i].shape, nd["stride"], nd["pt"], nd["pl"],
@@ -599,17 +640,33 @@ class SSDEngine:
         self._vgg_fp8_fwd = False
 
     # ---------------------------------------------------------------- static planning
+    @classmethod
+    def planned(cls, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, l2norm=None):
+        """The static plan alone (nodes, fm, grids, A, tensors, chain_start): no device is touched, nothing can be launched."""
+        e = cls.__new__(cls)
+        e.L = _lib.lib()
+        e.l2norm = ops.L2NormSpec.of(l2norm)
+        e.classes, e.in_size, e.device = classes, in_size, torch.device("cpu")
+        e.trunk, e.num_priors, e.sparse_heads = list(trunk), tuple(num_priors), True
+        e.block = e.L.ssd_opt_block_elems()
+        e._plan_shapes()
+        e._plan_params()
+        return e
+
     def _plan_shapes(self):
         s = self.in_size
         self.nodes = []                       # dicts: kind, cin, cout, k, stride, pt, pl, hin, hout, feature
         self.fm = []                          # (node index, h, c)
-        for kind, cin, cout, k, stride, mode, feat in self.trunk:
+        for kind, cin, cout, k, stride, mode, feat, *more in self.trunk:
+            dilation = more[0] if more else 1                # (an optional eighth element: only the VGG-16 trunk's fc6 has one)
+            if kind not in ("conv", "pool", "pool3s1") or (dilation != 1 and (kind, k, stride, mode) != ("conv", 3, 1, "same")):
+                raise ValueError("trunk node %d: no launch for %r" % (len(self.nodes), (kind, cin, cout, k, stride, mode, feat) + tuple(more)))
             if mode == "same":
-                ho, pt = ops.same_pad(s, k, stride)
+                ho, pt = ops.same_pad(s, dilation * (k - 1) + 1, stride)
             else:
                 ho, pt = ops.valid_out(s, k, stride), 0
             self.nodes.append(dict(kind=kind, cin=cin, cout=cout, k=k, stride=stride, pt=pt, pl=pt, hin=s, hout=ho,
-                                   feature=feat, same=(mode == "same")))
+                                   feature=feat, same=(mode == "same"), dilation=dilation))
             s = ho
             if feat:
                 self.fm.append((len(self.nodes) - 1, ho, cout))
@@ -619,7 +676,8 @@ class SSDEngine:
         j = len(self.nodes)
         while (j > 1 and len(self.nodes) - j < _lib.SSD_CHAIN_MAX_LAYERS and self.nodes[j - 1]["kind"] == "conv"
                and self.nodes[j - 2]["kind"] == "conv" and self.nodes[j - 1]["hin"] ** 2 <= 112 and self.nodes[j - 1]["hout"] ** 2 <= 112
-               and self.nodes[j - 1]["cin"] % 128 == 0 and self.nodes[j - 1]["cout"] % 128 == 0):
+               and self.nodes[j - 1]["cin"] % 128 == 0 and self.nodes[j - 1]["cout"] % 128 == 0
+               and self.nodes[j - 1]["dilation"] == 1):
             j -= 1
         self.chain_start = j if len(self.nodes) - j >= 2 else None
         if any(c % 128 for _, _, c in self.fm) or len(self.fm) > _lib.SSD_MAX_LEVELS:
@@ -633,6 +691,8 @@ class SSDEngine:
         pair = [(nd["kind"], nd["cin"], nd["cout"], nd["k"], nd["stride"]) for nd in self.nodes[:2]]
         self.first_pair = (pair == [("conv", 8, 64, 3, 1), ("conv", 64, 64, 3, 1)]
                            and self.nodes[1]["pt"] == self.nodes[1]["pl"] == 1)
+        # node kinds the block-scaled fp8 forward has no plan for (the VGG-16 SSD300's pool5 and fc6)
+        self.bf16_only = any(nd["kind"] == "pool3s1" or nd["dilation"] != 1 for nd in self.nodes)
 
     def _plan_params(self):
         self.tensors = []
@@ -805,7 +865,7 @@ class SSDEngine:
             packed = [torch.empty((B, h * h, npad), dtype=torch.bfloat16, device=dev)
                       for (_, h, _), npad in zip(self.fm, self.head_npad)]
             pool_code = {i: torch.empty((B, nd["hout"], nd["hout"], nd["cout"] // 8), dtype=torch.int32, device=dev)
-                         for i, nd in enumerate(self.nodes) if nd["kind"] == "pool"}
+                         for i, nd in enumerate(self.nodes) if nd["kind"] in ("pool", "pool3s1")}
             # ReLU sign bits of every convolution output (one byte per pixel and 8 channels): what the data gradients read
             # instead of the bf16 activation
             rbits = {i + 1: torch.empty((B, nd["hout"], nd["hout"], nd["cout"] // 8), dtype=torch.uint8, device=dev)
@@ -843,6 +903,9 @@ class SSDEngine:
         precision="mxfp8": inference only -- the trunk layers of mxfp8_vgg_plan on block-scaled fp8 operands, the rest, the
         chain and the heads in bf16, on the same streams as the bf16 forward; backward() then raises until a bf16 forward."""
         if precision == "mxfp8":
+            if self.bf16_only:
+                raise NotImplementedError("forward(x, 'mxfp8'): the VGG-16 SSD300 trunk (3x3 / stride-1 pooling, dilated fc6) has no "
+                                          "block-scaled fp8 plan; it runs in bf16")
             return self._forward_vgg_mxfp8(x)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
@@ -940,16 +1003,19 @@ class SSDEngine:
             args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"],
                     nd["hout"], nd["hout"])
             nxt = self.nodes[i + 1] if i + 1 < len(self.nodes) else None
-            if nxt is not None and nxt["kind"] == "pool":      # conv + the pooling behind it in one call
+            if nd["dilation"] != 1:                            # fc6: no sign bytes, its consumer's data gradient reads the map
+                ops.conv2d_atrous_fwd(args[0], args[1], args[2], nd["dilation"], True, out=acts[i + 1])
+            elif nxt is not None and nxt["kind"] == "pool":    # conv + the pooling behind it in one call
                 # nothing but the pooling reads this conv's full-resolution output (the backward pass works from the
-                # pooled map and the winner codes): ask for the pooled map only, where a fused kernel serves the layer
-                pool_only = self.pool_only.get(i, self.skip_fullres)
+                # pooled map and the winner codes): ask for the pooled map only, where a fused kernel serves the layer.
+                # A feature map is read by its head as well: its full-resolution map is always stored
+                pool_only = False if nd["feature"] else self.pool_only.get(i, self.skip_fullres)
                 args += (True, self._pool_same(nxt))
                 kw = dict(out=acts[i + 1], pool_out=acts[i + 2], code=c["pool_code"][i + 1], ws=self._ws)
                 if pool_only:                     # (refused with SSD_ERR_VALUE: no pooling kernel for this shape)
                     pool_only = _launched(ops.conv2d_fwd_pool, *args, pool_only=True, refused=ValueError, **kw)
                 self.pool_only[i] = pool_only
-                if not pool_only:
+                if not pool_only:                 # (with the map stored the library pools in a second launch where no kernel fuses it)
                     ops.conv2d_fwd_pool(*args, **kw)
             else:
                 done = False
@@ -960,6 +1026,8 @@ class SSDEngine:
                         self.bits_valid.add(i + 1)
                 if not done:
                     ops.conv2d_fwd(*args, True, out=acts[i + 1], ws=self._ws)
+        elif nd["kind"] == "pool3s1":
+            ops.maxpool3x3s1_fwd(acts[i], out=acts[i + 1], code=c["pool_code"][i])
         elif i == 0 or self.nodes[i - 1]["kind"] != "conv":
             ops.maxpool2x2_fwd_argmax(acts[i], out=acts[i + 1], code=c["pool_code"][i],
                                       same=self._pool_same(nd))

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..engine import SSDEngine
+from ..engine import SSDEngine, VGG16_SSD300_NUM_PRIORS, VGG16_SSD300_TRUNK
 from ..parallel import GradReducer, shard_range
 from .. import optimizers as _opt
 from ..utils.scalar_log import ScalarLog
@@ -85,7 +85,9 @@ class SSDObjectDetectionModel:
         scale (ops.L2NormSpec.of: None / False = off as in the reference, True = the paper's initial scale 20, a number, a dict
         or a spec).  The scale is one more variable of the engine: trained, clipped, saved and loaded like the others.
 
-        network (ops.NetworkSpec.of: None / "ssd300" = the reference's network, as without the argument; "resnet50_ssd512", a
+        network (ops.NetworkSpec.of: None / "ssd300" = the reference's network, as without the argument; "vgg16_ssd300" = the
+        SSD paper's VGG-16 SSD300 (engine.VGG16_SSD300_TRUNK: conv4_3 / fc7 feature maps, pool5 3x3 / 1, dilated fc6) on the
+        same engine class and the same step, l2norm as for ssd300 (the paper trains it with l2norm=True); "resnet50_ssd512", a
         dict or a spec): the ResNet-50 SSD512 network (resnet_engine.ResNet50SSDEngine) at a 512 or 256 input, optionally with
         live batch normalisation or an MX-fp8 training forward.  Its step is backward -> clip -> one optimizer launch over the
         flat buffer (the engine has no per-bucket schedule); everything else -- targets, both losses, the three optimizers,
@@ -103,9 +105,14 @@ class SSDObjectDetectionModel:
         self.cfg = SSDObjectDetectionModel.Config(classes, log_dir)
         self.device = torch.device(device)
         net = self.network
-        if net.kind == "ssd300":
+        if net.kind in ("ssd300", "vgg16_ssd300"):
+            # one engine class, two trunks: the same step (fused per-bucket optimizer, high-priority main stream), the same
+            # default boxes (grids 38, 19, 10, 5, 3, 1)
+            graph = {}
+            if net.kind == "vgg16_ssd300":
+                graph = dict(trunk=VGG16_SSD300_TRUNK, num_priors=VGG16_SSD300_NUM_PRIORS)
             self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed,
-                                     l2norm=l2norm)
+                                     l2norm=l2norm, **graph)
             self._pset = ops.build_priors(grids=self._engine.grids, device=device)
             self._forward_train = self._engine.forward
             self._backward_args = {}

@@ -435,17 +435,19 @@ class BatchNormSpec:
 
 class NetworkSpec:
     """Which network SSDObjectDetectionModel builds and how it trains it.
-      kind             "ssd300": the reference's 300 x 300 network (SSDEngine), the default; "resnet50_ssd512": the ResNet-50
-                       SSD512 network (ResNet50SSDEngine)
-      in_size          300 for ssd300; 512 (default) or 256 for the ResNet
+      kind             "ssd300": the reference's 300 x 300 network (SSDEngine), the default; "vgg16_ssd300": the SSD paper's
+                       VGG-16 SSD300 (SSDEngine on engine.VGG16_SSD300_TRUNK; bf16, no batchnorm); "resnet50_ssd512": the
+                       ResNet-50 SSD512 network (ResNet50SSDEngine)
+      in_size          300 for ssd300 and vgg16_ssd300; 512 (default) or 256 for the ResNet
       batchnorm        ResNet only: anything BatchNormSpec.of takes (None / False: the folded network)
       precision        of the TRAINING forward: "bf16" or "mxfp8" (ResNet only; not together with batchnorm, whose engine has no
                        fp8 plan)
       dgrad_precision  of the data gradients behind an mxfp8 training forward: None (fp8 where planned), "bf16" or "mxfp8"
     """
-    KINDS = ("ssd300", "resnet50_ssd512")
+    KINDS = ("ssd300", "resnet50_ssd512", "vgg16_ssd300")
     FIELDS = ("kind", "in_size", "batchnorm", "precision", "dgrad_precision")
-    IN_SIZES = {"ssd300": (300,), "resnet50_ssd512": (512, 256)}           # the first one is the default
+    IN_SIZES = {"ssd300": (300,), "resnet50_ssd512": (512, 256), "vgg16_ssd300": (300,)}     # the first one is the default
+    L2NORM_KINDS = ("ssd300", "vgg16_ssd300")                              # the networks SSDEngine runs: l2norm is its option
 
     def __init__(self, kind="ssd300", in_size=None, batchnorm=None, precision="bf16", dgrad_precision=None):
         if not isinstance(kind, str) or kind not in self.KINDS:
@@ -460,12 +462,12 @@ class NetworkSpec:
             raise ValueError("network precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         if dgrad_precision is not None and (not isinstance(dgrad_precision, str) or dgrad_precision not in ("bf16", "mxfp8")):
             raise ValueError("network dgrad_precision must be None, 'bf16' or 'mxfp8', not %r" % (dgrad_precision,))
-        if kind == "ssd300":
+        if kind in ("ssd300", "vgg16_ssd300"):
             if batchnorm is not None:
-                raise ValueError("network batchnorm: the ssd300 network has no batch normalisation")
+                raise ValueError("network batchnorm: the %s network has no batch normalisation" % kind)
             if precision != "bf16" or dgrad_precision is not None:
-                raise ValueError("network precision / dgrad_precision: the ssd300 network trains in bf16 (precision=%r, "
-                                 "dgrad_precision=%r)" % (precision, dgrad_precision))
+                raise ValueError("network precision / dgrad_precision: the %s network trains in bf16 (precision=%r, "
+                                 "dgrad_precision=%r)" % (kind, precision, dgrad_precision))
         if batchnorm is not None and precision == "mxfp8":
             raise ValueError("network batchnorm together with precision='mxfp8': a batchnorm engine has no fp8 training "
                              "forward (its fp8 inference runs on the folded network)")
@@ -478,7 +480,8 @@ class NetworkSpec:
     @classmethod
     def of(cls, v, l2norm=None):
         """None -> the ssd300 default; a kind name; a dict with keys of FIELDS; a NetworkSpec -> itself.  l2norm: the model's
-        l2norm argument, which only the ssd300 network serves.  ValueError (naming the key or value) for anything else."""
+        l2norm argument, which the ssd300 and vgg16_ssd300 networks serve (off unless asked for).  ValueError (naming the key
+        or value) for anything else."""
         if v is None:
             spec = cls()
         elif isinstance(v, cls):
@@ -493,8 +496,9 @@ class NetworkSpec:
             spec = cls(**v)
         else:
             raise ValueError("network must be None, a kind name, a dict or an ops.NetworkSpec, not %r" % (v,))
-        if spec.kind != "ssd300" and L2NormSpec.of(l2norm) is not None:
-            raise ValueError("l2norm together with network kind %r: L2Norm is wired for the ssd300 network only" % spec.kind)
+        if spec.kind not in cls.L2NORM_KINDS and L2NormSpec.of(l2norm) is not None:
+            raise ValueError("l2norm together with network kind %r: L2Norm is wired for the networks %s only"
+                             % (spec.kind, ", ".join(cls.L2NORM_KINDS)))
         return spec
 
     def as_dict(self):
@@ -1371,11 +1375,20 @@ def maxpool2x2_fwd_argmax(x, same=False, out=None, code=None):
     return out, code
 
 
-def maxpool2x2_bwd_argmax(code, dy, x_shape, out=None):
+def maxpool2x2_bwd_argmax(code, dy, x_shape, out=None, accumulate=False):
+    """Un-pooling from the recorded winners.  accumulate=True adds onto `out` (required: it holds the gradient that reached the
+    same activation on another path) with one fp32 addition and one rounding; elements that no window routes to keep their bits."""
     L = _lib.lib()
     _bf(dy)
     B, H, W, C = x_shape
     _, Ho, Wo, _ = dy.shape
+    if accumulate:
+        if out is None:
+            raise ValueError("maxpool2x2_bwd_argmax: accumulate=True adds onto `out`, which must be given")
+        _bf(out)
+        assert tuple(out.shape) == tuple(x_shape) and out.is_contiguous()
+        _lib.check(L.ssd_maxpool2x2_bwd_argmax_accumulate(_ptr(code), _ptr(dy), _ptr(out), B, H, W, C, Ho, Wo, _stream()))
+        return out
     if out is None:
         out = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dy.device)
     _lib.check(L.ssd_maxpool2x2_bwd_argmax(_ptr(code), _ptr(dy), _ptr(out), B, H, W, C, Ho, Wo, _stream()))
@@ -1593,7 +1606,7 @@ def maxpool3x3s2_bwd(code, dy, x_shape, out=None):
     return out
 
 
-# ---- the SSD paper's VGG-16 pieces: dilated fc6 and the 3x3 / stride-1 pool5 (no network uses them yet) ---------------------
+# ---- the SSD paper's VGG-16 pieces: dilated fc6 and the 3x3 / stride-1 pool5 (engine.VGG16_SSD300_TRUNK) --------------------
 _ATROUS_RANGE = ("atrous 3x3 convolution: Cin must be a multiple of 64, Cout / Cout_pad / ldy multiples of 8, ldy >= Cout, "
                  "every tensor below 2^31 bytes; got %s")
 _POOL3S1_RANGE = "3x3 / stride-1 max pooling: C must be a multiple of 8 and the map below 2^31 elements; got %s"

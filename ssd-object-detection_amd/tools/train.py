@@ -123,6 +123,7 @@ def l2norm_from_config(config):
 def network_from_config(config):
     """`model: network: {kind, in_size, batchnorm: {enable, momentum, eps}, precision, dgrad_precision}` (no reference
     counterpart) -> ops.NetworkSpec, or None when the key is absent: the default run builds the reference's 300 x 300 network.
+    kind "vgg16_ssd300" (the SSD paper's network) goes together with `model: l2norm:`, as "ssd300" does; the ResNet refuses it.
     `batchnorm` absent, null or with enable false: no batch normalisation.  ValueError for an unknown key, a section that is
     no mapping or bad values."""
     section = (config.get("model") or {}).get("network")

@@ -1,0 +1,222 @@
+"""GPU: SSDEngine on the VGG-16 SSD300 graph (engine.VGG16_SSD300_TRUNK), forward and backward, against tests/vgg16_oracle.py.
+
+Forward: the rule tests/test_engine_gpu.py applies to SSD300 -- rel_l2 < 1e-2 of loc and conf against the bf16-emulating CPU
+forward run on the engine's own bf16 filters -- at the full geometry (batch 1) and at two five-level geometries (batch 2):
+174 (maps 22, 11, 6, 3, 1; pool4 22 -> 11 even) and 164 (maps 21, 10, 5, 3, 1; pool4 is a VALID pooling of an ODD map, 21 ->
+10, so row and column 20 of conv4_3's gradient come from the head alone and the accumulating un-pooling must leave them).
+
+Backward: teacher-forced, as tests/test_engine_forced_gpu.py does it.  Every data-dependent decision is taken from the
+engine's own forward (masks, winner codes of pool1 .. pool4 and pool5, stored maps, the stored normalised map), gradient maps
+and tensors are NaN and the padding between tensors a fixed pattern before backward(); each parameter gradient and each
+gradient map must lie within 3 * rel_l2(R, T) + 1e-3 (forced_oracle.bounds).  conv4_3 is the first activation that feeds a
+head (through L2Norm where on) AND a pooling: its gradient is head first, un-pooled pool4 gradient added
+(ops.maxpool2x2_bwd_argmax(accumulate=True)).  The three wiring errors this graph invites -- the un-pooling overwrites the
+head's part, the head's part is missing, fc7's data gradient is not masked by fc6's map -- are shown to move a named tensor
+beyond twice its bound."""
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from tests import strict as S                                        # noqa: E402
+from tests import forced_oracle as FO                                # noqa: E402
+from tests import vgg16_oracle as VO                                 # noqa: E402
+
+CLASSES = 81
+RESULTS = {}
+GRIDS = {300: (38, 19, 10, 5, 3, 1), 174: (22, 11, 6, 3, 1), 164: (21, 10, 5, 3, 1)}
+OFF = ("overlap_heads", "chain", "relu_bits", "fuse_unpool", "fuse_first", "skip_fullres")
+
+
+def build(size, l2norm=None, sparse_heads=None, seed=7):
+    from ssd_object_detection_amd.engine import SSDEngine, VGG16_SSD300_TRUNK, VGG16_SSD300_NUM_PRIORS
+    trunk, pri = (VGG16_SSD300_TRUNK, VGG16_SSD300_NUM_PRIORS) if size == 300 else (VGG16_SSD300_TRUNK[:-2], VGG16_SSD300_NUM_PRIORS[:5])
+    e = SSDEngine(classes=CLASSES, seed=seed, in_size=size, trunk=trunk, num_priors=pri, l2norm=l2norm or None, sparse_heads=sparse_heads)
+    assert e.grids == tuple((h, h) for h in GRIDS[size])
+    if l2norm:                                                          # another scale per channel, one of them negative
+        v = 20.0 + 5.0 * torch.randn(e.l2norm_scale.numel, generator=torch.Generator().manual_seed(5))
+        v[7] = -v[7].abs()
+        e.view(e.l2norm_scale, e.param).copy_(v.cuda())
+    return e
+
+
+def plain(e):
+    e.overlap_heads, e.chain, e.relu_bits, e.fuse_unpool, e.fuse_first, e.skip_fullres = False, set(), None, None, False, False
+    return e
+
+
+class Forced(FO.Forced):
+    def written_maps(self):
+        e = self.engine
+        self.first_fused = e.first_fused
+        unwritten = {i for i, v in (e.fuse_unpool or {}).items() if v} | ({1} if self.first_fused else set())
+        return [a for a in range(1, len(e.nodes) + 1) if a not in unwritten]
+
+    def stored_forward(self):
+        e, c = self.engine, self.c
+        stored = [c["acts"][0].cpu()] + [None if e.pool_only.get(a - 1, False) else c["acts"][a].cpu() for a in range(1, len(e.nodes) + 1)]
+        codes = {i: FO.unpack_codes(w.cpu()) for i, w in c["pool_code"].items()}
+        l2norm = None
+        if e.l2norm is not None:
+            l2norm = dict(scale=FO.engine_weights(e)["l2norm0/scale"], y=c["l2n_y"].cpu(), eps=e.l2norm.eps)
+        return stored, codes, l2norm
+
+    def walk(self, *args, **kw):
+        return VO.backward_chain(*args, l2norm=self.l2norm, **kw)
+
+    def check_forward_state(self):
+        """exact preconditions: sign bytes, codes and pooled maps are those of the stored maps; conv4_3's map is stored"""
+        e, c = self.engine, self.c
+        fm0 = e.fm[0][0]
+        assert e.nodes[fm0 + 1]["kind"] == "pool" and e.pool_only[fm0] is False and self.stored[fm0 + 1] is not None
+        fc6 = [i for i, nd in enumerate(e.nodes) if nd["dilation"] != 1]
+        assert len(fc6) == 1 and (fc6[0] + 1) not in e.bits_valid, "fc6 writes no sign bytes: fc7's data gradient reads its map"
+        for a in sorted(e.bits_valid):
+            assert torch.equal(c["rbits"][a].cpu(), S.pack_bits(self.stored[a] > 0)), "sign bytes of activation %d" % a
+        seen = []
+        for p, nd in enumerate(e.nodes):
+            if nd["kind"] not in ("pool", "pool3s1"):
+                continue
+            seen.append(nd["kind"])
+            pooled, code = self.stored[p + 1], self.codes[p]
+            ks, stride, pad, none = (2, 2, 0, 4) if nd["kind"] == "pool" else (3, 1, 1, 15)
+            if self.stored[p] is not None:
+                y, want = S.ref_pool(self.stored[p].float(), ks, stride, pad, pad, nd["hout"], nd["hout"], none)
+                assert torch.equal(pooled.float(), y), "pooled map of node %d" % p
+                assert torch.equal(c["pool_code"][p].cpu(), S.pack_codes(want)), "winner codes of node %d" % p
+            else:
+                assert nd["kind"] == "pool" and p != fm0 + 1
+                assert torch.equal(pooled > 0, code < 4), "node %d: pooled map positive exactly where a winner is named" % p
+                assert int(code.max()) <= 4
+        assert seen == ["pool"] * 4 + ["pool3s1"]
+        assert self.stored[fm0 + 1] is not None and self.stored[fc6[0]] is not None and self.stored[fc6[0] - 1] is not None
+
+
+def result(key):
+    if key not in RESULTS:
+        scale = (1.0, 2.0, 4.0, 8.0, 16.0)        # the deeper levels' few pixels weigh as much as level 0's (see test_engine_forced_gpu.py)
+        if key == "174-l2norm":
+            RESULTS[key] = Forced(build(174, l2norm=True), 2, 13, level_scale=scale)
+        elif key == "164":
+            RESULTS[key] = Forced(build(164), 2, 17, level_scale=scale)
+        elif key == "164-off":
+            RESULTS[key] = Forced(plain(build(164, sparse_heads=False)), 2, 17, level_scale=scale)
+        else:
+            RESULTS[key] = Forced(build(300, seed=3), 1, 11)
+    return RESULTS[key]
+
+
+# ---------------------------------------------------------------- forward
+@pytest.mark.parametrize("size,B,l2norm", [(300, 1, False), (174, 2, True), (164, 2, False)])
+def test_forward_against_the_oracle(size, B, l2norm):
+    import ssd_object_detection_amd.ops as ops
+    e = build(size, l2norm=l2norm, seed=3)
+    x = ops.image_prep(torch.rand((B, size, size, 3), generator=torch.Generator().manual_seed(1)).cuda())
+    loc, conf = e.forward(x)
+    torch.cuda.synchronize()
+    A = sum(h * h * n for h, n in zip(GRIDS[size], e.num_priors))
+    assert loc.shape == (B, A, 4) and conf.shape == (B, A, CLASSES) and (size != 300 or A == 8732)
+    w = {k: v.float() for k, v in FO.engine_weights(e).items()}
+    scale = w.pop("l2norm0/scale", None)
+    loc_r, conf_r = VO.forward(e.trunk, e.num_priors, CLASSES, w, x.float().cpu(), l2norm_scale=scale)
+    el, ec = FO.rel_l2(loc.float().cpu(), loc_r), FO.rel_l2(conf.float().cpu(), conf_r)
+    print("forward %d batch %d: rel_l2 loc %.3e conf %.3e" % (size, B, el, ec))
+    assert el < 1e-2 and ec < 1e-2, (el, ec)
+    with pytest.raises(NotImplementedError, match="VGG-16"):
+        e.forward(x, "mxfp8")
+    assert not e._vgg_fp8_fwd                                             # refused before anything ran: backward() still allowed
+
+
+# ---------------------------------------------------------------- teacher-forced backward
+def test_reduced_174_l2norm_default_switches():
+    r = result("174-l2norm")
+    e = r.engine
+    assert e.chain_start == 22 and e.chain == {"fwd", "bwd"} and e.sparse_heads and e.batch_chain_wgrads and e.overlap_heads
+    assert "l2norm0/scale" in r.got and e.nodes[13]["hin"] == 22
+    assert e.fuse_unpool.get(14) is None, "conv5_1 must not un-pool in its store stage: conv4_3's gradient is already written"
+    r.check("VGG-16 trunk[:-2] at 174, batch 2, l2norm")
+
+
+def test_reduced_164_default_switches():
+    r = result("164")
+    e = r.engine
+    # at this geometry the planner's chain would start at fc7 (10 x 10 x 1024): 200 KB of input map, more than the chain kernel
+    # keeps in LDS, so it refuses at the first forward and the per-layer launches serve (the full geometry and 174 keep the chain)
+    assert e.chain_start == 19 and e.chain == set() and e.sparse_heads
+    assert e.nodes[13]["hin"] == 21 and e.nodes[13]["hout"] == 10 and "l2norm0/scale" not in r.got
+    assert e.relu_bits is not None and e.bits_valid and any(e.pool_only.values())
+    r.check("VGG-16 trunk[:-2] at 164, batch 2")
+    # row and column 20 of conv4_3's gradient: the head's part alone (a VALID pooling of an odd map does not reach them)
+    pooled_part = r.oracle(defect=("no_head", 0), first_node=12)["gact13"]      # what pool4 alone routes into the map
+    assert float(pooled_part[:, 20].abs().max()) == 0.0 and float(pooled_part[:, :, 20].abs().max()) == 0.0
+    assert float(pooled_part.abs().max()) > 0.0
+    edge = torch.zeros(21, 21, dtype=torch.bool)
+    edge[20], edge[:, 20] = True, True
+    assert FO.rel_l2(r.got["gact13"][:, edge], r.T["gact13"][:, edge]) <= r.bound["gact13"]
+
+
+def test_reduced_164_everything_off():
+    r = result("164-off")
+    e = r.engine
+    assert not e.sparse_heads and e.head_grad_buffers(2) is None
+    assert e.overlap_heads is False and not e.chain and e.relu_bits is None and e.fuse_unpool is None
+    assert e.fuse_first is False and not r.first_fused and e.skip_fullres is False
+    assert not e.bits_valid and not any(e.pool_only.values()) and all(s is not None for s in r.stored)
+    assert r.maps == list(range(1, len(e.nodes) + 1))
+    r.check("VGG-16 trunk[:-2] at 164, batch 2, everything off")
+
+
+def test_full_geometry_default_switches():
+    r = result("300")
+    e = r.engine
+    assert e.A == 8732 and e.chain_start == 22 and "bwd" in e.chain and "fwd" in e.chain and e.sparse_heads and e.overlap_heads
+    assert r.first_fused and any(e.pool_only.values()) and e.pool_only[12] is False
+    r.check("VGG-16 SSD300, batch 1")
+
+
+DEFECTS = [(("overwrite", (13, 13)), 10, "gact13"), (("no_head", 0), 10, "gact13"), (("no_mask", 19), 15, "gact19")]
+
+
+@pytest.mark.parametrize("defect,first_node,named", DEFECTS, ids=lambda v: str(v).replace(" ", ""))
+def test_seeded_defect_exceeds_twice_the_bound(defect, first_node, named):
+    r = result("164")
+    D = r.oracle(defect=defect, first_node=first_node)
+    hit = FO.moved(r.T, D, r.bound)
+    print(defect, sorted(hit, key=lambda v: -v[1] / v[2])[:5])
+    assert named in [h[0] for h in hit], (defect, "does not move %s to twice its bound" % named)
+
+
+# ---------------------------------------------------------------- repeatability and schedule
+def _bits_of(e, c, maps):
+    torch.cuda.synchronize()
+    return [e.grad.clone().view(torch.int32)] + [c["gacts"][a].clone().view(torch.int16) for a in maps]
+
+
+def test_two_backward_calls_give_the_same_bits():
+    r = result("174-l2norm")
+    e, c = r.engine, r.c
+    e.forward(r.x)
+    runs = []
+    for _ in range(2):
+        e.backward(r.dloc.cuda(), r.dconf.cuda())
+        runs.append(_bits_of(e, c, r.maps))
+    assert all(torch.equal(a, b) for a, b in zip(*runs))
+    got, _ = FO.engine_grads(e, c, r.maps)
+    assert all(torch.equal(got[k], r.got[k]) for k in got), "differs from the first (poisoned) run"
+
+
+def test_large_level_streams_are_bitwise_neutral():
+    """At a training batch the 38x38 and 19x19 heads' data gradients (and l2norm_bwd) run on a third stream, and pool4's
+    accumulating un-pooling waits for conv4_3's event (wait_for_head).  Forced here at batch 2 by lowering the engine's
+    large-level threshold: every bit must equal the one-stream order's."""
+    r = result("174-l2norm")
+    e, c = r.engine, r.c
+    e.forward(r.x)
+    e.BIG_LEVEL_PIXELS = 200                                             # (instance attribute) 2 * 22 * 22 and 2 * 11 * 11 pixels: large
+    assert [lvl for lvl, (_, h, _) in enumerate(e.fm) if 2 * h * h >= 200] == [0, 1] and e.split_heads_dgrad
+    try:
+        e.backward(r.dloc.cuda(), r.dconf.cuda())
+        got, _ = FO.engine_grads(e, c, r.maps)
+    finally:
+        del e.BIG_LEVEL_PIXELS
+    assert all(torch.equal(got[k], r.got[k]) for k in got), [k for k in got if not torch.equal(got[k], r.got[k])]
