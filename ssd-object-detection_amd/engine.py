@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, mx, ops
 
 # (kind, cin, cout, k, stride, mode, feature_map)   -- mode: TF padding; every conv has ReLU
 SSD300_TRUNK = [
@@ -84,9 +84,11 @@ VGG16_SSD300_TRUNK = SSD300_TRUNK[:10] + [
 VGG16_SSD300_NUM_PRIORS = (4, 6, 6, 6, 4, 4)
 
 
-def _mx_conv(nd):
-    """A convolution the block-scaled fp8 kernels serve (ops.conv2d_fwd_mxfp8): Cin whole MX k-steps, Cout whole MX blocks."""
-    return (nd["kind"] == "conv" and nd["cin"] % 128 == 0 and nd["cout"] % 32 == 0 and nd["k"] in (1, 3)
+def mxfp8_eligible(nd):
+    """Whether the block-scaled fp8 kernels serve node `nd` (ops.conv2d_fwd_mxfp8; a planned node or a graph node of
+    resnet_engine): a convolution whose input channels are whole MX k-steps (Cin % 128 == 0) and whose output channels are
+    whole MX blocks (Cout % 32 == 0)."""
+    return (nd.get("kind", nd.get("op")) == "conv" and nd["cin"] % 128 == 0 and nd["cout"] % 32 == 0 and nd["k"] in (1, 3)
             and nd["stride"] in (1, 2))
 
 
@@ -107,11 +109,11 @@ def mxfp8_vgg_plan(nodes, chain_start):
     end = n if chain_start is None else chain_start
 
     def pools_itself(i):                 # a 3x3 / stride-1 fp8 convolution with a pool behind it inside the run
-        return (_mx_conv(nodes[i]) and nodes[i]["k"] == 3 and nodes[i]["stride"] == 1 and i + 1 < end
+        return (mxfp8_eligible(nodes[i]) and nodes[i]["k"] == 3 and nodes[i]["stride"] == 1 and i + 1 < end
                 and nodes[i + 1]["kind"] == "pool")
 
     s = end
-    while s > 1 and (_mx_conv(nodes[s - 1]) or (nodes[s - 1]["kind"] == "pool" and pools_itself(s - 2))):
+    while s > 1 and (mxfp8_eligible(nodes[s - 1]) or (nodes[s - 1]["kind"] == "pool" and pools_itself(s - 2))):
         s -= 1
     size = [nd["hout"] ** 2 * nd["cout"] for nd in nodes]
     start = None
@@ -583,19 +585,13 @@ class SSDEngine:
         """l2norm: the SSD paper's L2 normalisation of feature map 0 in front of its head (ops.L2NormSpec.of: None / False = off,
         True, an initial scale, a dict or a spec).  Off, the engine plans the same tensors and launches what it did without
         the option; on, one more variable "l2norm0/scale" follows every other one."""
-        self.L = _lib.lib()
-        self.l2norm = ops.L2NormSpec.of(l2norm)
-        self.classes, self.in_size, self.device = classes, in_size, torch.device(device)
-        self.trunk, self.num_priors = list(trunk), tuple(num_priors)
-        self.block = self.L.ssd_opt_block_elems()
         # the heads' backward pass from the loss's compact gradient rows (csrc/sparse.hip); SSD_SPARSE_HEADS=0: the dense
         # kernels on the scattered gradient (tests compare the two)
-        self.sparse_heads = (os.environ.get("SSD_SPARSE_HEADS", "1") == "1") if sparse_heads is None else bool(sparse_heads)
+        self._plan(classes, in_size, trunk, num_priors, device, l2norm,
+                   (os.environ.get("SSD_SPARSE_HEADS", "1") == "1") if sparse_heads is None else bool(sparse_heads))
         # the trailing convolutions on LDS-sized maps (the extras behind the 19x19 map) as ONE launch, forward and data gradient
         # (ops.conv_chain); a set: {"fwd", "bwd"}, emptied by a refusal of the kernel
         self.chain = {"1": {"fwd", "bwd"}, "fwd": {"fwd"}, "bwd": {"bwd"}}.get(os.environ.get("SSD_CHAIN", "1"), set())
-        self._plan_shapes()
-        self._plan_params()
         self._alloc_params()
         self.init_params(seed)
         self._act_cache = {}
@@ -634,24 +630,31 @@ class SSDEngine:
         self.fuse_first = os.environ.get("SSD_FUSE_FIRST", "1") == "1"
         self.first_fused = False               # the last backward() ran that kernel: gacts[1] was consumed on chip, not written
         self.wgrad_probe = None                # dict(nodes={...}, events=[]): time those layers' weight-gradient launches in the step
-        # inference in block-scaled fp8 (forward(x, "mxfp8")): the plan (mxfp8_vgg_plan, at the first fp8 forward), the fp8 layers'
-        # quantised filters and whether the last forward ran in fp8 (backward() then refuses)
-        self._vgg_mx, self._vgg_mx_range, self._vgg_mx_w = None, None, None
-        self._vgg_fp8_fwd = False
+        # what the last forward left behind: "bf16" (everything backward() reads), "mxfp8" (an inference fp8 forward: backward()
+        # refuses) or, on an engine that trains in fp8, "mxfp8_train"
+        self.last_forward = "bf16"
 
     # ---------------------------------------------------------------- static planning
     @classmethod
     def planned(cls, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, l2norm=None):
         """The static plan alone (nodes, fm, grids, A, tensors, chain_start): no device is touched, nothing can be launched."""
         e = cls.__new__(cls)
-        e.L = _lib.lib()
-        e.l2norm = ops.L2NormSpec.of(l2norm)
-        e.classes, e.in_size, e.device = classes, in_size, torch.device("cpu")
-        e.trunk, e.num_priors, e.sparse_heads = list(trunk), tuple(num_priors), True
-        e.block = e.L.ssd_opt_block_elems()
-        e._plan_shapes()
-        e._plan_params()
+        e._plan(classes, in_size, trunk, num_priors, "cpu", l2norm, True)
         return e
+
+    def _plan(self, classes, in_size, trunk, num_priors, device, l2norm, sparse_heads):
+        """The static part of an engine, shared by __init__ and planned()."""
+        self.L = _lib.lib()
+        self.l2norm = ops.L2NormSpec.of(l2norm)
+        self.classes, self.in_size, self.device = classes, in_size, torch.device(device)
+        self.trunk, self.num_priors, self.sparse_heads = list(trunk), tuple(num_priors), sparse_heads
+        self.block = self.L.ssd_opt_block_elems()
+        # inference in block-scaled fp8 (forward(x, "mxfp8")): the plan (mxfp8_vgg_plan, at its first use), the stretch (lo, hi)
+        # of param_bf16 that holds the fp8 layers' filters and its quantised form
+        self._vgg_mx, self._mx_range = None, None
+        self.mx_filters = mx.FlatStore()
+        self._plan_shapes()
+        self._plan_params()
 
     def _plan_shapes(self):
         s = self.in_size
@@ -909,8 +912,18 @@ class SSDEngine:
             return self._forward_vgg_mxfp8(x)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
-        self._vgg_fp8_fwd = False
+        self.last_forward = "bf16"
         return self._walk(x, self._bf16_node)
+
+    def _head_fwd(self, lvl, c, ws):
+        """The head of level lvl (behind the L2 normalisation of its map where the engine has one), into c["loc"] / c["conf"]."""
+        wt, bt = self.head_params[lvl]
+        src = c["acts"][self.fm[lvl][0] + 1]
+        if lvl == 0 and self.l2norm is not None:
+            src = ops.l2norm_fwd(src, self.view(self.l2norm_scale, self.param), out=c["l2n_y"], rnorm=c["l2n_r"],
+                                 eps=self.l2norm.eps)
+        ops.conv2d_head_fwd(src, self.view(wt, self.param_bf16), self.view(bt, self.param), c["loc"], c["conf"],
+                            self.num_priors[lvl], self.classes, self.level_off[lvl], ws=ws)
 
     def _walk(self, x, launch_node):
         """The forward pass: trunk nodes through launch_node(i, c) (the chain excepted), heads, chain and their streams."""
@@ -922,16 +935,6 @@ class SSDEngine:
         side = self._side_stream() if self.overlap_heads else None
         tail = self._streams.tail_stream() if side is not None and self.tail_stream else None
         fm_level = {ni: lvl for lvl, (ni, _, _) in enumerate(self.fm)}
-
-        def head(lvl, ws):
-            ni = self.fm[lvl][0]
-            wt, bt = self.head_params[lvl]
-            src = acts[ni + 1]
-            if lvl == 0 and self.l2norm is not None:
-                src = ops.l2norm_fwd(src, self.view(self.l2norm_scale, self.param), out=c["l2n_y"], rnorm=c["l2n_r"],
-                                     eps=self.l2norm.eps)
-            ops.conv2d_head_fwd(src, self.view(wt, self.param_bf16), self.view(bt, self.param), c["loc"],
-                                c["conf"], self.num_priors[lvl], self.classes, self.level_off[lvl], ws=ws)
 
         def after_node(i):
             """Launch the head of the feature map node i produced, where it runs next to the trunk."""
@@ -946,7 +949,7 @@ class SSDEngine:
             else:
                 return
             with _Streams.behind(s, main):
-                head(lvl, ws)
+                self._head_fwd(lvl, c, ws)
 
         self.bits_valid = set()
         for i, nd in enumerate(self.nodes):
@@ -973,7 +976,7 @@ class SSDEngine:
                         if lvl is not None and tail is not None and self.chain_heads_split and lvl not in self.SIDE_HEADS:
                             nth += 1
                             if nth % 2 == 0:
-                                head(lvl, self._ws)           # (the main stream has nothing else left to do)
+                                self._head_fwd(lvl, c, self._ws)           # (the main stream has nothing else left to do)
                                 continue
                         after_node(j)
                     break
@@ -982,7 +985,7 @@ class SSDEngine:
             after_node(i)
         for lvl in range(len(self.fm)):
             if side is None or (lvl not in self.SIDE_HEADS and tail is None):
-                head(lvl, self._ws)
+                self._head_fwd(lvl, c, self._ws)
         if side is not None:
             main.wait_stream(side)
             if tail is not None:
@@ -1037,52 +1040,48 @@ class SSDEngine:
         """mxfp8_vgg_plan of this engine's trunk: (fp8, pooled, quant, writes)."""
         if self._vgg_mx is None:
             fp8, pooled, quant, writes = mxfp8_vgg_plan(self.nodes, self.chain_start)
-            # the fp8 layers' filters: ONE ops.quantize_mx_fp8 over their stretch of param_bf16 (conv filters start on
-            # optimizer-block boundaries, so every layer's (q, scale) is a slice of the result)
+            # the fp8 layers' filters: their stretch of param_bf16 (conv filters start on optimizer-block boundaries, so every
+            # layer's (q, scale) is a slice of mx_filters)
             lo = min(self.conv_params[i][0].offset for i in fp8)
             hi = max(bt.block0 + bt.nblocks for _, bt in (self.conv_params[i] for i in fp8)) * self.block
             assert all((self.conv_params[i][0].offset - lo) % 32 == 0 for i in fp8) and lo % 32 == 0 and (hi - lo) % 32 == 0
             self._vgg_mx = (fp8, pooled, quant, writes)
-            self._vgg_mx_range = (lo, hi)
+            self._mx_range = (lo, hi)
         return self._vgg_mx
 
-    def vgg_mxfp8_acts(self, B):
-        """{node: (q u8 [B,H,W,C], scale u8 [B,H,W,C/32])} for every node whose fp8 form the fp8 forward stores, beside the bf16
-        activations of batch size B (allocated at the first fp8 forward of that batch size; a bf16-only run allocates none)."""
-        c = self._acts(B)
-        mx = c.get("vgg_mxfp8")
-        if mx is None:
-            mx = {}
-            for i, w in self.vgg_mxfp8_plan()[3].items():
-                if "fp8" in w:
-                    nd = self.nodes[i]
-                    shape = (B, nd["hout"], nd["hout"], nd["cout"])
-                    mx[i] = (torch.empty(shape, dtype=torch.uint8, device=self.device),
-                             torch.empty(shape[:3] + (nd["cout"] // 32,), dtype=torch.uint8, device=self.device))
-            c["vgg_mxfp8"] = mx
-        return mx
+    def _mx_act_writes(self):
+        """{node: forms of its output the fp8 forward stores}."""
+        return self.vgg_mxfp8_plan()[3]
 
-    def vgg_mxfp8_weights(self, i):
+    def _mx_pairs(self, B, key, nodes):
+        """{node: mx.pair of its [B,H,W,C] map} for `nodes`, kept under `key` beside the bf16 activations of batch size B
+        (allocated at the first use for that batch size: a bf16-only run allocates none)."""
+        c = self._acts(B)
+        if key not in c:
+            c[key] = {i: mx.pair((B, self.nodes[i]["hout"], self.nodes[i]["hout"], self.nodes[i]["cout"]), self.device)
+                      for i in nodes}
+        return c[key]
+
+    def mxfp8_acts(self, B):
+        """{node: (q u8 [B,H,W,C], scale u8 [B,H,W,C/32])} for every node whose fp8 form the fp8 forward stores."""
+        return self._mx_pairs(B, "mxfp8", [i for i, w in self._mx_act_writes().items() if "fp8" in w])
+
+    def mxfp8_weights(self, i):
         """(q [Cout,k,k,Cin], scale [Cout,k,k,Cin/32]) of fp8 node i as the last fp8 forward quantised them."""
-        nd, (wt, _) = self.nodes[i], self.conv_params[i]
-        q, sc = self._vgg_mx_w
-        o = wt.offset - self._vgg_mx_range[0]
-        shape = (nd["cout"], nd["k"], nd["k"], nd["cin"])
-        return q[o:o + wt.numel].view(shape), sc[o // 32:(o + wt.numel) // 32].view(shape[:3] + (nd["cin"] // 32,))
+        wt = self.conv_params[i][0]
+        return self.mx_filters.view(wt.offset - self._mx_range[0], wt.shape)
+
+    def _quantize_filters(self):
+        lo, hi = self._mx_range
+        self.mx_filters.quantize(self.param_bf16[lo:hi])
 
     def _forward_vgg_mxfp8(self, x):
-        self.vgg_mxfp8_plan()
-        mx = self.vgg_mxfp8_acts(x.shape[0])
-        lo, hi = self._vgg_mx_range
-        if self._vgg_mx_w is None:
-            self._vgg_mx_w = (torch.empty((hi - lo,), dtype=torch.uint8, device=self.device),
-                              torch.empty(((hi - lo) // 32,), dtype=torch.uint8, device=self.device))
-        # quantised at every fp8 forward, nothing cached: no path that writes param_bf16 can leave a stale copy behind
-        ops.quantize_mx_fp8(self.param_bf16[lo:hi], q=self._vgg_mx_w[0], scale=self._vgg_mx_w[1])
-        self._vgg_fp8_fwd = True               # the bf16 maps, ReLU bits and pool codes backward() reads are not all written
-        return self._walk(x, lambda i, c: self._mxfp8_node(i, c, mx))
+        maps8 = self.mxfp8_acts(x.shape[0])
+        self._quantize_filters()
+        self.last_forward = "mxfp8"            # the bf16 maps, ReLU bits and pool codes backward() reads are not all written
+        return self._walk(x, lambda i, c: self._mxfp8_node(i, c, maps8))
 
-    def _mxfp8_node(self, i, c, mx):
+    def _mxfp8_node(self, i, c, maps8):
         """Launch trunk node i of the fp8 forward: an fp8 convolution (with the pool behind it where the plan fuses one), or
         node i as the bf16 forward launches it (+ the plan's one standalone quantise of its output)."""
         fp8, pooled, quant, writes = self._vgg_mx
@@ -1091,16 +1090,16 @@ class SSDEngine:
         if i not in fp8:
             self._bf16_node(i, c)
             if i in quant:
-                ops.quantize_mx_fp8(c["acts"][i + 1], q=mx[i][0], scale=mx[i][1])
+                ops.quantize_mx_fp8(c["acts"][i + 1], q=maps8[i][0], scale=maps8[i][1])
             return
         nd, acts = self.nodes[i], c["acts"]
-        xq, xs = mx[i - 1]
-        wq, ws = self.vgg_mxfp8_weights(i)
+        xq, xs = maps8[i - 1]
+        wq, ws = self.mxfp8_weights(i)
         bias = self.view(self.conv_params[i][1], self.param)
         args = (xq, xs, wq, ws, bias, nd["stride"], nd["pt"], nd["pl"], nd["hout"], nd["hout"], True)
         o = i + 1 if i + 1 in pooled else i         # the node whose map this launch writes
         w = writes[o]
-        q, sc = mx.get(o, (None, None))
+        q, sc = maps8.get(o, (None, None))
         kw = dict(want_bf16="bf16" in w, want_fp8="fp8" in w, out=acts[o + 1], out_q=q, out_scale=sc)
         if o != i:
             pnd = self.nodes[o]
@@ -1170,7 +1169,7 @@ class SSDEngine:
         The data-gradient chain (the critical path) runs on the current stream, every weight gradient on the side
         stream as soon as its input gradient exists: the split reductions and round tails of one overlap the MFMA
         work of the other.  Each launch still sums in a fixed order, so results do not depend on the overlap."""
-        if self._vgg_fp8_fwd:
+        if self.last_forward == "mxfp8":
             raise RuntimeError("backward() after an mxfp8 forward: it writes neither the bf16 maps nor the ReLU bits and pool "
                                "codes backward() reads; run forward(x) in bf16 first")
         if heads is None and self.sparse_heads:

@@ -1406,16 +1406,53 @@ def maxpool2x2_bwd(x, y, dy, out=None):
     return out
 
 
+def _mx_pair(shape, device):
+    """Uninitialised (q, scale) uint8 tensors of the MX-fp8 form of a [..., C] map: one e4m3 byte per element, one E8M0 scale
+    byte per 32 channels (at least one: a C the kernels do not serve still gets its refusal from them).  mx.pair is the
+    checked form; the only other place that spells this allocation."""
+    shape = tuple(shape)
+    return (torch.empty(shape, dtype=torch.uint8, device=device),
+            torch.empty(shape[:-1] + (max(shape[-1] // 32, 1),), dtype=torch.uint8, device=device))
+
+
+def _mx_default(shape, device, q, scale):
+    """(q, scale) as handed in; whichever is None from a fresh _mx_pair."""
+    if q is None or scale is None:
+        fresh = _mx_pair(shape, device)
+        q, scale = fresh[0] if q is None else q, fresh[1] if scale is None else scale
+    return q, scale
+
+
+def _mx_operands(xq, xs, wq, ws, bhwk, wshape):
+    """Check the operand quadruple of an fp8 convolution: (xq, xs) the MX-fp8 form of a [B,H,W,K] map, (wq, ws) that of
+    filters [N,k,k,K]; K is the GEMM's reduction, one scale byte per 32 of it."""
+    bhwk, wshape = tuple(bhwk), tuple(wshape)
+    K = bhwk[3]
+    assert xq.shape == bhwk and wq.shape == wshape and xs.shape == bhwk[:3] + (K // 32,) and ws.shape == wshape[:3] + (K // 32,)
+    for t in (xq, xs, wq, ws):
+        _dev(t, torch.uint8)
+
+
+def _mx_outputs(shape, device, want_bf16, want_fp8, out, out_q, out_scale):
+    """The outputs of an fp8 convolution with a bf16 epilogue, an fp8 one or both: (out, out_q, out_scale, result) -- an
+    output that is not wanted comes back as None (the C call's null), a wanted one that was not handed in is allocated;
+    result is what the wrapper returns: the bf16 map, (q, scale), or (bf16, q, scale) when both are wanted."""
+    assert want_bf16 or want_fp8
+    if not want_bf16:
+        out = None
+    elif out is None:
+        out = torch.empty(tuple(shape), dtype=torch.bfloat16, device=device)
+    out_q, out_scale = _mx_default(shape, device, out_q, out_scale) if want_fp8 else (None, None)
+    return out, out_q, out_scale, (out if not want_fp8 else (out, out_q, out_scale) if want_bf16 else (out_q, out_scale))
+
+
 def quantize_mx_fp8(x, q=None, scale=None):
     """bf16 tensor (last dimension a multiple of 32) -> (q uint8 same shape: OCP e4m3 bytes, scale uint8 [..., C/32]: E8M0).
     A block that holds a NaN or an infinity comes out as 32 NaN bytes (0x7F) under the scale byte 127."""
     L = _lib.lib()
     _bf(x)
     assert x.shape[-1] % 32 == 0
-    if q is None:
-        q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    if scale is None:
-        scale = torch.empty(x.shape[:-1] + (x.shape[-1] // 32,), dtype=torch.uint8, device=x.device)
+    q, scale = _mx_default(x.shape, x.device, q, scale)
     assert q.numel() == x.numel() and scale.numel() == x.numel() // 32
     _lib.check(L.ssd_quantize_mx_fp8(_ptr(x), _ptr(q), _ptr(scale), x.numel(), _stream()))
     return q, scale
@@ -1452,25 +1489,13 @@ def conv2d_fwd_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, w
     L = _lib.lib()
     B, H, W, Cin = xq.shape
     Cout, k = wq.shape[0], wq.shape[1]
-    assert want_bf16 or want_fp8
-    assert wq.shape == (Cout, k, k, Cin) and xs.shape == (B, H, W, Cin // 32) and ws.shape == (Cout, k, k, Cin // 32)
-    for t in (xq, xs, wq, ws):
-        _dev(t, torch.uint8)
-    if want_bf16 and out is None:
-        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.bfloat16, device=xq.device)
-    if want_fp8:
-        if out_q is None:
-            out_q = torch.empty((B, Ho, Wo, Cout), dtype=torch.uint8, device=xq.device)
-        if out_scale is None:
-            out_scale = torch.empty((B, Ho, Wo, max(Cout // 32, 1)), dtype=torch.uint8, device=xq.device)
-    rc = L.ssd_conv2d_fwd_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
-                                _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout, k,
-                                stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, _stream())
+    _mx_operands(xq, xs, wq, ws, (B, H, W, Cin), (Cout, k, k, Cin))
+    out, out_q, out_scale, result = _mx_outputs((B, Ho, Wo, Cout), xq.device, want_bf16, want_fp8, out, out_q, out_scale)
+    rc = L.ssd_conv2d_fwd_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out), _ptr(out_q), _ptr(out_scale),
+                                B, H, W, Cin, Cout, k, stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, _stream())
     _lib.check(rc, unsupported="block-scaled fp8 forward needs Cin % 128 == 0, k in (1, 3), stride in (1, 2), Cout % 8 == 0 "
                                "and Cout % 32 == 0 for an fp8 output")
-    if want_bf16 and want_fp8:
-        return out, out_q, out_scale
-    return out if want_bf16 else (out_q, out_scale)
+    return result
 
 
 def conv2d_fwd_pool_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, relu, same, want_bf16=True, want_fp8=False,
@@ -1481,26 +1506,14 @@ def conv2d_fwd_pool_mxfp8(xq, xs, wq, ws, bias, stride, pad_t, pad_l, Ho, Wo, re
     L = _lib.lib()
     B, H, W, Cin = xq.shape
     Cout, k = wq.shape[0], wq.shape[1]
-    assert want_bf16 or want_fp8
-    assert wq.shape == (Cout, k, k, Cin) and xs.shape == (B, H, W, Cin // 32) and ws.shape == (Cout, k, k, Cin // 32)
-    for t in (xq, xs, wq, ws):
-        _dev(t, torch.uint8)
+    _mx_operands(xq, xs, wq, ws, (B, H, W, Cin), (Cout, k, k, Cin))
     Hp, Wp = ((Ho + 1) // 2, (Wo + 1) // 2) if same else (Ho // 2, Wo // 2)
-    if want_bf16 and out is None:
-        out = torch.empty((B, Hp, Wp, Cout), dtype=torch.bfloat16, device=xq.device)
-    if want_fp8:
-        if out_q is None:
-            out_q = torch.empty((B, Hp, Wp, Cout), dtype=torch.uint8, device=xq.device)
-        if out_scale is None:
-            out_scale = torch.empty((B, Hp, Wp, max(Cout // 32, 1)), dtype=torch.uint8, device=xq.device)
-    _pooled_shapes((B, Hp, Wp), *(((out, Cout),) if want_bf16 else ()) + (((out_q, Cout), (out_scale, max(Cout // 32, 1))) if want_fp8 else ()))
-    rc = L.ssd_conv2d_fwd_pool_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out) if want_bf16 else None,
-                                     _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
-                                     k, stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, Hp, Wp, _stream())
+    out, out_q, out_scale, result = _mx_outputs((B, Hp, Wp, Cout), xq.device, want_bf16, want_fp8, out, out_q, out_scale)
+    _pooled_shapes((B, Hp, Wp), *((t, ch) for t, ch in ((out, Cout), (out_q, Cout), (out_scale, max(Cout // 32, 1))) if t is not None))
+    rc = L.ssd_conv2d_fwd_pool_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out), _ptr(out_q), _ptr(out_scale),
+                                     B, H, W, Cin, Cout, k, stride, pad_t, pad_l, Ho, Wo, 1 if relu else 0, Hp, Wp, _stream())
     _lib.check(rc, unsupported="pooled block-scaled fp8 forward needs k = 3, stride 1, Cin % 128 == 0 and Cout % 32 == 0")
-    if want_bf16 and want_fp8:
-        return out, out_q, out_scale
-    return out if want_bf16 else (out_q, out_scale)
+    return result
 
 
 def conv2d_bwd_data_mxfp8(dyq, dys, wtq, wts, relu_src, x_shape, stride, pad_t, pad_l, accumulate=False, want_bf16=True,
@@ -1513,30 +1526,18 @@ def conv2d_bwd_data_mxfp8(dyq, dys, wtq, wts, relu_src, x_shape, stride, pad_t, 
     B, H, W, Cin = x_shape
     _, Ho, Wo, Cout = dyq.shape
     k = wtq.shape[1]
-    assert want_bf16 or want_fp8
-    assert wtq.shape == (Cin, k, k, Cout) and dys.shape == (B, Ho, Wo, Cout // 32) and wts.shape == (Cin, k, k, Cout // 32)
-    for t in (dyq, dys, wtq, wts):
-        _dev(t, torch.uint8)
+    _mx_operands(dyq, dys, wtq, wts, (B, Ho, Wo, Cout), (Cin, k, k, Cout))
     if relu_src is not None:
         _bf(relu_src)
         assert relu_src.shape == tuple(x_shape)
     if stride != 1:
         raise NotImplementedError("block-scaled fp8 data gradient: stride 1 only (stride-2 layers use conv2d_bwd_data)")
-    if want_bf16 and out is None:
-        assert not accumulate
-        out = torch.empty(x_shape, dtype=torch.bfloat16, device=dyq.device)
-    if want_fp8:
-        if out_q is None:
-            out_q = torch.empty(x_shape, dtype=torch.uint8, device=dyq.device)
-        if out_scale is None:
-            out_scale = torch.empty(tuple(x_shape[:3]) + (max(Cin // 32, 1),), dtype=torch.uint8, device=dyq.device)
-    rc = L.ssd_conv2d_bwd_data_mxfp8(_ptr(dyq), _ptr(dys), _ptr(wtq), _ptr(wts), _ptr(relu_src), _ptr(out) if want_bf16 else None,
-                                     _ptr(out_q) if want_fp8 else None, _ptr(out_scale) if want_fp8 else None, B, H, W, Cin, Cout,
-                                     k, pad_t, pad_l, Ho, Wo, 1 if accumulate else 0, _stream())
+    assert out is not None or not (want_bf16 and accumulate)
+    out, out_q, out_scale, result = _mx_outputs(x_shape, dyq.device, want_bf16, want_fp8, out, out_q, out_scale)
+    rc = L.ssd_conv2d_bwd_data_mxfp8(_ptr(dyq), _ptr(dys), _ptr(wtq), _ptr(wts), _ptr(relu_src), _ptr(out), _ptr(out_q),
+                                     _ptr(out_scale), B, H, W, Cin, Cout, k, pad_t, pad_l, Ho, Wo, 1 if accumulate else 0, _stream())
     _lib.check(rc, unsupported="block-scaled fp8 data gradient needs Cout % 128 == 0, Cin % 32 == 0 and k in (1, 3)")
-    if want_bf16 and want_fp8:
-        return out, out_q, out_scale
-    return out if want_bf16 else (out_q, out_scale)
+    return result
 
 
 def add_relu_fwd_mxfp8(a, b, out=None, q=None, scale=None):
@@ -1546,10 +1547,7 @@ def add_relu_fwd_mxfp8(a, b, out=None, q=None, scale=None):
     assert a.shape == b.shape and a.shape[-1] % 32 == 0
     if out is None:
         out = torch.empty_like(a)
-    if q is None:
-        q = torch.empty(a.shape, dtype=torch.uint8, device=a.device)
-    if scale is None:
-        scale = torch.empty(a.shape[:-1] + (a.shape[-1] // 32,), dtype=torch.uint8, device=a.device)
+    q, scale = _mx_default(a.shape, a.device, q, scale)
     rc = L.ssd_add_relu_fwd_mxfp8(_ptr(a), _ptr(b), _ptr(out), _ptr(q), _ptr(scale), a.numel(), _stream())
     _lib.check(rc, unsupported="add_relu_fwd_mxfp8")
     return out, q, scale

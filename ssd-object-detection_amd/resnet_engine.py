@@ -19,8 +19,8 @@ kernels, heads' backward from the loss's compact rows) plus csrc/eltwise.hip (Ad
 Parameter storage, clip + Adam, checkpoints: inherited."""
 import torch
 
-from . import _lib, ops
-from .engine import SSDEngine, SSD512_NUM_PRIORS
+from . import _lib, mx, ops
+from .engine import SSDEngine, SSD512_NUM_PRIORS, mxfp8_eligible
 
 
 def resnet50_ssd512_graph(batchnorm=False):
@@ -65,14 +65,6 @@ def _kind(nd):
     return nd.get("kind", nd.get("op"))           # planned node (engine.nodes) or graph node (resnet50_ssd512_graph)
 
 
-def mxfp8_eligible(nd):
-    """Whether node `nd` runs in block-scaled fp8 (ops.conv2d_fwd_mxfp8): a convolution other than the stem whose input
-    channels are whole MX k-steps (Cin % 128 == 0) and whose output channels are whole MX blocks (Cout % 32 == 0)."""
-    src = nd["src"]
-    return (_kind(nd) == "conv" and isinstance(src, int) and src >= 0 and nd["cin"] % 128 == 0 and nd["cout"] % 32 == 0
-            and nd["k"] in (1, 3) and nd["stride"] in (1, 2))
-
-
 def mxfp8_plan(nodes, train=False):
     """The fp8 forward of a graph (resnet50_ssd512_graph() or the engine's planned nodes; no device needed).  Returns
     (fp8, writes): the set of nodes that run in fp8, and for every node the outputs it writes, a frozenset of "bf16" / "fp8".
@@ -82,7 +74,7 @@ def mxfp8_plan(nodes, train=False):
     quantisation of an activation.  train=True: the training-mode forward, whose producers also write the bf16 map of every
     node backward() reads -- each convolution's input (its weight gradient; it is also every ReLU mask a data gradient
     applies) besides the adds (identity-shortcut masks) and the feature maps (heads), which write it anyway."""
-    fp8 = {i for i, nd in enumerate(nodes) if mxfp8_eligible(nd)}
+    fp8 = {i for i, nd in enumerate(nodes) if mxfp8_eligible(nd) and nd["src"] >= 0}     # (>= 0: not the stem)
     writes = {i: set() for i in range(len(nodes))}
     for i, nd in enumerate(nodes):
         if nd["feature"] or _kind(nd) == "add":
@@ -205,17 +197,6 @@ class ResNet50SSDEngine(SSDEngine):
         self.overlap_heads = False
         self._bn_train = False                 # the last forward of a batchnorm engine used (and saved) batch statistics
         self._ws_bn = ops.MatchWorkspace()     # slab partials of the batch normalisation kernels
-        bn = self.batchnorm is not None        # a batchnorm engine has no fp8 plan: forward(x, "mxfp8") refuses
-        self.mx_fp8, self.mx_writes = (set(), {}) if bn else mxfp8_plan(self.nodes)
-        # filters of the fp8 layers: ONE ssd_quantize_mx_fp8 over the trunk's part of param_bf16 at every fp8 forward (conv
-        # filters start on optimizer-block boundaries, multiples of 32 elements, so each layer's (q, scale) is a slice of it);
-        # nothing is cached against the weights, so no path that writes param_bf16 can leave a stale copy behind
-        self.n_trunk = max(bt.block0 + bt.nblocks for _, bt in self.conv_params.values()) * self.block
-        self._mx_w = None                      # (q u8 [n_trunk], scale u8 [n_trunk / 32]), allocated at the first fp8 forward
-        self._mx_forward = False               # the last forward ran in fp8: the bf16 activations backward() needs are incomplete
-        self.mx_train_writes = {} if bn else mxfp8_plan(self.nodes, train=True)[1]
-        self._mx_train = False                 # ... in training mode: every bf16 map backward() reads was written
-        self._mx_wt = None                     # (q, scale) of the fp8 data gradients' transposed filters, at every fp8 backward
 
     # ---------------------------------------------------------------- static planning
     @classmethod
@@ -223,15 +204,9 @@ class ResNet50SSDEngine(SSDEngine):
         """The static plan alone -- graph, nodes, grids, A, tensors (names, indices, blocks) -- without a device: nothing is
         allocated or launched.  For what needs the layout only: decay_table(), ready_order(), bucket plans."""
         eng = cls.__new__(cls)
-        eng.L = _lib.lib()
-        eng.l2norm = None
         eng.batchnorm = ops.BatchNormSpec.of(batchnorm)
         eng.graph = resnet50_ssd512_graph(batchnorm=eng.batchnorm is not None)
-        eng.classes, eng.in_size, eng.device = classes, in_size, torch.device("cpu")
-        eng.trunk, eng.num_priors, eng.sparse_heads = [], tuple(SSD512_NUM_PRIORS), True
-        eng.block = eng.L.ssd_opt_block_elems()
-        eng._plan_shapes()
-        eng._plan_params()
+        eng._plan(classes, in_size, [], SSD512_NUM_PRIORS, "cpu", None, True)
         return eng
 
     def ready_order(self):
@@ -259,6 +234,28 @@ class ResNet50SSDEngine(SSDEngine):
         self.bn_channels = off
         self.bn_convs = {self.nodes[i]["src"] for i in self.bn_params}      # the normalised convolutions
 
+    def _plan_params(self):
+        super()._plan_params()
+        # the fp8 plans (a batchnorm engine has none: forward(x, "mxfp8") refuses)
+        n, bn = len(self.nodes), self.batchnorm is not None
+        self.mx_fp8, self.mx_writes = (set(), {}) if bn else mxfp8_plan(self.nodes)
+        self.mx_train_writes = {} if bn else mxfp8_plan(self.nodes, train=True)[1]
+        self.mx_dgrad, self.mx_groot, self.mx_gmaps = (set(), list(range(n)), {}) if bn else mxfp8_bwd_plan(self.nodes)
+        # mx_filters quantises the trunk's part of param_bf16 (conv filters start on optimizer-block boundaries, multiples of
+        # 32 elements, so each layer's (q, scale) is a slice of it)
+        self._mx_range = (0, max(bt.block0 + bt.nblocks for _, bt in self.conv_params.values()) * self.block)
+        # the transposed filters as slices of ONE buffer, the fp8 data gradients' first: mx_filters_t quantises its front
+        # (every slice starts on a 32-element block: Cout % 32 == 0 for all of them)
+        self.wt_off, self.n_wt8, off = {}, 0, 0               # node -> offset in the flat buffer; the fp8 front; n_wt in all
+        for i in sorted((i for i in self.conv_params if i > 0), key=lambda i: (i not in self.mx_dgrad, i)):
+            self.wt_off[i] = off
+            off += self.conv_params[i][0].numel
+            assert off % 32 == 0
+            if i in self.mx_dgrad:
+                self.n_wt8 = off
+        self.n_wt = off
+        self.mx_filters_t = mx.FlatStore()
+
     def _alloc_params(self):
         super()._alloc_params()
         if self.batchnorm is not None:
@@ -269,21 +266,9 @@ class ResNet50SSDEngine(SSDEngine):
             self._bn_rstd = torch.empty(n, dtype=torch.float32, device=dev)
             # where conv2d_bwd_weight puts the bias gradient of a normalised convolution: never read (the true gradient is 0)
             self._bn_dbias = torch.empty(max(nd["cout"] for nd in self.nodes), dtype=torch.float32, device=dev)
-            self.mx_dgrad, self.mx_groot, self.mx_gmaps = set(), list(range(len(self.nodes))), {}
-        else:
-            self.mx_dgrad, self.mx_groot, self.mx_gmaps = mxfp8_bwd_plan(self.nodes)
-        # the transposed filters as slices of ONE buffer, the fp8 data gradients' first: their MX-fp8 form is then one
-        # ssd_quantize_mx_fp8 over its front (every slice starts on a 32-element block: Cout % 32 == 0 for all of them)
-        order = sorted(self.w_t, key=lambda i: (i not in self.mx_dgrad, i))
-        sizes = [self.w_t[i].numel() for i in order]
-        assert all(v % 32 == 0 for v in sizes)
-        flat = torch.empty(sum(sizes), dtype=torch.bfloat16, device=self.device)
-        self.wt_off, off = {}, 0
-        for i, v in zip(order, sizes):
-            self.wt_off[i] = off
-            self.w_t[i] = flat[off:off + v].view(self.w_t[i].shape)
-            off += v
-        self.n_wt8 = sum(v for i, v in zip(order, sizes) if i in self.mx_dgrad)
+        flat = torch.empty(self.n_wt, dtype=torch.bfloat16, device=self.device)
+        for i, off in self.wt_off.items():
+            self.w_t[i] = flat[off:off + self.w_t[i].numel()].view(self.w_t[i].shape)
         self._wt_flat = flat
 
     def init_params(self, seed=0):
@@ -332,64 +317,22 @@ class ResNet50SSDEngine(SSDEngine):
                                for i, nd in enumerate(self.nodes) if nd["kind"] == "pool3"}
         return c
 
-    def mxfp8_acts(self, B):
-        """{node: (q u8 [B,H,W,C], scale u8 [B,H,W,C/32])} for every node that writes an fp8 map, beside the bf16 activations of
-        batch size B (allocated at the first fp8 forward of that batch size; a bf16-only run allocates none)."""
-        c = self._acts(B)
-        mx = c.get("mxfp8")
-        if mx is None:
-            mx = {}
-            for i, w in self.mx_writes.items():
-                if "fp8" in w:
-                    nd = self.nodes[i]
-                    shape = (B, nd["hout"], nd["hout"], nd["cout"])
-                    mx[i] = (torch.empty(shape, dtype=torch.uint8, device=self.device),
-                             torch.empty(shape[:3] + (nd["cout"] // 32,), dtype=torch.uint8, device=self.device))
-            c["mxfp8"] = mx
-        return mx
-
-    def mxfp8_weights(self, i):
-        """(q [Cout,k,k,Cin], scale [Cout,k,k,Cin/32]) of fp8 node i as the last fp8 forward quantised them."""
-        nd, (wt, _) = self.nodes[i], self.conv_params[i]
-        q, sc = self._mx_w
-        shape = (nd["cout"], nd["k"], nd["k"], nd["cin"])
-        return (q[wt.offset:wt.offset + wt.numel].view(shape),
-                sc[wt.offset // 32:(wt.offset + wt.numel) // 32].view(shape[:3] + (nd["cin"] // 32,)))
+    def _mx_act_writes(self):
+        return self.mx_writes
 
     def mxfp8_grads(self, B):
         """{root map: (q u8 [B,H,W,C], scale u8 [B,H,W,C/32])}: the fp8 forms of the gradient maps the fp8 data gradients read
-        (mxfp8_bwd_plan), allocated at the first fp8 backward of batch size B (a bf16-only run allocates none)."""
-        c = self._acts(B)
-        mx = c.get("mxfp8_grad")
-        if mx is None:
-            mx = {}
-            for r in self.mx_gmaps:
-                nd = self.nodes[r]
-                shape = (B, nd["hout"], nd["hout"], nd["cout"])
-                mx[r] = (torch.empty(shape, dtype=torch.uint8, device=self.device),
-                         torch.empty(shape[:3] + (nd["cout"] // 32,), dtype=torch.uint8, device=self.device))
-            c["mxfp8_grad"] = mx
-        return mx
+        (mxfp8_bwd_plan), allocated at the first fp8 backward of batch size B."""
+        return self._mx_pairs(B, "mxfp8_grad", self.mx_gmaps)
 
     def mxfp8_wt(self, i):
         """(q [Cin,k,k,Cout], scale [Cin,k,k,Cout/32]) of the transposed filters of fp8 data gradient i as the last fp8
         backward quantised them."""
-        nd, o = self.nodes[i], self.wt_off[i]
-        q, sc = self._mx_wt
-        shape = tuple(self.w_t[i].shape)
-        return q[o:o + self.w_t[i].numel()].view(shape), sc[o // 32:(o + self.w_t[i].numel()) // 32].view(shape[:3] + (nd["cout"] // 32,))
+        cout, k, _, cin = self.conv_params[i][0].shape
+        return self.mx_filters_t.view(self.wt_off[i], (cin, k, k, cout))
 
     def _quantize_wt(self):
-        if self._mx_wt is None:
-            self._mx_wt = (torch.empty((self.n_wt8,), dtype=torch.uint8, device=self.device),
-                           torch.empty((self.n_wt8 // 32,), dtype=torch.uint8, device=self.device))
-        ops.quantize_mx_fp8(self._wt_flat[:self.n_wt8], q=self._mx_wt[0], scale=self._mx_wt[1])
-
-    def _quantize_filters(self):
-        if self._mx_w is None:
-            self._mx_w = (torch.empty((self.n_trunk,), dtype=torch.uint8, device=self.device),
-                          torch.empty((self.n_trunk // 32,), dtype=torch.uint8, device=self.device))
-        ops.quantize_mx_fp8(self.param_bf16[:self.n_trunk], q=self._mx_w[0], scale=self._mx_w[1])
+        self.mx_filters_t.quantize(self._wt_flat[:self.n_wt8])
 
     def _in(self, acts, src):
         return acts[src + 1]                   # acts[0] = network input, acts[i + 1] = output of node i
@@ -406,21 +349,34 @@ class ResNet50SSDEngine(SSDEngine):
             if self.batchnorm is not None:
                 raise ValueError("forward(x, 'mxfp8') on a batchnorm engine: the fp8 plan rests on producer epilogues; fold "
                                  "the trained network first (folded()) and run that engine in fp8")
-            return self._forward_mxfp8(x, train)
-        if precision != "bf16":
+        elif precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
-        self._mx_forward = self._mx_train = False
-        self._bn_train = self.batchnorm is not None and bool(train)
+        fp8 = precision == "mxfp8"
         B = x.shape[0]
         c = self._acts(B)
         acts = c["acts"]
         acts[0] = x
         self.bits_valid = set()
+        self.last_forward = ("mxfp8_train" if train else "mxfp8") if fp8 else "bf16"
+        self._bn_train = self.batchnorm is not None and bool(train)
+        maps8 = writes = None                  # bf16: no node writes an fp8 form and no convolution reads one
+        if fp8:
+            maps8, writes = self.mxfp8_acts(B), self.mx_train_writes if train else self.mx_writes
+            self._quantize_filters()
         for i, nd in enumerate(self.nodes):
+            w = writes[i] if fp8 else ()
             if nd["kind"] == "conv":
                 wt, bt = self.conv_params[i]
-                ops.conv2d_fwd(self._in(acts, nd["src"]), self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"],
-                               nd["pt"], nd["pl"], nd["hout"], nd["hout"], nd["relu"], out=acts[i + 1], ws=self._ws)
+                if fp8 and i in self.mx_fp8:
+                    xq, xs = maps8[nd["src"]]
+                    wq, ws = self.mxfp8_weights(i)
+                    q, sc = maps8.get(i, (None, None))
+                    ops.conv2d_fwd_mxfp8(xq, xs, wq, ws, self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"], nd["hout"],
+                                         nd["hout"], nd["relu"], want_bf16="bf16" in w, want_fp8="fp8" in w, out=acts[i + 1],
+                                         out_q=q, out_scale=sc)
+                else:
+                    ops.conv2d_fwd(self._in(acts, nd["src"]), self.view(wt, self.param_bf16), self.view(bt, self.param),
+                                   nd["stride"], nd["pt"], nd["pl"], nd["hout"], nd["hout"], nd["relu"], out=acts[i + 1], ws=self._ws)
             elif nd["kind"] == "bn":
                 gamma, beta = (self.view(t, self.param) for t in self.bn_params[i])
                 rm, rv = self._bn_stat(i, self.bn_running_mean), self._bn_stat(i, self.bn_running_var)
@@ -436,49 +392,12 @@ class ResNet50SSDEngine(SSDEngine):
                 ops.maxpool3x3s2_fwd(self._in(acts, nd["src"]), out=acts[i + 1], code=c["pool3_code"][i])
             else:
                 a, sc = nd["src"]
-                ops.add_relu_fwd(acts[a + 1], acts[sc + 1], out=acts[i + 1])
-        for lvl, (ni, _, _) in enumerate(self.fm):
-            wt, bt = self.head_params[lvl]
-            ops.conv2d_head_fwd(acts[ni + 1], self.view(wt, self.param_bf16), self.view(bt, self.param), c["loc"], c["conf"],
-                                self.num_priors[lvl], self.classes, self.level_off[lvl], ws=self._ws)
-        return c["loc"], c["conf"]
-
-    def _forward_mxfp8(self, x, train):
-        B = x.shape[0]
-        c = self._acts(B)
-        mx = self.mxfp8_acts(B)
-        acts = c["acts"]
-        acts[0] = x
-        self.bits_valid = set()
-        self._mx_forward, self._mx_train = True, bool(train)
-        self._quantize_filters()
-        writes = self.mx_train_writes if train else self.mx_writes
-        for i, nd in enumerate(self.nodes):
-            w = writes[i]
-            if nd["kind"] == "conv":
-                wt, bt = self.conv_params[i]
-                if i in self.mx_fp8:
-                    xq, xs = mx[nd["src"]]
-                    wq, ws = self.mxfp8_weights(i)
-                    q, sc = mx.get(i, (None, None))
-                    ops.conv2d_fwd_mxfp8(xq, xs, wq, ws, self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"], nd["hout"],
-                                         nd["hout"], nd["relu"], want_bf16="bf16" in w, want_fp8="fp8" in w, out=acts[i + 1],
-                                         out_q=q, out_scale=sc)
-                else:
-                    ops.conv2d_fwd(self._in(acts, nd["src"]), self.view(wt, self.param_bf16), self.view(bt, self.param),
-                                   nd["stride"], nd["pt"], nd["pl"], nd["hout"], nd["hout"], nd["relu"], out=acts[i + 1], ws=self._ws)
-            elif nd["kind"] == "pool3":
-                ops.maxpool3x3s2_fwd(self._in(acts, nd["src"]), out=acts[i + 1], code=c["pool3_code"][i])
-            else:
-                a, sc_ = nd["src"]
                 if "fp8" in w:
-                    ops.add_relu_fwd_mxfp8(acts[a + 1], acts[sc_ + 1], out=acts[i + 1], q=mx[i][0], scale=mx[i][1])
+                    ops.add_relu_fwd_mxfp8(acts[a + 1], acts[sc + 1], out=acts[i + 1], q=maps8[i][0], scale=maps8[i][1])
                 else:
-                    ops.add_relu_fwd(acts[a + 1], acts[sc_ + 1], out=acts[i + 1])
-        for lvl, (ni, _, _) in enumerate(self.fm):
-            wt, bt = self.head_params[lvl]
-            ops.conv2d_head_fwd(acts[ni + 1], self.view(wt, self.param_bf16), self.view(bt, self.param), c["loc"], c["conf"],
-                                self.num_priors[lvl], self.classes, self.level_off[lvl], ws=self._ws)
+                    ops.add_relu_fwd(acts[a + 1], acts[sc + 1], out=acts[i + 1])
+        for lvl in range(len(self.fm)):
+            self._head_fwd(lvl, c, self._ws)
         return c["loc"], c["conf"]
 
     def backward(self, dloc, dconf, on_ready=None, fused_adam=None, heads=None, on_dgrad=None, dgrad_precision=None):
@@ -487,7 +406,7 @@ class ResNet50SSDEngine(SSDEngine):
         transposed filters quantised here, once per call); dgrad_precision="bf16" keeps every data gradient in bf16.  Weight
         gradients, heads, stride-2 data gradients and pooling always run in bf16 on the bf16 maps."""
         assert fused_adam is None and on_dgrad is None, "the per-bucket optimizer schedule belongs to the VGG chain engine"
-        if self._mx_forward and not self._mx_train:
+        if self.last_forward == "mxfp8":
             raise RuntimeError("backward() after an inference mxfp8 forward: the bf16 activations it needs were not all "
                                "written; run forward(x) in bf16 or forward(x, 'mxfp8', train=True) first")
         if self.batchnorm is not None and not self._bn_train:
@@ -495,9 +414,9 @@ class ResNet50SSDEngine(SSDEngine):
                                "saved; run forward(x, train=True) first")
         if dgrad_precision not in (None, "bf16", "mxfp8"):
             raise ValueError("dgrad_precision must be 'bf16' or 'mxfp8', not %r" % (dgrad_precision,))
-        if dgrad_precision == "mxfp8" and not self._mx_train:
+        if dgrad_precision == "mxfp8" and self.last_forward != "mxfp8_train":
             raise ValueError("fp8 data gradients need a forward(x, 'mxfp8', train=True) first")
-        fp8 = self._mx_train and dgrad_precision != "bf16"
+        fp8 = self.last_forward == "mxfp8_train" and dgrad_precision != "bf16"
         if heads is None:
             heads = self.heads_from_dense(dloc, dconf)
         c = self._acts(heads.B)

@@ -265,9 +265,9 @@ def poison(engine, c):
     engine.grad.view(torch.int32).fill_(PAD_BITS)
     for t in engine.tensors:
         engine.grad[t.offset:t.offset + t.numel].fill_(float("nan"))
-    if getattr(engine, "_mx_train", False):
+    if engine.last_forward == "mxfp8_train":
         stale = [t for pair in engine.mxfp8_grads(c["acts"][1].shape[0]).values() for t in pair]
-        for t in stale + list(engine._mx_wt or ()):
+        for t in stale + ([engine.mx_filters_t.q, engine.mx_filters_t.scale] if engine.mx_filters_t.allocated else []):
             t.fill_(0x7F)
 
 

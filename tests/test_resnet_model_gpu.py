@@ -127,7 +127,7 @@ def test_model_step_equals_the_hand_composed_step(ops, tmp_path, variant):
         assert_same_state(model.get_engine(), eng)
     assert model.get_engine().step_count == eng.step_count == opt.iterations == 2
     if variant == "mxfp8":                                                # the fp8 path really ran
-        assert model.get_engine()._mx_train and model.get_engine()._mx_wt is not None
+        assert model.get_engine().last_forward == "mxfp8_train" and model.get_engine().mx_filters_t.allocated
 
 
 def test_mxfp8_step_with_bf16_data_gradients(ops, tmp_path):
@@ -144,7 +144,7 @@ def test_mxfp8_step_with_bf16_data_gradients(ops, tmp_path):
     eng.clip_scales(0.01)
     eng.adam(1e-3, eng.grad, 1.0, True)
     assert_same_state(model.get_engine(), eng)
-    assert model.get_engine()._mx_wt is None                              # no fp8 data gradient quantised its filters
+    assert not model.get_engine().mx_filters_t.allocated                            # no fp8 data gradient quantised its filters
 
 
 def test_momentum_sgd_step_without_clipping(ops, tmp_path):
@@ -337,7 +337,7 @@ def test_mxfp8_inference_of_a_plain_resnet_model(ops, tmp_path):
     want = (score, cls, box, ops.nms(score, cls, box, cand, 0.45, 400))
     for a, b in zip(got, want):
         assert torch.equal(a, b)
-    assert model.folds_built == 0 and model.get_engine()._mx_forward
+    assert model.folds_built == 0 and model.get_engine().last_forward.startswith("mxfp8")
 
 
 # ---------------------------------------------------------------------------------------------------- 5. folded fp8 inference

@@ -124,7 +124,7 @@ def test_forward_against_the_oracle(size, B, l2norm):
     assert el < 1e-2 and ec < 1e-2, (el, ec)
     with pytest.raises(NotImplementedError, match="VGG-16"):
         e.forward(x, "mxfp8")
-    assert not e._vgg_fp8_fwd                                             # refused before anything ran: backward() still allowed
+    assert e.last_forward == "bf16"                                          # refused before anything ran: backward() still allowed
 
 
 # ---------------------------------------------------------------- teacher-forced backward

@@ -107,14 +107,14 @@ def test_network_layer_by_layer(ops, engine):
     torch.cuda.synchronize()
     fp8, pooled, quant, writes = eng.vgg_mxfp8_plan()
     assert fp8 == {6, 7, 8, 10, 11, 12, 13, 14, 15, 16} and pooled == {9} and quant == {5}
-    acts, mx = eng._acts(B)["acts"], eng.vgg_mxfp8_acts(B)
+    acts, mx = eng._acts(B)["acts"], eng.mxfp8_acts(B)
     with torch.no_grad():
         q_ref, s_ref = ops.quantize_mx_fp8(acts[6])
         assert torch.equal(mx[5][0], q_ref) and torch.equal(mx[5][1], s_ref), "standalone quantise of pooled map 5"
         for i in sorted(fp8):
             nd = eng.nodes[i]
             xq, xs = mx[i - 1]
-            wq, ws = eng.vgg_mxfp8_weights(i)
+            wq, ws = eng.mxfp8_weights(i)
             bias = eng.view(eng.conv_params[i][1], eng.param)
             args = (xq, xs, wq, ws, bias, nd["stride"], nd["pt"], nd["pl"], nd["hout"], nd["hout"], True)
             ya = conv_ref(ops.dequantize_mx_fp8(xq, xs), ops.dequantize_mx_fp8(wq, ws), bias, *args[5:10])
@@ -172,7 +172,7 @@ def test_determinism_and_isolation(ops):
     B = 4
     x = image(ops, B, 8)
     loc_a, conf_a = (t.clone() for t in eng.forward(x))
-    assert "vgg_mxfp8" not in eng._acts(B) and eng._vgg_mx_w is None, "a bf16-only run allocated fp8 buffers"
+    assert "mxfp8" not in eng._acts(B) and not eng.mx_filters.allocated, "a bf16-only run allocated fp8 buffers"
     loc8, conf8 = (t.clone() for t in eng.forward(x, "mxfp8"))
     loc8b, conf8b = eng.forward(x, "mxfp8")
     assert torch.equal(loc8, loc8b) and torch.equal(conf8, conf8b), "two fp8 forwards differ"

@@ -88,7 +88,7 @@ def main():
     print("device", torch.cuda.get_device_name(0), "| fp8 layers", len(eng.mx_fp8))
     eng._quantize_filters()
     tw = timed(eng._quantize_filters, a.reps)
-    print("filter quantisation (one ssd_quantize_mx_fp8 over %d trunk elements, every fp8 forward): %.1f us" % (eng.n_trunk, tw))
+    print("filter quantisation (one ssd_quantize_mx_fp8 over %d trunk elements, every fp8 forward): %.1f us" % (eng._mx_range[1], tw))
     batches = [int(v) for v in a.batches.split(",")]
     for B in batches:
         whole_network(eng, B, a.reps)

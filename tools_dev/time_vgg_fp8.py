@@ -46,7 +46,7 @@ def alternated(fns, reps):
 
 def per_layer(eng, B, reps):
     c = eng._acts(B)
-    acts, mx = c["acts"], eng.vgg_mxfp8_acts(B)
+    acts, mx = c["acts"], eng.mxfp8_acts(B)
     fp8, pooled, _, writes = eng.vgg_mxfp8_plan()
     print("\nper layer, batch %d (us per launch, mean of %d):" % (B, reps))
     print("%4s %-24s %-10s %9s %9s %7s" % ("node", "layer", "writes", "bf16", "mxfp8", "ratio"))
@@ -58,7 +58,7 @@ def per_layer(eng, B, reps):
         geo = (nd["stride"], nd["pt"], nd["pl"], nd["hout"], nd["hout"], True)
         xb, wb = acts[i], eng.view(wt, eng.param_bf16)
         xq, xs = mx[i - 1]
-        wq, ws = eng.vgg_mxfp8_weights(i)
+        wq, ws = eng.mxfp8_weights(i)
         o = i + 1 if i + 1 in pooled else i
         w = writes[o]
         q, sc = mx.get(o, (None, None))
@@ -103,9 +103,9 @@ def main():
     img = (torch.rand((B, 300, 300, 3), generator=torch.Generator().manual_seed(B)) * 2 - 1).cuda()
     x = ops.image_prep(img, normalize=False)
     eng.forward(x, "mxfp8")
-    lo, hi = eng._vgg_mx_range
-    tw = timed(lambda: ops.quantize_mx_fp8(eng.param_bf16[lo:hi], q=eng._vgg_mx_w[0], scale=eng._vgg_mx_w[1]), a.reps)
-    mx, acts = eng.vgg_mxfp8_acts(B), eng._acts(B)["acts"]
+    lo, hi = eng._mx_range
+    tw = timed(eng._quantize_filters, a.reps)
+    mx, acts = eng.mxfp8_acts(B), eng._acts(B)["acts"]
     qn = sorted(quant)[0]
     tq = timed(lambda: ops.quantize_mx_fp8(acts[qn + 1], q=mx[qn][0], scale=mx[qn][1]), a.reps)
     print("filter quantisation (one ssd_quantize_mx_fp8 over %d elements, every fp8 forward): %.1f us" % (hi - lo, tw))
