@@ -935,6 +935,80 @@ int ssd_dev_mfma_calibration_workgroups(void);
 double ssd_dev_mfma_calibration_flops(int iters);
 int ssd_dev_mfma_calibration(int iters, void* stamps, void* sink, void* stream);
 
+/* ---- JPEG: entropy decode on the host, reconstruction on the device (csrc/jpeg_host.h, csrc/jpeg.hip) --------------------------
+ * What the reference's reader does with skimage.io.imread (data_loaders/coco/make_dataset.py:112-117), split in two: the Huffman
+ * stage stays on host threads, everything arithmetic runs on the device and lands in the uint8 arena that
+ * ssd_image_resize_prep and ssd_augment_image (source kind 0) read.  The result equals libjpeg's default decode (integer
+ * "islow" IDCT, "fancy" chroma upsampling, 16-bit fixed-point colour) bit for bit.
+ *
+ * Streams served: baseline sequential DCT (SOF0), 8-bit samples, Huffman; one component (any sampling factors: a single
+ * component is never interleaved), or three YCbCr components with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; 8-bit
+ * quantisation tables; DHT / DQT anywhere before the scan; DRI and RSTn; one interleaved scan; fill bytes, FF 00 stuffing,
+ * APPn and COM skipped.
+ * SSD_ERR_UNSUPPORTED, nothing written: any other SOFn (extended, progressive, lossless, arithmetic) or DAC, sample precision
+ *   other than 8, 2 or 4 components, other sampling factors, 16-bit quantisation tables, a scan that does not hold all
+ *   components in frame order (multi-scan), three components marked RGB (Adobe transform 0, or ids 'R','G','B' without JFIF),
+ *   more than 2^31 - 1 coefficients.
+ * SSD_ERR_VALUE: no SOI; a segment length past the end or too short for its contents; zero width or height; a table id out of
+ *   range, a missing table, an over-subscribed Huffman table; a Huffman code not in its table; a DC category above 15; a
+ *   coefficient index past 63; entropy data that ends early; a missing or wrong restart marker; no EOI behind the scan.
+ * SSD_ERR_WORKSPACE: capacity smaller than the coefficient count (ssd_jpeg_entropy_decode); nothing written.
+ * Every read is checked against n, every write against capacity.
+ *
+ * The image record: SSD_JPEG_REC_WORDS int32 words, the same for the host header and for the device descriptor.  (Words, not
+ * a struct: the record crosses host -> pinned -> device as one int32 array of B records.) */
+#define SSD_JPEG_WIDTH 0
+#define SSD_JPEG_HEIGHT 1
+#define SSD_JPEG_NCOMP 2      /* 1 or 3 */
+#define SSD_JPEG_KIND 3       /* SSD_JPEG_GREY / _444 / _422 / _420 */
+#define SSD_JPEG_BLOCKS_W 4   /* [3] 8x8 blocks per row of each component's plane, padded to whole MCUs */
+#define SSD_JPEG_BLOCKS_H 7   /* [3] ... per column */
+#define SSD_JPEG_NCOEF 10     /* int16 coefficients of the image: 64 * sum over components of blocks_w * blocks_h */
+#define SSD_JPEG_RESTART 11   /* restart interval in MCUs, 0 = none */
+#define SSD_JPEG_COEF_OFF 12  /* [3] element offset of each component's plane; the host functions write them relative to the
+                                 image's first coefficient, the caller of ssd_jpeg_reconstruct adds the image's base */
+#define SSD_JPEG_QT 16        /* [3][64] the quantisation table of each component, natural (row-major) order */
+#define SSD_JPEG_REC_WORDS 208
+#define SSD_JPEG_GREY 0
+#define SSD_JPEG_444 1
+#define SSD_JPEG_422 2        /* luma 2x1 */
+#define SSD_JPEG_420 3        /* luma 2x2 */
+/* ssd_jpeg_info: HOST only (no HIP call).  Parses up to the scan header and fills rec.
+ * ssd_jpeg_entropy_decode: HOST only, re-entrant (no globals: any number of threads at once).  Writes the image's ncoef
+ *   QUANTISED coefficients: natural order, 64 per block, blocks row-major per component plane, planes at rec[COEF_OFF]; DC
+ *   prediction undone; blocks that pad the planes to whole MCUs included as the stream codes them.  rec may be NULL. */
+int ssd_jpeg_info(const void* data, size_t n, int32_t* rec);
+int ssd_jpeg_entropy_decode(const void* data, size_t n, int16_t* coef, size_t capacity, int32_t* rec);
+/* ssd_jpeg_reconstruct: coefficients -> RGB for a ragged batch, two launches (k_jpeg_idct, k_jpeg_rgb).
+ *   coef        DEVICE int16 [total_coef], 16-byte aligned
+ *   desc        DEVICE int32 [B, SSD_JPEG_REC_WORDS], COEF_OFF absolute (multiples of 64)
+ *   dst         DEVICE uint8 [dst_bytes]; image b is written as H*W*3 bytes of interleaved RGB at dst_off[b] (DEVICE int64
+ *               [B]), nothing else.  Grey streams write Y three times (the reference stacks grey images, :129-130)
+ *   scratch     DEVICE, >= ssd_jpeg_reconstruct_workspace_bytes(total_coef) bytes (SSD_ERR_WORKSPACE otherwise), 16-byte
+ *               aligned, no initial contents needed: the sample planes, one byte per coefficient at the coefficient's offset
+ * A record whose planes do not lie inside total_coef, whose grids do not cover W x H for its kind, or whose destination does not
+ * lie inside dst_bytes writes nothing (the kernels check; desc lives on the device).  SSD_ERR_VALUE before any launch: a NULL or
+ * misaligned pointer, B <= 0, total_coef <= 0 or not a multiple of 64, dst_bytes <= 0.
+ * Arithmetic, all integer, >> arithmetic, DS(x, n) = (x + (1 << (n-1))) >> n:
+ *   d = coef * q (int32, wrapping).  IDCT: Loeffler-Ligtenberg-Moschytz with 13-bit constants, columns first with DS(., 11), then
+ *   rows with DS(., 18), + 128, clamp to [0, 255].  One pass over d0..d7:
+ *     z1=(d2+d6)*4433; t2=z1-d6*15137; t3=z1+d2*6270; t0=(d0+d4)<<13; t1=(d0-d4)<<13
+ *     t10=t0+t3; t13=t0-t3; t11=t1+t2; t12=t1-t2;  o0=d7; o1=d5; o2=d3; o3=d1
+ *     z1=o0+o3; z2=o1+o2; z3=o0+o2; z4=o1+o3; z5=(z3+z4)*9633
+ *     o0*=2446; o1*=16819; o2*=25172; o3*=12299; z1*=-7373; z2*=-20995; z3=z3*-16069+z5; z4=z4*-3196+z5
+ *     o0+=z1+z3; o1+=z2+z4; o2+=z2+z3; o3+=z1+z4
+ *     out0..7 = DS of (t10+o3, t11+o2, t12+o1, t13+o0, t13-o0, t12-o1, t11-o2, t10-o3)
+ *   Chroma of 2x1 / 2x2 streams: the plane cropped to cw = ceil(W/2) columns (2x2: and ceil(H/2) rows), edges replicated, then
+ *     2x1: out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2, first and last column p itself
+ *     2x2: r[i] = 3 p[j][i] + p[j-1][i] for row 2j, 3 p[j][i] + p[j+1][i] for row 2j+1; out[2i] = (3 r[i] + r[i-1] + 8) >> 4,
+ *          out[2i+1] = (3 r[i] + r[i+1] + 7) >> 4, first column (4 r[0] + 8) >> 4, last column (4 r[cw-1] + 7) >> 4
+ *     cw <= 2: plain replication (libjpeg takes its triangle filter only for planes wider than two samples)
+ *   Colour, cb and cr minus 128, F(x) = int(x * 65536 + 0.5):  R = Y + ((F(1.402) cr + 32768) >> 16),
+ *     G = Y + ((-F(0.34414) cb - F(0.71414) cr + 32768) >> 16),  B = Y + ((F(1.772) cb + 32768) >> 16), each clamped. */
+size_t ssd_jpeg_reconstruct_workspace_bytes(long long total_coef);
+int ssd_jpeg_reconstruct(const int16_t* coef, const int32_t* desc, int B, uint8_t* dst, const int64_t* dst_off,
+                         long long dst_bytes, void* scratch, size_t scratch_bytes, long long total_coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

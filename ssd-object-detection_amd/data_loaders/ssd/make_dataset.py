@@ -15,12 +15,14 @@ The model consumes only this contract.  Sources:
                        ssd_box_prep) when SSDObjectDetectionModel.get_train_set batches such samples (which is what
                        train() does); iterated directly, such a split yields the decoded samples (RawSplit), not resized
                        images: there is no host-side resize in this package.
-  dataset="coco":      needs pycocotools + scikit-image + the COCO files (none of which exist in this image);
-                       the annotation/IO layer itself is outside this build's scope: wrap a
-                       COCO reader of your own as dataset=<reader>.
+  dataset="coco":      data_loaders.coco.COCODataLoader on dataset_root (annotations read with `json`, no pycocotools or
+                       scikit-image), through the same seam.  decode="device" (the default): the samples carry the files'
+                       bytes (ops.EncodedImage) and the model decodes whole batches, Huffman on host threads and the rest on
+                       the device; decode="host": Pillow decodes each file as it is read.
 Any other name raises ValueError, as the reference does (:33)."""
 import numpy as np
 
+from ... import ops
 from ..synthetic import synth_gt, synth_image
 
 COCO_CLASS_COUNT = 80
@@ -55,31 +57,47 @@ class _SyntheticSplit:
 
 class RawSplit:
     """One split of a reader-contract source, marked for device-side preprocessing: samples are (image uint8 [H,W,3],
-    cls f32 [n], box f32 [n,4] = COCO [x, y, w, h] top-left pixels) -- what SSDObjectDetectionModel.make_batch_raw takes."""
+    cls f32 [n], box f32 [n,4] = COCO [x, y, w, h] top-left pixels) -- what SSDObjectDetectionModel.make_batch_raw takes.  An
+    image that is still encoded (ops.EncodedImage) passes through untouched."""
     raw = True
 
     def __init__(self, source, limit=0):
         self._source, self._limit = source, int(limit)
+        if hasattr(source, "lazy"):                                      # a source of thunks stays one: only the samples a
+            self.lazy = self._lazy                                       # consumer calls for are read
 
-    def __iter__(self):
-        for i, sample in enumerate(self._source):
-            if self._limit and i >= self._limit:
-                break
-            image, cls, box = sample[:3]                                 # a fourth element (crowd flags) passes through
+    @staticmethod
+    def _convert(sample):
+        image, cls, box = sample[:3]                                     # a fourth element (crowd flags) passes through
+        if not isinstance(image, ops.EncodedImage):
             image = np.asarray(image)
             if image.ndim == 2:                                          # grey image: reference coco/make_dataset.py:129-130
                 image = np.stack([image, image, image], axis=2)
             if image.dtype != np.uint8:                                  # imread / 255 (reference :117): exact inverse
                 image = np.rint(np.asarray(image, np.float64) * 255.0).astype(np.uint8)
-            box = np.asarray(box, np.float32).reshape(-1, 4).copy()
-            box[:, :2] -= box[:, 2:] / np.float32(2.0)                   # centre (reference :132) back to top-left
-            yield (np.ascontiguousarray(image[..., :3]), np.asarray(cls, np.float32), box) + tuple(sample[3:4])
+            image = np.ascontiguousarray(image[..., :3])
+        box = np.asarray(box, np.float32).reshape(-1, 4).copy()
+        box[:, :2] -= box[:, 2:] / np.float32(2.0)                       # centre (reference :132) back to top-left
+        return (image, np.asarray(cls, np.float32), box) + tuple(sample[3:4])
+
+    def _lazy(self):
+        for i, thunk in enumerate(self._source.lazy()):
+            if self._limit and i >= self._limit:
+                break
+            yield lambda thunk=thunk: self._convert(thunk())
+
+    def __iter__(self):
+        for i, sample in enumerate(self._source):
+            if self._limit and i >= self._limit:
+                break
+            yield self._convert(sample)
 
 
 class SSDDataLoader:
-    def __init__(self, dataset_root, dataset="coco", shuffle=True, mini_batch=0, input_size=300):
+    def __init__(self, dataset_root, dataset="coco", shuffle=True, mini_batch=0, input_size=300, decode="device"):
         """input_size: the network's input (300: the reference's; 512 or 256 for the ResNet-50 SSD512 network).  The synthetic
-        splits produce images of that size; reader-contract splits are resized on the device to the model's own input."""
+        splits produce images of that size; reader-contract splits are resized on the device to the model's own input.
+        decode: dataset="coco" only -- "device" or "host" (COCODataLoader's)."""
         if isinstance(input_size, bool) or not isinstance(input_size, (int, np.integer)) or input_size < 1:
             raise ValueError("input_size must be a positive integer, not %r" % (input_size,))
         self._train_resize = (int(input_size), int(input_size))
@@ -103,13 +121,11 @@ class SSDDataLoader:
             rng = np.random.default_rng(0)
             self._colors = [rng.integers(80, 240, 3).tolist() for _ in range(COCO_CLASS_COUNT)]
         elif name == "coco":
-            try:
-                import pycocotools.coco  # noqa: F401
-                import skimage.io  # noqa: F401
-            except ImportError as e:
-                raise ImportError("dataset='coco' needs pycocotools and scikit-image plus the COCO files under %r; "
-                                  "use dataset='synthetic' here" % (dataset_root,)) from e
-            raise NotImplementedError("COCO annotation/IO layer is out of scope of this build (SURVEY.md section 2a)")
+            from ..coco import COCODataLoader
+            reader = COCODataLoader(dataset_root, shuffle=shuffle, mini_batch=mini_batch, decode=decode)
+            train, val = reader.get_dataset()                            # mini_batch is the reader's, on both splits (:108)
+            self._train_set, self._val_set = RawSplit(train, 0), RawSplit(val, 0)
+            self._names, self._colors = reader.get_names_and_colors()
         else:
             raise ValueError
 

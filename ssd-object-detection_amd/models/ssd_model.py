@@ -201,8 +201,11 @@ class SSDObjectDetectionModel:
                     if pos == batch_size:
                         imgs, clss, boxes = [], [], []
                         for t in mine:
-                            image, cls, box = t()
-                            imgs.append(np.asarray(image) if raw else np.asarray(image, np.float32))
+                            image, cls, box = t()[:3]                  # (a reader's crowd flags are the metric's business)
+                            if raw:
+                                imgs.append(image if isinstance(image, ops.EncodedImage) else np.asarray(image))
+                            else:
+                                imgs.append(np.asarray(image, np.float32))
                             clss.append(np.asarray(cls, np.float32))
                             boxes.append(np.asarray(box, np.float32))
                         make = model.make_batch_raw if raw else model.make_batch
@@ -262,24 +265,39 @@ class SSDObjectDetectionModel:
         cls, loc, mask = ops.match_encode(box, cls_, off, total, max_nt, self._pset, self.cfg.thresh)
         return x, (cls, loc, mask)
 
+    decode_workers = 8                     # host threads of the JPEG entropy decode (ops.image_arena); never sized from the machine
+    decode_fallback = "pil"                # streams the device decoder refuses: Pillow on the host, or None to refuse them too
+
+    def _raw_arena(self, images, upload):
+        """The ragged uint8 arena (flat u8, off i64 [B], hw i32 [B,2], all on the device) of a batch of reader-contract
+        images: decoded uint8 arrays [H,W,3], images still encoded as JPEG (ops.EncodedImage), or a mix.  Decoded arrays
+        alone are concatenated on the host and sent with `upload` (host array -> device tensor), three transfers; as soon as
+        one image is encoded the batch goes through ops.image_arena: entropy decode on host threads, one transfer, the
+        reconstruction kernels."""
+        if any(isinstance(im, ops.EncodedImage) for im in images):
+            flat, off, hw, self.last_decode_stats = ops.image_arena(list(images), self.device, self.decode_workers,
+                                                                    self.decode_fallback)
+            return flat, off, hw
+        hw = np.array([im.shape[:2] for im in images], np.int32)
+        sizes = [int(im.size) for im in images]
+        off = np.zeros(len(sizes), np.int64)
+        off[1:] = np.cumsum(sizes[:-1])
+        flat = np.concatenate([np.ascontiguousarray(im, np.uint8).reshape(-1) for im in images])
+        hw_d = upload(hw)
+        return upload(flat), upload(off), hw_d
+
     def make_batch_raw(self, images_u8, cls_list, box_tlwh_list, augment=None):
-        """The same from what the COCO reader yields before any preprocessing: decoded uint8 RGB images
-        of arbitrary sizes and COCO [x, y, w, h] pixel boxes.  '/255', cv2.resize to the network size, '(x-0.5)*2'
+        """The same from what the COCO reader yields before any preprocessing: uint8 RGB images of
+        arbitrary sizes -- decoded arrays, ops.EncodedImage (JPEG bytes, decoded on the way: _raw_arena) or a mix -- and COCO
+        [x, y, w, h] pixel boxes.  '/255', cv2.resize to the network size, '(x-0.5)*2'
         (reference data_loaders/coco/make_dataset.py:117, data_loaders/ssd/make_dataset.py:40-44, models/ssd_model.py:214)
         and the box conversion run on the device; returns the prepared bf16 network input instead of the f32 image.
         augment (ops.AugmentSpec): SSD data augmentation on the device as well (include/ssd_hip.h)."""
-        hw = np.array([im.shape[:2] for im in images_u8], np.int32)
-        sizes = [int(im.size) for im in images_u8]
-        off = np.zeros(len(sizes), np.int64)
-        off[1:] = np.cumsum(sizes[:-1])
-        flat = np.concatenate([np.ascontiguousarray(im, np.uint8).reshape(-1) for im in images_u8])
         dev = self.device
-        hw_d = torch.from_numpy(hw).to(dev)
+        flat_d, off_d, hw_d = self._raw_arena(images_u8, lambda a: torch.from_numpy(a).to(dev))
         if augment is not None:
-            return self._augmented(torch.from_numpy(flat).to(dev), 0, torch.from_numpy(off).to(dev), hw_d, box_tlwh_list,
-                                   cls_list, augment, tlwh=True)
-        x = ops.image_resize_prep(torch.from_numpy(flat).to(dev), torch.from_numpy(off).to(dev), hw_d,
-                                  int(self.cfg.input_shape[0]), True)
+            return self._augmented(flat_d, 0, off_d, hw_d, box_tlwh_list, cls_list, augment, tlwh=True)
+        x = ops.image_resize_prep(flat_d, off_d, hw_d, int(self.cfg.input_shape[0]), True)
         gt_box, gt_cls, gt_off, total, max_nt = ops.pack_gt(box_tlwh_list, cls_list, device=dev)
         gt_box = ops.box_prep(gt_box, gt_off, hw_d) if total else gt_box
         cls, loc, mask = ops.match_encode(gt_box, gt_cls, gt_off, total, max_nt, self._pset, self.cfg.thresh)
@@ -638,14 +656,9 @@ class SSDObjectDetectionModel:
         """Reader-contract samples (decoded uint8 images of any size, COCO top-left pixel boxes: RawSplit) -> the prepared
         network input and the relative centre-form boxes, by the device preprocessing of make_batch_raw (no augmentation).
         Returns (x bf16 [B,S,S,8], box f32 [total,4] device, counts)."""
-        imgs = [np.ascontiguousarray(b[0], np.uint8) for b in buf]
-        hw = np.array([im.shape[:2] for im in imgs], np.int32)
-        sizes = [int(im.size) for im in imgs]
-        off = np.zeros(len(sizes), np.int64)
-        off[1:] = np.cumsum(sizes[:-1])
-        hw_d = self._to_device(hw)
-        x = ops.image_resize_prep(self._to_device(np.concatenate([im.reshape(-1) for im in imgs])), self._to_device(off), hw_d,
-                                  int(self.cfg.input_shape[0]), True)
+        imgs = [b[0] if isinstance(b[0], ops.EncodedImage) else np.ascontiguousarray(b[0], np.uint8) for b in buf]
+        flat_d, off_d, hw_d = self._raw_arena(imgs, self._to_device)
+        x = ops.image_resize_prep(flat_d, off_d, hw_d, int(self.cfg.input_shape[0]), True)
         counts = [int(np.shape(b[2])[0]) for b in buf]
         gt_off = np.zeros(len(buf) + 1, np.int32)
         gt_off[1:] = np.cumsum(counts)

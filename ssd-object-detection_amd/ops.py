@@ -1349,6 +1349,223 @@ def augment_image(src, src_kind, src_off, src_hw, params, S=300, normalize=True,
     return out
 
 
+# ---- JPEG: Huffman on host threads, everything arithmetic on the device (include/ssd_hip.h) ------------------------------------
+JPEG_REC_WORDS = _lib.CONSTANTS["SSD_JPEG_REC_WORDS"]
+JPEG_KINDS = ("grey", "4:4:4", "4:2:2", "4:2:0")                   # SSD_JPEG_GREY .. SSD_JPEG_420
+JpegStats = collections.namedtuple("JpegStats", "images device fallback")
+_JPEG_UNSUPPORTED = ("not a stream the device decoder serves (baseline 8-bit Huffman, one scan, grey or YCbCr 4:4:4 / 4:2:2 / "
+                     "4:2:0 only; progressive, arithmetic, 12-bit, lossless, CMYK, RGB-marked and multi-scan streams are refused)")
+
+
+class EncodedImage:
+    """An image still encoded as JPEG: what COCODataLoader(decode="device") yields in place of the decoded array.  `shape` is
+    (H, W, 3) from the frame header, so code that only asks for a sample's size works on it unchanged."""
+    __slots__ = ("data", "height", "width")
+
+    def __init__(self, data, height, width):
+        self.data, self.height, self.width = bytes(data), int(height), int(width)
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 3)
+
+    def __repr__(self):
+        return "EncodedImage(%d bytes, %dx%d)" % (len(self.data), self.width, self.height)
+
+
+def _jpeg_record(rec):
+    g = _lib.CONSTANTS
+    nc = int(rec[g["SSD_JPEG_NCOMP"]])
+    return dict(width=int(rec[g["SSD_JPEG_WIDTH"]]), height=int(rec[g["SSD_JPEG_HEIGHT"]]), ncomp=nc,
+                kind=int(rec[g["SSD_JPEG_KIND"]]), blocks_w=rec[g["SSD_JPEG_BLOCKS_W"]:][:nc].tolist(),
+                blocks_h=rec[g["SSD_JPEG_BLOCKS_H"]:][:nc].tolist(), ncoef=int(rec[g["SSD_JPEG_NCOEF"]]),
+                restart=int(rec[g["SSD_JPEG_RESTART"]]), coef_off=rec[g["SSD_JPEG_COEF_OFF"]:][:nc].tolist(),
+                qt=rec[g["SSD_JPEG_QT"]:][:64 * nc].reshape(nc, 64).copy(), rec=rec)
+
+
+def jpeg_info(data):
+    """ssd_jpeg_info (host only): the frame of a JPEG byte string as a dict -- width, height, ncomp, kind (index into
+    JPEG_KINDS), blocks_w / blocks_h per component (padded to whole MCUs), ncoef, restart, coef_off, qt int32 [ncomp, 64] in
+    natural order, rec (the int32 record).  NotImplementedError for a stream the decoder does not serve, ValueError for a
+    corrupt one."""
+    data = bytes(data)
+    rec = np.zeros(JPEG_REC_WORDS, np.int32)
+    _lib.check(_lib.lib().ssd_jpeg_info(data, len(data), rec.ctypes.data), unsupported=_JPEG_UNSUPPORTED)
+    return _jpeg_record(rec)
+
+
+def jpeg_entropy_decode(data, capacity=None):
+    """ssd_jpeg_entropy_decode (host only, no HIP call): (coef int16 [ncoef], header dict as jpeg_info).  capacity: the size
+    of the buffer offered, in coefficients (default: what jpeg_info asks for); too small raises RuntimeError (SSD_ERR_WORKSPACE)."""
+    data = bytes(data)
+    need = jpeg_info(data)["ncoef"] if capacity is None else int(capacity)
+    coef = np.empty(max(need, 1), np.int16)
+    rec = np.zeros(JPEG_REC_WORDS, np.int32)
+    _lib.check(_lib.lib().ssd_jpeg_entropy_decode(data, len(data), coef.ctypes.data, need, rec.ctypes.data),
+               unsupported=_JPEG_UNSUPPORTED)
+    h = _jpeg_record(rec)
+    return coef[:h["ncoef"]], h
+
+
+def jpeg_reconstruct(coef, desc, dst, dst_off, scratch=None):
+    """ssd_jpeg_reconstruct: coef int16 [total] and desc int32 [B, JPEG_REC_WORDS] (absolute coefficient offsets) on the device
+    -> H*W*3 bytes of RGB per image at dst_off[b] (int64 [B]) of the uint8 buffer dst; nothing else is written.  scratch: uint8
+    [>= total] or None.  Returns dst."""
+    L = _lib.lib()
+    _dev(coef, torch.int16); _dev(desc, torch.int32); _dev(dst, torch.uint8); _dev(dst_off, torch.int64)
+    B, total = desc.shape[0], coef.numel()
+    assert desc.shape == (B, JPEG_REC_WORDS) and dst_off.shape == (B,)
+    need = L.ssd_jpeg_reconstruct_workspace_bytes(total)
+    if scratch is None:
+        scratch = torch.empty((max(need, 1),), dtype=torch.uint8, device=coef.device)
+    _dev(scratch, torch.uint8)
+    _lib.check(L.ssd_jpeg_reconstruct(_ptr(coef), _ptr(desc), B, _ptr(dst), _ptr(dst_off), dst.numel(), _ptr(scratch),
+                                      scratch.numel(), total, _stream()))
+    return dst
+
+
+_JPEG_STAGE = {}                   # device -> [pinned uint8 buffer, event behind the last copy out of it]
+_JPEG_POOLS = {}                   # workers -> ThreadPoolExecutor
+
+
+def _jpeg_pool(workers):
+    workers = int(workers)
+    if workers < 1:
+        raise ValueError("workers must be >= 1, not %r" % (workers,))
+    if workers not in _JPEG_POOLS:
+        import concurrent.futures
+        _JPEG_POOLS[workers] = concurrent.futures.ThreadPoolExecutor(workers, thread_name_prefix="ssd-jpeg")
+    return _JPEG_POOLS[workers]
+
+
+def _jpeg_stage(device, nbytes):
+    """The reused pinned staging buffer of a device, at least nbytes long and no longer read by an earlier copy."""
+    slot = _JPEG_STAGE.get(device)
+    if slot is not None and slot[1] is not None:
+        slot[1].synchronize()
+    if slot is None or slot[0].numel() < nbytes:
+        slot = [torch.empty((max(int(nbytes) * 5 // 4, 1 << 20),), dtype=torch.uint8).pin_memory(), None]
+        _JPEG_STAGE[device] = slot
+    return slot
+
+
+def _pil_decode(data):
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), np.uint8))
+
+
+def image_arena(items, device, workers=8, fallback="pil"):
+    """The ragged uint8 arena of ssd_image_resize_prep / ssd_augment_image (source kind 0) from a batch of images that are
+    JPEG byte strings (or EncodedImage), decoded uint8 arrays [H,W,3], or a mix.  Encoded images are entropy-decoded on a pool
+    of `workers` host threads (the C function releases the GIL) straight into one reused pinned buffer, copied with one
+    non-blocking transfer and reconstructed by one ssd_jpeg_reconstruct call on the current stream.  Returns
+    (arena u8 [sum H*W*3], off i64 [B], hw i32 [B,2], JpegStats).  See decode_jpeg_batch for refusals."""
+    L = _lib.lib()
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    B = len(items)
+    if B == 0:
+        raise ValueError("an empty batch")
+    if fallback not in ("pil", None):
+        raise ValueError("fallback must be 'pil' or None, not %r" % (fallback,))
+    g = _lib.CONSTANTS
+    host = {}                                              # index -> decoded array that is copied into its slot
+    enc = []                                               # (index, bytes, record)
+    hw = np.zeros((B, 2), np.int32)
+    for i, item in enumerate(items):
+        if isinstance(item, np.ndarray):
+            if item.dtype != np.uint8 or item.ndim != 3 or item.shape[2] != 3:
+                raise ValueError("sample %d: a decoded image must be uint8 [H,W,3], not %s %s" % (i, item.dtype, item.shape))
+            host[i] = np.ascontiguousarray(item)
+            hw[i] = item.shape[:2]
+            continue
+        data = item.data if isinstance(item, EncodedImage) else bytes(item)
+        rec = np.zeros(JPEG_REC_WORDS, np.int32)
+        rc = L.ssd_jpeg_info(data, len(data), rec.ctypes.data)
+        if rc == _lib.SSD_ERR_UNSUPPORTED:
+            if fallback is None:
+                raise NotImplementedError("sample %d: %s" % (i, _JPEG_UNSUPPORTED))
+            try:
+                host[i] = _pil_decode(data)
+            except ImportError:
+                raise NotImplementedError("sample %d: %s, and Pillow is not installed to decode it on the host"
+                                          % (i, _JPEG_UNSUPPORTED)) from None
+            hw[i] = host[i].shape[:2]
+            continue
+        if rc != _lib.SSD_OK:
+            raise ValueError("sample %d: corrupt JPEG stream (%s)" % (i, L.ssd_status_string(rc).decode()))
+        enc.append((i, data, rec))
+        hw[i] = (rec[g["SSD_JPEG_HEIGHT"]], rec[g["SSD_JPEG_WIDTH"]])
+    n_fallback = sum(1 for i in host if not isinstance(items[i], np.ndarray))
+    sizes = hw[:, 0].astype(np.int64) * hw[:, 1].astype(np.int64) * 3
+    off = np.zeros(B, np.int64)
+    off[1:] = np.cumsum(sizes[:-1])
+    total_bytes = int(sizes.sum())
+    E = len(enc)
+    base = np.zeros(E + 1, np.int64)
+    base[1:] = np.cumsum([int(r[g["SSD_JPEG_NCOEF"]]) for _, _, r in enc])
+    total_coef = int(base[E])
+    if total_coef > 0x7fffffff:
+        raise ValueError("the batch holds %d coefficients: more than one reconstruct call addresses" % total_coef)
+    # staging layout (bytes): coef int16 [total_coef] | desc int32 [E, REC] | dst_off int64 [E] | off int64 [B] | hw int32 [B,2]
+    o_desc = (2 * total_coef + 15) // 16 * 16
+    o_dst = o_desc + 4 * JPEG_REC_WORDS * E
+    o_off = o_dst + 8 * E
+    o_hw = o_off + 8 * B
+    nbytes = o_hw + 8 * B
+    slot = _jpeg_stage(device, nbytes)
+    stage = slot[0]
+    view = stage.numpy()
+    desc_h = view[o_desc:o_dst].view(np.int32).reshape(E, JPEG_REC_WORDS)
+    view[o_dst:o_off].view(np.int64)[:] = off[[i for i, _, _ in enc]] if E else 0
+    view[o_off:o_hw].view(np.int64)[:] = off
+    view[o_hw:nbytes].view(np.int32)[:] = hw.reshape(-1)
+    p0 = stage.data_ptr()
+
+    def work(k):
+        i, data, _ = enc[k]
+        return L.ssd_jpeg_entropy_decode(data, len(data), p0 + 2 * int(base[k]), int(base[k + 1] - base[k]),
+                                         p0 + o_desc + 4 * JPEG_REC_WORDS * k)
+
+    if E:
+        codes = list(_jpeg_pool(workers).map(work, range(E))) if workers > 1 and E > 1 else [work(k) for k in range(E)]
+        for k, rc in enumerate(codes):
+            if rc != _lib.SSD_OK:
+                raise ValueError("sample %d: corrupt JPEG stream (%s)" % (enc[k][0], L.ssd_status_string(rc).decode()))
+        c0 = g["SSD_JPEG_COEF_OFF"]
+        desc_h[:, c0:c0 + 3] += base[:E, None].astype(np.int32)
+    dev_buf = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    dev_buf.copy_(stage[:nbytes], non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record()
+    arena = torch.empty((total_bytes,), dtype=torch.uint8, device=device)
+    if E:
+        jpeg_reconstruct(dev_buf[:2 * total_coef].view(torch.int16), dev_buf[o_desc:o_dst].view(torch.int32).view(E, JPEG_REC_WORDS),
+                         arena, dev_buf[o_dst:o_off].view(torch.int64))
+    for i, image in host.items():
+        flat = image.reshape(-1) if image.flags.writeable else image.reshape(-1).copy()     # (from_numpy wants a writable array)
+        arena[int(off[i]):int(off[i] + sizes[i])].copy_(torch.from_numpy(flat), non_blocking=False)
+    return (arena, dev_buf[o_off:o_hw].view(torch.int64), dev_buf[o_hw:nbytes].view(torch.int32).view(B, 2),
+            JpegStats(images=B, device=E, fallback=n_fallback))
+
+
+def decode_jpeg_batch(encoded, device, workers=8, fallback="pil"):
+    """A batch of JPEG byte strings -> (arena u8, off i64 [B], hw i32 [B,2] (h, w), JpegStats(images, device, fallback)): the
+    decoded RGB images back to back on `device`, as image_resize_prep and augment_image (source kind 0) take them.  Huffman
+    decoding runs on `workers` host threads; dequantisation, IDCT, chroma upsampling and colour conversion on the device.  The
+    pixels equal libjpeg's default decode (what Pillow returns) bit for bit.
+    A stream the library refuses as unsupported is decoded by Pillow on the host and copied into its slot (stats.fallback counts
+    them); with fallback=None, or without Pillow, it raises NotImplementedError.  A corrupt stream raises ValueError.  Both name
+    the sample."""
+    for i, e in enumerate(encoded):
+        if not isinstance(e, (bytes, bytearray, memoryview, EncodedImage)):
+            raise ValueError("sample %d: expected JPEG bytes, not %s" % (i, type(e).__name__))
+    return image_arena(list(encoded), device, workers, fallback)
+
+
 def maxpool2x2_fwd(x, same=False, out=None):
     L = _lib.lib()
     _bf(x)

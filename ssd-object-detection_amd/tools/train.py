@@ -183,6 +183,21 @@ def clip_from_config(config):
     return clip
 
 
+def decode_from_config(config):
+    """`data: decode` ("device" | "host") and `data: decode_workers` (host threads of the JPEG entropy decode) -> (decode,
+    workers); both optional, absent = ("device", 8).  Read only for `dataset: "coco"`: any other dataset gets the defaults
+    whatever the keys say.  ValueError for an unknown mode or a worker count that is not a positive integer."""
+    data = config.get("data") or {}
+    if not (isinstance(data.get("dataset"), str) and data["dataset"].lower() == "coco"):
+        return "device", 8
+    decode, workers = data.get("decode", "device"), data.get("decode_workers", 8)
+    if decode not in ("device", "host"):
+        raise ValueError("data.decode must be 'device' or 'host', not %r" % (decode,))
+    if isinstance(workers, bool) or not isinstance(workers, int) or workers < 1:
+        raise ValueError("data.decode_workers must be a positive integer, not %r" % (workers,))
+    return decode, workers
+
+
 OPTIMIZER_KEYS = {"Adam": {"name", "beta_1", "beta_2", "epsilon"},
                   "SGD": {"name", "momentum", "nesterov", "weight_decay", "decay_bias"}}
 
@@ -233,11 +248,17 @@ def train(config):
     data_cfg, model_cfg = config["data"], config["model"]
     subset = data_cfg["mini_batch"]
     network = network_from_config(config)
+    decode, decode_workers = decode_from_config(config)
     data = SSDDataLoader(dataset_root=data_cfg["dataset_root"], dataset=data_cfg["dataset"], shuffle=data_cfg["shuffle"],
                          mini_batch=subset["num_data"] if subset["enable"] else 0,
-                         input_size=network.in_size if network is not None else 300)
+                         input_size=network.in_size if network is not None else 300, decode=decode)
+    if isinstance(data_cfg["dataset"], str) and data_cfg["dataset"].lower() == "coco":
+        n_cat = len(data.get_names_and_colors()[0])
+        if n_cat != data_cfg["num_classes"]:
+            raise ValueError("data.num_classes is %r but the annotation files list %d categories" % (data_cfg["num_classes"], n_cat))
     model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1,
                                     l2norm=l2norm_from_config(config), network=network)
+    model.decode_workers = decode_workers
 
     lr, wlr = model_cfg["train"]["lr"], model_cfg["warmup"]["lr"]
     optimizer = _make_optimizer(model_cfg["train"]["optimizer"], schedule_from_config(lr))
