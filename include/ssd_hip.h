@@ -630,6 +630,33 @@ int ssd_add_relu_fwd_mxfp8(const void* a, const void* b, void* out_bf16, void* q
 int ssd_conv2d_fwd_pool_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias,
                               void* y_pool_bf16, void* y_pool8, void* y_pool_scale, int B, int H, int W, int Cin, int Cout, int k,
                               int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, int Hp, int Wp, void* stream);
+/* The VGG-16 SSD300's inference fp8 forward (engine.py, fp8_inference=True; no reference counterpart): the dilated fc6 on
+ * block-scaled fp8 operands, and the two poolings no fp8 convolution can run inside its own launch -- pool4 behind conv4_3,
+ * whose full-resolution map a head reads, and the 3x3 / stride-1 pool5 -- as poolings that quantise what they store.
+ *   ssd_conv2d_atrous_fwd_mxfp8  relu?(Conv2D(3, dilation_rate = dilation, padding = "same") of x with w + bias): ssd_conv2d_atrous_fwd
+ *                           on the operands of ssd_conv2d_fwd_mxfp8 (x8 / xscale, w8 [Cout][3][3][Cin] / wscale), fp32 accumulation,
+ *                           ONE bf16 rounding; outputs as ssd_conv2d_fwd_mxfp8: any non-empty subset of y_bf16 [B,H,W,Cout] and the
+ *                           pair y8 / yscale = ssd_quantize_mx_fp8 of that bf16 map, bit for bit.  Any dilation >= 1, stride 1.
+ *                           ssd_conv2d_fwd_mxfp8's main loop with the tap offset times the dilation; taps that lie outside the
+ *                           map for every pixel (dilation >= H: a row of taps, >= W: a column) are not issued, which changes no
+ *                           bit.  At dilation 1 it equals ssd_conv2d_fwd_mxfp8(k = 3, stride 1, pads 1, 1) bit for bit.
+ *                           SSD_ERR_VALUE: a missing operand, no output, y8 without yscale (or the reverse), bad dimensions,
+ *                           dilation < 1; SSD_ERR_UNSUPPORTED: Cin % 128, Cout % 8, Cout % 32 with y8, an operand or output of
+ *                           2^31 bytes or more.  Either before anything is launched.
+ *   ssd_maxpool2x2_fwd_mxfp8    q u8 [B,Ho,Wo,C] + scale u8 [B,Ho,Wo,C/32] = ssd_quantize_mx_fp8(ssd_maxpool2x2_fwd(x)) bit for bit,
+ *                           in one pass: the maximum over the bf16 values of each window, then the rule of csrc/mxfp8.h on the
+ *                           pooled pixel's 32-channel blocks.  Ho = H / 2 (VALID) or (H + 1) / 2 (TF-SAME, windows clipped), Wo
+ *                           likewise.  y_bf16 (bf16 [B,Ho,Wo,C], may be null): the pooled map itself as well.
+ *   ssd_maxpool3x3s1_fwd_mxfp8  the same for ssd_maxpool3x3s1_fwd's y (3x3 / stride 1 / pad 1), outputs [B,H,W,C] / [B,H,W,C/32].
+ *                           Both: x bf16 [B,H,W,C]; no winner codes (inference only).  SSD_ERR_VALUE: a NULL x, q or scale, a
+ *                           dimension below 1, pooled sizes that are neither VALID nor SAME, overlapping tensors;
+ *                           SSD_ERR_UNSUPPORTED: C % 32, a map of 2^31 elements or more.  Nothing is launched on either. */
+int ssd_conv2d_atrous_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias,
+                                void* y_bf16, void* y8, void* yscale, int B, int H, int W, int Cin, int Cout, int dilation, int relu,
+                                void* stream);
+int ssd_maxpool2x2_fwd_mxfp8(const void* x, void* y_bf16, void* q, void* scale, int B, int H, int W, int C, int Ho, int Wo,
+                             void* stream);
+int ssd_maxpool3x3s1_fwd_mxfp8(const void* x, void* y_bf16, void* q, void* scale, int B, int H, int W, int C, void* stream);
 /* The stride-1 data gradients of the ResNet-50 trunk after a training-mode fp8 forward (resnet_engine.py, mxfp8_bwd_plan):
  *   ssd_conv2d_bwd_data_mxfp8  dx[B,H,W,Cin] = ssd_conv2d_bwd_data's result at stride 1 on block-scaled fp8 operands -- dy8
  *                           [B,Ho,Wo,Cout] / dyscale [B,Ho,Wo,Cout/32] and wt8 [Cin][k][k][Cout] / wtscale [Cin][k][k][Cout/32],

@@ -21,6 +21,9 @@
 // on dy and the transposed filters, an epilogue with ssd_conv2d_bwd_data's accumulate and ReLU mask.
 // Its pooled mode (POOL) serves the SSD300 VGG trunk's fp8 forward (engine.py, precision="mxfp8"): block3_conv3 and the 2x2
 // max pool behind it in one launch that stores the pooled map only -- the same main loop on tiles of 32 whole 2x2 windows.
+// Its dilated mode (ATROUS) serves fc6 of the VGG-16 SSD300's fp8 forward (engine.py, fp8_inference=True): the same main loop
+// with the tap offset times the dilation, over the taps that reach the map.
+#include <algorithm>
 #include "common.h"
 #include <hip/hip_bf16.h>
 #include "conv_common.h"
@@ -208,6 +211,8 @@ struct MxOut {
     int accumulate;                          // DG: y += result before the mask (y then holds the earlier gradient)
     int Mp;                                  // POOL: y / q / qs hold the 2x2 max-pooled map [B,Hp,Wp,N], Mp = B*Hp*Wp pixels
     FastDiv d_phw, d_pw;                     // POOL: divide by Hp*Wp and by Wp
+    unsigned long long taps;                 // ATROUS: the live taps, four bits each (tap = 3 ty + tx), in tap order
+    int ntaps, dil;                          // ATROUS: their count; the dilation (tap t reads row y + (t / 3) dil, pads = dil)
 };
 
 // The general MX-fp8 forward convolution: KS x KS filters (1 or 3), stride g.mul (1 or 2), TF-SAME pads g.pad_t / g.pad_l.  The
@@ -220,7 +225,11 @@ struct MxOut {
 // POOL = the convolution followed by a 2x2 / stride-2 max pool (ssd_conv2d_fwd_pool_mxfp8): a tile is 32 whole pooling windows
 // instead of 128 consecutive pixels, and the epilogue pools the bf16-rounded pixels of each window before its stores.  Every
 // conv pixel still sees the same k-steps in the same order, so it is bitwise the pixel of the plain launch.
-template <int KS, bool DG, bool POOL = false>
+// ATROUS = the dilated 3x3 / stride-1 forward (ssd_conv2d_atrous_fwd_mxfp8): the same main loop with the tap offset times
+// ep.dil and pads of ep.dil, over the live taps only -- a tap that lies outside the map for every pixel (dil >= H for a row
+// of taps, dil >= W for a column) would stage zeros through the out-of-range offset and add +0 to every accumulator, so
+// dropping it changes no bit.  At dil == 1 the steps are the plain launch's.
+template <int KS, bool DG, bool POOL = false, bool ATROUS = false>
 __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restrict__ x, const unsigned char* __restrict__ xs,
                                                     const unsigned char* __restrict__ w, const unsigned char* __restrict__ wsc,
                                                     ConvGeom g, MxOut ep) {
@@ -293,8 +302,9 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
         swrow = n < g.N ? (unsigned)n * (unsigned)KK * (unsigned)cb : 0xffffffffu;
     }
     auto issue = [&](int step, int buf) {
-        const int tap = step / csteps, cs = step - tap * csteps;
-        const int kh = tap / KS, kw = tap % KS;
+        const int slot = step / csteps, cs = step - slot * csteps;
+        const int tap = ATROUS ? (int)((ep.taps >> (4 * slot)) & 15ull) : slot;
+        const int kh = (tap / KS) * (ATROUS ? ep.dil : 1), kw = (tap % KS) * (ATROUS ? ep.dil : 1);
         char* base = smem + buf * F8_BUF;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -326,7 +336,7 @@ __global__ __launch_bounds__(256) void k_conv_mxfp8(const unsigned char* __restr
     for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int p = 0; p < 4; ++p) acc[c][p] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int nsteps = KK * csteps;
+    const int nsteps = (ATROUS ? ep.ntaps : KK) * csteps;
     const int gq = lane >> 4, li = lane & 15;
     issue(0, 0);
     for (int st = 0; st < nsteps; ++st) {
@@ -510,6 +520,7 @@ OnceLds g_f8_once;
 OnceLds g_f8g_once[2];
 OnceLds g_f8d_once[2];
 OnceLds g_f8p_once;
+OnceLds g_f8a_once;
 
 }  // namespace
 
@@ -591,6 +602,36 @@ int ssd_conv2d_fwd_pool_mxfp8(const void* x8, const void* xscale, const void* w8
     if (ensure_lds(g_f8p_once, reinterpret_cast<const void*>(k_conv_mxfp8<3, false, true>), F8_LDS) != 0) return SSD_ERR_LAUNCH;
     const unsigned grid = (unsigned)(((ep.Mp + 31) / 32) * ((Cout + 127) / 128));         // 32 pooling windows per tile
     hipLaunchKernelGGL((k_conv_mxfp8<3, false, true>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream,
+                       static_cast<const unsigned char*>(x8), static_cast<const unsigned char*>(xscale),
+                       static_cast<const unsigned char*>(w8), static_cast<const unsigned char*>(wscale), g, ep);
+    return ssd_launch_status();
+}
+
+int ssd_conv2d_atrous_fwd_mxfp8(const void* x8, const void* xscale, const void* w8, const void* wscale, const float* bias,
+                                void* y_bf16, void* y8, void* yscale, int B, int H, int W, int Cin, int Cout, int dilation, int relu,
+                                void* stream) {
+    if (!x8 || !xscale || !w8 || !wscale) return SSD_ERR_VALUE;
+    if ((!y_bf16 && !y8) || (!y8 != !yscale)) return SSD_ERR_VALUE;             // no output, or q without its scales
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || dilation < 1) return SSD_ERR_VALUE;
+    if (Cin % 128 || Cout % 8 || (y8 && Cout % 32)) return SSD_ERR_UNSUPPORTED;
+    if ((long long)B * H * W * Cin >= (1ll << 31) || (long long)Cout * 9 * Cin >= (1ll << 31) ||
+        (long long)B * H * W * Cout * 2 >= (1ll << 31))
+        return SSD_ERR_UNSUPPORTED;
+    const int dil = std::min(dilation, std::max(H, W));      // beyond the map only the centre tap is live, whatever the dilation
+    const ConvGeom g = make_geom(B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, dil, dil);
+    MxOut ep = {};
+    ep.bias = bias; ep.relu = relu; ep.y = static_cast<bf16_raw*>(y_bf16);
+    ep.q = static_cast<unsigned char*>(y8); ep.qs = static_cast<unsigned char*>(yscale);
+    ep.dil = dil;
+    for (int ty = 0; ty < 3; ++ty)                           // the live taps, as live_taps() of atrous.hip
+        for (int tx = 0; tx < 3; ++tx) {
+            if ((ty != 1 && dil >= H) || (tx != 1 && dil >= W)) continue;
+            ep.taps |= (unsigned long long)(3 * ty + tx) << (4 * ep.ntaps);
+            ++ep.ntaps;
+        }
+    if (ensure_lds(g_f8a_once, reinterpret_cast<const void*>(k_conv_mxfp8<3, false, false, true>), F8_LDS) != 0) return SSD_ERR_LAUNCH;
+    const unsigned grid = (unsigned)(((g.M + 127) / 128) * ((Cout + 127) / 128));
+    hipLaunchKernelGGL((k_conv_mxfp8<3, false, false, true>), dim3(grid), dim3(256), F8_LDS, (hipStream_t)stream,
                        static_cast<const unsigned char*>(x8), static_cast<const unsigned char*>(xscale),
                        static_cast<const unsigned char*>(w8), static_cast<const unsigned char*>(wscale), g, ep);
     return ssd_launch_status();

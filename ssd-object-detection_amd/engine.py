@@ -8,6 +8,7 @@ Activations are NHWC bf16, weights [Cout][k][k][Cin] bf16 (fp32 masters), accumu
 The 3-channel image is carried in 8 zero-padded channels (first-layer weights of channels 3..7 are and stay 0).
 The same engine runs the SSD paper's VGG-16 SSD300 (VGG16_SSD300_TRUNK below: no reference counterpart).
 """
+import collections
 import math
 import os
 
@@ -87,33 +88,45 @@ VGG16_SSD300_NUM_PRIORS = (4, 6, 6, 6, 4, 4)
 def mxfp8_eligible(nd):
     """Whether the block-scaled fp8 kernels serve node `nd` (ops.conv2d_fwd_mxfp8; a planned node or a graph node of
     resnet_engine): a convolution whose input channels are whole MX k-steps (Cin % 128 == 0) and whose output channels are
-    whole MX blocks (Cout % 32 == 0)."""
+    whole MX blocks (Cout % 32 == 0); a dilated one (a planned node's "dilation"; graph nodes carry no such key) only at
+    3x3 / stride 1 (ops.conv2d_atrous_fwd_mxfp8)."""
+    if nd.get("dilation", 1) != 1 and (nd["k"], nd["stride"]) != (3, 1):
+        return False
     return (nd.get("kind", nd.get("op")) == "conv" and nd["cin"] % 128 == 0 and nd["cout"] % 32 == 0 and nd["k"] in (1, 3)
             and nd["stride"] in (1, 2))
 
 
-def mxfp8_vgg_plan(nodes, chain_start):
-    """The inference fp8 forward of a VGG trunk (SSDEngine's planned nodes: node i reads node i - 1; no device needed).
-    Returns (fp8, pooled, quant, writes):
+MxTrunkPlan = collections.namedtuple("MxTrunkPlan", "fp8 pooled qpool quant writes")
+
+
+def mxfp8_trunk_plan(nodes, chain_start):
+    """The inference fp8 forward of an SSDEngine trunk (its planned nodes: node i reads node i - 1; no device needed).
+    Returns MxTrunkPlan(fp8, pooled, qpool, quant, writes):
       fp8     the convolutions that run on block-scaled fp8 operands: one run of them up to the chain (which stays bf16),
               each fed by the epilogue of the layer in front of it;
-      pooled  the pools that run inside the fp8 convolution in front of them (ops.conv2d_fwd_pool_mxfp8: 3x3 / stride 1);
+      pooled  the pools that run inside the fp8 convolution in front of them (ops.conv2d_fwd_pool_mxfp8: 3x3 / stride 1,
+              never a feature map: its head reads the full-resolution map, which that launch does not store);
+      qpool   the other pools of the run: each launches as a quantising pooling (ops.maxpool2x2_fwd_mxfp8 /
+              ops.maxpool3x3s1_fwd_mxfp8) that reads the bf16 map in front of it and stores the pooled map in fp8 -- every
+              3x3 / stride-1 pooling, and a 2x2 one whose convolution is a feature map or otherwise does not pool itself;
       quant   the ONE node whose bf16 output gets a standalone ops.quantize_mx_fp8: the input of the run's first layer;
       writes  {node: frozenset of "bf16" / "fp8"}, the forms of its output the walk stores -- exactly what its consumers read
-              (the heads read bf16), the quantised node's bf16 map besides, nothing for a convolution whose pool runs in
-              its own launch.
+              (the heads and the quantising poolings read bf16), the quantised node's bf16 map besides, nothing for a
+              convolution whose pool runs in its own launch.
     The run is the longest stretch of such layers that ends in front of the chain.  It starts at its first convolution
     whose input map is smaller than the map the layer writes: the standalone quantise then costs less than the layer's
     own store (SSD300: block3_conv1 on the 75x75x128 pooled map, not block2_conv2 on the 150x150x128 one)."""
     n = len(nodes)
     end = n if chain_start is None else chain_start
+    pools = ("pool", "pool3s1")
 
-    def pools_itself(i):                 # a 3x3 / stride-1 fp8 convolution with a pool behind it inside the run
-        return (mxfp8_eligible(nodes[i]) and nodes[i]["k"] == 3 and nodes[i]["stride"] == 1 and i + 1 < end
-                and nodes[i + 1]["kind"] == "pool")
+    def pools_itself(i):                 # a 3x3 / stride-1 fp8 convolution with a 2x2 pool behind it inside the run
+        nd = nodes[i]
+        return (mxfp8_eligible(nd) and nd["k"] == 3 and nd["stride"] == 1 and nd.get("dilation", 1) == 1 and not nd["feature"]
+                and i + 1 < end and nodes[i + 1]["kind"] == "pool")
 
     s = end
-    while s > 1 and (mxfp8_eligible(nodes[s - 1]) or (nodes[s - 1]["kind"] == "pool" and pools_itself(s - 2))):
+    while s > 1 and (mxfp8_eligible(nodes[s - 1]) or (nodes[s - 1]["kind"] in pools and mxfp8_eligible(nodes[s - 2]))):
         s -= 1
     size = [nd["hout"] ** 2 * nd["cout"] for nd in nodes]
     start = None
@@ -125,6 +138,7 @@ def mxfp8_vgg_plan(nodes, chain_start):
     assert start is not None, "no layer of this trunk can run in fp8 behind a quantise cheaper than its own store"
     fp8 = {i for i in range(start, end) if nodes[i]["kind"] == "conv"}
     pooled = {i + 1 for i in fp8 if pools_itself(i)}
+    qpool = {i for i in range(start, end) if nodes[i]["kind"] in pools and i not in pooled}
     quant = {start - 1}
     writes = {i: set() for i in range(n)}
     for i, nd in enumerate(nodes):
@@ -135,10 +149,17 @@ def mxfp8_vgg_plan(nodes, chain_start):
     writes[start - 1].add("bf16")
     for i, w in writes.items():
         assert w or (i in fp8 and i + 1 in pooled), "node %d has no consumer" % i
-        if "fp8" in w:
-            assert i in fp8 or i in pooled or i in quant, "node %d would need a standalone activation quantise" % i
-    assert all(i - 1 in fp8 for i in pooled)
-    return fp8, pooled, quant, {i: frozenset(w) for i, w in writes.items()}
+        if "fp8" in w:                   # (a quantising pooling is its own quantiser)
+            assert i in fp8 or i in pooled or i in qpool or i in quant, "node %d would need a standalone activation quantise" % i
+    assert all(i - 1 in fp8 for i in pooled | qpool) and not any(nodes[i - 1]["feature"] for i in pooled)
+    return MxTrunkPlan(fp8, pooled, qpool, quant, {i: frozenset(w) for i, w in writes.items()})
+
+
+def mxfp8_vgg_plan(nodes, chain_start):
+    """mxfp8_trunk_plan as the 4-tuple (fp8, pooled, quant, writes): the plan of a trunk without quantising poolings (the
+    default SSD300 and its 512 form), where qpool is empty."""
+    p = mxfp8_trunk_plan(nodes, chain_start)
+    return p.fp8, p.pooled, p.quant, p.writes
 
 
 class ParamTensor:
@@ -581,14 +602,18 @@ class SSDEngine:
     side_streams = True
 
     def __init__(self, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, device="cuda",
-                 seed=0, sparse_heads=None, l2norm=None):
+                 seed=0, sparse_heads=None, l2norm=None, fp8_inference=False):
         """l2norm: the SSD paper's L2 normalisation of feature map 0 in front of its head (ops.L2NormSpec.of: None / False = off,
         True, an initial scale, a dict or a spec).  Off, the engine plans the same tensors and launches what it did without
-        the option; on, one more variable "l2norm0/scale" follows every other one."""
+        the option; on, one more variable "l2norm0/scale" follows every other one.
+        fp8_inference: plan forward(x, "mxfp8") for a trunk with a 3x3 / stride-1 pooling or a dilated convolution as well (the
+        VGG-16 SSD300: mxfp8_trunk_plan's quantising poolings and the fp8 atrous convolution).  Off, such a trunk is
+        bf16_only and refuses that forward, as it always did; a trunk without those nodes has its fp8 plan either way."""
         # the heads' backward pass from the loss's compact gradient rows (csrc/sparse.hip); SSD_SPARSE_HEADS=0: the dense
         # kernels on the scattered gradient (tests compare the two)
         self._plan(classes, in_size, trunk, num_priors, device, l2norm,
-                   (os.environ.get("SSD_SPARSE_HEADS", "1") == "1") if sparse_heads is None else bool(sparse_heads))
+                   (os.environ.get("SSD_SPARSE_HEADS", "1") == "1") if sparse_heads is None else bool(sparse_heads),
+                   fp8_inference=fp8_inference)
         # the trailing convolutions on LDS-sized maps (the extras behind the 19x19 map) as ONE launch, forward and data gradient
         # (ops.conv_chain); a set: {"fwd", "bwd"}, emptied by a refusal of the kernel
         self.chain = {"1": {"fwd", "bwd"}, "fwd": {"fwd"}, "bwd": {"bwd"}}.get(os.environ.get("SSD_CHAIN", "1"), set())
@@ -636,22 +661,23 @@ class SSDEngine:
 
     # ---------------------------------------------------------------- static planning
     @classmethod
-    def planned(cls, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, l2norm=None):
+    def planned(cls, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, l2norm=None, fp8_inference=False):
         """The static plan alone (nodes, fm, grids, A, tensors, chain_start): no device is touched, nothing can be launched."""
         e = cls.__new__(cls)
-        e._plan(classes, in_size, trunk, num_priors, "cpu", l2norm, True)
+        e._plan(classes, in_size, trunk, num_priors, "cpu", l2norm, True, fp8_inference=fp8_inference)
         return e
 
-    def _plan(self, classes, in_size, trunk, num_priors, device, l2norm, sparse_heads):
+    def _plan(self, classes, in_size, trunk, num_priors, device, l2norm, sparse_heads, fp8_inference=False):
         """The static part of an engine, shared by __init__ and planned()."""
         self.L = _lib.lib()
+        self.fp8_inference = bool(fp8_inference)
         self.l2norm = ops.L2NormSpec.of(l2norm)
         self.classes, self.in_size, self.device = classes, in_size, torch.device(device)
         self.trunk, self.num_priors, self.sparse_heads = list(trunk), tuple(num_priors), sparse_heads
         self.block = self.L.ssd_opt_block_elems()
-        # inference in block-scaled fp8 (forward(x, "mxfp8")): the plan (mxfp8_vgg_plan, at its first use), the stretch (lo, hi)
+        # inference in block-scaled fp8 (forward(x, "mxfp8")): the plan (mxfp8_trunk_plan, at its first use), the stretch (lo, hi)
         # of param_bf16 that holds the fp8 layers' filters and its quantised form
-        self._vgg_mx, self._mx_range = None, None
+        self._mx_plan, self._mx_range = None, None
         self.mx_filters = mx.FlatStore()
         self._plan_shapes()
         self._plan_params()
@@ -694,8 +720,10 @@ class SSDEngine:
         pair = [(nd["kind"], nd["cin"], nd["cout"], nd["k"], nd["stride"]) for nd in self.nodes[:2]]
         self.first_pair = (pair == [("conv", 8, 64, 3, 1), ("conv", 64, 64, 3, 1)]
                            and self.nodes[1]["pt"] == self.nodes[1]["pl"] == 1)
-        # node kinds the block-scaled fp8 forward has no plan for (the VGG-16 SSD300's pool5 and fc6)
-        self.bf16_only = any(nd["kind"] == "pool3s1" or nd["dilation"] != 1 for nd in self.nodes)
+        # node kinds the block-scaled fp8 forward plans only where the engine was built with fp8_inference (the VGG-16 SSD300's
+        # pool5 and fc6)
+        self.bf16_only = (any(nd["kind"] == "pool3s1" or nd["dilation"] != 1 for nd in self.nodes)
+                          and not getattr(self, "fp8_inference", False))
 
     def _plan_params(self):
         self.tensors = []
@@ -903,7 +931,7 @@ class SSDEngine:
 
     def forward(self, x, precision="bf16"):
         """x: bf16 [B, S, S, 8] (ops.image_prep).  Returns (loc bf16 [B,A,4], conf bf16 [B,A,classes]).
-        precision="mxfp8": inference only -- the trunk layers of mxfp8_vgg_plan on block-scaled fp8 operands, the rest, the
+        precision="mxfp8": inference only -- the trunk layers of mxfp8_trunk_plan on block-scaled fp8 operands, the rest, the
         chain and the heads in bf16, on the same streams as the bf16 forward; backward() then raises until a bf16 forward."""
         if precision == "mxfp8":
             if self.bf16_only:
@@ -1036,22 +1064,28 @@ class SSDEngine:
                                       same=self._pool_same(nd))
 
     # ---------------------------------------------------------------- inference in block-scaled fp8 (MX e4m3)
-    def vgg_mxfp8_plan(self):
-        """mxfp8_vgg_plan of this engine's trunk: (fp8, pooled, quant, writes)."""
-        if self._vgg_mx is None:
-            fp8, pooled, quant, writes = mxfp8_vgg_plan(self.nodes, self.chain_start)
+    def mxfp8_plan(self):
+        """mxfp8_trunk_plan of this engine's trunk (MxTrunkPlan), with the filters' stretch of param_bf16 laid out."""
+        if self._mx_plan is None:
+            plan = mxfp8_trunk_plan(self.nodes, self.chain_start)
+            fp8 = plan.fp8
             # the fp8 layers' filters: their stretch of param_bf16 (conv filters start on optimizer-block boundaries, so every
             # layer's (q, scale) is a slice of mx_filters)
             lo = min(self.conv_params[i][0].offset for i in fp8)
             hi = max(bt.block0 + bt.nblocks for _, bt in (self.conv_params[i] for i in fp8)) * self.block
             assert all((self.conv_params[i][0].offset - lo) % 32 == 0 for i in fp8) and lo % 32 == 0 and (hi - lo) % 32 == 0
-            self._vgg_mx = (fp8, pooled, quant, writes)
+            self._mx_plan = plan
             self._mx_range = (lo, hi)
-        return self._vgg_mx
+        return self._mx_plan
+
+    def vgg_mxfp8_plan(self):
+        """mxfp8_plan() as the 4-tuple (fp8, pooled, quant, writes)."""
+        p = self.mxfp8_plan()
+        return p.fp8, p.pooled, p.quant, p.writes
 
     def _mx_act_writes(self):
         """{node: forms of its output the fp8 forward stores}."""
-        return self.vgg_mxfp8_plan()[3]
+        return self.mxfp8_plan().writes
 
     def _mx_pairs(self, B, key, nodes):
         """{node: mx.pair of its [B,H,W,C] map} for `nodes`, kept under `key` beside the bf16 activations of batch size B
@@ -1082,11 +1116,19 @@ class SSDEngine:
         return self._walk(x, lambda i, c: self._mxfp8_node(i, c, maps8))
 
     def _mxfp8_node(self, i, c, maps8):
-        """Launch trunk node i of the fp8 forward: an fp8 convolution (with the pool behind it where the plan fuses one), or
-        node i as the bf16 forward launches it (+ the plan's one standalone quantise of its output)."""
-        fp8, pooled, quant, writes = self._vgg_mx
+        """Launch trunk node i of the fp8 forward: an fp8 convolution (with the pool behind it where the plan fuses one), a
+        quantising pooling, or node i as the bf16 forward launches it (+ the plan's one standalone quantise of its output)."""
+        fp8, pooled, qpool, quant, writes = self._mx_plan
         if i in pooled:
             return                                 # the fp8 convolution in front of it wrote its output
+        if i in qpool:                             # reads the bf16 map in front of it, stores the pooled map in fp8
+            nd, w = self.nodes[i], writes[i]
+            kw = dict(want_bf16="bf16" in w, out=c["acts"][i + 1], q=maps8[i][0], scale=maps8[i][1])
+            if nd["kind"] == "pool3s1":
+                ops.maxpool3x3s1_fwd_mxfp8(c["acts"][i], **kw)
+            else:
+                ops.maxpool2x2_fwd_mxfp8(c["acts"][i], same=self._pool_same(nd), **kw)
+            return
         if i not in fp8:
             self._bf16_node(i, c)
             if i in quant:
@@ -1104,6 +1146,8 @@ class SSDEngine:
         if o != i:
             pnd = self.nodes[o]
             ops.conv2d_fwd_pool_mxfp8(*args, self._pool_same(pnd), **kw)
+        elif nd["dilation"] != 1:
+            ops.conv2d_atrous_fwd_mxfp8(xq, xs, wq, ws, bias, nd["dilation"], True, **kw)
         else:
             ops.conv2d_fwd_mxfp8(*args, **kw)
 

@@ -80,7 +80,7 @@ class SSDObjectDetectionModel:
             self.thresh = 0.5
 
     def __init__(self, classes, log_dir, device="cuda", seed=0, distributed=False, timestamp_dir=True, l2norm=None,
-                 network=None):
+                 network=None, fp8_inference=False):
         """l2norm: the SSD paper's L2 normalisation of the 38x38 feature map in front of its head, with a learned per-channel
         scale (ops.L2NormSpec.of: None / False = off as in the reference, True = the paper's initial scale 20, a number, a dict
         or a spec).  The scale is one more variable of the engine: trained, clipped, saved and loaded like the others.
@@ -94,8 +94,19 @@ class SSDObjectDetectionModel:
         split_batch, data parallelism, validation, checkpoints, the scalar log -- is the same code.  With split_batch a
         batchnorm network normalises each micro-batch with that micro-batch's statistics and updates its running statistics
         once per micro-batch; under data parallelism every rank normalises with its own batch (no synchronised batch norm).
-        ValueError for l2norm together with the ResNet."""
+        ValueError for l2norm together with the ResNet.
+
+        fp8_inference: the engine's switch of the same name -- detect / detections / evaluate(precision="mxfp8") for the
+        "vgg16_ssd300" network, which refuses that precision without it ("ssd300" has its fp8 forward either way).  It changes
+        nothing else: training, the variables and checkpoints are the same with and without it, so it is not part of the
+        network's identity.  ValueError for the ResNet, whose fp8 is NetworkSpec.precision."""
         self.network = ops.NetworkSpec.of(network, l2norm=l2norm)
+        if not isinstance(fp8_inference, bool):
+            raise ValueError("fp8_inference must be True or False, not %r" % (fp8_inference,))
+        if fp8_inference and self.network.kind not in ("ssd300", "vgg16_ssd300"):
+            raise ValueError("fp8_inference is the switch of the ssd300 / vgg16_ssd300 engines; the %s network's fp8 forward is "
+                             "set by its network spec (precision)" % self.network.kind)
+        self.fp8_inference = fp8_inference
         self.distributed = bool(distributed)
         if timestamp_dir:
             stamp = [time.strftime("%Y-%m-%d-%H%M%S", time.localtime())]
@@ -112,7 +123,7 @@ class SSDObjectDetectionModel:
             if net.kind == "vgg16_ssd300":
                 graph = dict(trunk=VGG16_SSD300_TRUNK, num_priors=VGG16_SSD300_NUM_PRIORS)
             self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed,
-                                     l2norm=l2norm, **graph)
+                                     l2norm=l2norm, fp8_inference=fp8_inference, **graph)
             self._pset = ops.build_priors(grids=self._engine.grids, device=device)
             self._forward_train = self._engine.forward
             self._backward_args = {}

@@ -1915,6 +1915,62 @@ def maxpool3x3s1_bwd(code, dy, x_shape, out=None):
     return out
 
 
+# ---- ... and their inference fp8 forms (engine.SSDEngine(fp8_inference=True)) --------------------------------------------------
+def conv2d_atrous_fwd_mxfp8(xq, xs, wq, ws, bias, dilation, relu, want_bf16=True, want_fp8=False, out=None, out_q=None,
+                            out_scale=None):
+    """conv2d_atrous_fwd on block-scaled fp8 operands (quantize_mx_fp8 of x [B,H,W,Cin] and w [Cout,3,3,Cin]); outputs as
+    conv2d_fwd_mxfp8: the bf16 map, (q, scale) = its quantize_mx_fp8, or (bf16, q, scale).  At dilation 1 it is
+    conv2d_fwd_mxfp8 at 3x3 / stride 1 / pads 1 bit for bit."""
+    L = _lib.lib()
+    B, H, W, Cin = xq.shape
+    Cout = wq.shape[0]
+    _mx_operands(xq, xs, wq, ws, (B, H, W, Cin), (Cout, 3, 3, Cin))
+    out, out_q, out_scale, result = _mx_outputs((B, H, W, Cout), xq.device, want_bf16, want_fp8, out, out_q, out_scale)
+    for name, t, ch in (("out", out, Cout), ("out_q", out_q, Cout), ("out_scale", out_scale, max(Cout // 32, 1))):
+        if t is not None:
+            _same_shape(name, t, (B, H, W, ch))
+    rc = L.ssd_conv2d_atrous_fwd_mxfp8(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(out), _ptr(out_q), _ptr(out_scale),
+                                       B, H, W, Cin, Cout, dilation, 1 if relu else 0, _stream())
+    _lib.check(rc, unsupported="block-scaled fp8 atrous forward needs Cin %% 128 == 0, Cout %% 8 == 0, Cout %% 32 == 0 for an fp8 "
+                               "output and every tensor below 2^31 bytes; got %s" % ((B, H, W, Cin, Cout),))
+    return result
+
+
+_POOL_MX_RANGE = "quantising max pooling: C must be a multiple of 32 and the map below 2^31 elements; got %s"
+
+
+def _pool_mx_outputs(x, shape, want_bf16, out, q, scale):
+    _bf(x)
+    if want_bf16 and out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+    q, scale = _mx_default(shape, x.device, q, scale)
+    _pooled_shapes(shape[:3], *((t, ch) for t, ch in ((out if want_bf16 else None, shape[3]), (q, shape[3]),
+                                                     (scale, max(shape[3] // 32, 1))) if t is not None))
+    return (out if want_bf16 else None), q, scale
+
+
+def maxpool2x2_fwd_mxfp8(x, same=False, want_bf16=False, out=None, q=None, scale=None):
+    """(q, scale) = quantize_mx_fp8(maxpool2x2_fwd(x, same)) bit for bit, in one pass over the bf16 map x [B,H,W,C]; with
+    want_bf16 (out, q, scale): the pooled bf16 map as well.  Inference only: no winner codes."""
+    L = _lib.lib()
+    B, H, W, C = x.shape
+    Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if same else (H // 2, W // 2)
+    out, q, scale = _pool_mx_outputs(x, (B, Ho, Wo, C), want_bf16, out, q, scale)
+    _lib.check(L.ssd_maxpool2x2_fwd_mxfp8(_ptr(x), _ptr(out), _ptr(q), _ptr(scale), B, H, W, C, Ho, Wo, _stream()),
+               unsupported=_POOL_MX_RANGE % ((B, H, W, C),))
+    return (out, q, scale) if want_bf16 else (q, scale)
+
+
+def maxpool3x3s1_fwd_mxfp8(x, want_bf16=False, out=None, q=None, scale=None):
+    """(q, scale) = quantize_mx_fp8(maxpool3x3s1_fwd(x)[0]) bit for bit, in one pass; with want_bf16 (out, q, scale)."""
+    L = _lib.lib()
+    B, H, W, C = x.shape
+    out, q, scale = _pool_mx_outputs(x, (B, H, W, C), want_bf16, out, q, scale)
+    _lib.check(L.ssd_maxpool3x3s1_fwd_mxfp8(_ptr(x), _ptr(out), _ptr(q), _ptr(scale), B, H, W, C, _stream()),
+               unsupported=_POOL_MX_RANGE % ((B, H, W, C),))
+    return (out, q, scale) if want_bf16 else (q, scale)
+
+
 def head_grad_pack(dloc, dconf, hw, per_cell, classes, npad, level_off, out=None):
     L = _lib.lib()
     _bf(dloc); _bf(dconf)

@@ -120,6 +120,16 @@ def l2norm_from_config(config):
     return spec if enable else None
 
 
+def fp8_inference_from_config(config):
+    """`model: fp8_inference: true` (no reference counterpart) -> the model's fp8_inference switch: the VGG-16 SSD300 network then
+    plans its block-scaled fp8 inference forward (validation or detection with precision "mxfp8").  False when the key is
+    absent.  ValueError for anything but true or false."""
+    value = (config.get("model") or {}).get("fp8_inference", False)
+    if not isinstance(value, bool):
+        raise ValueError("model.fp8_inference must be true or false, not %r" % (value,))
+    return value
+
+
 def network_from_config(config):
     """`model: network: {kind, in_size, batchnorm: {enable, momentum, eps}, precision, dgrad_precision}` (no reference
     counterpart) -> ops.NetworkSpec, or None when the key is absent: the default run builds the reference's 300 x 300 network.
@@ -257,7 +267,8 @@ def train(config):
         if n_cat != data_cfg["num_classes"]:
             raise ValueError("data.num_classes is %r but the annotation files list %d categories" % (data_cfg["num_classes"], n_cat))
     model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1,
-                                    l2norm=l2norm_from_config(config), network=network)
+                                    l2norm=l2norm_from_config(config), network=network,
+                                    fp8_inference=fp8_inference_from_config(config))
     model.decode_workers = decode_workers
 
     lr, wlr = model_cfg["train"]["lr"], model_cfg["warmup"]["lr"]

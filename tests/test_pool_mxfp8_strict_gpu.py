@@ -1,0 +1,151 @@
+"""GPU: the quantising poolings ssd_maxpool2x2_fwd_mxfp8 / ssd_maxpool3x3s1_fwd_mxfp8 (pool4 and pool5 of the VGG-16 SSD300's
+inference fp8 forward) under the strict harness: arena, guard bands, two poisons, every comparison torch.equal.
+
+Inputs are small integers times a power of two PER 32-CHANNEL BLOCK AND PIXEL (exponents over -20 .. 20, as
+strict.mx_eltwise_case), so the pixels of one window have different block scales: a kernel that pools the e4m3 codes of its
+inputs, or quantises the pooled block under the centre pixel's scale, fails.  Expectation: strict.ref_quantize_mx of
+strict.ref_pool's map (a pooled value is one of the inputs: exact in bf16).  With and without the optional bf16 output; the
+non-finite rule of csrc/mxfp8.h on the pooled values; a refusal leaves the outputs untouched."""
+import functools
+
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from tests import strict                                                                         # noqa: E402
+
+BF, U8 = torch.bfloat16, torch.uint8
+POOL3 = [(2, 19, 19, 64), (3, 5, 7, 32), (1, 2, 9, 32), (1, 1, 1, 32)]
+POOL2 = [(s, same) for s in [(2, 19, 19, 64), (1, 6, 8, 96), (3, 5, 7, 32)] for same in (True, False)] + [((1, 1, 1, 32), True)]
+
+
+@pytest.fixture(scope="module")
+def ops():
+    import ssd_object_detection_amd.ops as ops_
+    return ops_
+
+
+def pooled_shape(shape, ksize, same):
+    B, H, W, C = shape
+    if ksize == 3:
+        return B, H, W, C
+    return (B, (H + 1) // 2, (W + 1) // 2, C) if same else (B, H // 2, W // 2, C)
+
+
+def ref(x, ksize, same):
+    """strict.ref_pool's map of x (bf16) by the stated conventions, back in bf16 exactly"""
+    _, Ho, Wo, _ = pooled_shape(x.shape, ksize, same)
+    y, _ = strict.ref_pool(x.float(), 3, 1, 1, 1, Ho, Wo, 15) if ksize == 3 else strict.ref_pool(x.float(), 2, 2, 0, 0, Ho, Wo, 4)
+    out = y.to(BF)
+    assert torch.equal(out.float(), y)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case(shape, ksize, same):
+    g = strict._gen(*shape, ksize, 41)
+    x_int = strict.ints(g, shape, (-2, -1, 0, 0, 1, 1, 2, 3))
+    x_int[:, ::3, ::4] = strict.ints(g, x_int[:, ::3, ::4].shape, (-3, -1, 0))       # windows whose maximum is <= 0
+    e = torch.randint(-20, 21, tuple(shape[:-1]) + (shape[-1] // 32,), generator=g)
+    x = strict._pow2_blocks(x_int, e)
+    y = ref(x, ksize, same)
+    q, s = strict.ref_quantize_mx(y)
+    # the regime: pooled values are inputs (exact in bf16).  A pooled block mixes the scales of up to nine pixels, so its small
+    # elements round or underflow under its own scale: ref_quantize_mx states those bytes, the quantiser's strict tests cover
+    # the rounding itself
+    assert bool(torch.isfinite(y.float()).all())
+    if x.shape[1] * x.shape[2] > 1:
+        # the case can tell the pooled block's own scale from the scale of the window's first / centre pixel
+        qc, sc_ = strict.ref_quantize_mx(x)
+        centre = sc_ if ksize == 3 else sc_[:, ::2, ::2][:, :y.shape[1], :y.shape[2]]
+        assert float((centre != s).float().mean()) > 0.3
+    return dict(x=x, y=y, q=q, s=s)
+
+
+def run(ops, x, y_ref, q_ref, s_ref, ksize, same):
+    a = strict.Arena("cuda", strict.Arena.bytes_for(*(4 * [x.numel() * 2])) + (8 << 20))
+    src = a.put(x, "x")
+    shape = tuple(y_ref.shape)
+    y, q, sc = a.out(shape, BF, "y"), a.out(shape, U8, "q"), a.out(shape[:3] + (shape[3] // 32,), U8, "scale")
+    if ksize == 3:
+        def call(**kw):
+            return ops.maxpool3x3s1_fwd_mxfp8(src, **kw)
+    else:
+        def call(**kw):
+            return ops.maxpool2x2_fwd_mxfp8(src, same=same, **kw)
+    a.run(lambda: call(want_bf16=True, out=y, q=q, scale=sc), [(y, y_ref), (q, q_ref), (sc, s_ref)])
+    got = a.run(lambda: call(q=q, scale=sc), [(q, q_ref), (sc, s_ref)])           # (the unlisted bf16 buffer keeps its poison)
+    return got
+
+
+@pytest.mark.parametrize("shape", POOL3, ids=lambda s: str(s).replace(" ", ""))
+def test_maxpool3x3s1(ops, shape):
+    r = case(shape, 3, True)
+    run(ops, r["x"], r["y"], r["q"], r["s"], 3, True)
+    # ... which is the two launches it replaces, bit for bit
+    x = r["x"].cuda()
+    yb, _ = ops.maxpool3x3s1_fwd(x)
+    q2, s2 = ops.quantize_mx_fp8(yb)
+    assert torch.equal(yb.cpu(), r["y"]) and torch.equal(q2.cpu(), r["q"]) and torch.equal(s2.cpu(), r["s"])
+
+
+@pytest.mark.parametrize("p", POOL2, ids=lambda p: "%s %s" % (str(p[0]).replace(" ", ""), "same" if p[1] else "valid"))
+def test_maxpool2x2(ops, p):
+    shape, same = p
+    r = case(shape, 2, same)
+    run(ops, r["x"], r["y"], r["q"], r["s"], 2, same)
+    x = r["x"].cuda()
+    q2, s2 = ops.quantize_mx_fp8(ops.maxpool2x2_fwd(x, same=same))
+    assert torch.equal(q2.cpu(), r["q"]) and torch.equal(s2.cpu(), r["s"])
+
+
+NAN, INF = float("nan"), float("inf")
+
+
+@pytest.mark.parametrize("ksize", [2, 3])
+def test_non_finite(ops, ksize):
+    """An infinity that wins its window makes the pooled pixel's block non-finite: 32 bytes 0x7F under the scale byte 127, the
+    blocks beside it untouched; a NaN or a -inf that loses is dropped by the maximum, as in the bf16 poolings; a window of
+    -inf alone (the 1x1 map) is non-finite too."""
+    shape = (1, 5, 7, 96)
+    r = case(shape, ksize, True)
+    x = r["x"].clone()
+    x[0, 2, 3, 40] = INF                                   # middle block of one pixel: wins every window that holds it
+    x[0, 0, 0, 5] = NAN                                    # dropped: the other pixels of its windows decide
+    x[0, 4, 5, 70] = -INF                                  # loses wherever the window holds another pixel
+    x[0, 4, 1, 31] = -INF
+    _, Ho, Wo, _ = pooled_shape(shape, ksize, True)
+    yf, _ = strict.ref_pool(x.float(), 3, 1, 1, 1, Ho, Wo, 15) if ksize == 3 else strict.ref_pool(x.float(), 2, 2, 0, 0, Ho, Wo, 4)
+    y = yf.to(BF)
+    assert not bool(torch.isnan(yf).any()) and int(torch.isinf(yf).sum()) == (9 if ksize == 3 else 1)
+    q_ref, s_ref = strict.ref_quantize_mx(y)
+    bad = ~torch.isfinite(y.float().view(1, Ho, Wo, 3, 32)).all(-1)
+    assert int(bad.sum()) == (9 if ksize == 3 else 1) and bool((q_ref.view(1, Ho, Wo, 3, 32)[bad] == 0x7F).all())
+    assert bool((s_ref[bad] == 127).all()) and not bool((s_ref == 255).any())
+    gq, gs = run(ops, x, y, q_ref, s_ref, ksize, True)
+    deq = ops.dequantize_mx_fp8(gq.cpu(), gs.cpu()).view(1, Ho, Wo, 3, 32)
+    assert bool(torch.isnan(deq[bad]).all()) and bool(torch.isfinite(deq[~bad]).all())     # the blocks beside it stay finite
+    # the 1x1 map: its one window holds -inf alone in one block
+    one = torch.ones((1, 1, 1, 64), dtype=BF)
+    one[0, 0, 0, 33] = -INF
+    q1, s1 = strict.ref_quantize_mx(one)
+    assert bool((q1[..., 32:] == 0x7F).all()) and int(s1[0, 0, 0, 1]) == 127
+    run(ops, one, one, q1, s1, ksize, True)
+
+
+@pytest.mark.parametrize("ksize", [2, 3])
+def test_24_channels_are_refused(ops, ksize):
+    a = strict.Arena("cuda", 32 << 20)
+    x = a.put(strict.ints(strict._gen(24, ksize), (1, 4, 4, 24), (-1, 1, 2)), "x")
+    shape = pooled_shape((1, 4, 4, 24), ksize, True)
+    y, q, sc = a.out(shape, BF, "y"), a.out(shape, U8, "q"), a.out(shape[:3] + (1,), U8, "scale")
+
+    def refused():
+        for kw in (dict(want_bf16=True, out=y, q=q, scale=sc), dict(q=q, scale=sc)):
+            with pytest.raises(NotImplementedError, match="multiple of 32"):
+                if ksize == 3:
+                    ops.maxpool3x3s1_fwd_mxfp8(x, **kw)
+                else:
+                    ops.maxpool2x2_fwd_mxfp8(x, same=True, **kw)
+    a.run(refused, [])
