@@ -341,6 +341,37 @@ int ssd_detect_pairs(const void* conf, const void* loc, int dtype, const double*
  *   tp_count int32[C*4*3*10]  [class][range][m][threshold]: true positives not ignored with pos < (1, 10, max_dets)[m]
  *   Both are 0 where n_gt == 0 (the caller leaves the class out of that range's means).
  * Both return SSD_ERR_VALUE before any launch on the conditions of ssd_eval_match / ssd_eval_ap.
+ *
+ * PASCAL VOC (VOCdevkit's VOCevaldet) is a third pair; its definition and oracle is utils/metrics.py:voc_map (voc_match_image
+ * for the first stage, voc_ap_from_rows for the second).  It is not a special case of the pairs above: there is one IoU
+ * threshold and no greedy pass.
+ *
+ * ssd_eval_match_voc: ssd_eval_match's inputs without the threshold table, and
+ *   gt_difficult uint8[total_gt]  non-zero: a `difficult` box; NULL: none
+ *   iou_thresh   one threshold, finite and > 0 (VOC: 0.5)
+ *   max_dets     1 .. ssd_eval_voc_max_dets() (256: SSD's detection output keeps 200 per image)
+ * The selection and order of the detections are ssd_eval_match's.  Per detection, over ALL boxes of its class in its image,
+ * claimed or not, difficult ones included: ovmax = the highest IoU (iou_matrix in float64, continuous coordinates: VOCdevkit's
+ * +1 pixel convention is not applied), jmax = the FIRST index attaining it.  When ovmax >= iou_thresh: the detection is ignored
+ * if box jmax is difficult; else a true positive if no detection before it in the order has the same jmax with its own ovmax >=
+ * iou_thresh; else a false positive (a duplicate, even where a second box would also pass).  Otherwise a false positive.
+ *   n_det, det_score, det_cls, det_box  as ssd_eval_match
+ *   det_flags uint8[B*max_dets]   bit 0: true positive, bit 1: ignored
+ *   det_gt int32[B*max_dets]      jmax as an index into the image's boxes, -1 when ovmax < iou_thresh or there is no box
+ * All fully written; slots at or beyond n_det hold score 0, class -1, box 0, flags 0, det_gt -1.  Images with more than 64
+ * ground truths take a path without the per-box LDS arrays, with identical results; any number of boxes per image.
+ *
+ * ssd_eval_ap_voc: after the last batch, one workgroup per class, from rows sorted as for ssd_eval_ap.
+ *   flags_sorted uint8[N] (not NULL, even for N = 0; a row whose bit 1 is set counts as neither true nor false positive),
+ *   seg_off int32[C+1], n_pos int32[C] (non-difficult boxes per class), year 7 or 12,
+ *   recall_points HOST double[11] (np.arange(11) / 10.0: passed in, not recomputed)
+ *   ap double[C]: with ctp / cfp the cumulative counts, recall = ctp / n_pos, precision = ctp / max(ctp + cfp, 1):
+ *     year 7:  (sum over k = 0..10, added in that order, of max{precision[i] : recall[i] >= recall_points[k]}, 0 where none) / 11.0
+ *     year 12: mrec = [0, recall, 1], mpre = [0, precision, 0] made monotone from the right; the sum, in index order, of
+ *              (mrec[i+1] - mrec[i]) * mpre[i+1] where mrec[i+1] != mrec[i]
+ *   0 where n_pos <= 0 (the caller leaves the class out of its mean) or the class has no rows.  Segments of any length.
+ * Both return SSD_ERR_VALUE before any launch on the conditions of ssd_eval_match / ssd_eval_ap, and for a year other than 7 or
+ * 12 or an iou_thresh that is not finite or not > 0.
  * ---------------------------------------------------------------------------------------- */
 int ssd_eval_max_dets(void);
 int ssd_eval_match(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
@@ -357,6 +388,13 @@ int ssd_eval_match_coco(const float* score, const int32_t* cls, const float* box
 int ssd_eval_ap_coco(const uint16_t* tp_sorted, const uint16_t* ig_sorted, const int32_t* pos_sorted, const int32_t* seg_off,
                      const int32_t* n_gt, int C, int max_dets, const double* recall_points, double* ap, int32_t* tp_count,
                      void* stream);
+int ssd_eval_voc_max_dets(void);
+int ssd_eval_match_voc(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
+                       const int32_t* gt_cls, const double* gt_box, const int32_t* gt_off, const uint8_t* gt_difficult,
+                       double iou_thresh, int max_dets, int32_t* n_det, float* det_score, int32_t* det_cls, float* det_box,
+                       uint8_t* det_flags, int32_t* det_gt, void* stream);
+int ssd_eval_ap_voc(const uint8_t* flags_sorted, const int32_t* seg_off, const int32_t* n_pos, int C, int year,
+                    const double* recall_points, double* ap, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Convolution stack (NHWC bf16 activations, bf16 weights [Cout][k][k][Cin], fp32 accumulate on MFMA).

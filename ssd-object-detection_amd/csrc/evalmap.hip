@@ -15,8 +15,10 @@
 //                 load serves all thresholds).  Only true positives can raise the right-to-left precision envelope, so each
 //                 contributes precision = ctp / (i + 1) to the LAST recall point <= its recall (LDS 64-bit max on the bits of a
 //                 non-negative double); a suffix maximum over the 101 buckets is the sampled envelope.
+//   (k_eval_match_coco / k_eval_ap_coco: COCO's twelve metrics; k_eval_match_voc / k_eval_ap_voc: PASCAL VOC's AP -- further down)
 // IoU is utils/metrics.iou_matrix operation for operation in float64.  Compile with -ffp-contract=off.
 #include "common.h"
+#include <float.h>
 #include <limits.h>
 
 namespace {
@@ -69,38 +71,15 @@ __device__ __forceinline__ double iou_f64(float4 d, double gx, double gy, double
     return uni > 0.0 ? inter / fmax(uni, 1e-300) : 0.0;
 }
 
-__global__ __launch_bounds__(WG) void k_eval_match(const float* __restrict__ score, const int* __restrict__ cls,
-                                                   const float4* __restrict__ box, const uint8_t* __restrict__ keep, int A,
-                                                   const int* __restrict__ gt_cls, const double* __restrict__ gt_box,
-                                                   const int* __restrict__ gt_off, Thresholds thr, int max_dets,
-                                                   int* __restrict__ n_det, float* __restrict__ det_score,
-                                                   int* __restrict__ det_cls, float4* __restrict__ det_box,
-                                                   uint16_t* __restrict__ det_flags) {
-    // s_big: the sort keys [CAP] u64 + the candidate list [CAP] int during the selection, the IoU matrix [MAXD][GL] afterwards
-    __shared__ __attribute__((aligned(16))) double s_big[MAXD * GL];
-    __shared__ float4 s_dbox[MAXD];
-    __shared__ int s_dcls[MAXD];
-    __shared__ int s_danchor[MAXD];
-    __shared__ unsigned s_flags[MAXD];
-    __shared__ int s_ord[MAXD];                  // detection ranks ordered by (class, rank)
-    __shared__ int s_seg[MAXD];                  // first position in s_ord of every class segment (any order)
-    __shared__ int s_match[NT][MAXD];            // uncached mode: ground truth claimed by the detection at a position, -1 none
-    __shared__ double s_gbox[GL][4];
-    __shared__ int s_gcls[GL];
-    __shared__ int s_hist[256];
-    __shared__ int s_wave[WG / 64];
-    __shared__ int s_misc[4];
-    static_assert(sizeof(double) * MAXD * GL >= CAP * (sizeof(unsigned long long) + sizeof(int)), "keys + list fit");
-    unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_big);
-    int* s_idx = reinterpret_cast<int*>(s_key + CAP);
-
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const size_t off = (size_t)b * A;
-    const float* sc = score + off;
-    const uint8_t* kp = keep + off;
-
+// The selection stage of every matching kernel: the image's kept anchors ordered by (score desc, anchor asc), cut to the
+// first max_dets.  Candidate list (LDS atomics), exact radix cut when more than CAP anchors are kept, rank sort of 64-bit keys
+// (~score | anchor).  s_key [CAP] and s_idx [CAP] are scratch, dead on return; s_danchor[r] receives the anchor of rank r.
+// Returns the number of detections; ends on a barrier.
+__device__ __forceinline__ int select_ranked(const float* __restrict__ sc, const uint8_t* __restrict__ kp, int A, int max_dets,
+                                             unsigned long long* s_key, int* s_idx, int* s_hist, int* s_wave, int* s_misc,
+                                             int* s_danchor) {
+    const int tid = threadIdx.x;
     if (tid < 4) s_misc[tid] = 0;
-    if (tid < MAXD) s_flags[tid] = 0u;
     __syncthreads();
     // the kept anchors, unordered (the sort orders them completely: the anchor index is part of the key)
     auto note = [&](int a) {
@@ -188,6 +167,41 @@ __global__ __launch_bounds__(WG) void k_eval_match(const float* __restrict__ sco
         if (tid < n_in && rank < nd) s_danchor[rank] = (int)(unsigned)(mine & 0xffffffffull);
     }
     __syncthreads();                             // s_key / s_idx are dead from here on
+    return nd;
+}
+
+__global__ __launch_bounds__(WG) void k_eval_match(const float* __restrict__ score, const int* __restrict__ cls,
+                                                   const float4* __restrict__ box, const uint8_t* __restrict__ keep, int A,
+                                                   const int* __restrict__ gt_cls, const double* __restrict__ gt_box,
+                                                   const int* __restrict__ gt_off, Thresholds thr, int max_dets,
+                                                   int* __restrict__ n_det, float* __restrict__ det_score,
+                                                   int* __restrict__ det_cls, float4* __restrict__ det_box,
+                                                   uint16_t* __restrict__ det_flags) {
+    // s_big: the sort keys [CAP] u64 + the candidate list [CAP] int during the selection, the IoU matrix [MAXD][GL] afterwards
+    __shared__ __attribute__((aligned(16))) double s_big[MAXD * GL];
+    __shared__ float4 s_dbox[MAXD];
+    __shared__ int s_dcls[MAXD];
+    __shared__ int s_danchor[MAXD];
+    __shared__ unsigned s_flags[MAXD];
+    __shared__ int s_ord[MAXD];                  // detection ranks ordered by (class, rank)
+    __shared__ int s_seg[MAXD];                  // first position in s_ord of every class segment (any order)
+    __shared__ int s_match[NT][MAXD];            // uncached mode: ground truth claimed by the detection at a position, -1 none
+    __shared__ double s_gbox[GL][4];
+    __shared__ int s_gcls[GL];
+    __shared__ int s_hist[256];
+    __shared__ int s_wave[WG / 64];
+    __shared__ int s_misc[4];
+    static_assert(sizeof(double) * MAXD * GL >= CAP * (sizeof(unsigned long long) + sizeof(int)), "keys + list fit");
+    unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_big);
+    int* s_idx = reinterpret_cast<int*>(s_key + CAP);
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t off = (size_t)b * A;
+    const float* sc = score + off;
+    const uint8_t* kp = keep + off;
+
+    if (tid < MAXD) s_flags[tid] = 0u;
+    const int nd = select_ranked(sc, kp, A, max_dets, s_key, s_idx, s_hist, s_wave, s_misc, s_danchor);
     // the detections: outputs fully written (slots at or beyond nd: score 0, class -1, box 0)
     if (tid < max_dets) {
         const size_t o = (size_t)b * max_dets + tid;
@@ -447,93 +461,7 @@ __global__ __launch_bounds__(WG) void k_eval_match_coco(
     const uint8_t* kp = keep + off;
     const double scale = area_scale ? area_scale[b] : 1.0;
 
-    if (tid < 4) s_misc[tid] = 0;
-    __syncthreads();
-    // the kept anchors, unordered (the sort orders them completely: the anchor index is part of the key)
-    auto note = [&](int a) {
-        const int slot = atomicAdd(&s_misc[0], 1);
-        if (slot < CAP) s_idx[slot] = a;
-    };
-    if ((A & 3) == 0) {                          // rows of keep are 4-byte aligned: four anchors per load
-        const unsigned* kp4 = reinterpret_cast<const unsigned*>(kp);
-        const int nq = A >> 2;
-        for (int q = tid; q < nq; q += WG) {
-            const unsigned v = kp4[q];
-            if (!v) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if ((v >> (8 * e)) & 0xffu) note(4 * q + e);
-        }
-    } else {
-        for (int a = tid; a < A; a += WG)
-            if (kp[a]) note(a);
-    }
-    __syncthreads();
-    const int total = s_misc[0];
-    int n_in;                                    // keys that enter the sort
-    if (total <= CAP) {
-        n_in = total;
-        if (tid < total) {
-            const int a = s_idx[tid];
-            s_key[tid] = ((unsigned long long)(~ordered_bits(sc[a])) << 32) | (unsigned long long)(unsigned)a;
-        }
-    } else {
-        // more kept anchors than sort slots: k_eval_match's exact radix cut to the max_dets best
-        unsigned prefix = 0;
-        int k = max_dets;                        // rank (1-based, from the top) still to locate
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            if (tid < 256) s_hist[tid] = 0;
-            __syncthreads();
-            for (int a = tid; a < A; a += WG)
-                if (kp[a]) {
-                    const unsigned key = ordered_bits(sc[a]);
-                    if (shift == 24 || (key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
-                }
-            __syncthreads();
-            if (tid == 0) {
-                int run = 0, d = 255;
-                for (; d > 0; --d) {
-                    if (run + s_hist[d] >= k) break;
-                    run += s_hist[d];
-                }
-                s_misc[1] = d;
-                s_misc[2] = k - run;
-            }
-            __syncthreads();
-            prefix = (prefix << 8) | (unsigned)s_misc[1];
-            k = s_misc[2];
-            __syncthreads();
-        }
-        const unsigned cut_bits = prefix;        // take score > cut, and the first `k` (anchor order) with score == cut
-        int filled = 0, eq_seen = 0;
-        for (int a0 = 0; a0 < A; a0 += WG) {
-            const int a = a0 + tid;
-            bool is_c = a < A && kp[a];
-            const unsigned key = is_c ? ordered_bits(sc[a]) : 0u;
-            const bool is_eq = is_c && key == cut_bits;
-            is_c = is_c && key >= cut_bits;
-            int tot_eq = 0;
-            const int eq_rank = wg_prefix(is_eq, s_wave, tot_eq);
-            if (is_eq && eq_seen + eq_rank >= k) is_c = false;
-            eq_seen += tot_eq;
-            int tot = 0;
-            const int pos = wg_prefix(is_c, s_wave, tot);
-            if (is_c && filled + pos < CAP)
-                s_key[filled + pos] = ((unsigned long long)(~key) << 32) | (unsigned long long)(unsigned)a;
-            filled += tot;
-        }
-        n_in = min(filled, max_dets);            // == max_dets
-    }
-    __syncthreads();
-    // sort by rank: keys are unique, every thread counts the keys below its own (broadcast LDS reads)
-    const int nd = min(n_in, max_dets);
-    {
-        const unsigned long long mine = tid < n_in ? s_key[tid] : ~0ull;
-        int rank = 0;
-        for (int j = 0; j < n_in; ++j) rank += s_key[j] < mine ? 1 : 0;
-        if (tid < n_in && rank < nd) s_danchor[rank] = (int)(unsigned)(mine & 0xffffffffull);
-    }
-    __syncthreads();                             // s_key / s_idx are dead from here on
+    const int nd = select_ranked(sc, kp, A, max_dets, s_key, s_idx, s_hist, s_wave, s_misc, s_danchor);
     // the detections: outputs fully written (slots at or beyond nd: score 0, class -1, box 0)
     if (tid < max_dets) {
         const size_t o = (size_t)b * max_dets + tid;
@@ -813,6 +741,288 @@ __global__ __launch_bounds__(AWG) void k_eval_ap_coco(const uint16_t* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// PASCAL VOC (utils/metrics.voc_map, VOCdevkit's VOCevaldet): one IoU threshold, no greedy pass.
+//
+//   k_eval_match_voc  select_ranked, then one THREAD per detection: (ovmax, jmax) over ALL boxes of its class in the image,
+//                     claimed or not, difficult ones included, the FIRST index winning among equal IoUs.  A detection whose
+//                     ovmax reaches the threshold is ignored when box jmax is difficult, a true positive when it is the
+//                     lowest-ranked detection with that jmax, a false positive (duplicate) otherwise.  With at most GLV boxes
+//                     in the image they sit in LDS and the lowest rank per box is an LDS minimum; with more, boxes are read from
+//                     memory and a detection compares its rank with the earlier detections' jmax -- identical results.
+//   k_eval_ap_voc     per class from the flags sorted by (class, score desc, image, rank): the 11-point mean (year 7) or the
+//                     area under the monotone envelope (year 12).  Only true positives raise recall, and a row that is none
+//                     never lies above the envelope of the true positive before it, so both reduce to the true-positive rows:
+//                     year 7 is k_eval_ap's bucket maximum over 11 points; year 12 is the sum, in row order, of
+//                     (ctp / n_pos - (ctp - 1) / n_pos) * (largest precision at or after the row).  That suffix maximum comes
+//                     from a first pass that leaves the largest precision of every slot of rows in LDS; the second pass then
+//                     forms the terms in parallel and one thread adds them in order.
+constexpr int MAXDV = 256;                   // ssd_eval_voc_max_dets()
+constexpr int GLV = 64;                      // ground truths per image held in LDS
+constexpr int NPV = 11;                      // recall points of the VOC2007 metric
+constexpr int NSLOT = 2048;                  // year 12: slots of rows whose largest precision is kept in LDS
+constexpr int NSUB = 4096;                   // chunks per slot at most: NSLOT * NSUB * AWG rows >= 2^31
+
+struct RecallPoints11 { double v[NPV]; };
+
+__global__ __launch_bounds__(WG) void k_eval_match_voc(
+    const float* __restrict__ score, const int* __restrict__ cls, const float4* __restrict__ box,
+    const uint8_t* __restrict__ keep, int A, const int* __restrict__ gt_cls, const double* __restrict__ gt_box,
+    const int* __restrict__ gt_off, const uint8_t* __restrict__ gt_difficult, double iou_thresh, int max_dets,
+    int* __restrict__ n_det, float* __restrict__ det_score, int* __restrict__ det_cls, float4* __restrict__ det_box,
+    uint8_t* __restrict__ det_flags, int* __restrict__ det_gt) {
+    __shared__ unsigned long long s_key[CAP];
+    __shared__ int s_idx[CAP];
+    __shared__ float4 s_dbox[MAXDV];
+    __shared__ int s_dcls[MAXDV];
+    __shared__ int s_danchor[MAXDV];
+    __shared__ int s_jmax[MAXDV];                // box a detection passes the threshold with, -1 none
+    __shared__ double s_gbox[GLV][4];
+    __shared__ int s_gcls[GLV];
+    __shared__ int s_first[GLV];                 // lowest rank among the detections whose jmax is the box
+    __shared__ int s_hist[256];
+    __shared__ int s_wave[WG / 64];
+    __shared__ int s_misc[4];
+
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t off = (size_t)b * A;
+    const float* sc = score + off;
+    const uint8_t* kp = keep + off;
+
+    const int nd = select_ranked(sc, kp, A, max_dets, s_key, s_idx, s_hist, s_wave, s_misc, s_danchor);
+    const int g0 = gt_off[b];
+    const int G = max(gt_off[b + 1] - g0, 0);
+    const bool cached = G <= GLV;
+    // the detections: outputs fully written (slots at or beyond nd: score 0, class -1, box 0)
+    if (tid < max_dets) {
+        const size_t o = (size_t)b * max_dets + tid;
+        float s = 0.f;
+        int c = -1;
+        float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < nd) {
+            const int a = s_danchor[tid];
+            s = sc[a];
+            c = cls[off + a];
+            bx = box[off + a];
+            s_dcls[tid] = c;
+            s_dbox[tid] = bx;
+        }
+        det_score[o] = s;
+        det_cls[o] = c;
+        det_box[o] = bx;
+    }
+    if (tid == 0) n_det[b] = nd;
+    if (cached && tid < G) {
+        s_gcls[tid] = gt_cls[g0 + tid];
+        s_first[tid] = INT_MAX;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s_gbox[tid][e] = gt_box[4 * (size_t)(g0 + tid) + e];
+    }
+    __syncthreads();
+    // (ovmax, jmax): ascending j and >, so the first index wins among equal IoUs
+    int jm = -1;
+    if (tid < nd) {
+        const int c = s_dcls[tid];
+        const float4 d = s_dbox[tid];
+        double best = -1.0;
+        int bj = -1;
+        if (cached) {
+            for (int j = 0; j < G; ++j) {
+                if (s_gcls[j] != c) continue;
+                const double v = iou_f64(d, s_gbox[j][0], s_gbox[j][1], s_gbox[j][2], s_gbox[j][3]);
+                if (v > best) { best = v; bj = j; }
+            }
+        } else {
+            for (int j = 0; j < G; ++j) {
+                if (gt_cls[g0 + j] != c) continue;
+                const double* g = gt_box + 4 * (size_t)(g0 + j);
+                const double v = iou_f64(d, g[0], g[1], g[2], g[3]);
+                if (v > best) { best = v; bj = j; }
+            }
+        }
+        jm = (bj >= 0 && best >= iou_thresh) ? bj : -1;
+        s_jmax[tid] = jm;
+        if (cached && jm >= 0) atomicMin(&s_first[jm], tid);
+    }
+    __syncthreads();
+    if (tid < max_dets) {
+        unsigned f = 0u;
+        if (jm >= 0) {
+            if (gt_difficult && gt_difficult[g0 + jm]) {
+                f = 2u;
+            } else if (cached) {
+                f = s_first[jm] == tid ? 1u : 0u;
+            } else {
+                bool dup = false;                    // an earlier detection with the same box?
+                for (int r = 0; r < tid && !dup; ++r) dup = s_jmax[r] == jm;
+                f = dup ? 0u : 1u;
+            }
+        }
+        const size_t o = (size_t)b * max_dets + tid;
+        det_flags[o] = (uint8_t)f;
+        det_gt[o] = jm;
+    }
+}
+
+// AP of one class.  flags: every detection of the data set, sorted (bit 0 true positive, bit 1 ignored: neither count);
+// seg_off[c] .. seg_off[c+1] the class's rows.  Any segment length.
+__global__ __launch_bounds__(AWG) void k_eval_ap_voc(const uint8_t* __restrict__ flags, const int* __restrict__ seg_off,
+                                                    const int* __restrict__ n_pos, int year, RecallPoints11 pts,
+                                                    double* __restrict__ ap) {
+    __shared__ unsigned long long s_slot[NSLOT];     // year 12: bits of the largest precision in a slot, then of the suffix
+    __shared__ unsigned long long s_sub[NSUB];       // the same per chunk inside the current slot (slots of several chunks)
+    __shared__ unsigned long long s_best[NPV];       // year 7: bits of the best precision whose last recall point <= recall is k
+    __shared__ double s_pts[NPV];
+    __shared__ double s_term[AWG];
+    __shared__ double s_wmax[AWG / 64];
+    __shared__ int s_wtot[AWG / 64][2];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int npos = n_pos[c];
+    const long long lo = seg_off[c], hi = seg_off[c + 1];
+    if (npos <= 0 || hi <= lo) {                     // not part of the mean (the caller excludes it), or no detection
+        if (tid == 0) ap[c] = 0.0;
+        return;
+    }
+    const double dnpos = (double)npos;
+    const long long nchunk = (hi - lo + AWG - 1) / AWG;
+    const long long cps = (nchunk + NSLOT - 1) / NSLOT;      // chunks per slot
+    const int nslot = (int)((nchunk + cps - 1) / cps);
+    if (year == 7) {
+        if (tid < NPV) s_best[tid] = 0ull;
+        if (tid == 0) {                              // constant indices: a lane-indexed read would copy the argument to scratch
+#pragma unroll
+            for (int k = 0; k < NPV; ++k) s_pts[k] = pts.v[k];
+        }
+    } else {
+        for (int i = tid; i < nslot; i += AWG) s_slot[i] = 0ull;
+    }
+    __syncthreads();
+    // one chunk: the row's kind and its inclusive counts of true and false positives; the carries move on
+    int carry_tp = 0, carry_fp = 0;
+    auto scan = [&](long long i0, bool& is_tp, int& ctp, int& cfp) {
+        const long long i = i0 + tid;
+        const unsigned f = i < hi ? (unsigned)flags[i] & 3u : 2u;
+        is_tp = f == 1u;
+        const unsigned long long mt = __ballot(is_tp), mf = __ballot(f == 0u);
+        const unsigned long long upto = (2ull << lane) - 1ull;
+        ctp = __popcll(mt & upto);
+        cfp = __popcll(mf & upto);
+        __syncthreads();
+        if (lane == 0) { s_wtot[wave][0] = __popcll(mt); s_wtot[wave][1] = __popcll(mf); }
+        __syncthreads();
+        int tot_tp = 0, tot_fp = 0;
+#pragma unroll
+        for (int w = 0; w < AWG / 64; ++w) {
+            const int vt = s_wtot[w][0], vf = s_wtot[w][1];
+            if (w < wave) { ctp += vt; cfp += vf; }
+            tot_tp += vt;
+            tot_fp += vf;
+        }
+        ctp += carry_tp;
+        cfp += carry_fp;
+        carry_tp += tot_tp;
+        carry_fp += tot_fp;
+    };
+    // first pass: year 7 the bucket maxima, year 12 the slot maxima
+    for (long long ch = 0; ch < nchunk; ++ch) {
+        bool is_tp;
+        int ctp, cfp;
+        scan(lo + ch * AWG, is_tp, ctp, cfp);
+        if (!is_tp) continue;
+        const double prec = (double)ctp / (double)(ctp + cfp);
+        if (year == 7) {
+            const double rec = (double)ctp / dnpos;
+            int a = -1;                              // last k with pts[k] <= rec (none when pts[0] > rec)
+            for (int k = 0; k < NPV; ++k) a = s_pts[k] <= rec ? k : a;
+            if (a >= 0) atomicMax(&s_best[a], (unsigned long long)__double_as_longlong(prec));
+        } else {
+            atomicMax(&s_slot[ch / cps], (unsigned long long)__double_as_longlong(prec));
+        }
+    }
+    __syncthreads();
+    if (year == 7) {
+        if (tid == 0) {                              // envelope = suffix maximum over the buckets; the points added in order
+            unsigned long long run = 0ull;
+            for (int k = NPV - 1; k >= 0; --k) {
+                run = s_best[k] > run ? s_best[k] : run;
+                s_best[k] = run;
+            }
+            double res = 0.0;
+            for (int k = 0; k < NPV; ++k) res += __longlong_as_double((long long)s_best[k]);
+            ap[c] = res / 11.0;
+        }
+        return;
+    }
+    if (tid == 0) {                                  // s_slot[s] = largest precision in slot s or any later one
+        unsigned long long run = 0ull;
+        for (int k = nslot - 1; k >= 0; --k) {
+            run = s_slot[k] > run ? s_slot[k] : run;
+            s_slot[k] = run;
+        }
+    }
+    __syncthreads();
+    carry_tp = carry_fp = 0;
+    double acc = 0.0;                                // thread 0's
+    for (int sl = 0; sl < nslot; ++sl) {
+        const long long ch0 = (long long)sl * cps, ch1 = ch0 + cps < nchunk ? ch0 + cps : nchunk;
+        const int nsub = (int)(ch1 - ch0);
+        if (nsub > 1) {                              // the chunk maxima inside the slot, then their suffix
+            const int keep_tp = carry_tp, keep_fp = carry_fp;
+            for (int i = tid; i < nsub; i += AWG) s_sub[i] = 0ull;
+            __syncthreads();
+            for (long long ch = ch0; ch < ch1; ++ch) {
+                bool is_tp;
+                int ctp, cfp;
+                scan(lo + ch * AWG, is_tp, ctp, cfp);
+                if (is_tp)
+                    atomicMax(&s_sub[ch - ch0], (unsigned long long)__double_as_longlong((double)ctp / (double)(ctp + cfp)));
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned long long run = 0ull;
+                for (int k = nsub - 1; k >= 0; --k) {
+                    run = s_sub[k] > run ? s_sub[k] : run;
+                    s_sub[k] = run;
+                }
+            }
+            __syncthreads();
+            carry_tp = keep_tp;
+            carry_fp = keep_fp;
+        }
+        const unsigned long long after_slot = sl + 1 < nslot ? s_slot[sl + 1] : 0ull;
+        for (long long ch = ch0; ch < ch1; ++ch) {
+            const int first_tp = carry_tp;
+            bool is_tp;
+            int ctp, cfp;
+            scan(lo + ch * AWG, is_tp, ctp, cfp);
+            // largest precision at or after the row: inside the wave, the later waves, the later chunks and slots
+            double v = is_tp ? (double)ctp / (double)(ctp + cfp) : 0.0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const double o = __shfl_down(v, d);
+                if (lane + d < 64 && o > v) v = o;
+            }
+            if (lane == 0) s_wmax[wave] = v;
+            __syncthreads();
+#pragma unroll
+            for (int w = 1; w < AWG / 64; ++w)
+                if (w > wave && s_wmax[w] > v) v = s_wmax[w];
+            unsigned long long later = after_slot;
+            if (ch + 1 < ch1 && s_sub[ch + 1 - ch0] > later) later = s_sub[ch + 1 - ch0];
+            const double tail = __longlong_as_double((long long)later);
+            if (tail > v) v = tail;
+            if (is_tp) s_term[ctp - first_tp - 1] = ((double)ctp / dnpos - (double)(ctp - 1) / dnpos) * v;
+            __syncthreads();
+            if (tid == 0) {
+                const int n = carry_tp - first_tp;
+                for (int k = 0; k < n; ++k) acc += s_term[k];
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) ap[c] = acc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -874,6 +1084,32 @@ int ssd_eval_ap_coco(const uint16_t* tp_sorted, const uint16_t* ig_sorted, const
     for (int k = 0; k < NP; ++k) pts.v[k] = recall_points[k];
     hipLaunchKernelGGL(k_eval_ap_coco, dim3(C, NA), dim3(AWG), 0, (hipStream_t)stream, tp_sorted, ig_sorted, pos_sorted, seg_off,
                        n_gt, C, max_dets, pts, ap, tp_count);
+    return ssd_launch_status();
+}
+
+int ssd_eval_voc_max_dets(void) { return MAXDV; }
+
+int ssd_eval_match_voc(const float* score, const int32_t* cls, const float* box, const uint8_t* keep, int B, int A,
+                       const int32_t* gt_cls, const double* gt_box, const int32_t* gt_off, const uint8_t* gt_difficult,
+                       double iou_thresh, int max_dets, int32_t* n_det, float* det_score, int32_t* det_cls, float* det_box,
+                       uint8_t* det_flags, int32_t* det_gt, void* stream) {
+    if (B <= 0 || A <= 0 || max_dets <= 0 || max_dets > MAXDV) return SSD_ERR_VALUE;
+    if (!(iou_thresh > 0.0) || !(iou_thresh <= DBL_MAX)) return SSD_ERR_VALUE;
+    if (!score || !cls || !box || !keep || !gt_off) return SSD_ERR_VALUE;
+    if (!n_det || !det_score || !det_cls || !det_box || !det_flags || !det_gt) return SSD_ERR_VALUE;
+    hipLaunchKernelGGL(k_eval_match_voc, dim3(B), dim3(WG), 0, (hipStream_t)stream, score, cls,
+                       reinterpret_cast<const float4*>(box), keep, A, gt_cls, gt_box, gt_off, gt_difficult, iou_thresh, max_dets,
+                       n_det, det_score, det_cls, reinterpret_cast<float4*>(det_box), det_flags, det_gt);
+    return ssd_launch_status();
+}
+
+int ssd_eval_ap_voc(const uint8_t* flags_sorted, const int32_t* seg_off, const int32_t* n_pos, int C, int year,
+                    const double* recall_points, double* ap, void* stream) {
+    if (C <= 0 || (year != 7 && year != 12)) return SSD_ERR_VALUE;
+    if (!flags_sorted || !seg_off || !n_pos || !recall_points || !ap) return SSD_ERR_VALUE;
+    RecallPoints11 pts;
+    for (int k = 0; k < NPV; ++k) pts.v[k] = recall_points[k];
+    hipLaunchKernelGGL(k_eval_ap_voc, dim3(C), dim3(AWG), 0, (hipStream_t)stream, flags_sorted, seg_off, n_pos, year, pts, ap);
     return ssd_launch_status();
 }
 

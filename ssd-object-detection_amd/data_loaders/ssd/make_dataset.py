@@ -19,7 +19,11 @@ The model consumes only this contract.  Sources:
                        scikit-image), through the same seam.  decode="device" (the default): the samples carry the files'
                        bytes (ops.EncodedImage) and the model decodes whole batches, Huffman on host threads and the rest on
                        the device; decode="host": Pillow decodes each file as it is read.
-Any other name raises ValueError, as the reference does (:33)."""
+  dataset="pascal_voc": data_loaders.voc.VOCDataLoader on dataset_root (a VOCdevkit tree, annotations read with
+                       `xml.etree.ElementTree`), through the same seam and with the same `decode`; the samples' fourth element
+                       is the boxes' `difficult` flags.  VOC07+12 trainval and VOC2007 test; for other sets build a
+                       VOCDataLoader and pass it as the reader object.
+Any other name ("voc" among them) raises ValueError, as the reference does (:33)."""
 import numpy as np
 
 from ... import ops
@@ -97,7 +101,7 @@ class SSDDataLoader:
     def __init__(self, dataset_root, dataset="coco", shuffle=True, mini_batch=0, input_size=300, decode="device"):
         """input_size: the network's input (300: the reference's; 512 or 256 for the ResNet-50 SSD512 network).  The synthetic
         splits produce images of that size; reader-contract splits are resized on the device to the model's own input.
-        decode: dataset="coco" only -- "device" or "host" (COCODataLoader's)."""
+        decode: dataset="coco" and "pascal_voc" only -- "device" or "host" (COCODataLoader's / VOCDataLoader's)."""
         if isinstance(input_size, bool) or not isinstance(input_size, (int, np.integer)) or input_size < 1:
             raise ValueError("input_size must be a positive integer, not %r" % (input_size,))
         self._train_resize = (int(input_size), int(input_size))
@@ -124,6 +128,12 @@ class SSDDataLoader:
             from ..coco import COCODataLoader
             reader = COCODataLoader(dataset_root, shuffle=shuffle, mini_batch=mini_batch, decode=decode)
             train, val = reader.get_dataset()                            # mini_batch is the reader's, on both splits (:108)
+            self._train_set, self._val_set = RawSplit(train, 0), RawSplit(val, 0)
+            self._names, self._colors = reader.get_names_and_colors()
+        elif name == "pascal_voc":
+            from ..voc import VOCDataLoader
+            reader = VOCDataLoader(dataset_root, shuffle=shuffle, mini_batch=mini_batch, decode=decode)
+            train, val = reader.get_dataset()                            # mini_batch is the reader's, on both splits
             self._train_set, self._val_set = RawSplit(train, 0), RawSplit(val, 0)
             self._names, self._colors = reader.get_names_and_colors()
         else:

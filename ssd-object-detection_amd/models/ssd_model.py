@@ -64,11 +64,12 @@ class SSDObjectDetectionModel:
             # max_dets=100, num_data=0, precision="bf16"); missing keys take these defaults.  After every `every`-th epoch
             # the validation split (its first num_data samples if > 0) is evaluated with metric="device".  An optional key
             # scoring="best" | "all" (evaluate()'s; absent = "best") is kept only when given, and so is protocol="map" | "coco"
-            # (evaluate()'s; absent = "map": val/mAP, val/AP50, val/AP75; "coco": COCO's twelve values)
+            # (evaluate()'s; absent = "map": val/mAP, val/AP50, val/AP75; "coco": COCO's twelve values) | "voc07" | "voc12"
+            # (PASCAL VOC's mAP: val/mAP only)
             if val is not None and val.get("scoring", "best") not in ("best", "all"):
                 raise ValueError("val['scoring'] must be 'best' or 'all', not %r" % (val["scoring"],))
-            if val is not None and val.get("protocol", "map") not in ("map", "coco"):
-                raise ValueError("val['protocol'] must be 'map' or 'coco', not %r" % (val["protocol"],))
+            if val is not None and val.get("protocol", "map") not in ("map", "coco", "voc07", "voc12"):
+                raise ValueError("val['protocol'] must be 'map', 'coco', 'voc07' or 'voc12', not %r" % (val["protocol"],))
             self.val = None if val is None else dict(dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
                                                           max_dets=100, num_data=0, precision="bf16"), **val)
 
@@ -590,6 +591,10 @@ class SSDObjectDetectionModel:
         r = self.evaluate(samples, batch_size=val["batch_size"], score_thresh=val["score_thresh"], iou_thresh=val["iou_thresh"],
                           max_dets=val["max_dets"], precision=val["precision"], metric="device",
                           scoring=val.get("scoring", "best"), protocol=val.get("protocol", "map"))
+        if val.get("protocol", "map") in ("voc07", "voc12"):
+            self._scalars.write_values("val", step, {"mAP": r["mAP"]})
+            logger.info("validation at step %d: %s mAP %.4f", step, val["protocol"], r["mAP"])
+            return r
         if val.get("protocol", "map") == "coco":
             from ..utils.metrics import COCO_SUMMARY_KEYS
             self._scalars.write_values("val", step, {k: r[k] for k in COCO_SUMMARY_KEYS})
@@ -699,8 +704,10 @@ class SSDObjectDetectionModel:
         ops.detect_pairs (keep_top_k = acc.max_dets) go to acc.add as they are -- ssd_eval_match takes any row count, and its
         (score desc, index asc) order is the rows' own.  An accumulator of the COCO protocol (DeviceCocoAccumulator) also gets
         the samples' crowd flags (a fourth element, absent = none) and, for reader-contract samples, the area scale
-        (source width x source height) / (S x S)."""
+        (source width x source height) / (S x S).  An accumulator of the VOC protocol (DeviceVocAccumulator) gets the fourth
+        element as the boxes' `difficult` flags."""
         coco = getattr(acc, "protocol", "map") == "coco"
+        voc = getattr(acc, "protocol", "map") == "voc"
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         if scoring not in ("best", "all"):
@@ -730,6 +737,10 @@ class SSDObjectDetectionModel:
                 crowd, scale = self._coco_batch_extras(buf, raw)
                 acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off),
                         None if crowd is None else self._to_device(crowd), None if scale is None else self._to_device(scale))
+            elif voc:
+                hard = self._coco_batch_extras(buf, False)[0]
+                acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off),
+                        None if hard is None else self._to_device(hard))
             else:
                 acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off))
             buf.clear()
@@ -761,19 +772,26 @@ class SSDObjectDetectionModel:
         protocol="map" (default): the metric above.  protocol="coco": COCO's twelve box metrics (utils.metrics.coco_summary:
         AP, AP50, AP75, AP and AR by area range, AR at 1 / 10 / max_dets detections), with either metric mode; samples may
         carry a fourth element `crowd` (bool [n]); for reader-contract samples areas are in source pixels (area_scale =
-        source width x source height / S^2), for prepared samples in evaluation pixels.  Returns coco_summary's dict.  Any
-        other value raises ValueError."""
+        source width x source height / S^2), for prepared samples in evaluation pixels.  Returns coco_summary's dict.
+        protocol="voc07" | "voc12": PASCAL VOC's mAP at IoU 0.5 (utils.metrics.voc_map: the 11-point metric of VOC2007, or the
+        area under the monotone envelope of VOC2010 onward), with either metric mode; a sample's fourth element is read as the
+        boxes' `difficult` flags -- so a COCO sample's crowd flags are treated as difficult.  Returns voc_map's dict (mAP,
+        per_class, n_pos).  max_dets <= ops.eval_voc_max_dets() with metric="device".  Any other value raises ValueError."""
         from ..utils.metrics import coco_map
-        if protocol not in ("map", "coco"):
-            raise ValueError("protocol must be 'map' or 'coco', not %r" % (protocol,))
+        if protocol not in ("map", "coco", "voc07", "voc12"):
+            raise ValueError("protocol must be 'map', 'coco', 'voc07' or 'voc12', not %r" % (protocol,))
+        voc = protocol in ("voc07", "voc12")
         if precision not in ("bf16", "mxfp8"):
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         if scoring not in ("best", "all"):
             raise ValueError("scoring must be 'best' or 'all', not %r" % (scoring,))
         if metric == "device":
-            from ..utils.device_map import DeviceCocoAccumulator, DeviceMapAccumulator
-            acc = (DeviceCocoAccumulator if protocol == "coco" else DeviceMapAccumulator)(self.cfg.classes - 1, max_dets,
-                                                                                          self.device)
+            from ..utils.device_map import DeviceCocoAccumulator, DeviceMapAccumulator, DeviceVocAccumulator
+            if voc:
+                acc = DeviceVocAccumulator(self.cfg.classes - 1, max_dets, self.device, year=protocol[3:])
+            else:
+                acc = (DeviceCocoAccumulator if protocol == "coco" else DeviceMapAccumulator)(self.cfg.classes - 1, max_dets,
+                                                                                              self.device)
             self.evaluate_into(acc, samples, batch_size, score_thresh, iou_thresh, precision, scoring)
             result = acc.result()
             return (result, acc.detections()) if return_detections else result
@@ -782,7 +800,7 @@ class SSDObjectDetectionModel:
         size = float(self.cfg.input_shape[0])
         raw = bool(getattr(samples, "raw", False))
         dets, gts, buf = [], [], []
-        crowds, scales = [], []                                       # protocol="coco": per image
+        crowds, scales = [], []                                       # protocol="coco": per image; voc: crowds = difficult
 
         def flush():
             if not buf:
@@ -790,6 +808,7 @@ class SSDObjectDetectionModel:
             if protocol == "coco":
                 scale = self._coco_batch_extras(buf, raw)[1]
                 scales.extend([1.0] * len(buf) if scale is None else scale.tolist())
+            if protocol == "coco" or voc:
                 crowds.extend(np.asarray(b[3]).astype(bool).reshape(-1) if len(b) > 3 and b[3] is not None
                               else np.zeros(int(np.shape(b[1])[0]), bool) for b in buf)
             if raw:
@@ -829,6 +848,9 @@ class SSDObjectDetectionModel:
             from ..utils.metrics import coco_summary
             result = coco_summary(dets, [g + (c,) for g, c in zip(gts, crowds)], max_dets=max_dets,
                                   area_scale=np.asarray(scales, np.float64))
+        elif voc:
+            from ..utils.metrics import voc_map
+            result = voc_map(dets, [g + (c,) for g, c in zip(gts, crowds)], year=protocol[3:], max_dets=max_dets)
         else:
             result = coco_map(dets, gts, max_dets=max_dets)
         return (result, dets) if return_detections else result

@@ -914,6 +914,59 @@ def eval_ap_coco(tp_sorted, ig_sorted, pos_sorted, seg_off, n_gt, max_dets=100):
     return ap, tp_count
 
 
+def eval_voc_max_dets():
+    return int(_lib.lib().ssd_eval_voc_max_dets())
+
+
+_EVAL_VOC_RECALL_POINTS = np.arange(11) / 10.0         # utils.metrics.VOC_RECALL_POINTS: passed in, not recomputed
+EvalMatchVoc = collections.namedtuple("EvalMatchVoc", "n_det score cls box flags gt")
+
+
+def eval_match_voc(score, cls, box, keep, gt_cls, gt_box, gt_off, max_dets=100, gt_difficult=None, iou_thresh=0.5):
+    """ssd_eval_match_voc: eval_match's selection, then VOCdevkit's matching at one threshold (utils.metrics.voc_match_image).
+    gt_difficult u8 [total] or None (no difficult box).  Returns EvalMatchVoc(n_det i32 [B], score f32 [B,max_dets], cls i32
+    [B,max_dets], box f32 [B,max_dets,4], flags u8 [B,max_dets]: bit 0 true positive, bit 1 ignored, gt i32 [B,max_dets]: the
+    box of highest IoU as an index into the image's boxes, -1 when that IoU is below iou_thresh)."""
+    L = _lib.lib()
+    B, A = score.shape
+    _dev(score, torch.float32); _dev(cls, torch.int32); _dev(box, torch.float32); _dev(keep, torch.uint8)
+    _dev(gt_cls, torch.int32); _dev(gt_box, torch.float64); _dev(gt_off, torch.int32)
+    assert gt_off.numel() == B + 1 and gt_box.shape[0] == gt_cls.shape[0]
+    if gt_difficult is not None:
+        _dev(gt_difficult, torch.uint8)
+        assert gt_difficult.numel() == gt_cls.numel()
+    max_dets = int(max_dets)
+    dev = score.device
+    md = max(max_dets, 1)
+    n_det = torch.empty((B,), dtype=torch.int32, device=dev)
+    det_score = torch.empty((B, md), dtype=torch.float32, device=dev)
+    det_cls = torch.empty((B, md), dtype=torch.int32, device=dev)
+    det_box = torch.empty((B, md, 4), dtype=torch.float32, device=dev)
+    det_flags = torch.empty((B, md), dtype=torch.uint8, device=dev)
+    det_gt = torch.empty((B, md), dtype=torch.int32, device=dev)
+    _lib.check(L.ssd_eval_match_voc(_ptr(score), _ptr(cls), _ptr(box), _ptr(keep), B, A, _ptr(gt_cls), _ptr(gt_box), _ptr(gt_off),
+                                    _ptr(gt_difficult) if gt_difficult is not None else None, float(iou_thresh), max_dets,
+                                    _ptr(n_det), _ptr(det_score), _ptr(det_cls), _ptr(det_box), _ptr(det_flags), _ptr(det_gt),
+                                    _stream()))
+    return EvalMatchVoc(n_det, det_score, det_cls, det_box, det_flags, det_gt)
+
+
+def eval_ap_voc(flags_sorted, seg_off, n_pos, year="07"):
+    """ssd_eval_ap_voc: flags u8 [N] sorted by (class, score desc, image, rank), seg_off i32 [C+1], n_pos i32 [C] (non-difficult
+    boxes per class), year "07" (11-point) or "12" (area under the monotone envelope) -> AP f64 [C]; 0 where n_pos == 0."""
+    L = _lib.lib()
+    _dev(flags_sorted, torch.uint8); _dev(seg_off, torch.int32); _dev(n_pos, torch.int32)
+    C = n_pos.numel()
+    assert seg_off.numel() == C + 1
+    if flags_sorted.numel() == 0:                      # the entry point wants a pointer even when there is nothing to read
+        flags_sorted = torch.zeros((1,), dtype=torch.uint8, device=n_pos.device)
+    ap = torch.empty((C,), dtype=torch.float64, device=n_pos.device)
+    pts = _EVAL_VOC_RECALL_POINTS.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    _lib.check(L.ssd_eval_ap_voc(_ptr(flags_sorted), _ptr(seg_off), _ptr(n_pos), C, {"07": 7, "12": 12, 7: 7, 12: 12}.get(year, 0),
+                                 pts, _ptr(ap), _stream()))
+    return ap
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution stack (NHWC bf16)
 # ------------------------------------------------------------------------------------------------

@@ -60,7 +60,7 @@ def val_from_config(config):
     enable is false: the default run does not validate, as the reference does not.  The optional key `scoring` ("best": one
     label per anchor, the default when absent; "all": the multi-label detection output, evaluate(scoring="all")) is in the
     dict only when the config gives it, and so is `protocol` ("map", the default when absent: val/mAP, val/AP50, val/AP75;
-    "coco": COCO's twelve box metrics, evaluate(protocol="coco"))."""
+    "coco": COCO's twelve box metrics, evaluate(protocol="coco"); "voc07" / "voc12": PASCAL VOC's mAP, val/mAP only)."""
     section = (config.get("model") or {}).get("eval")
     if not section or not section.get("enable", False):
         return None
@@ -77,8 +77,8 @@ def val_from_config(config):
             raise ValueError("model.eval.scoring must be 'best' or 'all', not %r" % (section["scoring"],))
         val["scoring"] = str(section["scoring"])
     if "protocol" in section:
-        if section["protocol"] not in ("map", "coco"):
-            raise ValueError("model.eval.protocol must be 'map' or 'coco', not %r" % (section["protocol"],))
+        if section["protocol"] not in ("map", "coco", "voc07", "voc12"):
+            raise ValueError("model.eval.protocol must be 'map', 'coco', 'voc07' or 'voc12', not %r" % (section["protocol"],))
         val["protocol"] = str(section["protocol"])
     return val
 
@@ -195,10 +195,10 @@ def clip_from_config(config):
 
 def decode_from_config(config):
     """`data: decode` ("device" | "host") and `data: decode_workers` (host threads of the JPEG entropy decode) -> (decode,
-    workers); both optional, absent = ("device", 8).  Read only for `dataset: "coco"`: any other dataset gets the defaults
-    whatever the keys say.  ValueError for an unknown mode or a worker count that is not a positive integer."""
+    workers); both optional, absent = ("device", 8).  Read only for `dataset: "coco"` and `"pascal_voc"`: any other dataset gets
+    the defaults whatever the keys say.  ValueError for an unknown mode or a worker count that is not a positive integer."""
     data = config.get("data") or {}
-    if not (isinstance(data.get("dataset"), str) and data["dataset"].lower() == "coco"):
+    if not (isinstance(data.get("dataset"), str) and data["dataset"].lower() in ("coco", "pascal_voc")):
         return "device", 8
     decode, workers = data.get("decode", "device"), data.get("decode_workers", 8)
     if decode not in ("device", "host"):
@@ -266,6 +266,8 @@ def train(config):
         n_cat = len(data.get_names_and_colors()[0])
         if n_cat != data_cfg["num_classes"]:
             raise ValueError("data.num_classes is %r but the annotation files list %d categories" % (data_cfg["num_classes"], n_cat))
+    if isinstance(data_cfg["dataset"], str) and data_cfg["dataset"].lower() == "pascal_voc" and data_cfg["num_classes"] != 20:
+        raise ValueError("data.num_classes is %r but PASCAL VOC has 20 classes" % (data_cfg["num_classes"],))
     model = SSDObjectDetectionModel(classes=data_cfg["num_classes"], log_dir=model_cfg["log_dir"], distributed=world > 1,
                                     l2norm=l2norm_from_config(config), network=network,
                                     fp8_inference=fp8_inference_from_config(config))

@@ -6,12 +6,13 @@ IoU thresholds) behind ssd_score_decode + ssd_nms and keeps its small record ten
 all rows by (class, score desc, image, rank) -- a stable device sort of a 64-bit key over rows that are already in (image,
 rank) order --, runs ssd_eval_ap and reads one [C, 11] table back.  The definition, and the oracle of both kernels, is
 utils.metrics.coco_map.  DeviceCocoAccumulator is the same shape for COCO's twelve metrics (utils.metrics.coco_summary) on
-ssd_eval_match_coco / ssd_eval_ap_coco."""
+ssd_eval_match_coco / ssd_eval_ap_coco, and DeviceVocAccumulator for PASCAL VOC's AP (utils.metrics.voc_map) on
+ssd_eval_match_voc / ssd_eval_ap_voc."""
 import numpy as np
 import torch
 
 from .. import ops
-from .metrics import COCO_AREA_RANGES, coco_summary_from_tables, map_from_ap_table
+from .metrics import COCO_AREA_RANGES, VOC_YEARS, coco_summary_from_tables, map_from_ap_table, voc_result
 
 
 class DeviceMapAccumulator:
@@ -126,3 +127,62 @@ class DeviceCocoAccumulator:
         ap_h = host[:C * 40].reshape(C, 4, 10)                                 # the one device-to-host read
         cnt_h = np.rint(host[C * 40:C * 160]).astype(np.int64).reshape(C, 4, 3, 10)
         return coco_summary_from_tables(ap_h, cnt_h, np.rint(host[C * 160:]).astype(np.int64).reshape(4, C))
+
+
+class DeviceVocAccumulator:
+    """PASCAL VOC's mAP on the device: utils.metrics.voc_map as DeviceMapAccumulator is coco_map.  `add` enqueues one
+    ssd_eval_match_voc launch per batch and nothing synchronises; `result` sorts the rows as DeviceMapAccumulator does, counts
+    the non-difficult boxes per class, runs ssd_eval_ap_voc and reads one table back."""
+    protocol = "voc"
+
+    def __init__(self, classes, max_dets=100, device="cuda", year="07", iou_thresh=0.5):
+        if not 1 <= int(max_dets) <= ops.eval_voc_max_dets():
+            raise ValueError("max_dets must be in 1 .. %d, not %r" % (ops.eval_voc_max_dets(), max_dets))
+        if year not in VOC_YEARS:
+            raise ValueError("year must be '07' or '12', not %r" % (year,))
+        if not (np.isfinite(iou_thresh) and iou_thresh > 0):
+            raise ValueError("iou_thresh must be finite and > 0, not %r" % (iou_thresh,))
+        self.classes, self.max_dets, self.device = int(classes), int(max_dets), torch.device(device)
+        self.year, self.iou_thresh = year, float(iou_thresh)
+        self._records, self._gt_cls, self._gt_difficult = [], [], []
+
+    def add(self, score, cls, box, keep, gt_cls, gt_box, gt_off, gt_difficult=None):
+        """DeviceMapAccumulator.add's batch, and gt_difficult u8 [total] (None: no difficult box).  Enqueue only."""
+        self._records.append(ops.eval_match_voc(score, cls, box, keep, gt_cls, gt_box, gt_off, self.max_dets, gt_difficult,
+                                                self.iou_thresh))
+        self._gt_cls.append(gt_cls)
+        self._gt_difficult.append(torch.zeros_like(gt_cls, dtype=torch.uint8) if gt_difficult is None else gt_difficult)
+
+    def _cat(self, i):
+        return torch.cat([r[i] for r in self._records], 0)
+
+    def detections(self):
+        """Per image (score [k], cls [k], box [k,4]) numpy arrays: the top-max_dets kept detections that were scored."""
+        if not self._records:
+            return []
+        n = self._cat(0).cpu().numpy()
+        score, cls, box = self._cat(1).cpu().numpy(), self._cat(2).cpu().numpy(), self._cat(3).cpu().numpy()
+        return [(score[i, :k].copy(), cls[i, :k].copy(), box[i, :k].copy()) for i, k in enumerate(n)]
+
+    def result(self):
+        """The dict utils.metrics.voc_map returns for the same detections and ground truths."""
+        C, dev = self.classes, self.device
+        if not self._records:
+            return voc_result({}, {})
+        score, cls, flags = self._cat(1).reshape(-1), self._cat(2).reshape(-1), self._cat(4).reshape(-1)
+        # DeviceMapAccumulator's key: (class, score desc), stable over rows in (image, rank) order; empty slots last
+        bits = (score + 0.0).view(torch.int32).to(torch.int64)
+        ordered = torch.where(bits < 0, bits ^ 0x7fffffff, bits)
+        cls_key = torch.where(cls < 0, torch.full_like(cls, C), cls).to(torch.int64)
+        key = (cls_key << 32) | (0x7fffffff - ordered)
+        order = torch.sort(key, stable=True).indices
+        per_class = torch.bincount(cls_key, minlength=C + 1)[:C + 1]
+        seg_off = torch.zeros((C + 1,), dtype=torch.int32, device=dev)
+        seg_off[1:] = torch.cumsum(per_class[:C], 0).to(torch.int32)
+        gt = torch.cat(self._gt_cls, 0).to(torch.int64)
+        gt = gt[(gt >= 0) & (gt < C) & (torch.cat(self._gt_difficult, 0) == 0)]
+        n_pos = torch.bincount(gt, minlength=C)[:C].to(torch.int32)
+        ap = ops.eval_ap_voc(flags[order].contiguous(), seg_off, n_pos, self.year)
+        host = torch.stack([ap, n_pos.to(torch.float64)], 1).cpu().numpy()                  # the one device-to-host read
+        live = np.nonzero(host[:, 1] > 0)[0].tolist()
+        return voc_result({c: host[c, 0] for c in live}, {c: int(host[c, 1]) for c in live})

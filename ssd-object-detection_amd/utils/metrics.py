@@ -8,7 +8,10 @@ right and sampled at the 101 recall points 0, 0.01, ..., 1; AP = mean of the sam
 the classes that have ground truth.  Boxes are (cx, cy, w, h) in any common unit; at most `max_dets` detections per image.
 
 coco_summary (second half of the module) is the full protocol -- area ranges, crowd regions, average recall: COCO's twelve
-columns -- and equals coco_map in mAP / AP50 / AP75 / per_class when no box is crowd."""
+columns -- and equals coco_map in mAP / AP50 / AP75 / per_class when no box is crowd.
+
+voc_map (last part of the module) is PASCAL VOC's protocol instead: one IoU threshold, VOCdevkit's non-greedy matching with
+`difficult` boxes, the 11-point AP of VOC2007 or the area under the envelope of VOC2010 onward."""
 import numpy as np
 
 IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10)
@@ -326,3 +329,129 @@ def coco_summary(detections, ground_truths, max_dets=100, area_ranges=COCO_AREA_
             np.concatenate(pos_rows))
     ap, cnt = coco_tables_from_rows(rows, n_gt, max_dets)
     return coco_summary_from_tables(ap, cnt, n_gt)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# PASCAL VOC: VOCdevkit's VOCevaldet
+# ------------------------------------------------------------------------------------------------------------------------
+VOC_RECALL_POINTS = np.arange(11) / 10.0           # not linspace(0, 1, 11) / arange(0, 1.1, 0.1): those hold 0.30000000000000004
+VOC_YEARS = {"07": 7, "12": 12, 7: 7, 12: 12}
+
+
+def voc_match_image(dscore, dcls, dbox, gcls, gbox, gdifficult=None, iou_thresh=0.5, max_dets=100):
+    """The per-image stage of voc_map (what ssd_eval_match_voc computes).  Returns (score [k], cls [k], box [k,4], tp bool [k],
+    ignored bool [k], gt i32 [k]) for the first max_dets detections by (score desc, index asc): gt = jmax as an index into the
+    image's boxes, -1 when ovmax < iou_thresh (or the class has no box in the image)."""
+    dscore, dcls, dbox = np.asarray(dscore), np.asarray(dcls).astype(int), np.asarray(dbox).reshape(-1, 4)
+    keep = np.argsort(-dscore.astype(np.float64), kind="mergesort")[:max_dets]
+    dscore, dcls, dbox = dscore[keep], dcls[keep], dbox[keep]
+    gcls = np.asarray(gcls).astype(int).reshape(-1)
+    gbox = np.asarray(gbox, np.float64).reshape(-1, 4)
+    hard = np.zeros(len(gcls), bool) if gdifficult is None else np.asarray(gdifficult).astype(bool).reshape(-1)
+    k = len(dscore)
+    tp, ignored, gt = np.zeros(k, bool), np.zeros(k, bool), np.full(k, -1, np.int32)
+    b64 = dbox.astype(np.float64)
+    claimed = np.zeros(len(gcls), bool)
+    for r in range(k):                                                # already in decreasing score order
+        g_idx = np.nonzero(gcls == dcls[r])[0]
+        if not len(g_idx):
+            continue
+        iou = iou_matrix(b64[r:r + 1], gbox[g_idx])[0]
+        j = int(np.argmax(iou))                                       # the first index attaining ovmax
+        if not iou[j] >= iou_thresh:
+            continue
+        gt[r] = g_idx[j]
+        if hard[g_idx[j]]:
+            ignored[r] = True
+        elif not claimed[g_idx[j]]:
+            tp[r] = claimed[g_idx[j]] = True
+    return dscore, dcls, dbox, tp, ignored, gt
+
+
+def voc_ap_from_rows(rows, n_pos, year="07"):
+    """AP per class from matched rows -- the second stage of the device metric (ssd_eval_ap_voc) on the host.
+    rows = (cls [N], score [N], flags [N]) in (image, rank) order, bit 0 of flags = true positive, bit 1 = ignored (such a row
+    counts as neither; it wins over bit 0); n_pos: non-difficult boxes per class, a {class: count} mapping or a 1-D array.
+    Returns {class: AP} for the classes with n_pos > 0."""
+    if year not in VOC_YEARS:
+        raise ValueError("year must be '07' or '12', not %r" % (year,))
+    year = VOC_YEARS[year]
+    cls = np.asarray(rows[0]).astype(int).reshape(-1)
+    score = np.asarray(rows[1], np.float64).reshape(-1)
+    flags = np.asarray(rows[2]).astype(np.int64).reshape(-1)
+    counts = dict(n_pos) if hasattr(n_pos, "items") else {c: int(n) for c, n in enumerate(np.asarray(n_pos).reshape(-1))}
+    out = {}
+    for c in sorted(int(c) for c, n in counts.items() if n > 0):
+        sel = cls == c
+        order = np.argsort(-score[sel], kind="mergesort")             # stable: keeps (image, rank) among equal scores
+        fl = flags[sel][order]
+        ign = (fl & 2) != 0
+        ctp = np.cumsum(((fl & 1) != 0) & ~ign)
+        cfp = np.cumsum(((fl & 1) == 0) & ~ign)
+        recall = ctp / float(counts[c])
+        precision = ctp / np.maximum(ctp + cfp, 1)
+        if year == 7:
+            ap = 0.0
+            for t in VOC_RECALL_POINTS:
+                reached = recall >= t
+                ap += float(precision[reached].max()) if reached.any() else 0.0
+            out[c] = ap / 11.0
+            continue
+        mrec = np.concatenate([[0.0], recall, [1.0]])
+        mpre = np.concatenate([[0.0], precision, [0.0]])
+        mpre = np.maximum.accumulate(mpre[::-1])[::-1]                # monotone from the right
+        ap = 0.0
+        for i in np.nonzero(mrec[1:] != mrec[:-1])[0]:
+            ap += float((mrec[i + 1] - mrec[i]) * mpre[i + 1])
+        out[c] = ap
+    return out
+
+
+def voc_result(per_class, n_pos):
+    """voc_map's result dict from {class: AP} and the per-class counts of non-difficult boxes."""
+    per_class = {int(c): float(v) for c, v in sorted(per_class.items())}
+    mean = 0.0
+    for v in per_class.values():
+        mean += v
+    return dict(mAP=mean / len(per_class) if per_class else 0.0, per_class=per_class,
+                n_pos={int(c): int(n) for c, n in sorted(dict(n_pos).items())})
+
+
+def voc_map(detections, ground_truths, year="07", iou_thresh=0.5, max_dets=100):
+    """PASCAL VOC detection mAP: a plain numpy restatement of the published VOCdevkit procedure (VOCevaldet).  The devkit was
+    not available to compare against, so this definition is unpinned: it follows the published description, not a run of that
+    code.
+
+    detections: per image (score [k], cls [k], box [k,4]), as for coco_map; ground_truths: per image (cls [n], box [n,4][,
+    difficult bool [n]]); boxes (cx, cy, w, h) in any common unit.  Returns dict(mAP, per_class={cls: AP}, n_pos={cls: count}).
+
+    Per image the first max_dets detections by (score desc, index asc) are scored.  Per detection, among ALL boxes of its class
+    in its image -- claimed or not, difficult ones included -- ovmax is the highest IoU and jmax the first index attaining it.
+    IoU is iou_matrix: float64 over continuous coordinates.  VOCdevkit's `+1` pixel convention (widths as xmax - xmin + 1 of
+    integer pixel indices) is NOT applied, because boxes here live in network-input coordinates, not on a pixel grid.  When
+    ovmax >= iou_thresh (inclusive, as the devkit's): the detection is ignored if box jmax is difficult; else a true positive
+    if no earlier detection of the image has the same jmax with its own ovmax >= iou_thresh; else a false positive -- a
+    duplicate, even where a second box would also pass, which is where this differs from coco_map's greedy rule.  Otherwise
+    it is a false positive.  n_pos[c] counts the non-difficult boxes of class c; classes with n_pos == 0 are left out of the
+    mean and of per_class.  Per class the rows are sorted by (score desc, image asc, rank asc); ignored rows add to neither
+    count; recall = ctp / n_pos, precision = ctp / max(ctp + cfp, 1).
+    year="07": AP = (sum over k = 0..10, in that order, of max{precision[i] : recall[i] >= k / 10.0}, 0 where none) / 11.0.
+    year="12": mrec = [0, recall, 1], mpre = [0, precision, 0] made monotone from the right; AP = the sum in index order of
+    (mrec[i+1] - mrec[i]) * mpre[i+1] where mrec[i+1] != mrec[i].  mAP sums the classes in ascending order."""
+    if year not in VOC_YEARS:
+        raise ValueError("year must be '07' or '12', not %r" % (year,))
+    if not (np.isfinite(iou_thresh) and iou_thresh > 0):
+        raise ValueError("iou_thresh must be finite and > 0, not %r" % (iou_thresh,))
+    n_pos = {}
+    for g in ground_truths:
+        gc = np.asarray(g[0]).astype(int).reshape(-1)
+        hard = np.zeros(len(gc), bool) if len(g) < 3 or g[2] is None else np.asarray(g[2]).astype(bool).reshape(-1)
+        for c in gc[~hard]:
+            n_pos[int(c)] = n_pos.get(int(c), 0) + 1
+    cls_rows, score_rows, flag_rows = [np.zeros(0, int)], [np.zeros(0)], [np.zeros(0, np.uint8)]
+    for i, (dscore, dcls, dbox) in enumerate(detections):
+        g = ground_truths[i]
+        s, c, _, tp, ign, _ = voc_match_image(dscore, dcls, dbox, g[0], g[1], g[2] if len(g) > 2 else None, iou_thresh, max_dets)
+        cls_rows.append(c); score_rows.append(s); flag_rows.append(tp.astype(np.uint8) | (ign.astype(np.uint8) << 1))
+    rows = (np.concatenate(cls_rows), np.concatenate(score_rows), np.concatenate(flag_rows))
+    return voc_result(voc_ap_from_rows(rows, n_pos, year), n_pos)
