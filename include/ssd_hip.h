@@ -223,6 +223,50 @@ int ssd_multibox_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype
                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Softmax focal loss (Lin et al. 2017, "Focal Loss for Dense Object Detection", over the network's C softmax logits),
+ * forward + backward.  Opt-in, no reference counterpart.  Inputs as ssd_multibox_loss_fwd_bwd; nothing is mined: every anchor
+ * stays in the classification term, weighted by (1 - p_t)^gamma.  Per anchor a, with t = gt_cls[a] where gt_mask[a] and C-1
+ * elsewhere (gt_cls is not read on unmasked anchors), m = max_j z_j, e_j = exp(z_j - m), S = sum_j e_j, p_j = e_j / S:
+ *   q = (sum_{j != t} e_j) / S  (= 1 - p_t, never evaluated as that difference);
+ *   log p_t = log1p(-q) where q < 0.5, (z_t - m) - log S elsewhere (neither cancels on a confident row)
+ *   FL(a) = -alpha_t * q^gamma * log p_t;  alpha_t = alpha for t != C-1, 1 - alpha for the background; alpha == -1: alpha_t = 1
+ *   P = number of positives;  L_pos = sum_pos FL / P;  L_neg = sum_{not pos} FL / P;
+ *   L_loc = loc_weight * sum_pos sum_4 smoothL1(loc - gt_loc) / P
+ *   dconf[a, j] = grad_scale / P * alpha_t * (delta_tj - p_j) * (gamma * p_t * q^(gamma-1) * log p_t - q^gamma), evaluated in
+ *             a form that is finite at q == 0, where FL and the row are 0
+ *   dloc      ssd_multibox_loss_fwd_bwd's, bit for bit on the same inputs (one device function);  every element of both
+ *             gradients is written
+ *   out8      float[8]: L_loc, L_pos, L_neg, (L_loc + L_pos) + L_neg, P, N = B*A - P, 0, status (0 ok; 1 = P == 0: scalars 0,
+ *             gradients exact zeros, the rows form has every count 0 and every row_of_pixel -1; 3 = a logit or a positive's
+ *             offsets were NaN / Inf, reported first)
+ *   gamma     finite, in [0, 8]; alpha in [0, 1] or -1; loc_weight finite and >= 0, grad_scale finite: SSD_ERR_VALUE
+ *             otherwise, as for a NULL pointer, a dtype that is neither SSD_F32 nor SSD_BF16, B <= 0, A <= 0 or C < 2
+ *   C         <= SSD_LOSS_MAX_CLASSES (a block of 128 logit rows as f32 in LDS): SSD_ERR_UNSUPPORTED beyond.  No bound on A:
+ *             there is no per-image select
+ *   ws        >= ssd_softmax_focal_loss_workspace_bytes(B, A, C) bytes (SSD_ERR_WORKSPACE otherwise); needs NO initial
+ *             contents, no atomics
+ * Every refusal happens on the host before anything is launched.  Three launches: the count of positives, one streaming pass
+ * that reads each logit row once and writes its gradient once, the scalars.  Deterministic: integer counts and fixed-order
+ * f64 sums of per-block partials.  fp32 losses agree with a float64 evaluation to <= 1e-4 relative, f32 dconf elementwise to
+ * 1e-4 relative.
+ * The _heads form hands the gradient over as the rows of ssd_loss_fwd_bwd_heads (same struct, same channel order and zero
+ * padding, same refusals for `hg`; SSD_ERR_ASSERT when the levels do not sum to A).  Every anchor carries a gradient, so every
+ * pixel is a row: row r of level l is pixel r, both maps are the identity and count[l] = B * hw[l] (the sparse head kernels
+ * serve full density as they are).  dtype SSD_BF16 only (SSD_F32: SSD_ERR_UNSUPPORTED); scattered back, the rows are
+ * bit-identical to the dense form's dconf / dloc.
+ * ---------------------------------------------------------------------------------------- */
+size_t ssd_softmax_focal_loss_workspace_bytes(int B, int A, int C);
+int ssd_softmax_focal_loss_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                   const uint8_t* gt_mask, int B, int A, int C, float gamma, float alpha, float loc_weight,
+                                   float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
+                                   void* stream);
+size_t ssd_softmax_focal_loss_heads_workspace_bytes(int B, int A, int C);
+int ssd_softmax_focal_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                         const uint8_t* gt_mask, int B, int A, int C, float gamma, float alpha,
+                                         float loc_weight, float grad_scale, float* out8, const ssd_head_grads* hg, void* ws,
+                                         size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inference scoring + decode -- replaces the scoring half of SSDObjectDetectionModel.visualize
  * (models/ssd_model.py:479-488, mask=None branch) and the box decode of visualize_dataset (:466-467).
  *   conf [B*A*C], loc [B*A*4] (SSD_F32 / SSD_BF16), priors double[A*4]

@@ -19,6 +19,7 @@
 #include <cmath>
 #include "conv_common.h"
 #include "rowblock.h"
+#include "boxterm.h"
 
 namespace {
 
@@ -90,44 +91,6 @@ struct MbLevels {                            // the rows form's geometry (levels
     int* count;                              // [SSD_MAX_LEVELS]
 };
 
-// Fixed-order workgroup sums (NW waves).  The leading barrier also orders earlier LDS traffic.
-template <int NW>
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int lo = __shfl_xor(__double2loint(v), off);
-        const int hi = __shfl_xor(__double2hiint(v), off);
-        v += __hiloint2double(hi, lo);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) t += s_red[k];
-    return t;
-}
-
-template <int NW>
-__device__ __forceinline__ int block_sum_int(int v, int* s_red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) t += s_red[k];
-    return t;
-}
-
-__device__ __forceinline__ float smooth_l1(float d) {
-    const float a = fabsf(d);
-    return a < 1.f ? 0.5f * d * d : a - 0.5f;
-}
-
-__device__ __forceinline__ float clamp1(float d) { return fminf(fmaxf(d, -1.f), 1.f); }
-
 // the one predicate every kernel uses for "anchor is a mined negative of its image" (the anchor is not a positive)
 __device__ __forceinline__ bool mined_neg(float key, float tau, int mined) { return mined != 0 && key >= tau; }
 
@@ -198,10 +161,7 @@ __global__ __launch_bounds__(WG) void k_mb_rows(const T* __restrict__ conf, cons
                 if (!(fabsf(lse) < INFINITY)) acc_pos = (double)NAN;
                 if (mask[g] != 0) {
                     acc_pos += (double)((m - z[cls[g]]) + logs);
-                    const float4 gl = reinterpret_cast<const float4*>(gloc)[g];
-                    const T* pl = loc + 4 * g;
-                    acc_sl1 = (double)smooth_l1(to_f32<T>(pl[0]) - gl.x) + (double)smooth_l1(to_f32<T>(pl[1]) - gl.y) +
-                              (double)smooth_l1(to_f32<T>(pl[2]) - gl.z) + (double)smooth_l1(to_f32<T>(pl[3]) - gl.w);
+                    acc_sl1 = box_loss<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g]);
                 }
             }
         }
@@ -411,7 +371,7 @@ __global__ __launch_bounds__(WG) void k_mb_grad(const T* __restrict__ conf, cons
     const int nrow = (int)min((size_t)ROWS, p.n - row0);
     const int P = mb_total_pos(w, p.B, s_redi);
     const float sc = P > 0 ? p.grad_scale / (float)P : 0.f;
-    const float sl = P > 0 ? p.grad_scale * p.alpha / (float)P : 0.f;
+    const float sl = box_scale(p.grad_scale, p.alpha, P);
 
     for (int i = threadIdx.x; i < (ROWS * C + 3) / 4; i += WG)
         reinterpret_cast<float4*>(s_g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -432,42 +392,13 @@ __global__ __launch_bounds__(WG) void k_mb_grad(const T* __restrict__ conf, cons
         }
         if (half == 0) {
             float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pos) {
-                const float4 gl = reinterpret_cast<const float4*>(gloc)[g];
-                const T* pl = loc + 4 * g;
-                d.x = sl * clamp1(to_f32<T>(pl[0]) - gl.x);
-                d.y = sl * clamp1(to_f32<T>(pl[1]) - gl.y);
-                d.z = sl * clamp1(to_f32<T>(pl[2]) - gl.z);
-                d.w = sl * clamp1(to_f32<T>(pl[3]) - gl.w);
-            }
+            if (pos) d = box_grad<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl);
             T* o = dloc + 4 * g;
             o[0] = from_f32<T>(d.x); o[1] = from_f32<T>(d.y); o[2] = from_f32<T>(d.z); o[3] = from_f32<T>(d.w);
         }
     }
     __syncthreads();
-    // coalesced store of the gradient block
-    T* dst = dconf + row0 * C;
-    const size_t count = (size_t)nrow * C;
-    if constexpr (sizeof(T) == 4) {
-        const size_t nvec = count / 4;
-        for (size_t i = threadIdx.x; i < nvec; i += WG)
-            reinterpret_cast<float4*>(dst)[i] = *reinterpret_cast<const float4*>(s_g + 4 * i);
-        for (size_t i = nvec * 4 + threadIdx.x; i < count; i += WG) dst[i] = s_g[i];
-    } else {
-        const size_t nvec = count / 8;
-        for (size_t i = threadIdx.x; i < nvec; i += WG) {
-            const float* f = s_g + 8 * i;
-            unsigned wds[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const __hip_bfloat16 a = __float2bfloat16(f[2 * k]), b2 = __float2bfloat16(f[2 * k + 1]);
-                wds[k] = (unsigned)(*reinterpret_cast<const unsigned short*>(&a)) |
-                         ((unsigned)(*reinterpret_cast<const unsigned short*>(&b2)) << 16);
-            }
-            reinterpret_cast<uint4*>(dst)[i] = make_uint4(wds[0], wds[1], wds[2], wds[3]);
-        }
-        for (size_t i = nvec * 8 + threadIdx.x; i < count; i += WG) dst[i] = from_f32<T>(s_g[i]);
-    }
+    store_block<T>(dconf + row0 * C, s_g, (size_t)nrow * C);   // coalesced store of the gradient block
     if (blockIdx.x == 0) mb_scalars(w, p, P, out, s_redi, s_redd);
 }
 
@@ -535,7 +466,7 @@ __global__ __launch_bounds__(WG) void k_mb_grad_rows(const __hip_bfloat16* __res
     const int nrow = (int)min((size_t)ROWS, p.n - row0);
     const int P = mb_total_pos(w, p.B, s_redi);
     const float sc = P > 0 ? p.grad_scale / (float)P : 0.f;
-    const float sl = P > 0 ? p.grad_scale * p.alpha / (float)P : 0.f;
+    const float sl = box_scale(p.grad_scale, p.alpha, P);
     const int r = threadIdx.x >> 1, half = threadIdx.x & 1;
     if (r < nrow) {
         const size_t g = row0 + r;
@@ -558,13 +489,9 @@ __global__ __launch_bounds__(WG) void k_mb_grad_rows(const __hip_bfloat16* __res
                 const int k0 = half ? (C + 1) / 2 : 0, k1 = half ? C : (C + 1) / 2;
                 for (int k = k0; k < k1; ++k) o[k] = from_f32<T>((__expf(to_f32<T>(z[k]) - lse) - (k == label ? 1.f : 0.f)) * sc);
                 if (pos && half == 0) {
-                    const float4 gl = reinterpret_cast<const float4*>(gloc)[g];
-                    const T* pl = loc + 4 * g;
+                    const float4 dl = box_grad<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl);
                     T* ol = d + slot * 4;
-                    ol[0] = from_f32<T>(sl * clamp1(to_f32<T>(pl[0]) - gl.x));
-                    ol[1] = from_f32<T>(sl * clamp1(to_f32<T>(pl[1]) - gl.y));
-                    ol[2] = from_f32<T>(sl * clamp1(to_f32<T>(pl[2]) - gl.z));
-                    ol[3] = from_f32<T>(sl * clamp1(to_f32<T>(pl[3]) - gl.w));
+                    ol[0] = from_f32<T>(dl.x); ol[1] = from_f32<T>(dl.y); ol[2] = from_f32<T>(dl.z); ol[3] = from_f32<T>(dl.w);
                 }
             }
         }

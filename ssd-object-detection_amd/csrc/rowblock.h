@@ -98,3 +98,59 @@ __device__ __forceinline__ void stage_store(const T* __restrict__ src, size_t co
     }
     for (size_t i = nvec * PER + threadIdx.x; i < count; i += RB_WG) lds[i] = to_f32<T>(src[i]);   // ragged tail (last block only)
 }
+
+// The way back: `count` contiguous floats of an LDS block to dst (16-byte aligned) as T, coalesced 16 B per lane.
+template <typename T>
+__device__ __forceinline__ void store_block(T* __restrict__ dst, const float* lds, size_t count) {
+    if constexpr (sizeof(T) == 4) {
+        const size_t nvec = count / 4;
+        for (size_t i = threadIdx.x; i < nvec; i += RB_WG)
+            reinterpret_cast<float4*>(dst)[i] = *reinterpret_cast<const float4*>(lds + 4 * i);
+        for (size_t i = nvec * 4 + threadIdx.x; i < count; i += RB_WG) dst[i] = lds[i];
+    } else {
+        const size_t nvec = count / 8;
+        for (size_t i = threadIdx.x; i < nvec; i += RB_WG) {
+            const float* f = lds + 8 * i;
+            unsigned wds[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const __hip_bfloat16 a = __float2bfloat16(f[2 * k]), b2 = __float2bfloat16(f[2 * k + 1]);
+                wds[k] = (unsigned)(*reinterpret_cast<const unsigned short*>(&a)) |
+                         ((unsigned)(*reinterpret_cast<const unsigned short*>(&b2)) << 16);
+            }
+            reinterpret_cast<uint4*>(dst)[i] = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+        }
+        for (size_t i = nvec * 8 + threadIdx.x; i < count; i += RB_WG) dst[i] = from_f32<T>(lds[i]);
+    }
+}
+
+// Fixed-order workgroup sums (NW waves).  The leading barrier also orders earlier LDS traffic.
+template <int NW>
+__device__ __forceinline__ double block_sum(double v, double* s_red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int lo = __shfl_xor(__double2loint(v), off);
+        const int hi = __shfl_xor(__double2hiint(v), off);
+        v += __hiloint2double(hi, lo);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) t += s_red[k];
+    return t;
+}
+
+template <int NW>
+__device__ __forceinline__ int block_sum_int(int v, int* s_red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int t = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) t += s_red[k];
+    return t;
+}

@@ -843,6 +843,25 @@ class SSDEngine:
         self.step_count = 0
         self.refresh_weights(cast=True)
 
+    def set_background_prior(self, pi=0.01):
+        """Start every head's class biases at a foreground prior (Lin et al. 2017, section 4.1, for C softmax logits): for every
+        default box the bias of conf channel C-1 becomes log((C-1)(1-pi)/pi) and the other conf biases 0, so that a head whose
+        filters contribute nothing puts 1 - pi on the background and pi / (C-1) on every class.  Loc biases and all filters
+        keep their bits.  Every copy the forward passes read is refreshed: the bf16 parameters, what is derived from them,
+        and the fp8 operand store where one exists.  pi in (0, 1), else ValueError.
+        Never called implicitly: a focal loss wants it before the first step of a run from scratch."""
+        if isinstance(pi, bool) or not isinstance(pi, (int, float, np.integer, np.floating)) or not 0.0 < pi < 1.0:
+            raise ValueError("pi must be a number in (0, 1), not %r" % (pi,))
+        C = self.classes
+        row = torch.zeros(C, dtype=torch.float32, device=self.device)
+        row[C - 1] = math.log((C - 1) * (1.0 - pi) / pi)
+        for _, bt in self.head_params:
+            cb = bt.parts[1]                                   # "head%d/conf_bias": [per_cell * C], a box's C channels together
+            self.view(cb, self.param).view(-1, C).copy_(row)
+        self.refresh_weights(cast=True)
+        if self.mx_filters.allocated:                          # an fp8 forward has run: its operand store follows param_bf16
+            self._quantize_filters()
+
     def refresh_weights(self, cast=False, tensors=None):
         """bf16 copy (if not already written by the optimizer kernel) + transposed copies for the data gradient.
         tensors=(t0, t1): only the copies of parameter tensors t0..t1-1 (the per-bucket optimizer step)."""

@@ -52,8 +52,9 @@ class SSDObjectDetectionModel:
             self.split_batch_size = split_batch_size
             self.start_epoch = start_epoch                 # > 0: resumed run (no warm-up, epochs start_epoch..epoch-1)
             self.augment = augment                         # ops.AugmentSpec: SSD data augmentation on the device; None = off
-            # the training loss: None / "reference" = the reference's _ssd_loss; "multibox" or an ops.LossSpec = the SSD
-            # paper's loss (per-image mining, smooth L1, every term over P).  ValueError for anything else
+            # the training loss: None / "reference" = the reference's _ssd_loss; "multibox" = the SSD paper's loss (per-image
+            # mining, smooth L1, every term over P); "softmax_focal" = the softmax focal loss over every anchor; or an
+            # ops.LossSpec of either with its parameters.  ValueError for anything else
             self.loss = ops.LossSpec.of(loss)
             # per-tensor clip norm of the gradients (tf.clip_by_norm(g, clip), reference :249); None or 0: no clipping (the
             # clip kernels run with clip = 0: every scale is 1, the norms are still written)
@@ -173,6 +174,13 @@ class SSDObjectDetectionModel:
 
     def get_engine(self):
         return self._engine
+
+    def set_background_prior(self, pi=0.01):
+        """The engine's set_background_prior: every head's conf biases start so that softmax puts 1 - pi on the background
+        (what a focal loss wants before the first step of a run from scratch).  Never called implicitly; tools/train.py calls
+        it for `model.train.loss.background_prior`.  Under data parallelism every rank calls it (the replicas stay identical)."""
+        self._engine.set_background_prior(pi)
+        self._version += 1                           # a cached inference engine was made from the old biases
 
     # ------------------------------------------------------------------ input pipeline (A8)
     def _rank_world(self):
@@ -334,6 +342,14 @@ class SSDObjectDetectionModel:
             else:
                 out, dconf, dloc = ops.multibox_loss(pred_cls, pred_box, gt_cls, gt_box, gt_mask, spec.neg_pos_ratio,
                                                      spec.loc_weight)
+        elif spec is not None and spec.kind == "softmax_focal":
+            if heads is not None:
+                out = ops.softmax_focal_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads, spec.gamma, spec.alpha,
+                                                   spec.loc_weight)
+                dconf = dloc = None
+            else:
+                out, dconf, dloc = ops.softmax_focal_loss(pred_cls, pred_box, gt_cls, gt_box, gt_mask, spec.gamma, spec.alpha,
+                                                          spec.loc_weight)
         elif heads is not None:
             out = ops.ssd_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads)
             dconf = dloc = None

@@ -272,22 +272,31 @@ def ssd_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, grad_scale=1.0, ws=N
 
 class LossSpec:
     """Which training loss a step uses.  kind "reference": the reference's _ssd_loss (ssd_loss / ssd_loss_heads; the other
-    two fields are not used).  kind "multibox": the SSD paper's loss (multibox_loss / multibox_loss_heads) with
-    `neg_pos_ratio` mined negatives per positive, per image, and the box term weighted by `loc_weight`."""
-    KINDS = ("reference", "multibox")
+    fields are not used).  kind "multibox": the SSD paper's loss (multibox_loss / multibox_loss_heads) with
+    `neg_pos_ratio` mined negatives per positive, per image, and the box term weighted by `loc_weight`.  kind
+    "softmax_focal": the softmax focal loss (softmax_focal_loss / softmax_focal_loss_heads) over every anchor with the
+    focusing exponent `gamma` in [0, 8], the class balance `alpha` in [0, 1] (-1: off) and `loc_weight`; it mines nothing."""
+    KINDS = ("reference", "multibox", "softmax_focal")
 
-    def __init__(self, kind="reference", neg_pos_ratio=3, loc_weight=1.0):
+    def __init__(self, kind="reference", neg_pos_ratio=3, loc_weight=1.0, gamma=2.0, alpha=0.25):
         if kind not in self.KINDS:
             raise ValueError("loss kind must be one of %s, not %r" % (", ".join(self.KINDS), kind))
         if isinstance(neg_pos_ratio, bool) or not isinstance(neg_pos_ratio, (int, np.integer)) or neg_pos_ratio < 1:
             raise ValueError("neg_pos_ratio must be an integer >= 1, not %r" % (neg_pos_ratio,))
-        if isinstance(loc_weight, bool) or not isinstance(loc_weight, (int, float, np.integer, np.floating)):
-            raise ValueError("loc_weight must be a number, not %r" % (loc_weight,))
+        for name, value in (("loc_weight", loc_weight), ("gamma", gamma), ("alpha", alpha)):
+            if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a number, not %r" % (name, value))
         if not (np.isfinite(loc_weight) and loc_weight >= 0):
             raise ValueError("loc_weight must be finite and >= 0, not %r" % (loc_weight,))
+        if not (np.isfinite(gamma) and 0 <= gamma <= 8):
+            raise ValueError("gamma must be finite and in [0, 8], not %r" % (gamma,))
+        if not (0 <= alpha <= 1 or alpha == -1):
+            raise ValueError("alpha must be in [0, 1], or -1 for no class balance, not %r" % (alpha,))
         self.kind = kind
         self.neg_pos_ratio = int(neg_pos_ratio)
         self.loc_weight = float(loc_weight)
+        self.gamma = float(gamma)
+        self.alpha = float(alpha)
 
     @classmethod
     def of(cls, loss):
@@ -301,6 +310,8 @@ class LossSpec:
         raise ValueError("loss must be None, a kind name or an ops.LossSpec, not %r" % (loss,))
 
     def __repr__(self):
+        if self.kind == "softmax_focal":
+            return "LossSpec(kind=%r, gamma=%r, alpha=%r, loc_weight=%r)" % (self.kind, self.gamma, self.alpha, self.loc_weight)
         return "LossSpec(kind=%r, neg_pos_ratio=%d, loc_weight=%r)" % (self.kind, self.neg_pos_ratio, self.loc_weight)
 
 
@@ -648,6 +659,56 @@ def multibox_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, neg_pos_ratio=3
     _lib.check(L.ssd_multibox_loss_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A, C,
                                                  spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out),
                                                  ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream()))
+    return out
+
+
+_focal_ws = MatchWorkspace()
+
+
+def _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight):
+    B, A, C = conf.shape
+    assert conf.is_cuda and conf.is_contiguous() and loc.is_contiguous()
+    assert loc.shape == (B, A, 4) and gt_loc.shape == (B, A, 4)
+    assert gt_cls.shape == (B, A) and gt_mask.shape == (B, A)
+    _dev(gt_cls, torch.int32); _dev(gt_loc, torch.float32); _dev(gt_mask, torch.uint8)
+    spec = LossSpec("softmax_focal", loc_weight=loc_weight, gamma=gamma, alpha=alpha)     # ValueError before anything is allocated
+    return B, A, C, spec
+
+
+def softmax_focal_loss(conf, loc, gt_cls, gt_loc, gt_mask, gamma=2.0, alpha=0.25, loc_weight=1.0, grad_scale=1.0, ws=None):
+    """ssd_softmax_focal_loss_fwd_bwd: the softmax focal loss over every anchor (background = class C-1; alpha=-1: no class
+    balance), the MultiBox box term, every term over P, and its gradient.  Arguments as ssd_loss.  Returns (out8 f32[8] device
+    tensor, dconf, dloc); out8 = loc, pos, neg, total, P, N = B*A - P, 0, status."""
+    L = _lib.lib()
+    B, A, C, spec = _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight)
+    assert conf.dtype == loc.dtype and conf.dtype in (torch.float32, torch.bfloat16)
+    dtype = 0 if conf.dtype == torch.float32 else 1
+    out = torch.empty((8,), dtype=torch.float32, device=conf.device)
+    dconf = torch.empty_like(conf)
+    dloc = torch.empty_like(loc)
+    wsobj = ws or _focal_ws
+    wbuf = wsobj.get(L.ssd_softmax_focal_loss_workspace_bytes(B, A, C), conf.device)
+    wsobj.clean_key = None                         # (a buffer shared with ssd_loss_heads no longer holds its zeroed words)
+    _lib.check(L.ssd_softmax_focal_loss_fwd_bwd(_ptr(conf), _ptr(loc), dtype, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A,
+                                                C, spec.gamma, spec.alpha, spec.loc_weight, float(grad_scale), _ptr(out),
+                                                _ptr(dconf), _ptr(dloc), _ptr(wbuf), wbuf.numel(), _stream()))
+    return out, dconf, dloc
+
+
+def softmax_focal_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, gamma=2.0, alpha=0.25, loc_weight=1.0, grad_scale=1.0,
+                             ws=None):
+    """ssd_softmax_focal_loss_fwd_bwd_heads: the loss of softmax_focal_loss with its gradient as per-level pixel rows in `hgb`
+    (HeadGradBuffers; bf16 only): every pixel is a row, the maps are the identity.  Returns out8 (device f32[8])."""
+    L = _lib.lib()
+    B, A, C, spec = _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight)
+    assert conf.dtype == loc.dtype == torch.bfloat16 and hgb.B == B
+    out = torch.empty((8,), dtype=torch.float32, device=conf.device)
+    wsobj = ws or _focal_ws
+    wbuf = wsobj.get(L.ssd_softmax_focal_loss_heads_workspace_bytes(B, A, C), conf.device)
+    wsobj.clean_key = None
+    _lib.check(L.ssd_softmax_focal_loss_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B,
+                                                      A, C, spec.gamma, spec.alpha, spec.loc_weight, float(grad_scale),
+                                                      _ptr(out), ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream()))
     return out
 
 

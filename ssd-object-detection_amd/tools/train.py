@@ -83,21 +83,48 @@ def val_from_config(config):
     return val
 
 
-def loss_from_config(config):
-    """`model: train: loss: {kind, neg_pos_ratio, loc_weight}` (no reference counterpart) -> ops.LossSpec, or None when the
-    section is absent: the default run trains with the reference's loss.  kind "multibox" is the SSD paper's loss;
-    ValueError for an unknown key, an unknown kind or bad values."""
+def _loss_section(config):
     section = ((config.get("model") or {}).get("train") or {}).get("loss")
+    if section is not None and not isinstance(section, dict):
+        raise ValueError("model.train.loss must be a mapping, not %r" % (section,))
+    return section
+
+
+def loss_from_config(config):
+    """`model: train: loss: {kind, neg_pos_ratio, loc_weight}` or `{kind: softmax_focal, gamma, alpha, loc_weight,
+    background_prior}` (no reference counterpart) -> ops.LossSpec, or None when the section is absent: the default run trains
+    with the reference's loss.  kind "multibox" is the SSD paper's loss, "softmax_focal" the softmax focal loss over every
+    anchor.  ValueError for an unknown key, an unknown kind, bad values, or a key of another kind: gamma, alpha and
+    background_prior belong to softmax_focal alone, neg_pos_ratio to the mined losses.  background_prior itself is read by
+    background_prior_from_config."""
+    section = _loss_section(config)
     if section is None:
         return None
-    if not isinstance(section, dict):
-        raise ValueError("model.train.loss must be a mapping, not %r" % (section,))
-    unknown = set(section) - {"kind", "neg_pos_ratio", "loc_weight"}
+    focal_keys = {"gamma", "alpha", "background_prior"}
+    unknown = set(section) - {"kind", "neg_pos_ratio", "loc_weight"} - focal_keys
     if unknown:
         raise ValueError("unknown model.train.loss keys: %s" % sorted(unknown))
+    kind = section.get("kind", "reference")
+    foreign = set(section) & ({"neg_pos_ratio"} if kind == "softmax_focal" else focal_keys)
+    if foreign:
+        raise ValueError("model.train.loss keys %s do not apply to the loss kind %r" % (sorted(foreign), kind))
     from ..ops import LossSpec
-    return LossSpec(kind=section.get("kind", "reference"), neg_pos_ratio=section.get("neg_pos_ratio", 3),
-                    loc_weight=section.get("loc_weight", 1.0))
+    return LossSpec(kind=kind, neg_pos_ratio=section.get("neg_pos_ratio", 3), loc_weight=section.get("loc_weight", 1.0),
+                    gamma=section.get("gamma", 2.0), alpha=section.get("alpha", 0.25))
+
+
+def background_prior_from_config(config):
+    """`model: train: loss: background_prior` (softmax_focal only: loss_from_config refuses it elsewhere) -> the foreground
+    prior pi in (0, 1) for model.set_background_prior, or None when the key is absent.  A run applies it once, when it
+    starts from scratch; a resumed run keeps its checkpoint's biases."""
+    section = _loss_section(config)
+    if section is None or section.get("background_prior") is None:
+        return None
+    loss_from_config(config)
+    pi = section["background_prior"]
+    if isinstance(pi, bool) or not isinstance(pi, (int, float)) or not 0.0 < pi < 1.0:
+        raise ValueError("model.train.loss.background_prior must be a number in (0, 1), not %r" % (pi,))
+    return float(pi)
 
 
 def l2norm_from_config(config):
@@ -288,6 +315,9 @@ def train(config):
         warmup_optimizer.iterations = int(extra.get("warmup_iterations", 0))
         start_epoch = int(extra.get("epoch", 0))
         logger.info("Resuming from %s at epoch %d (optimizer step %d)", resume, start_epoch, optimizer.iterations)
+    prior = background_prior_from_config(config)
+    if prior is not None and not resume:     # a run from scratch: the conf biases start at the prior (a resumed run keeps its own)
+        model.set_background_prior(prior)
 
     if rank == 0:                            # the run's configuration next to its logs (reference tools/train.py:55-56)
         os.makedirs(model.get_log_dir(), exist_ok=True)
