@@ -267,6 +267,55 @@ int ssd_softmax_focal_loss_fwd_bwd_heads(const void* conf, const void* loc, int 
                                          size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The box term of the two losses above by kind: smooth L1 of the four offsets (kind 0: the entries above, which forward here),
+ * or the GIoU (Rezatofighi et al. 2019), DIoU or CIoU (Zheng et al. 2020) loss of the decoded boxes.  Opt-in, no reference
+ * counterpart.  Arguments, results, refusals, workspaces and launches as the entry of the same name without _box, plus
+ *   box_kind  SSD_BOX_SMOOTH_L1 | SSD_BOX_GIOU | SSD_BOX_DIOU | SSD_BOX_CIOU; anything else: SSD_ERR_VALUE
+ *   priors    DEVICE double[A*4] (cx, cy, w, h), the array the matcher and ssd_score_decode read; may be NULL with kind 0, which
+ *             does not read it; NULL with an IoU kind: SSD_ERR_VALUE.  Both refusals happen on the host before any launch
+ * Per positive anchor a, prior d = priors[a], t = loc[a], g = gt_loc[a], W = log(1000 / 16), f32 arithmetic:
+ *   decode    relative to the prior's centre (every kind is translation invariant; a small width is not cancelled against an
+ *             absolute position):  cx = t0 d_w, cy = t1 d_h, w = d_w exp(clamp(t2, -W, W)), h = d_h exp(clamp(t3, -W, W));
+ *             (gx, gy, gw, gh) from g in the same way;  x1 = cx - w/2, x2 = cx + w/2, ..., X1 = gx - gw/2, ...
+ *   iw = max(0, min(x2, X2) - max(x1, X1)), ih likewise;  I = iw ih;  U = w h + gw gh - I;  IoU = I / U
+ *   cw = max(x2, X2) - min(x1, X1), ch likewise
+ *   GIoU      L = 1 - IoU + (cw ch - U) / (cw ch)
+ *   DIoU      L = 1 - IoU + rho^2 / c^2,  rho^2 = (cx - gx)^2 + (cy - gy)^2,  c^2 = cw^2 + ch^2
+ *   CIoU      L = DIoU + alpha v,  v = (4 / pi^2) (atan(gw / gh) - atan(w / h))^2,  alpha = v / ((1 - IoU) + v) where v > 0,
+ *             else 0; alpha is a constant in the gradient, dv/dw and dv/dh are the true derivatives (the 1 / (w^2 + h^2) kept)
+ *   no epsilons: with positive prior sizes and the clamp every denominator is positive
+ *   dL/dt0 = d_w dL/dcx, dL/dt1 = d_h dL/dcy, dL/dt2 = w dL/dw where |t2| < W, else 0; t3 likewise
+ *   ties      max(p, q) / min(p, q) pass the gradient to the predicted coordinate under the strict comparison only, max(0, .)
+ *             where its argument is > 0
+ *   L_loc = loc_weight * sum_pos L / P;  dloc = grad_scale * loc_weight / P * pos * dL/dt: every element is written, exact zeros
+ *             off the positives;  P, N, tau, the classification terms and dconf are those of kind 0, bit for bit
+ *   status    3 also where a positive's box loss or gradient is not finite (a prior with a size that is not positive, say)
+ * Both losses evaluate one device function: their dloc agree bit for bit on the same inputs, as for kind 0.  f32 losses agree
+ * with a float64 evaluation to <= 1e-4 relative, f32 dloc per anchor to 1e-4 of the anchor's largest component.
+ * ---------------------------------------------------------------------------------------- */
+#define SSD_BOX_SMOOTH_L1 0
+#define SSD_BOX_GIOU 1
+#define SSD_BOX_DIOU 2
+#define SSD_BOX_CIOU 3
+int ssd_multibox_loss_box_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                  const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
+                                  float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
+                                  void* stream, int box_kind, const double* priors);
+int ssd_multibox_loss_box_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                        const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
+                                        float grad_scale, float* out8, const ssd_head_grads* hg, void* ws, size_t ws_bytes,
+                                        void* stream, int box_kind, const double* priors);
+int ssd_softmax_focal_loss_box_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                       const uint8_t* gt_mask, int B, int A, int C, float gamma, float alpha, float loc_weight,
+                                       float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
+                                       void* stream, int box_kind, const double* priors);
+int ssd_softmax_focal_loss_box_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls,
+                                             const float* gt_loc, const uint8_t* gt_mask, int B, int A, int C, float gamma,
+                                             float alpha, float loc_weight, float grad_scale, float* out8,
+                                             const ssd_head_grads* hg, void* ws, size_t ws_bytes, void* stream, int box_kind,
+                                             const double* priors);
+
+/* ------------------------------------------------------------------------------------------
  * Inference scoring + decode -- replaces the scoring half of SSDObjectDetectionModel.visualize
  * (models/ssd_model.py:479-488, mask=None branch) and the box decode of visualize_dataset (:466-467).
  *   conf [B*A*C], loc [B*A*4] (SSD_F32 / SSD_BF16), priors double[A*4]

@@ -2,7 +2,9 @@
 // loss (loss.hip) stays the default.  It differs from that loss in three ways:
 //   * hard negatives are mined PER IMAGE: image b keeps its k_b = min(ratio * P_b, A - P_b) non-positive anchors of largest
 //     key(a) = CE(a, background) (ties at the k_b-th key kept), an image without positives mines nothing;
-//   * the box term is smooth L1 (gradient: the difference clamped to [-1, 1]);
+//   * the box term is smooth L1 (gradient: the difference clamped to [-1, 1]), or, by the box kind of the _box entries, the GIoU /
+//     DIoU / CIoU loss of the decoded boxes (boxterm.h; the kernels that evaluate it are instantiations of their own, so the
+//     smooth-L1 kernels are the code they were);
 //   * all three terms are divided by the number of positives P of the call.
 //   L_pos = sum_pos CE(a, gt_cls) / P;  L_neg = sum_neg key(a) / P;  L_loc = alpha * sum_pos sum_4 smoothL1(loc - gt_loc) / P
 //   dconf = grad_scale / P * [pos * (softmax - onehot(gt_cls)) + neg * (softmax - onehot(C-1))]
@@ -43,7 +45,7 @@ struct MbWs {                                // layout of the caller's workspace
     float* key;                              // [n] background CE of every anchor
     float* lse;                              // [n] logsumexp per anchor
     double* part_pos;                        // [nblk] per-block sum of the positives' CE (NaN: a logit row was not finite)
-    double* part_sl1;                        // [nblk] per-block sum of the positives' smooth L1
+    double* part_sl1;                        // [nblk] per-block sum of the positives' box term (smooth L1 or an IoU kind)
     unsigned* img_tau;                       // [B] bits of tau_b
     int* img_mined;                          // [B] k_b > 0
     int* img_P;                              // [B]
@@ -82,6 +84,7 @@ struct MbParams {
     float alpha, grad_scale;
 };
 
+
 struct MbLevels {                            // the rows form's geometry (levels == 0: dense form)
     int levels;
     int hw[SSD_MAX_LEVELS], n[SSD_MAX_LEVELS], npad[SSD_MAX_LEVELS], off[SSD_MAX_LEVELS + 1];
@@ -96,12 +99,13 @@ __device__ __forceinline__ bool mined_neg(float key, float tau, int mined) { ret
 
 // ------------------------------------------------------------------------------------------------
 // Pass 1: one read of conf (k_loss_rows' staging: persistent grid, the next block's logits requested before the current block
-// is reduced).  Per anchor: logsumexp and the background CE; per block: the positives' CE and smooth-L1 sums.  A block of 128
+// is reduced).  Per anchor: logsumexp and the background CE; per block: the positives' CE and box-term sums.  A block of 128
 // rows may straddle two images: nothing here is per image.
-template <typename T, int CC>
+template <typename T, int CC, bool IOU>
 __global__ __launch_bounds__(WG) void k_mb_rows(const T* __restrict__ conf, const T* __restrict__ loc,
                                                 const int* __restrict__ cls, const float* __restrict__ gloc,
-                                                const uint8_t* __restrict__ mask, size_t n, int C_rt, MbWs w) {
+                                                const uint8_t* __restrict__ mask, size_t n, int C_rt, MbWs w, int A,
+                                                BoxArgs bx) {
     extern __shared__ __attribute__((aligned(16))) float s_z[];   // [ROWS*C]
     __shared__ double s_red[4];
     const int C = CC ? CC : C_rt;
@@ -161,7 +165,13 @@ __global__ __launch_bounds__(WG) void k_mb_rows(const T* __restrict__ conf, cons
                 if (!(fabsf(lse) < INFINITY)) acc_pos = (double)NAN;
                 if (mask[g] != 0) {
                     acc_pos += (double)((m - z[cls[g]]) + logs);
-                    acc_sl1 = box_loss<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g]);
+                    const float4 gl = reinterpret_cast<const float4*>(gloc)[g];
+                    if constexpr (IOU) {
+                        float4 unused;
+                        acc_sl1 = box_term<T>(bx, A, g, loc + 4 * g, gl, 1.f, &unused);
+                    } else {
+                        acc_sl1 = box_loss<T>(loc + 4 * g, gl);
+                    }
                 }
             }
         }
@@ -358,11 +368,11 @@ __device__ __forceinline__ void mb_scalars(const MbWs& w, const MbParams& p, int
 }
 
 // Pass 3, dense form: gradients, written once and coalesced.  Only selected rows re-read their logits.
-template <typename T>
+template <typename T, bool IOU>
 __global__ __launch_bounds__(WG) void k_mb_grad(const T* __restrict__ conf, const T* __restrict__ loc,
                                                 const int* __restrict__ cls, const float* __restrict__ gloc,
                                                 const uint8_t* __restrict__ mask, MbParams p, T* __restrict__ dconf,
-                                                T* __restrict__ dloc, MbWs w, float* __restrict__ out) {
+                                                T* __restrict__ dloc, MbWs w, float* __restrict__ out, BoxArgs bx) {
     extern __shared__ __attribute__((aligned(16))) float s_g[];   // [ROWS*C] gradient block
     __shared__ int s_redi[4];
     __shared__ double s_redd[4];
@@ -392,7 +402,10 @@ __global__ __launch_bounds__(WG) void k_mb_grad(const T* __restrict__ conf, cons
         }
         if (half == 0) {
             float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pos) d = box_grad<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl);
+            if (pos) {
+                if constexpr (IOU) box_term<T>(bx, p.A, g, loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl, &d);
+                else d = box_grad<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl);
+            }
             T* o = dloc + 4 * g;
             o[0] = from_f32<T>(d.x); o[1] = from_f32<T>(d.y); o[2] = from_f32<T>(d.z); o[3] = from_f32<T>(d.w);
         }
@@ -456,9 +469,11 @@ __global__ __launch_bounds__(WG) void k_mb_assign(const uint8_t* __restrict__ ma
 }
 
 // Gradient of the selected anchors only, written into the compact rows (the arithmetic of k_mb_grad).
+template <bool IOU>
 __global__ __launch_bounds__(WG) void k_mb_grad_rows(const __hip_bfloat16* __restrict__ conf, const __hip_bfloat16* __restrict__ loc,
                                                      const int* __restrict__ cls, const float* __restrict__ gloc,
-                                                     const uint8_t* __restrict__ mask, MbParams p, MbWs w, MbLevels h) {
+                                                     const uint8_t* __restrict__ mask, MbParams p, MbWs w, MbLevels h,
+                                                     BoxArgs bx) {
     typedef __hip_bfloat16 T;
     __shared__ int s_redi[4];
     const int C = p.C;
@@ -489,7 +504,9 @@ __global__ __launch_bounds__(WG) void k_mb_grad_rows(const __hip_bfloat16* __res
                 const int k0 = half ? (C + 1) / 2 : 0, k1 = half ? C : (C + 1) / 2;
                 for (int k = k0; k < k1; ++k) o[k] = from_f32<T>((__expf(to_f32<T>(z[k]) - lse) - (k == label ? 1.f : 0.f)) * sc);
                 if (pos && half == 0) {
-                    const float4 dl = box_grad<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl);
+                    float4 dl;
+                    if constexpr (IOU) box_term<T>(bx, p.A, g, loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl, &dl);
+                    else dl = box_grad<T>(loc + 4 * g, reinterpret_cast<const float4*>(gloc)[g], sl);
                     T* ol = d + slot * 4;
                     ol[0] = from_f32<T>(dl.x); ol[1] = from_f32<T>(dl.y); ol[2] = from_f32<T>(dl.z); ol[3] = from_f32<T>(dl.w);
                 }
@@ -505,46 +522,50 @@ int register_lds(OnceLds& once, K kern, size_t lds, size_t most) {
 }
 
 // the launches both forms share: conf read once, the per-image select
-template <typename T>
+template <typename T, bool IOU>
 int launch_rows_select(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
-                       const MbParams& p, const MbLevels& h, MbWs w, hipStream_t s) {
+                       const MbParams& p, const BoxArgs& bx, const MbLevels& h, MbWs w, hipStream_t s) {
     const size_t lds = rows_lds_bytes(p.C);
     const size_t most = (LDS_LIMIT - 64) / 16 * 16;
     const unsigned pgrid = (unsigned)min((size_t)MAX_PERSIST, p.nblk);
     static OnceLds once81, once0, once_sel;
-    if (p.C == 81 ? register_lds(once81, k_mb_rows<T, 81>, lds, most) : register_lds(once0, k_mb_rows<T, 0>, lds, most)) return SSD_ERR_LAUNCH;
+    if (p.C == 81 ? register_lds(once81, k_mb_rows<T, 81, IOU>, lds, most) : register_lds(once0, k_mb_rows<T, 0, IOU>, lds, most)) return SSD_ERR_LAUNCH;
     const size_t slds = select_lds_bytes(p.A);
     if (register_lds(once_sel, k_mb_select, slds, select_lds_bytes(SSD_MULTIBOX_MAX_ANCHORS))) return SSD_ERR_LAUNCH;
     if (p.C == 81)
-        hipLaunchKernelGGL((k_mb_rows<T, 81>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc, mask, p.n, p.C, w);
+        hipLaunchKernelGGL((k_mb_rows<T, 81, IOU>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc, mask,
+                           p.n, p.C, w, p.A, bx);
     else
-        hipLaunchKernelGGL((k_mb_rows<T, 0>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc, mask, p.n, p.C, w);
+        hipLaunchKernelGGL((k_mb_rows<T, 0, IOU>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc, mask,
+                           p.n, p.C, w, p.A, bx);
     hipLaunchKernelGGL(k_mb_select, dim3(p.B), dim3(SWG), slds, s, mask, w, p, h);
     return 0;
 }
 
-template <typename T>
+template <typename T, bool IOU>
 int launch_dense(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
-                 const MbParams& p, float* out, void* dconf, void* dloc, MbWs w, hipStream_t s) {
+                 const MbParams& p, const BoxArgs& bx, float* out, void* dconf, void* dloc, MbWs w, hipStream_t s) {
     const size_t lds = rows_lds_bytes(p.C);
     static OnceLds once_grad;
-    if (register_lds(once_grad, k_mb_grad<T>, lds, (LDS_LIMIT - 64) / 16 * 16)) return SSD_ERR_LAUNCH;
+    if (register_lds(once_grad, k_mb_grad<T, IOU>, lds, (LDS_LIMIT - 64) / 16 * 16)) return SSD_ERR_LAUNCH;
     MbLevels h = {};
-    if (int rc = launch_rows_select<T>(conf, loc, cls, gloc, mask, p, h, w, s)) return rc;
-    hipLaunchKernelGGL(k_mb_grad<T>, dim3((unsigned)p.nblk), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc,
-                       mask, p, (T*)dconf, (T*)dloc, w, out);
+    if (int rc = launch_rows_select<T, IOU>(conf, loc, cls, gloc, mask, p, bx, h, w, s)) return rc;
+    hipLaunchKernelGGL((k_mb_grad<T, IOU>), dim3((unsigned)p.nblk), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc,
+                       mask, p, (T*)dconf, (T*)dloc, w, out, bx);
     return ssd_launch_status();
 }
 
 // the refusals both entries share, before any launch
 int mb_check(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask, int B, int A,
-             int C, int ratio, float alpha, float grad_scale, const float* out8, MbParams* p) {
+             int C, int ratio, float alpha, float grad_scale, const float* out8, int box_kind, const double* priors, MbParams* p, BoxArgs* bx) {
+    if (box_kind < SSD_BOX_SMOOTH_L1 || box_kind > SSD_BOX_CIOU || (box_kind != SSD_BOX_SMOOTH_L1 && !priors)) return SSD_ERR_VALUE;
     if (B <= 0 || A <= 0 || C < 2 || ratio < 1) return SSD_ERR_VALUE;
     if (!(alpha >= 0.f) || !(alpha < INFINITY) || !std::isfinite(grad_scale)) return SSD_ERR_VALUE;
     if (!conf || !loc || !cls || !gloc || !mask || !out8) return SSD_ERR_VALUE;
     if (C > SSD_LOSS_MAX_CLASSES || A > SSD_MULTIBOX_MAX_ANCHORS) return SSD_ERR_UNSUPPORTED;
     p->n = (size_t)B * A; p->nblk = (p->n + ROWS - 1) / ROWS;
     p->A = A; p->B = B; p->C = C; p->ratio = ratio; p->alpha = alpha; p->grad_scale = grad_scale;
+    bx->kind = box_kind; bx->priors = priors;
     return 0;
 }
 
@@ -565,25 +586,47 @@ int ssd_multibox_loss_fwd_bwd(const void* conf, const void* loc, int dtype, cons
                               const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
                               float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
                               void* stream) {
+    return ssd_multibox_loss_box_fwd_bwd(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, neg_pos_ratio, loc_weight, grad_scale,
+                                         out8, dconf, dloc, ws, ws_bytes, stream, SSD_BOX_SMOOTH_L1, nullptr);
+}
+
+int ssd_multibox_loss_box_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                  const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
+                                  float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
+                                  void* stream, int box_kind, const double* priors) {
     MbParams p;
+    BoxArgs bx;
     if (dtype != SSD_F32 && dtype != SSD_BF16) return SSD_ERR_VALUE;
-    if (int rc = mb_check(conf, loc, gt_cls, gt_loc, gt_mask, B, A, C, neg_pos_ratio, loc_weight, grad_scale, out8, &p)) return rc;
+    if (int rc = mb_check(conf, loc, gt_cls, gt_loc, gt_mask, B, A, C, neg_pos_ratio, loc_weight, grad_scale, out8, box_kind, priors, &p, &bx)) return rc;
     if (!dconf || !dloc) return SSD_ERR_VALUE;
     if (!ws || ws_bytes < mb_ws_layout((size_t)B, (size_t)A, nullptr, nullptr)) return SSD_ERR_WORKSPACE;
     MbWs w;
     mb_ws_layout((size_t)B, (size_t)A, static_cast<char*>(ws), &w);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SSD_F32) return launch_dense<float>(conf, loc, gt_cls, gt_loc, gt_mask, p, out8, dconf, dloc, w, s);
-    return launch_dense<__hip_bfloat16>(conf, loc, gt_cls, gt_loc, gt_mask, p, out8, dconf, dloc, w, s);
+    const bool iou = box_kind != SSD_BOX_SMOOTH_L1;
+    if (dtype == SSD_F32)
+        return iou ? launch_dense<float, true>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, dconf, dloc, w, s)
+                   : launch_dense<float, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, dconf, dloc, w, s);
+    return iou ? launch_dense<__hip_bfloat16, true>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, dconf, dloc, w, s)
+               : launch_dense<__hip_bfloat16, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, dconf, dloc, w, s);
 }
 
 int ssd_multibox_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
                                     const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
                                     float grad_scale, float* out8, const ssd_head_grads* hg, void* ws, size_t ws_bytes,
                                     void* stream) {
+    return ssd_multibox_loss_box_fwd_bwd_heads(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, neg_pos_ratio, loc_weight,
+                                               grad_scale, out8, hg, ws, ws_bytes, stream, SSD_BOX_SMOOTH_L1, nullptr);
+}
+
+int ssd_multibox_loss_box_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                        const uint8_t* gt_mask, int B, int A, int C, int neg_pos_ratio, float loc_weight,
+                                        float grad_scale, float* out8, const ssd_head_grads* hg, void* ws, size_t ws_bytes,
+                                        void* stream, int box_kind, const double* priors) {
     MbParams p;
+    BoxArgs bx;
     if (dtype != SSD_F32 && dtype != SSD_BF16) return SSD_ERR_VALUE;
-    if (int rc = mb_check(conf, loc, gt_cls, gt_loc, gt_mask, B, A, C, neg_pos_ratio, loc_weight, grad_scale, out8, &p)) return rc;
+    if (int rc = mb_check(conf, loc, gt_cls, gt_loc, gt_mask, B, A, C, neg_pos_ratio, loc_weight, grad_scale, out8, box_kind, priors, &p, &bx)) return rc;
     if (dtype != SSD_BF16) return SSD_ERR_UNSUPPORTED;
     if (!hg || !hg->count || hg->levels <= 0 || hg->levels > SSD_MAX_LEVELS) return SSD_ERR_VALUE;
     MbLevels h = {};
@@ -607,10 +650,16 @@ int ssd_multibox_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype
     mb_ws_layout((size_t)B, (size_t)A, static_cast<char*>(ws), &w);
     hipStream_t s = (hipStream_t)stream;
     typedef __hip_bfloat16 T;
-    if (int rc = launch_rows_select<T>(conf, loc, gt_cls, gt_loc, gt_mask, p, h, w, s)) return rc;
+    const bool iou = box_kind != SSD_BOX_SMOOTH_L1;
+    if (int rc = iou ? launch_rows_select<T, true>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, h, w, s)
+                     : launch_rows_select<T, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, h, w, s)) return rc;
     hipLaunchKernelGGL(k_mb_assign, dim3(B, hg->levels), dim3(WG), 0, s, gt_mask, w, p, h, out8);
-    hipLaunchKernelGGL(k_mb_grad_rows, dim3((unsigned)p.nblk), dim3(WG), 0, s, (const T*)conf, (const T*)loc, gt_cls, gt_loc,
-                       gt_mask, p, w, h);
+    if (iou)
+        hipLaunchKernelGGL(k_mb_grad_rows<true>, dim3((unsigned)p.nblk), dim3(WG), 0, s, (const T*)conf, (const T*)loc, gt_cls,
+                           gt_loc, gt_mask, p, w, h, bx);
+    else
+        hipLaunchKernelGGL(k_mb_grad_rows<false>, dim3((unsigned)p.nblk), dim3(WG), 0, s, (const T*)conf, (const T*)loc, gt_cls,
+                           gt_loc, gt_mask, p, w, h, bx);
     return ssd_launch_status();
 }
 

@@ -3,7 +3,8 @@
 // classification term, weighted by (1 - p_t)^gamma; nothing is mined, so there is no select and no histogram:
 //   t = gt_cls[a] if gt_mask[a] else C-1;  e_j = exp(z_j - max z);  Q = sum_{j != t} e_j;  S = Q + e_t;  q = Q / S (= 1 - p_t)
 //   log p_t = log1p(-q) if q < 0.5 else (z_t - max z) - log S           (neither form cancels)
-//   FL(a) = -alpha_t q^gamma log p_t;  L_pos = sum_pos FL / P;  L_neg = sum_{not pos} FL / P;  L_loc as MultiBox (boxterm.h)
+//   FL(a) = -alpha_t q^gamma log p_t;  L_pos = sum_pos FL / P;  L_neg = sum_{not pos} FL / P;  L_loc as MultiBox (boxterm.h:
+//   smooth L1, or an IoU kind through the _box entries, in an instantiation of k_sf_rows of its own)
 //   dconf[a, j] = grad_scale / P * alpha_t * (delta_tj - p_j) * (gamma p_t q^(gamma-1) log p_t - q^gamma)
 // evaluated as -q^gamma (gamma p_t h + 1) with h = -log p_t / q (h = 1 at q == 0), which is finite at q == 0, and with
 // delta_tt - p_t taken as q.
@@ -34,7 +35,7 @@ struct SfWs {                                // layout of the caller's workspace
     int* cnt;                                // [nc] positives per CNT_CHUNK mask bytes
     double* part_pos;                        // [nblk] per-block sum of the positives' FL
     double* part_neg;                        // [nblk] ... of the other anchors' FL
-    double* part_sl1;                        // [nblk] ... of the positives' smooth L1
+    double* part_sl1;                        // [nblk] ... of the positives' box term (smooth L1 or an IoU kind)
     int* bad;                                // [nblk] a logit of the block, or an offset of one of its positives, was not finite
 };
 
@@ -62,6 +63,7 @@ struct SfParams {
     float gamma, alpha_fg, alpha_bg;         // alpha_t of a target class / of the background (both 1 with alpha == -1)
     float loc_weight, grad_scale;
 };
+
 
 struct SfLevels {                            // the rows form's geometry
     int levels;
@@ -134,11 +136,11 @@ __device__ __forceinline__ float focal_row(float* z, int C_rt, int t, int half, 
 // Launch 2.  Persistent grid over blocks of ROWS anchor rows, k_mb_rows' staging (the next block's logits are requested before
 // the current block is computed on).  ROWSFORM: the gradient goes to the compact rows of `h` (every pixel is a row: the maps
 // are the identity) instead of dconf / dloc.
-template <typename T, int CC, bool ROWSFORM>
+template <typename T, int CC, bool ROWSFORM, bool IOU>
 __global__ __launch_bounds__(WG) void k_sf_rows(const T* __restrict__ conf, const T* __restrict__ loc,
                                                 const int* __restrict__ cls, const float* __restrict__ gloc,
                                                 const uint8_t* __restrict__ mask, SfParams p, T* __restrict__ dconf,
-                                                T* __restrict__ dloc, SfWs w, SfLevels h) {
+                                                T* __restrict__ dloc, SfWs w, SfLevels h, BoxArgs bx) {
     extern __shared__ __attribute__((aligned(16))) float s_z[];   // [ROWS*C]: logits, then the gradient block
     __shared__ double s_red[4];
     __shared__ int s_redi[4];
@@ -186,8 +188,12 @@ __global__ __launch_bounds__(WG) void k_sf_rows(const T* __restrict__ conf, cons
                 float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (pos) {
                     const float4 gl = reinterpret_cast<const float4*>(gloc)[g];
-                    acc_sl1 = box_loss<T>(loc + 4 * g, gl);
-                    d = box_grad<T>(loc + 4 * g, gl, sl);
+                    if constexpr (IOU) {
+                        acc_sl1 = box_term<T>(bx, p.A, g, loc + 4 * g, gl, sl, &d);
+                    } else {
+                        acc_sl1 = box_loss<T>(loc + 4 * g, gl);
+                        d = box_grad<T>(loc + 4 * g, gl, sl);
+                    }
                 }
                 T* ol;
                 if constexpr (ROWSFORM) {
@@ -259,28 +265,34 @@ __global__ __launch_bounds__(WG) void k_sf_scalars(SfWs w, SfParams p, float* __
     }
 }
 
-template <typename T, int CC, bool ROWSFORM>
+template <typename T, int CC, bool ROWSFORM, bool IOU>
 int launch_rows(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
-                const SfParams& p, void* dconf, void* dloc, const SfWs& w, const SfLevels& h, hipStream_t s) {
+                const SfParams& p, const BoxArgs& bx, void* dconf, void* dloc, const SfWs& w, const SfLevels& h, hipStream_t s) {
     // more than 64 KB of dynamic LDS is registered once per device and kernel, for the largest block the bounds admit
     static OnceLds once;
     const size_t lds = rows_lds_bytes(p.C);
-    if (lds > 64 * 1024 && ensure_lds(once, reinterpret_cast<const void*>(k_sf_rows<T, CC, ROWSFORM>),
+    if (lds > 64 * 1024 && ensure_lds(once, reinterpret_cast<const void*>(k_sf_rows<T, CC, ROWSFORM, IOU>),
                                       (int)rows_lds_bytes(SSD_LOSS_MAX_CLASSES)))
         return SSD_ERR_LAUNCH;
     const unsigned pgrid = (unsigned)min((size_t)MAX_PERSIST, p.nblk);
-    hipLaunchKernelGGL((k_sf_rows<T, CC, ROWSFORM>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc,
-                       mask, p, (T*)dconf, (T*)dloc, w, h);
+    hipLaunchKernelGGL((k_sf_rows<T, CC, ROWSFORM, IOU>), dim3(pgrid), dim3(WG), lds, s, (const T*)conf, (const T*)loc, cls, gloc,
+                       mask, p, (T*)dconf, (T*)dloc, w, h, bx);
     return 0;
 }
 
 // the three launches of either form
 template <typename T, bool ROWSFORM>
 int launch_all(const void* conf, const void* loc, const int32_t* cls, const float* gloc, const uint8_t* mask,
-               const SfParams& p, float* out, void* dconf, void* dloc, const SfWs& w, const SfLevels& h, hipStream_t s) {
+               const SfParams& p, const BoxArgs& bx, float* out, void* dconf, void* dloc, const SfWs& w, const SfLevels& h,
+               hipStream_t s) {
     hipLaunchKernelGGL(k_sf_count, dim3((unsigned)p.nc), dim3(WG), 0, s, mask, p.n, w.cnt);
-    const int rc = p.C == 81 ? launch_rows<T, 81, ROWSFORM>(conf, loc, cls, gloc, mask, p, dconf, dloc, w, h, s)
-                             : launch_rows<T, 0, ROWSFORM>(conf, loc, cls, gloc, mask, p, dconf, dloc, w, h, s);
+    int rc;
+    if (bx.kind != SSD_BOX_SMOOTH_L1)
+        rc = p.C == 81 ? launch_rows<T, 81, ROWSFORM, true>(conf, loc, cls, gloc, mask, p, bx, dconf, dloc, w, h, s)
+                       : launch_rows<T, 0, ROWSFORM, true>(conf, loc, cls, gloc, mask, p, bx, dconf, dloc, w, h, s);
+    else
+        rc = p.C == 81 ? launch_rows<T, 81, ROWSFORM, false>(conf, loc, cls, gloc, mask, p, bx, dconf, dloc, w, h, s)
+                       : launch_rows<T, 0, ROWSFORM, false>(conf, loc, cls, gloc, mask, p, bx, dconf, dloc, w, h, s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_sf_scalars, dim3(1), dim3(WG), 0, s, w, p, out);
     return ssd_launch_status();
@@ -288,7 +300,9 @@ int launch_all(const void* conf, const void* loc, const int32_t* cls, const floa
 
 // the refusals both entries share, before any launch
 int sf_check(const void* conf, const void* loc, int dtype, const int32_t* cls, const float* gloc, const uint8_t* mask, int B,
-             int A, int C, float gamma, float alpha, float loc_weight, float grad_scale, const float* out8, SfParams* p) {
+             int A, int C, float gamma, float alpha, float loc_weight, float grad_scale, const float* out8, int box_kind,
+             const double* priors, SfParams* p, BoxArgs* bx) {
+    if (box_kind < SSD_BOX_SMOOTH_L1 || box_kind > SSD_BOX_CIOU || (box_kind != SSD_BOX_SMOOTH_L1 && !priors)) return SSD_ERR_VALUE;
     if (!std::isfinite(gamma) || gamma < 0.f || gamma > 8.f) return SSD_ERR_VALUE;
     if (!((alpha >= 0.f && alpha <= 1.f) || alpha == -1.f)) return SSD_ERR_VALUE;
     if (!std::isfinite(loc_weight) || loc_weight < 0.f || !std::isfinite(grad_scale)) return SSD_ERR_VALUE;
@@ -303,6 +317,7 @@ int sf_check(const void* conf, const void* loc, int dtype, const int32_t* cls, c
     p->alpha_fg = alpha == -1.f ? 1.f : alpha;
     p->alpha_bg = alpha == -1.f ? 1.f : 1.f - alpha;
     p->loc_weight = loc_weight; p->grad_scale = grad_scale;
+    bx->kind = box_kind; bx->priors = priors;
     return 0;
 }
 
@@ -321,24 +336,43 @@ int ssd_softmax_focal_loss_fwd_bwd(const void* conf, const void* loc, int dtype,
                                    const uint8_t* gt_mask, int B, int A, int C, float gamma, float alpha, float loc_weight,
                                    float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
                                    void* stream) {
+    return ssd_softmax_focal_loss_box_fwd_bwd(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, gamma, alpha, loc_weight,
+                                              grad_scale, out8, dconf, dloc, ws, ws_bytes, stream, SSD_BOX_SMOOTH_L1, nullptr);
+}
+
+int ssd_softmax_focal_loss_box_fwd_bwd(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
+                                       const uint8_t* gt_mask, int B, int A, int C, float gamma, float alpha, float loc_weight,
+                                       float grad_scale, float* out8, void* dconf, void* dloc, void* ws, size_t ws_bytes,
+                                       void* stream, int box_kind, const double* priors) {
     SfParams p;
-    if (int rc = sf_check(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, gamma, alpha, loc_weight, grad_scale, out8, &p)) return rc;
+    BoxArgs bx;
+    if (int rc = sf_check(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, gamma, alpha, loc_weight, grad_scale, out8, box_kind, priors, &p, &bx)) return rc;
     if (!dconf || !dloc) return SSD_ERR_VALUE;
     if (!ws || ws_bytes < sf_ws_layout(p.n, nullptr, nullptr)) return SSD_ERR_WORKSPACE;
     SfWs w;
     sf_ws_layout(p.n, static_cast<char*>(ws), &w);
     const SfLevels h = {};
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SSD_F32) return launch_all<float, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, out8, dconf, dloc, w, h, s);
-    return launch_all<__hip_bfloat16, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, out8, dconf, dloc, w, h, s);
+    if (dtype == SSD_F32) return launch_all<float, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, dconf, dloc, w, h, s);
+    return launch_all<__hip_bfloat16, false>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, dconf, dloc, w, h, s);
 }
 
 int ssd_softmax_focal_loss_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls, const float* gt_loc,
                                          const uint8_t* gt_mask, int B, int A, int C, float gamma, float alpha,
                                          float loc_weight, float grad_scale, float* out8, const ssd_head_grads* hg, void* ws,
                                          size_t ws_bytes, void* stream) {
+    return ssd_softmax_focal_loss_box_fwd_bwd_heads(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, gamma, alpha, loc_weight,
+                                                    grad_scale, out8, hg, ws, ws_bytes, stream, SSD_BOX_SMOOTH_L1, nullptr);
+}
+
+int ssd_softmax_focal_loss_box_fwd_bwd_heads(const void* conf, const void* loc, int dtype, const int32_t* gt_cls,
+                                             const float* gt_loc, const uint8_t* gt_mask, int B, int A, int C, float gamma,
+                                             float alpha, float loc_weight, float grad_scale, float* out8,
+                                             const ssd_head_grads* hg, void* ws, size_t ws_bytes, void* stream, int box_kind,
+                                             const double* priors) {
     SfParams p;
-    if (int rc = sf_check(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, gamma, alpha, loc_weight, grad_scale, out8, &p)) return rc;
+    BoxArgs bx;
+    if (int rc = sf_check(conf, loc, dtype, gt_cls, gt_loc, gt_mask, B, A, C, gamma, alpha, loc_weight, grad_scale, out8, box_kind, priors, &p, &bx)) return rc;
     if (dtype != SSD_BF16) return SSD_ERR_UNSUPPORTED;
     if (!hg || !hg->count || hg->levels <= 0 || hg->levels > SSD_MAX_LEVELS) return SSD_ERR_VALUE;
     SfLevels h = {};
@@ -360,7 +394,7 @@ int ssd_softmax_focal_loss_fwd_bwd_heads(const void* conf, const void* loc, int 
     if (!ws || ws_bytes < sf_ws_layout(p.n, nullptr, nullptr)) return SSD_ERR_WORKSPACE;
     SfWs w;
     sf_ws_layout(p.n, static_cast<char*>(ws), &w);
-    return launch_all<__hip_bfloat16, true>(conf, loc, gt_cls, gt_loc, gt_mask, p, out8, nullptr, nullptr, w, h, (hipStream_t)stream);
+    return launch_all<__hip_bfloat16, true>(conf, loc, gt_cls, gt_loc, gt_mask, p, bx, out8, nullptr, nullptr, w, h, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -325,11 +325,12 @@ class SSDObjectDetectionModel:
 
     # ------------------------------------------------------------------ loss (A6)
     @staticmethod
-    def _ssd_loss(y_true, y_pred, heads=None, loss=None):
+    def _ssd_loss(y_true, y_pred, heads=None, loss=None, priors=None):
         """Returns (total loss tensor, info) where info maps the reference's three names to device scalars and
         carries the gradients w.r.t. (pred_box, pred_cls) under 'dloc' / 'dconf' -- or, with `heads` (the engine's
         ops.HeadGradBuffers), as the compact per-level rows the heads' backward pass consumes ('heads').  `loss`: None,
-        a kind name or an ops.LossSpec (None / "reference": the reference's loss)."""
+        a kind name or an ops.LossSpec (None / "reference": the reference's loss).  `priors`: the model's ops.PriorSet, which the
+        IoU box terms of a LossSpec (box="giou" | "diou" | "ciou") decode with; the other losses do not read it."""
         gt_cls, gt_box, gt_mask = y_true
         pred_box, pred_cls = y_pred
         assert gt_cls.shape[0] == gt_box.shape[0] == gt_mask.shape[0] == pred_box.shape[0] == pred_cls.shape[0]
@@ -337,19 +338,19 @@ class SSDObjectDetectionModel:
         if spec is not None and spec.kind == "multibox":
             if heads is not None:
                 out = ops.multibox_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads, spec.neg_pos_ratio,
-                                              spec.loc_weight)
+                                              spec.loc_weight, box=spec.box, priors=priors)
                 dconf = dloc = None
             else:
                 out, dconf, dloc = ops.multibox_loss(pred_cls, pred_box, gt_cls, gt_box, gt_mask, spec.neg_pos_ratio,
-                                                     spec.loc_weight)
+                                                     spec.loc_weight, box=spec.box, priors=priors)
         elif spec is not None and spec.kind == "softmax_focal":
             if heads is not None:
                 out = ops.softmax_focal_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads, spec.gamma, spec.alpha,
-                                                   spec.loc_weight)
+                                                   spec.loc_weight, box=spec.box, priors=priors)
                 dconf = dloc = None
             else:
                 out, dconf, dloc = ops.softmax_focal_loss(pred_cls, pred_box, gt_cls, gt_box, gt_mask, spec.gamma, spec.alpha,
-                                                          spec.loc_weight)
+                                                          spec.loc_weight, box=spec.box, priors=priors)
         elif heads is not None:
             out = ops.ssd_loss_heads(pred_cls, pred_box, gt_cls, gt_box, gt_mask, heads)
             dconf = dloc = None
@@ -432,7 +433,7 @@ class SSDObjectDetectionModel:
                 self._targets_event = None
             heads = eng.head_grad_buffers(pred_loc.shape[0]) if pred_conf.dtype == torch.bfloat16 else None
             _, info = self._ssd_loss((gt_cls[i:i + batch_step], gt_bbox[i:i + batch_step], gt_mask[i:i + batch_step]),
-                                     (pred_loc, pred_conf), heads, getattr(cfg, "loss", None))
+                                     (pred_loc, pred_conf), heads, getattr(cfg, "loss", None), self._pset)
             if overlap:
                 post = gates = None
                 if fused_dp:

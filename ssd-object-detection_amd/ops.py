@@ -275,12 +275,19 @@ class LossSpec:
     fields are not used).  kind "multibox": the SSD paper's loss (multibox_loss / multibox_loss_heads) with
     `neg_pos_ratio` mined negatives per positive, per image, and the box term weighted by `loc_weight`.  kind
     "softmax_focal": the softmax focal loss (softmax_focal_loss / softmax_focal_loss_heads) over every anchor with the
-    focusing exponent `gamma` in [0, 8], the class balance `alpha` in [0, 1] (-1: off) and `loc_weight`; it mines nothing."""
+    focusing exponent `gamma` in [0, 8], the class balance `alpha` in [0, 1] (-1: off) and `loc_weight`; it mines nothing.
+    `box`: the box term of "multibox" and "softmax_focal" -- "smooth_l1" of the four offsets, or the "giou" / "diou" / "ciou"
+    loss of the decoded boxes (include/ssd_hip.h), which needs the priors at the call; the reference's loss has its L1 only."""
     KINDS = ("reference", "multibox", "softmax_focal")
+    BOXES = ("smooth_l1", "giou", "diou", "ciou")                  # SSD_BOX_* in this order
 
-    def __init__(self, kind="reference", neg_pos_ratio=3, loc_weight=1.0, gamma=2.0, alpha=0.25):
+    def __init__(self, kind="reference", neg_pos_ratio=3, loc_weight=1.0, gamma=2.0, alpha=0.25, box="smooth_l1"):
         if kind not in self.KINDS:
             raise ValueError("loss kind must be one of %s, not %r" % (", ".join(self.KINDS), kind))
+        if not isinstance(box, str) or box not in self.BOXES:
+            raise ValueError("box must be one of %s, not %r" % (", ".join(self.BOXES), box))
+        if box != "smooth_l1" and kind == "reference":
+            raise ValueError("box=%r needs the loss kind multibox or softmax_focal: the reference's loss has no such term" % (box,))
         if isinstance(neg_pos_ratio, bool) or not isinstance(neg_pos_ratio, (int, np.integer)) or neg_pos_ratio < 1:
             raise ValueError("neg_pos_ratio must be an integer >= 1, not %r" % (neg_pos_ratio,))
         for name, value in (("loc_weight", loc_weight), ("gamma", gamma), ("alpha", alpha)):
@@ -297,6 +304,12 @@ class LossSpec:
         self.loc_weight = float(loc_weight)
         self.gamma = float(gamma)
         self.alpha = float(alpha)
+        self.box = box
+
+    @property
+    def box_kind(self):
+        """SSD_BOX_* of `box`."""
+        return self.BOXES.index(self.box)
 
     @classmethod
     def of(cls, loss):
@@ -310,9 +323,10 @@ class LossSpec:
         raise ValueError("loss must be None, a kind name or an ops.LossSpec, not %r" % (loss,))
 
     def __repr__(self):
+        box = "" if self.box == "smooth_l1" else ", box=%r" % self.box
         if self.kind == "softmax_focal":
-            return "LossSpec(kind=%r, gamma=%r, alpha=%r, loc_weight=%r)" % (self.kind, self.gamma, self.alpha, self.loc_weight)
-        return "LossSpec(kind=%r, neg_pos_ratio=%d, loc_weight=%r)" % (self.kind, self.neg_pos_ratio, self.loc_weight)
+            return "LossSpec(kind=%r, gamma=%r, alpha=%r, loc_weight=%r%s)" % (self.kind, self.gamma, self.alpha, self.loc_weight, box)
+        return "LossSpec(kind=%r, neg_pos_ratio=%d, loc_weight=%r%s)" % (self.kind, self.neg_pos_ratio, self.loc_weight, box)
 
 
 class L2NormSpec:
@@ -616,22 +630,40 @@ def batchnorm_bwd(dy, x, gamma, mean, rstd, out=None, dgamma=None, dbeta=None, w
 _multibox_ws = MatchWorkspace()
 
 
-def _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight):
+def _box_priors(spec, priors, A, device):
+    """The priors argument of the _box entries: a PriorSet or an f64 [A,4] device tensor, required by the IoU kinds (ValueError
+    without it, or with another shape); None stays None for smooth L1, which does not read it."""
+    if priors is None:
+        if spec.box != "smooth_l1":
+            raise ValueError("box=%r needs priors (a PriorSet or an f64 [A,4] device tensor)" % (spec.box,))
+        return None
+    t = priors.priors if isinstance(priors, PriorSet) else priors
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != (A, 4):
+        raise ValueError("priors must be a PriorSet or a tensor of shape [%d, 4], not %r" % (A, getattr(t, "shape", t)))
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.device != device:
+        raise ValueError("priors must be a contiguous float64 tensor on %s, not %s on %s" % (device, t.dtype, t.device))
+    return t
+
+
+def _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight, box="smooth_l1"):
     B, A, C = conf.shape
     assert conf.is_cuda and conf.is_contiguous() and loc.is_contiguous()
     assert loc.shape == (B, A, 4) and gt_loc.shape == (B, A, 4)
     assert gt_cls.shape == (B, A) and gt_mask.shape == (B, A)
     _dev(gt_cls, torch.int32); _dev(gt_loc, torch.float32); _dev(gt_mask, torch.uint8)
-    spec = LossSpec("multibox", neg_pos_ratio, loc_weight)         # ValueError for bad values, before anything is allocated
+    spec = LossSpec("multibox", neg_pos_ratio, loc_weight, box=box)     # ValueError for bad values, before anything is allocated
     return B, A, C, spec
 
 
-def multibox_loss(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio=3, loc_weight=1.0, grad_scale=1.0, ws=None):
-    """ssd_multibox_loss_fwd_bwd: the SSD paper's loss (per-image hard-negative mining, smooth L1, every term over P) and its
+def multibox_loss(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio=3, loc_weight=1.0, grad_scale=1.0, ws=None,
+                  box="smooth_l1", priors=None):
+    """ssd_multibox_loss_box_fwd_bwd: the SSD paper's loss (per-image hard-negative mining, smooth L1, every term over P) and its
     gradient.  Arguments as ssd_loss.  Returns (out8 f32[8] device tensor, dconf, dloc); out8 = loc, pos, neg, total, P, N,
-    tau_min, status."""
+    tau_min, status.  box: "smooth_l1", or "giou" / "diou" / "ciou" of the boxes decoded with `priors` (a PriorSet or an f64
+    [A,4] device tensor; ValueError without them)."""
     L = _lib.lib()
-    B, A, C, spec = _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight)
+    B, A, C, spec = _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight, box)
+    pri = _box_priors(spec, priors, A, conf.device)
     assert conf.dtype == loc.dtype and conf.dtype in (torch.float32, torch.bfloat16)
     dtype = 0 if conf.dtype == torch.float32 else 1
     out = torch.empty((8,), dtype=torch.float32, device=conf.device)
@@ -640,47 +672,53 @@ def multibox_loss(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio=3, loc_weigh
     wsobj = ws or _multibox_ws
     wbuf = wsobj.get(L.ssd_multibox_loss_workspace_bytes(B, A, C), conf.device)
     wsobj.clean_key = None                         # (a buffer shared with ssd_loss_heads no longer holds its zeroed words)
-    _lib.check(L.ssd_multibox_loss_fwd_bwd(_ptr(conf), _ptr(loc), dtype, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A, C,
-                                           spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out), _ptr(dconf),
-                                           _ptr(dloc), _ptr(wbuf), wbuf.numel(), _stream()))
+    _lib.check(L.ssd_multibox_loss_box_fwd_bwd(_ptr(conf), _ptr(loc), dtype, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A, C,
+                                               spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out), _ptr(dconf),
+                                               _ptr(dloc), _ptr(wbuf), wbuf.numel(), _stream(), spec.box_kind,
+                                               None if pri is None else _ptr(pri)))
     return out, dconf, dloc
 
 
-def multibox_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, neg_pos_ratio=3, loc_weight=1.0, grad_scale=1.0, ws=None):
-    """ssd_multibox_loss_fwd_bwd_heads: the loss of multibox_loss with its gradient as compact per-level pixel rows in `hgb`
+def multibox_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, neg_pos_ratio=3, loc_weight=1.0, grad_scale=1.0, ws=None,
+                        box="smooth_l1", priors=None):
+    """ssd_multibox_loss_box_fwd_bwd_heads: the loss of multibox_loss with its gradient as compact per-level pixel rows in `hgb`
     (HeadGradBuffers; bf16 only).  Returns out8 (device f32[8])."""
     L = _lib.lib()
-    B, A, C, spec = _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight)
+    B, A, C, spec = _multibox_args(conf, loc, gt_cls, gt_loc, gt_mask, neg_pos_ratio, loc_weight, box)
+    pri = _box_priors(spec, priors, A, conf.device)
     assert conf.dtype == loc.dtype == torch.bfloat16 and hgb.B == B
     out = torch.empty((8,), dtype=torch.float32, device=conf.device)
     wsobj = ws or _multibox_ws
     wbuf = wsobj.get(L.ssd_multibox_loss_heads_workspace_bytes(B, A, C), conf.device)
     wsobj.clean_key = None
-    _lib.check(L.ssd_multibox_loss_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A, C,
-                                                 spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out),
-                                                 ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream()))
+    _lib.check(L.ssd_multibox_loss_box_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A,
+                                                     C, spec.neg_pos_ratio, spec.loc_weight, float(grad_scale), _ptr(out),
+                                                     ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream(), spec.box_kind,
+                                                     None if pri is None else _ptr(pri)))
     return out
 
 
 _focal_ws = MatchWorkspace()
 
 
-def _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight):
+def _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight, box="smooth_l1"):
     B, A, C = conf.shape
     assert conf.is_cuda and conf.is_contiguous() and loc.is_contiguous()
     assert loc.shape == (B, A, 4) and gt_loc.shape == (B, A, 4)
     assert gt_cls.shape == (B, A) and gt_mask.shape == (B, A)
     _dev(gt_cls, torch.int32); _dev(gt_loc, torch.float32); _dev(gt_mask, torch.uint8)
-    spec = LossSpec("softmax_focal", loc_weight=loc_weight, gamma=gamma, alpha=alpha)     # ValueError before anything is allocated
+    spec = LossSpec("softmax_focal", loc_weight=loc_weight, gamma=gamma, alpha=alpha, box=box)   # ValueError before anything is allocated
     return B, A, C, spec
 
 
-def softmax_focal_loss(conf, loc, gt_cls, gt_loc, gt_mask, gamma=2.0, alpha=0.25, loc_weight=1.0, grad_scale=1.0, ws=None):
-    """ssd_softmax_focal_loss_fwd_bwd: the softmax focal loss over every anchor (background = class C-1; alpha=-1: no class
-    balance), the MultiBox box term, every term over P, and its gradient.  Arguments as ssd_loss.  Returns (out8 f32[8] device
-    tensor, dconf, dloc); out8 = loc, pos, neg, total, P, N = B*A - P, 0, status."""
+def softmax_focal_loss(conf, loc, gt_cls, gt_loc, gt_mask, gamma=2.0, alpha=0.25, loc_weight=1.0, grad_scale=1.0, ws=None,
+                       box="smooth_l1", priors=None):
+    """ssd_softmax_focal_loss_box_fwd_bwd: the softmax focal loss over every anchor (background = class C-1; alpha=-1: no class
+    balance), the MultiBox box term (`box`, `priors`: as multibox_loss), every term over P, and its gradient.  Arguments as
+    ssd_loss.  Returns (out8 f32[8] device tensor, dconf, dloc); out8 = loc, pos, neg, total, P, N = B*A - P, 0, status."""
     L = _lib.lib()
-    B, A, C, spec = _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight)
+    B, A, C, spec = _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight, box)
+    pri = _box_priors(spec, priors, A, conf.device)
     assert conf.dtype == loc.dtype and conf.dtype in (torch.float32, torch.bfloat16)
     dtype = 0 if conf.dtype == torch.float32 else 1
     out = torch.empty((8,), dtype=torch.float32, device=conf.device)
@@ -689,26 +727,29 @@ def softmax_focal_loss(conf, loc, gt_cls, gt_loc, gt_mask, gamma=2.0, alpha=0.25
     wsobj = ws or _focal_ws
     wbuf = wsobj.get(L.ssd_softmax_focal_loss_workspace_bytes(B, A, C), conf.device)
     wsobj.clean_key = None                         # (a buffer shared with ssd_loss_heads no longer holds its zeroed words)
-    _lib.check(L.ssd_softmax_focal_loss_fwd_bwd(_ptr(conf), _ptr(loc), dtype, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A,
-                                                C, spec.gamma, spec.alpha, spec.loc_weight, float(grad_scale), _ptr(out),
-                                                _ptr(dconf), _ptr(dloc), _ptr(wbuf), wbuf.numel(), _stream()))
+    _lib.check(L.ssd_softmax_focal_loss_box_fwd_bwd(_ptr(conf), _ptr(loc), dtype, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B, A,
+                                                    C, spec.gamma, spec.alpha, spec.loc_weight, float(grad_scale), _ptr(out),
+                                                    _ptr(dconf), _ptr(dloc), _ptr(wbuf), wbuf.numel(), _stream(), spec.box_kind,
+                                                    None if pri is None else _ptr(pri)))
     return out, dconf, dloc
 
 
 def softmax_focal_loss_heads(conf, loc, gt_cls, gt_loc, gt_mask, hgb, gamma=2.0, alpha=0.25, loc_weight=1.0, grad_scale=1.0,
-                             ws=None):
-    """ssd_softmax_focal_loss_fwd_bwd_heads: the loss of softmax_focal_loss with its gradient as per-level pixel rows in `hgb`
+                             ws=None, box="smooth_l1", priors=None):
+    """ssd_softmax_focal_loss_box_fwd_bwd_heads: the loss of softmax_focal_loss with its gradient as per-level pixel rows in `hgb`
     (HeadGradBuffers; bf16 only): every pixel is a row, the maps are the identity.  Returns out8 (device f32[8])."""
     L = _lib.lib()
-    B, A, C, spec = _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight)
+    B, A, C, spec = _softmax_focal_args(conf, loc, gt_cls, gt_loc, gt_mask, gamma, alpha, loc_weight, box)
+    pri = _box_priors(spec, priors, A, conf.device)
     assert conf.dtype == loc.dtype == torch.bfloat16 and hgb.B == B
     out = torch.empty((8,), dtype=torch.float32, device=conf.device)
     wsobj = ws or _focal_ws
     wbuf = wsobj.get(L.ssd_softmax_focal_loss_heads_workspace_bytes(B, A, C), conf.device)
     wsobj.clean_key = None
-    _lib.check(L.ssd_softmax_focal_loss_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B,
-                                                      A, C, spec.gamma, spec.alpha, spec.loc_weight, float(grad_scale),
-                                                      _ptr(out), ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream()))
+    _lib.check(L.ssd_softmax_focal_loss_box_fwd_bwd_heads(_ptr(conf), _ptr(loc), 1, _ptr(gt_cls), _ptr(gt_loc), _ptr(gt_mask), B,
+                                                          A, C, spec.gamma, spec.alpha, spec.loc_weight, float(grad_scale),
+                                                          _ptr(out), ctypes.byref(hgb.c), _ptr(wbuf), wbuf.numel(), _stream(),
+                                                          spec.box_kind, None if pri is None else _ptr(pri)))
     return out
 
 

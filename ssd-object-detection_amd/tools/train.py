@@ -91,26 +91,28 @@ def _loss_section(config):
 
 
 def loss_from_config(config):
-    """`model: train: loss: {kind, neg_pos_ratio, loc_weight}` or `{kind: softmax_focal, gamma, alpha, loc_weight,
+    """`model: train: loss: {kind, neg_pos_ratio, loc_weight, box}` or `{kind: softmax_focal, gamma, alpha, loc_weight, box,
     background_prior}` (no reference counterpart) -> ops.LossSpec, or None when the section is absent: the default run trains
     with the reference's loss.  kind "multibox" is the SSD paper's loss, "softmax_focal" the softmax focal loss over every
     anchor.  ValueError for an unknown key, an unknown kind, bad values, or a key of another kind: gamma, alpha and
-    background_prior belong to softmax_focal alone, neg_pos_ratio to the mined losses.  background_prior itself is read by
-    background_prior_from_config."""
+    background_prior belong to softmax_focal alone, neg_pos_ratio to the mined losses, box (smooth_l1 | giou | diou | ciou: the
+    box term) to multibox and softmax_focal.  background_prior itself is read by background_prior_from_config."""
     section = _loss_section(config)
     if section is None:
         return None
     focal_keys = {"gamma", "alpha", "background_prior"}
-    unknown = set(section) - {"kind", "neg_pos_ratio", "loc_weight"} - focal_keys
+    unknown = set(section) - {"kind", "neg_pos_ratio", "loc_weight", "box"} - focal_keys
     if unknown:
         raise ValueError("unknown model.train.loss keys: %s" % sorted(unknown))
     kind = section.get("kind", "reference")
     foreign = set(section) & ({"neg_pos_ratio"} if kind == "softmax_focal" else focal_keys)
+    if kind == "reference":
+        foreign |= set(section) & {"box"}
     if foreign:
         raise ValueError("model.train.loss keys %s do not apply to the loss kind %r" % (sorted(foreign), kind))
     from ..ops import LossSpec
     return LossSpec(kind=kind, neg_pos_ratio=section.get("neg_pos_ratio", 3), loc_weight=section.get("loc_weight", 1.0),
-                    gamma=section.get("gamma", 2.0), alpha=section.get("alpha", 0.25))
+                    gamma=section.get("gamma", 2.0), alpha=section.get("alpha", 0.25), box=section.get("box", "smooth_l1"))
 
 
 def background_prior_from_config(config):
