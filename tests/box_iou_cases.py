@@ -6,7 +6,10 @@ anchor of the last image is one (a positive in the last row of a ragged last row
 
 The losses have kinks where the gradient jumps: the four corner ties (x1 = X1, ...), iw = 0, ih = 0 and |t2|, |t3| = W.  A float32
 evaluation may fall on the other side of one, so a positive closer to a kink than 1e-3 of the smallest of (w, h, gw, gh) --
-1e-3 absolute for the clamp -- is drawn again.  make_case asserts that fewer than 2 % of the first draws needed it."""
+1e-3 absolute for the clamp -- is drawn again.  make_case asserts that fewer than 2 % of the first draws needed it.
+
+So these cases never hand a kernel a tie, a touching pair, pred == target or a clamped log-size.  tests/box_iou_edge_cases.py is
+where the kinks are met on purpose, with operands that decide every comparison exactly (tests/test_box_iou_edges_gpu.py)."""
 import functools
 
 import numpy as np
@@ -91,3 +94,12 @@ def dloc_bound(ref, bf16=False):
     bound is not achievable: a component near zero is a difference of terms of the size of the largest); a bf16 output adds its
     rounding, the project's 4e-3 |ref| per element.  0 off the positives: exact zeros."""
     return 1e-4 * np.abs(ref).max(axis=-1, keepdims=True) + (4e-3 * np.abs(ref) if bf16 else 0.0)
+
+
+def dloc_bound_floored(ref, scale, bf16=False):
+    """dloc_bound with a floor, for the inputs of tests/box_iou_edge_cases.py: per anchor 1e-4 * scale * max(largest |component| of
+    the row's gradient, 1), where ref [..., 4] = scale * gradient and scale = grad_scale * loc_weight / P.  The floor is derived:
+    at identical boxes GIoU's gradient is the difference of two terms that are each w dIoU/dw = 1 (DIoU's value there), so the
+    row's own largest component is about 0 and says nothing about the size of what was subtracted.  Where a row's largest
+    component is 1 or more this is dloc_bound.  bf16 adds its rounding, 4e-3 |ref| per element."""
+    return 1e-4 * np.maximum(np.abs(ref).max(axis=-1, keepdims=True), scale) + (4e-3 * np.abs(ref) if bf16 else 0.0)

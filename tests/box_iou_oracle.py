@@ -12,7 +12,11 @@ Per positive, prior size (d_w, d_h), prediction t, target g, W = log(1000 / 16);
     ciou: L = diou + alpha v, v = (4 / pi^2) (atan(gw / gh) - atan(w / h))^2, alpha = v / ((1 - IoU) + v) where v > 0 else 0,
           alpha a constant in the gradient, dv/dw and dv/dh the true derivatives
 The tie rule: max(p, q) and min(p, q) pass the gradient to the predicted coordinate (p) only under the strict comparison
-(p > q, p < q); max(0, .) only where its argument is > 0; the clamp only where |t| < W.  No epsilons."""
+(p > q, p < q); max(0, .) only where its argument is > 0; the clamp only where |t| < W.  No epsilons.
+
+rows(..., relax=) restates the rule with ONE comparison family made non-strict (RELAX): what a kernel with a `>=` for a `>` would
+compute.  tests/test_box_iou_edges_cpu.py uses it to show that the inputs of tests/box_iou_edge_cases.py tell such a kernel from
+the rule; nothing else may pass it."""
 import numpy as np
 
 from tests import multibox_oracle as M
@@ -20,11 +24,18 @@ from tests import softmax_focal_oracle as F
 
 KINDS = ("giou", "diou", "ciou")
 W = float(np.log(1000.0 / 16.0))
+RELAX = ("intersection", "hull", "positive", "clamp")     # the corner indicators a, the corner indicators b, iwr / ihr >= 0, |t| <= W
 
 
-def rows(kind, prior_wh, t, g, dtype=np.float64):
-    """prior_wh [n,2], t [n,4], g [n,4] -> (L [n], dL/dt [n,4]), every operation in `dtype`."""
+def rows(kind, prior_wh, t, g, dtype=np.float64, relax=None):
+    """prior_wh [n,2], t [n,4], g [n,4] -> (L [n], dL/dt [n,4]), every operation in `dtype`.  relax: None (the rule) or one of
+    RELAX, the family of comparisons that also passes the gradient at equality (a mutation, for the tests of the tests)."""
     assert kind in KINDS, kind
+    assert relax is None or relax in RELAX, relax
+    lt, gt = (np.less_equal, np.greater_equal) if relax == "intersection" else (np.less, np.greater)
+    hlt, hgt = (np.less_equal, np.greater_equal) if relax == "hull" else (np.less, np.greater)
+    pos = np.greater_equal if relax == "positive" else np.greater
+    inside = np.less_equal if relax == "clamp" else np.less
     f = dtype
     prior_wh, t, g = (np.asarray(x, dtype=f) for x in (prior_wh, t, g))
     half, one, two, zero, Wf = f(0.5), f(1.0), f(2.0), f(0.0), f(W)
@@ -43,9 +54,9 @@ def rows(kind, prior_wh, t, g, dtype=np.float64):
         iou = I / U
         cw, ch = np.maximum(x2, X2) - np.minimum(x1, X1), np.maximum(y2, Y2) - np.minimum(y1, Y1)
         ind = lambda c: np.where(c, one, zero).astype(f)
-        ax2, ax1 = ind((iwr > 0) & (x2 < X2)), ind((iwr > 0) & (x1 > X1))
-        ay2, ay1 = ind((ihr > 0) & (y2 < Y2)), ind((ihr > 0) & (y1 > Y1))
-        bx2, bx1, by2, by1 = ind(x2 > X2), ind(x1 < X1), ind(y2 > Y2), ind(y1 < Y1)
+        ax2, ax1 = ind(pos(iwr, zero) & lt(x2, X2)), ind(pos(iwr, zero) & gt(x1, X1))
+        ay2, ay1 = ind(pos(ihr, zero) & lt(y2, Y2)), ind(pos(ihr, zero) & gt(y1, Y1))
+        bx2, bx1, by2, by1 = ind(hgt(x2, X2)), ind(hlt(x1, X1)), ind(hgt(y2, Y2)), ind(hlt(y1, Y1))
         z = np.zeros_like(w)
         # derivatives with respect to cx, cy, w, h
         dI = [ih * (ax2 - ax1), iw * (ay2 - ay1), half * ih * (ax2 + ax1), half * iw * (ay2 + ay1)]
@@ -75,8 +86,8 @@ def rows(kind, prior_wh, t, g, dtype=np.float64):
                 s = alpha * (two * kpi) * da / (w * w + h * h)
                 dq[2] = dq[2] - s * h
                 dq[3] = dq[3] + s * w
-        grad = np.stack([dw * dq[0], dh * dq[1], np.where(np.abs(t[:, 2]) < Wf, w * dq[2], zero),
-                         np.where(np.abs(t[:, 3]) < Wf, h * dq[3], zero)], axis=1).astype(f)
+        grad = np.stack([dw * dq[0], dh * dq[1], np.where(inside(np.abs(t[:, 2]), Wf), w * dq[2], zero),
+                         np.where(inside(np.abs(t[:, 3]), Wf), h * dq[3], zero)], axis=1).astype(f)
     return L.astype(f), grad
 
 

@@ -5,7 +5,11 @@ for bit, statuses 1 and 3, reproducibility and the absence of host synchronisati
 
 Bounds: the scalars within 1e-4 relative (the header's rule for the loss kernels), P and N exact, f32 dloc per anchor within
 1e-4 of the anchor's largest reference component (tests/test_box_iou_cpu.py shows that a float32 evaluation meets a third of it),
-bf16 adds 4e-3 |ref| per element (tests/test_multibox_gpu.py's figure), dconf bit-identical to the smooth-L1 call's."""
+bf16 adds 4e-3 |ref| per element (tests/test_multibox_gpu.py's figure), dconf bit-identical to the smooth-L1 call's.
+
+The inputs here keep away from the losses' kinks (box_iou_cases.near_kink), so the header's tie rule -- strict comparisons, the
+clamp's zero gradient, the guard at pred == target -- is not what these tests run: tests/test_box_iou_edges_gpu.py meets the
+kinks on purpose, on the inputs of tests/box_iou_edge_cases.py."""
 import ctypes
 
 import numpy as np
