@@ -4,7 +4,8 @@ at the front of image 0 -- each once as a positive and once as a background anch
     "below"   z_t 12 below every other logit (confident and wrong)
     "equal"   all logits equal
     "twomax"  two equal maxima, one of them the target
-and, with B >= 2, a last image without positives beside images with them."""
+and, with B >= 2, a last image without positives beside images with them.
+extreme_case: rows beyond the +-16 clip -- logit gaps of 30 .. 120, where q == 0 and p_t == 0 exactly in float32."""
 import functools
 
 import numpy as np
@@ -60,6 +61,43 @@ def make_case(B, A, C, bf16=False, seed=0):
     for arr in (conf, loc, gt_loc, gt_cls):
         arr.setflags(write=False)
     return dict(B=B, A=A, C=C, conf=conf, loc=loc, gt_loc=gt_loc, gt_cls=gt_cls, gt_mask=mask.astype(np.uint8), designed=designed)
+
+
+EXTREME_GAPS = (30.0, 88.0, 104.0, 120.0)                                # all exact in bf16 next to logits that are multiples of 1/2
+EXTREME_CLASSES = (2, 3, 21, 81, 303)
+EXTREME_GAMMAS, EXTREME_ALPHAS = (0.0, 0.5, 1.0, 2.0, 8.0), (-1.0, 0.0, 0.25, 1.0)
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_case(C, seed=0):
+    """B = 1, A = 16: for every gap of EXTREME_GAPS a row whose target logit lies that far ABOVE every other logit (at 104 and 120
+    Q underflows and q == 0 exactly in float32: the h = 1 branch; at 30 q ~ 1e-11 on the log1p branch) and one whose target lies
+    that far BELOW (p_t == 0 exactly, q == 1), each once as a positive and once as a background anchor.  The other logits are
+    multiples of 1/2 in [-4, 4], so every logit is a bfloat16 value.  P = 8.  Adds "rows": [(anchor, gap, side, positive)]."""
+    rng = np.random.default_rng(7000 + C + seed)
+    A = 4 * len(EXTREME_GAPS)
+    conf = (rng.integers(-8, 9, (1, A, C)) / 2.0).astype(np.float32)
+    loc = (rng.integers(-8, 9, (1, A, 4)) / 4.0).astype(np.float32)
+    gt_loc = (rng.integers(-8, 9, (1, A, 4)) / 4.0).astype(np.float32)
+    mask = np.zeros((1, A), dtype=bool)
+    gt_cls = rng.integers(0, C - 1, (1, A)).astype(np.int32)
+    rows = []
+    a = 0
+    for gap in EXTREME_GAPS:
+        for side in ("above", "below"):
+            for positive in (True, False):
+                mask[0, a] = positive
+                t = int(gt_cls[0, a]) if positive else C - 1
+                z = conf[0, a]
+                others = np.arange(C) != t
+                z[t] = z[others].max() + gap if side == "above" else z[others].min() - gap
+                rows.append((a, gap, side, positive))
+                a += 1
+    gt_cls[~mask] = 0x7fffff
+    assert np.array_equal(to_bf16(conf), conf) and np.array_equal(to_bf16(loc), loc)
+    for arr in (conf, loc, gt_loc, gt_cls):
+        arr.setflags(write=False)
+    return dict(B=1, A=A, C=C, conf=conf, loc=loc, gt_loc=gt_loc, gt_cls=gt_cls, gt_mask=mask.astype(np.uint8), rows=tuple(rows))
 
 
 def dconf_bound(ref, bf16=False):

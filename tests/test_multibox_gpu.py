@@ -55,11 +55,14 @@ def check_against_oracle(ops, r, ratio=3, alpha=1.0, gs=1.0):
     same = ~flips
     scale = np.abs(ref["dcls"]).max()
     err = np.abs(d[same] - ref["dcls"][same]).max()
-    print("dconf err / scale", err / scale)
+    print("dconf err / scale", err / scale, "flips", int(flips.sum()))
     assert err <= 2e-5 * scale + (0 if r["dtype"] == F32 else 4e-3 * scale)
     dl = dloc.float().cpu().numpy().astype(np.float64)
     lscale = np.abs(ref["dbox"]).max()
     print("dloc err / scale", np.abs(dl - ref["dbox"]).max() / lscale)
+    print("error / bound: scalars", max(abs(out[i] - ref[k]) / max(1e-4 * abs(ref[k]), 1e-300) for i, k in enumerate(["loc", "pos", "neg", "total"])),
+          "dconf", err / (2e-5 * scale + (0 if r["dtype"] == F32 else 4e-3 * scale)),
+          "dloc", np.abs(dl - ref["dbox"]).max() / ((1e-6 if r["dtype"] == F32 else 4e-3) * lscale))
     assert np.abs(dl - ref["dbox"]).max() <= (1e-6 if r["dtype"] == F32 else 4e-3) * lscale
     assert not dl[~pos].any() and not d[~pos & ~rows_got].any()        # exact zeros everywhere else
     return out, ref

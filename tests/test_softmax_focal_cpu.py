@@ -146,6 +146,41 @@ def test_float32_stable_form_meets_the_bound_and_the_naive_forms_do_not(C, gamma
         assert r.max() > 1.0, variant
 
 
+@pytest.mark.parametrize("C", K.EXTREME_CLASSES)
+def test_float32_stable_form_meets_the_bound_on_the_extreme_rows(C):
+    """Logit gaps of 30 .. 120 (K.extreme_case): a plain float32 evaluation of the stable form stays finite and inside the GPU
+    test's bound, 1e-4 |ref| + 2^-100 on the gradient and the same form on FL, for every gamma (0 and the bound 8 included) and
+    every alpha (0 and 1: one side's weight exactly zero).  In float32 the rows hold q == 0 exactly (the h = 1 branch) and
+    p_t == 0 exactly (q == 1)."""
+    c = K.extreme_case(C)
+    z = c["conf"].reshape(-1, C)
+    mask = c["gt_mask"].astype(bool).reshape(-1)
+    t = np.where(mask, c["gt_cls"].reshape(-1), C - 1).astype(np.int64)
+    idx = np.arange(z.shape[0])
+    for a, gap, side, positive in c["rows"]:
+        rest = np.delete(z[a], t[a])
+        assert bool(mask[a]) == positive and np.abs(rest).max() <= 4.0
+        assert (z[a, t[a]] - rest.max() == gap) if side == "above" else (rest.min() - z[a, t[a]] == gap)
+    e32 = np.exp(z - z.max(1, keepdims=True))                            # float32
+    pt32 = e32[idx, t] / e32.sum(1, dtype=np.float32)
+    worst = 0.0
+    for gamma in K.EXTREME_GAMMAS:
+        for alpha in K.EXTREME_ALPHAS:
+            fl, ref, _ = F.rows(z, t, gamma, alpha)
+            with np.errstate(all="raise", under="ignore"):                # no overflow, no invalid operation, no division by zero
+                fl32, got, q32 = F.rows(z, t, gamma, alpha, np.float32)
+            assert np.isfinite(fl32).all() and np.isfinite(got).all() and np.isfinite(ref).all()
+            assert (q32 == 0).any() and (pt32 == 0).any() and (q32[pt32 == 0] == 1).all()
+            r = max(float((np.abs(got.astype(np.float64) - ref) / K.dconf_bound(ref)).max()),
+                    float((np.abs(fl32.astype(np.float64) - fl) / K.dconf_bound(fl)).max()))
+            worst = max(worst, r)
+            assert r <= 1.0, (gamma, alpha, r)
+            if alpha in (0.0, 1.0):                                       # the zero-weight side: exact zeros in both evaluations
+                side = mask if alpha == 0.0 else ~mask
+                assert not got[side].any() and not ref[side].any() and not fl32[side].any()
+    print("C", C, "extreme rows, stable f32: worst error / bound", worst)
+
+
 def test_cases_hold_the_designed_rows():
     for shape in K.SHAPES:
         for bf16 in (False, True):

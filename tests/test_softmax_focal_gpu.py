@@ -1,6 +1,7 @@
 """GPU: the softmax focal loss (ssd_softmax_focal_loss_fwd_bwd and its rows form) against the float64 oracle of
 tests/softmax_focal_oracle.py on the inputs of tests/softmax_focal_cases.py, an exact case under the strict harness
-(tests/strict.py), the rows form against the dense one bit for bit, reproducibility and the absence of host synchronisation.
+(tests/strict.py) in both forms, the rows form against the dense one bit for bit, rows with logit gaps up to 120 over the edges
+of gamma and alpha, reproducibility and the absence of host synchronisation.
 
 Bounds: the scalars within 1e-4 relative (the header's rule for the loss kernels), P and N exact, f32 dconf elementwise within
 1e-4 |ref| + 2^-100 (tests/test_softmax_focal_cpu.py shows that a float32 evaluation of the stable form meets it and the naive
@@ -166,12 +167,10 @@ def heads_case(ops, geom, B, C=21, seed=3, no_pos=False, nan_at=None):
     return [t.cuda() for t in (conf, loc, cls, gloc, mask)], hgb, (hw, per, npad, A)
 
 
-@pytest.mark.parametrize("geom,B", [(SSD300, 2), (SSD512, 1)], ids=["SSD300 B=2", "SSD512 B=1"])
-def test_rows_form_is_the_dense_form(ops, geom, B):
-    """every pixel is a row: identity maps, count == B * hw, channels in the head GEMM's order with zero padding; scattered back
-    the rows are the dense bf16 call's gradients bit for bit, and out8 is the same"""
-    C = 21
-    inp, hgb, (hw, per, npad, A) = heads_case(ops, geom, B, C)
+def check_rows_form(ops, geom, B, C, seed=3):
+    """the body of test_rows_form_is_the_dense_form on heads_case(geom, B, C, seed); returns the inputs and the dense call's
+    (out8, dconf, dloc) for further checks of the same case"""
+    inp, hgb, (hw, per, npad, A) = heads_case(ops, geom, B, C, seed)
     out_r = ops.softmax_focal_loss_heads(*inp, hgb, 2.0, 0.25, 1.0, 0.5)
     out_d, dconf, dloc = ops.softmax_focal_loss(*inp, 2.0, 0.25, 1.0, 0.5)
     assert torch.equal(out_r.view(I32), out_d.view(I32)) and float(out_d[7]) == 0.0
@@ -184,6 +183,109 @@ def test_rows_form_is_the_dense_form(ops, geom, B):
     sl, sc = hgb.dense(C)
     assert torch.equal(sl.view(torch.int16), dloc.view(torch.int16)) and torch.equal(sc.view(torch.int16), dconf.view(torch.int16))
     assert bool((dconf != 0).any(dim=2).all())                            # every anchor carries a gradient
+    return inp, out_d, dconf, dloc
+
+
+@pytest.mark.parametrize("geom,B", [(SSD300, 2), (SSD512, 1)], ids=["SSD300 B=2", "SSD512 B=1"])
+def test_rows_form_is_the_dense_form(ops, geom, B):
+    """every pixel is a row: identity maps, count == B * hw, channels in the head GEMM's order with zero padding; scattered back
+    the rows are the dense bf16 call's gradients bit for bit, and out8 is the same"""
+    check_rows_form(ops, geom, B, 21)
+
+
+STRICT_LEVELS = ((25, 4, 0), (9, 4, 8), (2, 6, 0), (1, 2, 0))             # (hw, per_cell, npad above its minimum): 150 anchors
+
+
+@pytest.mark.parametrize("gs", [1.0, 0.25], ids=["gs=1", "gs=0.25"])
+def test_rows_form_exact_under_the_strict_harness(lib, ops, gs):
+    """exact_case (B = 2, A = 150, C = 4, bf16) through ssd_softmax_focal_loss_fwd_bwd_heads into a strict.Arena: rows,
+    row_of_pixel, pixel_of_row, count and out8 are arena outputs, the workspace is exactly the queried size.  Expected bit for
+    bit: the rows are the dense exact gradients in the head order, the padding is zeros (level 1 has 8 padding channels although
+    4 + C = 8), both maps are the identity, count[l] = B * hw[l] and count[4:8] is untouched.  A refused call (gamma = 9; the
+    f32 dtype, which this form does not take) writes nothing."""
+    from tests.test_loss_strict_gpu import HeadBuffers
+    L = lib.lib()
+    r = exact_case(BF, gs)
+    B, A, C = r["B"], r["A"], r["C"]
+    levels = [dict(hw=hw, n=n, npad=(n * (4 + C) + 7) // 8 * 8 + extra) for hw, n, extra in STRICT_LEVELS]
+    assert sum(l["hw"] * l["n"] for l in levels) == A and levels[1]["npad"] == levels[1]["n"] * (4 + C) + 8
+    names = ("conf", "loc", "gt_cls", "gt_loc", "gt_mask")
+    want8, d0, l0 = ops.softmax_focal_loss(*[r[k].cuda() for k in names], 0.0, -1.0, 1.0, gs)
+    assert torch.equal(d0.cpu(), r["dconf"]) and torch.equal(l0.cpu(), r["dloc"])       # (by value, as the arena compares)
+    w = want8.cpu().numpy().astype(np.float64)
+    ln4 = float(np.log(4.0))
+    assert abs(w[1] - ln4) <= 1e-4 * ln4 and abs(w[2] - (B * A - 8) * ln4 / 8) <= 1e-4 * w[2] and w[4] == 8 and w[7] == 0
+    # the expectation: anchor off_l + pixel * n + slot of image b lives in row b * hw + pixel of level l
+    want_rows, off = [], 0
+    for l in levels:
+        hw, n, npad = l["hw"], l["n"], l["npad"]
+        rows = torch.zeros((B, hw, npad), dtype=BF)
+        rows[:, :, :n * 4] = r["dloc"][:, off:off + hw * n].reshape(B, hw, n * 4)
+        rows[:, :, n * 4:n * (4 + C)] = r["dconf"][:, off:off + hw * n].reshape(B, hw, n * C)
+        want_rows.append(rows.reshape(B * hw, npad))
+        off += hw * n
+    nb = lambda t: t.numel() * t.element_size()
+    ws_bytes = L.ssd_softmax_focal_loss_heads_workspace_bytes(B, A, C)
+    a = strict.Arena("cuda", strict.Arena.bytes_for(*[nb(r[k]) for k in names], *HeadBuffers.bytes(dict(B=B, levels=levels)), ws_bytes))
+    conf, loc, cls, gloc, mask = [a.put(r[k], k) for k in names]
+    out8 = a.out((8,), F32, "out8")
+    hb = HeadBuffers(a, lib, dict(B=B, levels=levels))
+    ws = a.workspace().get(ws_bytes, "cuda")
+
+    def call(gamma, dtype=1):
+        return L.ssd_softmax_focal_loss_fwd_bwd_heads(ptr(conf), ptr(loc), dtype, ptr(cls), ptr(gloc), ptr(mask), B, A, C, gamma,
+                                                      -1.0, 1.0, gs, ptr(out8), ctypes.byref(hb.c), ptr(ws), ws_bytes, stream())
+
+    def fn():
+        assert call(0.0) == 0
+    counts = torch.zeros((8,), dtype=I32)
+    counts[:len(levels)] = torch.tensor([B * l["hw"] for l in levels], dtype=I32)
+    expect = [(out8, want8), (hb.count, counts, torch.arange(8) < len(levels))]
+    for i, l in enumerate(levels):
+        ident = torch.arange(B * l["hw"], dtype=I32)
+        expect += [(hb.rop[i], ident), (hb.por[i], ident), (hb.rows[i], want_rows[i])]
+    a.run(fn, expect)
+
+    def refused():
+        assert call(9.0) == lib.SSD_ERR_VALUE
+        assert call(0.0, dtype=0) == lib.SSD_ERR_UNSUPPORTED
+    a.run(refused, [])                                                    # every output keeps its poison
+
+
+# ---------------------------------------------------------------------------------------------------- extreme rows
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", K.EXTREME_CLASSES)
+def test_extreme_rows_stay_finite_and_inside_the_bound(ops, C, dtype):
+    """K.extreme_case: logit gaps of 30 .. 120, the target above (q == 0 exactly at 104 and 120: the h = 1 branch the header
+    promises to be finite) or below (p_t == 0, q == 1), over gamma 0 .. 8 (the bound) and alpha -1, 0, 0.25, 1.  Every scalar and
+    gradient element is finite, the status is 0, the bounds are those of test_dense_against_the_oracle.  With alpha == 1 the
+    background rows of dconf are exact zeros and L_neg == 0; with alpha == 0 the same holds for the positives and L_pos.
+    The device's expf may flush the denormal e^-88 (and the e^-104 that numpy rounds up to the smallest one): the difference
+    reaches dconf as less than 1e-37, which the bound's 2^-100 floor covers -- nothing is widened for it."""
+    bf16 = dtype == BF
+    c = K.extreme_case(C)
+    conf, loc, cls, gloc, mask = upload(c, dtype)
+    assert np.array_equal(conf.float().cpu().numpy(), c["conf"]) and np.array_equal(loc.float().cpu().numpy(), c["loc"])
+    pos = c["gt_mask"].astype(bool)
+    worst = 0.0
+    for gamma in K.EXTREME_GAMMAS:
+        for alpha in K.EXTREME_ALPHAS:
+            where = (C, gamma, alpha)
+            ref = F.softmax_focal_loss(c["gt_cls"], c["gt_loc"], c["gt_mask"], c["loc"], c["conf"], gamma, alpha, 0.5, 1.0)
+            out8, dconf, dloc = ops.softmax_focal_loss(conf, loc, cls, gloc, mask, gamma, alpha, 0.5, 1.0)
+            o = out8.cpu().numpy().astype(np.float64)
+            got = dconf.float().cpu().numpy().astype(np.float64)
+            assert np.isfinite(o).all() and np.isfinite(got).all() and bool(torch.isfinite(dloc.float()).all()), (where, o)
+            check_scalars(o, ref, where)
+            assert o[7] == 0.0 and ref["status"] == 0
+            ratio = np.abs(got - ref["dcls"]) / K.dconf_bound(ref["dcls"], bf16)
+            worst = max(worst, float(ratio.max()))
+            assert ratio.max() <= 1.0, (where, np.unravel_index(ratio.argmax(), ratio.shape), ratio.max())
+            if alpha == 1.0:
+                assert not got[~pos].any() and o[2] == 0.0 and got[pos].any(), where
+            if alpha == 0.0:
+                assert not got[pos].any() and o[1] == 0.0 and got[~pos].any(), where
+    print("C", C, "bf16" if bf16 else "f32", "extreme rows: worst dconf error / bound", worst)
 
 
 def test_status_1_and_3_in_both_forms(ops):
