@@ -974,6 +974,18 @@ int ssd_sgd_step(float* param, const float* grad, void* param_bf16, long long n,
 int ssd_sgd_momentum_step(float* param, const float* grad, float* velocity, void* param_bf16, long long n,
                           const int32_t* block_tensor, const float* scale, const float* decay, float grad_scale, float lr,
                           float momentum, int nesterov, void* stream);
+/* Exponential moving average of the parameters (no reference counterpart: TF's ExponentialMovingAverage / timm's ModelEma, the
+ * weights a detector is validated and deployed with).  Per element, in fp32, om = one_minus_decay:
+ *   e' = e + om * (p - e)
+ * ema is read and written, param is only read.  One pass behind the optimizer launch that wrote param (a slice of the flat
+ * buffer like that launch's, or all of it), 12 bytes per element, no reductions, no atomics, no workspace; nothing outside
+ * [0, n) is touched.  The compiler may contract the multiply-add into one fma, so the result is promised bit for bit only
+ * where the difference, the product and the sum are all exact.  Two factors are exact by construction: om == 1 stores param's
+ * bits (-0.0, denormals and NaN payloads included) without reading ema -- the initialisation and "restart the average" --
+ * and om == 0 leaves ema's bits as they are (nothing is launched).
+ * SSD_ERR_VALUE (nothing launched): ema or param NULL; n <= 0 or not a multiple of ssd_opt_block_elems(); one_minus_decay NaN
+ * or outside [0, 1]; the ranges [ema, ema + n) and [param, param + n) overlap. */
+int ssd_ema_step(float* ema, const float* param, long long n, float one_minus_decay, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * L2 normalisation over the channels with a learned per-channel scale (no reference counterpart: the SSD paper's layer on

@@ -172,6 +172,23 @@ __global__ __launch_bounds__(256) void k_sgd_momentum(float* __restrict__ p, con
                                                            (unsigned)f2bf_bits(pp[2]) | ((unsigned)f2bf_bits(pp[3]) << 16));
 }
 
+// Exponential moving average of the parameters: e' = e + om * (p - e), om = 1 - decay.  One pass behind the optimizer launch
+// that wrote p, 12 bytes per element.  COPY (om == 1, chosen on the host: the same for every wave) stores p's bits and never
+// reads e: e + 1 * (p - e) rounds the difference first and is not p.
+template <bool COPY>
+__global__ __launch_bounds__(256) void k_ema(float* __restrict__ e, const float* __restrict__ p, long long n, float om) {
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float4 pv = *reinterpret_cast<const float4*>(p + i);
+    if (COPY) {
+        *reinterpret_cast<float4*>(e + i) = pv;
+        return;
+    }
+    float4 ev = *reinterpret_cast<float4*>(e + i);
+    ev.x += om * (pv.x - ev.x); ev.y += om * (pv.y - ev.y); ev.z += om * (pv.z - ev.z); ev.w += om * (pv.w - ev.w);
+    *reinterpret_cast<float4*>(e + i) = ev;
+}
+
 }  // namespace
 
 extern "C" {
@@ -229,6 +246,21 @@ int ssd_sgd_momentum_step(float* param, const float* grad, float* velocity, void
     hipLaunchKernelGGL(k_sgd_momentum, dim3((unsigned)(n / OPT_BLOCK)), dim3(256), 0, (hipStream_t)stream, param, grad,
                        velocity, static_cast<unsigned short*>(param_bf16), n, block_tensor, scale, decay, grad_scale, lr,
                        momentum, nesterov);
+    return ssd_launch_status();
+}
+
+int ssd_ema_step(float* ema, const float* param, long long n, float one_minus_decay, void* stream) {
+    const float om = one_minus_decay;
+    if (!ema || !param || n <= 0 || n % OPT_BLOCK || !(om >= 0.f && om <= 1.f)) return SSD_ERR_VALUE;
+    const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema), p0 = reinterpret_cast<uintptr_t>(param);
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+    if (e0 < p0 + bytes && p0 < e0 + bytes) return SSD_ERR_VALUE;
+    if (om == 0.f) return SSD_OK;                // e + 0 * (p - e) would turn a -0.0 into +0.0: e keeps its bits, nothing to launch
+    const dim3 grid((unsigned)(n / OPT_BLOCK));
+    if (om == 1.f)
+        hipLaunchKernelGGL(k_ema<true>, grid, dim3(256), 0, (hipStream_t)stream, ema, param, n, om);
+    else
+        hipLaunchKernelGGL(k_ema<false>, grid, dim3(256), 0, (hipStream_t)stream, ema, param, n, om);
     return ssd_launch_status();
 }
 

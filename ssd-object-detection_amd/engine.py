@@ -9,6 +9,8 @@ The 3-channel image is carried in 8 zero-padded channels (first-layer weights of
 The same engine runs the SSD paper's VGG-16 SSD300 (VGG16_SSD300_TRUNK below: no reference counterpart).
 """
 import collections
+import contextlib
+import logging
 import math
 import os
 
@@ -16,6 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib, mx, ops
+
+logger = logging.getLogger(__name__)
 
 # (kind, cin, cout, k, stride, mode, feature_map)   -- mode: TF padding; every conv has ReLU
 SSD300_TRUNK = [
@@ -600,6 +604,12 @@ class SSDEngine:
     # backward() spreads its work over side streams (weight gradients, heads, optimizer buckets) around the data-gradient
     # chain on the caller's stream: what a high-priority stream for that chain is good for
     side_streams = True
+    # the exponential moving average of the weights (enable_ema): a second flat fp32 buffer, the updates it has taken, and the
+    # factor 1 - decay of the optimizer step in flight (None: the optimizer launches are followed by nothing)
+    ema = None
+    ema_updates = 0
+    ema_om = None
+    _averaged = False                          # inside `with averaged():` param and ema have changed places
 
     def __init__(self, classes=81, in_size=300, trunk=SSD300_TRUNK, num_priors=SSD300_NUM_PRIORS, device="cuda",
                  seed=0, sparse_heads=None, l2norm=None, fp8_inference=False):
@@ -1232,6 +1242,7 @@ class SSDEngine:
         The data-gradient chain (the critical path) runs on the current stream, every weight gradient on the side
         stream as soon as its input gradient exists: the split reductions and round tails of one overlap the MFMA
         work of the other.  Each launch still sums in a fixed order, so results do not depend on the overlap."""
+        self._live_only("backward()")
         if self.last_forward == "mxfp8":
             raise RuntimeError("backward() after an mxfp8 forward: it writes neither the bf16 maps nor the ReLU bits and pool "
                                "codes backward() reads; run forward(x) in bf16 first")
@@ -1317,11 +1328,13 @@ class SSDEngine:
         """clip_by_norm + Adam + bf16 / transposed copies for parameter tensors t0..t1-1 on the current stream.
         Per tensor the arithmetic is that of clip_scales() + adam() over the whole flat buffer, bit for bit.
         clip=None: the gradient is already clipped (and summed over ranks): only grad_scale (1 / world) applies."""
+        self._live_only("adam_range()")
         sl, n, bt = self._clip_scales_range(t0, t1, clip)
         _lib.check(self.L.ssd_adam_step(ops._ptr(self.param[sl]), ops._ptr(self.grad[sl]), ops._ptr(self.adam_m[sl]),
                                         ops._ptr(self.adam_v[sl]), ops._ptr(self.param_bf16[sl]), n, ops._ptr(bt),
                                         ops._ptr(self.clip_scale[t0:]) if clip is not None else None, float(grad_scale),
                                         float(lr_t), float(beta1), float(beta2), float(eps), ops._stream()))
+        self._ema_follow(sl)
         self.slots = "adam"
         self.refresh_weights(tensors=(t0, t1))
 
@@ -1346,12 +1359,14 @@ class SSDEngine:
         velocity lives in adam_m.  decay: decay_table() or None.  Per tensor the arithmetic is that of clip_scales() +
         sgd_momentum() over the whole flat buffer, bit for bit.
         clip=None: the gradient is already clipped (and summed over ranks): only grad_scale (1 / world) applies."""
+        self._live_only("sgd_range()")
         sl, n, bt = self._clip_scales_range(t0, t1, clip)
         _lib.check(self.L.ssd_sgd_momentum_step(ops._ptr(self.param[sl]), ops._ptr(self.grad[sl]), ops._ptr(self.adam_m[sl]),
                                                 ops._ptr(self.param_bf16[sl]), n, ops._ptr(bt),
                                                 ops._ptr(self.clip_scale[t0:]) if clip is not None else None,
                                                 ops._ptr(decay[t0:]) if decay is not None else None, float(grad_scale),
                                                 float(lr), float(momentum), 1 if nesterov else 0, ops._stream()))
+        self._ema_follow(sl)
         self.slots = "sgd_momentum"
         self.refresh_weights(tensors=(t0, t1))
 
@@ -1369,6 +1384,7 @@ class SSDEngine:
                                               ops._stream()))
 
     def adam(self, lr, grad, grad_scale=1.0, use_clip_scale=False, beta1=0.9, beta2=0.999, eps=1e-7):
+        self._live_only("adam()")
         self.step_count += 1
         t = self.step_count
         lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
@@ -1376,40 +1392,105 @@ class SSDEngine:
                                         ops._ptr(self.param_bf16), self.n_flat, ops._ptr(self.block_tensor),
                                         ops._ptr(self.clip_scale) if use_clip_scale else None, float(grad_scale),
                                         float(lr_t), float(beta1), float(beta2), float(eps), ops._stream()))
+        self._ema_follow()
         self.slots = "adam"
         self.refresh_weights()
 
     def sgd_momentum(self, lr, grad, grad_scale=1.0, use_clip_scale=False, momentum=0.9, nesterov=False, decay=None):
         """Momentum SGD over the whole flat buffer (ssd_sgd_momentum_step); the velocity lives in adam_m, adam_v is untouched.
         decay: decay_table() or None."""
+        self._live_only("sgd_momentum()")
         self.step_count += 1
         _lib.check(self.L.ssd_sgd_momentum_step(ops._ptr(self.param), ops._ptr(grad), ops._ptr(self.adam_m),
                                                 ops._ptr(self.param_bf16), self.n_flat, ops._ptr(self.block_tensor),
                                                 ops._ptr(self.clip_scale) if use_clip_scale else None,
                                                 ops._ptr(decay) if decay is not None else None, float(grad_scale), float(lr),
                                                 float(momentum), 1 if nesterov else 0, ops._stream()))
+        self._ema_follow()
         self.slots = "sgd_momentum"
         self.refresh_weights()
 
     def sgd(self, lr, grad, grad_scale=1.0, use_clip_scale=False):
+        self._live_only("sgd()")
         self.step_count += 1
         _lib.check(self.L.ssd_sgd_step(ops._ptr(self.param), ops._ptr(grad), ops._ptr(self.param_bf16), self.n_flat,
                                        ops._ptr(self.block_tensor), ops._ptr(self.clip_scale) if use_clip_scale else None,
                                        float(grad_scale), float(lr), ops._stream()))
+        self._ema_follow()
         self.refresh_weights()
+
+    # ---------------------------------------------------------------- averaged weights
+    def enable_ema(self):
+        """Keep an exponential moving average of the flat parameter buffer (no reference counterpart): `ema`, fp32 [n_flat],
+        starts as a bit-for-bit copy of param (ssd_ema_step with factor 1) and ema_updates at 0; called again it restarts the
+        average from the current weights.  From then on every optimizer launch (adam_range / sgd_range per bucket, adam /
+        sgd_momentum / sgd over the whole buffer) is followed, on its stream, by one ssd_ema_step over the slice it wrote with
+        the factor ema_om = 1 - decay -- while ema_om is None, and on an engine without the average, by nothing.  The caller
+        owns the schedule: it sets ema_om before an optimizer step and counts ema_updates after it (the model does, from
+        ops.EmaSpec).  The average never feeds back into param or the optimizer slots."""
+        self._live_only("enable_ema()")
+        if self.ema is None:
+            self.ema = torch.empty_like(self.param)
+        ops.ema_step(self.ema, self.param, 1.0)
+        self.ema_updates, self.ema_om = 0, None
+
+    def _ema_follow(self, sl=None):
+        """Behind an optimizer launch over param[sl] (None: the whole buffer), on the same stream: the average of that slice."""
+        if self.ema is None or self.ema_om is None:
+            return
+        e, p = (self.ema, self.param) if sl is None else (self.ema[sl], self.param[sl])
+        _lib.check(self.L.ssd_ema_step(ops._ptr(e), ops._ptr(p), p.numel(), float(self.ema_om), ops._stream()))
+
+    def _live_only(self, what):
+        if self._averaged:
+            raise RuntimeError("%s inside `with averaged():` -- the forward paths read the averaged weights there; training and "
+                               "checkpoints work on the live ones" % what)
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with eng.averaged():` -- every forward path reads the averaged weights: param and ema change places, the bf16 copy,
+        the transposed and fragment-packed copies are rebuilt from the average (refresh_weights(cast=True)) and so is the fp8
+        operand store where one is allocated; on exit the two change back and the copies are rebuilt from the live weights,
+        bit for bit what they were (each copy is a function of param alone).  On the current stream.  Inside, backward(), the
+        optimizer methods, enable_ema() and state_dict() / load_state_dict() raise RuntimeError, and so does a nested block.
+        ValueError on an engine without the average.
+        Only the flat buffer is averaged.  A batchnorm engine's gamma and beta live in it and are averaged with it; its
+        running mean and variance are not -- the averaged network normalises with the live running statistics."""
+        if self.ema is None:
+            raise ValueError("averaged() on an engine without an average: call enable_ema() first")
+        self._live_only("averaged()")
+        self._swap_average(True)
+        try:
+            yield self
+        finally:
+            self._swap_average(False)
+
+    def _swap_average(self, on):
+        self.param, self.ema = self.ema, self.param
+        self._averaged = on
+        self.refresh_weights(cast=True)
+        if self.mx_filters.allocated:                          # an fp8 forward has run: its operand store follows param_bf16
+            self._quantize_filters()
 
     # ---------------------------------------------------------------- state
     LAYOUT_VERSION = 2                         # 2: a level's loc / conf filters are separate variables (64 tensors for SSD300)
 
     def state_dict(self):
-        return dict(param=self.param.cpu(), adam_m=self.adam_m.cpu(), adam_v=self.adam_v.cpu(), step=self.step_count,
-                    names=[t.name for t in self.tensors], shapes=[t.shape for t in self.tensors],
-                    offsets=[t.offset for t in self.tensors], layout_version=self.LAYOUT_VERSION, slots=self.slots)
+        """The flat buffers, the step count and the layout they belong to; `ema` and `ema_updates` besides on an engine that
+        keeps the average (enable_ema), and only there: a plain engine's keys are what they were."""
+        self._live_only("state_dict()")
+        sd = dict(param=self.param.cpu(), adam_m=self.adam_m.cpu(), adam_v=self.adam_v.cpu(), step=self.step_count,
+                  names=[t.name for t in self.tensors], shapes=[t.shape for t in self.tensors],
+                  offsets=[t.offset for t in self.tensors], layout_version=self.LAYOUT_VERSION, slots=self.slots)
+        if self.ema is not None:
+            sd.update(ema=self.ema.cpu(), ema_updates=self.ema_updates)
+        return sd
 
     def load_state_dict(self, sd):
         """The flat buffers are only meaningful together with the layout they were saved under: names, shapes and offsets of
         every variable must match this engine's (another class count, block size or an older fused-head layout would
         otherwise load misaligned weights silently where the sizes happen to coincide)."""
+        self._live_only("load_state_dict()")
         mine = ([t.name for t in self.tensors], [tuple(t.shape) for t in self.tensors], [t.offset for t in self.tensors])
         theirs = (list(sd.get("names", [])), [tuple(x) for x in sd.get("shapes", [])], list(sd.get("offsets", [])))
         if sd.get("layout_version", 1) != self.LAYOUT_VERSION or mine != theirs or sd["param"].numel() != self.n_flat:
@@ -1427,3 +1508,11 @@ class SSDEngine:
         self.step_count = int(sd["step"])
         self.slots = slots
         self.refresh_weights(cast=True)
+        # the average: taken where this engine keeps one and the checkpoint has it; restarted from the loaded weights where the
+        # checkpoint has none; ignored by an engine that keeps none
+        if self.ema is not None and "ema" in sd:
+            self.ema.copy_(sd["ema"])
+            self.ema_updates = int(sd.get("ema_updates", 0))
+        elif self.ema is not None:
+            logger.info("checkpoint holds no averaged weights: the average restarts from the loaded parameters")
+            self.enable_ema()

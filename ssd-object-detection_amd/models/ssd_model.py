@@ -11,6 +11,7 @@ What differs from the reference, by design:
     clipped gradients are summed with one RCCL all-reduce and divided by the rank count.
   * inference adds a real NMS pass (`detect`), which the reference lacks.
 """
+import contextlib
 import logging
 import math
 import os
@@ -38,7 +39,7 @@ class SSDObjectDetectionModel:
     class TrainConfig:
         def __init__(self, epoch, batch_size, optimizer, warmup=True, warmup_optimizer=None, warmup_step=1000,
                      visualization_log_interval=10, split_batch=False, split_batch_size=4, start_epoch=0, augment=None,
-                     val=None, loss=None, clip=0.01):
+                     val=None, loss=None, clip=0.01, ema=None):
             if warmup_optimizer is None:
                 warmup_optimizer = _opt.Adam(_opt.PolynomialDecay(1e-6, 1000, 0.001))
             self.epoch = epoch
@@ -71,8 +72,16 @@ class SSDObjectDetectionModel:
                 raise ValueError("val['scoring'] must be 'best' or 'all', not %r" % (val["scoring"],))
             if val is not None and val.get("protocol", "map") not in ("map", "coco", "voc07", "voc12"):
                 raise ValueError("val['protocol'] must be 'map', 'coco', 'voc07' or 'voc12', not %r" % (val["protocol"],))
+            # ... and weights="ema" | "live" | "both" (absent: the averaged weights where the run keeps an average, else the live
+            # ones; "both": val/... from the averaged weights and val_live/... from the live ones), kept only when given
+            if val is not None and val.get("weights", "ema") not in ("ema", "live", "both"):
+                raise ValueError("val['weights'] must be 'ema', 'live' or 'both', not %r" % (val["weights"],))
             self.val = None if val is None else dict(dict(every=1, batch_size=32, score_thresh=0.05, iou_thresh=0.45,
                                                           max_dets=100, num_data=0, precision="bf16"), **val)
+            # an exponential moving average of the weights (ops.EmaSpec.of: None = off, a decay, a dict(decay, warmup) or a
+            # spec): updated behind every optimizer step, the warm-up optimizer's included; validation, evaluate / detect /
+            # detections(weights="ema") and save(weights="ema") read it
+            self.ema = ops.EmaSpec.of(ema)
 
     class Config:
         def __init__(self, classes, log_dir):
@@ -144,6 +153,8 @@ class SSDObjectDetectionModel:
         # engine (the folded fp8 one of a batchnorm network) was made from
         self._version = 0
         self._folded = None                          # (version, engine.folded())
+        self.ema_spec = None                         # ops.EmaSpec of the engine's averaged weights (enable_ema); None: no average
+        self._loaded_ema = None                      # (ema, ema_updates) of a checkpoint loaded before the average was enabled
         self.folds_built = 0
         self._prior_box = None
         self._comm_stream = None
@@ -181,6 +192,41 @@ class SSDObjectDetectionModel:
         it for `model.train.loss.background_prior`.  Under data parallelism every rank calls it (the replicas stay identical)."""
         self._engine.set_background_prior(pi)
         self._version += 1                           # a cached inference engine was made from the old biases
+
+    def enable_ema(self, spec):
+        """Keep an exponential moving average of the weights (ops.EmaSpec.of(spec); engine.enable_ema): it starts at the
+        current weights with no updates -- or, right after load() of a checkpoint that carries an average, at that average
+        and its update count.  TrainConfig(ema=...) calls this at the first step of a run that has not; called again it only
+        replaces the spec (the decay schedule), the average goes on.  Under data parallelism every rank calls it."""
+        spec = ops.EmaSpec.of(spec)
+        if spec is None:
+            raise ValueError("enable_ema needs a decay, a dict(decay, warmup) or an ops.EmaSpec, not None")
+        eng = self._engine
+        if eng.ema is None:
+            eng.enable_ema()
+            if self._loaded_ema is not None:
+                eng.ema.copy_(self._loaded_ema[0])
+                eng.ema_updates = int(self._loaded_ema[1])
+        self._loaded_ema = None
+        self.ema_spec = spec
+
+    @contextlib.contextmanager
+    def _weights(self, weights):
+        """The weights the inference calls read: "live", or "ema" -- the block runs inside engine.averaged(), and _version is
+        bumped on entry and on exit so that a cached folded network is rebuilt and never serves the other set."""
+        if weights not in ("live", "ema"):
+            raise ValueError("weights must be 'live' or 'ema', not %r" % (weights,))
+        if weights == "live":
+            yield
+            return
+        if self._engine.ema is None:
+            raise ValueError("weights='ema' on a model without averaged weights: TrainConfig(ema=...) or enable_ema() first")
+        self._version += 1
+        try:
+            with self._engine.averaged():
+                yield
+        finally:
+            self._version += 1
 
     # ------------------------------------------------------------------ input pipeline (A8)
     def _rank_world(self):
@@ -402,6 +448,11 @@ class SSDObjectDetectionModel:
             blocks = [t.nblocks for t in eng.tensors]
             self._reducer = GradReducer(eng.grad, [t.block0 * eng.block for t in eng.tensors], blocks, eng.block,
                                         lambda t0, t1: eng.clip_range_in_place(t0, t1, self._clip))
+        if getattr(cfg, "ema", None) is not None and cfg.ema is not self.ema_spec:
+            self.enable_ema(cfg.ema)
+        if self.ema_spec is not None:                  # this step's factor: every optimizer launch below is followed by the average's
+            eng.ema_om = self.ema_spec.one_minus_decay(eng.ema_updates)
+        self._loaded_ema = None                        # (a checkpoint's average nobody asked for before training went on)
         momentum = isinstance(ssd_optimizer, _opt.SGD) and ssd_optimizer.uses_slots     # the momentum / decay kernel
         decay = None
         if momentum and ssd_optimizer.weight_decay > 0.0:
@@ -507,6 +558,9 @@ class SSDObjectDetectionModel:
             self._slot_owner = ssd_optimizer
 
     def _finish_step(self, info, lr, pred_conf, pred_loc):
+        if self.ema_spec is not None:                 # the optimizer step is enqueued, the average's update behind it
+            self._engine.ema_updates += 1
+            self._engine.ema_om = None
         self._last_raw = info["raw"]                  # device f32[8] row for the sync-free scalar log (N4)
         info = {k: v for k, v in info.items() if k in ("cls loss pos", "cls loss neg", "loc loss", "status")}
         info["lr"] = lr
@@ -538,6 +592,9 @@ class SSDObjectDetectionModel:
         eng = self._engine
         sums = [eng.param.double().sum(), eng.param.double().abs().sum(), eng.adam_m.double().abs().sum(),
                 eng.adam_v.double().sum(), torch.tensor(float(eng.step_count), dtype=torch.float64, device=eng.param.device)]
+        if eng.ema is not None:                                # every rank averages the same parameters
+            sums += [eng.ema.double().sum(), eng.ema.double().abs().sum(),
+                     torch.tensor(float(eng.ema_updates), dtype=torch.float64, device=eng.param.device)]
         if getattr(eng, "batchnorm", None) is not None:       # the running statistics are state too (per rank afterwards)
             sums += [eng.bn_running_mean.double().sum(), eng.bn_running_mean.double().abs().sum(),
                      eng.bn_running_var.double().sum()]
@@ -597,7 +654,16 @@ class SSDObjectDetectionModel:
         """Validation inside a run: the kept validation split through evaluate(metric="device") on the step's stream, then
         val/mAP, val/AP50, val/AP75 in scalars.jsonl at the optimizer's step count, behind the epoch's train lines.  Data
         parallel: the replicas are identical, so every rank evaluates the whole split (no collective inside the pass) and
-        rank 0 writes."""
+        rank 0 writes.  A run that keeps averaged weights validates them (val["weights"] absent or "ema"); "live" validates the
+        live ones, "both" writes val/... for the averaged and val_live/... for the live ones (and returns the averaged)."""
+        mode = val.get("weights") or ("ema" if self._engine.ema is not None else "live")
+        if mode == "both":
+            r = self._validate_with(val, step, "ema", "val")
+            self._validate_with(val, step, "live", "val_live")
+            return r
+        return self._validate_with(val, step, mode, "val")
+
+    def _validate_with(self, val, step, weights, family):
         samples = self._val_set
         if val["num_data"] > 0:
             import itertools
@@ -607,18 +673,19 @@ class SSDObjectDetectionModel:
                 samples = _RawList(samples)
         r = self.evaluate(samples, batch_size=val["batch_size"], score_thresh=val["score_thresh"], iou_thresh=val["iou_thresh"],
                           max_dets=val["max_dets"], precision=val["precision"], metric="device",
-                          scoring=val.get("scoring", "best"), protocol=val.get("protocol", "map"))
+                          scoring=val.get("scoring", "best"), protocol=val.get("protocol", "map"), weights=weights)
+        what = "validation" if (weights, family) == ("live", "val") else "validation (%s weights)" % weights
         if val.get("protocol", "map") in ("voc07", "voc12"):
-            self._scalars.write_values("val", step, {"mAP": r["mAP"]})
-            logger.info("validation at step %d: %s mAP %.4f", step, val["protocol"], r["mAP"])
+            self._scalars.write_values(family, step, {"mAP": r["mAP"]})
+            logger.info("%s at step %d: %s mAP %.4f", what, step, val["protocol"], r["mAP"])
             return r
         if val.get("protocol", "map") == "coco":
             from ..utils.metrics import COCO_SUMMARY_KEYS
-            self._scalars.write_values("val", step, {k: r[k] for k in COCO_SUMMARY_KEYS})
-            logger.info("validation at step %d: %s", step, " ".join("%s %.4f" % (k, r[k]) for k in COCO_SUMMARY_KEYS))
+            self._scalars.write_values(family, step, {k: r[k] for k in COCO_SUMMARY_KEYS})
+            logger.info("%s at step %d: %s", what, step, " ".join("%s %.4f" % (k, r[k]) for k in COCO_SUMMARY_KEYS))
             return r
-        self._scalars.write_values("val", step, {k: r[k] for k in ("mAP", "AP50", "AP75")})
-        logger.info("validation at step %d: mAP %.4f AP50 %.4f AP75 %.4f", step, r["mAP"], r["AP50"], r["AP75"])
+        self._scalars.write_values(family, step, {k: r[k] for k in ("mAP", "AP50", "AP75")})
+        logger.info("%s at step %d: mAP %.4f AP50 %.4f AP75 %.4f", what, step, r["mAP"], r["AP50"], r["AP75"])
         return r
 
     def _log(self, step, info, cfg, stage):
@@ -638,13 +705,16 @@ class SSDObjectDetectionModel:
             raise
 
     # ------------------------------------------------------------------ inference (A9 + A9')
-    def detect(self, image, score_thresh=0.3, iou_thresh=0.45, max_cand=400, precision="bf16"):
+    def detect(self, image, score_thresh=0.3, iou_thresh=0.45, max_cand=400, precision="bf16", weights="live"):
         """image f32 [B,300,300,3] in [-1,1] -> (score, cls, box_px, keep) device tensors [B,A(,4)].
         Scoring/decoding as the reference's visualize(); `keep` adds per-class NMS (no reference counterpart).
         precision="mxfp8": the network forward runs most of its trunk on block-scaled fp8 operands (SSDEngine.forward; no
-        reference counterpart); "bf16" (default) as in training.  Any other value raises ValueError."""
-        return self._detect_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh, max_cand,
-                                     precision)
+        reference counterpart); "bf16" (default) as in training.  Any other value raises ValueError.
+        weights="ema": the network runs with the averaged weights (enable_ema / TrainConfig(ema=...); ValueError on a model
+        that keeps none); "live" (default): with the weights the last optimizer step left."""
+        with self._weights(weights):
+            return self._detect_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh,
+                                         max_cand, precision)
 
     def _forward_infer(self, x, precision):
         """(loc, conf) of the inference forward: the engine's own (running statistics for a batchnorm network); "mxfp8" on a
@@ -664,13 +734,15 @@ class SSDObjectDetectionModel:
         keep = ops.nms(score, cls, box, cand, iou_thresh, max_cand)
         return score, cls, box, keep
 
-    def detections(self, image, score_thresh=0.01, iou_thresh=0.45, max_cand=None, keep_top_k=200, precision="bf16"):
+    def detections(self, image, score_thresh=0.01, iou_thresh=0.45, max_cand=None, keep_top_k=200, precision="bf16",
+                   weights="live"):
         """image f32 [B,300,300,3] in [-1,1] -> ops.DetectPairs(n_det, score, cls, anchor, box, valid, n_cand): the compact
         multi-label detection output (ops.detect_pairs; no reference counterpart).  Every (anchor, class) pair above
         score_thresh is a candidate, so an anchor may be reported under several classes; per-class NMS over the best max_cand
-        pairs (None: the library maximum), then the best keep_top_k rows per image.  precision as detect()."""
-        return self._detections_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh, max_cand,
-                                         keep_top_k, precision)
+        pairs (None: the library maximum), then the best keep_top_k rows per image.  precision and weights as detect()."""
+        with self._weights(weights):
+            return self._detections_prepared(ops.image_prep(image.contiguous(), normalize=False), score_thresh, iou_thresh,
+                                             max_cand, keep_top_k, precision)
 
     def _detections_prepared(self, x, score_thresh, iou_thresh, max_cand=None, keep_top_k=200, precision="bf16"):
         """detections() from the prepared network input bf16 [B,S,S,8]."""
@@ -714,7 +786,8 @@ class SSDObjectDetectionModel:
             scale = np.array([float(np.shape(b[0])[1]) * float(np.shape(b[0])[0]) / s2 for b in buf], np.float64)
         return crowd, scale
 
-    def evaluate_into(self, acc, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, precision="bf16", scoring="best"):
+    def evaluate_into(self, acc, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, precision="bf16", scoring="best",
+                      weights="live"):
         """The batch loop of evaluate(metric="device"): every batch of `samples` through the network, scoring/decoding, NMS
         and acc.add (utils.device_map.DeviceMapAccumulator) on the current stream.  Host arrays reach the device through
         pinned memory; nothing in the loop reads the device or waits for it.  scoring="all": the compact rows of
@@ -722,7 +795,7 @@ class SSDObjectDetectionModel:
         (score desc, index asc) order is the rows' own.  An accumulator of the COCO protocol (DeviceCocoAccumulator) also gets
         the samples' crowd flags (a fourth element, absent = none) and, for reader-contract samples, the area scale
         (source width x source height) / (S x S).  An accumulator of the VOC protocol (DeviceVocAccumulator) gets the fourth
-        element as the boxes' `difficult` flags."""
+        element as the boxes' `difficult` flags.  weights as detect(): the whole loop runs with that set."""
         coco = getattr(acc, "protocol", "map") == "coco"
         voc = getattr(acc, "protocol", "map") == "voc"
         if precision not in ("bf16", "mxfp8"):
@@ -762,14 +835,15 @@ class SSDObjectDetectionModel:
                 acc.add(score, cls, box, keep, self._to_device(gt_cls), box_d.double() * size, self._to_device(gt_off))
             buf.clear()
 
-        for sample in samples:
-            buf.append(sample)
-            if len(buf) == batch_size:
-                flush()
-        flush()
+        with self._weights(weights):
+            for sample in samples:
+                buf.append(sample)
+                if len(buf) == batch_size:
+                    flush()
+            flush()
 
     def evaluate(self, samples, batch_size=32, score_thresh=0.05, iou_thresh=0.45, max_dets=100, return_detections=False,
-                 precision="bf16", metric="host", scoring="best", protocol="map"):
+                 precision="bf16", metric="host", scoring="best", protocol="map", weights="live"):
         """Evaluation pass (the reference fetches its val split at models/ssd_model.py:291 and drops it):
         samples = iterable of (image f32 [S,S,3] in [0,1], cls [n], box [n,4] relative cx,cy,w,h) as the loaders yield
         them, or a split of reader-contract samples (getattr(samples, "raw"): decoded uint8 images of any size, COCO top-left
@@ -793,7 +867,14 @@ class SSDObjectDetectionModel:
         protocol="voc07" | "voc12": PASCAL VOC's mAP at IoU 0.5 (utils.metrics.voc_map: the 11-point metric of VOC2007, or the
         area under the monotone envelope of VOC2010 onward), with either metric mode; a sample's fourth element is read as the
         boxes' `difficult` flags -- so a COCO sample's crowd flags are treated as difficult.  Returns voc_map's dict (mAP,
-        per_class, n_pos).  max_dets <= ops.eval_voc_max_dets() with metric="device".  Any other value raises ValueError."""
+        per_class, n_pos).  max_dets <= ops.eval_voc_max_dets() with metric="device".  Any other value raises ValueError.
+        weights as detect(): "ema" evaluates the averaged weights (the whole pass inside engine.averaged())."""
+        with self._weights(weights):
+            return self._evaluate(samples, batch_size, score_thresh, iou_thresh, max_dets, return_detections, precision, metric,
+                                  scoring, protocol)
+
+    def _evaluate(self, samples, batch_size, score_thresh, iou_thresh, max_dets, return_detections, precision, metric, scoring,
+                  protocol):
         from ..utils.metrics import coco_map
         if protocol not in ("map", "coco", "voc07", "voc12"):
             raise ValueError("protocol must be 'map', 'coco', 'voc07' or 'voc12', not %r" % (protocol,))
@@ -873,17 +954,29 @@ class SSDObjectDetectionModel:
         return (result, dets) if return_detections else result
 
     # ------------------------------------------------------------------ checkpoint
-    def save(self, path="model_weight.pt", extra=None, collective=True):
+    def save(self, path="model_weight.pt", extra=None, collective=True, weights="live"):
         """Weights + Adam moments + step count (the reference's Keras .h5 has weights only, models/ssd_model.py:405-407);
         `extra` (e.g. optimizer iteration counters, epoch) is stored alongside for resume.
         Data parallel: the replicas are identical, rank 0 writes and the others wait for the file (collective=False on
-        error paths, where the other ranks may never arrive)."""
+        error paths, where the other ranks may never arrive).
+        A model that keeps averaged weights saves them and their update count as well (`ema`, `ema_updates`), so a resumed run
+        goes on averaging.  weights="ema": the deployable model instead -- `param` is the average, the optimizer slots and
+        the step count are zero and there are no `ema` keys, so it loads into a model that keeps no average (ValueError on a
+        model that has none to save)."""
+        if weights not in ("live", "ema"):
+            raise ValueError("weights must be 'live' or 'ema', not %r" % (weights,))
+        if weights == "ema" and self._engine.ema is None:
+            raise ValueError("save(weights='ema') on a model without averaged weights")
         rank, world = self._rank_world()
         if rank == 0:
             d = os.path.dirname(path)
             if d:
                 os.makedirs(d, exist_ok=True)
             sd = self._engine.state_dict()
+            if weights == "ema":
+                sd["param"] = sd.pop("ema")
+                del sd["ema_updates"]
+                sd.update(adam_m=torch.zeros_like(sd["adam_m"]), adam_v=torch.zeros_like(sd["adam_v"]), step=0)
             sd["network"] = self.network.as_dict()
             if extra:
                 sd["extra"] = dict(extra)
@@ -899,6 +992,9 @@ class SSDObjectDetectionModel:
             raise ValueError("checkpoint %s holds the network %s, this model is %s" % (path, theirs.describe(),
                                                                                      self.network.describe()))
         self._engine.load_state_dict(sd)
+        # a checkpoint's average, loaded before this model was told to keep one: enable_ema() (the first step of a run with
+        # TrainConfig(ema=...)) takes it from here
+        self._loaded_ema = (sd["ema"], sd.get("ema_updates", 0)) if "ema" in sd and self._engine.ema is None else None
         self._version += 1
         self._slot_owner = _RESTORED
         logger.info("Model is loaded from %s", path)

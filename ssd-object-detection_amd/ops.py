@@ -2144,3 +2144,59 @@ def cast_bf16(src, dst=None):
         dst = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
     _lib.check(L.ssd_cast_bf16(_ptr(src), _ptr(dst), src.numel(), _stream()))
     return dst
+
+
+class EmaSpec:
+    """An exponential moving average of the weights, kept beside them for validation, detection and the saved model
+    (ema_step): e' = decay e + (1 - decay) p after every optimizer step.  warmup: TF ExponentialMovingAverage's num_updates rule,
+    decay_t = min(decay, (1 + t) / (10 + t)) at the t-th update from 0 -- the first updates follow the weights closely instead
+    of remembering the random initialisation for 1 / (1 - decay) steps.  decay in (0, 1), else ValueError."""
+
+    def __init__(self, decay=0.9998, warmup=True):
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.integer, np.floating)) or not 0.0 < decay < 1.0:
+            raise ValueError("ema decay must be a number in (0, 1), not %r" % (decay,))
+        if not isinstance(warmup, bool):
+            raise ValueError("ema warmup must be True or False, not %r" % (warmup,))
+        self.decay = float(decay)
+        self.warmup = warmup
+
+    @classmethod
+    def of(cls, v):
+        """None -> None (no average); a number -> that decay; an EmaSpec -> itself; a dict with the keys decay / warmup -> a
+        spec.  ValueError for anything else."""
+        if v is None:
+            return None
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, dict):
+            unknown = sorted(set(v) - {"decay", "warmup"}, key=str)
+            if unknown:
+                raise ValueError("ema: unknown key(s) %s (known: decay, warmup)" % ", ".join(repr(k) for k in unknown))
+            return cls(**v)
+        if not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)):
+            return cls(decay=v)
+        raise ValueError("ema must be None, a decay in (0, 1), a dict(decay, warmup) or an ops.EmaSpec, not %r" % (v,))
+
+    def decay_at(self, t):
+        """The decay of update t (t = the updates made before it), a Python float (double)."""
+        if t < 0:
+            raise ValueError("ema update index must be >= 0, not %r" % (t,))
+        return min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+
+    def one_minus_decay(self, t):
+        """What ema_step gets for update t: float32(1 - decay_at(t)), the difference taken in double."""
+        return float(np.float32(1.0 - self.decay_at(t)))
+
+    def __repr__(self):
+        return "EmaSpec(decay=%r, warmup=%r)" % (self.decay, self.warmup)
+
+
+def ema_step(ema, param, one_minus_decay):
+    """ssd_ema_step: ema += one_minus_decay * (param - ema) in place (both fp32, contiguous, the same element count, a multiple
+    of the optimizer block); 1 copies param bit for bit, 0 leaves ema as it is.  ValueError (SSD_ERR_VALUE, nothing launched)
+    for a factor outside [0, 1], a count that is no multiple of the block or overlapping operands."""
+    L = _lib.lib()
+    _dev(ema, torch.float32); _dev(param, torch.float32)
+    assert ema.numel() == param.numel(), (ema.numel(), param.numel())
+    _lib.check(L.ssd_ema_step(_ptr(ema), _ptr(param), ema.numel(), float(one_minus_decay), _stream()))
+    return ema

@@ -406,6 +406,7 @@ class ResNet50SSDEngine(SSDEngine):
         transposed filters quantised here, once per call); dgrad_precision="bf16" keeps every data gradient in bf16.  Weight
         gradients, heads, stride-2 data gradients and pooling always run in bf16 on the bf16 maps."""
         assert fused_adam is None and on_dgrad is None, "the per-bucket optimizer schedule belongs to the VGG chain engine"
+        self._live_only("backward()")
         if self.last_forward == "mxfp8":
             raise RuntimeError("backward() after an inference mxfp8 forward: the bf16 activations it needs were not all "
                                "written; run forward(x) in bf16 or forward(x, 'mxfp8', train=True) first")

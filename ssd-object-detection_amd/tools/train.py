@@ -60,11 +60,12 @@ def val_from_config(config):
     enable is false: the default run does not validate, as the reference does not.  The optional key `scoring` ("best": one
     label per anchor, the default when absent; "all": the multi-label detection output, evaluate(scoring="all")) is in the
     dict only when the config gives it, and so is `protocol` ("map", the default when absent: val/mAP, val/AP50, val/AP75;
-    "coco": COCO's twelve box metrics, evaluate(protocol="coco"); "voc07" / "voc12": PASCAL VOC's mAP, val/mAP only)."""
+    "coco": COCO's twelve box metrics, evaluate(protocol="coco"); "voc07" / "voc12": PASCAL VOC's mAP, val/mAP only), and so is
+    `weights` ("ema" | "live" | "both": which weights a run with `model: train: ema:` validates; absent = the averaged ones)."""
     section = (config.get("model") or {}).get("eval")
     if not section or not section.get("enable", False):
         return None
-    unknown = set(section) - set(VAL_DEFAULTS) - {"enable", "scoring", "protocol"}
+    unknown = set(section) - set(VAL_DEFAULTS) - {"enable", "scoring", "protocol", "weights"}
     if unknown:
         raise ValueError("unknown model.eval keys: %s" % sorted(unknown))
     val = {k: type(d)(section.get(k, d)) for k, d in VAL_DEFAULTS.items()}
@@ -80,6 +81,10 @@ def val_from_config(config):
         if section["protocol"] not in ("map", "coco", "voc07", "voc12"):
             raise ValueError("model.eval.protocol must be 'map', 'coco', 'voc07' or 'voc12', not %r" % (section["protocol"],))
         val["protocol"] = str(section["protocol"])
+    if "weights" in section:
+        if section["weights"] not in ("ema", "live", "both"):
+            raise ValueError("model.eval.weights must be 'ema', 'live' or 'both', not %r" % (section["weights"],))
+        val["weights"] = str(section["weights"])
     return val
 
 
@@ -127,6 +132,26 @@ def background_prior_from_config(config):
     if isinstance(pi, bool) or not isinstance(pi, (int, float)) or not 0.0 < pi < 1.0:
         raise ValueError("model.train.loss.background_prior must be a number in (0, 1), not %r" % (pi,))
     return float(pi)
+
+
+def ema_from_config(config):
+    """`model: train: ema: {enable, decay, warmup}` (no reference counterpart: an exponential moving average of the weights for
+    validation, detection and the saved model) -> ops.EmaSpec, or None when the key is absent or enable is false: the default
+    run keeps no average.  ValueError for an unknown key or bad values."""
+    section = ((config.get("model") or {}).get("train") or {}).get("ema")
+    if section is None:
+        return None
+    if not isinstance(section, dict):
+        raise ValueError("model.train.ema must be a mapping, not %r" % (section,))
+    unknown = set(section) - {"enable", "decay", "warmup"}
+    if unknown:
+        raise ValueError("unknown model.train.ema keys: %s" % sorted(unknown, key=str))
+    from ..ops import EmaSpec
+    spec = EmaSpec(**{k: section[k] for k in ("decay", "warmup") if k in section})     # (bad values raise when disabled too)
+    enable = section.get("enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError("model.train.ema.enable must be true or false, not %r" % (enable,))
+    return spec if enable else None
 
 
 def l2norm_from_config(config):
@@ -301,6 +326,9 @@ def train(config):
                                     l2norm=l2norm_from_config(config), network=network,
                                     fp8_inference=fp8_inference_from_config(config))
     model.decode_workers = decode_workers
+    ema = ema_from_config(config)
+    if ema is not None:                      # before a resume: the checkpoint's average goes where the engine keeps one
+        model.enable_ema(ema)
 
     lr, wlr = model_cfg["train"]["lr"], model_cfg["warmup"]["lr"]
     optimizer = _make_optimizer(model_cfg["train"]["optimizer"], schedule_from_config(lr))
@@ -330,7 +358,7 @@ def train(config):
     fields = {name: cfg_get(config, path) for name, path in TRAIN_CONFIG_KEYS.items()}
     fields.update(optimizer=optimizer, warmup_optimizer=warmup_optimizer, start_epoch=start_epoch,
                   augment=augment_from_config(config), val=val_from_config(config), loss=loss_from_config(config),
-                  clip=clip_from_config(config))
+                  clip=clip_from_config(config), ema=ema)
     model.train(data_loader=data, cfg=SSDObjectDetectionModel.TrainConfig(**fields))
     model.save(os.path.join(model.get_log_dir(), model_cfg["save"]))      # rank 0 writes; the others wait
     return model
