@@ -1920,6 +1920,9 @@ def add_relu_fwd_mxfp8(a, b, out=None, q=None, scale=None):
     if out is None:
         out = torch.empty_like(a)
     q, scale = _mx_default(a.shape, a.device, q, scale)
+    _caller_buffer("out", out, a.shape, torch.bfloat16)
+    _caller_buffer("q", q, a.shape, torch.uint8)
+    _caller_buffer("scale", scale, tuple(a.shape[:-1]) + (a.shape[-1] // 32,), torch.uint8)
     rc = L.ssd_add_relu_fwd_mxfp8(_ptr(a), _ptr(b), _ptr(out), _ptr(q), _ptr(scale), a.numel(), _stream())
     _lib.check(rc, unsupported="add_relu_fwd_mxfp8")
     return out, q, scale
@@ -1932,6 +1935,7 @@ def add_relu_fwd(a, b, out=None):
     assert a.shape == b.shape
     if out is None:
         out = torch.empty_like(a)
+    _caller_buffer("out", out, a.shape, torch.bfloat16)
     _lib.check(L.ssd_add_relu_fwd(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()))
     return out
 
@@ -1944,6 +1948,7 @@ def relu_mask_bwd(g, act, out=None, accumulate=False):
     if out is None:
         assert not accumulate
         out = torch.empty_like(g)
+    _caller_buffer("out", out, g.shape, torch.bfloat16)
     _lib.check(L.ssd_relu_mask_bwd(_ptr(g), _ptr(act), _ptr(out), 1 if accumulate else 0, g.numel(), _stream()))
     return out
 
@@ -1959,6 +1964,8 @@ def maxpool3x3s2_fwd(x, out=None, code=None):
         out = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
     if code is None:
         code = torch.empty((B, Ho, Wo, C // 8), dtype=torch.int32, device=x.device)
+    _caller_buffer("out", out, (B, Ho, Wo, C), torch.bfloat16)
+    _caller_buffer("code", code, (B, Ho, Wo, C // 8), torch.int32)
     _lib.check(L.ssd_maxpool3x3s2_fwd(_ptr(x), _ptr(out), _ptr(code), B, H, W, C, Ho, Wo, pt, pl, _stream()))
     return out, code
 
@@ -1972,6 +1979,7 @@ def maxpool3x3s2_bwd(code, dy, x_shape, out=None):
     assert dy.shape == (B, Ho, Wo, C) and code.shape == (B, Ho, Wo, C // 8)
     if out is None:
         out = torch.empty(x_shape, dtype=torch.bfloat16, device=dy.device)
+    _caller_buffer("out", out, x_shape, torch.bfloat16)
     _lib.check(L.ssd_maxpool3x3s2_bwd(_ptr(code), _ptr(dy), _ptr(out), B, H, W, C, Ho, Wo, pt, pl, _stream()))
     return out
 
@@ -1986,6 +1994,13 @@ def _same_shape(name, t, shape):
     """A caller's output buffer: contiguous and of the shape this call writes, or ValueError (as _pooled_shapes)."""
     if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError("%s of shape %s, contiguous %s: this call writes %s" % (name, tuple(t.shape), t.is_contiguous(), tuple(shape)))
+
+
+def _caller_buffer(name, t, shape, dtype):
+    """_same_shape, and of the element type this call writes: a device tensor of `dtype`, or ValueError."""
+    _same_shape(name, t, shape)
+    if t.dtype != dtype or not t.is_cuda:
+        raise ValueError("%s is %s on %s: this call writes %s on the device" % (name, t.dtype, t.device, dtype))
 
 
 def conv2d_atrous_fwd(x, w, bias, dilation, relu, out=None):

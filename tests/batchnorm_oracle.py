@@ -45,8 +45,11 @@ MOMENTUM = 0.1
 # channel per finalize lane and four channels per workgroup-merge thread; (1007, 192) a width that does not divide the workgroup
 # (idle lanes) and slabs of unequal chunk counts; (4099, 64) 129 slabs, the last of three rows; (8192, 256) several passes per slab
 SHAPES = [(2, 64), (3, 128), (65, 64), (130, 1024), (1007, 192), (4099, 64), (8192, 256)]
-# past the cap of 1024 slabs: the first slabs take two chunks (kernel tests only)
-EXTRA_SHAPES = [(33000, 64)]
+# past the cap of 1024 slabs: the first slabs take two chunks (kernel tests only).  Past one sweep of the apply grid as well
+# (tests/sweep_cases.py has the arithmetic): (65703, 64) 2054 chunks on 1024 slabs, slabs 0..5 take a third chunk, the 7-row last
+# chunk is slab 5's third, six workgroups of the 2048 apply workgroups make a second trip; (2085, 2048) one row per chunk, 66 slabs
+# of 31 or 32 chunks, 37 apply workgroups make a second trip
+EXTRA_SHAPES = [(33000, 64), (65703, 64), (2085, 2048)]
 KINDS = ("unit", "offset64", "offset-300", "small", "constant", "zero")
 
 

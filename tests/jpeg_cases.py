@@ -82,6 +82,42 @@ def corrupted(name):
     return out
 
 
+# ---- images past one stride of the reconstruction kernels' loops -------------------------------------------------------------------
+# k_jpeg_idct walks the 8x8 blocks of an image (all components) 64 x 256 = 16 384 at a time, k_jpeg_rgb its pixels 128 x 256 =
+# 32 768 at a time (IDCT_GRID_X, RGB_GRID_X in csrc/jpeg.hip); the largest fixture has 264 blocks and 5 063 pixels.  No larger
+# file is committed: the kernels take coefficients, so a large image is a fixture's block grid repeated.
+IDCT_STRIDE, RGB_STRIDE = 64 * 256, 128 * 256
+# name: (fixture, copies across, copies down, width, height).  4:4:4: 3 x 77 x 72 = 16 632 blocks (the last 248 of the Cr plane
+# on a second trip), 348 881 pixels (eleven trips), neither extent a multiple of 8; 4:2:0: the fancy upsampling across block
+# borders, 96 393 pixels (three trips)
+LARGE = {"444": ("c83x61_444", 7, 9, 611, 571), "420": ("c83x61_420_rst", 4, 4, 381, 253)}
+
+
+def tiled(name, tx, ty, width, height):
+    """(coef int16 [ncoef], header) of an image whose every component plane is the fixture's grid of blocks repeated tx x ty
+    times and cropped to width x height; the luma DC of copy (i, j) is raised by 3 ((7 j + i) % 5), so copies differ.  Its
+    decode is jpeg_oracle.reconstruct of these coefficients (the oracle is Pillow's decode bit for bit on every fixture)."""
+    coef, h = oracle(name)
+    parts, bws, bhs, offs, off = [], [], [], [], 0
+    for c in range(h["ncomp"]):
+        bw, bh = h["blocks_w"][c], h["blocks_h"][c]
+        blk = np.asarray(coef[h["coef_off"][c]:][:64 * bw * bh]).reshape(bh, bw, 64)
+        big = np.tile(blk, (ty, tx, 1))
+        if c == 0:
+            step = 3 * ((7 * np.arange(ty)[:, None] + np.arange(tx)[None, :]) % 5)
+            big[..., 0] += np.repeat(np.repeat(step, bh, 0), bw, 1).astype(np.int16)
+        parts.append(big.reshape(-1))
+        bws.append(bw * tx)
+        bhs.append(bh * ty)
+        offs.append(off)
+        off += big.size
+        need_w, need_h = (width, height) if c == 0 or h["kind"] == J.K444 else \
+            ((width + 1) // 2, (height + 1) // 2 if h["kind"] == J.K420 else height)
+        assert 0 < need_w <= 8 * bws[-1] and 0 < need_h <= 8 * bhs[-1], (c, need_w, need_h)      # the planes cover the image
+    return np.concatenate(parts).astype(np.int16), dict(h, width=width, height=height, blocks_w=bws, blocks_h=bhs, coef_off=offs,
+                                                        ncoef=off, restart=0)
+
+
 # ---- a COCO-shaped directory ------------------------------------------------------------------------------------------------------
 CATEGORIES = [(90, "zebra crossing"), (1, "person"), (3, "car")]            # non-contiguous ids, not sorted in the file
 # eighty categories with gaps in their ids, for the model-level tests (the networks' heads are built for 80 classes)

@@ -20,6 +20,9 @@ import numpy as np
 U = 2.0 ** -24
 EPS = 1e-10
 SHAPES = [(1, 128), (7, 256), (130, 512), (67, 1024), (2 * 1444, 512)]
+# past one sweep of both grids (tests/sweep_cases.py has the arithmetic): three trips of the forward's 8192 waves (13 waves make
+# the third) and of the backward's 6144, whose 1536 workgroups write every row of partials; one and two vectors per lane
+EXTRA_SHAPES = [(16397, 128), (16397, 1024)]
 
 
 def bf16_round(a):

@@ -14,11 +14,15 @@ DEV = "cuda"
 
 def _records(names):
     """(coef int16 [total], desc int32 [B, REC]) of the oracle's coefficients, offsets absolute"""
+    return _records_of([C.oracle(name) for name in names])
+
+
+def _records_of(pairs):
+    """_records of (coefficients, header) pairs"""
     from ssd_object_detection_amd import _lib
     g = _lib.CONSTANTS
-    coefs, desc, base = [], np.zeros((len(names), g["SSD_JPEG_REC_WORDS"]), np.int32), 0
-    for b, name in enumerate(names):
-        coef, h = C.oracle(name)
+    coefs, desc, base = [], np.zeros((len(pairs), g["SSD_JPEG_REC_WORDS"]), np.int32), 0
+    for b, (coef, h) in enumerate(pairs):
         r = desc[b]
         r[g["SSD_JPEG_WIDTH"]], r[g["SSD_JPEG_HEIGHT"]], r[g["SSD_JPEG_NCOMP"]] = h["width"], h["height"], h["ncomp"]
         r[g["SSD_JPEG_KIND"]], r[g["SSD_JPEG_NCOEF"]], r[g["SSD_JPEG_RESTART"]] = h["kind"], h["ncoef"], h["restart"]
@@ -35,9 +39,13 @@ def _reconstruct_strict(names):
     """one ssd_jpeg_reconstruct call for `names` into per-image slots of a poisoned arena: every image equals Pillow's decode,
     every guard byte (1 MiB in front of and behind each image, the coefficients, the records and the scratch) is intact, the
     inputs are unchanged, and nothing depends on what the scratch or the arena held before"""
+    _reconstruct_strict_of([C.oracle(n) for n in names], [C.decoded(n) for n in names], names)
+
+
+def _reconstruct_strict_of(pairs, images, names):
     from ssd_object_detection_amd import ops
-    coef, desc = _records(names)
-    want = [torch.from_numpy(C.decoded(n).reshape(-1).copy()) for n in names]
+    coef, desc = _records_of(pairs)
+    want = [torch.from_numpy(np.ascontiguousarray(img).reshape(-1).copy()) for img in images]
     arena = S.Arena(DEV, S.Arena.bytes_for(coef.nbytes, desc.nbytes, 8 * len(names), coef.size, *[w.numel() for w in want]))
     coef_d = arena.put(torch.from_numpy(coef), "coef")
     desc_d = arena.put(torch.from_numpy(desc), "desc")
@@ -58,6 +66,20 @@ def test_reconstruct_reversed_batch():
 
 def test_reconstruct_single_pixel_image():
     _reconstruct_strict(["c1x1"])
+
+
+@pytest.mark.parametrize("key", sorted(C.LARGE))
+def test_reconstruct_past_one_stride_of_the_loops(key):
+    """jpeg_cases.LARGE: a fixture's blocks repeated to more than 16 384 blocks (4:4:4: k_jpeg_idct's second trip) and more than
+    32 768 pixels (k_jpeg_rgb's: eleven and three trips), against the numpy oracle's reconstruction of the same coefficients;
+    a small fixture rides in the same call"""
+    from tests import jpeg_oracle as J
+    coef, h = C.tiled(*C.LARGE[key])
+    blocks, pixels = coef.size // 64, h["width"] * h["height"]
+    print(key, blocks, "blocks,", pixels, "pixels")
+    assert pixels > 2 * C.RGB_STRIDE and (key != "444" or blocks > C.IDCT_STRIDE)
+    small = "c17x9_420"
+    _reconstruct_strict_of([(coef, h), C.oracle(small)], [J.reconstruct(coef, h), C.decoded(small)], [key, small])
 
 
 def test_reconstruct_refuses_bad_arguments_and_skips_bad_records():

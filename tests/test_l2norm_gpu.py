@@ -5,7 +5,8 @@ holds that result to the bounds, and then hands it to Arena.run as the reference
 the same bits under the other poison and from a second run.
 
 Shapes: one pixel; pixel counts that leave partial workgroups (4 waves = 4 pixels per round) and lanes without channels
-(C = 128, 256); two 16-byte vectors per lane (C = 1024); the engine's own two-image map."""
+(C = 128, 256); two 16-byte vectors per lane (C = 1024); the engine's own two-image map; and l2norm_oracle.EXTRA_SHAPES, three
+trips of both capped grids (tests/sweep_cases.py)."""
 import ctypes
 
 import numpy as np
@@ -18,12 +19,15 @@ from tests import l2norm_oracle as O                                 # noqa: E40
 from tests import strict                                             # noqa: E402
 
 BF, F32 = torch.bfloat16, torch.float32
+ALL_SHAPES = O.SHAPES + O.EXTRA_SHAPES
 _CASES = {}
 
 
 def case(shape):
-    """inputs, float64 references and bounds of a shape, computed once"""
+    """inputs, float64 references and bounds of a shape, computed once (of the large extra shapes only the latest is kept)"""
     if shape not in _CASES:
+        for old in [s for s in _CASES if s in O.EXTRA_SHAPES]:
+            del _CASES[old]
         k = O.make_case(*shape)
         k["y64"], k["r64"], _ = O.fwd64(k["x"], k["s"])
         for name, old in (("", None), ("_acc", k["old"])):
@@ -54,7 +58,7 @@ def first_run(a, fn, outs):
     return [o.detach().clone() for o in outs]
 
 
-@pytest.mark.parametrize("shape", O.SHAPES, ids=str)
+@pytest.mark.parametrize("shape", ALL_SHAPES, ids=str)
 def test_forward(ops, shape):
     k = case(shape)
     P, C = shape
@@ -75,7 +79,7 @@ def test_forward(ops, shape):
 
 
 @pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
-@pytest.mark.parametrize("shape", O.SHAPES, ids=str)
+@pytest.mark.parametrize("shape", ALL_SHAPES, ids=str)
 def test_backward(ops, shape, accumulate):
     k = case(shape)
     P, C = shape
