@@ -897,6 +897,41 @@ int ssd_maxpool3x3s1_fwd(const void* x, void* y, void* code, int B, int H, int W
 int ssd_maxpool3x3s1_bwd(const void* code, const void* dy, void* dx, int B, int H, int W, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution: the operator a MobileNet-SSD / SSDLite trunk alternates with the 1x1 convolution (no reference
+ * counterpart; no network launches it yet).  Semantics are Keras / TensorFlow's DepthwiseConv2D(3, strides = s,
+ * depth_multiplier = 1) + bias (+ ReLU) and its tape.gradient: channel c of the output depends on channel c of the input
+ * alone -- a nine-tap stencil bound by memory bandwidth, not a GEMM.
+ *
+ * Layouts: x [B,H,W,C], y and dy [B,Ho,Wo,C], dx [B,H,W,C], all bf16 NHWC; w bf16 [3][3][C] (Keras's (3,3,C,1) kernel,
+ * channel-contiguous); bias fp32 [C] or NULL; dw fp32 [3][3][C] and dbias fp32 [C] or NULL, both written, not accumulated.
+ * Geometry: stride 1 or 2; padding is passed explicitly as for ssd_conv2d_fwd: pad_t and pad_l are each 0 or 1, the bottom
+ * and right padding is implied by the output size -- (Ho-1)*stride + 3 - H - pad_t must lie in 0..2, likewise for the width --
+ * and what falls outside the map reads as zero.  TF SAME at stride 2 on an even map is pad_t = 0 with one row below; a
+ * torch-style padding 1 with Ho = (H-1)/2 + 1 is served as well.
+ * Arithmetic: the forward pass forms the nine products in fp32 and accumulates them in tap order (ky outer, kx inner) starting
+ * from the bias, then max(., 0) where relu, then ONE rounding to bf16.  The data gradient is gathered per input pixel (no
+ * scatter, no atomics): dx[b,iy,ix,c] = the fp32 sum, in tap order, of dy[b,oy,ox,c] * w[ky][kx][c] over the taps for which
+ * oy = (iy + pad_t - ky) / stride is integral and inside the map, likewise ox; with accumulate the bf16 dx already there is
+ * added; then zero where relu_src <= 0 (relu_src: NULL, or the forward activation, which may be stored in dx's place as for
+ * ssd_conv2d_bwd_data); one rounding.  The weight gradient sums x * dy (dbias: dy) over all B*Ho*Wo output pixels as
+ * fixed-order partial sums over pixel slabs in ws, reduced in slab order: bitwise reproducible, no floating-point atomics; ws
+ * needs no initial contents and exactly ssd_dwconv3x3_bwd_weight_workspace_bytes(...) bytes.
+ * Supported: C % 8 == 0, every tensor below 2^31 bytes.
+ *
+ * Refusals, decided on the host before anything is launched.  SSD_ERR_VALUE: a NULL required pointer (everything but bias,
+ * relu_src and dbias); B, H, W, C, Ho or Wo < 1; a stride outside {1, 2}; pad_t or pad_l outside {0, 1}, or Ho / Wo that break
+ * the rule above; an output that overlaps an input (relu_src aliasing dx is the one exception).  SSD_ERR_WORKSPACE: ws NULL or
+ * smaller than the query.  SSD_ERR_UNSUPPORTED (the size query returns 0): C % 8 != 0, or a tensor of 2^31 bytes or more.
+ * ---------------------------------------------------------------------------------------- */
+int ssd_dwconv3x3_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int stride, int pad_t,
+                      int pad_l, int Ho, int Wo, int relu, void* stream);
+int ssd_dwconv3x3_bwd_data(const void* dy, const void* w, const void* relu_src, void* dx, int B, int H, int W, int C, int stride,
+                           int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream);
+size_t ssd_dwconv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int C, int stride, int Ho, int Wo);
+int ssd_dwconv3x3_bwd_weight(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int C, int stride,
+                             int pad_t, int pad_l, int Ho, int Wo, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward pass of ALL head convolutions (models/ssd_model.py:153-162; 3x3, stride 1, SAME, no activation) from the compact
  * gradient rows of ssd_loss_fwd_bwd_heads -- the part of tape.gradient (:248) behind the loc / conf outputs.  Work is
  * proportional to the rows that carry a gradient (4P of B*A anchors), not to the feature maps; results equal the dense

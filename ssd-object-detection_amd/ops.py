@@ -2085,6 +2085,68 @@ def maxpool3x3s1_bwd(code, dy, x_shape, out=None):
     return out
 
 
+# ---- depthwise 3x3 convolution (MobileNet-SSD / SSDLite's other half; no network launches it yet) ------------------------------
+_DW_RANGE = "depthwise 3x3 convolution: C must be a multiple of 8 and every tensor below 2^31 bytes; got %s"
+
+
+def dwconv3x3_fwd(x, w, bias, stride, pad_t, pad_l, Ho, Wo, relu, out=None):
+    """DepthwiseConv2D(3, strides=stride, depth_multiplier=1) + bias (+ ReLU): x bf16 [B,H,W,C], w bf16 [3,3,C], bias fp32 [C] or
+    None; explicit top / left padding (0 or 1), the rest implied by (Ho, Wo) as for conv2d_fwd."""
+    L = _lib.lib()
+    _bf(x); _bf(w)
+    B, H, W, C = x.shape
+    assert w.shape == (3, 3, C)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
+    _caller_buffer("out", out, (B, Ho, Wo, C), torch.bfloat16)
+    _lib.check(L.ssd_dwconv3x3_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
+                                   1 if relu else 0, _stream()),
+               unsupported=_DW_RANGE % ((B, H, W, C, stride),))
+    return out
+
+
+def dwconv3x3_bwd_data(dy, w, relu_src, x_shape, stride, pad_t, pad_l, accumulate=False, out=None):
+    """Its data gradient: dy bf16 [B,Ho,Wo,C], w the forward filters [3,3,C]; out (+)= the gathered gradient, then zeroed where
+    relu_src <= 0 (relu_src may be `out` itself)."""
+    L = _lib.lib()
+    _bf(dy); _bf(w)
+    B, H, W, C = x_shape
+    _, Ho, Wo, _ = dy.shape
+    assert dy.shape == (B, Ho, Wo, C) and w.shape == (3, 3, C)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dy.device)
+    _caller_buffer("out", out, x_shape, torch.bfloat16)
+    if relu_src is not None:
+        _caller_buffer("relu_src", relu_src, x_shape, torch.bfloat16)
+    _lib.check(L.ssd_dwconv3x3_bwd_data(_ptr(dy), _ptr(w), _ptr(relu_src), _ptr(out), B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
+                                        1 if accumulate else 0, _stream()),
+               unsupported=_DW_RANGE % ((B, H, W, C, stride),))
+    return out
+
+
+def dwconv3x3_bwd_weight(x, dy, stride, pad_t, pad_l, dw=None, dbias=None, want_bias=True, ws=None):
+    """Its weight and bias gradient (fp32 [3,3,C] and [C], written): x bf16 [B,H,W,C], dy bf16 [B,Ho,Wo,C]."""
+    L = _lib.lib()
+    _bf(x); _bf(dy)
+    B, H, W, C = x.shape
+    _, Ho, Wo, _ = dy.shape
+    assert dy.shape == (B, Ho, Wo, C)
+    if dw is None:
+        dw = torch.empty((3, 3, C), dtype=torch.float32, device=x.device)
+    if dbias is None and want_bias:
+        dbias = torch.empty((C,), dtype=torch.float32, device=x.device)
+    _caller_buffer("dw", dw, (3, 3, C), torch.float32)
+    if dbias is not None:
+        _caller_buffer("dbias", dbias, (C,), torch.float32)
+    nbytes = L.ssd_dwconv3x3_bwd_weight_workspace_bytes(B, H, W, C, stride, Ho, Wo)
+    wbuf = (ws or _conv_ws).get(nbytes, x.device)
+    _lib.check(L.ssd_dwconv3x3_bwd_weight(_ptr(x), _ptr(dy), _ptr(dw), _ptr(dbias), B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
+                                          _ptr(wbuf), wbuf.numel(), _stream()),
+               unsupported=_DW_RANGE % ((B, H, W, C, stride),))
+    return dw, dbias
+
+
 # ---- ... and their inference fp8 forms (engine.SSDEngine(fp8_inference=True)) --------------------------------------------------
 def conv2d_atrous_fwd_mxfp8(xq, xs, wq, ws, bias, dilation, relu, want_bf16=True, want_fp8=False, out=None, out_q=None,
                             out_scale=None):
