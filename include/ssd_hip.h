@@ -898,7 +898,7 @@ int ssd_maxpool3x3s1_bwd(const void* code, const void* dy, void* dx, int B, int 
 
 /* ------------------------------------------------------------------------------------------
  * Depthwise 3x3 convolution: the operator a MobileNet-SSD / SSDLite trunk alternates with the 1x1 convolution (no reference
- * counterpart; no network launches it yet).  Semantics are Keras / TensorFlow's DepthwiseConv2D(3, strides = s,
+ * counterpart; the "dwconv" nodes of engine.MOBILENET_V1_SSD300_TRUNK launch it).  Semantics are Keras / TensorFlow's DepthwiseConv2D(3, strides = s,
  * depth_multiplier = 1) + bias (+ ReLU) and its tape.gradient: channel c of the output depends on channel c of the input
  * alone -- a nine-tap stencil bound by memory bandwidth, not a GEMM.
  *
@@ -927,6 +927,15 @@ int ssd_dwconv3x3_fwd(const void* x, const void* w, const float* bias, void* y, 
                       int pad_l, int Ho, int Wo, int relu, void* stream);
 int ssd_dwconv3x3_bwd_data(const void* dy, const void* w, const void* relu_src, void* dx, int B, int H, int W, int C, int stride,
                            int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream);
+/* ReLU sign bytes, in the layout of ssd_conv2d_fwd_relubits.  ssd_dwconv3x3_fwd_relubits = ssd_dwconv3x3_fwd (relu = 1), y bit
+ * for bit, that also writes relu_bits u8 [B*Ho*Wo][C/8]: bit k of byte c is set where channel 8c + k of y is > 0.
+ * ssd_dwconv3x3_bwd_data_bits = ssd_dwconv3x3_bwd_data, dx bit for bit, with the mask given as relu_bits u8 [B*H*W][C/8] instead
+ * of relu_src: one byte per stored 16-byte group.  Both refuse what their siblings refuse, and with SSD_ERR_VALUE a NULL
+ * relu_bits and relu_bits overlapping an output (or, where it is an output itself, an input). */
+int ssd_dwconv3x3_fwd_relubits(const void* x, const void* w, const float* bias, void* y, void* relu_bits, int B, int H, int W, int C,
+                               int stride, int pad_t, int pad_l, int Ho, int Wo, void* stream);
+int ssd_dwconv3x3_bwd_data_bits(const void* dy, const void* w, const void* relu_bits, void* dx, int B, int H, int W, int C, int stride,
+                                int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream);
 size_t ssd_dwconv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int C, int stride, int Ho, int Wo);
 int ssd_dwconv3x3_bwd_weight(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int C, int stride,
                              int pad_t, int pad_l, int Ho, int Wo, void* ws, size_t ws_bytes, void* stream);

@@ -1,6 +1,6 @@
 // Depthwise 3x3 convolution for gfx950 (MI355X): forward, data gradient and weight gradient of Keras
 // DepthwiseConv2D(3, strides = s, depth_multiplier = 1) + bias (+ ReLU) -- the operator a MobileNet-SSD / SSDLite trunk alternates
-// with the 1x1 convolution.  No network launches it yet.  x, y, dy, dx bf16 NHWC; w bf16 [3][3][C]; bias fp32 [C].
+// with the 1x1 convolution (engine.MOBILENET_V1_SSD300_TRUNK's "dwconv" nodes).  x, y, dy, dx bf16 NHWC; w bf16 [3][3][C]; bias fp32 [C].
 //
 // Nothing mixes channels, so there is no GEMM: per element two bytes come in, two go out and nine FMAs happen in between.  These are
 // streaming kernels.  A lane owns one channel group (8 channels: one 16-byte load or store) of one pixel COLUMN and walks a strip
@@ -69,6 +69,18 @@ __device__ __forceinline__ dw_u32x4 dw_pack(const float (&f)[8]) {
     return dw_u32x4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
 }
 
+// bit k: element k of the packed group is > 0, read off the bf16 patterns that are stored, so the byte agrees with the stored map
+// whatever the rounding did.  The group has been through max(., 0): no element is negative or a NaN, and -0 counts as zero.
+__device__ __forceinline__ unsigned char dw_signs(const dw_u32x4& v) {
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m |= ((v[k] & 0x00007fffu) ? 1u : 0u) << (2 * k);
+        m |= ((v[k] & 0x7fff0000u) ? 1u : 0u) << (2 * k + 1);
+    }
+    return (unsigned char)m;
+}
+
 // off, or an offset beyond the descriptor where !ok.  The empty asm hides that the mask is one of two constants: hipcc otherwise
 // splits the strip's walk into branches on the row conditions, and a branch ends the run of loads in flight.
 __device__ __forceinline__ unsigned dw_offset(unsigned off, bool ok) {
@@ -90,15 +102,19 @@ __device__ __forceinline__ void dw_weights(const bf16_raw* __restrict__ w, int C
 
 // Output rows o0 .. o0 + DW_RH - 1 of column ox; source row r of the strip is iy = o0 S - pad_t + r and is tap row ky = r - S j
 // of output row j.
-template <int S>
+// BITS: the lane also stores the sign byte of its 16-byte group (bit k: channel 8 cg + k > 0) at [pixel][cg] of `bits`, a sixteenth
+// of the group's own byte offset, through a descriptor of that map's exact size: dropped where the 16-byte store is dropped.
+template <int S, bool BITS>
 __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_fwd(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ w,
-                                                         const float* __restrict__ bias, bf16_raw* __restrict__ y, DwGeom g, int relu) {
+                                                         const float* __restrict__ bias, bf16_raw* __restrict__ y,
+                                                         unsigned char* __restrict__ bits, DwGeom g, int relu) {
     const int idx = blockIdx.x * DW_NT + threadIdx.x;
     if (idx >= g.total) return;
     const int t0 = fdiv(idx, g.d_c8), cg = idx - t0 * g.c8;
     const int t1 = fdiv(t0, g.d_cols), ox = t0 - t1 * g.cols;
     const int b = fdiv(t1, g.d_strips), o0 = (t1 - b * g.nstrips) * DW_RH;
     const __amdgpu_buffer_rsrc_t xres = dw_rsrc(x, g.xbytes), yres = dw_rsrc(y, g.ybytes);
+    const __amdgpu_buffer_rsrc_t bres = dw_rsrc(BITS ? (const void*)bits : (const void*)y, g.ybytes >> 4);
     dw_u32x4 wq[9];
     dw_weights(w, g.C, cg, wq);
     float acc[DW_RH][8];
@@ -161,7 +177,10 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_fwd(const bf16_raw* __restr
                 if (ky != 2) continue;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) acc[j][k] = fmaxf(acc[j][k], floor_);
-                __builtin_amdgcn_raw_buffer_store_b128(dw_pack(acc[j]), yres, dw_offset(yoff + (unsigned)(j * g.Wo * g.C) * 2u, j < nrows), 0, 0);
+                const unsigned o = yoff + (unsigned)(j * g.Wo * g.C) * 2u;
+                const dw_u32x4 q = dw_pack(acc[j]);
+                __builtin_amdgcn_raw_buffer_store_b128(q, yres, dw_offset(o, j < nrows), 0, 0);
+                if (BITS) __builtin_amdgcn_raw_buffer_store_b8(dw_signs(q), bres, dw_offset(o >> 4, j < nrows), 0, 0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -173,17 +192,21 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_fwd(const bf16_raw* __restr
 // the output rows are walked from the bottom up, so every input row receives ky = 0, 1, 2 in this order, and kx likewise.
 // relu_src may be dx itself: a lane reads its element of either before it stores it, and no other lane touches that element.
 // EXTRA: the call accumulates or masks (the plain form reads nothing of dx).
-template <int S, bool EXTRA>
+// BITS: the mask is the sign byte [pixel][cg] of relu_bits (relu_src is unused) and EXTRA says whether the call accumulates.  The
+// byte of input row j is loaded with the row group in which that row receives its last tap row, so it is in a register a group
+// ahead of its use; only the old dx of an accumulating call is still read at the point of use.
+template <int S, bool EXTRA, bool BITS = false>
 __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_dgrad(const bf16_raw* __restrict__ dy, const bf16_raw* __restrict__ w,
-                                                           const bf16_raw* relu_src, bf16_raw* dx, DwGeom g, int accumulate) {
+                                                           const bf16_raw* relu_src, const unsigned char* __restrict__ relu_bits,
+                                                           bf16_raw* dx, DwGeom g, int accumulate) {
     const int idx = blockIdx.x * DW_NT + threadIdx.x;
     if (idx >= g.total) return;
     const int t0 = fdiv(idx, g.d_c8), cg = idx - t0 * g.c8;
     const int t1 = fdiv(t0, g.d_cols), ix = t0 - t1 * g.cols;
     const int b = fdiv(t1, g.d_strips), u0 = (t1 - b * g.nstrips) * DW_RH;
     const __amdgpu_buffer_rsrc_t dyres = dw_rsrc(dy, g.ybytes), dxres = dw_rsrc(dx, g.xbytes);
-    const __amdgpu_buffer_rsrc_t mres = dw_rsrc(relu_src ? relu_src : dx, g.xbytes);
-    const bool masked = relu_src != nullptr;
+    const __amdgpu_buffer_rsrc_t mres = BITS ? dw_rsrc(relu_bits, g.xbytes >> 4) : dw_rsrc(relu_src ? relu_src : dx, g.xbytes);
+    const bool masked = BITS || relu_src != nullptr;
     dw_u32x4 wq[9];
     dw_weights(w, g.C, cg, wq);
     float acc[DW_RH][8];
@@ -200,6 +223,7 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_dgrad(const bf16_raw* __res
     // output rows M_HI .. M_LO in groups of DW_GR, as the forward pass groups its source rows
     constexpr int M_LO = S == 1 ? -2 : -1, M_HI = (DW_RH - 1) / S, R = M_HI - M_LO + 1, G = (R + DW_GR - 1) / DW_GR;
     dw_u32x4 buf[2][DW_GR][3];
+    unsigned char mbyte[DW_RH];
     auto load_group = [&](int grp) {
 #pragma unroll
         for (int rr = 0; rr < DW_GR; ++rr) {
@@ -209,6 +233,14 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_dgrad(const bf16_raw* __res
             const bool rowok = (unsigned)oy < (unsigned)g.Ho;
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) buf[grp & 1][rr][kx] = dw_load(dyres, coloff[kx] + (unsigned)(oy * g.Wo * g.C) * 2u, rowok && colok[kx]);
+        }
+        if (!BITS) return;
+#pragma unroll
+        for (int j = 0; j < DW_RH; ++j) {                                  // the input rows that this group completes
+            const int kymax = S == 1 ? 2 : ((j & 1) ? 1 : 2);
+            if ((M_HI - (j - kymax) / S) / DW_GR != grp) continue;
+            const bool inside = (unsigned)(u0 + j - g.pad_t) < (unsigned)g.H;
+            mbyte[j] = __builtin_amdgcn_raw_buffer_load_b8(mres, dw_offset((xoff + (unsigned)(j * g.W * g.C) * 2u) >> 4, inside), 0, 0);
         }
     };
     load_group(0);
@@ -243,7 +275,19 @@ __global__ __launch_bounds__(DW_NT) void k_dwconv3x3_dgrad(const bf16_raw* __res
                 const int iy = u0 + j - g.pad_t;
                 const bool inside = (unsigned)iy < (unsigned)g.H;
                 const unsigned o = xoff + (unsigned)(j * g.W * g.C) * 2u;
-                if (EXTRA) {
+                if (BITS) {
+                    float old[8];
+                    if (EXTRA) dw_unpack(dw_load(dxres, o, inside && accumulate), old);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) acc[j][k] += EXTRA ? old[k] : 0.f;          // (+ 0: the sibling's sum, bit for bit)
+                    dw_u32x4 q = dw_pack(acc[j]);
+                    const unsigned mb = mbyte[j];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)                                             // a masked element is +0, as the sibling's
+                        q[k] &= (((mb >> (2 * k)) & 1u) ? 0x0000ffffu : 0u) | (((mb >> (2 * k + 1)) & 1u) ? 0xffff0000u : 0u);
+                    __builtin_amdgcn_raw_buffer_store_b128(q, dxres, dw_offset(o, inside), 0, 0);
+                    continue;
+                } else if (EXTRA) {
                     float old[8], mk[8];
                     dw_unpack(dw_load(dxres, o, inside && accumulate), old);    // zeros where nothing is accumulated onto
                     dw_unpack(dw_load(mres, o, inside && masked), mk);
@@ -438,38 +482,68 @@ DwWgradPlan dw_wgrad_plan(int B, int C, int Ho, int Wo) {
 
 extern "C" {
 
-int ssd_dwconv3x3_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int stride, int pad_t,
-                      int pad_l, int Ho, int Wo, int relu, void* stream) {
-    if (!x || !w || !y) return SSD_ERR_VALUE;
+// The forward pass with or without sign bytes (relu_bits u8 [B*Ho*Wo][C/8], an output like y).
+static int dw_fwd(const void* x, const void* w, const float* bias, void* y, void* relu_bits, bool want_bits, int B, int H, int W, int C,
+                  int stride, int pad_t, int pad_l, int Ho, int Wo, int relu, void* stream) {
+    if (!x || !w || !y || (want_bits && !relu_bits)) return SSD_ERR_VALUE;
     const int rc = dw_geometry(B, H, W, C, stride, pad_t, pad_l, Ho, Wo);
     if (rc != SSD_OK) return rc;
-    const long long ybytes = (long long)B * Ho * Wo * C * 2;
-    if (overlaps(y, ybytes, x, (long long)B * H * W * C * 2) || overlaps(y, ybytes, w, 9ll * C * 2) || overlaps(y, ybytes, bias, 4ll * C))
+    const long long xbytes = (long long)B * H * W * C * 2, ybytes = (long long)B * Ho * Wo * C * 2, bbytes = ybytes / 16;
+    if (overlaps(y, ybytes, x, xbytes) || overlaps(y, ybytes, w, 9ll * C * 2) || overlaps(y, ybytes, bias, 4ll * C)) return SSD_ERR_VALUE;
+    if (want_bits && (overlaps(relu_bits, bbytes, y, ybytes) || overlaps(relu_bits, bbytes, x, xbytes) ||
+                      overlaps(relu_bits, bbytes, w, 9ll * C * 2) || overlaps(relu_bits, bbytes, bias, 4ll * C)))
         return SSD_ERR_VALUE;
     const DwGeom g = dw_geom(B, H, W, C, pad_t, pad_l, Ho, Wo, Wo, Ho);
     const dim3 grid((unsigned)((g.total + DW_NT - 1) / DW_NT));
-    auto kern = stride == 1 ? k_dwconv3x3_fwd<1> : k_dwconv3x3_fwd<2>;
+    auto kern = stride == 1 ? (want_bits ? k_dwconv3x3_fwd<1, true> : k_dwconv3x3_fwd<1, false>)
+                            : (want_bits ? k_dwconv3x3_fwd<2, true> : k_dwconv3x3_fwd<2, false>);
     hipLaunchKernelGGL(kern, grid, dim3(DW_NT), 0, (hipStream_t)stream, static_cast<const bf16_raw*>(x), static_cast<const bf16_raw*>(w),
-                       bias, static_cast<bf16_raw*>(y), g, relu ? 1 : 0);
+                       bias, static_cast<bf16_raw*>(y), static_cast<unsigned char*>(relu_bits), g, relu ? 1 : 0);
     return ssd_launch_status();
 }
 
-int ssd_dwconv3x3_bwd_data(const void* dy, const void* w, const void* relu_src, void* dx, int B, int H, int W, int C, int stride,
-                           int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream) {
-    if (!dy || !w || !dx) return SSD_ERR_VALUE;
+int ssd_dwconv3x3_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int stride, int pad_t,
+                      int pad_l, int Ho, int Wo, int relu, void* stream) {
+    return dw_fwd(x, w, bias, y, nullptr, false, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, relu, stream);
+}
+
+int ssd_dwconv3x3_fwd_relubits(const void* x, const void* w, const float* bias, void* y, void* relu_bits, int B, int H, int W, int C,
+                               int stride, int pad_t, int pad_l, int Ho, int Wo, void* stream) {
+    return dw_fwd(x, w, bias, y, relu_bits, true, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, 1, stream);
+}
+
+// The data gradient masked by nothing, by relu_src (bf16, may be dx) or by relu_bits (u8 [B*H*W][C/8], never dx).
+static int dw_bwd_data(const void* dy, const void* w, const void* relu_src, const void* relu_bits, bool want_bits, void* dx, int B, int H,
+                       int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream) {
+    if (!dy || !w || !dx || (want_bits && !relu_bits)) return SSD_ERR_VALUE;
     const int rc = dw_geometry(B, H, W, C, stride, pad_t, pad_l, Ho, Wo);
     if (rc != SSD_OK) return rc;
     const long long dxbytes = (long long)B * H * W * C * 2;
     if (overlaps(dx, dxbytes, dy, (long long)B * Ho * Wo * C * 2) || overlaps(dx, dxbytes, w, 9ll * C * 2)) return SSD_ERR_VALUE;
     if (relu_src && relu_src != dx && overlaps(dx, dxbytes, relu_src, dxbytes)) return SSD_ERR_VALUE;
+    if (want_bits && overlaps(dx, dxbytes, relu_bits, dxbytes / 16)) return SSD_ERR_VALUE;
     const DwGeom g = dw_geom(B, H, W, C, pad_t, pad_l, Ho, Wo, W, H + pad_t);
     const dim3 grid((unsigned)((g.total + DW_NT - 1) / DW_NT));
     const bool extra = accumulate || relu_src;
     auto kern = stride == 1 ? (extra ? k_dwconv3x3_dgrad<1, true> : k_dwconv3x3_dgrad<1, false>)
                             : (extra ? k_dwconv3x3_dgrad<2, true> : k_dwconv3x3_dgrad<2, false>);
+    if (want_bits)
+        kern = stride == 1 ? (accumulate ? k_dwconv3x3_dgrad<1, true, true> : k_dwconv3x3_dgrad<1, false, true>)
+                           : (accumulate ? k_dwconv3x3_dgrad<2, true, true> : k_dwconv3x3_dgrad<2, false, true>);
     hipLaunchKernelGGL(kern, grid, dim3(DW_NT), 0, (hipStream_t)stream, static_cast<const bf16_raw*>(dy), static_cast<const bf16_raw*>(w),
-                       static_cast<const bf16_raw*>(relu_src), static_cast<bf16_raw*>(dx), g, accumulate ? 1 : 0);
+                       static_cast<const bf16_raw*>(relu_src), static_cast<const unsigned char*>(relu_bits), static_cast<bf16_raw*>(dx), g,
+                       accumulate ? 1 : 0);
     return ssd_launch_status();
+}
+
+int ssd_dwconv3x3_bwd_data(const void* dy, const void* w, const void* relu_src, void* dx, int B, int H, int W, int C, int stride,
+                           int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream) {
+    return dw_bwd_data(dy, w, relu_src, nullptr, false, dx, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, accumulate, stream);
+}
+
+int ssd_dwconv3x3_bwd_data_bits(const void* dy, const void* w, const void* relu_bits, void* dx, int B, int H, int W, int C, int stride,
+                                int pad_t, int pad_l, int Ho, int Wo, int accumulate, void* stream) {
+    return dw_bwd_data(dy, w, nullptr, relu_bits, true, dx, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, accumulate, stream);
 }
 
 size_t ssd_dwconv3x3_bwd_weight_workspace_bytes(int B, int H, int W, int C, int stride, int Ho, int Wo) {

@@ -89,6 +89,31 @@ VGG16_SSD300_TRUNK = SSD300_TRUNK[:10] + [
 VGG16_SSD300_NUM_PRIORS = (4, 6, 6, 6, 4, 4)
 
 
+def _separable(c, cout, stride, feature=False):
+    """A MobileNet block: depthwise 3x3 (kind "dwconv": kernel [3][3][C], bias [C], ReLU) and the 1x1 convolution behind it."""
+    return [("dwconv", c, c, 3, stride, "same", False), ("conv", c, cout, 1, 1, "same", feature)]
+
+
+# MobileNet-v1 SSD300 (Howard et al. 2017, table 1, at width 1; no reference counterpart): the batch normalisations folded into
+# the biases, plain ReLU, Keras SAME padding.  Feature maps: the last 19x19 block (node 22, 512 channels), the last 10x10 block
+# (node 26, 1024 channels) and four extras pairs in "same" mode: grids 19, 10, 5, 3, 2, 1 and 4, 6, 6, 6, 4, 4 default boxes per
+# cell = 2268 anchors.  The last extras pair is 128 / 256 wide (Caffe MobileNet-SSD: 64 / 128): the chain kernel and the sparse
+# heads take multiples of 128.  The heads are the engine's ordinary 3x3 ones (SSDLite's separable heads: not planned).
+MOBILENET_V1_SSD300_TRUNK = (
+    [("conv", 8, 32, 3, 2, "same", False)]           # 300 -> 150 (Cin 3 padded to 8)
+    + _separable(32, 64, 1)                          # 150
+    + _separable(64, 128, 2) + _separable(128, 128, 1)       # 75
+    + _separable(128, 256, 2) + _separable(256, 256, 1)      # 38
+    + _separable(256, 512, 2) + 4 * _separable(512, 512, 1) + _separable(512, 512, 1, True)     # 19; node 22 -> feature map 0
+    + _separable(512, 1024, 2) + _separable(1024, 1024, 1, True)                                # 10; node 26 -> feature map 1
+    + [("conv", 1024, 256, 1, 1, "same", False), ("conv", 256, 512, 3, 2, "same", True),        # -> feature map 2 (5x5x512)
+       ("conv", 512, 128, 1, 1, "same", False), ("conv", 128, 256, 3, 2, "same", True),         # -> feature map 3 (3x3x256)
+       ("conv", 256, 128, 1, 1, "same", False), ("conv", 128, 256, 3, 2, "same", True),         # -> feature map 4 (2x2x256)
+       ("conv", 256, 128, 1, 1, "same", False), ("conv", 128, 256, 3, 2, "same", True)])        # -> feature map 5 (1x1x256)
+MOBILENET_V1_SSD300_NUM_PRIORS = (4, 6, 6, 6, 4, 4)
+RELU_KINDS = ("conv", "dwconv")                  # node kinds with a ReLU of their own: it masks the data gradient of the node behind
+
+
 def mxfp8_eligible(nd):
     """Whether the block-scaled fp8 kernels serve node `nd` (ops.conv2d_fwd_mxfp8; a planned node or a graph node of
     resnet_engine): a convolution whose input channels are whole MX k-steps (Cin % 128 == 0) and whose output channels are
@@ -434,6 +459,11 @@ class _BackwardPass:
             written[i] = True
             return
         wt, bt = e.conv_params[i]
+        if nd["kind"] == "dwconv":
+            self.on_side(lambda ws: self.dw_wgrad(i, ws), [wt.index, bt.index], grouped=True)
+            self.dw_dgrad(i)
+            self.opt_bucket(i)
+            return
         if i == 0 and self.first_fused:                    # its weight gradient came out of the second layer's data-gradient kernel
             self.on_side(lambda ws: None, [wt.index, bt.index], grouped=True)
         elif i not in self.batched_w:                      # (else its weight gradient left with the batched launch)
@@ -561,6 +591,30 @@ class _BackwardPass:
             e1.record()
             probe["events"].append((i, e0, e1))
 
+    def dw_wgrad(self, i, ws):
+        e, nd = self.eng, self.eng.nodes[i]
+        wt, bt = e.conv_params[i]
+        ops.dwconv3x3_bwd_weight(self.acts[i], self.gacts[i + 1], nd["stride"], nd["pt"], nd["pl"], dw=e.view(wt, e.grad),
+                                 dbias=e.view(bt, e.grad), ws=ws)
+
+    def dw_dgrad(self, i):
+        """Data gradient of depthwise node i on the main stream, masked by the ReLU of the node in front of it: from that
+        node's sign bytes where this step's forward pass wrote them (and the engine takes them: dw_dgrad_bits), else from the
+        bf16 map.  It reads the bf16 parameters themselves (no transposed copy): the bucket's optimizer, which rewrites them, is
+        enqueued behind this launch like behind every other data gradient (opt_bucket)."""
+        e, nd = self.eng, self.eng.nodes[i]
+        assert e.nodes[i - 1]["kind"] in RELU_KINDS, "a depthwise node behind a pooling: no unmasked launch planned"
+        self.wait_for_head(i)
+        w = e.view(e.conv_params[i][0], e.param_bf16)
+        x = self.acts[i]
+        if e.relu_bits is not None and e.dw_dgrad_bits and i in e.bits_valid:
+            ops.dwconv3x3_bwd_data_bits(self.gacts[i + 1], w, self.c["rbits"][i], x.shape, nd["stride"], nd["pt"], nd["pl"],
+                                        accumulate=self.written[i], out=self.gacts[i])
+        else:
+            ops.dwconv3x3_bwd_data(self.gacts[i + 1], w, x, x.shape, nd["stride"], nd["pt"], nd["pl"], accumulate=self.written[i],
+                                   out=self.gacts[i])
+        self.written[i] = True
+
     def dgrad(self, i):
         """Data gradient of convolution i (> 0, not in the chain) on the main stream."""
         e, c, nd, written = self.eng, self.c, self.eng.nodes[i], self.written
@@ -586,10 +640,10 @@ class _BackwardPass:
                 self.unpooled.add(i - 1)
         if nd["dilation"] != 1:
             # fc6 behind pool5: the pooling's codes carry the ReLU of the layer in front of it, nothing to mask here
-            assert e.nodes[i - 1]["kind"] != "conv", "a dilated convolution behind a convolution: no masked launch planned"
+            assert e.nodes[i - 1]["kind"] not in RELU_KINDS, "a dilated convolution behind a convolution: no masked launch planned"
             ops.conv2d_atrous_bwd_data(g_out, e.w_t[i], None, self.acts[i].shape, nd["dilation"], accumulate=written[i],
                                        out=self.gacts[i])
-        elif not fused and e.nodes[i - 1]["kind"] == "conv": # (its ReLU masks the gradient)
+        elif not fused and e.nodes[i - 1]["kind"] in RELU_KINDS:    # (its ReLU masks the gradient)
             self.masked_dgrad("conv%d" % i, g_out, e.w_t[i], i, nd["stride"], nd["pt"], nd["pl"], written[i], e._ws)
         elif not fused:
             ops.conv2d_bwd_data(g_out, e.w_t[i], None, self.acts[i].shape, nd["stride"], nd["pt"], nd["pl"],
@@ -660,6 +714,10 @@ class SSDEngine:
         # key (str) -> that kernel reads them
         self.relu_bits = {} if os.environ.get("SSD_RELU_BITS", "1") == "1" else None
         self.bits_valid = set()
+        # a depthwise node's data gradient takes its mask from the sign bytes (ops.dwconv3x3_bwd_data_bits) rather than from
+        # the bf16 map: over the trunk's twelve masked depthwise data gradients at batch 64 it measured 336 us against 583 us
+        # (DESIGN.md section 9); both paths give the same bits
+        self.dw_dgrad_bits = os.environ.get("SSD_DW_DGRAD_BITS", "1") == "1"
         # second layer's data gradient and first layer's weight gradient in one kernel (the gradient w.r.t. the first layer's
         # output has no other consumer and is never stored); False after a refusal
         self.fuse_first = os.environ.get("SSD_FUSE_FIRST", "1") == "1"
@@ -698,7 +756,10 @@ class SSDEngine:
         self.fm = []                          # (node index, h, c)
         for kind, cin, cout, k, stride, mode, feat, *more in self.trunk:
             dilation = more[0] if more else 1                # (an optional eighth element: only the VGG-16 trunk's fc6 has one)
-            if kind not in ("conv", "pool", "pool3s1") or (dilation != 1 and (kind, k, stride, mode) != ("conv", 3, 1, "same")):
+            if kind == "dwconv" and (cin != cout or cin % 8 or (k, mode) != (3, "same") or stride not in (1, 2) or more or not self.nodes):
+                raise ValueError("trunk node %d: a depthwise node is (\"dwconv\", C, C, 3, 1 | 2, \"same\", feature) with C a multiple "
+                                 "of 8, behind another node; got %r" % (len(self.nodes), (kind, cin, cout, k, stride, mode, feat) + tuple(more)))
+            if kind not in ("conv", "dwconv", "pool", "pool3s1") or (dilation != 1 and (kind, k, stride, mode) != ("conv", 3, 1, "same")):
                 raise ValueError("trunk node %d: no launch for %r" % (len(self.nodes), (kind, cin, cout, k, stride, mode, feat) + tuple(more)))
             if mode == "same":
                 ho, pt = ops.same_pad(s, dilation * (k - 1) + 1, stride)
@@ -718,6 +779,14 @@ class SSDEngine:
                and self.nodes[j - 1]["cin"] % 128 == 0 and self.nodes[j - 1]["cout"] % 128 == 0
                and self.nodes[j - 1]["dilation"] == 1):
             j -= 1
+        # ... and, in a trunk with depthwise nodes, whose images fit the kernel's LDS in both directions (ops.chain_lds_bytes:
+        # ssd_conv_chain's own arithmetic): a run that does not fit loses its first layers until it does, so what is planned
+        # here is what launches (MobileNet: 10x10x1024 in front of the extras is 206 KB; the chain starts one layer later).
+        # The older trunks keep the rule above and learn a refusal at the first launch (self.chain empties): only a reduced
+        # geometry of theirs is refused (the VGG-16 trunk at 164), and their plans and launches stay what they were
+        self.has_dw = any(nd["kind"] == "dwconv" for nd in self.nodes)
+        while self.has_dw and len(self.nodes) - j >= 2 and not self._chain_fits(j):
+            j += 1
         self.chain_start = j if len(self.nodes) - j >= 2 else None
         if any(c % 128 for _, _, c in self.fm) or len(self.fm) > _lib.SSD_MAX_LEVELS:
             self.sparse_heads = False
@@ -732,8 +801,19 @@ class SSDEngine:
                            and self.nodes[1]["pt"] == self.nodes[1]["pl"] == 1)
         # node kinds the block-scaled fp8 forward plans only where the engine was built with fp8_inference (the VGG-16 SSD300's
         # pool5 and fc6)
-        self.bf16_only = (any(nd["kind"] == "pool3s1" or nd["dilation"] != 1 for nd in self.nodes)
-                          and not getattr(self, "fp8_inference", False))
+        # ...; a depthwise node has no fp8 form at all
+        if self.has_dw and getattr(self, "fp8_inference", False):
+            raise ValueError("fp8_inference=True: a trunk with depthwise (\"dwconv\") nodes runs in bf16 only")
+        self.bf16_only = self.has_dw or (any(nd["kind"] == "pool3s1" or nd["dilation"] != 1 for nd in self.nodes)
+                                         and not getattr(self, "fp8_inference", False))
+
+    def _chain_fits(self, j):
+        """Whether nodes j .. end as ONE ssd_conv_chain launch stay within its LDS, forward (images: the input of node j, then
+        every output but the last) and data gradient (the last node's output gradient first, the walk reversed)."""
+        nds = self.nodes[j:]
+        fwd = [(nd["hin"] ** 2, nd["cin"], nd["hout"] ** 2, nd["cout"]) for nd in nds]
+        bwd = [(nd["hout"] ** 2, nd["cout"], nd["hin"] ** 2, nd["cin"]) for nd in reversed(nds)]
+        return max(ops.chain_lds_bytes(fwd), ops.chain_lds_bytes(bwd)) <= ops.CHAIN_LDS_MAX
 
     def _plan_params(self):
         self.tensors = []
@@ -756,6 +836,8 @@ class SSDEngine:
 
         self.conv_params = {}
         for i, nd in enumerate(self.nodes):
+            if nd["kind"] == "dwconv":                      # [3][3][C]: what the kernels read, forward and data gradient
+                self.conv_params[i] = (add("dwconv%d/kernel" % i, (3, 3, nd["cout"])), add("dwconv%d/bias" % i, (nd["cout"],)))
             if nd["kind"] != "conv":
                 continue
             self.conv_params[i] = (add("conv%d/kernel" % i, (nd["cout"], nd["k"], nd["k"], nd["cin"])),
@@ -832,6 +914,12 @@ class SSDEngine:
         host = np.zeros(self.n_flat, np.float32)
         for t in self.tensors:
             if not t.name.endswith("kernel"):
+                continue
+            if t.name.startswith("dwconv"):
+                # He-uniform over the true fan-in 9 (variance 2 / 9): thirteen depthwise layers without a normalisation keep
+                # their maps alive; Keras's glorot over 9C + 9 shrinks every map by ~1 / C and the network dies out
+                lim = math.sqrt(6.0 / 9.0)
+                host[t.offset:t.offset + t.numel] = rng.uniform(-lim, lim, t.shape).astype(np.float32).reshape(-1)
                 continue
             cout, k, _, cin = t.shape
             if t.name.startswith("head"):                       # loc and conf: two separate Keras layers (:155-162)
@@ -929,7 +1017,7 @@ class SSDEngine:
             # ReLU sign bits of every convolution output (one byte per pixel and 8 channels): what the data gradients read
             # instead of the bf16 activation
             rbits = {i + 1: torch.empty((B, nd["hout"], nd["hout"], nd["cout"] // 8), dtype=torch.uint8, device=dev)
-                     for i, nd in enumerate(self.nodes) if nd["kind"] == "conv" and nd["cout"] % 8 == 0}
+                     for i, nd in enumerate(self.nodes) if nd["kind"] in RELU_KINDS and nd["cout"] % 8 == 0}
             hgb = None
             if self.sparse_heads:
                 hgb = ops.HeadGradBuffers(B, [h * h for _, h, _ in self.fm], self.num_priors, self.head_npad, device=dev)
@@ -964,8 +1052,8 @@ class SSDEngine:
         chain and the heads in bf16, on the same streams as the bf16 forward; backward() then raises until a bf16 forward."""
         if precision == "mxfp8":
             if self.bf16_only:
-                raise NotImplementedError("forward(x, 'mxfp8'): the VGG-16 SSD300 trunk (3x3 / stride-1 pooling, dilated fc6) has no "
-                                          "block-scaled fp8 plan; it runs in bf16")
+                raise NotImplementedError("forward(x, 'mxfp8'): this trunk (3x3 / stride-1 pooling and dilated fc6 of the VGG-16 SSD300 "
+                                          "without fp8_inference, or depthwise nodes) has no block-scaled fp8 plan; it runs in bf16")
             return self._forward_vgg_mxfp8(x)
         if precision != "bf16":
             raise ValueError("precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
@@ -1086,6 +1174,15 @@ class SSDEngine:
                         self.bits_valid.add(i + 1)
                 if not done:
                     ops.conv2d_fwd(*args, True, out=acts[i + 1], ws=self._ws)
+        elif nd["kind"] == "dwconv":
+            wt, bt = self.conv_params[i]
+            args = (acts[i], self.view(wt, self.param_bf16), self.view(bt, self.param), nd["stride"], nd["pt"], nd["pl"],
+                    nd["hout"], nd["hout"])
+            if self.relu_bits is not None:                     # (the sign-byte form serves every shape the plain one serves)
+                ops.dwconv3x3_fwd_relubits(*args, c["rbits"][i + 1], out=acts[i + 1])
+                self.bits_valid.add(i + 1)
+            else:
+                ops.dwconv3x3_fwd(*args, True, out=acts[i + 1])
         elif nd["kind"] == "pool3s1":
             ops.maxpool3x3s1_fwd(acts[i], out=acts[i + 1], code=c["pool_code"][i])
         elif i == 0 or self.nodes[i - 1]["kind"] != "conv":

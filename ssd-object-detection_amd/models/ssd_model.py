@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..engine import SSDEngine, VGG16_SSD300_NUM_PRIORS, VGG16_SSD300_TRUNK
+from ..engine import (MOBILENET_V1_SSD300_NUM_PRIORS, MOBILENET_V1_SSD300_TRUNK, SSDEngine, VGG16_SSD300_NUM_PRIORS,
+                      VGG16_SSD300_TRUNK)
 from ..parallel import GradReducer, shard_range
 from .. import optimizers as _opt
 from ..utils.scalar_log import ScalarLog
@@ -98,7 +99,10 @@ class SSDObjectDetectionModel:
 
         network (ops.NetworkSpec.of: None / "ssd300" = the reference's network, as without the argument; "vgg16_ssd300" = the
         SSD paper's VGG-16 SSD300 (engine.VGG16_SSD300_TRUNK: conv4_3 / fc7 feature maps, pool5 3x3 / 1, dilated fc6) on the
-        same engine class and the same step, l2norm as for ssd300 (the paper trains it with l2norm=True); "resnet50_ssd512", a
+        same engine class and the same step, l2norm as for ssd300 (the paper trains it with l2norm=True);
+        "mobilenet_v1_ssd300" = MobileNet-v1 SSD300 (engine.MOBILENET_V1_SSD300_TRUNK: depthwise 3x3 + 1x1 blocks, 2268 default
+        boxes on grids 19 .. 1 with ops.MOBILENET_SSD300_S_REF), same engine class and step, bf16 only: ValueError together with
+        l2norm or fp8_inference; "resnet50_ssd512", a
         dict or a spec): the ResNet-50 SSD512 network (resnet_engine.ResNet50SSDEngine) at a 512 or 256 input, optionally with
         live batch normalisation or an MX-fp8 training forward.  Its step is backward -> clip -> one optimizer launch over the
         flat buffer (the engine has no per-bucket schedule); everything else -- targets, both losses, the three optimizers,
@@ -114,6 +118,8 @@ class SSDObjectDetectionModel:
         self.network = ops.NetworkSpec.of(network, l2norm=l2norm)
         if not isinstance(fp8_inference, bool):
             raise ValueError("fp8_inference must be True or False, not %r" % (fp8_inference,))
+        if fp8_inference and self.network.kind == "mobilenet_v1_ssd300":
+            raise ValueError("fp8_inference together with network kind 'mobilenet_v1_ssd300': its depthwise layers run in bf16 only")
         if fp8_inference and self.network.kind not in ("ssd300", "vgg16_ssd300"):
             raise ValueError("fp8_inference is the switch of the ssd300 / vgg16_ssd300 engines; the %s network's fp8 forward is "
                              "set by its network spec (precision)" % self.network.kind)
@@ -127,15 +133,18 @@ class SSDObjectDetectionModel:
         self.cfg = SSDObjectDetectionModel.Config(classes, log_dir)
         self.device = torch.device(device)
         net = self.network
-        if net.kind in ("ssd300", "vgg16_ssd300"):
-            # one engine class, two trunks: the same step (fused per-bucket optimizer, high-priority main stream), the same
-            # default boxes (grids 38, 19, 10, 5, 3, 1)
-            graph = {}
+        if net.kind in ops.NetworkSpec.ENGINE_KINDS:
+            # one engine class, three trunks: the same step (fused per-bucket optimizer, high-priority main stream); the two
+            # VGG trunks share the default boxes (grids 38, 19, 10, 5, 3, 1), MobileNet has its own (19, 10, 5, 3, 2, 1)
+            graph, boxes = {}, {}
             if net.kind == "vgg16_ssd300":
                 graph = dict(trunk=VGG16_SSD300_TRUNK, num_priors=VGG16_SSD300_NUM_PRIORS)
+            elif net.kind == "mobilenet_v1_ssd300":
+                graph = dict(trunk=MOBILENET_V1_SSD300_TRUNK, num_priors=MOBILENET_V1_SSD300_NUM_PRIORS)
+                boxes = dict(s_ref=ops.MOBILENET_SSD300_S_REF)
             self._engine = SSDEngine(classes=self.cfg.classes, in_size=self.cfg.input_shape[0], device=device, seed=seed,
                                      l2norm=l2norm, fp8_inference=fp8_inference, **graph)
-            self._pset = ops.build_priors(grids=self._engine.grids, device=device)
+            self._pset = ops.build_priors(grids=self._engine.grids, device=device, **boxes)
             self._forward_train = self._engine.forward
             self._backward_args = {}
         else:

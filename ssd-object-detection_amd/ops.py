@@ -16,6 +16,9 @@ SSD300_RATIOS = ((2,), (2, 3), (2, 3), (2, 3), (2,), (2,))
 # are pixels of a 512 input: at input S they are S_REF * S / 512 (ssd512_s_ref)
 SSD512_S_REF = (20, 51, 133, 215, 297, 379, 461, 543)
 SSD512_RATIOS = ((2,), (2, 3), (2, 3), (2, 3), (2, 3), (2,), (2,))
+# MobileNet-v1 SSD300 (engine.MOBILENET_V1_SSD300_TRUNK; grids 19, 10, 5, 3, 2, 1 = 2268 anchors): scales 0.2 .. 0.95 of 300 in equal
+# steps and one beyond, the MobileNet-SSD convention; the ratios are SSD300_RATIOS
+MOBILENET_SSD300_S_REF = (60, 105, 150, 195, 240, 285, 330)
 
 
 def ssd512_s_ref(in_size):
@@ -461,17 +464,20 @@ class BatchNormSpec:
 class NetworkSpec:
     """Which network SSDObjectDetectionModel builds and how it trains it.
       kind             "ssd300": the reference's 300 x 300 network (SSDEngine), the default; "vgg16_ssd300": the SSD paper's
-                       VGG-16 SSD300 (SSDEngine on engine.VGG16_SSD300_TRUNK; bf16, no batchnorm); "resnet50_ssd512": the
-                       ResNet-50 SSD512 network (ResNet50SSDEngine)
-      in_size          300 for ssd300 and vgg16_ssd300; 512 (default) or 256 for the ResNet
+                       VGG-16 SSD300 (SSDEngine on engine.VGG16_SSD300_TRUNK; bf16, no batchnorm); "mobilenet_v1_ssd300":
+                       MobileNet-v1 SSD300 (SSDEngine on engine.MOBILENET_V1_SSD300_TRUNK: depthwise 3x3 + 1x1 blocks, 2268
+                       anchors; bf16, no batchnorm, no l2norm, no fp8); "resnet50_ssd512": the ResNet-50 SSD512 network
+                       (ResNet50SSDEngine)
+      in_size          300 for ssd300, vgg16_ssd300 and mobilenet_v1_ssd300; 512 (default) or 256 for the ResNet
       batchnorm        ResNet only: anything BatchNormSpec.of takes (None / False: the folded network)
       precision        of the TRAINING forward: "bf16" or "mxfp8" (ResNet only; not together with batchnorm, whose engine has no
                        fp8 plan)
       dgrad_precision  of the data gradients behind an mxfp8 training forward: None (fp8 where planned), "bf16" or "mxfp8"
     """
-    KINDS = ("ssd300", "resnet50_ssd512", "vgg16_ssd300")
+    KINDS = ("ssd300", "resnet50_ssd512", "vgg16_ssd300", "mobilenet_v1_ssd300")
     FIELDS = ("kind", "in_size", "batchnorm", "precision", "dgrad_precision")
-    IN_SIZES = {"ssd300": (300,), "resnet50_ssd512": (512, 256), "vgg16_ssd300": (300,)}     # the first one is the default
+    IN_SIZES = {"ssd300": (300,), "resnet50_ssd512": (512, 256), "vgg16_ssd300": (300,), "mobilenet_v1_ssd300": (300,)}   # the first one is the default
+    ENGINE_KINDS = ("ssd300", "vgg16_ssd300", "mobilenet_v1_ssd300")      # the networks SSDEngine runs: bf16 training, no batchnorm
     L2NORM_KINDS = ("ssd300", "vgg16_ssd300")                              # the networks SSDEngine runs: l2norm is its option
 
     def __init__(self, kind="ssd300", in_size=None, batchnorm=None, precision="bf16", dgrad_precision=None):
@@ -487,7 +493,7 @@ class NetworkSpec:
             raise ValueError("network precision must be 'bf16' or 'mxfp8', not %r" % (precision,))
         if dgrad_precision is not None and (not isinstance(dgrad_precision, str) or dgrad_precision not in ("bf16", "mxfp8")):
             raise ValueError("network dgrad_precision must be None, 'bf16' or 'mxfp8', not %r" % (dgrad_precision,))
-        if kind in ("ssd300", "vgg16_ssd300"):
+        if kind in self.ENGINE_KINDS:
             if batchnorm is not None:
                 raise ValueError("network batchnorm: the %s network has no batch normalisation" % kind)
             if precision != "bf16" or dgrad_precision is not None:
@@ -1260,6 +1266,22 @@ def conv_chain(in0, layers):
         Hi, Wi, Kc = out.shape[1], out.shape[2], s["N"]
     rc = L.ssd_conv_chain(_ptr(in0), arr, len(layers), B, _stream())
     _lib.check(rc, unsupported="ssd_conv_chain does not serve these layers")
+
+
+CHAIN_LDS_MAX = 160 * 1024                   # csrc/chain.hip: CH_LDS_MAX
+
+
+def chain_lds_bytes(layers):
+    """LDS bytes of one ssd_conv_chain launch, the host code's own arithmetic: layers = [(input pixels, input channels, output
+    pixels, output channels)] in launch order.  An image of P pixels and C channels takes P (2 C + 16) bytes; image l (0: the
+    chain's input, l: the output of layer l - 1; the last output goes to memory only) lives in region l & 1; both regions round
+    up to 16 bytes, and one zero row of the widest input follows them.  The launch is refused above CHAIN_LDS_MAX."""
+    region = [0, 0]
+    for l, (pin, cin, pout, cout) in enumerate(layers):
+        region[l & 1] = max(region[l & 1], pin * (2 * cin + 16))
+        if l + 1 < len(layers):
+            region[(l + 1) & 1] = max(region[(l + 1) & 1], pout * (2 * cout + 16))
+    return sum((r + 15) // 16 * 16 for r in region) + max(2 * cin for _, cin, _, _ in layers)
 
 
 def conv2d_fwd_relubits(x, w, bias, stride, pad_t, pad_l, Ho, Wo, bits, out=None, ws=None):
@@ -2085,7 +2107,7 @@ def maxpool3x3s1_bwd(code, dy, x_shape, out=None):
     return out
 
 
-# ---- depthwise 3x3 convolution (MobileNet-SSD / SSDLite's other half; no network launches it yet) ------------------------------
+# ---- depthwise 3x3 convolution (MobileNet-SSD / SSDLite's other half: engine.MOBILENET_V1_SSD300_TRUNK's "dwconv" nodes) ---------
 _DW_RANGE = "depthwise 3x3 convolution: C must be a multiple of 8 and every tensor below 2^31 bytes; got %s"
 
 
@@ -2121,6 +2143,41 @@ def dwconv3x3_bwd_data(dy, w, relu_src, x_shape, stride, pad_t, pad_l, accumulat
         _caller_buffer("relu_src", relu_src, x_shape, torch.bfloat16)
     _lib.check(L.ssd_dwconv3x3_bwd_data(_ptr(dy), _ptr(w), _ptr(relu_src), _ptr(out), B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
                                         1 if accumulate else 0, _stream()),
+               unsupported=_DW_RANGE % ((B, H, W, C, stride),))
+    return out
+
+
+def dwconv3x3_fwd_relubits(x, w, bias, stride, pad_t, pad_l, Ho, Wo, bits, out=None):
+    """dwconv3x3_fwd with ReLU that also writes the sign bytes of its output (uint8 [B,Ho,Wo,C/8], conv2d_fwd_relubits's layout)."""
+    L = _lib.lib()
+    _bf(x); _bf(w)
+    B, H, W, C = x.shape
+    assert w.shape == (3, 3, C)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
+    _caller_buffer("out", out, (B, Ho, Wo, C), torch.bfloat16)
+    _caller_buffer("bits", bits, (B, Ho, Wo, C // 8), torch.uint8)
+    _lib.check(L.ssd_dwconv3x3_fwd_relubits(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), _ptr(bits), B, H, W, C, stride, pad_t, pad_l,
+                                            Ho, Wo, _stream()),
+               unsupported=_DW_RANGE % ((B, H, W, C, stride),))
+    return out
+
+
+def dwconv3x3_bwd_data_bits(dy, w, bits, x_shape, stride, pad_t, pad_l, accumulate=False, out=None):
+    """dwconv3x3_bwd_data with the ReLU mask given as the sign bytes of the layer in front (uint8 [B,H,W,C/8]): same result, one
+    mask byte per 16-byte group instead of sixteen."""
+    L = _lib.lib()
+    _bf(dy); _bf(w)
+    B, H, W, C = x_shape
+    _, Ho, Wo, _ = dy.shape
+    assert dy.shape == (B, Ho, Wo, C) and w.shape == (3, 3, C)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dy.device)
+    _caller_buffer("out", out, x_shape, torch.bfloat16)
+    _caller_buffer("bits", bits, (B, H, W, C // 8), torch.uint8)
+    _lib.check(L.ssd_dwconv3x3_bwd_data_bits(_ptr(dy), _ptr(w), _ptr(bits), _ptr(out), B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
+                                             1 if accumulate else 0, _stream()),
                unsupported=_DW_RANGE % ((B, H, W, C, stride),))
     return out
 

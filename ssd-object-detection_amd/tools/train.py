@@ -188,6 +188,7 @@ def network_from_config(config):
     """`model: network: {kind, in_size, batchnorm: {enable, momentum, eps}, precision, dgrad_precision}` (no reference
     counterpart) -> ops.NetworkSpec, or None when the key is absent: the default run builds the reference's 300 x 300 network.
     kind "vgg16_ssd300" (the SSD paper's network) goes together with `model: l2norm:`, as "ssd300" does; the ResNet refuses it.
+    kind "mobilenet_v1_ssd300" (MobileNet-v1 SSD300: in_size 300, bf16, no batchnorm) refuses `l2norm` and `fp8_inference`.
     `batchnorm` absent, null or with enable false: no batch normalisation.  ValueError for an unknown key, a section that is
     no mapping or bad values."""
     section = (config.get("model") or {}).get("network")

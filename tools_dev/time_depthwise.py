@@ -11,8 +11,15 @@ rotate through operand sets of more than 256 MiB together.  Device events around
 per-call times, min..max beside it.  Every shape runs in a child process of its own under a time limit; the first failure ends
 the run.
 
-usage: python tools_dev/time_depthwise.py [--batch 64] [--calls 20] [--repeats 7] [--limit 120]"""
+--forms: the sign-byte forms instead.  Per shape, alternated in one process: ssd_dwconv3x3_fwd against ssd_dwconv3x3_fwd_relubits, and
+the data gradient plain, masked from relu_src (6 bytes per element) and masked from sign bytes (ssd_dwconv3x3_bwd_data_bits: 4.125).
+Then the sums over the trunk's masked depthwise data gradients: the twelve behind a 1x1 layer (and, beside them, all thirteen: the
+first is masked by the stem), per form, with the summed min and max -- the sign-byte form is the engine's default only if it is
+faster in the sum of the twelve by more than the relu_src form's own min..max.
+
+usage: python tools_dev/time_depthwise.py [--forms] [--batch 64] [--calls 20] [--repeats 7] [--limit 120]"""
 import argparse
+import json
 import os
 import statistics
 import subprocess
@@ -25,6 +32,8 @@ sys.path.insert(0, ROOT)
 SHAPES = [(150, 150, 32, 1), (150, 150, 64, 2), (75, 75, 128, 1), (75, 75, 128, 2), (38, 38, 256, 1), (38, 38, 256, 2),
           (19, 19, 512, 1), (19, 19, 512, 2), (10, 10, 1024, 1)]
 YARDSTICK = (19, 19, 512, 1)
+# how often the trunk runs each shape's data gradient behind a 1x1 layer (the first depthwise layer sits behind the stem)
+BEHIND_1X1 = [0, 1, 1, 1, 1, 1, 5, 1, 1]
 CACHE = 256 << 20
 
 ap = argparse.ArgumentParser()
@@ -33,7 +42,29 @@ ap.add_argument("--calls", type=int, default=20)
 ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--limit", type=int, default=120, help="seconds per child process")
 ap.add_argument("--only", type=int, default=None, help="(child) index into SHAPES, or -1 for the yardstick comparison")
+ap.add_argument("--forms", action="store_true", help="the sign-byte forms against their siblings, and the trunk's sums")
 args = ap.parse_args()
+
+if args.only is None and args.forms:
+    rows = []
+    for i in range(len(SHAPES)):
+        cmd = [sys.executable, os.path.abspath(__file__), "--forms", "--batch", str(args.batch), "--calls", str(args.calls), "--repeats",
+               str(args.repeats), "--only", str(i)]
+        done = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(done.stdout)
+        sys.stdout.flush()
+        if done.returncode != 0:
+            sys.exit("step %d ended with status %d: stopping" % (i, done.returncode))
+        rows.append(json.loads([ln for ln in done.stdout.splitlines() if ln.startswith("FORMS ")][-1][6:]))
+    for title, mult in (("the twelve behind a 1x1 layer", BEHIND_1X1), ("all thirteen", [m + (i == 0) for i, m in enumerate(BEHIND_1X1)])):
+        print("masked depthwise data gradients of one step, %s (us: median, summed min..max):" % title)
+        tot = {k: [sum(m * r[k][j] for m, r in zip(mult, rows)) for j in range(3)] for k in ("dgrad", "dgrad + relu_src", "dgrad + bits")}
+        for k, (med, lo, hi) in tot.items():
+            print("  %-20s %8.1f   %.1f..%.1f" % (k, med, lo, hi))
+        src, bits = tot["dgrad + relu_src"], tot["dgrad + bits"]
+        print("  relu_src - bits = %.1f us; relu_src's own min..max = %.1f us -> %s" % (
+            src[0] - bits[0], src[2] - src[1], "sign bytes" if src[0] - bits[0] > src[2] - src[1] else "relu_src"), flush=True)
+    sys.exit(0)
 
 if args.only is None:
     for i in list(range(len(SHAPES))) + [-1]:
@@ -101,7 +132,29 @@ def measure(variants):
     return us
 
 
-if args.only >= 0:
+if args.only >= 0 and args.forms:
+    H, W, C, stride = SHAPES[args.only]
+    sets, (Ho, Wo, pt, pl), nx, ny = operand_sets(H, W, C, stride, False)
+    for s in sets:                                                  # the map in front (about half of it positive) and its sign bytes
+        s["src"] = torch.randn((B, H, W, C), device="cuda").relu().to(BF)
+        s["xbits"] = ((s["src"] > 0).view(B, H, W, C // 8, 8).int() << torch.arange(8, device="cuda", dtype=torch.int32)).sum(-1).to(torch.uint8)
+        s["ybits"] = torch.empty((B, Ho, Wo, C // 8), dtype=torch.uint8, device="cuda")
+    S = lambda i: sets[i % len(sets)]                               # noqa: E731
+    us = measure({
+        "fwd": lambda i: ops.dwconv3x3_fwd(S(i)["x"], S(i)["w"], S(i)["bias"], stride, pt, pl, Ho, Wo, True, out=S(i)["y"]),
+        "fwd_relubits": lambda i: ops.dwconv3x3_fwd_relubits(S(i)["x"], S(i)["w"], S(i)["bias"], stride, pt, pl, Ho, Wo, S(i)["ybits"],
+                                                             out=S(i)["y"]),
+        "dgrad": lambda i: ops.dwconv3x3_bwd_data(S(i)["dy"], S(i)["w"], None, (B, H, W, C), stride, pt, pl, out=S(i)["dx"]),
+        "dgrad + relu_src": lambda i: ops.dwconv3x3_bwd_data(S(i)["dy"], S(i)["w"], S(i)["src"], (B, H, W, C), stride, pt, pl, out=S(i)["dx"]),
+        "dgrad + bits": lambda i: ops.dwconv3x3_bwd_data_bits(S(i)["dy"], S(i)["w"], S(i)["xbits"], (B, H, W, C), stride, pt, pl, out=S(i)["dx"]),
+    })
+    print("(%d, %d, %d, %d) stride %d -> %d x %d; %d operand sets" % (B, H, W, C, stride, Ho, Wo, len(sets)), flush=True)
+    nbytes = {"fwd": 2 * (nx + ny), "fwd_relubits": 2 * (nx + ny) + ny // 8, "dgrad": 2 * (nx + ny), "dgrad + relu_src": 4 * nx + 2 * ny,
+              "dgrad + bits": 2 * (nx + ny) + nx // 8}
+    for name in us:
+        report("dwconv3x3 " + name, us[name], nbytes[name])
+    print("FORMS " + json.dumps({k: [statistics.median(v), min(v), max(v)] for k, v in us.items()}), flush=True)
+elif args.only >= 0:
     H, W, C, stride = SHAPES[args.only]
     sets, (Ho, Wo, pt, pl), nx, ny = operand_sets(H, W, C, stride, False)
     S = lambda i: sets[i % len(sets)]                               # noqa: E731
